@@ -16,12 +16,19 @@ pinned), synthetic randomized-reset batches, random-init policy.  `--workload en
 `python bench.py --gpus N` launches the N ranks itself (torch.distributed.run, one process per GPU, RCCL) when it is not
 already running under a launcher (WORLD_SIZE unset) and relays rank 0's line; under a launcher it is a rank.
 
-Prints ONE JSON line (rank 0).  The timed region of exactly --steps steps is repeated (`repeats`) and `value` is the
-MEDIAN repeat (min / max alongside): one 0.7 ms launch is not a measurement.  `roofline` prices the dominant kernel
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times exactly --steps steps once (`--repeats R`: R such
+windows, `value` the MEDIAN one) and prints the line: `value` env-steps/s and `ms_per_step` over that window.
+`--full` adds everything else, each taking runs of its own: the timed region is repeated (`repeats`, as many as fit
+~1.5 s unless --repeats is given; one 0.7 ms launch is not a measurement); `roofline` prices the dominant kernel
 (so100_rollout_fused in the default mode) with the algorithmic 452 B/env-step of SURVEY.md section 8(d), its duration
 measured live with HIP events around every launch of the timed repeats; `cpu_baseline` times the CPU oracle (a port,
 not the reference) on the host cores; `sb3_vecenv_path` is the numpy-in / numpy-out `So100VecEnv.step` round trip that an
 unmodified SB3 learner drives (ref: main.py:57-63, 234-238), same batch, same physics flags, same run.
+
+`--dump-outputs DIR` writes what the last step of the first timed window produced (warmup + steps steps after the seeded
+reset, so the same arguments give the same inputs in every run and mode) as float32 DIR/<name>.npy: the rollout-buffer row
+(obs, action, reward, done, value, log_prob) and the observation the next step starts from (next_obs); rank 0's shard,
+a fixed seeded sample of the envs when that would exceed 64 MB.
 """
 import argparse
 import json
@@ -29,6 +36,7 @@ import os
 import sys
 import time
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -237,15 +245,20 @@ def main():
     ap.add_argument("--warmup", type=int, default=128)
     ap.add_argument("--envs", type=int, default=4096, help="envs per GPU")
     ap.add_argument("--workload", default="env01_free", choices=list(WORKLOADS))
+    ap.add_argument("--full", action="store_true", help="also the supplementary measurements: repeats of the timed region, roofline, "
+                    "sb3_vecenv_path, cpu_baseline, the 1M-env kernel (the --no-* options below skip single ones)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-large-batch", action="store_true", help="skip the supplementary 1M-env kernel measurement")
     ap.add_argument("--no-sb3-path", action="store_true", help="skip the So100VecEnv numpy round-trip measurement")
-    ap.add_argument("--repeats", type=int, default=0, help="repeats of the timed region (0 = as many as fit ~1.5 s, 3..40)")
+    ap.add_argument("--repeats", type=int, default=0, help="repeats of the timed region (0 = one, with --full as many as fit ~1.5 s, 3..40)")
     ap.add_argument("--policy", default="persistent", choices=["persistent", "fused", "torch"])
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs as DIR/<name>.npy (float32)")
     ap.add_argument("--worker", default=None, help=argparse.SUPPRESS)      # script the launcher starts (tests use a stub)
     args = ap.parse_args()
     if args.gpus < 1:
         sys.exit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # not under a launcher: start the ranks ourselves, before anything here initialises the GPU
         argv = [a for a in sys.argv[1:]]
@@ -313,7 +326,9 @@ def main():
         if len(evpool) < 2:                                  # (stepwise modes record a pair per step: refill)
             evpool.extend(torch.cuda.Event(enable_timing=True) for _ in range(64))
         return evpool.pop(), evpool.pop()
-    evpool.extend(torch.cuda.Event(enable_timing=True) for _ in range(2*(42*((args.steps + ROLLOUT_T - 1)//ROLLOUT_T) + 4)))
+    if args.full:
+        evpool.extend(torch.cuda.Event(enable_timing=True) for _ in range(2*(42*((args.steps + ROLLOUT_T - 1)//ROLLOUT_T) + 4)))
+    last_row = [None]                                        # rollout-buffer row of the latest step (--dump-outputs)
 
     def run(nsteps, record=False):
         """exactly nsteps vectorised env steps, in rollout chunks of at most T steps"""
@@ -324,6 +339,7 @@ def main():
             if pending[ci] is not None:                      # buffer about to be overwritten: its gather must be done
                 pending[ci].wait(); pending[ci] = None
             chunk = chunks[ci][:Tc]
+            last_row[0] = chunk[Tc - 1]
             if args.policy == "persistent":
                 if record:                                   # events on the launch stream (torch's current stream = where the C ABI enqueues)
                     ea, eb = ev_pair(); ea.record()
@@ -380,51 +396,67 @@ def main():
 
     run(args.warmup)
     first, first_own = timed(False)
-    # repeats of the timed region: as many as fit ~1.5 s (3..40) unless given; every rank must agree on the count
-    reps = args.repeats if args.repeats > 0 else max(3, min(40, int(1.5 / max(first, 1e-6))))
+    outputs = None
+    if args.dump_outputs and rank == 0:                      # after the first window: the same steps in a plain and a --full run
+        od = sim.obs_dim
+        row = last_row[0]
+        outputs = {"obs": row[:, :od], "action": row[:, od:od + 6], "reward": row[:, od + 6], "done": row[:, od + 7],
+                   "value": row[:, od + 8], "log_prob": row[:, od + 9], "next_obs": sim.obs}
+        limit = 64 << 20
+        env_bytes = sum(v[0].numel() * 4 for v in outputs.values())
+        idx = None
+        if n * env_bytes > limit:                            # a fixed, seeded sample of the envs
+            idx = torch.from_numpy(np.sort(np.random.RandomState(0).choice(n, limit // env_bytes, replace=False))).to(dev)
+        outputs = {k: (v if idx is None else v[idx]).float().cpu().numpy() for k, v in outputs.items()}
+    # repeats of the timed region: one in a plain run, with --full as many as fit ~1.5 s (3..40) unless given; every
+    # rank must agree on the count
+    reps = args.repeats if args.repeats > 0 else (max(3, min(40, int(1.5 / max(first, 1e-6)))) if args.full else 1)
     if use_dist:
         rr = torch.tensor([reps], device=dev); dist.broadcast(rr, src=0); reps = int(rr.item())
     dts, owns = [first], [first_own]
-    rec = args.policy == "persistent"                        # one event pair per 64-step launch costs nothing; per-step pairs would
+    rec = args.full and args.policy == "persistent"          # one event pair per 64-step launch costs nothing; per-step pairs would
     for _ in range(reps - 1):
         d, o = timed(rec)
         dts.append(d); owns.append(o)
-    if len(kev) == 0:                                        # stepwise modes (or a single repeat): one more pass, only for the kernel events
+    if args.full and len(kev) == 0:                          # stepwise modes (or a single repeat): one more pass, only for the kernel events
         timed(True)
     torch.cuda.synchronize(dev)
     order = sorted(range(len(dts)), key=lambda i: dts[i])
     med = order[len(order) // 2]
     dt = dts[med]
-    kern_total_ms = sum(a.elapsed_time(b) for a, b, _ in kev); kern_units = sum(u for _, _, u in kev)
-    units = kev[0][2]                                        # env-steps of one full launch (the first recorded one)
-    kern_ms = kern_total_ms / kern_units * units             # average duration of a launch of `units` env-steps
-    kernel_name = "so100_rollout_fused" if args.policy == "persistent" else ("so100_step_mw" if n <= 16384 else "so100_step_fused")
     per_rank = None
     if use_dist:                                             # every rank's own rate over the median repeat
         mine = torch.tensor([n * args.steps / owns[med]], device=dev, dtype=torch.float64)
         allr = [torch.zeros_like(mine) for _ in range(world)]; dist.all_gather(allr, mine)
         per_rank = [float(x.item()) for x in allr]
 
-    # HBM traffic of the dominant kernel: rocprofv3 PMC counters cannot be collected from inside this process; the
-    # committed PMC pass is quoted only when it was taken on THIS kernel source (fingerprint), workload and batch size.
-    traffic, traffic_note = None, "no committed PMC pass matches this kernel source / workload / batch size"
-    try:
-        import glob
-        sha = source_sha16()
-        for f in sorted(glob.glob(os.path.join(ROOT, "profiles", "*_pmc_summary.json"))):
-            pmc = json.load(open(f))
-            if pmc.get("source_sha16") != sha or pmc.get("bench_workload") != args.workload or pmc.get("envs") != n or pmc.get("policy", "persistent") != args.policy:
-                continue
-            hit = [v for k, v in pmc["kernels"].items() if kernel_name in k and "hbm_traffic_bytes_per_env_step" in v]
-            if hit:
-                traffic = hit[0]["hbm_traffic_bytes_per_env_step"]; traffic_note = os.path.basename(f)
-    except Exception as ex:                                  # a broken summary file must not break the bench line
-        traffic, traffic_note = None, f"PMC summary unreadable: {ex}"
+    if args.full:
+        kern_total_ms = sum(a.elapsed_time(b) for a, b, _ in kev); kern_units = sum(u for _, _, u in kev)
+        units = kev[0][2]                                    # env-steps of one full launch (the first recorded one)
+        kern_ms = kern_total_ms / kern_units * units         # average duration of a launch of `units` env-steps
+        kernel_name = "so100_rollout_fused" if args.policy == "persistent" else ("so100_step_mw" if n <= 16384 else "so100_step_fused")
+        # HBM traffic of the dominant kernel: rocprofv3 PMC counters cannot be collected from inside this process; the
+        # committed PMC pass is quoted only when it was taken on THIS kernel source (fingerprint), workload and batch size.
+        traffic, traffic_note = None, "no committed PMC pass matches this kernel source / workload / batch size"
+        try:
+            import glob
+            sha = source_sha16()
+            for f in sorted(glob.glob(os.path.join(ROOT, "profiles", "*_pmc_summary.json"))):
+                pmc = json.load(open(f))
+                if pmc.get("source_sha16") != sha or pmc.get("bench_workload") != args.workload or pmc.get("envs") != n or pmc.get("policy", "persistent") != args.policy:
+                    continue
+                hit = [v for k, v in pmc["kernels"].items() if kernel_name in k and "hbm_traffic_bytes_per_env_step" in v]
+                if hit:
+                    traffic = hit[0]["hbm_traffic_bytes_per_env_step"]; traffic_note = os.path.basename(f)
+        except Exception as ex:                              # a broken summary file must not break the bench line
+            traffic, traffic_note = None, f"PMC summary unreadable: {ex}"
 
+    if outputs is not None:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in outputs.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
     if rank == 0:
-        bytes_per = BYTES_PER_ENV_STEP_BY_KIND.get((kind, bool(flags & CONTACT_BITS)), BYTES_PER_ENV_STEP)
         value = world * n * args.steps / dt
-        achieved = bytes_per * units / (kern_ms * 1e-3) / 1e9
         out = {
             "metric": "env steps/sec at 4096 envs/GPU, Env01 PPO rollout", "value": value, "unit": "env-steps/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
@@ -435,25 +467,28 @@ def main():
             "config": {"workload": f"{args.workload}: Env{kind:02d} x {n} envs/GPU, frame_skip 16, " + wl_desc
                                    + ", SB3-MlpPolicy-shaped rollout (" + args.policy + " policy), randomized resets, staggered episodes",
                        "envs_per_gpu": n, "rollout_chunk": T, "parallelism": f"env-sharded x{world}, RCCL gather per chunk" if world > 1 else "single GPU"},
+        }
+        if args.full:
+            bytes_per = BYTES_PER_ENV_STEP_BY_KIND.get((kind, bool(flags & CONTACT_BITS)), BYTES_PER_ENV_STEP)
+            achieved = bytes_per * units / (kern_ms * 1e-3) / 1e9
             # `traffic` and `algorithmic_bytes_per_launch` are both per launch of THIS run (`env_steps_per_launch` env-steps): the PMC pass
             # measures bytes per env-step of the same kernel / workload / batch (its own launches are 64-step chunks) and is scaled to it
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                         "traffic": None if traffic is None else traffic * units, "traffic_source": traffic_note,
-                         "traffic_unit": "bytes per launch of env_steps_per_launch env-steps (FETCH_SIZE+WRITE_SIZE per env-step from the PMC pass in profiles/, x env_steps_per_launch)",
-                         "traffic_bytes_per_env_step": traffic, "algorithmic_bytes_per_launch": bytes_per * units, "kernel": kernel_name, "kernel_ms": kern_ms,
-                         "kernel_launches_timed": len(kev), "env_steps_per_launch": units, "bytes_per_env_step": bytes_per,
-                         "kernel_env_steps_per_s": units / (kern_ms * 1e-3)},
-        }
-        if args.workload == "env01_free":                    # the measured instruction count (PMC) is for this workload only
-            tf = FLOP_PER_ENV_STEP * units / (kern_ms * 1e-3) / 1e12
-            out["roofline"]["valu"] = {"flop_per_env_step": FLOP_PER_ENV_STEP, "flop_per_env_step_survey_estimate": FLOP_PER_ENV_STEP_SURVEY,
-                                       "achieved_tflops": tf, "peak_tflops": VALU_PEAK_TFLOPS, "frac": tf / VALU_PEAK_TFLOPS}
-        if world == 1 and not args.no_sb3_path:
-            out["sb3_vecenv_path"] = sb3_vecenv_path(kind, flags, n, dev)
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(kind, flags, -1 if (flags & CONTACT_BITS) else 2)     # pad rows: the oracle's Newton (PGS crawls on them)
-        if world == 1 and args.workload == "env01_free" and not args.no_large_batch:
-            out["roofline"]["large_batch"] = large_batch_roofline(kind, flags, dev)
+            out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                               "traffic": None if traffic is None else traffic * units, "traffic_source": traffic_note,
+                               "traffic_unit": "bytes per launch of env_steps_per_launch env-steps (FETCH_SIZE+WRITE_SIZE per env-step from the PMC pass in profiles/, x env_steps_per_launch)",
+                               "traffic_bytes_per_env_step": traffic, "algorithmic_bytes_per_launch": bytes_per * units, "kernel": kernel_name, "kernel_ms": kern_ms,
+                               "kernel_launches_timed": len(kev), "env_steps_per_launch": units, "bytes_per_env_step": bytes_per,
+                               "kernel_env_steps_per_s": units / (kern_ms * 1e-3)}
+            if args.workload == "env01_free":                # the measured instruction count (PMC) is for this workload only
+                tf = FLOP_PER_ENV_STEP * units / (kern_ms * 1e-3) / 1e12
+                out["roofline"]["valu"] = {"flop_per_env_step": FLOP_PER_ENV_STEP, "flop_per_env_step_survey_estimate": FLOP_PER_ENV_STEP_SURVEY,
+                                           "achieved_tflops": tf, "peak_tflops": VALU_PEAK_TFLOPS, "frac": tf / VALU_PEAK_TFLOPS}
+            if world == 1 and not args.no_sb3_path:
+                out["sb3_vecenv_path"] = sb3_vecenv_path(kind, flags, n, dev)
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(kind, flags, -1 if (flags & CONTACT_BITS) else 2)     # pad rows: the oracle's Newton (PGS crawls on them)
+            if world == 1 and args.workload == "env01_free" and not args.no_large_batch:
+                out["roofline"]["large_batch"] = large_batch_roofline(kind, flags, dev)
         sys.stdout.flush()
         os.write(result_fd, (json.dumps(out) + "\n").encode())
     if use_dist:

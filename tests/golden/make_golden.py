@@ -17,7 +17,8 @@ So every line of reward / obs / ctrl / reset / curriculum / reprojection logic t
 reference's; only the physics underneath is ours.  The recorded trajectories (inputs: actions +
 uniforms; outputs: obs, reward, terminated, qpos/qvel) are what tests/test_golden_task.py replays
 through the oracle's C task layer.  Pure-function fixtures (joint penalty, base reward, pinhole
-projection incl. a hand-checkable example) are emitted too.
+projection incl. a hand-checkable example) are emitted too, and the MJCF attributes that tests/test_model_def.py checks
+the model constants against (mjcf.json).
 
 Only DATA is written (tests/golden/*.json); no reference source or bytecode is copied.
 `env_base_02.py` uses CAMERA_NAME without importing it (NameError upstream); the harness injects
@@ -305,6 +306,35 @@ def reference_cli_surface():
             "dirs": [ref_main.MODEL_DIR, ref_main.LOG_DIR, ref_main.RECORDING_DIR]}
 
 
+def mjcf_facts():
+    """The attributes of the reference MJCF (so_arm100_camera.xml, env01.xml) that tests/test_model_def.py checks
+    csrc/so100_model_def.h against, as raw attribute strings (-> mjcf.json)."""
+    import xml.etree.ElementTree as ET
+    model = os.path.join(REF_SRC, "so100_mujoco_rl", "envs", "model")
+    arm = ET.parse(os.path.join(model, "so_arm100_camera.xml")).getroot()
+    scene = ET.parse(os.path.join(model, "env01.xml")).getroot()
+    bodies = {b.get("name"): b for b in arm.iter("body")}
+    classes = {d.get("class"): d for d in arm.iter("default") if d.get("class")}
+    links = {}
+    for name in ("Rotation_Pitch", "Upper_Arm", "Lower_Arm", "Wrist_Pitch_Roll", "Fixed_Jaw", "Moving_Jaw"):
+        b = bodies[name]; j = b.find("joint")
+        links[name] = {"body": dict(b.attrib), "inertial": dict(b.find("inertial").attrib), "joint": dict(j.attrib),
+                       "joint_class": dict(classes[j.get("class")].find("joint").attrib),
+                       "finger_collision_geoms": [dict(g.attrib) for g in b.findall("geom") if g.get("class") == "finger_collision"]}
+    cube = [b for b in scene.iter("body") if b.get("name") == "block_a"][0]
+    return {"arm_compiler": dict(arm.find("compiler").attrib), "scene_compiler": dict(scene.find("compiler").attrib), "links": links,
+            "so_arm100_joint": dict(classes["so_arm100"].find("joint").attrib),
+            "so_arm100_position": dict(classes["so_arm100"].find("position").attrib),
+            "actuator_joints": [a.get("joint") for a in arm.find("actuator")],
+            "fixed_jaw_camera": dict(bodies["Fixed_Jaw"].find("camera").attrib),
+            "finger_collision_geom": dict(classes["finger_collision"].find("geom").attrib),
+            "scene_excludes": [[e.get("body1"), e.get("body2")] for e in scene.find("contact")],
+            "arm_excludes": [[e.get("body1"), e.get("body2")] for e in arm.find("contact")],
+            "floor": dict([g for g in scene.iter("geom") if g.get("name") == "floor"][0].attrib),
+            "cube_joint": dict(cube.find("joint").attrib), "cube_geom": dict(cube.find("geom").attrib),
+            "scene_has_option": scene.find("option") is not None}
+
+
 def f(x):
     """json-able float/array"""
     if isinstance(x, (list, tuple)):
@@ -322,6 +352,7 @@ def dump(name, obj):
 
 
 def main():
+    dump("mjcf.json", mjcf_facts())
     registry = install_stubs()
     sys.path.insert(0, REF_SRC)
     os.chdir(tempfile.mkdtemp())          # env_base_02 creates ./images in the cwd

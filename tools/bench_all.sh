@@ -4,17 +4,17 @@
 set -e
 OUT=gpurun_out/${1:-bench_all}
 mkdir -p "$OUT"
-python bench.py > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
+python bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/bench_driver_args.json" 2>/dev/null
 for w in env01_nopads env01_reference env01_contact; do
-  python bench.py --workload $w > "$OUT/bench_$w.json" 2> "$OUT/bench_$w.err"
+  python bench.py --full --workload $w > "$OUT/bench_$w.json" 2> "$OUT/bench_$w.err"
 done
 for w in env01_reference_links env01_reference_proxies; do
-  python bench.py --workload $w --no-cpu-baseline > "$OUT/bench_$w.json" 2>/dev/null
+  python bench.py --full --workload $w --no-cpu-baseline > "$OUT/bench_$w.json" 2>/dev/null
 done
-python bench.py --workload env02_reference --envs 16384 --no-cpu-baseline > "$OUT/bench_env02_16384.json" 2>/dev/null
-python bench.py --workload env05_reference --envs 8192 --no-cpu-baseline > "$OUT/bench_env05_8192.json" 2>/dev/null
-SO100_FORCE_DIST=1 python bench.py --no-cpu-baseline --no-sb3-path > "$OUT/bench_force_dist.json" 2>/dev/null
+python bench.py --full --workload env02_reference --envs 16384 --no-cpu-baseline > "$OUT/bench_env02_16384.json" 2>/dev/null
+python bench.py --full --workload env05_reference --envs 8192 --no-cpu-baseline > "$OUT/bench_env05_8192.json" 2>/dev/null
+SO100_FORCE_DIST=1 python bench.py --full --no-cpu-baseline --no-sb3-path > "$OUT/bench_force_dist.json" 2>/dev/null
 python - "$OUT" <<'PY'
 import json, sys, glob, os
 for f in sorted(glob.glob(os.path.join(sys.argv[1], "bench_*.json"))):

@@ -10,8 +10,8 @@ EXTRA="--workload $WL --no-sb3-path"
 OUT=$PWD/gpurun_out/$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-BENCH="python3 $PWD/bench.py --steps 1024 --warmup 128 --no-cpu-baseline --no-large-batch $EXTRA"
-PMCB="python3 $PWD/bench.py --steps 256 --warmup 64 --no-cpu-baseline --no-large-batch $EXTRA"
+BENCH="python3 $PWD/bench.py --full --steps 1024 --warmup 128 --no-cpu-baseline --no-large-batch $EXTRA"
+PMCB="python3 $PWD/bench.py --full --steps 256 --warmup 64 --no-cpu-baseline --no-large-batch $EXTRA"
 cd /tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- $BENCH > "$OUT/stats.log" 2>&1
 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY --output-format csv -d "$OUT/sq" -- $PMCB > "$OUT/sq.log" 2>&1
