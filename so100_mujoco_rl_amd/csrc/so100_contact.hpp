@@ -1469,9 +1469,9 @@ template <typename T>
 SO100_HD void substep_with_pads(T q[6], T v[6], T qc[6], const T ctrl[6], T ff[6], T fl[6], T aw[6], Cube<T>& cube, const T applied[3],
                                 unsigned flags, int solver_iters, int contact_iters, Arm<T>& A, bool first, T dq[6], T* residual,
                                 ContactsPriv<T>& cs, int& zones, int* stat = nullptr) {
-    if (first) arm_trig(q, A); else arm_trig_update(q, dq, A);
-    arm_bias(v, A);
-    arm_mass(A);
+    if (first) arm_trig(q, A); else arm_trig_update<T, false>(q, dq, A);
+    arm_bias<T, false>(v, A);
+    arm_mass<T, false>(A);
     arm_factor(flags, A);
     const bool cube_live = (flags & F_CUBE_PINNED) == 0u;
     WorldFK<T> W;

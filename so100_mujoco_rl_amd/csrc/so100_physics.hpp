@@ -159,6 +159,30 @@ template <int K, typename T> SO100_HD void to_parent(const T x[3], T s, T c, T y
     T t[3]; rot_axis<so100g::LINK_AXIS[K]>(x, s, c, t); cmat<K>(t, y);
 }
 
+// ---------------------------------------------------------------------------------------------
+// pairs: two values of T carried through the same arithmetic.  On the device V2<float> is a native two-float vector, so
+// `*`, `+`, `-` become v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32 (two IEEE fp32 operations per instruction, issued at
+// the rate of one scalar v_fma_f32).  Elsewhere it is a two-member struct with the same operators.  Each half is computed
+// by the same expression as the scalar code; only FMA-contraction choices of the compiler can differ between the two.
+// ---------------------------------------------------------------------------------------------
+template <typename T> struct V2s {
+    T x, y;
+    SO100_HD V2s() = default;
+    SO100_HD V2s(T a, T b) : x(a), y(b) {}
+    template <typename U> SO100_HD explicit V2s(U a) : x(T(a)), y(T(a)) {}        // splat (T(const) in the templated helpers)
+    SO100_HD V2s operator-() const { return V2s(-x, -y); }
+    SO100_HD V2s& operator+=(const V2s& o) { x += o.x; y += o.y; return *this; }
+    SO100_HD V2s& operator-=(const V2s& o) { x -= o.x; y -= o.y; return *this; }
+};
+template <typename T> SO100_HD V2s<T> operator+(const V2s<T>& a, const V2s<T>& b) { return V2s<T>(a.x + b.x, a.y + b.y); }
+template <typename T> SO100_HD V2s<T> operator-(const V2s<T>& a, const V2s<T>& b) { return V2s<T>(a.x - b.x, a.y - b.y); }
+template <typename T> SO100_HD V2s<T> operator*(const V2s<T>& a, const V2s<T>& b) { return V2s<T>(a.x * b.x, a.y * b.y); }
+template <typename T> struct V2sel { using type = V2s<T>; };
+#if defined(__HIP_DEVICE_COMPILE__)
+template <> struct V2sel<float> { using type = float __attribute__((ext_vector_type(2))); };
+#endif
+template <typename T> using V2 = typename V2sel<T>::type;
+
 // symmetric 3x3 stored (xx, yy, zz, xy, xz, yz)
 template <typename T> SO100_HD void sym_mul(const T I[6], const T v[3], T r[3]) {
     const T x = I[0]*v[0] + I[3]*v[1] + I[4]*v[2];
@@ -282,8 +306,12 @@ template <int K, typename T> struct LinkCrb {
             M[K*(K+1)/2 + K] = n[AX] + T(so100g::ARMATURE);
             walk<K>(s, c, f, n, M);
         }
-        // ---- accumulate into the parent
-        if constexpr (K > 0) {
+        if constexpr (K > 0) accumulate(s, c, cmp);
+    }
+    // add link K's composite into its parent's
+    SO100_HD static void accumulate(const T s[6], const T c[6], Composite<T> cmp[6]) {
+        constexpr int AX = so100g::LINK_AXIS[K];
+        {
             T hp[3], Ir[6], Ip[6];
             to_parent<K>(cmp[K].h, s[K], c[K], hp);
             sym_rot_axis<AX>(cmp[K].I, s[K], c[K], Ir);
@@ -319,6 +347,117 @@ template <int K, typename T> struct LinkCrb {
     }
 };
 
+// The same recursions in pair form (arm_bias / arm_mass with PK = true): every transform that two 3-vectors take with the
+// same s, c and constants runs once on a V2[3].  RNEA carries W = (wd, w) forward and FN = (f, n) backward; the CRBA column walk
+// carries (f, n).  A half is unpacked only where it feeds a term of its own (w x (w x p), h x a, p x f).
+template <int K, typename T> struct LinkFwdP {
+    using V = V2<T>;
+    SO100_HD static void run(const T s[6], const T c[6], const T v[6], V W[3], T a[3], V FN[6][3]) {
+        constexpr int AX = so100g::LINK_AXIS[K];
+        constexpr int B = (AX + 1) % 3, C = (AX + 2) % 3;
+        const T qd = v[K];
+        if constexpr (K == 0) {
+            T ao[3] = { a[0], a[1], a[2] };
+            to_child<K>(ao, s[K], c[K], a);
+            W[AX] = V{ T(0), qd }; W[B] = V{ T(0), T(0) }; W[C] = V{ T(0), T(0) };
+        } else {
+            V t[3];
+            crossp<K>(W, t);                                   // (wd x p, w x p)
+            const T w[3] = { W[0].y, W[1].y, W[2].y }, t2p[3] = { t[0].y, t[1].y, t[2].y };
+            T t2[3], ao[3];
+            cross(w, t2p, t2);
+            ao[0] = a[0] + t[0].x + t2[0]; ao[1] = a[1] + t[1].x + t2[1]; ao[2] = a[2] + t[2].x + t2[2];
+            V Wc[3];
+            to_child<K>(W, V(s[K]), V(c[K]), Wc);
+            to_child<K>(ao, s[K], c[K], a);
+            Wc[B].x += Wc[C].y*qd; Wc[C].x -= Wc[B].y*qd;
+            Wc[AX].y += qd;
+            W[0] = Wc[0]; W[1] = Wc[1]; W[2] = Wc[2];
+        }
+        const V h[3] = { V(so100g::LINK_H[K][0]), V(so100g::LINK_H[K][1]), V(so100g::LINK_H[K][2]) };
+        const V Io[6] = { V(so100g::LINK_IORG[K][0]), V(so100g::LINK_IORG[K][1]), V(so100g::LINK_IORG[K][2]),
+                          V(so100g::LINK_IORG[K][3]), V(so100g::LINK_IORG[K][4]), V(so100g::LINK_IORG[K][5]) };
+        const T hs[3] = { T(so100g::LINK_H[K][0]), T(so100g::LINK_H[K][1]), T(so100g::LINK_H[K][2]) };
+        const T m = T(so100g::LINK_MASS[K]);
+        V U[3], S[3];
+        cross(W, h, U);                                        // (wd x h, w x h)
+        sym_mul(Io, W, S);                                     // (Io wd, Io w)
+        const T w[3] = { W[0].y, W[1].y, W[2].y };
+        const T u2p[3] = { U[0].y, U[1].y, U[2].y }, Iw[3] = { S[0].y, S[1].y, S[2].y };
+        T u2[3], v2[3], u3[3];
+        cross(w, u2p, u2); cross(w, Iw, v2); cross(hs, a, u3);
+#pragma unroll
+        for (int i = 0; i < 3; i++) FN[K][i] = V{ m*a[i] + U[i].x + u2[i], S[i].x + v2[i] + u3[i] };
+    }
+};
+
+template <int K, typename T> struct LinkBwdP {
+    using V = V2<T>;
+    SO100_HD static void run(const T s[6], const T c[6], V FN[6][3], T bias[6]) {
+        bias[K] = FN[K][so100g::LINK_AXIS[K]].y;
+        if constexpr (K > 0) {
+            V P[3]; T t[3];
+            to_parent<K>(FN[K], V(s[K]), V(c[K]), P);
+            const T fp[3] = { P[0].x, P[1].x, P[2].x };
+            pcross<K>(fp, t);
+#pragma unroll
+            for (int i = 0; i < 3; i++) { P[i].y = P[i].y + t[i]; FN[K-1][i] += P[i]; }
+        }
+    }
+};
+
+// CRBA in pair form: columns K and K-1 of M take the same to_parent / pcross for every frame J < K-1, so they walk those
+// frames together as F = (f_K, f_K-1), N = (n_K, n_K-1); column K takes its first frame (J = K-1) alone, before link K's
+// composite is added into its parent's (column K-1 needs the complete composite of link K-1).
+template <typename T> struct CrbP {
+    using V = V2<T>;
+    // f = axis x h, n = Ic[:, axis] of link K's composite; the diagonal entry of M
+    template <int K> SO100_HD static void column(const Composite<T> cmp[6], T f[3], T n[3], T M[21]) {
+        constexpr int AX = so100g::LINK_AXIS[K], B = (AX + 1) % 3, C = (AX + 2) % 3;
+        f[AX] = T(0); f[B] = -cmp[K].h[C]; f[C] = cmp[K].h[B];
+        n[0] = cmp[K].I[sym_idx(0, AX)]; n[1] = cmp[K].I[sym_idx(1, AX)]; n[2] = cmp[K].I[sym_idx(2, AX)];
+        M[K*(K+1)/2 + K] = n[AX] + T(so100g::ARMATURE);
+    }
+    // carry (f, n) of one column from frame J1 to frame J1-1 (LinkCrb::walk's step) and read M[K][J1-1]
+    template <int K, int J1> SO100_HD static void step(const T s[6], const T c[6], T f[3], T n[3], T M[21]) {
+        T fp[3], np[3], t[3];
+        to_parent<J1>(f, s[J1], c[J1], fp);
+        to_parent<J1>(n, s[J1], c[J1], np);
+        pcross<J1>(fp, t);
+        f[0] = fp[0]; f[1] = fp[1]; f[2] = fp[2];
+        n[0] = np[0] + t[0]; n[1] = np[1] + t[1]; n[2] = np[2] + t[2];
+        M[K*(K+1)/2 + (J1-1)] = n[so100g::LINK_AXIS[J1-1]];
+    }
+    // the same step for columns K (.x) and K-1 (.y) together, for frames J1 .. 1
+    template <int K, int J1> SO100_HD static void walk2(const T s[6], const T c[6], V F[3], V N[3], T M[21]) {
+        if constexpr (J1 > 0) {
+            V fp[3], np[3], t[3];
+            const V sv = V(s[J1]), cv = V(c[J1]);
+            to_parent<J1>(F, sv, cv, fp);
+            to_parent<J1>(N, sv, cv, np);
+            pcross<J1>(fp, t);
+#pragma unroll
+            for (int i = 0; i < 3; i++) { F[i] = fp[i]; N[i] = np[i] + t[i]; }
+            constexpr int AXJ = so100g::LINK_AXIS[J1-1];
+            M[K*(K+1)/2 + (J1-1)] = N[AXJ].x;
+            M[(K-1)*K/2 + (J1-1)] = N[AXJ].y;
+            walk2<K, J1-1>(s, c, F, N, M);
+        }
+    }
+    // columns K and K-1 (K odd), and the composites of links K and K-1 added into their parents
+    template <int K> SO100_HD static void columns(const T s[6], const T c[6], Composite<T> cmp[6], T M[21]) {
+        T fa[3], na[3], fb[3], nb[3];
+        column<K>(cmp, fa, na, M);
+        step<K, K>(s, c, fa, na, M);
+        LinkCrb<K, T>::accumulate(s, c, cmp);
+        column<K-1>(cmp, fb, nb, M);
+        V F[3] = { V{ fa[0], fb[0] }, V{ fa[1], fb[1] }, V{ fa[2], fb[2] } };
+        V N[3] = { V{ na[0], nb[0] }, V{ na[1], nb[1] }, V{ na[2], nb[2] } };
+        walk2<K, K-1>(s, c, F, N, M);
+        if constexpr (K - 1 > 0) LinkCrb<K-1, T>::accumulate(s, c, cmp);
+    }
+};
+
 // stages of arm_dynamics (separately callable: the persistent rollout kernel runs arm_bias and arm_mass on different waves)
 template <typename T> SO100_HD void arm_trig(const T q[6], Arm<T>& A) {
 #pragma unroll
@@ -328,8 +467,20 @@ template <typename T> SO100_HD void arm_trig(const T q[6], Arm<T>& A) {
 // truncation < 1e-11).  fp32 only: 66 instructions instead of ~150 for six fresh sin/cos pairs; the fp64 (host-test)
 // instantiation recomputes exact trig so that the formulation-equivalence tests keep their 1e-13 tolerances.
 // Round-off accumulates over at most frame_skip-1 updates (~2e-7): arm_trig() resynchronises at every env step.
-template <typename T> SO100_HD void arm_trig_update(const T q[6], const T dq[6], Arm<T>& A) {
+// PK = true: joints (0, 1), (2, 3), (4, 5) as pairs (the same expressions, half the instructions)
+template <typename T, bool PK = true> SO100_HD void arm_trig_update(const T q[6], const T dq[6], Arm<T>& A) {
     if constexpr (sizeof(T) == 8) { arm_trig(q, A); }
+    else if constexpr (PK) {
+        using V = V2<T>;
+#pragma unroll
+        for (int k = 0; k < 6; k += 2) {
+            const V d = V{ dq[k], dq[k+1] }, d2 = d*d, s0 = V{ A.s[k], A.s[k+1] }, c0 = V{ A.c[k], A.c[k+1] };
+            const V sd = d*(V(1) + d2*(V(-1.0/6.0) + d2*V(1.0/120.0)));
+            const V cd = V(1) + d2*(V(-0.5) + d2*(V(1.0/24.0) + d2*V(-1.0/720.0)));
+            const V sn = s0*cd + c0*sd, cs = c0*cd - s0*sd;
+            A.s[k] = sn.x; A.s[k+1] = sn.y; A.c[k] = cs.x; A.c[k+1] = cs.y;
+        }
+    }
     else {
 #pragma unroll
         for (int k = 0; k < 6; k++) {
@@ -341,24 +492,46 @@ template <typename T> SO100_HD void arm_trig_update(const T q[6], const T dq[6],
         }
     }
 }
-template <typename T> SO100_HD void arm_bias(const T v[6], Arm<T>& A) {
+// PK = true: the pair form (LinkFwdP / LinkBwdP / CrbP); PK = false: one 3-vector at a time.  Both compute every value by
+// the same expression (tests/test_pair_bitwise.py: bitwise equal without FMA contraction).
+template <typename T, bool PK = true> SO100_HD void arm_bias(const T v[6], Arm<T>& A) {
     // RNEA (bias): base at rest, gravity folded in as a base acceleration of +g along world z
-    T w[3] = { T(0), T(0), T(0) }, wd[3] = { T(0), T(0), T(0) }, a[3] = { T(0), T(0), T(so100g::GRAVITY) };
-    T f[6][3], n[6][3];
-    LinkFwd<0, T>::run(A.s, A.c, v, w, wd, a, f, n);
-    LinkFwd<1, T>::run(A.s, A.c, v, w, wd, a, f, n);
-    LinkFwd<2, T>::run(A.s, A.c, v, w, wd, a, f, n);
-    LinkFwd<3, T>::run(A.s, A.c, v, w, wd, a, f, n);
-    LinkFwd<4, T>::run(A.s, A.c, v, w, wd, a, f, n);
-    LinkFwd<5, T>::run(A.s, A.c, v, w, wd, a, f, n);
-    LinkBwd<5, T>::run(A.s, A.c, f, n, A.bias);
-    LinkBwd<4, T>::run(A.s, A.c, f, n, A.bias);
-    LinkBwd<3, T>::run(A.s, A.c, f, n, A.bias);
-    LinkBwd<2, T>::run(A.s, A.c, f, n, A.bias);
-    LinkBwd<1, T>::run(A.s, A.c, f, n, A.bias);
-    LinkBwd<0, T>::run(A.s, A.c, f, n, A.bias);
+    if constexpr (PK) {
+        using V = V2<T>;
+        V W[3] = { V{ T(0), T(0) }, V{ T(0), T(0) }, V{ T(0), T(0) } };      // (wd, w)
+        T a[3] = { T(0), T(0), T(so100g::GRAVITY) };
+        V FN[6][3];                                                           // (f, n)
+        LinkFwdP<0, T>::run(A.s, A.c, v, W, a, FN);
+        LinkFwdP<1, T>::run(A.s, A.c, v, W, a, FN);
+        LinkFwdP<2, T>::run(A.s, A.c, v, W, a, FN);
+        LinkFwdP<3, T>::run(A.s, A.c, v, W, a, FN);
+        LinkFwdP<4, T>::run(A.s, A.c, v, W, a, FN);
+        LinkFwdP<5, T>::run(A.s, A.c, v, W, a, FN);
+        LinkBwdP<5, T>::run(A.s, A.c, FN, A.bias);
+        LinkBwdP<4, T>::run(A.s, A.c, FN, A.bias);
+        LinkBwdP<3, T>::run(A.s, A.c, FN, A.bias);
+        LinkBwdP<2, T>::run(A.s, A.c, FN, A.bias);
+        LinkBwdP<1, T>::run(A.s, A.c, FN, A.bias);
+        LinkBwdP<0, T>::run(A.s, A.c, FN, A.bias);
+        return;
+    } else {
+        T w[3] = { T(0), T(0), T(0) }, wd[3] = { T(0), T(0), T(0) }, a[3] = { T(0), T(0), T(so100g::GRAVITY) };
+        T f[6][3], n[6][3];
+        LinkFwd<0, T>::run(A.s, A.c, v, w, wd, a, f, n);
+        LinkFwd<1, T>::run(A.s, A.c, v, w, wd, a, f, n);
+        LinkFwd<2, T>::run(A.s, A.c, v, w, wd, a, f, n);
+        LinkFwd<3, T>::run(A.s, A.c, v, w, wd, a, f, n);
+        LinkFwd<4, T>::run(A.s, A.c, v, w, wd, a, f, n);
+        LinkFwd<5, T>::run(A.s, A.c, v, w, wd, a, f, n);
+        LinkBwd<5, T>::run(A.s, A.c, f, n, A.bias);
+        LinkBwd<4, T>::run(A.s, A.c, f, n, A.bias);
+        LinkBwd<3, T>::run(A.s, A.c, f, n, A.bias);
+        LinkBwd<2, T>::run(A.s, A.c, f, n, A.bias);
+        LinkBwd<1, T>::run(A.s, A.c, f, n, A.bias);
+        LinkBwd<0, T>::run(A.s, A.c, f, n, A.bias);
+    }
 }
-template <typename T> SO100_HD void arm_mass(Arm<T>& A) {
+template <typename T, bool PK = true> SO100_HD void arm_mass(Arm<T>& A) {
     // CRBA
     Composite<T> cmp[6];
 #pragma unroll
@@ -369,12 +542,18 @@ template <typename T> SO100_HD void arm_mass(Arm<T>& A) {
 #pragma unroll
         for (int i = 0; i < 6; i++) cmp[k].I[i] = T(so100g::LINK_IORG[k][i]);
     }
-    LinkCrb<5, T>::run(A.s, A.c, cmp, A.M);
-    LinkCrb<4, T>::run(A.s, A.c, cmp, A.M);
-    LinkCrb<3, T>::run(A.s, A.c, cmp, A.M);
-    LinkCrb<2, T>::run(A.s, A.c, cmp, A.M);
-    LinkCrb<1, T>::run(A.s, A.c, cmp, A.M);
-    LinkCrb<0, T>::run(A.s, A.c, cmp, A.M);
+    if constexpr (PK) {
+        CrbP<T>::template columns<5>(A.s, A.c, cmp, A.M);
+        CrbP<T>::template columns<3>(A.s, A.c, cmp, A.M);
+        CrbP<T>::template columns<1>(A.s, A.c, cmp, A.M);
+    } else {
+        LinkCrb<5, T>::run(A.s, A.c, cmp, A.M);
+        LinkCrb<4, T>::run(A.s, A.c, cmp, A.M);
+        LinkCrb<3, T>::run(A.s, A.c, cmp, A.M);
+        LinkCrb<2, T>::run(A.s, A.c, cmp, A.M);
+        LinkCrb<1, T>::run(A.s, A.c, cmp, A.M);
+        LinkCrb<0, T>::run(A.s, A.c, cmp, A.M);
+    }
 }
 template <typename T> SO100_HD void arm_dynamics(const T q[6], const T v[6], Arm<T>& A) {
     arm_trig(q, A);
@@ -690,13 +869,13 @@ SO100_HD void arm_finish(T q[6], T v[6], T qc[6], const T ctrl[6], T ff[6], T fl
     arm_solve_integrate(q, v, qc, ctrl, ff, fl, flags, iters, A, dq, residual);
 }
 
-template <typename T>
+template <typename T, bool PK = true>
 SO100_HD void arm_substep(T q[6], T v[6], T qc[6], const T ctrl[6], T ff[6], T fl[6], unsigned flags, int iters, Arm<T>& A,
                           bool first, T dq[6], T* residual = nullptr) {
     // first substep of an env step: exact sin/cos; later ones: incremental update by the previous substep's increment
-    if (first) arm_trig(q, A); else arm_trig_update(q, dq, A);
-    arm_bias(v, A);
-    arm_mass(A);
+    if (first) arm_trig(q, A); else arm_trig_update<T, PK>(q, dq, A);
+    arm_bias<T, PK>(v, A);
+    arm_mass<T, PK>(A);
     arm_finish(q, v, qc, ctrl, ff, fl, flags, iters, A, dq, residual);
 }
 

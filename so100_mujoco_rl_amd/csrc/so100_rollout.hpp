@@ -130,7 +130,8 @@ struct ContactMemo { int zones = -1, prev_n = 0; };
 // tell, although those registers hold nothing on wave 3.  After its solve the contact wave therefore overwrites all of it
 // with constants (`forget`, the caller's `forget_caller_state` for what lives outside this function): every path from the
 // Newton to a use passes that definition, so the old values are dead during the solve and their registers are free.
-template <bool PADS, bool LINKS, class Hook, class Forget>
+// PK: the arm dynamics in pair form (so100_physics.hpp); the callers choose it where it costs the kernel no scratch
+template <bool PADS, bool LINKS, bool PK, class Hook, class Forget>
 __device__ __forceinline__ void physics_phase_mw(const SimParams& p, int wave, int lane, EnvState& e, float ctrl[6], float cstale[3],
                                                  Arm<float>& A, const PhaseLds& L, ContactMemo& memo, Prof& prof_, Hook after_first_barrier, Forget forget_caller_state) {
     float (*xq)[64] = L.xq; float (*xc)[64] = L.xc; float (*xb)[64] = L.xb; float (*xa)[64] = L.xa; float (*xk)[64] = L.xk; float (*xm)[64] = L.xm;
@@ -187,7 +188,7 @@ __device__ __forceinline__ void physics_phase_mw(const SimParams& p, int wave, i
     for (int sub = 0; sub < p.frame_skip; sub++) {
         if (wave == 0) {
             // sin/cos: exact at the first substep, then rotated by the integration increment (arm_substep does the same)
-            if (sub == 0) arm_trig<float>(e.q, A); else arm_trig_update<float>(e.q, dq, A);
+            if (sub == 0) arm_trig<float>(e.q, A); else arm_trig_update<float, PK>(e.q, dq, A);
 #pragma unroll
             for (int i = 0; i < 6; i++) { xq[i][lane] = A.s[i]; xq[6 + i][lane] = A.c[i]; xq[12 + i][lane] = e.v[i]; }
             if (pads) {
@@ -220,7 +221,7 @@ __device__ __forceinline__ void physics_phase_mw(const SimParams& p, int wave, i
 #pragma unroll
                 for (int i = 0; i < 6; i++) { q1[i] = xq[18 + i][lane]; c1[i] = xk[i][lane]; }
             }
-            arm_bias<float>(v1, A);
+            arm_bias<float, PK>(v1, A);
 #pragma unroll
             for (int i = 0; i < 6; i++) xb[i][lane] = A.bias[i];
             if (pads) {                                    // what the contact wave's primal solve needs of q, ctrl and the bias (see "LDS" above)
@@ -232,7 +233,7 @@ __device__ __forceinline__ void physics_phase_mw(const SimParams& p, int wave, i
             }
             SO100_PROF(4);                                 // RNEA (wave 1)
         } else if (wave == 0) {
-            arm_mass<float>(A);
+            arm_mass<float, PK>(A);
             if (pads) {                                    // the contact wave's primal solve needs M itself
 #pragma unroll
                 for (int i = 0; i < 21; i++) xm[i][lane] = A.M[i];
@@ -575,6 +576,7 @@ __global__ void __launch_bounds__(64*NW) so100_rollout_fused(SimParams p, float*
     static_assert(!XW || MAXPADC*CF*64 + 36*64 <= MAXC*CF*64, "joint frames must fit in the unused tail of the contact store");
     float (*xw)[64] = XW ? reinterpret_cast<float (*)[64]>(pool + MAXPADC*CF*64) : nullptr;
     constexpr bool PADS = FL < 0 || (FL & (int)F_ANY_CONTACT) != 0;
+    // (the arm dynamics in pair form unless that costs scratch: the contact variants and FL = 7 keep the scalar form)
     constexpr bool LINKS = FL < 0 || (FL & (int)F_ANY_LINKS) != 0;
     __shared__ float xa[PADS ? 15 : 1][64];                       // pad contacts: the contact wave's accelerations, contact code, residual, set signature
     __shared__ float xk[PADS ? 12 : 1][64];                       //               ctrl and arm warm start of the env step
@@ -747,7 +749,7 @@ __global__ void __launch_bounds__(64*NW) so100_rollout_fused(SimParams p, float*
         {
             Arm<float> A;
                         const PhaseLds lds{ xq, xc, xb, pool, xa, xk, xm, pbuf, xw };
-            physics_phase_mw<PADS, LINKS>(p, wave, lane, e, ctx.ctrl, cstale, A, lds, memo, prof_, [&](int sub) {
+            physics_phase_mw<PADS, LINKS, !PADS && FL != 7>(p, wave, lane, e, ctx.ctrl, cstale, A, lds, memo, prof_, [&](int sub) {
                 if (wave == 3 && sub == 0 && t + 1 < ra.T) {       // wave 0 has consumed xn before this barrier
                     float eps[8];
                     policy_noise(p.env_id_offset + (uint32_t)env, ra.step_counter0 + (uint32_t)(t + 1), p.seed_lo, p.seed_hi, eps);

@@ -308,8 +308,8 @@ SO100_HD void physics_substeps(EnvState& e, const float ctrl[6], const SimParams
             const int n = e.cstat & 255, dr = e.cstat >> 8;
             e.cstat = (st[0] > n ? st[0] : n) | ((dr + st[2] > 0xFFFF ? 0xFFFF : dr + st[2]) << 8);
             e.csig = st[3];
-        } else {
-            arm_substep<float>(e.q, e.v, e.qc, ctrl, e.ff, e.fl, p.flags, p.solver_iters, A, s == 0, dq, &e.res);
+        } else {                                              // (the scalar form of the arm dynamics: the pair form costs this kernel scratch)
+            arm_substep<float, false>(e.q, e.v, e.qc, ctrl, e.ff, e.fl, p.flags, p.solver_iters, A, s == 0, dq, &e.res);
             cube_substep<float>(e.cube, applied, p.flags, p.contact_iters);
         }
     }
