@@ -162,6 +162,31 @@ typedef struct {
 int  so100_rollout(so100_sim* sim, const so100_policy_weights* w, const so100_rollout_io* io, int32_t T,
                    uint32_t step_counter0, void* hip_stream);
 
+/* ---- rendering (DESIGN.md "Rendering") ----------------------------------------------------------------------------
+ * Ray-cast camera images of envs [env_begin, env_begin + env_count) from their current qpos, in two launches on hip_stream (a
+ * scene kernel: one lane per env; a pixel kernel: one workgroup per 1024 pixels of one env).  Reads the state matrix only: the
+ * simulation is not perturbed.  The first call (and a call with a larger env_count than any before) allocates the handle's scene
+ * buffer (112 floats per env); otherwise nothing is allocated and nothing synchronises.
+ * ref: MujocoEnv.render (rgb_array, envs/env_base_01.py:13-18, 48-49) and EndCamOffScreenViewer.render (envs/env_base_02.py:22-38). */
+#define SO100_CAM_END   0         /* the wrist camera end_point_camera (so_arm100_camera.xml:125): fovy 120, default 1080 x 1920, ROW 0 = BOTTOM */
+#define SO100_CAM_SCENE 1         /* MuJoCo's free camera of the reference's viewer: fovy 45, default 800 x 800, rows top-down */
+#define SO100_GEOM_FLOOR 1u       /* plane z = 0, checker (segmentation id 1)                                      */
+#define SO100_GEOM_CUBE  2u       /* the 2 cm cube (id 2)                                                          */
+#define SO100_GEOM_LINKS 4u       /* the five arm stand-in capsules of SO100_F_LINKS_FLOOR (ids 3..7)              */
+#define SO100_GEOM_PADS  8u       /* the 8 finger-pad boxes (ids 8..15); sky is id 0                               */
+typedef struct {
+    int32_t camera;               /* SO100_CAM_END or SO100_CAM_SCENE                                              */
+    int32_t width, height;        /* 1..4096 each                                                                  */
+    int32_t env_begin, env_count; /* a range inside [0, N)                                                         */
+    uint32_t geom_mask;           /* SO100_GEOM_* bits; 0 = the camera's default (end: floor | cube; scene: floor | cube | links) */
+    const float* free_cam;        /* HOST pointer or NULL (defaults): lookat[3], distance, azimuth_deg, elevation_deg, fovy_deg; scene camera only */
+    uint8_t* rgb_dev;             /* [env_count][height][width][3] or NULL                                         */
+    float*   depth_dev;           /* [env_count][height][width] camera-axis depth in metres (sky: 40) or NULL     */
+    uint8_t* seg_dev;             /* [env_count][height][width] segmentation id or NULL; at least one output is required */
+} so100_render_io;
+
+int  so100_render(so100_sim* sim, const so100_render_io* io, void* hip_stream);
+
 int  so100_abi_version(void);
 int  so100_obs_dim(int32_t env_kind);                     /* ref: env_base_01.py:63-75 (15), env_base_02.py:56-69 (8) */
 int  so100_num_state_fields(void);                        /* rows of the [field][N] state matrix */

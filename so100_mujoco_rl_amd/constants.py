@@ -11,6 +11,14 @@ REWARD_THRESHOLD = {1: 6000, 2: 8000, 3: 8000, 4: 8000, 5: 8000, 6: 8000}
 RENDER_FPS = 31                                          # ref: envs/env_base_01.py:32
 FRAME_SKIP = 16                                          # ref: envs/env_base_01.py:45
 
+# rendering (DESIGN.md "Rendering"); sizes are (width, height)
+END_CAMERA_SIZE = (1080, 1920)                           # ref: envs/env_base_02.py:22-23 (END_CAM_RES_WIDTH / _HEIGHT)
+SCENE_CAMERA_SIZE = (800, 800)                           # ref: envs/env_base_01.py:48-49 (MujocoEnv width / height)
+# MuJoCo free camera of the viewer: ref: envs/env_base_01.py:13-18 (distance, elevation, azimuth); lookat = <statistic center>
+# (envs/model/env01.xml:9); fovy = MuJoCo's default visual/global fovy
+SCENE_CAMERA = {"lookat": (0.0, 0.0, 0.1), "distance": 1.25, "azimuth": 45.0, "elevation": -25.0, "fovy": 45.0}
+OVERLAY_SIZE = (END_CAMERA_SIZE[0] // 4, END_CAMERA_SIZE[1] // 4)   # the wrist view pasted into Env03-05 frames: ref: envs/env_base_02.py:71-83
+
 JOINT_STEP_SCALE = 0.075                                 # ref: envs/utils.py:9
 REST_POSITION = [0.0, -3.141, 3.117, 1.0, 0.0, 0.0]      # ref: envs/utils.py:11
 START_POSITION = [0.0, -2.04, 1.19, 1.5, -1.58, 0.5]     # ref: envs/env03_v1.py:10

@@ -2,6 +2,7 @@
 // instantiations are compiled in so100_kind.hip (one object per env kind), this file only dispatches to them.
 #include "so100_kernels.hpp"
 #include "so100_balance.hpp"
+#include "so100_render.hpp"
 
 namespace so100 {
 extern template struct KindOps<1>; extern template struct KindOps<2>; extern template struct KindOps<3>;
@@ -36,6 +37,8 @@ struct so100_sim {
     float* state = nullptr;        // [SF_COUNT][N]
     float* start_tab = nullptr;    // [36][6]
     int32_t* slot_env = nullptr;   // [workgroups x epw] lane-slot map of the persistent rollout kernel (pad-contact variants; so100_balance.hpp)
+    float* render_scene = nullptr; // [envs][RS_STRIDE] scene records of so100_render (so100_render.hpp); allocated on first use, grown on demand
+    int render_scene_envs = 0;
 };
 
 namespace {
@@ -153,6 +156,7 @@ void so100_destroy(so100_sim* s) {
     if (s->state) (void)hipFree(s->state);
     if (s->start_tab) (void)hipFree(s->start_tab);
     if (s->slot_env) (void)hipFree(s->slot_env);
+    if (s->render_scene) (void)hipFree(s->render_scene);
     delete s;
 }
 
@@ -220,6 +224,54 @@ int so100_rollout(so100_sim* s, const so100_policy_weights* w, const so100_rollo
     }
     RolloutPtrs rp{ io->obs_dev, io->rew_dev, io->done_dev, io->trunc_dev, io->terminal_obs_dev, io->ep_return_dev, io->ep_length_dev };
     HIP_TRY(DISPATCH_KIND(s->cfg.env_kind, rollout)(s->prm, s->state, s->start_tab, rp, pw, ra, (hipStream_t)stream), SO100_E_LAUNCH);
+    return 0;
+}
+
+int so100_render(so100_sim* s, const so100_render_io* io, void* stream) {
+    if (!s || !io) return fail(SO100_E_INVALID, "so100_render: null argument%s");
+    if (io->camera != SO100_CAM_END && io->camera != SO100_CAM_SCENE)
+        return fail(SO100_E_INVALID, "so100_render: camera must be SO100_CAM_END (0) or SO100_CAM_SCENE (1), got %s%ld", "", (long)io->camera);
+    if (io->width < 1 || io->width > 4096) return fail(SO100_E_INVALID, "so100_render: width must be in 1..4096, got %s%ld", "", (long)io->width);
+    if (io->height < 1 || io->height > 4096) return fail(SO100_E_INVALID, "so100_render: height must be in 1..4096, got %s%ld", "", (long)io->height);
+    if (io->env_begin < 0 || io->env_begin >= s->prm.n) return fail(SO100_E_INVALID, "so100_render: env_begin must be in [0, N), got %s%ld", "", (long)io->env_begin);
+    if (io->env_count < 1 || io->env_count > s->prm.n - io->env_begin)
+        return fail(SO100_E_INVALID, "so100_render: env_count must be >= 1 with env_begin + env_count <= N, got %s%ld", "", (long)io->env_count);
+    if (io->geom_mask & ~(SO100_GEOM_FLOOR | SO100_GEOM_CUBE | SO100_GEOM_LINKS | SO100_GEOM_PADS))
+        return fail(SO100_E_INVALID, "so100_render: geom_mask has unknown bits (%s%ld)", "", (long)io->geom_mask);
+    if (!io->rgb_dev && !io->depth_dev && !io->seg_dev) return fail(SO100_E_INVALID, "so100_render: rgb_dev, depth_dev and seg_dev are all NULL%s");
+    if (io->free_cam && io->camera != SO100_CAM_SCENE) return fail(SO100_E_INVALID, "so100_render: free_cam is for the scene camera only%s");
+    RenderLaunch L;
+    L.camera = io->camera; L.W = io->width; L.H = io->height; L.begin = io->env_begin; L.count = io->env_count; L.n = s->prm.n;
+    L.mask = io->geom_mask != 0 ? io->geom_mask : (io->camera == SO100_CAM_END ? RG_DEFAULT_END : RG_DEFAULT_SCENE);
+    for (int i = 0; i < 3; i++) L.cam_p[i] = 0.0f;
+    for (int i = 0; i < 9; i++) L.cam_R[i] = 0.0f;
+    double fovy = RENDER_END_FOVY;
+    if (io->camera == SO100_CAM_SCENE) {
+        double lookat[3] = { RENDER_SCENE_LOOKAT[0], RENDER_SCENE_LOOKAT[1], RENDER_SCENE_LOOKAT[2] };
+        double dist = RENDER_SCENE_DISTANCE, az = RENDER_SCENE_AZIMUTH, el = RENDER_SCENE_ELEVATION;
+        fovy = RENDER_SCENE_FOVY;
+        if (const float* fc = io->free_cam) {
+            for (int i = 0; i < 7; i++) if (!std::isfinite(fc[i])) return fail(SO100_E_INVALID, "so100_render: free_cam[%s%ld] is not finite", "", (long)i);
+            if (!(fc[3] > 0.0f)) return fail(SO100_E_INVALID, "so100_render: free_cam distance must be > 0%s");
+            if (!(fc[6] > 0.0f && fc[6] < 180.0f)) return fail(SO100_E_INVALID, "so100_render: free_cam fovy_deg must be in (0, 180)%s");
+            lookat[0] = fc[0]; lookat[1] = fc[1]; lookat[2] = fc[2]; dist = fc[3]; az = fc[4]; el = fc[5]; fovy = fc[6];
+        }
+        double p[3], R[9];
+        free_camera_pose<double>(lookat, dist, az, el, p, R);
+        for (int i = 0; i < 3; i++) L.cam_p[i] = (float)p[i];
+        for (int i = 0; i < 9; i++) L.cam_R[i] = (float)R[i];
+    }
+    L.inv_f = (float)render_inv_focal(fovy, io->height);
+    DeviceGuard g(s->cfg.device);
+    if (!g.ok) return fail(SO100_E_NODEVICE, "so100_render: cannot select the device%s");
+    if (io->env_count > s->render_scene_envs) {
+        if (s->render_scene) { HIP_TRY(hipStreamSynchronize((hipStream_t)stream), SO100_E_LAUNCH); (void)hipFree(s->render_scene); s->render_scene = nullptr; }
+        s->render_scene_envs = 0;
+        const size_t bytes = (size_t)io->env_count*RS_STRIDE*sizeof(float);
+        if (hipMalloc(&s->render_scene, bytes) != hipSuccess) { s->render_scene = nullptr; return fail(SO100_E_NOMEM, "so100_render: hipMalloc of %s%ld bytes failed", "", (long)bytes); }
+        s->render_scene_envs = io->env_count;
+    }
+    HIP_TRY(render_launch(s->state, L, s->render_scene, io->rgb_dev, io->depth_dev, io->seg_dev, (hipStream_t)stream), SO100_E_LAUNCH);
     return 0;
 }
 

@@ -11,13 +11,15 @@ import torch
 
 from . import constants as K
 from .lib import F_REFERENCE
-from .vec_env import So100VecEnv, make_spaces
+from .vec_env import So100VecEnv, make_spaces, render_frames
 
 
 class So100Env:
-    metadata = {"render_modes": [], "render_fps": K.RENDER_FPS}
+    metadata = {"render_modes": ["rgb_array"], "render_fps": K.RENDER_FPS}
 
     def __init__(self, env_kind=1, device=None, flags=F_REFERENCE, seed=0, render_mode=None, max_episode_steps=None, **kwargs):
+        if render_mode not in (None, "rgb_array"):
+            raise ValueError(f"render_mode must be None or 'rgb_array', got {render_mode!r}")
         self.kind = env_kind
         self.observation_space, self.action_space = make_spaces(env_kind)
         # a one-env So100VecEnv underneath: its numpy round trip (pinned host buffers the step kernel reads / writes directly, one launch, one sync per step)
@@ -55,7 +57,12 @@ class So100Env:
         self._v.close()
 
     def render(self):
-        return None
+        """render_mode "rgb_array": host uint8 [800, 800, 3], the scene camera (ref: MujocoEnv.render with DEFAULT_CAMERA_CONFIG,
+        envs/env_base_01.py:13-18), with the wrist view in the bottom-left corner for Env03-05 (envs/env_base_02.py:71-83).
+        render_mode None: None."""
+        if self.render_mode != "rgb_array":
+            return None
+        return render_frames(self.sim, 1)[0]
 
 
 def _entry(kind):

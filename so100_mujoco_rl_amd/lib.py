@@ -11,6 +11,8 @@ import subprocess
 import numpy as np
 import torch  # imported BEFORE the .so so that both bind to the same libamdhip64 (see csrc/Makefile)
 
+from . import constants as K
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SO100_LIB", os.path.join(_HERE, "libso100sim.so"))   # SO100_LIB: A/B builds of the same ABI (tools/)
 
@@ -62,13 +64,24 @@ class RolloutIO(C.Structure):
                                           "ep_return_dev", "ep_length_dev", "terminal_obs_chunk_dev")]
 
 
+class RenderIO(C.Structure):
+    _fields_ = [("camera", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("env_begin", C.c_int32), ("env_count", C.c_int32),
+                ("geom_mask", C.c_uint32), ("free_cam", C.c_void_p), ("rgb_dev", C.c_void_p), ("depth_dev", C.c_void_p), ("seg_dev", C.c_void_p)]
+
+
+CAM_END, CAM_SCENE = 0, 1                       # include/so100_sim.h: SO100_CAM_*
+CAMERAS = {"end": CAM_END, "scene": CAM_SCENE}
+G_FLOOR, G_CUBE, G_LINKS, G_PADS = 1, 2, 4, 8   # SO100_GEOM_*: geometry bits of so100_render
+GEOM_NAMES = {"floor": G_FLOOR, "cube": G_CUBE, "links": G_LINKS, "pads": G_PADS}
+
+
 class PolicyIO(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("obs_dev", "noise_dev", "act_env_dev", "act_raw_dev", "value_dev", "logp_dev", "rollout_row_dev")]
 
 
 EXPORTS = ["so100_abi_version", "so100_obs_dim", "so100_num_state_fields", "so100_state_field_index", "so100_state_field_name", "so100_create",
            "so100_envs_per_workgroup", "so100_destroy", "so100_reset", "so100_step", "so100_get_state", "so100_set_state", "so100_get_field",
-           "so100_set_field", "so100_last_error", "so100_policy_forward", "so100_rollout"]
+           "so100_set_field", "so100_last_error", "so100_policy_forward", "so100_rollout", "so100_render"]
 
 
 def build(verbose=False):
@@ -107,6 +120,7 @@ def load():
         L.so100_set_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.so100_get_field.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
         L.so100_set_field.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+        L.so100_render.argtypes = [C.c_void_p, C.POINTER(RenderIO), C.c_void_p]
         if L.so100_abi_version() != ABI_VERSION:
             raise So100Error("libso100sim.so ABI version mismatch")
         _lib = L
@@ -265,6 +279,69 @@ class So100Sim:
                        self.done.data_ptr(), self.trunc.data_ptr(), self.terminal_obs.data_ptr(), self.ep_return.data_ptr(), self.ep_length.data_ptr(),
                        _ptr(terminal_obs_chunk, torch.float32, (T, self.n, self.obs_dim), self.device))
         _check(self.L.so100_rollout(self.h, C.byref(self._pw), C.byref(io), T, int(step_counter0) & 0xFFFFFFFF, self._stream()), "so100_rollout")
+
+    def render(self, camera="end", width=None, height=None, envs=None, geoms=None, rgb=True, depth=False, segmentation=False,
+               free_camera=None, out=None):
+        """Ray-cast camera images of the envs' current state on the GPU (two launches on the current stream; DESIGN.md "Rendering").
+
+        camera: "end" (the wrist camera end_point_camera, default 1080 x 1920, ROW 0 = BOTTOM of the view like the reference's
+        mjr_readPixels) or "scene" (the viewer's free camera, default 800 x 800, rows top-down like Gymnasium's rgb_array).
+        envs: None (all), a slice with step 1, or (begin, count).  geoms: None (the camera's default), an int of G_* bits or an
+        iterable of names from GEOM_NAMES.  free_camera (scene camera only): dict with any of lookat (3), distance, azimuth,
+        elevation, fovy (degrees).  out: a dict from an earlier call (same shapes) whose tensors are written in place -- the
+        pixel-observation loop allocates nothing per step.
+        Returns a dict of device tensors: "rgb" uint8 [count, H, W, 3], "depth" float32 [count, H, W] (camera-axis metres, sky 40),
+        "segmentation" uint8 [count, H, W] (0 sky, 1 floor, 2 cube, 3..7 arm capsules, 8..15 finger pads).
+        Memory: count * H * W * (3 rgb + 4 depth + 1 segmentation) bytes of output, plus a 448-byte scene record per env held by
+        the handle (e.g. 4096 envs x 84 x 84 rgb: 87 MB; one 1080 x 1920 wrist frame with all three: 16.6 MB)."""
+        if camera not in CAMERAS:
+            raise So100Error(f"camera must be one of {sorted(CAMERAS)}, got {camera!r}")
+        cam = CAMERAS[camera]
+        dw, dh = K.END_CAMERA_SIZE if cam == CAM_END else K.SCENE_CAMERA_SIZE
+        W, H = int(width or dw), int(height or dh)
+        if envs is None:
+            begin, count = 0, self.n
+        elif isinstance(envs, slice):
+            if envs.step not in (None, 1):
+                raise So100Error("envs: only slices with step 1")
+            begin, stop, _ = envs.indices(self.n)
+            count = stop - begin
+        else:
+            begin, count = (int(v) for v in envs)
+        if geoms is None:
+            mask = 0
+        elif isinstance(geoms, int):
+            mask = geoms
+        else:
+            mask = 0
+            for g in geoms:
+                if g not in GEOM_NAMES:
+                    raise So100Error(f"unknown geometry {g!r} (known: {sorted(GEOM_NAMES)})")
+                mask |= GEOM_NAMES[g]
+        fc = None
+        if free_camera is not None:
+            c = dict(K.SCENE_CAMERA)
+            unknown = set(free_camera) - set(c)
+            if unknown:
+                raise So100Error(f"free_camera: unknown keys {sorted(unknown)}")
+            c.update(free_camera)
+            fc = (C.c_float * 7)(*[float(v) for v in c["lookat"]], float(c["distance"]), float(c["azimuth"]), float(c["elevation"]), float(c["fovy"]))
+        want = {"rgb": (rgb, torch.uint8, (count, H, W, 3)), "depth": (depth, torch.float32, (count, H, W)),
+                "segmentation": (segmentation, torch.uint8, (count, H, W))}
+        res = {}
+        for k, (on, dt, shape) in want.items():
+            if not on:
+                continue
+            t = None if out is None else out.get(k)
+            if t is None:
+                t = torch.empty(shape, dtype=dt, device=self.device)
+            _ptr(t, dt, shape, self.device)
+            res[k] = t
+        io = RenderIO(cam, W, H, begin, count, mask, C.cast(fc, C.c_void_p) if fc is not None else None,
+                      res["rgb"].data_ptr() if "rgb" in res else None, res["depth"].data_ptr() if "depth" in res else None,
+                      res["segmentation"].data_ptr() if "segmentation" in res else None)
+        _check(self.L.so100_render(self.h, C.byref(io), self._stream()), "so100_render")
+        return res
 
     def get_state(self):
         qpos = torch.empty(13, self.n, dtype=torch.float32, device=self.device)

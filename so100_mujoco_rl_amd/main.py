@@ -2,14 +2,15 @@
 
     python -m so100_mujoco_rl_amd.main -a PPO [-m MODEL] train  -e Env01-v1 [--envs 4096] [--iters N]
     python -m so100_mujoco_rl_amd.main -a PPO [-m MODEL] test   -e Env01-v1 [--show-io] [--show-i]
-    python -m so100_mujoco_rl_amd.main -a PPO [-m MODEL] record -e Env01-v1
+    python -m so100_mujoco_rl_amd.main -a PPO [-m MODEL] record -e Env01-v1 [--steps 3000] [--video/--no-video]
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 -m so100_mujoco_rl_amd.main -a PPO train -e Env01-v1     # 8 x 4096 envs
 
 Same directory layout (models/ logs/ movies/), default model path models/{env}_{algo}/best_model.*, reward thresholds
 (6000 / 8000, ref: __init__.py:9,16) and checkpoint naming ({env}_{algo}_cp_*, ref: main.py:227-232).  Differences, all
 forced by the environment being a batched GPU simulator: N envs instead of 1; the learner is stable-baselines3 when it
 is importable and the built-in PPO (ppo.py) or DDPG (ddpg.py; ref: main.py:38-55), both with SB3-compatible state_dicts, otherwise; `record` writes a state trajectory
-(.npz) because there is no rasteriser (viewer / video are out of scope).
+(.npz) beside its video, which is a Motion-JPEG AVI (video.py) of the GPU ray caster's frames (DESIGN.md "Rendering") instead of
+VecVideoRecorder's MP4.
 """
 import logging
 import os
@@ -246,8 +247,8 @@ def _evaluate(eval_env, eval_col, learner):
     return float(ret.mean().item())
 
 
-def _rollout_policy(environment, algorithm, model_file, n, steps, show_io, show_i, record_path=None):
-    env = So100VecEnv(environment, n, flags=F_REFERENCE, seed=1)
+def _rollout_policy(environment, algorithm, model_file, n, steps, show_io, show_i, record_path=None, video_path=None):
+    env = So100VecEnv(environment, n, flags=F_REFERENCE, seed=1, render_mode="rgb_array" if video_path else None, render_envs=1)
     if model_file is None:
         model_file = _default_model_path(environment, algorithm)
     if not os.path.isfile(model_file):
@@ -262,8 +263,15 @@ def _rollout_policy(environment, algorithm, model_file, n, steps, show_io, show_
         act_fn = net.mean_action
     obs = env.reset_tensor()
     total = 0.0; traj = []
+    writer = None
+    if video_path is not None:                         # ref: main.py:151-171 (VecVideoRecorder: one frame of env 0 per step)
+        from .video import MjpegAviWriter
+        os.makedirs(os.path.dirname(video_path) or ".", exist_ok=True)
+        writer = MjpegAviWriter(video_path, *K.SCENE_CAMERA_SIZE, K.RENDER_FPS)
     with torch.no_grad():
         for t in range(steps):
+            if writer is not None:
+                writer.write(env.get_images()[0])
             a = act_fn(obs).clamp(-1, 1).contiguous()
             if (show_io or show_i) and t % 30 == 0:           # ref: main.py:110-113
                 logger.info(str(obs[0].tolist() + (a[0].tolist() if show_io else [])) + ("," if show_i else ""))
@@ -275,7 +283,10 @@ def _rollout_policy(environment, algorithm, model_file, n, steps, show_io, show_
     logger.info(f"mean reward/step over {steps} steps x {n} envs: {total/steps:+.4f}")
     if record_path is not None:
         np.savez(record_path, trajectory=np.stack(traj), layout="qpos[13] qvel[12] obs action[6] per step, env 0")
-        logger.info(f"wrote {record_path} (state trajectory; no rasteriser in this build)")
+        logger.info(f"wrote {record_path} (state trajectory)")
+    if writer is not None:
+        writer.close()
+        logger.info(f"wrote {video_path} ({writer.frames} frames, {K.SCENE_CAMERA_SIZE[0]} x {K.SCENE_CAMERA_SIZE[1]} Motion-JPEG at {K.RENDER_FPS} fps)")
     return total / steps
 
 
@@ -293,10 +304,14 @@ def test(ctx, environment, show_io, show_i, envs, steps):
 
 @cli.command(name="record", help="Record a model with a given environment")
 @click.option("-e", "--environment", required=True, type=str)
+@click.option("--steps", default=3000, type=int, help="steps to record (ref: main.py:151 video_length)")
+@click.option("--video/--no-video", default=True, help="also write movies/rec-<env>-step-0-to-step-<steps>.avi (Motion-JPEG)")
 @click.pass_context
-def record(ctx, environment):
+def record(ctx, environment, steps, video):
     path = os.path.join(RECORDING_DIR, f"{environment}_{ctx.obj['ALGORITHM_NAME']}.npz")
-    _rollout_policy(environment, ctx.obj["ALGORITHM_NAME"], ctx.obj["MODEL_PATH"], 1, 3000, False, False, record_path=path)   # 3000 steps, ref: main.py:161
+    # VecVideoRecorder's file name (name_prefix "rec-<env>", ref: main.py:154-160)
+    video_path = os.path.join(RECORDING_DIR, f"rec-{environment}-step-0-to-step-{steps}.avi") if video else None
+    _rollout_policy(environment, ctx.obj["ALGORITHM_NAME"], ctx.obj["MODEL_PATH"], 1, steps, False, False, record_path=path, video_path=video_path)
 
 
 if __name__ == "__main__":

@@ -65,16 +65,50 @@ def kind_from_id(env_id):
     raise KeyError(f"unknown env id {env_id!r}; known: {sorted(K.ENV_IDS.values())}")
 
 
+def tile_images(images):
+    """SB3's tile_images: N frames [h, w, c] -> one [ceil(sqrt N) h, ceil(N / ceil(sqrt N)) w, c] grid, row-major, zero-padded"""
+    img = np.asarray(images)
+    n, h, w, c = img.shape
+    rows = int(np.ceil(np.sqrt(n)))
+    cols = int(np.ceil(float(n) / rows))
+    img = np.concatenate([img, np.zeros((rows * cols - n, h, w, c), img.dtype)]) if rows * cols > n else img
+    return img.reshape(rows, cols, h, w, c).transpose(0, 2, 1, 3, 4).reshape(rows * h, cols * w, c)
+
+
+def render_frames(sim, count):
+    """host uint8 [count, 800, 800, 3]: the scene camera's frames of envs [0, count) -- what the reference's rgb_array render returns.
+    Env03-05 (ref: So100OffscreenBaseEnv) also paste the wrist view in: ref: envs/env_base_02.py:71-83 shrinks the 1080 x 1920
+    end-camera frame by 4, flips it to top-down and writes it to r[-h:, :w] -- the BOTTOM-LEFT corner (the comment there says
+    "bottom right").  Here the wrist view is rendered at 270 x 480 directly instead of resized."""
+    bufs = getattr(sim, "_frame_bufs", None)
+    if bufs is None or bufs[0]["rgb"].shape[0] != count:
+        bufs = sim._frame_bufs = ({}, {})
+    fr = sim.render("scene", envs=(0, count), out=bufs[0] or None)["rgb"]
+    bufs[0]["rgb"] = fr
+    if sim.kind in (3, 4, 5):
+        w, h = K.OVERLAY_SIZE
+        ov = sim.render("end", width=w, height=h, envs=(0, count), out=bufs[1] or None)["rgb"]
+        bufs[1]["rgb"] = ov
+        fr = fr.clone()
+        fr[:, -h:, :w] = ov.flip(1)
+    return fr.cpu().numpy()
+
+
 class So100VecEnv(_VecEnvBase):
-    metadata = {"render_modes": [], "render_fps": K.RENDER_FPS}
+    metadata = {"render_modes": ["rgb_array"], "render_fps": K.RENDER_FPS}
 
     def __init__(self, env_id="Env01-v1", num_envs=4096, device=None, flags=F_REFERENCE, seed=0, env_id_offset=0,
                  solver_iters=2, contact_iters=20, max_episode_steps=None, stagger_episodes=False, full_infos=False, use_graph=True,
-                 envs_per_workgroup=0):
+                 envs_per_workgroup=0, render_mode=None, render_envs=1):
         self.env_id = env_id
         self.kind = kind_from_id(env_id) if isinstance(env_id, str) else int(env_id)
+        if render_mode not in (None, "rgb_array"):
+            raise ValueError(f"render_mode must be None or 'rgb_array', got {render_mode!r}")
+        self.render_mode = render_mode
+        self.render_envs = max(0, min(int(render_envs), num_envs))     # envs [0, render_envs) are rendered by get_images() / render()
         obs_space, act_space = make_spaces(self.kind)
         _VecEnvBase.__init__(self, num_envs, obs_space, act_space)
+        self.render_mode = render_mode
         self.sim = So100Sim(self.kind, num_envs, device=device, flags=flags, solver_iters=solver_iters, contact_iters=contact_iters,
                             max_episode_steps=max_episode_steps, seed=seed, env_id_offset=env_id_offset,
                             envs_per_workgroup=envs_per_workgroup)      # 0 = automatic; pin it when shards of another batch size must agree bit for bit (DESIGN.md section 6)
@@ -177,10 +211,19 @@ class So100VecEnv(_VecEnvBase):
         return [False] * len(self._indices(indices))
 
     def get_images(self):
-        return [None] * self.num_envs
+        """rgb_array frames (host uint8 [800, 800, 3]) of envs < render_envs, None for the others (as SB3's vec envs do for envs
+        that do not render); all None without render_mode="rgb_array"."""
+        if self.render_mode != "rgb_array" or self.render_envs == 0:
+            return [None] * self.num_envs
+        fr = render_frames(self.sim, self.render_envs)
+        return [fr[i] for i in range(self.render_envs)] + [None] * (self.num_envs - self.render_envs)
 
     def render(self, mode=None):
-        return None                                     # rasteriser / viewer are out of scope
+        """the frames of get_images() tiled like SB3's VecEnv.render (tile_images); None without render_mode="rgb_array"."""
+        mode = mode or self.render_mode
+        if mode != "rgb_array" or self.render_mode != "rgb_array" or self.render_envs == 0:
+            return None
+        return tile_images([im for im in self.get_images() if im is not None])
 
     def _indices(self, indices):
         if indices is None:

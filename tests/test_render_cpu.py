@@ -1,0 +1,235 @@
+"""The render model on the CPU: the host instantiation of csrc/so100_render.hpp (tests/_rendercheck) against the NumPy fp64
+ray caster (tests/render_ref.py, poses from the oracle), the wrist camera against the reference's own projection
+(so100o_project_bbox), the scene camera's free-camera formula, and the Motion-JPEG AVI writer.  No GPU needed."""
+import ctypes as C
+import io
+import os
+import struct
+import subprocess
+
+import numpy as np
+import pytest
+
+import render_ref as RR
+from oracle import so100_oracle as O
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+JNT_RANGE = [(-2.2, 2.2), (-3.14158, 0.2), (0.0, 3.14158), (-2.0, 1.8), (-3.14158, 3.14158), (-0.2, 2.0)]
+# depth bound: the scene camera's pose is exact, the wrist camera's comes from fp32 FK (task_poses: 1e-7 m / 2e-7 rad off the
+# oracle), which grazing floor rays and 3 cm-near pads turn into up to 5e-5 relative depth (DESIGN.md "Rendering")
+DEPTH_RTOL = {RR.CAM_END: 1e-4, RR.CAM_SCENE: 1e-5}
+
+
+@pytest.fixture(scope="module")
+def H():
+    subprocess.check_call(["make", "-C", os.path.join(HERE, "_rendercheck"), "-s"])
+    h = C.CDLL(os.path.join(HERE, "_rendercheck", "librendercheck.so"))
+    h.rc_render.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    return h
+
+
+def host_render(H, qpos, camera, W, Hh, mask=0, free_cam=None):
+    """host instantiation: (rgb [n, H, W, 3], depth [n, H, W], seg [n, H, W]) of qpos [n, 13]"""
+    q = np.ascontiguousarray(np.asarray(qpos, np.float32).reshape(-1, 13))
+    n = q.shape[0]
+    rgb = np.zeros((n, Hh, W, 3), np.uint8); dep = np.zeros((n, Hh, W), np.float32); seg = np.zeros((n, Hh, W), np.uint8)
+    fc = None if free_cam is None else np.ascontiguousarray(free_cam, np.float32)
+    H.rc_render(q.ctypes.data, n, camera, W, Hh, mask, None if fc is None else fc.ctypes.data, rgb.ctypes.data, dep.ctypes.data, seg.ctypes.data, None)
+    return rgb, dep, seg
+
+
+def random_states(n, seed):
+    """joint angles uniform in jnt_range; even states: a resting cube, odd: a tilted cube in the air (fp32-representable)"""
+    rs = np.random.RandomState(seed)
+    out = np.zeros((n, 13))
+    for i in range(n):
+        out[i, :6] = [rs.uniform(a, b) for a, b in JNT_RANGE]
+        out[i, 6:9] = [rs.uniform(-0.3, 0.3), rs.uniform(-0.45, -0.15), 0.01]
+        out[i, 9] = 1.0
+        if i % 2:
+            out[i, 8] = rs.uniform(0.05, 0.3)
+            qq = rs.randn(4); out[i, 9:13] = qq / np.linalg.norm(qq)
+    return out.astype(np.float32).astype(np.float64)
+
+
+def compare(rgb, dep, seg, q, camera, W, Hh, mask, free_cam=None):
+    """the pass conditions against render_ref; returns a short failure string or None"""
+    r2, d2, s2 = RR.render(q, camera, W, Hh, mask, free_cam)
+    eq = seg == s2
+    if eq.mean() < 0.995:
+        return f"segmentation equal on {eq.mean():.4f} of the pixels"
+    bad = ~eq & ~RR.near_edge(s2.astype(np.int64))
+    if bad.any():
+        return f"{int(bad.sum())} segmentation mismatches away from an edge"
+    drel = np.abs(dep[eq].astype(np.float64) - d2[eq]) / d2[eq]
+    if drel.max() > DEPTH_RTOL[camera]:
+        return f"depth off by {drel.max():.2e} relative"
+    # a checker square's edge is an edge of the image too (floor pixels whose 8-neighbourhood spans two squares)
+    par = RR.checker_parity(q, camera, W, Hh, free_cam)
+    ok = eq & ~RR.near_edge(np.where(s2 == 1, par, -2))
+    dr = np.abs(rgb.astype(np.int64) - r2.astype(np.int64)).max(-1)[ok]
+    if dr.size and dr.max() > 1:
+        return f"rgb off by {dr.max()} LSB"
+    return None
+
+
+@pytest.mark.parametrize("camera", [RR.CAM_END, RR.CAM_SCENE])
+def test_host_matches_numpy_reference(H, camera):
+    states = random_states(50, 11 + camera)
+    sizes = [(64, 48), (96, 160), (83, 61)]
+    masks = [1, 2, 4, 8, 15]
+    fails = []
+    for i, q in enumerate(states):
+        W, Hh = sizes[i % 3]
+        for mask in masks if i < 12 else [masks[i % 5]]:
+            rgb, dep, seg = host_render(H, q, camera, W, Hh, mask)
+            f = compare(rgb[0], dep[0], seg[0], q, camera, W, Hh, mask)
+            if f:
+                fails.append((i, W, Hh, mask, f))
+    assert not fails, fails[:5]
+
+
+def test_every_geometry_shows_up(H):
+    """the comparison above is not vacuous: over the states, sky, floor, cube, every arm capsule and finger pads all appear (the
+    pads are 2 mm thick: at 64 x 48 not every one of them covers a pixel centre)"""
+    seen = set()
+    for q in random_states(50, 11):
+        for cam in (RR.CAM_END, RR.CAM_SCENE):
+            seen |= set(np.unique(host_render(H, q, cam, 64, 48, 15)[2]).tolist())
+    assert set(range(0, 8)) <= seen and len(seen & set(range(8, 16))) >= 2, sorted(seen)
+
+
+def _bbox_states(n):
+    """Env03-like poses whose 8 cube corners all project into the 1080 x 1920 wrist frame (so100o_project on every corner)"""
+    L = O.lib()
+    rs = np.random.RandomState(5)
+    out = []
+    while len(out) < n:
+        q = np.zeros(13)
+        q[:6] = np.array([0.0, -2.04, 1.19, 1.5, -1.58, 0.5]) + rs.uniform(-0.25, 0.25, 6)   # ref: env03_v1.py:10 START_POSITION
+        q[6:9] = [rs.uniform(-0.1, 0.1), rs.uniform(-0.4, -0.25), 0.01]
+        q[9] = 1.0
+        q = q.astype(np.float32).astype(np.float64)
+        d = RR.kinematics(q)
+        cp, cm = (C.c_double * 3)(*d.cam_xpos), (C.c_double * 9)(*d.cam_xmat)
+        ok = True
+        for k in range(8):
+            c = (C.c_double * 3)(*[q[6 + a] + (0.01 if (k >> (2 - a)) & 1 else -0.01) for a in range(3)])
+            uv = (C.c_int * 2)()
+            ok &= bool(L.so100o_project(cp, cm, c, uv))
+        if ok:
+            out.append(q)
+    return out
+
+
+def test_wrist_camera_matches_the_reference_projection(H):
+    """seg == cube's bounding box at 1080 x 1920 against so100o_project_bbox (env_base_02.py:129-176).  project() maps a point at
+    continuous pixel coordinate u to 1080 - int(1080 - u) = ceil(u), so its box edges lie 0 or 1 px beyond the half-open pixel range
+    [first, last + 1) of the rendered silhouette -- on both axes.  A flipped row order or a mirrored column order would be far off."""
+    L = O.lib()
+    for q in _bbox_states(4):
+        _, _, seg = host_render(H, q, RR.CAM_END, 1080, 1920, RR.G_FLOOR | RR.G_CUBE)
+        ys, xs = np.nonzero(seg[0] == 2)
+        assert xs.size > 50
+        d = RR.kinematics(q)
+        box = (C.c_int * 4)()
+        assert L.so100o_project_bbox((C.c_double * 3)(*d.cam_xpos), (C.c_double * 9)(*d.cam_xmat), (C.c_double * 3)(*q[6:9]), box)
+        got = np.array([xs.min(), ys.min(), xs.max() + 1, ys.max() + 1])
+        diff = np.array(box[:]) - got
+        assert np.all((diff >= 0) & (diff <= 1)), (list(box), got.tolist())
+
+
+def _centroid(seg):
+    ys, xs = np.nonzero(seg == 2)
+    return xs.mean() + 0.5, ys.mean() + 0.5
+
+
+def _expected_pixel(p, fc, W, Hh):
+    o, R = RR.free_camera(fc[:3], fc[3], fc[4], fc[5])
+    x, y, z = (np.asarray(p) - o) @ R
+    f = 0.5 * Hh / np.tan(np.radians(fc[6]) / 2)
+    return W / 2 + f * x / -z, Hh / 2 - f * y / -z
+
+
+def test_scene_camera_lookat_and_overrides(H):
+    W, Hh = 201, 151
+    q = np.zeros(13); q[:6] = [0.0, -3.141, 3.117, 1.0, 0.0, 0.0]; q[9] = 1.0           # arm at rest (ref: utils.py:11)
+    # the default camera looks at (0, 0, 0.1): a cube there lands on the image centre
+    q[6:9] = [0.0, 0.0, 0.1]
+    cx, cy = _centroid(host_render(H, q, RR.CAM_SCENE, W, Hh, RR.G_CUBE)[2][0])
+    assert abs(cx - W / 2) < 0.5 and abs(cy - Hh / 2) < 0.5, (cx, cy)
+    # overrides move a fixed world point to where the free-camera formula puts it
+    p = [0.05, -0.3, 0.02]
+    q[6:9] = p
+    for fc in ([0.0, -0.2, 0.05, 0.9, 30.0, -40.0, 45.0], [0.1, -0.3, 0.0, 0.6, 120.0, -20.0, 60.0], [0.0, 0.0, 0.1, 1.6, -60.0, -60.0, 45.0]):
+        seg = host_render(H, q, RR.CAM_SCENE, W, Hh, RR.G_CUBE, free_cam=fc)[2][0]
+        ex, ey = _expected_pixel(p, fc, W, Hh)
+        cx, cy = _centroid(seg)
+        assert abs(cx - ex) < 1.0 and abs(cy - ey) < 1.0, (fc, (cx, cy), (ex, ey))
+
+
+def test_scene_camera_overrides_match_reference(H):
+    q = random_states(1, 3)[0]
+    fc = [0.05, -0.25, 0.05, 0.8, 100.0, -35.0, 50.0]
+    rgb, dep, seg = host_render(H, q, RR.CAM_SCENE, 96, 80, 15, free_cam=fc)
+    assert compare(rgb[0], dep[0], seg[0], q, RR.CAM_SCENE, 96, 80, 15, fc) is None
+
+
+def _parse_avi(path):
+    data = open(path, "rb").read()
+    assert data[:4] == b"RIFF" and data[8:12] == b"AVI " and struct.unpack("<I", data[4:8])[0] == len(data) - 8
+    chunks = {}
+    frames = []
+    idx = []
+    movi = None
+
+    def walk(lo, hi):
+        nonlocal movi
+        p = lo
+        while p < hi:
+            cid, size = struct.unpack("<4sI", data[p:p + 8])
+            if cid == b"LIST":
+                kind = data[p + 8:p + 12]
+                if kind == b"movi":
+                    movi = p + 8
+                walk(p + 12, p + 8 + size)
+            elif cid == b"00dc":
+                frames.append(data[p + 8:p + 8 + size])
+            elif cid == b"idx1":
+                for k in range(size // 16):
+                    idx.append(struct.unpack("<4sIII", data[p + 8 + 16 * k:p + 24 + 16 * k]))
+            else:
+                chunks[cid] = data[p + 8:p + 8 + size]
+            p += 8 + size + (size & 1)
+    walk(12, len(data))
+    return chunks, frames, idx, movi, data
+
+
+def test_mjpeg_avi_round_trip(tmp_path):
+    from PIL import Image
+    from so100_mujoco_rl_amd.video import MjpegAviWriter
+    W, Hh, n = 96, 64, 5
+    yy, xx = np.mgrid[0:Hh, 0:W]
+    frames = [np.stack([xx * 2 + 10 * i, yy * 3, np.full_like(xx, 40 * i)], -1).astype(np.uint8) for i in range(n)]
+    path = str(tmp_path / "v.avi")
+    w = MjpegAviWriter(path, W, Hh, 31)
+    for f in frames:
+        w.write(f)
+    w.close()
+    chunks, data_frames, idx, movi, raw = _parse_avi(path)
+    us, _, _, flags, total, _, streams, _, aw, ah = struct.unpack("<10I", chunks[b"avih"][:40])
+    assert us == round(1e6 / 31) and total == n and streams == 1 and (aw, ah) == (W, Hh) and flags & 0x10
+    fcc_type, handler = struct.unpack("<4s4s", chunks[b"strh"][:8])
+    assert fcc_type == b"vids" and handler == b"MJPG"
+    scale, rate, _, length = struct.unpack("<4I", chunks[b"strh"][20:36])
+    assert rate / scale == 31 and length == n
+    assert struct.unpack("<Iii", chunks[b"strf"][:12]) == (40, W, Hh)
+    assert len(idx) == n and len(data_frames) == n
+    for (cid, fl, off, size), jpg, ref in zip(idx, data_frames, frames):
+        assert cid == b"00dc" and fl & 0x10
+        assert raw[movi + off:movi + off + 4] == b"00dc" and struct.unpack("<I", raw[movi + off + 4:movi + off + 8])[0] == size
+        im = np.asarray(Image.open(io.BytesIO(jpg)).convert("RGB"))
+        assert im.shape == (Hh, W, 3)
+        assert np.abs(im.astype(np.float64) - ref).mean() < 3.0
+    with pytest.raises(ValueError):
+        MjpegAviWriter(str(tmp_path / "x.avi"), W, Hh, 31).write(np.zeros((Hh, W + 1, 3), np.uint8))
