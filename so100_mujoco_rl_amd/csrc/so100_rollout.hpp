@@ -279,7 +279,7 @@ __device__ __forceinline__ void physics_phase_mw(const SimParams& p, int wave, i
         __syncthreads();
         SO100_PROF(5);                                     // barrier 2 wait
         // ---- second half: solves
-        float cal[3], caa[3], acc0[6]; ArmRows<float> r0;
+        float cal[3], caa[3], acc0[6]; ArmRows<float> r0; float pgs_res = 0.0f;
         if (wave == 2 && cube_in_step) { cube_solve<float>(cb, p.flags, p.contact_iters, cprep, cal, caa); SO100_PROF(6); }   // Newton behind the arm's solve
         if (wave == 0) {
 #pragma unroll
@@ -288,9 +288,8 @@ __device__ __forceinline__ void physics_phase_mw(const SimParams& p, int wave, i
             arm_tau<float>(e.q, e.v, ctrl, A, tau);
             if ((p.flags & (F_FRICTIONLOSS | F_LIMITS)) != 0u) {
                 arm_rows<float>(e.q, e.v, tau, e.ff, e.fl, p.flags, A, r0);
-                float res;
-                arm_pgs<float>(e.ff, e.fl, p.solver_iters, A, r0, acc0, res);
-                e.res = tmax(e.res, res);
+                arm_pgs<float>(e.ff, e.fl, p.solver_iters, A, r0, acc0, pgs_res);
+                if (!pads) e.res = tmax(e.res, pgs_res);   // with pads: after barrier 3, only if no contact Newton replaced this solve
             } else {
                 if (pads) arm_row_consts<float>(e.q, e.v, p.flags, r0);
 #pragma unroll
@@ -361,13 +360,16 @@ __device__ __forceinline__ void physics_phase_mw(const SimParams& p, int wave, i
                     for (int i = 0; i < 6; i++) acc0[i] = xa[i][lane];
                     arm_row_forces<float>(r0, acc0, e.ff, e.fl);          // the block PGS's warm-start memory for when the contact is gone
                     e.res = tmax(e.res, xa[13][lane]);
+                } else {
+                    e.res = tmax(e.res, pgs_res);            // (the host / one-wave substep_with_pads reports the same residual)
                 }
 #pragma unroll
                 for (int i = 0; i < 6; i++) { e.aw[i] = acc0[i]; xk[6 + i][lane] = acc0[i]; }      // the next substep's Newton warm start (read after its first barrier)
                 const int n0 = e.cstat & 255, dr = (e.cstat >> 8) + (code >> 16);
                 e.cstat = (nc > n0 ? nc : n0) | ((dr > 0xFFFF ? 0xFFFF : dr) << 8);
                 e.csig = nc > 0 ? __float_as_int(xa[14][lane]) : 0;
-                e.cload += nc > 0 ? 1 << 16 : 0;               // this launch's contact substeps ride in the upper half until the launch folds them in
+                if (nc > 0 && (unsigned)e.cload < (CLOAD_MAX << 16))       // this launch's contact substeps ride in the upper half until the
+                    e.cload = (int)((unsigned)e.cload + (1u << 16));         // launch folds them in; saturated at CLOAD_MAX, below the sign bit
             }
             arm_integrate<float>(e.q, e.v, e.qc, acc0, dq);
         }
@@ -798,7 +800,10 @@ __global__ void __launch_bounds__(64*NW) so100_rollout_fused(SimParams p, float*
         if (wave == 3) prof_.flush_wg(wave, lane, e3, (lane % np) == 0 && e3 < p.n); else prof_.flush_wg(wave, lane, env, live);
     }
     if (wave == 0 && live) {
-        if constexpr (PADS) e.cload = ((e.cload & 0xFFFF) + (e.cload >> 16)) >> 1;       // contact load: average of its history and this launch's count
+        if constexpr (PADS) {                              // contact load: average of its history and this launch's count, both <= CLOAD_MAX
+            const unsigned hist = (unsigned)e.cload & 0xFFFFu, now = (unsigned)e.cload >> 16;
+            e.cload = (int)(((hist < CLOAD_MAX ? hist : CLOAD_MAX) + (now < CLOAD_MAX ? now : CLOAD_MAX)) >> 1);
+        }
         store_env_state<KIND, FL>(state, p.n, env, e);
         if (ra.T > 0) {
 #pragma unroll

@@ -33,6 +33,9 @@ struct SimParams {
 enum : int { B_HAS_PREV = 1, B_HAVE_BLOCK = 2, B_HAVE_LAST_BLOCK = 4, B_HAVE_CENTER = 8, B_HAVE_ANGVEL = 16,
              B_BLOCK_UPDATED = 32, B_ANTIGRAV = 64, B_BAD_STATE = 128 /* latched: a non-finite state ended an episode */,
              B_BAD_ACTION = 256 /* this step's action was non-finite (consumed by env_step_finish) */ };
+// EnvState::cload: the persistent rollout kernel counts a launch's contact substeps in the upper 16 bits and saturates that count here,
+// below the sign bit (T x frame_skip is unbounded); the fold at the launch's end keeps the stored load in [0, CLOAD_MAX]
+constexpr unsigned CLOAD_MAX = 0x7FFFu;
 
 struct EnvState {
     float q[6];                 // arm joint angles                      (qpos[0:6])

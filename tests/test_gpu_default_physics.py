@@ -15,6 +15,7 @@ pytestmark = pytest.mark.gpu
 
 import substep_harness as SH                              # noqa: E402
 from oracle import so100_oracle as O                      # noqa: E402  (the checker)
+from test_substep_parity import SHIPPED                   # noqa: E402  ((solver_iters, contact_iters): the shipped (2, 20) and (4, 30))
 
 REFP = O.F_REFERENCE
 C5 = O.F_CONTACT5
@@ -39,17 +40,30 @@ def _start(env, col, qpos, qvel, kind):
 
 
 PROXIES = O.F_LINKS_FLOOR | O.F_LINKS_CUBE                 # every capsule proxy pair: the run-time-flags kernels so100_rollout_fused / so100_step_mw<K, -1>
+# per-case bounds where the measurement is worse than the shared one (test_default_rollout_kernel_vs_stepwise_and_oracle)
+TIGHT_SHARE = {(2, C5): 0.985}                             # persistent vs stepwise rows within 1e-5: measured 0.995
+ORACLE_MISSES = {(1, REFP): 42}                            # oracle rows outside 2e-5 (contact events a substep apart): measured 14 of 480
 
 
 @pytest.mark.parametrize("kind,flags", [(1, REFP), (2, C5), (5, REFP), (6, REFP), (3, REFP), (1, REFP | PROXIES), (2, C5 | PROXIES)])
 def test_default_rollout_kernel_vs_stepwise_and_oracle(kind, flags):
+    _default_rollout_kernel_vs_stepwise_and_oracle(kind, flags, (4, 30))
+
+
+@pytest.mark.parametrize("kind,flags", [(1, REFP), (2, C5), (5, REFP), (6, REFP), (3, REFP), (1, REFP | PROXIES), (2, C5 | PROXIES)])
+def test_default_rollout_kernel_vs_stepwise_and_oracle_at_shipped_settings(kind, flags):
+    """test_default_rollout_kernel_vs_stepwise_and_oracle at the shipped solver settings (solver_iters, contact_iters) = SHIPPED = (2, 20), with the same bounds"""
+    _default_rollout_kernel_vs_stepwise_and_oracle(kind, flags, SHIPPED)
+
+
+def _default_rollout_kernel_vs_stepwise_and_oracle(kind, flags, iters):
     from so100_mujoco_rl_amd.vec_env import So100VecEnv
     from so100_mujoco_rl_amd.collector import RolloutCollector
     n, T, T2, tl = 200, 10, 5, 12                            # tail workgroup partially filled; a second, shorter chunk; TimeLimit hits inside it
     qpos, qvel = _contact_rich_state(n, flags, 10 + kind)
     runs = []
     for persistent in (True, False):
-        env = So100VecEnv(kind, n, flags=flags, seed=4, max_episode_steps=tl, solver_iters=4, contact_iters=30)
+        env = So100VecEnv(kind, n, flags=flags, seed=4, max_episode_steps=tl, solver_iters=iters[0], contact_iters=iters[1])
         sd = RolloutCollector.random_policy_state(env.sim.obs_dim, env.device, seed=2)
         sd["action_net.bias"][1] = 0.5                       # shoulder down: the pads stay on / are pressed into the table
         if flags & O.F_PADS_CUBE:
@@ -95,13 +109,15 @@ def test_default_rollout_kernel_vs_stepwise_and_oracle(kind, flags):
             else:
                 classes["fail"] += 1
     touched = float(((acs & 255) > 0).float().mean())
-    print(f"[default rollout kernel, kind {kind} flags {flags}] persistent vs stepwise: {tight:.3f} of rows within 1e-5, {loose:.3f} within 2e-2; "
+    print(f"[default rollout kernel, kind {kind} flags {flags} iters {iters}] persistent vs stepwise: {tight:.3f} of rows within 1e-5, {loose:.3f} within 2e-2; "
           f"vs oracle ({len(sample)} envs x {T} steps): {classes}, median err {np.median(errs):.2e}; envs with a pad contact in step 10 {touched:.2f}")
     assert torch.isfinite(a["obs"]).all() and torch.isfinite(a["rewards"]).all() and torch.isfinite(aq).all() and torch.isfinite(av).all()
     assert touched > 0.2                                     # the contact path really ran
     assert (acs >> 8).max() == 0 and (scs >> 8).max() == 0   # nothing over the contact budget
-    assert loose == 1.0 and tight > 0.5
-    assert classes["fail"] == 0 and classes["tight"] >= 0.5*len(errs) and np.median(errs) < 2e-5
+    # measured on MI355X at both solver settings: every row of the two kernels within 1e-5 (kind 2 with F_CONTACT5: 0.995); 0 of 480 oracle
+    # rows outside the tight class (kind 1 with F_REFERENCE: 14).  Bounds: 3x the measured misses
+    assert loose == 1.0 and tight >= TIGHT_SHARE.get((kind, flags), 0.99)
+    assert classes["fail"] == 0 and classes["tight"] >= len(errs) - ORACLE_MISSES.get((kind, flags), 15) and np.median(errs) < 2e-5
 
 
 def test_contact5_determinism_and_shard_invariance_4096():
@@ -168,6 +184,65 @@ def test_workgroup_balancing_leaves_every_result_bit_identical():
         for k in ("obs", "actions", "rewards", "dones", "values", "log_probs", "last_obs"):
             assert torch.equal(a[k], b[k]), k
     assert torch.equal(qa, qb) and torch.equal(va, vb) and torch.equal(csa, csb) and torch.equal(la, lb)
+
+
+CLOAD_MAX = 0x7FFF          # csrc/so100_task.hpp: the per-launch contact-substep count saturates below the sign bit
+
+
+def _switch_policy(od, dev):
+    """shoulder pushed down (a1 = +0.5) where the shoulder angle obs[1] > -1.7, pushed back (-0.5) to its -pi limit where it is below; no
+    noise.  One saturated tanh unit per layer makes the switch, so one policy keeps pressed arms on the table and parked arms off it"""
+    sd = {k: torch.zeros(*sh, device=dev) for k, sh in (("pi_w0", (64, od)), ("pi_b0", (64,)), ("pi_w1", (64, 64)), ("pi_b1", (64,)),
+          ("mu_w", (6, 64)), ("mu_b", (6,)), ("vf_w0", (64, od)), ("vf_b0", (64,)), ("vf_w1", (64, 64)), ("vf_b1", (64,)), ("v_w", (1, 64)), ("v_b", (1,)))}
+    sd["pi_w0"][0, 1] = 50.0; sd["pi_b0"][0] = 50.0*1.7; sd["pi_w1"][0, 0] = 5.0; sd["mu_w"][1, 0] = 0.5
+    sd["log_std"] = torch.full((6,), -30.0, device=dev)
+    return sd
+
+
+def test_contact_load_saturates_over_long_launches():
+    """so100_rollout counts a launch's contact substeps in the upper half of the contact_load row: with T x frame_skip >= 32768 a resting
+    contact used to run into the sign bit (undefined behaviour; the fold then stored a negative load).  64 envs x 32 steps x 1024 substeps
+    = 32768 per launch, two launches: every load stays in [0, CLOAD_MAX]; arms parked off the table read 0, arms pressed onto it > 0; the
+    workgroup balancing dealt from those loads changes no result bit (SO100_BALANCE=0 run)."""
+    import os
+    from so100_mujoco_rl_amd.lib import So100Sim
+    n, T, fs = 64, 32, 1024
+    qf, vf, _ = SH.floor_batch(192, 3)
+    keep = np.nonzero(qf[:, 1] > -1.5)[0][:n//2]                   # pressed arms: shoulder well above the policy's switch at -1.7
+    assert len(keep) == n//2
+    qpos = np.zeros((n, 13), np.float32); qvel = np.zeros((n, 12), np.float32)
+    qpos[1::2] = qf[keep]; qvel[1::2] = vf[keep]
+    qpos[::2] = qf[keep]; qpos[::2, :6] = [0.0, -1.9, 1.6, 0.3, 1.5708, 0.1]                 # parked: folded up, pushed back to the shoulder limit
+    outs = []
+    for bal in ("1", "0"):
+        os.environ["SO100_BALANCE"] = bal
+        try:
+            sim = So100Sim(1, n, flags=REFP, frame_skip=fs, max_episode_steps=0, seed=8)
+        finally:
+            del os.environ["SO100_BALANCE"]
+        sim.reset()
+        sim.set_state(torch.from_numpy(np.ascontiguousarray(qpos.T)).cuda(), torch.from_numpy(np.ascontiguousarray(qvel.T)).cuda())
+        sim.obs[:, :6] = torch.from_numpy(np.ascontiguousarray(qpos[:, :6])).cuda()     # the first policy step reads the injected angles
+        sim.set_policy({k: v.contiguous() for k, v in _switch_policy(sim.obs_dim, sim.device).items()})
+        buf = torch.zeros(T, n, sim.obs_dim + 10, device=sim.device)
+        loads, bufs = [], []
+        for launch in range(2):
+            sim.rollout(buf, launch*T)
+            loads.append(sim.get_field("contact_load", dtype=torch.int32).cpu().numpy())
+            bufs.append(buf.clone())
+        q, v = sim.get_state()
+        outs.append((loads, bufs, q.clone(), v.clone()))
+        sim.close()
+    (la, ba, qa, va), (lb, bb, qb, vb) = outs
+    for k, ld in enumerate(la):
+        print(f"[contact_load, launch {k + 1} of {T} x {fs} substeps] pressed: min {ld[1::2].min()} max {ld[1::2].max()}; parked: max {ld[::2].max()}")
+        assert ld.min() >= 0 and ld.max() <= CLOAD_MAX
+        assert (ld[::2] == 0).all() and (ld[1::2] > 0).all()
+    assert ld[1::2].max() > CLOAD_MAX//2                         # resting contacts: the second launch's count reached the saturation
+    for a, b in zip(la + ba, lb + bb):
+        assert np.array_equal(a, b) if isinstance(a, np.ndarray) else torch.equal(a, b)
+    assert torch.equal(qa, qb) and torch.equal(va, vb)
+    assert torch.isfinite(qa).all() and torch.isfinite(va).all()
 
 
 def test_link_proxies_keep_the_arm_above_the_table_on_the_gpu():

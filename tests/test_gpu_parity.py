@@ -31,12 +31,15 @@ ARM = O.F_FRICTIONLOSS | O.F_LIMITS | O.F_CUBE_PINNED
 FREE = O.F_CUBE_PINNED
 
 
-def _run_pair(kind, flags, n, steps, seed, action_scale=1.0, solver_iters=4, contact_iters=6, max_steps=0, inject=True):
+def _run_pair(kind, flags, n, steps, seed, action_scale=1.0, solver_iters=4, contact_iters=6, max_steps=0, inject=True, pad_iters=None):
     """Step n envs on the GPU and in the oracle with identical actions / uniforms; yield per-step results.
-    Oracle solver: PGS on the dual to 1e-15 -- or its primal Newton when pad rows are simulated (PGS needs ~1e4 sweeps on them)."""
+    Oracle solver: PGS on the dual to 1e-15 -- or its primal Newton when pad rows are simulated (PGS needs ~1e4 sweeps on them).
+    pad_iters: (solver_iters, contact_iters) when pad rows are simulated (default: solver_iters, 30)."""
     rs = np.random.RandomState(seed)
     pads = (flags & (O.F_PADS_FLOOR | O.F_PADS_CUBE)) != 0
-    sim = _sim(kind, n, flags=flags, solver_iters=solver_iters, contact_iters=30 if pads else contact_iters, max_episode_steps=max_steps, seed=seed)
+    if pads:
+        solver_iters, contact_iters = pad_iters or (solver_iters, 30)
+    sim = _sim(kind, n, flags=flags, solver_iters=solver_iters, contact_iters=contact_iters, max_episode_steps=max_steps, seed=seed)
     orc = [O.OracleEnv(kind, flags=flags, iters=-1 if pads else 0, seed=seed, env_id=i) for i in range(n)]
     for e in orc:
         e.e.max_episode_steps = max_steps
@@ -125,11 +128,21 @@ def test_env06_vs_oracle_with_gripper_term():
 
 @pytest.mark.parametrize("kind,flags", [(5, NOPADS), (3, NOPADS), (4, NOPADS), (5, REFP), (3, REFP), (4, REFP)])
 def test_lookat_envs_vs_oracle(kind, flags):
+    _lookat_envs_vs_oracle(kind, flags, None)
+
+
+@pytest.mark.parametrize("kind", [5, 3, 4])
+def test_lookat_envs_with_pads_vs_oracle_at_shipped_settings(kind):
+    """the REFP cases of test_lookat_envs_vs_oracle at the shipped solver settings (solver_iters, contact_iters) = (2, 20), same bounds"""
+    _lookat_envs_vs_oracle(kind, REFP, (2, 20))
+
+
+def _lookat_envs_vs_oracle(kind, flags, pad_iters):
     """REFP = the default physics of So100VecEnv / main.py for these kinds (so100_step_mw<K, 23>): the look-at arms stay above the
     table, so the pad narrowphase runs and finds nothing -- the results must be the NOPADS ones to the same tolerance"""
     n, steps = 64, 60
     n_px = n_px_bad = 0
-    for t, sim, orc, og, oo, rew, done, trunc, _ in _run_pair(kind, flags, n, steps, seed=20 + kind, action_scale=0.6):
+    for t, sim, orc, og, oo, rew, done, trunc, _ in _run_pair(kind, flags, n, steps, seed=20 + kind, action_scale=0.6, pad_iters=pad_iters):
         np.testing.assert_allclose(og[:, :6], oo[:, :6], rtol=0, atol=1e-6)
         d = np.abs(og[:, 6:] - oo[:, 6:])
         n_px += d.size; n_px_bad += int((d > 1e-4).sum())
@@ -382,9 +395,12 @@ def test_policy_kernel_vs_torch(kind):
     act_env = torch.zeros(n, 6, device="cuda"); act_raw = torch.zeros_like(act_env)
     value = torch.zeros(n, device="cuda"); logp = torch.zeros(n, device="cuda"); row = torch.zeros(n, od + 10, device="cuda")
     sim.policy_forward(obs, act_env, 0, noise=noise, act_raw=act_raw, value=value, logp=logp, rollout_row=row)
-    a, v, lp = _torch_policy(t, obs, noise)
-    # tolerance: fp32 accumulation order + exp2-based tanh (abs err < 2e-7 per activation)
-    assert (act_raw - a).abs().max() < 2e-5 and (value - v).abs().max() < 2e-5 and (logp - lp).abs().max() < 2e-5
+    a, v, lp = _torch_policy({k: w.double() for k, w in t.items()}, obs.double(), noise.double())      # float64 reference
+    ea, ev, el = [float((x.double() - y).abs().max()) for x, y in ((act_raw, a), (value, v), (logp, lp))]
+    print(f"[policy kernel vs fp64, obs width {od}] action {ea:.2e} value {ev:.2e} log-prob {el:.2e}")
+    # tolerance: fp32 accumulation order + exp2-based tanh (abs err < 2e-7 per activation); measured on MI355X against fp64:
+    # action 1.1e-6, value 1.5e-6, log-prob 1.8e-6 (obs width 15 and 8)
+    assert ea < 6e-6 and ev < 6e-6 and el < 6e-6
     assert torch.equal(act_env, act_raw.clamp(-1, 1))
     assert torch.equal(row[:, :od], obs) and torch.equal(row[:, od:od + 6], act_raw)
     assert torch.equal(row[:, od + 8], value) and torch.equal(row[:, od + 9], logp)

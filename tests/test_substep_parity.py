@@ -2,11 +2,16 @@
 substep_with_pads) against the fp64 oracle -- every env, every substep, no survivor filter (tests/substep_harness.py).  The
 same harness drives the HIP kernels through the C ABI in tests/test_gpu_substep_parity.py.
 
-Stated fp32 bound on h * qacc (the velocity change of one substep, h = 2 ms) from IDENTICAL fp32-rounded states:
-  * env-substeps without pad contact:   2e-6 rad/s  (dual block PGS, 4 sweeps; measured 5e-7)
+Every test runs at the shipped solver settings SHIPPED = (solver_iters, contact_iters) = (2, 20) -- what So100Sim, So100VecEnv and
+bench.py use -- and at (4, 30).  Stated fp32 bound on h * qacc (the velocity change of one substep, h = 2 ms) from IDENTICAL
+fp32-rounded states, the same at both settings:
+  * env-substeps without pad contact:   2e-6 rad/s  (dual block PGS, 2 or 4 sweeps; measured 5e-7 at both; 1 sweep: 9e-5)
   * env-substeps with pad contact:      5e-5 rad/s (m/s for the cube) and 1e-2 of |h qacc| + 1e-3 -- the pad rows are stiff (1/R ~ 3e3
     against M ~ 0.1, condition ~1e5), so fp32 carries 3-4 significant digits of a contact force (measured: 5e-6 pad/floor,
     1.6e-5 in the coupled grasp, relative 3e-3).
+Solver residual: < 1e-2 on contact substeps at both settings.  On contact-free substeps at 2 sweeps the residual row is the change of
+the last sweep, not the distance from the converged solve (pad/floor: 0.1 % of them above 1e-2, p99 6e-8): those envs are held to the
+2e-6 bound against the oracle AND against a 64-sweep solve from the same state (tests/substep_harness.py).
 "parity unpinned (physics)": the oracle restates MuJoCo's published algorithm; MuJoCo itself is not available."""
 import ctypes as C
 import os
@@ -31,35 +36,65 @@ def P(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+SHIPPED = (2, 20)                                         # (solver_iters, contact_iters): lib.So100Sim, vec_env.So100VecEnv, bench.py
+
+
 class HostDevice:
     """one fp32 substep of the device code per env; warm starts (friction / limit forces, previous acceleration, cube block)
     carried from substep to substep like the state rows of the handle"""
-    def __init__(self, H, n, flags):
+    def __init__(self, H, n, flags, iters=(4, 30)):
         self.H, self.flags = H, flags
+        self.solver_iters, self.contact_iters = iters
         self.warm = np.zeros((n, 49))
+
+    def _substep(self, st, q, act, solver_iters):
+        ctrl = (q[:6].astype(np.float32) + act.astype(np.float32)*SH.JS).astype(np.float64)
+        stat = np.zeros(5, np.int32); ap = np.zeros(3)
+        self.H.hc_csub_f(P(st), P(ctrl), P(ap), self.flags, solver_iters, self.contact_iters, 1, P(stat))
+        return stat
 
     def __call__(self, q32, v32, act):
         n = len(q32)
         gq = np.zeros((n, 13)); gv = np.zeros((n, 12)); cnt = np.zeros(n, np.int64); sig = np.zeros(n, np.int64); res = np.zeros(n)
-        ap = np.zeros(3)
+        self.before = []
         for i in range(n):
             st = self.warm[i]
             st[:6] = q32[i, :6]; st[6:12] = v32[i, :6]; st[30:33] = q32[i, 6:9]; st[33:37] = q32[i, 9:13]; st[37:43] = v32[i, 6:12]
-            ctrl = (q32[i, :6].astype(np.float32) + act[i].astype(np.float32)*SH.JS).astype(np.float64)
-            stat = np.zeros(5, np.int32)
-            self.H.hc_csub_f(P(st), P(ctrl), P(ap), self.flags, 4, 30, 1, P(stat))
+            self.before.append((st.copy(), q32[i].copy(), act[i].copy()))
+            stat = self._substep(st, q32[i], act[i], self.solver_iters)
             gq[i, :6] = st[:6]; gq[i, 6:9] = st[30:33]; gq[i, 9:13] = st[33:37]; gv[i, :6] = st[6:12]; gv[i, 6:12] = st[37:43]
             cnt[i] = stat[0]; sig[i] = stat[4]; res[i] = stat[3]*1e-9
         return gq, gv, cnt, sig, res
 
+    def resolve(self, envs, iters):
+        """the last substep of `envs` again, from the same state and warm starts, with `iters` block-PGS sweeps"""
+        gv = np.zeros((len(envs), 12))
+        for k, i in enumerate(envs):
+            st, q, a = self.before[i]
+            st = st.copy()
+            self._substep(st, q, a, iters)
+            gv[k, :6] = st[6:12]; gv[k, 6:12] = st[37:43]
+        return gv
 
-def _check(T, n_pairs_min_contact, coupled_min=0):
+
+def _check(T, n_pairs_min_contact, coupled_min=0, iters=(4, 30)):
     assert T.contact >= n_pairs_min_contact and T.coupled >= coupled_min          # the batch did exercise the contact path
     assert T.knife <= 0.02*T.pairs                                                 # poses decided inside fp32 round-off are rare
     assert T.count_mismatch == 0 and T.set_mismatch == 0
     assert T.worst_dv < 2e-6
     assert T.worst_dv_contact < 5e-5 and T.worst_rel < 1e-2
-    assert T.worst_res < 1e-2
+    check_residual(T, iters)
+
+
+def check_residual(T, iters):
+    """(4, 30): every residual < 1e-2.  2 sweeps: the Newton's residual < 1e-2 on contact substeps; a contact-free residual above 1e-2 is
+    the last sweep's change (stale), so those envs must match the oracle AND a 64-sweep solve from the same state within the free bound"""
+    assert T.worst_res_contact < 1e-2
+    if iters[0] >= 4:
+        assert T.worst_res < 1e-2
+    else:
+        assert T.resolved == T.stale
+        assert T.worst_dv_stale < 2e-6 and T.worst_dv_resolved < 2e-6
 
 
 def test_feature_signature_matches_the_oracle_ids(H):
@@ -72,17 +107,35 @@ def test_feature_signature_matches_the_oracle_ids(H):
 
 
 def test_pad_floor_per_substep_host_fp32(H):
+    _pad_floor_per_substep_host_fp32(H, (4, 30))
+
+
+def test_pad_floor_per_substep_host_fp32_at_shipped_settings(H):
+    """test_pad_floor_per_substep_host_fp32 at the shipped solver settings (solver_iters, contact_iters) = SHIPPED = (2, 20), with the same bounds"""
+    _pad_floor_per_substep_host_fp32(H, SHIPPED)
+
+
+def _pad_floor_per_substep_host_fp32(H, iters):
     n = 64
     qpos, qvel, act = SH.floor_batch(n, 0)
-    T = SH.run_substep_parity(HostDevice(H, n, O.F_REFERENCE), qpos, qvel, act, O.F_REFERENCE, 32, "host fp32, pad/floor")
-    _check(T, n_pairs_min_contact=n*32//3)
+    T = SH.run_substep_parity(HostDevice(H, n, O.F_REFERENCE, iters), qpos, qvel, act, O.F_REFERENCE, 32, f"host fp32 {iters}, pad/floor")
+    _check(T, n_pairs_min_contact=n*32//3, iters=iters)
 
 
 def test_pad_cube_grasp_per_substep_host_fp32(H):
+    _pad_cube_grasp_per_substep_host_fp32(H, (4, 30))
+
+
+def test_pad_cube_grasp_per_substep_host_fp32_at_shipped_settings(H):
+    """test_pad_cube_grasp_per_substep_host_fp32 at the shipped solver settings (solver_iters, contact_iters) = SHIPPED = (2, 20), with the same bounds"""
+    _pad_cube_grasp_per_substep_host_fp32(H, SHIPPED)
+
+
+def _pad_cube_grasp_per_substep_host_fp32(H, iters):
     n = 32
     qpos, qvel, act = SH.grasp_batch(n, 1)
-    T = SH.run_substep_parity(HostDevice(H, n, O.F_CONTACT5), qpos, qvel, act, O.F_CONTACT5, 48, "host fp32, grasp")
-    _check(T, n_pairs_min_contact=n*48//3, coupled_min=n*48//4)
+    T = SH.run_substep_parity(HostDevice(H, n, O.F_CONTACT5, iters), qpos, qvel, act, O.F_CONTACT5, 48, f"host fp32 {iters}, grasp")
+    _check(T, n_pairs_min_contact=n*48//3, coupled_min=n*48//4, iters=iters)
 
 
 # ---- link proxies (SO100_F_LINKS_FLOOR: stand-in capsules for the arm's collision meshes, contacts on ANY link) ---------------
@@ -101,20 +154,38 @@ def wrist_first_batch(n, seed):
 
 
 def test_link_proxies_per_substep_host_fp32(H):
+    _link_proxies_per_substep_host_fp32(H, (4, 30))
+
+
+def test_link_proxies_per_substep_host_fp32_at_shipped_settings(H):
+    """test_link_proxies_per_substep_host_fp32 at the shipped solver settings (solver_iters, contact_iters) = SHIPPED = (2, 20), with the same bounds"""
+    _link_proxies_per_substep_host_fp32(H, SHIPPED)
+
+
+def _link_proxies_per_substep_host_fp32(H, iters):
     n = 48
     qpos, qvel, act = wrist_first_batch(n, 0)
-    T = SH.run_substep_parity(HostDevice(H, n, LINKS), qpos, qvel, act, LINKS, 32, "host fp32, link proxies, wrist first")
-    _check(T, n_pairs_min_contact=n*32//3)
+    T = SH.run_substep_parity(HostDevice(H, n, LINKS, iters), qpos, qvel, act, LINKS, 32, f"host fp32 {iters}, link proxies, wrist first")
+    _check(T, n_pairs_min_contact=n*32//3, iters=iters)
     qpos, qvel, act = SH.floor_batch(n, 0)                    # pads AND proxies on the table
-    T = SH.run_substep_parity(HostDevice(H, n, LINKS), qpos, qvel, act, LINKS, 24, "host fp32, link proxies + pads")
-    _check(T, n_pairs_min_contact=n*24//2)
+    T = SH.run_substep_parity(HostDevice(H, n, LINKS, iters), qpos, qvel, act, LINKS, 24, f"host fp32 {iters}, link proxies + pads")
+    _check(T, n_pairs_min_contact=n*24//2, iters=iters)
 
 
 def test_link_proxies_with_the_coupled_grasp_per_substep_host_fp32(H):
+    _link_proxies_with_the_coupled_grasp_per_substep_host_fp32(H, (4, 30))
+
+
+def test_link_proxies_with_the_coupled_grasp_per_substep_host_fp32_at_shipped_settings(H):
+    """test_link_proxies_with_the_coupled_grasp_per_substep_host_fp32 at the shipped solver settings (solver_iters, contact_iters) = SHIPPED = (2, 20), with the same bounds"""
+    _link_proxies_with_the_coupled_grasp_per_substep_host_fp32(H, SHIPPED)
+
+
+def _link_proxies_with_the_coupled_grasp_per_substep_host_fp32(H, iters):
     n, flags = 24, LINKS | O.F_PADS_CUBE
     qpos, qvel, act = SH.grasp_batch(n, 1)
-    T = SH.run_substep_parity(HostDevice(H, n, flags), qpos, qvel, act, flags, 40, "host fp32, link proxies + grasp")
-    _check(T, n_pairs_min_contact=n*40//4, coupled_min=n*40//5)
+    T = SH.run_substep_parity(HostDevice(H, n, flags, iters), qpos, qvel, act, flags, 40, f"host fp32 {iters}, link proxies + grasp")
+    _check(T, n_pairs_min_contact=n*40//4, coupled_min=n*40//5, iters=iters)
 
 
 # ---- link proxies against the cube (SO100_F_LINKS_CUBE: Rotation_Pitch / Upper_Arm vs block_a, SURVEY.md Q7) ---------------------------
@@ -134,11 +205,20 @@ def link_cube_batch(n, seed):
 
 
 def test_link_cube_per_substep_host_fp32(H):
+    _link_cube_per_substep_host_fp32(H, (4, 30))
+
+
+def test_link_cube_per_substep_host_fp32_at_shipped_settings(H):
+    """test_link_cube_per_substep_host_fp32 at the shipped solver settings (solver_iters, contact_iters) = SHIPPED = (2, 20), with the same bounds"""
+    _link_cube_per_substep_host_fp32(H, SHIPPED)
+
+
+def _link_cube_per_substep_host_fp32(H, iters):
     n = 32
     qpos, qvel, act = link_cube_batch(n, 0)
-    T = SH.run_substep_parity(HostDevice(H, n, LCUBE), qpos, qvel, act, LCUBE, 12, "host fp32, link proxies vs cube")
-    _check(T, n_pairs_min_contact=n*12//3, coupled_min=n*12//3)
+    T = SH.run_substep_parity(HostDevice(H, n, LCUBE, iters), qpos, qvel, act, LCUBE, 12, f"host fp32 {iters}, link proxies vs cube")
+    _check(T, n_pairs_min_contact=n*12//3, coupled_min=n*12//3, iters=iters)
     flags = LCUBE | O.F_PADS_CUBE                            # the closing-jaw grasp with every proxy pair switched on as well
     qpos, qvel, act = SH.grasp_batch(16, 2)
-    T = SH.run_substep_parity(HostDevice(H, 16, flags), qpos, qvel, act, flags, 32, "host fp32, all proxies + grasp")
-    _check(T, n_pairs_min_contact=16*32//4, coupled_min=16*32//5)
+    T = SH.run_substep_parity(HostDevice(H, 16, flags, iters), qpos, qvel, act, flags, 32, f"host fp32 {iters}, all proxies + grasp")
+    _check(T, n_pairs_min_contact=16*32//4, coupled_min=16*32//5, iters=iters)
