@@ -85,8 +85,8 @@ __global__ void __launch_bounds__(WG, ((FL == (int)SO100_F_CUBE_PINNED && reach_
     for (int i = 0; i < OD; i++) io.obs[(size_t)env*OD + i] = obs[i];
     io.rew[env] = r.reward;
     if (io.rollout_row) {
-        io.rollout_row[(size_t)env*(OD + 10) + OD + 6] = r.reward;
-        io.rollout_row[(size_t)env*(OD + 10) + OD + 7] = r.done ? (r.trunc_only ? 2.0f : 1.0f) : 0.0f;
+        io.rollout_row[(size_t)env*(OD + ROW_EXTRA) + OD + ROW_REWARD] = r.reward;
+        io.rollout_row[(size_t)env*(OD + ROW_EXTRA) + OD + ROW_DONE] = done_code(r.done, r.trunc_only);
     }
     io.done[env] = r.done ? 1 : 0;
     io.trunc[env] = r.trunc_only ? 1 : 0;
@@ -156,8 +156,8 @@ __global__ void __launch_bounds__(256) so100_step_mw(SimParams p, StepPtrs io) {
     for (int i = 0; i < OD; i++) io.obs[(size_t)env*OD + i] = obs[i];
     io.rew[env] = r.reward;
     if (io.rollout_row) {
-        io.rollout_row[(size_t)env*(OD + 10) + OD + 6] = r.reward;
-        io.rollout_row[(size_t)env*(OD + 10) + OD + 7] = r.done ? (r.trunc_only ? 2.0f : 1.0f) : 0.0f;
+        io.rollout_row[(size_t)env*(OD + ROW_EXTRA) + OD + ROW_REWARD] = r.reward;
+        io.rollout_row[(size_t)env*(OD + ROW_EXTRA) + OD + ROW_DONE] = done_code(r.done, r.trunc_only);
     }
     io.done[env] = r.done ? 1 : 0;
     io.trunc[env] = r.trunc_only ? 1 : 0;
@@ -210,11 +210,9 @@ __global__ void __launch_bounds__(WG) so100_init_state(int n, float* state) {
 // for measurements).  The 4-wave kernel so100_step_mw splits one env step over 4 waves: lowest latency, and it wins while the batch
 // leaves SIMDs idle (256 CUs x 64 envs = 16384).  Beyond that the one-wave kernel so100_step_fused has the higher throughput -- for the
 // contact variants too, although they carry 1.0-1.5 KB of scratch per lane there and so100_step_mw<K, 23 | 55> none: measured at 32 768 ...
-// 262 144 envs (profiles/r03_large_batch_dispatch.txt) the 4-wave kernel ties at 32 768 and loses 2x from 65 536 on, for every flag set.
-// One threshold for all; the two names are kept so that a future contact kernel can move its own.
+// 262 144 envs (profiles/r03_large_batch_dispatch.txt) the 4-wave kernel ties at 32 768 and loses 2x from 65 536 on, for every flag set:
+// one threshold for all.
 constexpr int MW_MAX_ENVS = 16384;
-constexpr int MW_MAX_ENVS_PADS = 16384;
-inline int mw_max_envs_for(unsigned flags) { return (flags & (SO100_F_PADS_FLOOR | SO100_F_PADS_CUBE | SO100_F_LINKS_FLOOR | SO100_F_LINKS_CUBE)) ? MW_MAX_ENVS_PADS : MW_MAX_ENVS; }
 inline dim3 grid_for(int n) { return dim3((unsigned)((n + WG - 1)/WG)); }
 
 struct RolloutPtrs { float* obs; float* rew; uint8_t* done; uint8_t* trunc; float* tobs; float* ep_ret; int32_t* ep_len; };

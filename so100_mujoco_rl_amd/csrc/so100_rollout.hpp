@@ -125,6 +125,26 @@ struct PhaseLds { float (*xq)[64]; float (*xc)[64]; float (*xb)[64]; float* cbuf
 // (physics_substeps): zones = the arm rows' zones of the last contact solve (-1: none yet), prev_n = length of the (id | mask) list in L.pbuf
 struct ContactMemo { int zones = -1, prev_n = 0; };
 
+// xc [24][64]: the cube's hand-over image between wave 0 (env state), wave 2 (steps it) and the contact wave (reads pose and velocity), one
+// column per env.  Rows: pos (3) | quat (4) | vel (6) | warm (6) | anti-gravity force | position the LAST substep started from (3, Q1: stale xpos).
+constexpr int XC_POS = 0, XC_QUAT = 3, XC_VEL = 7, XC_WARM = 13, XC_ANTIGRAV = 19, XC_STALE = 20;
+__device__ __forceinline__ void cube_to_lds(float (*xc)[64], int col, const Cube<float>& c) {
+#pragma unroll
+    for (int i = 0; i < 3; i++) xc[XC_POS + i][col] = c.pos[i];
+#pragma unroll
+    for (int i = 0; i < 4; i++) xc[XC_QUAT + i][col] = c.quat[i];
+#pragma unroll
+    for (int i = 0; i < 6; i++) { xc[XC_VEL + i][col] = c.vel[i]; xc[XC_WARM + i][col] = c.warm[i]; }
+}
+__device__ __forceinline__ void cube_from_lds(float (*xc)[64], int col, Cube<float>& c) {
+#pragma unroll
+    for (int i = 0; i < 3; i++) c.pos[i] = xc[XC_POS + i][col];
+#pragma unroll
+    for (int i = 0; i < 4; i++) c.quat[i] = xc[XC_QUAT + i][col];
+#pragma unroll
+    for (int i = 0; i < 6; i++) { c.vel[i] = xc[XC_VEL + i][col]; c.warm[i] = xc[XC_WARM + i][col]; }
+}
+
 // Register pressure.  The kernel is ONE control-flow graph: whatever another wave will read later (wave 0's env state `e`, its
 // mass-matrix factor A, wave 2's cube block) is live across the contact wave's Newton as far as the register allocator can
 // tell, although those registers hold nothing on wave 3.  After its solve the contact wave therefore overwrites all of it
@@ -157,23 +177,13 @@ __device__ __forceinline__ void physics_phase_mw(const SimParams& p, int wave, i
     }
     if (cube_live) {
         if (wave == 0) {
-#pragma unroll
-            for (int i = 0; i < 3; i++) xc[i][lane] = e.cube.pos[i];
-#pragma unroll
-            for (int i = 0; i < 4; i++) xc[3 + i][lane] = e.cube.quat[i];
-#pragma unroll
-            for (int i = 0; i < 6; i++) { xc[7 + i][lane] = e.cube.vel[i]; xc[13 + i][lane] = e.cube.warm[i]; }
-            xc[19][lane] = (e.bits & B_ANTIGRAV) ? (float)(so100g::CUBE_MASS*so100g::GRAVITY) : 0.0f;
+            cube_to_lds(xc, lane, e.cube);
+            xc[XC_ANTIGRAV][lane] = (e.bits & B_ANTIGRAV) ? (float)(so100g::CUBE_MASS*so100g::GRAVITY) : 0.0f;
         }
         __syncthreads();
         if (wave == 2) {
-#pragma unroll
-            for (int i = 0; i < 3; i++) cb.pos[i] = xc[i][lane];
-#pragma unroll
-            for (int i = 0; i < 4; i++) cb.quat[i] = xc[3 + i][lane];
-#pragma unroll
-            for (int i = 0; i < 6; i++) { cb.vel[i] = xc[7 + i][lane]; cb.warm[i] = xc[13 + i][lane]; }
-            applied[2] = xc[19][lane];
+            cube_from_lds(xc, lane, cb);
+            applied[2] = xc[XC_ANTIGRAV][lane];
         }
     } else {
         if (wave == 0) { cstale[0] = e.cube.pos[0]; cstale[1] = e.cube.pos[1]; cstale[2] = e.cube.pos[2]; }      // kinematic cube
@@ -183,7 +193,6 @@ __device__ __forceinline__ void physics_phase_mw(const SimParams& p, int wave, i
     // (Tried: letting wave 2 run the cube's 16 substeps back to back ahead of the arm when no pad can touch it.  A workgroup
     // barrier needs every wave, so the others simply waited for it at the first one: 72 -> 101 us per step.  The cube stays in
     // step with the arm: detection + row set-up in the first half-substep, Newton in the second.)
-    const bool cube_in_step = cube_live;
 #pragma unroll 1
     for (int sub = 0; sub < p.frame_skip; sub++) {
         if (wave == 0) {
@@ -197,14 +206,7 @@ __device__ __forceinline__ void physics_phase_mw(const SimParams& p, int wave, i
             }
             SO100_PROF(2);                                 // trig (wave 0)
         }
-        if (padcube && wave == 2 && sub > 0) {             // the cube's pose for this substep's narrowphase / coupled solve
-#pragma unroll
-            for (int i = 0; i < 3; i++) xc[i][lane] = cb.pos[i];
-#pragma unroll
-            for (int i = 0; i < 4; i++) xc[3 + i][lane] = cb.quat[i];
-#pragma unroll
-            for (int i = 0; i < 6; i++) { xc[7 + i][lane] = cb.vel[i]; xc[13 + i][lane] = cb.warm[i]; }
-        }
+        if (padcube && wave == 2 && sub > 0) cube_to_lds(xc, lane, cb);       // the cube's pose for this substep's narrowphase / coupled solve
         __syncthreads();
         SO100_PROF(3);                                     // barrier 1 wait
         after_first_barrier(sub);
@@ -240,8 +242,8 @@ __device__ __forceinline__ void physics_phase_mw(const SimParams& p, int wave, i
             }
             arm_factor<float>(p.flags, A);          // everything that needs only M happens before the barrier
             SO100_PROF(4);                                 // CRBA + factor (wave 0)
-        } else if (wave == 2 && cube_in_step) {
-            if (sub == p.frame_skip - 1) { xc[20][lane] = cb.pos[0]; xc[21][lane] = cb.pos[1]; xc[22][lane] = cb.pos[2]; }   // stale xpos (Q1)
+        } else if (wave == 2 && cube_live) {
+            if (sub == p.frame_skip - 1) { xc[XC_STALE][lane] = cb.pos[0]; xc[XC_STALE + 1][lane] = cb.pos[1]; xc[XC_STALE + 2][lane] = cb.pos[2]; }   // stale xpos (Q1)
             cube_prepare<float>(cb, applied, p.flags, cprep);           // contact detection + row setup ...
             SO100_PROF(4);                                 // cube_prepare (wave 2)
         } else if (wave == 3 && pads) {
@@ -257,10 +259,10 @@ __device__ __forceinline__ void physics_phase_mw(const SimParams& p, int wave, i
             for (int i = 0; i < 6; i++) c3b.vel[i] = 0.0f;
             if (padcube) {
 #pragma unroll
-                for (int i = 0; i < 3; i++) { c3b.pos[i] = xc[i][el]; cpos3[i] = c3b.pos[i]; }
-                float qn[4] = { xc[3][el], xc[4][el], xc[5][el], xc[6][el] };
+                for (int i = 0; i < 3; i++) { c3b.pos[i] = xc[XC_POS + i][el]; cpos3[i] = c3b.pos[i]; }
+                float qn[4] = { xc[XC_QUAT][el], xc[XC_QUAT + 1][el], xc[XC_QUAT + 2][el], xc[XC_QUAT + 3][el] };
 #pragma unroll
-                for (int i = 0; i < 6; i++) c3b.vel[i] = xc[7 + i][el];
+                for (int i = 0; i < 6; i++) c3b.vel[i] = xc[XC_VEL + i][el];
                 quat_normalize(qn); quat_to_mat(qn, Rc3);
             }
             coupled3 = detect_pad_contacts<float>(W3, v3, c3b, Rc3, p.flags, padcube, cs3);
@@ -280,7 +282,7 @@ __device__ __forceinline__ void physics_phase_mw(const SimParams& p, int wave, i
         SO100_PROF(5);                                     // barrier 2 wait
         // ---- second half: solves
         float cal[3], caa[3], acc0[6]; ArmRows<float> r0; float pgs_res = 0.0f;
-        if (wave == 2 && cube_in_step) { cube_solve<float>(cb, p.flags, p.contact_iters, cprep, cal, caa); SO100_PROF(6); }   // Newton behind the arm's solve
+        if (wave == 2 && cube_live) { cube_solve<float>(cb, p.flags, p.contact_iters, cprep, cal, caa); SO100_PROF(6); }   // Newton behind the arm's solve
         if (wave == 0) {
 #pragma unroll
             for (int i = 0; i < 6; i++) A.bias[i] = xb[i][lane];
@@ -316,8 +318,8 @@ __device__ __forceinline__ void physics_phase_mw(const SimParams& p, int wave, i
                 }
                 if (padcube) {
 #pragma unroll
-                    for (int i = 0; i < 3; i++) cpos3[i] = xc[i][el];
-                    float qn[4] = { xc[3][el], xc[4][el], xc[5][el], xc[6][el] };
+                    for (int i = 0; i < 3; i++) cpos3[i] = xc[XC_POS + i][el];
+                    float qn[4] = { xc[XC_QUAT][el], xc[XC_QUAT + 1][el], xc[XC_QUAT + 2][el], xc[XC_QUAT + 3][el] };
                     quat_normalize(qn); quat_to_mat(qn, Rc3);
                 }
 #pragma unroll
@@ -328,8 +330,8 @@ __device__ __forceinline__ void physics_phase_mw(const SimParams& p, int wave, i
                 arm_row_consts_from<float>(v3, p.flags, sD3, clv3, r3);
                 if (coupled3) {
 #pragma unroll
-                    for (int i = 0; i < 6; i++) cwarm[i] = xc[13 + i][el];
-                    ap3[2] = xc[19][el];
+                    for (int i = 0; i < 6; i++) cwarm[i] = xc[XC_WARM + i][el];
+                    ap3[2] = xc[XC_ANTIGRAV][el];
                 }
                 SO100_PROF(11);                                // contact solve set-up (wave 3)
                 const float res = contact_solve<LINKS>(tau3, r3, A3.M, W3, cs3, coupled3, cpos3, cwarm, Rc3, ap3, p.contact_iters, x3, xcube, &memo.zones, SO100_PROF_WORK);
@@ -373,7 +375,7 @@ __device__ __forceinline__ void physics_phase_mw(const SimParams& p, int wave, i
             }
             arm_integrate<float>(e.q, e.v, e.qc, acc0, dq);
         }
-        if (wave == 2 && cube_in_step) {
+        if (wave == 2 && cube_live) {
             if (padcube && (__float_as_int(xa[12][lane]) & 256) != 0) {      // arm and cube were solved together on the contact wave
 #pragma unroll
                 for (int i = 0; i < 3; i++) { cal[i] = xa[6 + i][lane]; caa[i] = xa[9 + i][lane]; cb.warm[i] = cal[i] - cprep.a0[i]; cb.warm[3 + i] = caa[i]; }
@@ -383,22 +385,15 @@ __device__ __forceinline__ void physics_phase_mw(const SimParams& p, int wave, i
         SO100_PROF(9);                                     // integrate
     }
     if (cube_live) {
-        if (wave == 2) {
-#pragma unroll
-            for (int i = 0; i < 3; i++) xc[i][lane] = cb.pos[i];
-#pragma unroll
-            for (int i = 0; i < 4; i++) xc[3 + i][lane] = cb.quat[i];
-#pragma unroll
-            for (int i = 0; i < 6; i++) { xc[7 + i][lane] = cb.vel[i]; xc[13 + i][lane] = cb.warm[i]; }
-        }
+        if (wave == 2) cube_to_lds(xc, lane, cb);
         __syncthreads();
         if (wave == 0) {
 #pragma unroll
-            for (int i = 0; i < 3; i++) { e.cube.pos[i] = xc[i][lane]; cstale[i] = xc[20 + i][lane]; }
+            for (int i = 0; i < 3; i++) { e.cube.pos[i] = xc[XC_POS + i][lane]; cstale[i] = xc[XC_STALE + i][lane]; }
 #pragma unroll
-            for (int i = 0; i < 4; i++) e.cube.quat[i] = xc[3 + i][lane];
+            for (int i = 0; i < 4; i++) e.cube.quat[i] = xc[XC_QUAT + i][lane];
 #pragma unroll
-            for (int i = 0; i < 6; i++) { e.cube.vel[i] = xc[7 + i][lane]; e.cube.warm[i] = xc[13 + i][lane]; }
+            for (int i = 0; i < 6; i++) { e.cube.vel[i] = xc[XC_VEL + i][lane]; e.cube.warm[i] = xc[XC_WARM + i][lane]; }
         }
     }
 }
@@ -406,16 +401,16 @@ __device__ __forceinline__ void physics_phase_mw(const SimParams& p, int wave, i
 // ---------------------------------------------------------------------------------------------------------------
 // Stand-alone policy forward on the matrix cores (the policy phase of the rollout kernel as its own launch): each
 // workgroup (4 waves) keeps its weight fragments in registers and walks over tiles of 64 envs (grid-stride), so the
-// weights are fetched once per workgroup, not once per 64 envs.  Same arithmetic as so100_rollout_fused's policy phase.
-// Replaces the VALU kernel so100_policy_forward_kernel as what so100_policy_forward launches (1 M envs: 961 -> see
-// profiles/): the VALU kernel re-staged 43 KB of weights per 64 envs and ran the 2 x 64 x (OD + 64) products at VALU rate.
+// weights are fetched once per workgroup, not once per 64 envs.  Same arithmetic as so100_rollout_fused's policy phase; this kernel
+// takes a tile's observations from HBM and the noise injected or drawn on the spot, and writes to the PolicyIO arrays.  It is what
+// so100_policy_forward launches: the step-wise collector's policy step.
 // ---------------------------------------------------------------------------------------------------------------
 template <int OD>
 __global__ void __launch_bounds__(256, 2) so100_policy_forward_mfma(int n, PolicyWeights w, PolicyIO io, uint32_t seed_lo, uint32_t seed_hi,
                                                                  uint32_t env_id_offset, uint32_t step_counter) {
-    constexpr int ODP = (OD + 3) & ~3;
-    constexpr int LD = 65;
-    __shared__ __attribute__((aligned(16))) float hd[6*64 + 64 + 16];   // mu_w | v_w | mu_b(6) log_std(6) v_b(1)
+    constexpr int ODP = policy_odp(OD);
+    constexpr int LD = POLICY_LD;
+    __shared__ __attribute__((aligned(16))) float hd[HD_WORDS];
     __shared__ float oxt[64][ODP + 1];
     __shared__ float h1t[2][64][LD];
     __shared__ float h2t[2][64][LD];
@@ -438,10 +433,10 @@ __global__ void __launch_bounds__(256, 2) so100_policy_forward_mfma(int n, Polic
         for (int s2 = 0; s2 < 32; s2++) bw2[ct][s2] = W2[unit*64 + 2*s2 + lh];
     }
     if (wave == 3) {
-        for (int i = lane; i < 6*64; i += 64) hd[i] = w.mu_w[i];
-        hd[6*64 + lane] = w.v_w[lane];
-        if (lane < 6) { hd[7*64 + lane] = w.mu_b[lane]; hd[7*64 + 6 + lane] = w.log_std[lane]; }
-        if (lane == 0) hd[7*64 + 12] = w.v_b[0];
+        for (int i = lane; i < 6*64; i += 64) hd[HD_MU_W + i] = w.mu_w[i];
+        hd[HD_V_W + lane] = w.v_w[lane];
+        if (lane < 6) { hd[HD_MU_B + lane] = w.mu_b[lane]; hd[HD_LOG_STD + lane] = w.log_std[lane]; }
+        if (lane == 0) hd[HD_V_B] = w.v_b[0];
     }
     for (int i = threadIdx.x; i < 64*(ODP + 1); i += 256) (&oxt[0][0])[i] = 0.0f;     // padding columns stay zero
     const int ntiles = (n + 63)/64;
@@ -493,7 +488,7 @@ __global__ void __launch_bounds__(256, 2) so100_policy_forward_mfma(int n, Polic
         // heads: waves 0, 1, 3 two action means each; wave 2 the value head and the noise
         if (wave != 2) {
             const int a0 = wave == 0 ? 0 : (wave == 1 ? 2 : 4);
-            float m0 = hd[7*64 + a0], m1 = hd[7*64 + a0 + 1];
+            float m0 = hd[HD_MU_B + a0], m1 = hd[HD_MU_B + a0 + 1];
 #pragma unroll 4
             for (int k = 0; k < 64; k += 4) {
                 const float x0 = h2t[0][lane][k], x1 = h2t[0][lane][k+1], x2 = h2t[0][lane][k+2], x3 = h2t[0][lane][k+3];
@@ -504,12 +499,12 @@ __global__ void __launch_bounds__(256, 2) so100_policy_forward_mfma(int n, Polic
             }
             xmean[a0][lane] = m0; xmean[a0 + 1][lane] = m1;
         } else {
-            float v = hd[7*64 + 12];
+            float v = hd[HD_V_B];
 #pragma unroll 8
-            for (int k = 0; k < 64; k++) v = __builtin_fmaf(hd[6*64 + k], h2t[1][lane][k], v);
+            for (int k = 0; k < 64; k++) v = __builtin_fmaf(hd[HD_V_W + k], h2t[1][lane][k], v);
             if (live) {
                 if (io.value) io.value[env] = v;
-                if (io.rollout_row) io.rollout_row[(size_t)env*(OD + 10) + OD + 8] = v;
+                if (io.rollout_row) io.rollout_row[(size_t)env*(OD + ROW_EXTRA) + OD + ROW_VALUE] = v;
             }
             float eps[8];
             if (io.noise) {
@@ -526,18 +521,18 @@ __global__ void __launch_bounds__(256, 2) so100_policy_forward_mfma(int n, Polic
             float lp = 0.0f;
 #pragma unroll
             for (int a = 0; a < 6; a++) {
-                const float ls = hd[7*64 + 6 + a], e = xn[a][lane];
+                const float ls = hd[HD_LOG_STD + a], e = xn[a][lane];
                 const float act = __builtin_fmaf(__builtin_expf(ls), e, xmean[a][lane]);
                 lp += -0.5f*e*e - ls - 0.9189385332046727f;
                 io.act_env[(size_t)env*6 + a] = tclamp(act, -1.0f, 1.0f);
                 if (io.act_raw) io.act_raw[(size_t)env*6 + a] = act;
-                if (io.rollout_row) io.rollout_row[(size_t)env*(OD + 10) + OD + a] = act;
+                if (io.rollout_row) io.rollout_row[(size_t)env*(OD + ROW_EXTRA) + OD + ROW_ACT + a] = act;
             }
             if (io.logp) io.logp[env] = lp;
-            if (io.rollout_row) io.rollout_row[(size_t)env*(OD + 10) + OD + 9] = lp;
+            if (io.rollout_row) io.rollout_row[(size_t)env*(OD + ROW_EXTRA) + OD + ROW_LOGP] = lp;
         } else if (wave == 1 && live && io.rollout_row) {
 #pragma unroll
-            for (int k = 0; k < OD; k++) io.rollout_row[(size_t)env*(OD + 10) + k] = oxt[lane][k];
+            for (int k = 0; k < OD; k++) io.rollout_row[(size_t)env*(OD + ROW_EXTRA) + k] = oxt[lane][k];
         }
     }
 }
@@ -559,9 +554,9 @@ __global__ void __launch_bounds__(64*NW) so100_rollout_fused(SimParams p, float*
     static_assert(ROWS == 64 || ROWS == 32, "envs per workgroup the policy phase is tiled for");
     constexpr bool HALF = ROWS == 32;
     constexpr int OD = obs_dim<KIND>();
-    constexpr int ODP = (OD + 3) & ~3;                            // K of layer 1, padded with zero weights
-    constexpr int LD = 65;                                        // LDS row stride of the [env][unit] activation images
-    __shared__ __attribute__((aligned(16))) float hd[6*64 + 64 + 16];   // mu_w | v_w | mu_b(6) log_std(6) v_b(1)
+    constexpr int ODP = policy_odp(OD);                           // K of layer 1, padded with zero weights
+    constexpr int LD = POLICY_LD;                                 // LDS row stride of the [env][unit] activation images
+    __shared__ __attribute__((aligned(16))) float hd[HD_WORDS];
     __shared__ float oxt[64][ODP + 1];                            // observation [env][k]
     // The hidden-activation images and the action means in ONE array: they are dead during the physics phase, when the bytes
     // carry the pad-contact records ([MAXC][CF][64] floats = 61 440 B) and the mass matrix for the contact wave ([21][64]).
@@ -619,10 +614,10 @@ __global__ void __launch_bounds__(64*NW) so100_rollout_fused(SimParams p, float*
         for (int s2 = 0; s2 < 32; s2++) { if constexpr (W2_LDS) w2s[wave][ct][s2][lane] = W2[unit*64 + 2*s2 + lh]; else bw2[ct][s2] = W2[unit*64 + 2*s2 + lh]; }
     }
     if (wave == NW - 1) {
-        for (int i = lane; i < 6*64; i += 64) hd[i] = w.mu_w[i];
-        hd[6*64 + lane] = w.v_w[lane];
-        if (lane < 6) { hd[7*64 + lane] = w.mu_b[lane]; hd[7*64 + 6 + lane] = w.log_std[lane]; }
-        if (lane == 0) hd[7*64 + 12] = w.v_b[0];
+        for (int i = lane; i < 6*64; i += 64) hd[HD_MU_W + i] = w.mu_w[i];
+        hd[HD_V_W + lane] = w.v_w[lane];
+        if (lane < 6) { hd[HD_MU_B + lane] = w.mu_b[lane]; hd[HD_LOG_STD + lane] = w.log_std[lane]; }
+        if (lane == 0) hd[HD_V_B] = w.v_b[0];
     }
     EnvState e;
     if (wave == 0) {
@@ -698,12 +693,12 @@ __global__ void __launch_bounds__(64*NW) so100_rollout_fused(SimParams p, float*
         }
         __syncthreads();
         SO100_PROF(0);                                             // policy hidden layers (MFMA + tanh + 2 barriers)
-        float* row = ra.buf + ((size_t)t*p.n + (size_t)env)*(OD + 10);
+        float* row = ra.buf + ((size_t)t*p.n + (size_t)env)*(OD + ROW_EXTRA);
         // ---- heads (VALU, lane = env): the 6 x 64 mean head is split two actions per wave over waves 0, 1, 3 and the
         //      value head runs on wave 2; each mean is the same k-ordered fmaf chain as in the stand-alone policy kernel
         if (wave != 2) {
             const int a0 = wave == 0 ? 0 : (wave == 1 ? 2 : 4);
-            float m0 = hd[7*64 + a0], m1 = hd[7*64 + a0 + 1];
+            float m0 = hd[HD_MU_B + a0], m1 = hd[HD_MU_B + a0 + 1];
 #pragma unroll 4
             for (int k = 0; k < 64; k += 4) {
                 const float x0 = h2t[0][lane][k], x1 = h2t[0][lane][k+1], x2 = h2t[0][lane][k+2], x3 = h2t[0][lane][k+3];
@@ -714,10 +709,10 @@ __global__ void __launch_bounds__(64*NW) so100_rollout_fused(SimParams p, float*
             }
             xmean[a0][lane] = m0; xmean[a0 + 1][lane] = m1;
         } else {
-            float v = hd[7*64 + 12];
+            float v = hd[HD_V_B];
 #pragma unroll 8
-            for (int k = 0; k < 64; k++) v = __builtin_fmaf(hd[6*64 + k], h2t[1][lane][k], v);
-            if (live) row[OD + 8] = v;
+            for (int k = 0; k < 64; k++) v = __builtin_fmaf(hd[HD_V_W + k], h2t[1][lane][k], v);
+            if (live) row[OD + ROW_VALUE] = v;
         }
         __syncthreads();
         if (wave == 0) {
@@ -728,16 +723,16 @@ __global__ void __launch_bounds__(64*NW) so100_rollout_fused(SimParams p, float*
             float act[6], lp = 0.0f;
 #pragma unroll
             for (int a = 0; a < 6; a++) {
-                const float ls = hd[7*64 + 6 + a];
+                const float ls = hd[HD_LOG_STD + a];
                 const float raw = __builtin_fmaf(__builtin_expf(ls), eps[a], mean[a]);
                 lp += -0.5f*eps[a]*eps[a] - ls - 0.9189385332046727f;
                 act[a] = live ? tclamp(raw, -1.0f, 1.0f) : 0.0f;
-                if (live) row[OD + a] = raw;
+                if (live) row[OD + ROW_ACT + a] = raw;
             }
             if (live) {
 #pragma unroll
                 for (int k = 0; k < OD; k++) row[k] = oxt[lane][k];
-                row[OD + 9] = lp;
+                row[OD + ROW_LOGP] = lp;
             }
             draw8(p, p.env_id_offset + (uint32_t)env, (uint32_t)e.rngc, 0, nullptr, ustep);
             e.rngc++;
@@ -750,7 +745,7 @@ __global__ void __launch_bounds__(64*NW) so100_rollout_fused(SimParams p, float*
         //      lanes with pad contacts to the solver tolerance (same warm start and active-set memory, differently rounded inputs).
         {
             Arm<float> A;
-                        const PhaseLds lds{ xq, xc, xb, pool, xa, xk, xm, pbuf, xw };
+            const PhaseLds lds{ xq, xc, xb, pool, xa, xk, xm, pbuf, xw };
             physics_phase_mw<PADS, LINKS, !PADS && FL != 7>(p, wave, lane, e, ctx.ctrl, cstale, A, lds, memo, prof_, [&](int sub) {
                 if (wave == 3 && sub == 0 && t + 1 < ra.T) {       // wave 0 has consumed xn before this barrier
                     float eps[8];
@@ -776,7 +771,7 @@ __global__ void __launch_bounds__(64*NW) so100_rollout_fused(SimParams p, float*
                 for (int k = 0; k < OD; k++) { oxt[lane][k] = obs[k]; last_obs[k] = obs[k]; }
                 last = r;
                 if (live) {
-                    row[OD + 6] = r.reward; row[OD + 7] = r.done ? (r.trunc_only ? 2.0f : 1.0f) : 0.0f;
+                    row[OD + ROW_REWARD] = r.reward; row[OD + ROW_DONE] = done_code(r.done, r.trunc_only);
                     if (r.done) {
                         if (ra.tobs_chunk) {
 #pragma unroll

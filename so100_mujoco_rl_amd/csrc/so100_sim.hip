@@ -120,7 +120,7 @@ int so100_create(const so100_config* cfg, so100_sim** out) {
         if (cfg->flags == SO100_F_CUBE_PINNED && (cfg->num_envs + 31)/32 <= cus) epw = 32;
         if (cfg->envs_per_workgroup != 0) epw = (int)cfg->envs_per_workgroup;             // the caller pins it (validated above)
         s->prm.epw = epw;
-        s->prm.mw_max = mw_max_envs_for(cfg->flags);
+        s->prm.mw_max = MW_MAX_ENVS;
         if (const char* ov = getenv("SO100_MW_MAX_ENVS")) { const long v = atol(ov); if (v >= 0) s->prm.mw_max = (int32_t)(v > (1L << 30) ? (1L << 30) : v); }
     }
     const size_t bytes = (size_t)SF_COUNT*(size_t)cfg->num_envs*sizeof(float);
