@@ -218,3 +218,46 @@ class OracleBatch:
             self.L.so100o_envs_free(self.envs)
         except Exception:
             pass
+
+
+# ---- the kernels' own random draws, restated independently (numpy uint64 / float64, no float32 anywhere) --------------------
+_M32 = np.uint64(0xFFFFFFFF)
+POLICY_STREAM_C2, POLICY_STREAM_C3 = 16, 0x504F4C          # counter words 2 and 3 of the policy-noise stream ("POL")
+
+
+def philox4x32_np(c0, c1, c2, c3, k0, k1):
+    """Philox4x32-10 (Salmon et al., SC'11) on broadcastable integer arrays; returns uint64[..., 4] holding 32-bit words.
+    Written from the paper, not from so100o_philox4x32: tests/test_rng_reference.py holds both to Random123's known answers."""
+    c = [np.asarray(x, np.uint64) & _M32 for x in np.broadcast_arrays(c0, c1, c2, c3)]
+    k0 = np.uint64(int(k0) & 0xFFFFFFFF); k1 = np.uint64(int(k1) & 0xFFFFFFFF)
+    m0, m1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
+    w0, w1 = np.uint64(0x9E3779B9), np.uint64(0xBB67AE85)
+    s32 = np.uint64(32)
+    for _ in range(10):
+        p0 = m0 * c[0]; p1 = m1 * c[2]                       # 32 x 32 -> 64 bit products: no overflow in uint64
+        c = [(p1 >> s32) ^ c[1] ^ k0, p1 & _M32, (p0 >> s32) ^ c[3] ^ k1, p0 & _M32]
+        k0 = (k0 + w0) & _M32; k1 = (k1 + w1) & _M32
+    return np.stack(c, -1)
+
+
+def box_muller_ref(r_even, r_odd):
+    """The policy-noise transform of two 32-bit words in float64: u1 = ((r_even >> 8) + 1) 2^-24 in (0, 1], u2 = (r_odd >> 8) 2^-24
+    in [0, 1); returns (rad cos(ang), rad sin(ang)) with rad = sqrt(-2 ln u1), ang = 2 pi u2 - pi."""
+    u1 = ((np.asarray(r_even, np.uint64) >> np.uint64(8)).astype(np.float64) + 1.0) * 2.0**-24
+    u2 = (np.asarray(r_odd, np.uint64) >> np.uint64(8)).astype(np.float64) * 2.0**-24
+    rad = np.sqrt(-2.0*np.log(u1)); ang = 2.0*np.pi*u2 - np.pi
+    return rad*np.cos(ang), rad*np.sin(ang)
+
+
+def policy_noise_ref(seed, env_gid, step):
+    """float64[..., 6]: the standard normals the policy kernels draw for env `env_gid` (uint32, env_id_offset included) at policy
+    step counter `step` (uint32) under `seed` (uint64); env_gid and step broadcast against each other.  Contract (csrc/so100_task.hpp,
+    policy_noise): for b in 0, 1 the Philox counter is (env_gid, step, 16 + b, 0x504F4C), the key (seed & 0xffffffff, seed >> 32);
+    words (2i, 2i + 1) of block b give eps[4b + 2i], eps[4b + 2i + 1] by box_muller_ref; the first six of the eight are used."""
+    seed = int(seed); env_gid, step = np.broadcast_arrays(np.asarray(env_gid, np.uint64), np.asarray(step, np.uint64))
+    eps = np.empty(env_gid.shape + (8,), np.float64)
+    for b in range(2):
+        r = philox4x32_np(env_gid, step, POLICY_STREAM_C2 + b, POLICY_STREAM_C3, seed & 0xFFFFFFFF, seed >> 32)
+        for i in range(2):
+            eps[..., 4*b + 2*i], eps[..., 4*b + 2*i + 1] = box_muller_ref(r[..., 2*i], r[..., 2*i + 1])
+    return eps[..., :6]

@@ -8,8 +8,8 @@
 //   action = mean + exp(log_std) * eps, eps ~ N(0,1) (Philox4x32-10 + Box-Muller, or injected), log_prob, clip to [-1,1]
 // Two kernels in so100_rollout.hpp run it: so100_policy_forward_mfma (its own launch) and the policy phase of
 // so100_rollout_fused.  The two 64-wide hidden layers run on the matrix cores (exact-fp32 v_mfma_f32_32x32x2_f32), heads /
-// sampling on the VALU.  This header holds what the two share: the weight / IO structs, the LDS and rollout-row layouts, the
-// tanh and the Philox + Box-Muller noise.  The network itself is written out in each kernel, the same operations in the same
+// sampling on the VALU.  This header holds what the two share: the weight / IO structs, the LDS and rollout-row layouts and the
+// tanh (the Philox + Box-Muller noise, policy_noise, is in so100_task.hpp).  The network itself is written out in each kernel, the same operations in the same
 // order, and test_persistent_rollout_equals_stepwise holds the two together to 1e-6.  (It was also built as shared functions
 // here; each of them, even the once-per-launch weight loading, changed the register allocation or scratch size of some
 // instantiation of the rollout kernel, which is tuned to the last 16 B: DESIGN.md 8e.)
@@ -50,23 +50,7 @@ __device__ __forceinline__ float fast_tanh(float x) {
     return 1.0f - 2.0f*trcp(e + 1.0f);
 }
 
-// ---------------------------------------------------------------------------------------------------------------
-// Policy noise shared by the stand-alone policy kernel and the persistent rollout kernel
-// ---------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void policy_noise(uint32_t env_gid, uint32_t step_counter, uint32_t seed_lo, uint32_t seed_hi, float eps[8]) {
-#pragma unroll
-    for (int b = 0; b < 2; b++) {
-        uint32_t r[4];
-        philox4x32(env_gid, step_counter, 16u + (uint32_t)b, 0x504F4Cu, seed_lo, seed_hi, r);
-#pragma unroll
-        for (int i = 0; i < 2; i++) {                                  // Box-Muller on (0,1] x [0,1)
-            const float u1 = ((float)(r[2*i] >> 8) + 1.0f) * (1.0f/16777216.0f);
-            const float u2 = (float)(r[2*i + 1] >> 8) * (1.0f/16777216.0f);
-            const float rad = __builtin_sqrtf(-2.0f*__builtin_logf(u1));
-            float sn, cs; tsincos<float>(6.283185307179586f*u2 - 3.141592653589793f, sn, cs);
-            eps[4*b + 2*i] = rad*cs; eps[4*b + 2*i + 1] = rad*sn;
-        }
-    }
-}
+// The policy noise (Philox + Box-Muller) both kernels draw is policy_noise() in so100_task.hpp, beside the env's own draw8: host-compilable, so
+// tests/_hostcheck holds its fp32 transform to the fp64 reference sampler.
 
 }  // namespace so100

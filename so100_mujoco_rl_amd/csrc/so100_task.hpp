@@ -154,6 +154,26 @@ SO100_HD void draw8(const SimParams& p, uint32_t env_gid, uint32_t counter, int 
     }
 }
 
+// ---- policy noise: six standard normals per (env, policy step), shared by the stand-alone policy kernel and the persistent rollout kernel.
+// Its own Philox stream: counter words (env, step, 16 + b, 0x504F4C) -- draw8 above only ever forms c3 = 0.
+// Box-Muller of two 32-bit words on (0,1] x [0,1); reference: oracle/so100_oracle.py box_muller_ref / policy_noise_ref.
+SO100_HD void policy_noise_pair(uint32_t r_even, uint32_t r_odd, float& e0, float& e1) {
+    const float u1 = ((float)(r_even >> 8) + 1.0f) * (1.0f/16777216.0f);
+    const float u2 = (float)(r_odd >> 8) * (1.0f/16777216.0f);
+    const float rad = __builtin_sqrtf(-2.0f*__builtin_logf(u1));
+    float sn, cs; tsincos<float>(6.283185307179586f*u2 - 3.141592653589793f, sn, cs);
+    e0 = rad*cs; e1 = rad*sn;
+}
+SO100_HD void policy_noise(uint32_t env_gid, uint32_t step_counter, uint32_t seed_lo, uint32_t seed_hi, float eps[8]) {
+#pragma unroll
+    for (int b = 0; b < 2; b++) {
+        uint32_t r[4];
+        philox4x32(env_gid, step_counter, 16u + (uint32_t)b, 0x504F4Cu, seed_lo, seed_hi, r);
+#pragma unroll
+        for (int i = 0; i < 2; i++) policy_noise_pair(r[2*i], r[2*i + 1], eps[4*b + 2*i], eps[4*b + 2*i + 1]);
+    }
+}
+
 // ---- pure task functions -----------------------------------------------------------------------------
 SO100_HD float joint_penalty(float a, float lo, float hi) {                // ref: env_base_01.py:153-163
     const float lt = lo + 0.05f*(hi - lo), ut = hi - 0.05f*(hi - lo);

@@ -120,8 +120,11 @@ namespace {
 float g_tab[36*6]; bool g_tab_ok = false;
 const float* tab() { if (!g_tab_ok) { for (int i = 0; i < 36; i++) for (int j = 0; j < 6; j++) g_tab[6*i+j] = (float)SO100_VALID_START_POSITIONS[i][j]; g_tab_ok = true; } return g_tab; }
 template <int KIND> void env_new(EnvState* e) { env_init<KIND>(*e); }
-template <int KIND> void env_rst(EnvState* e, const float* inject, float* obs) {
-    SimParams p{}; float u[8]; draw8(p, 0, (uint32_t)e->rngc, 1, inject, u); e->rngc++; env_reset<KIND>(*e, u, tab(), obs);
+SimParams keyed(unsigned long long seed, unsigned env_id) {           // the RNG keying of one env: env_gid = env_id_offset + 0
+    SimParams p{}; p.n = 1; p.seed_lo = (uint32_t)seed; p.seed_hi = (uint32_t)(seed >> 32); p.env_id_offset = env_id; return p;
+}
+template <int KIND> void env_rst(EnvState* e, const SimParams& p, const float* inject, float* obs) {
+    float u[8]; draw8(p, p.env_id_offset, (uint32_t)e->rngc, 1, inject, u); e->rngc++; env_reset<KIND>(*e, u, tab(), obs);
 }
 template <int KIND> void env_stp(EnvState* e, const SimParams& p, const float* a, const float* inject, float* obs, float* tobs, float* rew, int* done, int* trunc) {
     StepResult r = env_step_vec<KIND>(*e, a, p, p.env_id_offset, inject, tab(), obs, tobs);
@@ -132,10 +135,13 @@ template <int KIND> void env_stp(EnvState* e, const SimParams& p, const float* a
 extern "C" {
 void* hc_env_new(int kind) { EnvState* e = new EnvState; KSWITCH(kind, env_new, e); return e; }
 void hc_env_free(void* e) { delete (EnvState*)e; }
-void hc_env_reset(void* e, int kind, const float* inject, float* obs) { KSWITCH(kind, env_rst, (EnvState*)e, inject, obs); }
-void hc_env_step(void* e, int kind, unsigned flags, int iters, int citers, int max_steps, const float* a, const float* inject,
-                 float* obs, float* tobs, float* rew, int* done, int* trunc) {
-    SimParams p{}; p.n = 1; p.flags = flags; p.solver_iters = iters; p.contact_iters = citers; p.frame_skip = 16; p.max_episode_steps = max_steps;
+// seed / env_id key the env's own Philox draws when inject is null (the oracle's OracleEnv(kind, seed=, env_id=))
+void hc_env_reset(void* e, int kind, unsigned long long seed, unsigned env_id, const float* inject, float* obs) {
+    const SimParams p = keyed(seed, env_id); KSWITCH(kind, env_rst, (EnvState*)e, p, inject, obs);
+}
+void hc_env_step(void* e, int kind, unsigned flags, int iters, int citers, int max_steps, unsigned long long seed, unsigned env_id,
+                 const float* a, const float* inject, float* obs, float* tobs, float* rew, int* done, int* trunc) {
+    SimParams p = keyed(seed, env_id); p.flags = flags; p.solver_iters = iters; p.contact_iters = citers; p.frame_skip = 16; p.max_episode_steps = max_steps;
     KSWITCH(kind, env_stp, (EnvState*)e, p, a, inject, obs, tobs, rew, done, trunc);
 }
 void hc_env_stats(void* ev, double* out2) { EnvState* e = (EnvState*)ev; out2[0] = e->cstat; out2[1] = e->res; }
@@ -144,5 +150,20 @@ void hc_env_qpos(void* ev, double* qpos13, double* qvel12) {
     for (int i = 0; i < 6; i++) { qpos13[i] = e->q[i]; qvel12[i] = e->v[i]; qvel12[6+i] = e->cube.vel[i]; }
     for (int i = 0; i < 3; i++) qpos13[6+i] = e->cube.pos[i];
     for (int i = 0; i < 4; i++) qpos13[9+i] = e->cube.quat[i];
+}
+}
+
+// ---- the device's random draws on the host: Philox, the env's uniforms (draw8), the policy noise -----------------------------
+extern "C" {
+void hc_philox4x32(const uint32_t* c4, const uint32_t* k2, uint32_t* out4) { philox4x32(c4[0], c4[1], c4[2], c4[3], k2[0], k2[1], out4); }
+void hc_draw8(unsigned long long seed, unsigned env_gid, unsigned counter, int phase, float* u8) {
+    const SimParams p = keyed(seed, 0); draw8(p, env_gid, counter, phase, nullptr, u8);
+}
+void hc_policy_noise(unsigned long long seed, unsigned env_gid, unsigned step, float* eps8) {
+    policy_noise(env_gid, step, (uint32_t)seed, (uint32_t)(seed >> 32), eps8);
+}
+// the fp32 Box-Muller of n word pairs (policy_noise's inner transform), for sweeps over u1 and u2
+void hc_policy_noise_pairs(const uint32_t* r_even, const uint32_t* r_odd, long n, float* e0, float* e1) {
+    for (long i = 0; i < n; i++) policy_noise_pair(r_even[i], r_odd[i], e0[i], e1[i]);
 }
 }

@@ -87,6 +87,9 @@ def _pre_activation_range(t, obs):
 # The persistent kernel's log-prob is recomputed from the stored raw action: at log_std = -3 an fp32 mean error of ~2e-6 moves the
 # recovered eps by ~4e-5, which is what dominates that bound.
 PERSISTENT_VALUE, PERSISTENT_LOGP = 1.5e-5, 4e-4           # measured 4.9e-6, 1.4e-4
+# ... and against the reference noise itself (oracle.policy_noise_ref: the eps the kernel must have drawn for that env and step), which
+# needs no recovery: raw action against mean64 + exp(log_std) eps_ref, stored log-prob against the log-density of eps_ref
+PERSISTENT_ACTION_REF, PERSISTENT_LOGP_REF = 1e-5, 5e-6    # measured 3.4e-6, 1.6e-6 (the recovered-eps log-prob above: 1.4e-4, bound 4e-4)
 STEPWISE_ACTION, STEPWISE_VALUE, STEPWISE_LOGP = 8e-6, 8e-6, 2.5e-6     # measured 2.7e-6, 2.7e-6, 8.1e-7
 
 
@@ -94,7 +97,9 @@ STEPWISE_ACTION, STEPWISE_VALUE, STEPWISE_LOGP = 8e-6, 8e-6, 2.5e-6     # measur
 def test_policy_phase_vs_fp64(kind, epw):
     """persistent kernel (obs width 15: Env01; 8: Env05) at 16 / 32 / 64 envs per workgroup, then the stepwise kernel on the same
     observations.  Persistent: value within the bound of the fp64 value; eps = (raw action - mean64) / exp(log_std) and the kernel's
-    log-prob within the bound of the fp64 log-prob of that eps; the env stepped with clamp(raw, -1, 1) (oracle replay)."""
+    log-prob within the bound of the fp64 log-prob of that eps; the env stepped with clamp(raw, -1, 1) (oracle replay).  And with nothing
+    taken from the kernel: raw action against mean64 + exp(log_std) eps_ref and the stored log-prob against the log-density of eps_ref, where
+    eps_ref = oracle.policy_noise_ref(seed, env, step) is the noise the kernel is meant to have drawn."""
     from so100_mujoco_rl_amd.vec_env import So100VecEnv
     from so100_mujoco_rl_amd.collector import RolloutCollector
     from so100_mujoco_rl_amd.lib import POLICY_TENSORS, SB3_STATE_DICT_KEYS
@@ -112,6 +117,11 @@ def test_policy_phase_vs_fp64(kind, epw):
     eps = (raw - mean)/ls.exp()
     logp = (-0.5*eps**2 - ls - LOG2PI_HALF).sum(1)
     ev = float((b["values"].reshape(-1).double().cpu() - value).abs().max()); el = float((b["log_probs"].reshape(-1).double().cpu() - logp).abs().max())
+    # the same two quantities with eps known from outside: the reference sampler at (seed 6, env, step counter = row of the chunk)
+    eps_ref = torch.from_numpy(O.policy_noise_ref(6, np.arange(n)[None, :], np.arange(T)[:, None])).reshape(-1, 6)
+    pa = float((raw - (mean + ls.exp()*eps_ref)).abs().max())
+    pl = float((b["log_probs"].reshape(-1).double().cpu() - (-0.5*eps_ref**2 - ls - LOG2PI_HALF).sum(1)).abs().max())
+    print(f"[policy vs fp64 and reference noise, obs width {od}, epw {epw}] persistent: raw action {pa:.2e} log-prob {pl:.2e} (recovered-eps log-prob {el:.2e})")
     x1, x2, s1, s2 = _pre_activation_range(t, obs)
     clipped = float((raw.abs() > 1).double().mean())
     # the stepwise policy kernel on the same observations, with the noise given explicitly: action, value and log-prob against fp64
@@ -128,6 +138,7 @@ def test_policy_phase_vs_fp64(kind, epw):
           f"raw actions outside [-1, 1] {clipped:.2f}; persistent: value {ev:.2e} log-prob {el:.2e}; stepwise: action {sa:.2e} value {sv:.2e} log-prob {sl:.2e}")
     assert x1 > 5 and x2 > 5 and s1 > 0.05 and s2 > 0.05 and clipped > 0.05   # saturated units and clipped actions were exercised
     assert ev < PERSISTENT_VALUE and el < PERSISTENT_LOGP
+    assert pa < PERSISTENT_ACTION_REF and pl < PERSISTENT_LOGP_REF
     assert sa < STEPWISE_ACTION and sv < STEPWISE_VALUE and sl < STEPWISE_LOGP
     assert torch.equal(ae, ar.clamp(-1, 1))
     # what the env received: clamp(raw, -1, 1), replayed in the oracle (8 envs; Env05's last two observations carry 5 x the pixel centre)

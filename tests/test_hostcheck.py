@@ -25,8 +25,8 @@ def H():
     h = C.CDLL(os.path.join(HERE, "_hostcheck", "libhostcheck.so"))
     h.hc_env_new.restype = C.c_void_p
     h.hc_env_free.argtypes = [C.c_void_p]
-    h.hc_env_reset.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-    h.hc_env_step.argtypes = [C.c_void_p, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 7
+    h.hc_env_reset.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_uint, C.c_void_p, C.c_void_p]
+    h.hc_env_step.argtypes = [C.c_void_p, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint] + [C.c_void_p] * 7
     h.hc_env_qpos.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     return h
 
@@ -149,13 +149,13 @@ def test_task_layer_fp32_vs_oracle(H, kind, flags):
         e = O.OracleEnv(kind, flags=flags, iters=0); e.e.max_episode_steps = 25
         h = H.hc_env_new(kind)
         inj = rs.random_sample(16).astype(np.float32)
-        oo = e.reset(inject=inj); oh = np.zeros(od, np.float32); H.hc_env_reset(h, kind, p(inj), p(oh))
+        oo = e.reset(inject=inj); oh = np.zeros(od, np.float32); H.hc_env_reset(h, kind, 0, 0, p(inj), p(oh))
         np.testing.assert_allclose(oh, oo, rtol=0, atol=1e-6)
         for t in range(60):
             a = np.clip(rs.uniform(-1, 1, 6) * 0.7, -1, 1).astype(np.float32); inj = rs.random_sample(16).astype(np.float32)
             oo, ro, to, tro, tobo = e.step(a, inject=inj, autoreset=True)
             oh = np.zeros(od, np.float32); th = np.zeros(od, np.float32); rh = C.c_float(); dh = C.c_int(); trh = C.c_int()
-            H.hc_env_step(h, kind, flags, 4, 6, 25, p(a), p(inj), p(oh), p(th), C.byref(rh), C.byref(dh), C.byref(trh))
+            H.hc_env_step(h, kind, flags, 4, 6, 25, 0, 0, p(a), p(inj), p(oh), p(th), C.byref(rh), C.byref(dh), C.byref(trh))
             tol = 2e-5 if reach else 6e-3
             np.testing.assert_allclose(oh[:6], oo[:6], rtol=0, atol=1e-5 if reach else 2e-6)
             np.testing.assert_allclose(oh, oo, rtol=0, atol=tol, err_msg=f"kind {kind} step {t}")

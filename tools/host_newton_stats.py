@@ -8,6 +8,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 subprocess.check_call(["make", "-C", os.path.join(ROOT, "tests", "_hostcheck"), "-s"])
 H = C.CDLL(os.path.join(ROOT, "tests", "_hostcheck", os.environ.get("HC_LIB", "libhostcheck.so")))
 H.hc_env_new.restype = C.c_void_p
+H.hc_env_reset.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_uint, C.c_void_p, C.c_void_p]
+H.hc_env_step.argtypes = [C.c_void_p, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint] + [C.c_void_p] * 7
 for f in ("hc_cdbg_passes", "hc_cdbg_signpasses", "hc_cdbg_gradpasses", "hc_cdbg_lastiter"):
     getattr(H, f).restype = C.c_long
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 128
@@ -18,13 +20,13 @@ P = lambda a: a.ctypes.data_as(C.c_void_p)
 envs = [C.c_void_p(H.hc_env_new(1)) for _ in range(n)]
 obs = np.zeros(15, np.float32); tobs = np.zeros(15, np.float32); rew = C.c_float(); done = C.c_int(); trunc = C.c_int()
 for e in envs:
-    inj = rs.random_sample(16).astype(np.float32); H.hc_env_reset(e, 1, P(inj), P(obs))
+    inj = rs.random_sample(16).astype(np.float32); H.hc_env_reset(e, 1, 0, 0, P(inj), P(obs))
 hist = (C.c_long*64)(); H.hc_cdbg_hist(hist, 1)
 stat = np.zeros(2); touching = 0
 for t in range(steps):
     for e in envs:
         a = np.clip(rs.randn(6), -1, 1).astype(np.float32); inj = rs.random_sample(16).astype(np.float32)
-        H.hc_env_step(e, 1, FLAGS, 2, 20, 4000, P(a), P(inj), P(obs), P(tobs), C.byref(rew), C.byref(done), C.byref(trunc))
+        H.hc_env_step(e, 1, FLAGS, 2, 20, 4000, 0, 0, P(a), P(inj), P(obs), P(tobs), C.byref(rew), C.byref(done), C.byref(trunc))
         H.hc_env_stats(e, P(stat)); touching += (int(stat[0]) & 255) > 0
     if t == steps//4:
         H.hc_cdbg_hist(hist, 1)                              # discard the start-up transient
