@@ -117,6 +117,8 @@ def lib():
         L.so100o_envs_at.argtypes = [C.POINTER(Env), C.c_int]
         L.so100o_envs_free.argtypes = [C.POINTER(Env)]
         L.so100o_env_init.argtypes = [C.POINTER(Model), C.POINTER(Env), C.c_int, C.c_uint, C.c_int, C.c_uint64, C.c_uint32]
+        L.so100o_capsule_box.argtypes = [C.c_void_p, C.c_void_p, d_] + [C.c_void_p] * 6
+        L.so100o_uniform4.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
         _lib = L
     return _lib
 

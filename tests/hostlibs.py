@@ -1,0 +1,73 @@
+"""The one place that builds and loads the host twins of the device code: tests/_hostcheck/libhostcheck.so (physics, contacts, task
+layer, random draws) and tests/_rendercheck/librendercheck.so (render).  Each is made once per process and cached; argtypes and restype
+are declared here for EVERY exported symbol (tests/test_hostlibs.py holds the tables to the extern "C" definitions), so that no call
+depends on which test ran first: a `long` result without its restype is silently cut to 32 bits, a Python float without argtypes raises."""
+import ctypes as C
+import os
+import subprocess
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+
+_p, _i, _u, _l, _f, _d, _ull = C.c_void_p, C.c_int, C.c_uint, C.c_long, C.c_float, C.c_double, C.c_ulonglong
+
+# name: (restype, argtypes); every pointer parameter is a c_void_p (numpy arrays through ptr(), C.byref() of a scalar, or None)
+HOSTCHECK = {
+    "hc_dyn_d": (None, [_p]*4), "hc_dyn_f": (None, [_p]*4),
+    "hc_sub_d": (None, [_p]*5 + [_u, _i, _i]), "hc_sub_f": (None, [_p]*5 + [_u, _i, _i]),
+    "hc_poses_d": (None, [_p]*2), "hc_poses_f": (None, [_p]*2),
+    "hc_cube_d": (None, [_p]*5 + [_u, _i, _i]), "hc_cube_f": (None, [_p]*5 + [_u, _i, _i]),
+    "hc_sincos_f": (None, [_f, _p, _p]),
+    "hc_dbg_counters": (None, [_p]),
+    "hc_capbox_d": (_i, [_p, _p, _d] + [_p]*6), "hc_capbox_f": (_i, [_p, _p, _d] + [_p]*6),
+    "hc_csub_d": (None, [_p]*3 + [_u, _i, _i, _i, _p]), "hc_csub_f": (None, [_p]*3 + [_u, _i, _i, _i, _p]),
+    "hc_boxbox_d": (_i, [_p]*9), "hc_boxbox_f": (_i, [_p]*9),
+    "hc_cdbg_trace": (None, [_i]),
+    "hc_cdbg_counters": (None, [_p]),
+    "hc_cdbg_passes": (_l, []), "hc_cdbg_signpasses": (_l, []), "hc_cdbg_gradpasses": (_l, []), "hc_cdbg_lastiter": (_l, []),
+    "hc_cdbg_hist": (None, [_p, _i]),
+    "hc_contact_id_hash": (_i, [_i]),
+    "hc_env_new": (_p, [_i]),
+    "hc_env_free": (None, [_p]),
+    "hc_env_reset": (None, [_p, _i, _ull, _u, _p, _p]),
+    "hc_env_step": (None, [_p, _i, _u, _i, _i, _i, _ull, _u] + [_p]*7),
+    "hc_env_stats": (None, [_p, _p]),
+    "hc_env_qpos": (None, [_p]*3),
+    "hc_philox4x32": (None, [_p]*3),
+    "hc_draw8": (None, [_ull, _u, _u, _i, _p]),
+    "hc_policy_noise": (None, [_ull, _u, _u, _p]),
+    "hc_policy_noise_pairs": (None, [_p, _p, _l, _p, _p]),
+}
+RENDERCHECK = {
+    "rc_record_floats": (_i, []),
+    "rc_render": (_i, [_p, _i, _i, _i, _i, _u] + [_p]*5),
+}
+
+_libs = {}
+
+
+def _load(path, make_dir, make_vars, signatures):
+    if path not in _libs:
+        subprocess.check_call(["make", "-C", make_dir, "-s"] + make_vars)
+        lib = C.CDLL(path)
+        for name, (restype, argtypes) in signatures.items():
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
+        _libs[path] = lib
+    return _libs[path]
+
+
+def hostcheck(out="libhostcheck.so", extra=""):
+    """tests/_hostcheck/hostcheck.cpp built into `out` (a name in tests/_hostcheck or an absolute path) with the compiler arguments
+    `extra` after the Makefile's own, e.g. -DSO100_MODEL_GEN_HEADER=... for a second generated model"""
+    d = os.path.join(HERE, "_hostcheck")
+    return _load(os.path.join(d, out), d, [f"OUT={out}", f"EXTRA={extra}"], HOSTCHECK)
+
+
+def rendercheck():
+    d = os.path.join(HERE, "_rendercheck")
+    return _load(os.path.join(d, "librendercheck.so"), d, [], RENDERCHECK)
+
+
+def ptr(a):
+    """the data pointer of a numpy array, for a c_void_p parameter"""
+    return a.ctypes.data_as(C.c_void_p)

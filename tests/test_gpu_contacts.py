@@ -12,55 +12,17 @@ import pytest
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
+from gpu_support import inject_state, make_sim, oracle_step   # noqa: E402
 from oracle import so100_oracle as O                      # noqa: E402  (the checker)
-from test_oracle_contacts import L, M, floor_poses, fresh, _grasp_state   # noqa: E402
-from test_substep_parity import SHIPPED                   # noqa: E402  ((solver_iters, contact_iters) = (2, 20): the shipped settings)
+from scenes import C5, JS, L, M, NOPADS, REFP, SHIPPED, floor_batch, fresh, grasp_batch, idle_batch   # noqa: E402
 
-REFP = O.F_REFERENCE                                       # friction + limits + cube/floor + pad/floor
-C5 = O.F_CONTACT5
-NOPADS = O.F_FRICTIONLOSS | O.F_LIMITS | O.F_FLOOR
-JS = np.float32(0.075)
 STEADY_MIN = 18          # envs (of 96) whose contact set is steady over the 16 substeps of the injected step (measured: 24; the test prints the classes)
-
-
-def _sim(*a, **k):
-    from so100_mujoco_rl_amd.lib import So100Sim
-    return So100Sim(*a, **k)
-
-
-def _inject(sim, qpos, qvel):
-    """qpos [n,13], qvel [n,12] (numpy) -> the handle (reset first: every other row at its post-reset value)"""
-    sim.reset()
-    sim.set_state(torch.from_numpy(np.ascontiguousarray(qpos.T, np.float32)).cuda(), torch.from_numpy(np.ascontiguousarray(qvel.T, np.float32)).cuda())
-
-
-def _oracle_step(qpos, qvel, act, flags, nsub=16):
-    """raw oracle physics from the injected state: returns final qpos, qvel and the per-substep pad-contact counts"""
-    d = fresh()
-    O.arr(d.qpos)[:] = qpos.astype(np.float32).astype(np.float64); O.arr(d.qvel)[:] = qvel.astype(np.float32).astype(np.float64)
-    O.arr(d.ctrl)[:] = O.arr(d.qpos)[:6] + (act.astype(np.float32)*JS).astype(np.float64)      # env01_v1.py:18-24 in NumPy-2 promotion
-    counts = []
-    for _ in range(nsub):
-        L.so100o_step(C.byref(M), C.byref(d), flags, -1, 1)
-        counts.append((sum(1 for i in range(d.ncon) if d.con[i].kind == 1), sum(1 for i in range(d.ncon) if d.con[i].kind == 2)))
-    return O.arr(d.qpos).copy(), O.arr(d.qvel).copy(), counts
-
-
-def _floor_batch(n, seed):
-    rs = np.random.RandomState(seed)
-    poses = floor_poses(n, seed + 100, band=0.002)
-    qpos = np.zeros((n, 13)); qvel = np.zeros((n, 12))
-    for i, q in enumerate(poses):
-        qpos[i, :6] = q; qpos[i, 6:9] = [0.15 + 0.02*rs.randn(), -0.25, 0.0099]; qpos[i, 9] = 1.0
-        qvel[i, :6] = rs.randn(6)*0.3
-    act = rs.uniform(-1, 1, (n, 6)).astype(np.float32)
-    return qpos, qvel, act
 
 
 def _stale_envs(res, iters):
     """envs whose residual row exceeds 1e-2.  At 2 block-PGS sweeps that row is the max over the step's substeps of the Newton's residual
     (contact substeps) and of the last sweep's change (contact-free substeps: not the distance from the converged solve,
-    tests/test_substep_parity.py check_residual); it is bounded per substep there.  Here those envs are counted and held to the same
+    tests/substep_harness.py check_residual); it is bounded per substep there.  Here those envs are counted and held to the same
     state bounds as every other env.  (4, 30): none allowed."""
     k = int((res >= 1e-2).sum())
     if iters != SHIPPED:
@@ -84,19 +46,19 @@ def _pad_floor_step_vs_oracle(n, iters):
     workgroup (contact wave: 4 cooperating lanes per env), 8192 with 32 (2 lanes per env), 16384 with 64 (one lane per env),
     n > 16384 the one-wave throughput kernel (the first 96 envs are the injected ones)"""
     m = 96
-    qpos, qvel, act = _floor_batch(m, 0)
-    sim = _sim(1, n, flags=REFP, solver_iters=iters[0], contact_iters=iters[1], max_episode_steps=0, seed=3)
-    QP = np.zeros((n, 13)); QP[:, 9] = 1.0; QP[:, 6:9] = [0.2, -0.2, 0.0099]; QP[:, :6] = [0, -1.5, 1.5, 0.5, 0, 0.2]; QV = np.zeros((n, 12))
+    qpos, qvel, act = floor_batch(m, 0)
+    sim = make_sim(1, n, flags=REFP, solver_iters=iters[0], contact_iters=iters[1], max_episode_steps=0, seed=3)
+    QP, QV = idle_batch(n)
     QP[:m] = qpos; QV[:m] = qvel
     A = np.zeros((n, 6), np.float32); A[:m] = act
-    _inject(sim, QP, QV)
+    sim.reset(); inject_state(sim, QP, QV)
     sim.step(torch.from_numpy(A).cuda())
     gq, gv = sim.get_state(); gq = gq.cpu().numpy().T[:m]; gv = gv.cpu().numpy().T[:m]
     cstat = sim.get_field("contact_stat", dtype=torch.int32).cpu().numpy()[:m]
     res = sim.get_field("solver_residual").cpu().numpy()[:m]
     steady = 0; touched = 0; worst_steady = 0.0; worst_any = 0.0
     for i in range(m):
-        oq, ov, counts = _oracle_step(qpos[i], qvel[i], act[i], REFP)
+        oq, ov, counts = oracle_step(qpos[i], qvel[i], act[i], REFP)
         nmax = max(c[0] for c in counts)
         touched += nmax > 0
         eq = np.abs(gq[i, :6] - oq[:6]).max(); ev = np.abs(gv[i, :6] - ov[:6]).max()
@@ -140,8 +102,8 @@ def test_pads_keep_the_gripper_above_the_floor_at_full_size():
         return out[::16]
 
     def run(flags, n_envs, off, sl):
-        sim = _sim(1, n_envs, flags=flags, seed=9, env_id_offset=off, max_episode_steps=0)
-        _inject(sim, QP[sl], QV[sl]); a = torch.from_numpy(act[sl]).cuda(); low = 1.0
+        sim = make_sim(1, n_envs, flags=flags, seed=9, env_id_offset=off, max_episode_steps=0)
+        sim.reset(); inject_state(sim, QP[sl], QV[sl]); a = torch.from_numpy(act[sl]).cuda(); low = 1.0
         for t in range(40):
             sim.step(a)
             if t % 4 == 3:
@@ -159,23 +121,6 @@ def test_pads_keep_the_gripper_above_the_floor_at_full_size():
     assert final0.min() < -0.02                               # without the pad contacts the gripper is centimetres under the floor
 
 
-def _grasp_batch(n, seed):
-    rs = np.random.RandomState(seed)
-    q, centre, cq = _grasp_state()
-    qpos = np.zeros((n, 13)); qvel = np.zeros((n, 12))
-    qpos[:, :6] = q; qpos[:, 5] = 0.065 + rs.uniform(0.0, 0.01, n)          # moving pads 0.1 .. 0.6 mm from the cube: contact within the first step
-    qpos[:, 6:9] = centre + rs.uniform(-1, 1, (n, 3))*np.array([0.0004, 0.002, 0.002])
-    # cube axes = jaw axes, turned by a small random rotation (generic orientations: no two SAT axes tie)
-    for i in range(n):
-        w = rs.randn(3)*0.03; ang = np.linalg.norm(w); ax = w/ang
-        dq = np.array([np.cos(ang/2), *(np.sin(ang/2)*ax)])
-        a, b = cq, dq
-        qpos[i, 9:13] = [a[0]*b[0] - a[1]*b[1] - a[2]*b[2] - a[3]*b[3], a[0]*b[1] + a[1]*b[0] + a[2]*b[3] - a[3]*b[2],
-                         a[0]*b[2] - a[1]*b[3] + a[2]*b[0] + a[3]*b[1], a[0]*b[3] + a[1]*b[2] - a[2]*b[1] + a[3]*b[0]]
-    act = np.zeros((n, 6), np.float32); act[:, 5] = -1.0                    # close the jaw as fast as the action allows
-    return qpos, qvel, act
-
-
 @pytest.mark.parametrize("n", [64, 8192, 16384 + 64])
 def test_pad_cube_grasp_vs_oracle(n):
     _pad_cube_grasp_vs_oracle(n, (4, 30))
@@ -191,12 +136,12 @@ def _pad_cube_grasp_vs_oracle(n, iters):
     """BASELINE.json configs[4]: the jaw closes on a cube floating between the pads; arm and cube dofs are coupled in one
     12-unknown solve.  Step by step against the oracle for as long as both see the same pad/cube contact counts."""
     m = 64
-    qpos, qvel, act = _grasp_batch(m, 1)
-    sim = _sim(1, n, flags=C5, solver_iters=iters[0], contact_iters=iters[1], max_episode_steps=0, seed=3)
-    QP = np.zeros((n, 13)); QP[:, 9] = 1.0; QP[:, 6:9] = [0.2, -0.2, 0.0099]; QP[:, :6] = [0, -1.5, 1.5, 0.5, 0, 0.2]; QV = np.zeros((n, 12))
+    qpos, qvel, act = grasp_batch(m, 1)
+    sim = make_sim(1, n, flags=C5, solver_iters=iters[0], contact_iters=iters[1], max_episode_steps=0, seed=3)
+    QP, QV = idle_batch(n)
     QP[:m] = qpos; QV[:m] = qvel
     A = np.zeros((n, 6), np.float32); A[:m] = act
-    _inject(sim, QP, QV)
+    sim.reset(); inject_state(sim, QP, QV)
     ds = []
     for i in range(m):
         d = fresh(); O.arr(d.qpos)[:] = qpos[i].astype(np.float32).astype(np.float64); ds.append(d)
@@ -241,16 +186,16 @@ def test_contact_kernels_agree_with_each_other(flags):
     from so100_mujoco_rl_amd.collector import RolloutCollector
     m = 128
     if flags == C5:
-        qpos, qvel, act = _grasp_batch(m, 2)
+        qpos, qvel, act = grasp_batch(m, 2)
     else:
-        qpos, qvel, act = _floor_batch(m, 2)
+        qpos, qvel, act = floor_batch(m, 2)
         act[:] = act[0]; act[:, 1] = 0.6                     # ONE action for the whole batch (shoulder down), so that the persistent kernel's
     outs = {}                                                # bias-only policy below can reproduce it: its rollout leg runs for both flag sets
     for name, n in (("mw", m), ("fused", 16384 + m)):
-        sim = _sim(1, n, flags=flags, contact_iters=12, max_episode_steps=0, seed=3)
-        QP = np.zeros((n, 13)); QP[:, 9] = 1.0; QP[:, 6:9] = [0.2, -0.2, 0.0099]; QP[:, :6] = [0, -1.5, 1.5, 0.5, 0, 0.2]; QV = np.zeros((n, 12))
+        sim = make_sim(1, n, flags=flags, contact_iters=12, max_episode_steps=0, seed=3)
+        QP, QV = idle_batch(n)
         QP[:m] = qpos; QV[:m] = qvel; A = np.zeros((n, 6), np.float32); A[:m] = act
-        _inject(sim, QP, QV)
+        sim.reset(); inject_state(sim, QP, QV)
         for t in range(3):
             sim.step(torch.from_numpy(A).cuda())
         q, v = sim.get_state()
@@ -260,7 +205,7 @@ def test_contact_kernels_agree_with_each_other(flags):
     sd = RolloutCollector.random_policy_state(15, env.device, seed=1)
     sd["action_net.weight"].zero_(); sd["action_net.bias"].copy_(torch.from_numpy(act[0])); sd["log_std"].fill_(-30.0)
     col = RolloutCollector(env, sd, T=3, persistent=True, bootstrap_truncated=False)
-    _inject(env.sim, qpos, qvel); col._started = True
+    env.sim.reset(); inject_state(env.sim, qpos, qvel); col._started = True
     assert np.abs(act - act[0]).max() == 0                   # one action for all envs -> the rollout kernel is compared too
     col.collect(3)
     q, v = env.sim.get_state()
@@ -287,7 +232,7 @@ def test_tail_workgroups_with_pad_contacts(flags):
     """batch sizes that are not a multiple of the envs-per-workgroup count (16 here): env by env the results must be BIT-IDENTICAL
     to the same envs inside a 256-env batch -- the contact wave's lane groups that belong to no env must not matter"""
     for n in (1, 17, 130):
-        big = _sim(1, 256, flags=flags, seed=5, max_episode_steps=25); small = _sim(1, n, flags=flags, seed=5, max_episode_steps=25)
+        big = make_sim(1, 256, flags=flags, seed=5, max_episode_steps=25); small = make_sim(1, n, flags=flags, seed=5, max_episode_steps=25)
         assert torch.equal(big.reset()[:n], small.reset())
         g = torch.Generator(device="cuda"); g.manual_seed(3); touched = 0
         for t in range(40):
@@ -317,7 +262,7 @@ def _whole_env_steps_with_pad_contacts_vs_oracle(kind, flags, iters):
     substep apart in fp32 and fp64 (its observation then jumps by > 1e-3); most envs never do within the run."""
     n, steps = 48, (40 if kind == 1 else 16)                  # (Env01 starts higher above the table)
     rs = np.random.RandomState(kind)
-    sim = _sim(kind, n, flags=flags, solver_iters=iters[0], contact_iters=iters[1], max_episode_steps=0, seed=11)
+    sim = make_sim(kind, n, flags=flags, solver_iters=iters[0], contact_iters=iters[1], max_episode_steps=0, seed=11)
     orc = [O.OracleEnv(kind, flags=flags, iters=-1, seed=11, env_id=i) for i in range(n)]
     for e in orc:
         e.e.max_episode_steps = 0

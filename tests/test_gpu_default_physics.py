@@ -13,18 +13,16 @@ import pytest
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
-import substep_harness as SH                              # noqa: E402
+from gpu_support import inject_state                      # noqa: E402
 from oracle import so100_oracle as O                      # noqa: E402  (the checker)
-from test_substep_parity import SHIPPED                   # noqa: E402  ((solver_iters, contact_iters): the shipped (2, 20) and (4, 30))
-
-REFP = O.F_REFERENCE
-C5 = O.F_CONTACT5
+from scenes import (C5, L, M, PROXIES, REFP, SHIPPED, capsule_box, floor_batch, fresh, grasp_batch, link_cube_states,   # noqa: E402
+                    proxy_bottoms, wrist_first_poses)
 
 
 def _contact_rich_state(n, flags, seed):
-    qpos, qvel, _ = SH.floor_batch(n, seed)
+    qpos, qvel, _ = floor_batch(n, seed)
     if flags & O.F_PADS_CUBE:                               # second half: the closing-jaw grasp of BASELINE.json configs[4]
-        gq, gv, _ = SH.grasp_batch(n - n//2, seed + 1)
+        gq, gv, _ = grasp_batch(n - n//2, seed + 1)
         qpos[n//2:] = gq; qvel[n//2:] = gv
     return qpos.astype(np.float32), qvel.astype(np.float32)
 
@@ -32,14 +30,13 @@ def _contact_rich_state(n, flags, seed):
 def _start(env, col, qpos, qvel, kind):
     sim = env.sim
     sim.reset()
-    sim.set_state(torch.from_numpy(np.ascontiguousarray(qpos.T)).cuda(), torch.from_numpy(np.ascontiguousarray(qvel.T)).cuda())
+    inject_state(sim, qpos, qvel)
     if kind in (3, 4, 5):                                    # look-at kinds servo to their COMMANDED angles (env_base_02.py:85-86)
         for i in range(6):
             sim.set_field(f"cmd{i}", torch.from_numpy(np.ascontiguousarray(qpos[:, i])).cuda())
     col._started = True
 
 
-PROXIES = O.F_LINKS_FLOOR | O.F_LINKS_CUBE                 # every capsule proxy pair: the run-time-flags kernels so100_rollout_fused / so100_step_mw<K, -1>
 # per-case bounds where the measurement is worse than the shared one (test_default_rollout_kernel_vs_stepwise_and_oracle)
 TIGHT_SHARE = {(2, C5): 0.985}                             # persistent vs stepwise rows within 1e-5: measured 0.995
 ORACLE_MISSES = {(1, REFP): 42}                            # oracle rows outside 2e-5 (contact events a substep apart): measured 14 of 480
@@ -126,14 +123,14 @@ def test_contact5_determinism_and_shard_invariance_4096():
     test_pads_keep_the_gripper_above_the_floor_at_full_size."""
     from so100_mujoco_rl_amd.lib import So100Sim
     n = 4096
-    qpos, qvel, act = SH.grasp_batch(n, 7)
+    qpos, qvel, act = grasp_batch(n, 7)
     rs = np.random.RandomState(1)
     act = act + rs.uniform(-0.3, 0.3, act.shape).astype(np.float32); act[:, 5] = -1.0
 
     def run(n_envs, off, sl):
         sim = So100Sim(1, n_envs, flags=C5, seed=9, env_id_offset=off, max_episode_steps=0)     # (Env02 would re-randomise the cube on its first step: Q1)
         sim.reset()
-        sim.set_state(torch.from_numpy(np.ascontiguousarray(qpos[sl].T, np.float32)).cuda(), torch.from_numpy(np.ascontiguousarray(qvel[sl].T, np.float32)).cuda())
+        inject_state(sim, qpos[sl], qvel[sl])
         a = torch.from_numpy(np.ascontiguousarray(act[sl])).cuda(); coupled = 0
         outs = []
         for t in range(8):
@@ -207,7 +204,7 @@ def test_contact_load_saturates_over_long_launches():
     import os
     from so100_mujoco_rl_amd.lib import So100Sim
     n, T, fs = 64, 32, 1024
-    qf, vf, _ = SH.floor_batch(192, 3)
+    qf, vf, _ = floor_batch(192, 3)
     keep = np.nonzero(qf[:, 1] > -1.5)[0][:n//2]                   # pressed arms: shoulder well above the policy's switch at -1.7
     assert len(keep) == n//2
     qpos = np.zeros((n, 13), np.float32); qvel = np.zeros((n, 12), np.float32)
@@ -221,7 +218,7 @@ def test_contact_load_saturates_over_long_launches():
         finally:
             del os.environ["SO100_BALANCE"]
         sim.reset()
-        sim.set_state(torch.from_numpy(np.ascontiguousarray(qpos.T)).cuda(), torch.from_numpy(np.ascontiguousarray(qvel.T)).cuda())
+        inject_state(sim, qpos, qvel)
         sim.obs[:, :6] = torch.from_numpy(np.ascontiguousarray(qpos[:, :6])).cuda()     # the first policy step reads the injected angles
         sim.set_policy({k: v.contiguous() for k, v in _switch_policy(sim.obs_dim, sim.device).items()})
         buf = torch.zeros(T, n, sim.obs_dim + 10, device=sim.device)
@@ -251,9 +248,8 @@ def test_link_proxies_keep_the_arm_above_the_table_on_the_gpu():
     the oracle; with the reference physics alone (pads only) the same links end centimetres under the table.  Run-time-flags kernels."""
     import ctypes as C
     from so100_mujoco_rl_amd.lib import So100Sim, F_REFERENCE_LINKS
-    from test_oracle_contacts import _wrist_first_poses, proxy_bottoms, fresh, L, M
     n = 512
-    poses = np.array(_wrist_first_poses(64, 11))
+    poses = np.array(wrist_first_poses(64, 11))
     rs = np.random.RandomState(2)
     QP = np.zeros((n, 13)); QP[:, 9] = 1.0; QP[:, 6:9] = [0.2, -0.3, 0.0099]
     QP[:, :6] = poses[rs.randint(0, len(poses), n)] + rs.uniform(-1, 1, (n, 6))*0.002
@@ -268,7 +264,7 @@ def test_link_proxies_keep_the_arm_above_the_table_on_the_gpu():
     def run(flags):
         sim = So100Sim(1, n, flags=flags, seed=9, max_episode_steps=0)
         sim.reset()
-        sim.set_state(torch.from_numpy(np.ascontiguousarray(QP.T, np.float32)).cuda(), torch.zeros(12, n, device="cuda"))
+        inject_state(sim, QP, np.zeros((n, 12)))
         a = torch.from_numpy(act).cuda(); low = 1.0
         for t in range(40):
             sim.step(a)
@@ -306,7 +302,6 @@ def test_link_cube_proxies_push_the_cube_and_survive_whole_rollouts_on_the_gpu()
         within 1e-6 rad / 1e-4 rad/s of the converged solve -- tools/pgs_probe.py)"""
     import ctypes as C
     from so100_mujoco_rl_amd.lib import So100Sim, F_REFERENCE_LINKS, F_REFERENCE_PROXIES
-    from test_oracle_contacts import link_cube_states, capsule_box, fresh, L, M
     n = 64
     states = link_cube_states(n, 21)
     QP = np.zeros((n, 13))
@@ -329,7 +324,7 @@ def test_link_cube_proxies_push_the_cube_and_survive_whole_rollouts_on_the_gpu()
     def run(flags, steps=8):
         sim = So100Sim(1, n, flags=flags, seed=4, max_episode_steps=0)
         sim.reset()
-        sim.set_state(torch.from_numpy(np.ascontiguousarray(QP.T, np.float32)).cuda(), torch.zeros(12, n, device="cuda"))
+        inject_state(sim, QP, np.zeros((n, 12)))
         a = torch.from_numpy(act).cuda()
         for _ in range(steps):
             sim.step(a)

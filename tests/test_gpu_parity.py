@@ -17,63 +17,21 @@ import pytest
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
+from gpu_support import make_sim, policy_tensors, run_pair, state_err, torch_policy   # noqa: E402
 from oracle import so100_oracle as O                      # noqa: E402  (the checker)
-
-
-def _sim(*a, **k):
-    from so100_mujoco_rl_amd.lib import So100Sim
-    return So100Sim(*a, **k)
-
-
-NOPADS = O.F_FRICTIONLOSS | O.F_LIMITS | O.F_FLOOR         # friction loss + limits + cube/floor, no finger-pad contacts (round 1's "reference")
-REFP = O.F_REFERENCE                                       # + the 8 finger pads vs the floor: what So100Sim / So100VecEnv / main.py run by default
-ARM = O.F_FRICTIONLOSS | O.F_LIMITS | O.F_CUBE_PINNED
-FREE = O.F_CUBE_PINNED
-
-
-def _run_pair(kind, flags, n, steps, seed, action_scale=1.0, solver_iters=4, contact_iters=6, max_steps=0, inject=True, pad_iters=None):
-    """Step n envs on the GPU and in the oracle with identical actions / uniforms; yield per-step results.
-    Oracle solver: PGS on the dual to 1e-15 -- or its primal Newton when pad rows are simulated (PGS needs ~1e4 sweeps on them).
-    pad_iters: (solver_iters, contact_iters) when pad rows are simulated (default: solver_iters, 30)."""
-    rs = np.random.RandomState(seed)
-    pads = (flags & (O.F_PADS_FLOOR | O.F_PADS_CUBE)) != 0
-    if pads:
-        solver_iters, contact_iters = pad_iters or (solver_iters, 30)
-    sim = _sim(kind, n, flags=flags, solver_iters=solver_iters, contact_iters=contact_iters, max_episode_steps=max_steps, seed=seed)
-    orc = [O.OracleEnv(kind, flags=flags, iters=-1 if pads else 0, seed=seed, env_id=i) for i in range(n)]
-    for e in orc:
-        e.e.max_episode_steps = max_steps
-    inj = rs.random_sample((n, 16)).astype(np.float32)
-    obs_g = sim.reset(inject=torch.from_numpy(inj).cuda() if inject else None).cpu().numpy().copy()
-    obs_o = np.stack([e.reset(inject=inj[i] if inject else None) for i, e in enumerate(orc)])
-    yield -1, sim, orc, obs_g, obs_o, None, None, None, None
-    for t in range(steps):
-        a = np.clip(rs.uniform(-1, 1, (n, 6)) * action_scale, -1, 1).astype(np.float32)
-        inj = rs.random_sample((n, 16)).astype(np.float32)
-        og, rg, dg, tg = sim.step(torch.from_numpy(a).cuda(), inject=torch.from_numpy(inj).cuda() if inject else None)
-        res = [e.step(a[i], inject=inj[i] if inject else None, autoreset=True) for i, e in enumerate(orc)]
-        oo = np.stack([r[0] for r in res]); ro = np.array([r[1] for r in res])
-        do = np.array([r[2] or r[3] for r in res]); to = np.array([r[3] and not r[2] for r in res])
-        yield t, sim, orc, og.cpu().numpy().copy(), oo, (rg.cpu().numpy().copy(), ro), (dg.cpu().numpy().copy(), do), (tg.cpu().numpy().copy(), to), res
-
-
-def _state_err(sim, orc):
-    qpos, qvel = sim.get_state()
-    qpos = qpos.cpu().numpy().T; qvel = qvel.cpu().numpy().T
-    qo = np.stack([O.arr(e.d.qpos).copy() for e in orc]); vo = np.stack([O.arr(e.d.qvel).copy() for e in orc])
-    return np.abs(qpos - qo).max(), np.abs(qvel - vo).max()
+from scenes import ARM, FREE, NOPADS, REFP                # noqa: E402
 
 
 @pytest.mark.parametrize("flags,name", [(FREE, "constraint-free"), (ARM, "friction+limits"), (NOPADS, "reference")])
 def test_env01_vs_oracle(flags, name):
     n, steps = (48, 40) if flags == NOPADS else (96, 60)
     worst_o = worst_r = 0.0
-    for t, sim, orc, og, oo, rew, done, trunc, _ in _run_pair(1, flags, n, steps, seed=7):
+    for t, sim, orc, og, oo, rew, done, trunc, _ in run_pair(1, flags, n, steps, seed=7):
         worst_o = max(worst_o, np.abs(og - oo).max())
         if rew is not None:
             worst_r = max(worst_r, np.abs(rew[0] - rew[1]).max())
             assert not done[0].any() and not done[1].any()
-    eq, ev = _state_err(sim, orc)
+    eq, ev = state_err(sim, orc)
     print(f"[{name}] obs {worst_o:.2e} reward {worst_r:.2e} qpos {eq:.2e} qvel {ev:.2e}")
     assert worst_o < 2e-5 and worst_r < 1e-4
     assert eq < 2e-5 and ev < 5e-4
@@ -82,7 +40,7 @@ def test_env01_vs_oracle(flags, name):
 def test_env02_vs_oracle_with_reach_branch():
     n, steps = 64, 30
     hits = 0
-    gen = _run_pair(2, ARM, n, steps, seed=11)
+    gen = run_pair(2, ARM, n, steps, seed=11)
     for t, sim, orc, og, oo, rew, done, trunc, _ in gen:
         np.testing.assert_allclose(og, oo, rtol=0, atol=2e-5)
         if rew is not None:
@@ -98,7 +56,7 @@ def test_env02_vs_oracle_with_reach_branch():
                 e3 = np.zeros(3); O.lib().so100o_end_effector(d.xpos[6], d.xmat[6], e3.ctypes.data_as(O.C.c_void_p))
                 O.arr(d.xpos)[8] = e3
     assert hits > 0                            # the reach branch fired (also pinned by golden trajectory 5)
-    eq, ev = _state_err(sim, orc)
+    eq, ev = state_err(sim, orc)
     assert eq < 2e-5 and ev < 5e-4
 
 
@@ -107,7 +65,7 @@ def test_env06_vs_oracle_with_gripper_term():
     within 3 cm and the cube is NOT re-randomised; TimeLimit resets inside the run exercise the block memory."""
     n, steps = 64, 36
     hits = 0
-    for t, sim, orc, og, oo, rew, done, trunc, _ in _run_pair(6, ARM, n, steps, seed=13, max_steps=14):
+    for t, sim, orc, og, oo, rew, done, trunc, _ in run_pair(6, ARM, n, steps, seed=13, max_steps=14):
         np.testing.assert_allclose(og, oo, rtol=0, atol=2e-5)
         if rew is not None:
             np.testing.assert_allclose(rew[0], rew[1], rtol=0, atol=2e-3)      # d(gripper)/d(jaw) <= 114 / rad
@@ -122,7 +80,7 @@ def test_env06_vs_oracle_with_gripper_term():
                 e3 = np.zeros(3); O.lib().so100o_end_effector(d.xpos[6], d.xmat[6], e3.ctypes.data_as(O.C.c_void_p))
                 O.arr(d.xpos)[8] = e3
     assert hits >= 4 * (n // 4)                # forced reaches + the first step after every reset (all poses zero, Q1)
-    eq, ev = _state_err(sim, orc)
+    eq, ev = state_err(sim, orc)
     assert eq < 2e-5 and ev < 5e-4
 
 
@@ -142,7 +100,7 @@ def _lookat_envs_vs_oracle(kind, flags, pad_iters):
     table, so the pad narrowphase runs and finds nothing -- the results must be the NOPADS ones to the same tolerance"""
     n, steps = 64, 60
     n_px = n_px_bad = 0
-    for t, sim, orc, og, oo, rew, done, trunc, _ in _run_pair(kind, flags, n, steps, seed=20 + kind, action_scale=0.6, pad_iters=pad_iters):
+    for t, sim, orc, og, oo, rew, done, trunc, _ in run_pair(kind, flags, n, steps, seed=20 + kind, action_scale=0.6, pad_iters=pad_iters):
         np.testing.assert_allclose(og[:, :6], oo[:, :6], rtol=0, atol=1e-6)
         d = np.abs(og[:, 6:] - oo[:, 6:])
         n_px += d.size; n_px_bad += int((d > 1e-4).sum())
@@ -152,14 +110,14 @@ def _lookat_envs_vs_oracle(kind, flags, pad_iters):
             np.testing.assert_allclose(rew[0], rew[1], rtol=0, atol=1.2e-2 if kind == 4 else 2e-3)
             np.testing.assert_array_equal(done[0].astype(bool), done[1])
     assert n_px_bad <= 0.01 * n_px               # off-by-one pixels are rare
-    eq, ev = _state_err(sim, orc)
+    eq, ev = state_err(sim, orc)
     assert eq < 3e-5 and ev < 5e-4
 
 
 def test_env05_termination_and_autoreset():
     """Rotate the base away until the cube is lost for > 30 steps: terminated, terminal obs, auto-reset."""
     n = 64
-    sim = _sim(5, n, flags=NOPADS, contact_iters=6, max_episode_steps=0, seed=3)
+    sim = make_sim(5, n, flags=NOPADS, contact_iters=6, max_episode_steps=0, seed=3)
     orc = [O.OracleEnv(5, flags=NOPADS, iters=0, seed=3, env_id=i) for i in range(n)]
     for e in orc:
         e.e.max_episode_steps = 0
@@ -188,7 +146,7 @@ def test_env05_termination_and_autoreset():
 
 def test_timelimit_truncation_and_episode_stats():
     n = 128
-    sim = _sim(1, n, flags=FREE, max_episode_steps=7, seed=1)
+    sim = make_sim(1, n, flags=FREE, max_episode_steps=7, seed=1)
     sim.reset()
     el = torch.arange(n, dtype=torch.int32).cuda() % 7
     sim.set_field("elapsed_steps", el)
@@ -214,7 +172,7 @@ def test_device_rng_matches_oracle_philox():
     """No injection: the device Philox stream equals the oracle's, so resets agree (up to fp32 sin/cos)."""
     n = 256
     for kind in (1, 2):
-        sim = _sim(kind, n, flags=FREE, seed=0xDEADBEEF12345, env_id_offset=1000)
+        sim = make_sim(kind, n, flags=FREE, seed=0xDEADBEEF12345, env_id_offset=1000)
         og = sim.reset().cpu().numpy()
         for i in range(0, n, 17):
             e = O.OracleEnv(kind, flags=FREE, seed=0xDEADBEEF12345, env_id=1000 + i)
@@ -229,7 +187,7 @@ def test_golden_trajectories_on_gpu(golden_dir, idx):
     """The trajectories recorded from the reference's own Python (over oracle physics) replayed on the HIP path."""
     tr = json.load(open(os.path.join(golden_dir, "trajectories.json")))[idx]
     n = 64                                              # 64 identical lanes; lane 0 and lane 63 are checked
-    sim = _sim(tr["kind"], n, flags=tr["flags"], solver_iters=4, contact_iters=6, max_episode_steps=0)
+    sim = make_sim(tr["kind"], n, flags=tr["flags"], solver_iters=4, contact_iters=6, max_episode_steps=0)
     rep = lambda v: torch.tensor(np.tile(np.array(v, np.float32), (n, 1))).cuda()
     ob = sim.reset(inject=rep(tr["reset_inject"])).cpu().numpy()
     np.testing.assert_allclose(ob[0], np.array(tr["reset_obs"], np.float32), rtol=0, atol=1e-6)
@@ -288,9 +246,9 @@ def test_non_finite_action_ends_only_that_episode(kind):
 
 
 def _run_pair_with(kind, flags, n, steps, seed, poison):
-    """_run_pair with the actions of step poison[0] overwritten per env by poison[1] (same values on both sides)."""
+    """gpu_support.run_pair with the actions of step poison[0] overwritten per env by poison[1] (same values on both sides)."""
     rs = np.random.RandomState(seed)
-    sim = _sim(kind, n, flags=flags, solver_iters=4, contact_iters=6, max_episode_steps=0, seed=seed)
+    sim = make_sim(kind, n, flags=flags, solver_iters=4, contact_iters=6, max_episode_steps=0, seed=seed)
     orc = [O.OracleEnv(kind, flags=flags, iters=0, seed=seed, env_id=i) for i in range(n)]
     for e in orc:
         e.e.max_episode_steps = 0
@@ -313,7 +271,7 @@ def _run_pair_with(kind, flags, n, steps, seed, poison):
 
 def test_state_roundtrip_and_errors():
     from so100_mujoco_rl_amd import lib
-    sim = _sim(1, 100, flags=FREE)
+    sim = make_sim(1, 100, flags=FREE)
     sim.reset()
     qpos, qvel = sim.get_state()
     qpos2 = qpos + 0.01; qvel2 = qvel - 0.5
@@ -344,7 +302,7 @@ def test_full_size_properties(kind, n, flags):
             epw //= 2
 
     def rollout(n_envs, offset, acts_slice):
-        sim = _sim(kind, n_envs, flags=flags, seed=99, env_id_offset=offset, envs_per_workgroup=epw)
+        sim = make_sim(kind, n_envs, flags=flags, seed=99, env_id_offset=offset, envs_per_workgroup=epw)
         outs = [sim.reset().clone()]
         for a in acts:
             ob, r, d, tr = sim.step(a[acts_slice].contiguous())
@@ -367,21 +325,11 @@ def test_full_size_properties(kind, n, flags):
 
 
 # ---- rollout-side fused policy kernel vs a plain PyTorch fp32 reference of the same op -----------------------------
-def _torch_policy(t, obs, noise):
-    h = torch.tanh(obs @ t["pi_w0"].T + t["pi_b0"]); h = torch.tanh(h @ t["pi_w1"].T + t["pi_b1"])
-    mean = h @ t["mu_w"].T + t["mu_b"]
-    g = torch.tanh(obs @ t["vf_w0"].T + t["vf_b0"]); g = torch.tanh(g @ t["vf_w1"].T + t["vf_b1"])
-    value = (g @ t["v_w"].T + t["v_b"]).squeeze(1)
-    act = mean + t["log_std"].exp() * noise
-    logp = (-0.5 * noise ** 2 - t["log_std"] - 0.9189385332046727).sum(1)
-    return act, value, logp
-
-
 @pytest.mark.parametrize("kind", [1, 5])
 def test_policy_kernel_vs_torch(kind):
     from so100_mujoco_rl_amd import lib
     n = 1000                                                   # not a multiple of 64: tail lanes are masked
-    sim = _sim(kind, n, flags=FREE)
+    sim = make_sim(kind, n, flags=FREE)
     od = sim.obs_dim
     g = torch.Generator(device="cuda"); g.manual_seed(kind)
     rnd = lambda *s: torch.randn(*s, device="cuda", generator=g)
@@ -395,7 +343,7 @@ def test_policy_kernel_vs_torch(kind):
     act_env = torch.zeros(n, 6, device="cuda"); act_raw = torch.zeros_like(act_env)
     value = torch.zeros(n, device="cuda"); logp = torch.zeros(n, device="cuda"); row = torch.zeros(n, od + 10, device="cuda")
     sim.policy_forward(obs, act_env, 0, noise=noise, act_raw=act_raw, value=value, logp=logp, rollout_row=row)
-    a, v, lp = _torch_policy({k: w.double() for k, w in t.items()}, obs.double(), noise.double())      # float64 reference
+    a, v, lp = torch_policy({k: w.double() for k, w in t.items()}, obs.double(), noise.double())      # float64 reference
     ea, ev, el = [float((x.double() - y).abs().max()) for x, y in ((act_raw, a), (value, v), (logp, lp))]
     print(f"[policy kernel vs fp64, obs width {od}] action {ea:.2e} value {ev:.2e} log-prob {el:.2e}")
     # tolerance: fp32 accumulation order + exp2-based tanh (abs err < 2e-7 per activation); measured on MI355X against fp64:
@@ -405,12 +353,12 @@ def test_policy_kernel_vs_torch(kind):
     assert torch.equal(row[:, :od], obs) and torch.equal(row[:, od:od + 6], act_raw)
     assert torch.equal(row[:, od + 8], value) and torch.equal(row[:, od + 9], logp)
     # device RNG: deterministic, depends on the step counter, standard normal
-    sim2 = _sim(kind, 65536, flags=FREE, seed=5); sim2.set_policy(t)
+    sim2 = make_sim(kind, 65536, flags=FREE, seed=5); sim2.set_policy(t)
     o2 = torch.zeros(65536, od, device="cuda"); a1 = torch.zeros(65536, 6, device="cuda"); a2 = torch.zeros_like(a1); a3 = torch.zeros_like(a1)
     e1 = torch.zeros_like(a1)
     sim2.policy_forward(o2, e1, 7, act_raw=a1); sim2.policy_forward(o2, e1, 7, act_raw=a2); sim2.policy_forward(o2, e1, 8, act_raw=a3)
     assert torch.equal(a1, a2) and not torch.equal(a1, a3)
-    mean0, _, _ = _torch_policy(t, o2[:1], torch.zeros(1, 6, device="cuda"))
+    mean0, _, _ = torch_policy(t, o2[:1], torch.zeros(1, 6, device="cuda"))
     eps = (a1 - mean0) / t["log_std"].exp()
     assert eps.mean().abs() < 0.01 and (eps.std() - 1).abs() < 0.01 and (eps ** 4).mean().sub(3).abs() < 0.1
     # the env step fills reward / done into the same rollout row
@@ -425,7 +373,7 @@ def test_north_star_1000_steps():
     n, steps = 16, 1000
     for flags in (ARM, FREE, NOPADS):
         rs = np.random.RandomState(3)
-        sim = _sim(1, n, flags=flags, solver_iters=2, max_episode_steps=0, seed=2)     # 2 sweeps = the product default
+        sim = make_sim(1, n, flags=flags, solver_iters=2, max_episode_steps=0, seed=2)     # 2 sweeps = the product default
         orc = [O.OracleEnv(1, flags=flags, iters=0, seed=2, env_id=i) for i in range(n)]
         for e in orc:
             e.e.max_episode_steps = 0
@@ -541,7 +489,7 @@ def test_c_abi_from_plain_cpp(tmp_path):
     out = subprocess.check_output([exe, str(n), str(steps)], text=True)
     m = re.search(r"obs_checksum (\S+)\s+reward_sum (\S+)", out)
     assert m, out
-    sim = _sim(1, n, flags=lib.F_REFERENCE, solver_iters=3, contact_iters=4, seed=42)     # SO100_F_REFERENCE in abi_demo.cpp
+    sim = make_sim(1, n, flags=lib.F_REFERENCE, solver_iters=3, contact_iters=4, seed=42)     # SO100_F_REFERENCE in abi_demo.cpp
     sim.reset()
     idx = np.arange(6 * n, dtype=np.uint64)
     a = ((idx * np.uint64(2654435761)) % np.uint64(2001)).astype(np.float32) / np.float32(1000.0) - np.float32(1.0)   # as abi_demo.cpp (64-bit product)
@@ -634,10 +582,9 @@ def test_stepwise_calls_are_graph_capturable():
     n, T = 512, 6
     outs = []
     for use_graph in (False, True):
-        sim = _sim(1, n, flags=ARM, seed=8)
+        sim = make_sim(1, n, flags=ARM, seed=8)
         sd = RolloutCollector.random_policy_state(15, sim.device, seed=4)
-        from so100_mujoco_rl_amd.lib import POLICY_TENSORS, SB3_STATE_DICT_KEYS
-        sim.set_policy({k: sd[SB3_STATE_DICT_KEYS[k]].contiguous() for k in POLICY_TENSORS})
+        sim.set_policy(policy_tensors(sd))
         sim.reset()
         act = torch.zeros(n, 6, device="cuda"); row = torch.zeros(n, 25, device="cuda")
         rows = []
@@ -670,8 +617,8 @@ def test_multiwave_step_kernel_equals_throughput_kernel(kind, flags):
     handle (throughput kernel) must evolve exactly like a 200-env handle (latency kernel) under the same actions: same
     arithmetic, split over waves -- results agree to the last bit or two, including TimeLimit resets and the tail workgroup."""
     n, big, steps = 200, 16384 + 192, 40
-    a_mw = _sim(kind, n, flags=flags, seed=9, max_episode_steps=15)
-    a_sw = _sim(kind, big, flags=flags, seed=9, max_episode_steps=15)
+    a_mw = make_sim(kind, n, flags=flags, seed=9, max_episode_steps=15)
+    a_sw = make_sim(kind, big, flags=flags, seed=9, max_episode_steps=15)
     o1 = a_mw.reset().clone(); o2 = a_sw.reset()[:n].clone()
     assert torch.equal(o1, o2)
     g = torch.Generator(device="cuda"); g.manual_seed(1)
@@ -695,7 +642,7 @@ def test_dense_throughput_kernel_131072():
     n, steps = 131072, 5
     rs = np.random.RandomState(12)
     sample = np.sort(rs.choice(n, 32, replace=False)); sample[0] = 0; sample[-1] = n - 1
-    sim = _sim(1, n, flags=NOPADS, solver_iters=4, seed=23, max_episode_steps=3)
+    sim = make_sim(1, n, flags=NOPADS, solver_iters=4, seed=23, max_episode_steps=3)
     orc = [O.OracleEnv(1, flags=NOPADS, iters=0, seed=23, env_id=int(i)) for i in sample]
     for e in orc:
         e.e.max_episode_steps = 3
@@ -714,7 +661,7 @@ def test_dense_throughput_kernel_131072():
     full = torch.cat(trace, 1); sim.close()
     halves = []
     for off in (0, n // 2):
-        s2 = _sim(1, n // 2, flags=NOPADS, solver_iters=4, seed=23, max_episode_steps=3, env_id_offset=off); s2.reset(); tr2 = []
+        s2 = make_sim(1, n // 2, flags=NOPADS, solver_iters=4, seed=23, max_episode_steps=3, env_id_offset=off); s2.reset(); tr2 = []
         for t in range(steps):
             ob, r, d, _ = s2.step(acts[t][off:off + n // 2].contiguous())
             tr2.append(torch.cat([ob, r[:, None], d[:, None].float()], 1).clone())
@@ -731,7 +678,7 @@ def test_large_batch_dispatch_65536_vs_oracle():
     rs = np.random.RandomState(11)
     sample = np.sort(rs.choice(n, 64, replace=False)); sample[0] = 0; sample[-1] = n - 1
     for kind, flags in ((1, FREE), (1, NOPADS)):
-        sim = _sim(kind, n, flags=flags, solver_iters=4, seed=21, max_episode_steps=4)       # TimeLimit resets inside the run
+        sim = make_sim(kind, n, flags=flags, solver_iters=4, seed=21, max_episode_steps=4)       # TimeLimit resets inside the run
         orc = [O.OracleEnv(kind, flags=flags, iters=0, seed=21, env_id=int(i)) for i in sample]
         for e in orc:
             e.e.max_episode_steps = 4
@@ -754,7 +701,7 @@ def test_large_batch_dispatch_65536_vs_oracle():
         # determinism + shard invariance of the throughput kernel (two half-size handles, both still above the 16 384 switch)
         halves = []
         for off in (0, n // 2):
-            s2 = _sim(kind, n // 2, flags=flags, solver_iters=4, seed=21, max_episode_steps=4, env_id_offset=off)
+            s2 = make_sim(kind, n // 2, flags=flags, solver_iters=4, seed=21, max_episode_steps=4, env_id_offset=off)
             s2.reset()
             g2 = torch.Generator(device="cuda"); g2.manual_seed(5); tr2 = []
             for t in range(steps):
@@ -766,14 +713,13 @@ def test_large_batch_dispatch_65536_vs_oracle():
         if flags == FREE:                                    # the policy kernel at the same batch (grid-stride over 1024 tiles)
             from so100_mujoco_rl_amd.collector import RolloutCollector
             sd = RolloutCollector.random_policy_state(15, sim.device, seed=3)
-            from so100_mujoco_rl_amd.lib import POLICY_TENSORS, SB3_STATE_DICT_KEYS
-            tens = {k: sd[SB3_STATE_DICT_KEYS[k]].contiguous() for k in POLICY_TENSORS}
+            tens = policy_tensors(sd)
             sim.set_policy(tens)
             noise = torch.randn(n, 6, device="cuda", generator=g)
             act_env = torch.empty(n, 6, device="cuda"); raw = torch.empty(n, 6, device="cuda")
             val = torch.empty(n, device="cuda"); lp = torch.empty(n, device="cuda")
             sim.policy_forward(sim.obs, act_env, 0, noise=noise, act_raw=raw, value=val, logp=lp)
-            ra, rv, rl = _torch_policy(tens, sim.obs, noise)
+            ra, rv, rl = torch_policy(tens, sim.obs, noise)
             torch.testing.assert_close(raw, ra, rtol=0, atol=2e-5); torch.testing.assert_close(val, rv, rtol=0, atol=2e-5)
             torch.testing.assert_close(lp, rl, rtol=0, atol=1e-4)
             torch.testing.assert_close(act_env, ra.clamp(-1, 1), rtol=0, atol=2e-5)
@@ -784,12 +730,11 @@ def test_policy_saturation_is_finite():
     """A saturated hidden unit (pre-activation far beyond +-44, where exp(2x) overflows) must give tanh = +-1, not NaN: a trained
     or loaded SB3 policy with large weights / observations would otherwise write NaN actions and values into the rollout buffer."""
     from so100_mujoco_rl_amd.collector import RolloutCollector
-    from so100_mujoco_rl_amd.lib import POLICY_TENSORS, SB3_STATE_DICT_KEYS
     n = 256
-    sim = _sim(1, n, flags=FREE, seed=1)
+    sim = make_sim(1, n, flags=FREE, seed=1)
     sim.reset()
     sd = RolloutCollector.random_policy_state(15, sim.device, seed=3)
-    tens = {k: sd[SB3_STATE_DICT_KEYS[k]].clone().contiguous() for k in POLICY_TENSORS}
+    tens = {k: v.clone() for k, v in policy_tensors(sd).items()}
     for k in ("pi_w0", "vf_w0", "pi_w1", "vf_w1"):
         tens[k] *= 400.0                                     # pre-activations of several hundred in both layers
     sim.set_policy(tens)
@@ -801,7 +746,7 @@ def test_policy_saturation_is_finite():
     sim.policy_forward(obs, act_env, 0, noise=noise, act_raw=raw, value=val, logp=lp)
     for x in (act_env, raw, val, lp):
         assert torch.isfinite(x).all()
-    ra, rv, rl = _torch_policy(tens, obs, noise)
+    ra, rv, rl = torch_policy(tens, obs, noise)
     torch.testing.assert_close(raw, ra, rtol=0, atol=1e-4); torch.testing.assert_close(val, rv, rtol=1e-5, atol=1e-4)
     # and through the persistent rollout kernel (its own copy of the policy phase)
     buf = torch.zeros(3, n, 25, device="cuda")
@@ -867,7 +812,7 @@ def test_device_outputs_stay_current_after_numpy_steps(tmp_path):
 def test_odd_batch_sizes_and_frame_skips_vs_oracle(n, frame_skip):
     """Tail workgroups (N not a multiple of 64, N = 1) and frame_skip values other than the reference's 16, against the oracle."""
     rs = np.random.RandomState(n)
-    sim = _sim(2, n, flags=NOPADS, solver_iters=4, contact_iters=6, max_episode_steps=9, seed=5, frame_skip=frame_skip)
+    sim = make_sim(2, n, flags=NOPADS, solver_iters=4, contact_iters=6, max_episode_steps=9, seed=5, frame_skip=frame_skip)
     orc = [O.OracleEnv(2, flags=NOPADS, iters=0, seed=5, env_id=i) for i in range(n)]
     for e in orc:
         e.e.max_episode_steps = 9; e.e.frame_skip = frame_skip
@@ -883,9 +828,9 @@ def test_odd_batch_sizes_and_frame_skips_vs_oracle(n, frame_skip):
         np.testing.assert_allclose(rg.cpu().numpy(), np.array([r[1] for r in res]), rtol=0, atol=1e-4)
         np.testing.assert_array_equal(dg.cpu().numpy().astype(bool), np.array([r[2] or r[3] for r in res]))
     # and the rollout kernel on the same odd sizes: finite, right shape, TimeLimit fires
-    from so100_mujoco_rl_amd.collector import RolloutCollector, SB3_STATE_DICT_KEYS, POLICY_TENSORS
+    from so100_mujoco_rl_amd.collector import RolloutCollector
     sd = RolloutCollector.random_policy_state(sim.obs_dim, sim.device, seed=0)
-    sim.set_policy({k: sd[SB3_STATE_DICT_KEYS[k]].contiguous() for k in POLICY_TENSORS})
+    sim.set_policy(policy_tensors(sd))
     buf = torch.zeros(12, n, sim.obs_dim + 10, device="cuda")
     sim.rollout(buf, 0)
     assert torch.isfinite(buf).all() and float(buf[..., -3].sum()) >= n

@@ -16,11 +16,10 @@ import pytest
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
+from gpu_support import LOG2PI_HALF, policy_tensors, run_pair, state_err   # noqa: E402
 from oracle import so100_oracle as O                      # noqa: E402  (the checker)
-from test_gpu_parity import FREE, _run_pair, _state_err   # noqa: E402
-from test_rng_reference import UNINJECTED_CASES, UNINJECTED_N, UNINJECTED_SEED, UNINJECTED_STEPS, UNINJECTED_TIMELIMIT      # noqa: E402
+from scenes import FREE, UNINJECTED_CASES, UNINJECTED_N, UNINJECTED_SEED, UNINJECTED_STEPS, UNINJECTED_TIMELIMIT      # noqa: E402
 
-LOG2PI_HALF = 0.9189385332046727
 BIG_SEED = 0xDEADBEEF12345                                 # seed_hi != 0
 # bounds against the float64 reference sampler: about 3x the worst error measured on MI355X over every case below
 NOISE_EPS = 2.3e-6                                         # measured 7.6e-7: |raw action - eps_ref| over every case below, both kernels (they agree bit for bit)
@@ -34,11 +33,6 @@ def _noise_policy(od, device, seed=0):
     sd["action_net.weight"] = torch.zeros_like(sd["action_net.weight"]); sd["action_net.bias"] = torch.zeros_like(sd["action_net.bias"])
     assert float(sd["log_std"].abs().max()) == 0.0
     return sd
-
-
-def _tensors(sd):
-    from so100_mujoco_rl_amd.lib import POLICY_TENSORS, SB3_STATE_DICT_KEYS
-    return {k: sd[SB3_STATE_DICT_KEYS[k]].contiguous() for k in POLICY_TENSORS}
 
 
 def _gid(offset, n):
@@ -69,7 +63,7 @@ def test_stepwise_kernel_noise_vs_reference(kind, seed, offset):
     n = 200
     sim = So100Sim(kind, n, flags=FREE, seed=seed, env_id_offset=offset)
     od = sim.obs_dim
-    sim.set_policy(_tensors(_noise_policy(od, sim.device, seed=kind)))
+    sim.set_policy(policy_tensors(_noise_policy(od, sim.device, seed=kind)))
     g = torch.Generator(device="cuda"); g.manual_seed(kind)
     obs = torch.randn(n, od, device="cuda", generator=g).contiguous()
     # exp(0) == 1 on the device and the zero head gives mean == 0: an injected noise comes back as the raw action, bit for bit
@@ -127,7 +121,7 @@ def test_persistent_and_stepwise_kernels_draw_the_same_noise(kind):
     n, seed, offset = 200, BIG_SEED, 1000
     b = _collect_two_chunks(kind, n, seed, offset, 32)
     sim = So100Sim(kind, n, flags=FREE, seed=seed, env_id_offset=offset)
-    sim.set_policy(_tensors(_noise_policy(sim.obs_dim, sim.device, seed=kind)))
+    sim.set_policy(policy_tensors(_noise_policy(sim.obs_dim, sim.device, seed=kind)))
     act_env = torch.zeros(n, 6, device="cuda"); raw = torch.zeros_like(act_env); logp = torch.zeros(n, device="cuda")
     for t in range(15):
         sim.policy_forward(b["obs"][t].contiguous(), act_env, t, act_raw=raw, logp=logp)
@@ -181,7 +175,7 @@ def test_uninjected_env_draws_vs_oracle(kind):
     reach = kind in (1, 2, 6)
     n_px = n_px_bad = resets = 0
     worst_o = worst_r = 0.0
-    for t, sim, orc, og, oo, rew, done, trunc, _ in _run_pair(kind, flags, n, steps, seed=seed, action_scale=scale, max_steps=tl, inject=False):
+    for t, sim, orc, og, oo, rew, done, trunc, _ in run_pair(kind, flags, n, steps, seed=seed, action_scale=scale, max_steps=tl, inject=False):
         if t < 0:
             np.testing.assert_allclose(og, oo, rtol=0, atol=1e-6)              # the reset observation
             continue
@@ -199,7 +193,7 @@ def test_uninjected_env_draws_vs_oracle(kind):
             np.testing.assert_allclose(rew[0], rew[1], rtol=0, atol=1.2e-2 if kind == 4 else 2e-3)
     assert t == steps - 1
     assert resets >= 2*n
-    eq, ev = _state_err(sim, orc)
+    eq, ev = state_err(sim, orc)
     print(f"[un-injected env draws vs oracle, kind {kind}] obs {worst_o:.2e} reward {worst_r:.2e} pixel entries off by > 1e-4: {n_px_bad} of {n_px}; "
           f"qpos {eq:.2e} qvel {ev:.2e}; resets {resets}")
     assert n_px_bad <= 0.01*n_px

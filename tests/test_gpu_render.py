@@ -6,7 +6,6 @@ The device compiles with -ffp-contract=fast, the host instantiation with -ffp-co
 hence the same edge-tolerant bounds as tests/test_render_cpu.py."""
 import ctypes as C
 import io
-import os
 import struct
 
 import numpy as np
@@ -15,19 +14,16 @@ import pytest
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
+import render_checks as T                                 # noqa: E402  (host instantiation + the pass conditions)
 import render_ref as RR                                   # noqa: E402
-import test_render_cpu as T                               # noqa: E402  (host instantiation + the pass conditions)
+from hostlibs import rendercheck                          # noqa: E402
 
 SIZES = [(64, 64), (84, 84), (83, 61), (270, 480)]
 
 
 @pytest.fixture(scope="module")
 def H():
-    import subprocess
-    subprocess.check_call(["make", "-C", os.path.join(T.HERE, "_rendercheck"), "-s"])
-    h = C.CDLL(os.path.join(T.HERE, "_rendercheck", "librendercheck.so"))
-    h.rc_render.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    return h
+    return rendercheck()
 
 
 @pytest.fixture(scope="module")
@@ -234,7 +230,7 @@ def test_record_writes_a_video(tmp_path, monkeypatch):
     assert r.exit_code == 0
     traj = np.load(tmp_path / "movies" / "Env03-v1_PPO.npz")["trajectory"]
     assert traj.shape == (64, 13 + 12 + 8 + 6)
-    chunks, frames, idx, _, _ = T._parse_avi(str(tmp_path / "movies" / "rec-Env03-v1-step-0-to-step-64.avi"))
+    chunks, frames, idx, _, _ = T.parse_avi(str(tmp_path / "movies" / "rec-Env03-v1-step-0-to-step-64.avi"))
     assert struct.unpack("<10I", chunks[b"avih"][:40])[4] == 64 and len(frames) == 64 and len(idx) == 64
     for jpg in frames[::9]:
         im = np.asarray(Image.open(io.BytesIO(jpg)).convert("RGB"))

@@ -15,10 +15,9 @@ import pytest
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
+from gpu_support import LOG2PI_HALF, torch_policy          # noqa: E402
 from oracle import so100_oracle as O                      # noqa: E402  (the checker)
-from test_gpu_parity import FREE, _torch_policy           # noqa: E402
-
-LOG2PI_HALF = 0.9189385332046727
+from scenes import FREE                                   # noqa: E402
 
 
 @pytest.mark.parametrize("n,epw", [(200, 0), (4096, 0), (200, 64)])
@@ -72,7 +71,7 @@ def _saturating_policy(od, seed):
 def _fp64(t, obs):
     """(mean, value) of both towers in float64 on the host from float32 weights and observations"""
     t64 = {k: v.double().cpu() for k, v in t.items()}
-    mean, value, _ = _torch_policy(t64, obs.double().cpu(), torch.zeros(obs.shape[0], 6, dtype=torch.float64))
+    mean, value, _ = torch_policy(t64, obs.double().cpu(), torch.zeros(obs.shape[0], 6, dtype=torch.float64))
     return mean, value
 
 

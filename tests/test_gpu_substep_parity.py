@@ -6,7 +6,7 @@ kernel with 16 / 32 / 64 envs per workgroup (4 / 2 / 1 cooperating contact lanes
 a flag set WITHOUT a compile-time instantiation (run-time-flags kernels so100_step_mw / so100_step_fused<K, -1>).
 
 Every case runs at the shipped solver settings (2, 20) and at (4, 30), with the same bounds (the residual check of the 2-sweep leg is
-split: tests/test_substep_parity.py check_residual).  Stated fp32 bound on h * qacc from identical fp32-rounded states (h = 2 ms):
+split: tests/substep_harness.py check_residual).  Stated fp32 bound on h * qacc from identical fp32-rounded states (h = 2 ms):
 2e-6 rad/s without pad contact, 5e-5 rad/s (m/s for the cube) and 1e-2 relative with it (stiff pad rows: condition ~1e5).
 "parity unpinned (physics)": MuJoCo is not available."""
 import numpy as np
@@ -16,28 +16,24 @@ torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 import substep_harness as SH                              # noqa: E402
+from gpu_support import inject_state, make_sim            # noqa: E402
 from oracle import so100_oracle as O                      # noqa: E402  (the checker)
-from test_substep_parity import SHIPPED, check_residual   # noqa: E402
-
-REFP = O.F_REFERENCE
-C5 = O.F_CONTACT5
-UNINSTANTIATED = O.F_FRICTIONLOSS | O.F_FLOOR | O.F_PADS_FLOOR      # 21: no limits -> KindOps::step falls through to <K, -1>
+from scenes import (C5, LCUBE, LINKS, REFP, SHIPPED, UNINSTANTIATED, floor_batch, grasp_batch, idle_batch, link_cube_batch,   # noqa: E402
+                    wrist_first_batch)
 
 
 class HipDevice:
     def __init__(self, n, m, flags, iters=(4, 30)):
-        from so100_mujoco_rl_amd.lib import So100Sim
-        self.sim = So100Sim(1, n, flags=flags, solver_iters=iters[0], contact_iters=iters[1], frame_skip=1, max_episode_steps=0, seed=3)
+        self.sim = make_sim(1, n, flags=flags, solver_iters=iters[0], contact_iters=iters[1], frame_skip=1, max_episode_steps=0, seed=3)
         self.n, self.m, self.flags, self.iters = n, m, flags, iters
         self.twin = None
         self.sim.reset()
-        QP = np.zeros((n, 13)); QP[:, 9] = 1.0; QP[:, 6:9] = [0.2, -0.2, 0.0099]; QP[:, :6] = [0, -1.5, 1.5, 0.5, 0, 0.2]
-        self.QP = QP; self.QV = np.zeros((n, 12)); self.A = np.zeros((n, 6), np.float32)
+        self.QP, self.QV = idle_batch(n); self.A = np.zeros((n, 6), np.float32)
 
     def __call__(self, q32, v32, act):
         m, sim = self.m, self.sim
         self.QP[:m] = q32; self.QV[:m] = v32; self.A[:m] = act
-        sim.set_state(torch.from_numpy(np.ascontiguousarray(self.QP.T, np.float32)).cuda(), torch.from_numpy(np.ascontiguousarray(self.QV.T, np.float32)).cuda())
+        inject_state(sim, self.QP, self.QV)
         if self.iters[0] < 4:                             # every state row (warm starts included) as the step sees it, for resolve()
             self.before = {f: sim.get_field(f, dtype=torch.int32) for f in sim.field_names()}
         sim.step(torch.from_numpy(self.A).cuda())
@@ -49,22 +45,12 @@ class HipDevice:
 
     def resolve(self, envs, iters):
         """the last substep again on a twin handle (same batch size, so the same kernel) with `iters` block-PGS sweeps, from the same state rows"""
-        from so100_mujoco_rl_amd.lib import So100Sim
         if self.twin is None:
-            self.twin = So100Sim(1, self.n, flags=self.flags, solver_iters=iters, contact_iters=self.iters[1], frame_skip=1, max_episode_steps=0, seed=3)
+            self.twin = make_sim(1, self.n, flags=self.flags, solver_iters=iters, contact_iters=self.iters[1], frame_skip=1, max_episode_steps=0, seed=3)
         for f, w in self.before.items():
             self.twin.set_field(f, w)
         self.twin.step(torch.from_numpy(self.A).cuda())
         return self.twin.get_state()[1].cpu().numpy().T[envs].astype(np.float64)
-
-
-def _check(T, min_contact, min_coupled=0, iters=(4, 30)):
-    assert T.contact >= min_contact and T.coupled >= min_coupled
-    assert T.knife <= 0.02*T.pairs
-    assert T.count_mismatch == 0 and T.set_mismatch == 0
-    assert T.worst_dv < 2e-6
-    assert T.worst_dv_contact < 5e-5 and T.worst_rel < 1e-2
-    check_residual(T, iters)
 
 
 @pytest.mark.parametrize("n,flags", [(96, REFP), (8192, REFP), (16384, REFP), (16384 + 96, REFP), (96, UNINSTANTIATED), (16384 + 96, UNINSTANTIATED)])
@@ -80,9 +66,9 @@ def test_pad_floor_per_substep_at_shipped_settings(n, flags):
 
 def _pad_floor_per_substep(n, flags, iters):
     m, nsub = 96, 24
-    qpos, qvel, act = SH.floor_batch(m, 0)
+    qpos, qvel, act = floor_batch(m, 0)
     T = SH.run_substep_parity(HipDevice(n, m, flags, iters), qpos, qvel, act, flags, nsub, f"HIP {iters} n={n} flags={flags} pad/floor")
-    _check(T, m*nsub//3, iters=iters)
+    SH.check_tally(T, m*nsub//3, iters=iters)
 
 
 @pytest.mark.parametrize("n", [48, 8192, 16384 + 48])
@@ -99,11 +85,10 @@ def test_link_proxies_per_substep_at_shipped_settings(n):
 def _link_proxies_per_substep(n, iters):
     """SO100_F_LINKS_FLOOR (capsule proxies of the arm's collision meshes: contacts on ANY link, the general form of the solver), through
     the run-time-flags kernels: poses that reach the table wrist / forearm first"""
-    from test_substep_parity import wrist_first_batch, LINKS
     m, nsub = 48, 24
     qpos, qvel, act = wrist_first_batch(m, 0)
     T = SH.run_substep_parity(HipDevice(n, m, LINKS, iters), qpos, qvel, act, LINKS, nsub, f"HIP {iters} n={n} link proxies")
-    _check(T, m*nsub//3, iters=iters)
+    SH.check_tally(T, m*nsub//3, iters=iters)
 
 
 @pytest.mark.parametrize("n", [64, 8192, 16384, 16384 + 64])
@@ -119,9 +104,9 @@ def test_pad_cube_grasp_per_substep_at_shipped_settings(n):
 
 def _pad_cube_grasp_per_substep(n, iters):
     m, nsub = 64, 40
-    qpos, qvel, act = SH.grasp_batch(m, 1)
+    qpos, qvel, act = grasp_batch(m, 1)
     T = SH.run_substep_parity(HipDevice(n, m, C5, iters), qpos, qvel, act, C5, nsub, f"HIP {iters} n={n} grasp")
-    _check(T, m*nsub//3, m*nsub//4, iters=iters)
+    SH.check_tally(T, m*nsub//3, m*nsub//4, iters=iters)
 
 
 @pytest.mark.parametrize("n", [32, 8192, 16384 + 32])
@@ -139,13 +124,12 @@ def _link_cube_per_substep(n, iters):
     """SO100_F_LINKS_CUBE (Rotation_Pitch / Upper_Arm capsules vs the cube: the pairs the reference scene leaves live) through the
     run-time-flags kernels -- 4 / 2 / 1 contact lanes per env and the one-wave kernel: the cube placed against either capsule, arm and cube
     solved together (12 unknowns, records on links 0 / 1); then the closing-jaw grasp with every proxy pair switched on as well"""
-    from test_substep_parity import link_cube_batch, LCUBE
     m, nsub = 32, 12
     qpos, qvel, act = link_cube_batch(m, 0)
     T = SH.run_substep_parity(HipDevice(n, m, LCUBE, iters), qpos, qvel, act, LCUBE, nsub, f"HIP {iters} n={n} link proxies vs cube")
-    _check(T, m*nsub//3, m*nsub//3, iters=iters)
+    SH.check_tally(T, m*nsub//3, m*nsub//3, iters=iters)
     if n == 32:
         flags = LCUBE | O.F_PADS_CUBE
-        qpos, qvel, act = SH.grasp_batch(m, 2)
+        qpos, qvel, act = grasp_batch(m, 2)
         T = SH.run_substep_parity(HipDevice(n, m, flags, iters), qpos, qvel, act, flags, 32, f"HIP {iters} n={n} all proxies + grasp")
-        _check(T, m*32//4, m*32//5, iters=iters)
+        SH.check_tally(T, m*32//4, m*32//5, iters=iters)

@@ -6,44 +6,22 @@ The two sides share NO code: the oracle is MuJoCo-structured (world-frame spatia
 convergence); the device headers use a different formulation throughout.  Agreement to 1e-14 in fp64 is the evidence
 that both are right; the fp32 numbers below are the device's expected round-off."""
 import ctypes as C
-import json
-import os
-import subprocess
 
 import numpy as np
 import pytest
 from scipy.spatial.transform import Rotation as R
 
+from hostlibs import hostcheck, ptr
 from oracle import so100_oracle as O
-
-HERE = os.path.dirname(os.path.abspath(__file__))
+from scenes import ARM, L, M, fresh
 
 
 @pytest.fixture(scope="module")
 def H():
-    subprocess.check_call(["make", "-C", os.path.join(HERE, "_hostcheck"), "-s"])
-    h = C.CDLL(os.path.join(HERE, "_hostcheck", "libhostcheck.so"))
-    h.hc_env_new.restype = C.c_void_p
-    h.hc_env_free.argtypes = [C.c_void_p]
-    h.hc_env_reset.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_uint, C.c_void_p, C.c_void_p]
-    h.hc_env_step.argtypes = [C.c_void_p, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint] + [C.c_void_p] * 7
-    h.hc_env_qpos.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    return h
+    return hostcheck()
 
 
-L = O.lib(); M = O.model()
 RNG = np.array(M.jnt_range)
-
-
-def p(a):
-    return a.ctypes.data_as(C.c_void_p)
-
-
-def fresh(q6=None, v6=None):
-    d = O.Data(); L.so100o_reset_data(C.byref(M), C.byref(d))
-    if q6 is not None: O.arr(d.qpos)[:6] = q6
-    if v6 is not None: O.arr(d.qvel)[:6] = v6
-    return d
 
 
 def test_sincos_fp32(H):
@@ -63,14 +41,14 @@ def test_dynamics_and_poses_match_oracle(H):
         d = fresh(q, v); L.so100o_forward(C.byref(M), C.byref(d), 0, 0)
         Mo = O.arr(d.M).reshape(12, 12)[:6, :6]; bo = O.arr(d.qfrc_bias)[:6]
         Mh = np.zeros(36); bh = np.zeros(6)
-        H.hc_dyn_d(p(q), p(v), p(Mh), p(bh))
+        H.hc_dyn_d(ptr(q), ptr(v), ptr(Mh), ptr(bh))
         w["M"] = max(w["M"], np.abs(Mh.reshape(6, 6) - Mo).max()); w["b"] = max(w["b"], np.abs(bh - bo).max())
-        H.hc_dyn_f(p(q), p(v), p(Mh), p(bh))
+        H.hc_dyn_f(ptr(q), ptr(v), ptr(Mh), ptr(bh))
         w["Mf"] = max(w["Mf"], np.abs(Mh.reshape(6, 6) - Mo).max()); w["bf"] = max(w["bf"], np.abs(bh - bo).max())
         out = np.zeros(27)
         ref = np.r_[O.arr(d.xpos)[5], O.arr(d.xpos)[6], O.arr(d.xmat)[6], O.arr(d.cam_xpos), O.arr(d.cam_xmat)]
-        H.hc_poses_d(p(q), p(out)); w["pose"] = max(w["pose"], np.abs(out - ref).max())
-        H.hc_poses_f(p(q), p(out)); w["posef"] = max(w["posef"], np.abs(out - ref).max())
+        H.hc_poses_d(ptr(q), ptr(out)); w["pose"] = max(w["pose"], np.abs(out - ref).max())
+        H.hc_poses_f(ptr(q), ptr(out)); w["posef"] = max(w["posef"], np.abs(out - ref).max())
     assert w["M"] < 1e-15 and w["b"] < 1e-13 and w["pose"] < 1e-14          # fp64: same mechanics, different algorithm
     assert w["Mf"] < 1e-7 and w["bf"] < 2e-6 and w["posef"] < 2e-6          # fp32 round-off
 
@@ -84,12 +62,9 @@ def _arm_traj(H, fn, iters_o, iters_h, flags, nenv, nstep, seed):
             ctrl = O.arr(d.qpos)[:6] + rs.uniform(-1, 1, 6) * 0.075
             O.arr(d.ctrl)[:] = ctrl
             L.so100o_step(C.byref(M), C.byref(d), flags, iters_o, 16)
-            fn(p(qh), p(vh), p(ctrl.copy()), p(ff), p(fl), flags, iters_h, 16)
+            fn(ptr(qh), ptr(vh), ptr(ctrl.copy()), ptr(ff), ptr(fl), flags, iters_h, 16)
             wq = max(wq, np.abs(qh - O.arr(d.qpos)[:6]).max()); wv = max(wv, np.abs(vh - O.arr(d.qvel)[:6]).max())
     return wq, wv
-
-
-ARM = O.F_FRICTIONLOSS | O.F_LIMITS | O.F_CUBE_PINNED
 
 
 def test_block_pgs_reaches_the_oracle_optimum(H):
@@ -122,7 +97,7 @@ def _cube_traj(H, fn, iters_h, tilt, seed, nsub=400):
         ph = pos.copy(); qh = quat.copy(); vh = vel.copy(); wh = np.zeros(16); ap = np.zeros(3)
         for _ in range(nsub // 8):
             L.so100o_step(C.byref(M), C.byref(d), O.F_FLOOR, 0, 8)
-            fn(p(ph), p(qh), p(vh), p(wh), p(ap), O.F_FLOOR, iters_h, 8)
+            fn(ptr(ph), ptr(qh), ptr(vh), ptr(wh), ptr(ap), O.F_FLOOR, iters_h, 8)
             w = max(w, np.abs(ph - O.arr(d.qpos)[6:9]).max(), np.abs(qh - O.arr(d.qpos)[9:13]).max())
             wv = max(wv, np.abs(vh - O.arr(d.qvel)[6:]).max())
     return w, wv
@@ -149,13 +124,13 @@ def test_task_layer_fp32_vs_oracle(H, kind, flags):
         e = O.OracleEnv(kind, flags=flags, iters=0); e.e.max_episode_steps = 25
         h = H.hc_env_new(kind)
         inj = rs.random_sample(16).astype(np.float32)
-        oo = e.reset(inject=inj); oh = np.zeros(od, np.float32); H.hc_env_reset(h, kind, 0, 0, p(inj), p(oh))
+        oo = e.reset(inject=inj); oh = np.zeros(od, np.float32); H.hc_env_reset(h, kind, 0, 0, ptr(inj), ptr(oh))
         np.testing.assert_allclose(oh, oo, rtol=0, atol=1e-6)
         for t in range(60):
             a = np.clip(rs.uniform(-1, 1, 6) * 0.7, -1, 1).astype(np.float32); inj = rs.random_sample(16).astype(np.float32)
             oo, ro, to, tro, tobo = e.step(a, inject=inj, autoreset=True)
             oh = np.zeros(od, np.float32); th = np.zeros(od, np.float32); rh = C.c_float(); dh = C.c_int(); trh = C.c_int()
-            H.hc_env_step(h, kind, flags, 4, 6, 25, 0, 0, p(a), p(inj), p(oh), p(th), C.byref(rh), C.byref(dh), C.byref(trh))
+            H.hc_env_step(h, kind, flags, 4, 6, 25, 0, 0, ptr(a), ptr(inj), ptr(oh), ptr(th), C.byref(rh), C.byref(dh), C.byref(trh))
             tol = 2e-5 if reach else 6e-3
             np.testing.assert_allclose(oh[:6], oo[:6], rtol=0, atol=1e-5 if reach else 2e-6)
             np.testing.assert_allclose(oh, oo, rtol=0, atol=tol, err_msg=f"kind {kind} step {t}")

@@ -4,26 +4,18 @@ whole trajectories (they are independent formulations: link-frame dynamics + wre
 world-frame rows); in fp32 per env step (16 substeps) from injected states -- across contact make/break events fp32 and fp64
 trajectories separate (a corner touching one substep earlier changes the velocity by ~0.1 rad/s), which is physics, not error."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from hostlibs import hostcheck, ptr
 from oracle import so100_oracle as O
-from test_oracle_contacts import C5, REF, M, L, floor_poses, fresh, rot, box_box, _grasp_state
-
-HERE = os.path.dirname(os.path.abspath(__file__))
+from scenes import C5, REFP, M, L, box_box, capsule_box, floor_poses, fresh, grasp_state, rot
 
 
 @pytest.fixture(scope="module")
 def H():
-    subprocess.check_call(["make", "-C", os.path.join(HERE, "_hostcheck"), "-s"])
-    return C.CDLL(os.path.join(HERE, "_hostcheck", "libhostcheck.so"))
-
-
-def P(a):
-    return a.ctypes.data_as(C.c_void_p)
+    return hostcheck()
 
 
 def pack(q, v, cube, cq, cvel=None):
@@ -35,7 +27,7 @@ def pack(q, v, cube, cq, cvel=None):
 
 def host_steps(fn, st, ctrl, flags, n, iters=4, citers=20):
     stat = np.zeros(5, np.int32); ct = np.ascontiguousarray(ctrl, np.float64); ap = np.zeros(3)
-    fn(P(st), P(ct), P(ap), flags, iters, citers, n, P(stat))
+    fn(ptr(st), ptr(ct), ptr(ap), flags, iters, citers, n, ptr(stat))
     return stat
 
 
@@ -55,7 +47,7 @@ def test_box_box_device_code_equals_oracle(H):
         for name, fn in (("d", H.hc_boxbox_d), ("f", H.hc_boxbox_f)):
             p2 = np.zeros((8, 3)); n2 = np.zeros(3); d2 = np.zeros(8)
             args = [np.ascontiguousarray(a, np.float64) for a in (cA, RA, hA, cB, RB, hB)]
-            k2 = fn(*[P(a) for a in args], P(p2), P(n2), P(d2))
+            k2 = fn(*[ptr(a) for a in args], ptr(p2), ptr(n2), ptr(d2))
             out[name] = (k2, p2[:k2], n2, d2[:k2])
         k2, p2, n2, d2 = out["d"]
         assert k2 == k
@@ -78,12 +70,12 @@ def test_pad_floor_device_code_vs_oracle(H):
         s64 = pack(q, v, cube, cq); s32 = pack(q, v, cube, cq)
         n64 = 0; same_sets = True
         for sub in range(96):                                # 96 substeps in fp64; fp32 for as long as it sees the same contact sets
-            L.so100o_step(C.byref(M), C.byref(d), REF, -1, 1)
-            st = host_steps(H.hc_csub_d, s64, ctrl, REF, 1); n64 = max(n64, st[0])
+            L.so100o_step(C.byref(M), C.byref(d), REFP, -1, 1)
+            st = host_steps(H.hc_csub_d, s64, ctrl, REFP, 1); n64 = max(n64, st[0])
             assert st[0] == sum(1 for i in range(d.ncon) if d.con[i].kind == 1)
             e = err(s64, d); worst64 = max(worst64, e[0], e[1]*1e-2)
             if same_sets:
-                st32 = host_steps(H.hc_csub_f, s32, ctrl, REF, 1)
+                st32 = host_steps(H.hc_csub_f, s32, ctrl, REFP, 1)
                 same_sets = st32[0] == st[0]                 # a corner made / broke contact a substep apart: the runs separate here
                 if same_sets:
                     e = err(s32, d); worst32 = max(worst32, e[0], e[1]*1e-2); compared += 1
@@ -95,7 +87,7 @@ def test_pad_floor_device_code_vs_oracle(H):
 
 def test_grasp_device_code_vs_oracle(H):
     """the coupled 12-dof solve (pad/cube box-box + cube/floor + friction-loss + limits) through the closing-jaw scenario"""
-    q, centre, cq = _grasp_state()
+    q, centre, cq = grasp_state()
     ctrl = q.copy(); ctrl[5] = -0.2
     d = fresh(q, cube=centre, cquat=cq); O.arr(d.ctrl)[:] = ctrl
     s64 = pack(q, np.zeros(6), centre, cq); s32 = pack(q, np.zeros(6), centre, cq)
@@ -112,7 +104,7 @@ def test_grasp_device_code_vs_oracle(H):
             e32 = err(s32, d); w32 = max(w32, e32[0], e32[1]*1e-2)
     assert coupled_seen > 100 and ncon_max >= 8
     assert w32 < 1e-5                                        # 1e-5 rad / m, 1e-3 rad/s / m/s while the cube is being hit at ~1 m/s
-    cnt = np.zeros(3, np.int64); H.hc_cdbg_counters(P(cnt))
+    cnt = np.zeros(3, np.int64); H.hc_cdbg_counters(ptr(cnt))
     assert cnt[1] < 4*cnt[0]                                 # Newton stays at a few iterations per substep
 
 
@@ -123,16 +115,16 @@ def test_contact_budget_is_counted_not_exceeded(H):
     found = 0
     for trial in range(4000):
         q = np.array([-2.2, -3.14158, 0, -2.0, -3.14158, -0.2]) + np.array([4.4, 3.34158, 3.14158, 3.8, 6.28316, 2.2])*rs.rand(6)
-        d = fresh(q, cube=[0.2, -0.3, 0.0099]); L.so100o_forward(C.byref(M), C.byref(d), REF, -1)
+        d = fresh(q, cube=[0.2, -0.3, 0.0099]); L.so100o_forward(C.byref(M), C.byref(d), REFP, -1)
         if d.ncon_dropped == 0:
             continue
         found += 1
         s64 = pack(q, np.zeros(6), [0.2, -0.3, 0.0099], [1, 0, 0, 0])
-        st = host_steps(H.hc_csub_d, s64, q, REF, 1)
+        st = host_steps(H.hc_csub_d, s64, q, REFP, 1)
         npad = sum(1 for i in range(d.ncon) if d.con[i].kind == 1)
         assert npad == 16 and st[0] == 16 and st[2] == d.ncon_dropped
         d2 = fresh(q, cube=[0.2, -0.3, 0.0099]); O.arr(d2.ctrl)[:] = q
-        L.so100o_step(C.byref(M), C.byref(d2), REF, -1, 1)
+        L.so100o_step(C.byref(M), C.byref(d2), REFP, -1, 1)
         e = err(s64, d2)
         assert e[0] < 1e-10 and e[1] < 1e-7
         if found >= 3:
@@ -146,10 +138,9 @@ def test_active_set_memory_over_whole_env_steps(H):
     code vs the oracle for as long as both see the same contact counts (this is the scenario of tests/test_gpu_contacts.py on the
     host; the first version of the memory stopped at a kink of the piecewise-quadratic cost and was 3e-3 off here)."""
     rs = np.random.RandomState(1)
-    q0, centre, cq = _grasp_state()
+    q0, centre, cq = grasp_state()
     worst = 0.0; compared = 0; passes0 = None
-    H.hc_cdbg_passes.restype = C.c_long
-    c0 = np.zeros(3, np.int64); H.hc_cdbg_counters(P(c0)); p0 = H.hc_cdbg_passes()
+    c0 = np.zeros(3, np.int64); H.hc_cdbg_counters(ptr(c0)); p0 = H.hc_cdbg_passes()
     for i in range(12):
         q = q0.copy(); q[5] = 0.065 + rs.uniform(0.0, 0.01)
         cube = centre + rs.uniform(-1, 1, 3)*np.array([0.0004, 0.002, 0.002])
@@ -170,7 +161,7 @@ def test_active_set_memory_over_whole_env_steps(H):
             if stat[0] != nmax:
                 break
             e = err(st, d); worst = max(worst, e[0], e[1]*1e-2); compared += 1
-    c1 = np.zeros(3, np.int64); H.hc_cdbg_counters(P(c1)); p1 = H.hc_cdbg_passes()
+    c1 = np.zeros(3, np.int64); H.hc_cdbg_counters(ptr(c1)); p1 = H.hc_cdbg_passes()
     assert compared > 40
     assert worst < 2e-5                                      # measured 1e-6: 2e-5 rad / m, 2e-3 per second
     assert (p1 - p0) < 3.5*(c1 - c0)[0]                      # row passes per solve (7.2 before the memory; 2.9 with it)
@@ -191,8 +182,6 @@ def test_feature_hash_of_the_active_set_memory(H):
 def test_capsule_box_device_code_equals_oracle(H):
     """the device's capsule-box stand-in (so100_contact.hpp: capsule_box) against oracle/so100_oracle.c: so100o_capsule_box: fp64 to round-off,
     fp32 to 2e-6 m in distance, 5e-5 m in position, 5e-3 in the normal on the same hit-or-miss decision except within round-off of touching"""
-    from test_oracle_contacts import capsule_box
-    H.hc_capbox_d.argtypes = H.hc_capbox_f.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     rs = np.random.RandomState(11); hits = 0; grazing = 0
     for _ in range(3000):
         R, _ = rot(rs); c = rs.randn(3)*0.1; h = np.full(3, 0.01); r = 0.02 + 0.004*rs.rand()
@@ -204,7 +193,7 @@ def test_capsule_box_device_code_equals_oracle(H):
         args = [np.ascontiguousarray(x, np.float64) for x in (a, b, c, R, h)]
         for name, fn, tol in (("d", H.hc_capbox_d, 1e-12), ("f", H.hc_capbox_f, 2e-6)):
             p2 = np.zeros(3); n2 = np.zeros(3); d2 = np.zeros(1)
-            k2 = fn(P(args[0]), P(args[1]), float(r), P(args[2]), P(args[3]), P(args[4]), P(p2), P(n2), P(d2))
+            k2 = fn(ptr(args[0]), ptr(args[1]), float(r), ptr(args[2]), ptr(args[3]), ptr(args[4]), ptr(p2), ptr(n2), ptr(d2))
             if k2 != k:
                 assert name == "f" and abs(dist if k else d2[0]) < 2e-6       # fp32 may disagree only within round-off of touching
                 grazing += 1

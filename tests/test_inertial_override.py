@@ -11,15 +11,12 @@ import subprocess
 import numpy as np
 import pytest
 
+from hostlibs import HERE, hostcheck, ptr
 from oracle import so100_oracle as O
+from scenes import floor_poses
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(os.path.dirname(HERE), "so100_mujoco_rl_amd", "csrc")
 L = O.lib(); M0 = O.model()
-
-
-def P(a):
-    return a.ctypes.data_as(C.c_void_p)
 
 
 def _table():
@@ -46,12 +43,10 @@ def alt(tmp_path_factory):
     subprocess.check_call(["g++", "-O1", "-std=c++17", "-o", str(d / "gen"), os.path.join(CSRC, "gen_model.cpp")])
     subprocess.check_call([str(d / "gen"), str(hdr), str(f)])
     assert "INERTIALS_OVERRIDDEN = true" in hdr.read_text()
-    so = d / "libhostcheck_alt.so"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unknown-pragmas",
-                           f'-DSO100_MODEL_GEN_HEADER="{hdr}"', "-o", str(so), os.path.join(HERE, "_hostcheck", "hostcheck.cpp")])
+    H = hostcheck(out=str(d / "libhostcheck_alt.so"), extra=f"-DSO100_MODEL_GEN_HEADER='\"{hdr}\"'")
     m = O.Model()
-    L.so100o_model_init_with_inertials(C.byref(m), P(np.ascontiguousarray(tab.reshape(-1))))
-    return C.CDLL(str(so)), m, tab
+    L.so100o_model_init_with_inertials(C.byref(m), ptr(np.ascontiguousarray(tab.reshape(-1))))
+    return H, m, tab
 
 
 def test_override_reaches_both_sides_and_they_agree(alt):
@@ -68,7 +63,7 @@ def test_override_reaches_both_sides_and_they_agree(alt):
             L.so100o_forward(C.byref(m), C.byref(d), 0, 0)
             ref[name] = (O.arr(d.M).reshape(12, 12)[:6, :6].copy(), O.arr(d.qfrc_bias)[:6].copy())
         Mh = np.zeros(36); bh = np.zeros(6)
-        H.hc_dyn_d(P(q), P(v), P(Mh), P(bh))
+        H.hc_dyn_d(ptr(q), ptr(v), ptr(Mh), ptr(bh))
         wM = max(wM, np.abs(Mh.reshape(6, 6) - ref["alt"][0]).max()); wb = max(wb, np.abs(bh - ref["alt"][1]).max())
         dM = max(dM, np.abs(ref["alt"][0] - ref["shipped"][0]).max())
     assert wM < 1e-15 and wb < 1e-13 and dM > 1e-3
@@ -78,7 +73,6 @@ def test_whole_substeps_with_contacts_agree_under_the_override(alt):
     """32 substeps of the reference physics (friction loss, limits, pad / floor contacts, cube) from poses at the table: device code on the
     alternative header (fp64) against the oracle on the same table; the regulariser of the pad rows (body_invweight0) and the servo's kv
     are derived from the inertials, so this exercises everything the table feeds"""
-    from test_oracle_contacts import floor_poses
     H, M1, _ = alt
     flags = O.F_REFERENCE
     wq = wv = 0; contacts = 0
@@ -89,7 +83,7 @@ def test_whole_substeps_with_contacts_agree_under_the_override(alt):
         O.arr(d.ctrl)[:] = ctrl
         st = np.zeros(49); st[:6] = q0; st[30:33] = [0.15, -0.25, 0.0099]; st[33] = 1.0
         stat = np.zeros(5, np.int32); ap = np.zeros(3)
-        H.hc_csub_d(P(st), P(ctrl), P(ap), flags, 60, 60, 32, P(stat))
+        H.hc_csub_d(ptr(st), ptr(ctrl), ptr(ap), flags, 60, 60, 32, ptr(stat))
         L.so100o_step(C.byref(M1), C.byref(d), flags, -1, 32)
         contacts += int(stat[0] > 0)
         wq = max(wq, np.abs(st[:6] - O.arr(d.qpos)[:6]).max()); wv = max(wv, np.abs(st[6:12] - O.arr(d.qvel)[:6]).max())

@@ -8,68 +8,14 @@ import numpy as np
 import pytest
 
 from oracle import so100_oracle as O
+from scenes import (C5, JNT_HI, JNT_LO, L, LCUBE, LINKS, M, REFP, box_box, capsule_box, floor_poses, fresh, grasp_state, link_cube_states,
+                    pad_frames, proxy_bottoms, rot, wrist_first_poses)
 
-L = O.lib()
-M = O.model()
 ARMROWS = O.F_FRICTIONLOSS | O.F_LIMITS
-REF = O.F_REFERENCE
-C5 = O.F_CONTACT5
-LO = np.array([-2.2, -3.14158, 0, -2.0, -3.14158, -0.2]); HI = np.array([2.2, 0.2, 3.14158, 1.8, 3.14158, 2.0])
-
-
-def fresh(q=None, v=None, cube=None, cquat=None):
-    d = O.Data()
-    L.so100o_reset_data(C.byref(M), C.byref(d))
-    if q is not None:
-        O.arr(d.qpos)[:6] = q
-    if v is not None:
-        O.arr(d.qvel)[:len(v)] = v
-    if cube is not None:
-        O.arr(d.qpos)[6:9] = cube
-    if cquat is not None:
-        O.arr(d.qpos)[9:13] = np.asarray(cquat) / np.linalg.norm(cquat)
-    return d
 
 
 def fwd(d, flags, iters):
     L.so100o_forward(C.byref(M), C.byref(d), flags, iters)
-
-
-def pad_frames(d):
-    """world centre and rotation of the 8 pad boxes"""
-    xp = O.arr(d.xpos); xm = O.arr(d.xmat)
-    out = []
-    for g in range(8):
-        b = M.pad_body[g]; R = xm[b].reshape(3, 3)
-        out.append((xp[b] + R @ np.array(M.pad_pos[g][:]), R.copy(), np.array(M.pad_size[g][:])))
-    return out
-
-
-def floor_poses(n, seed, band=0.003):
-    """random arm poses whose lowest pad corner is within `band` below .. above the floor"""
-    rs = np.random.RandomState(seed); out = []
-    while len(out) < n:
-        q = LO + (HI - LO) * rs.rand(6)
-        d = fresh(q); L.so100o_kinematics(C.byref(M), C.byref(d))
-        z = min(c[2] - (np.abs(R[2]) * h).sum() for c, R, h in pad_frames(d))
-        if -band < z < 0.0005 and O.arr(d.xpos)[5][2] > 0.03:
-            out.append(q)
-    return out
-
-
-def rot(rs):
-    q = rs.randn(4); q /= np.linalg.norm(q)
-    w, x, y, z = q
-    return np.array([[1 - 2*(y*y + z*z), 2*(x*y - w*z), 2*(x*z + w*y)], [2*(x*y + w*z), 1 - 2*(x*x + z*z), 2*(y*z - w*x)],
-                     [2*(x*z - w*y), 2*(y*z + w*x), 1 - 2*(x*x + y*y)]]), q
-
-
-def box_box(cA, RA, hA, cB, RB, hB):
-    pos = np.zeros((8, 3)); n = np.zeros(3); dist = np.zeros(8)
-    p = lambda a: np.ascontiguousarray(a, np.float64).ctypes.data_as(C.c_void_p)
-    cA, RA, hA, cB, RB, hB = [np.ascontiguousarray(a, np.float64) for a in (cA, RA, hA, cB, RB, hB)]
-    k = L.so100o_box_box(p(cA), p(RA), p(hA), p(cB), p(RB), p(hB), pos.ctypes.data_as(C.c_void_p), n.ctypes.data_as(C.c_void_p), dist.ctypes.data_as(C.c_void_p))
-    return k, pos[:k].copy(), n.copy(), dist[:k].copy()
 
 
 def inside(p, c, R, h, tol):
@@ -170,7 +116,7 @@ def test_contact_jacobian_is_the_material_point_velocity():
     rs = np.random.RandomState(0)
     for q in floor_poses(6, 5):
         cube = None
-        d = fresh(q, cube=[0.1, -0.25, 0.0099]); fwd(d, REF, -1)
+        d = fresh(q, cube=[0.1, -0.25, 0.0099]); fwd(d, REFP, -1)
         assert d.ncon > 0
         xp = O.arr(d.xpos).copy(); xm = O.arr(d.xmat).copy(); qpos0 = O.arr(d.qpos).copy()
         for ci in range(d.ncon):
@@ -215,10 +161,10 @@ def _kkt(d, nvs, tol):
 def test_newton_equals_pgs_without_pad_contacts():
     rs = np.random.RandomState(2)
     for _ in range(20):
-        q = LO + (HI - LO)*rs.rand(6)
+        q = JNT_LO + (JNT_HI - JNT_LO)*rs.rand(6)
         if rs.rand() < 0.5:
-            q[rs.randint(6)] = (HI if rs.rand() < 0.5 else LO)[0] * 0 + (HI + 0.01)[rs.randint(6)]   # push some joint past a limit
-            q = np.clip(q, LO - 0.02, HI + 0.02)
+            q[rs.randint(6)] = (JNT_HI if rs.rand() < 0.5 else JNT_LO)[0] * 0 + (JNT_HI + 0.01)[rs.randint(6)]   # push some joint past a limit
+            q = np.clip(q, JNT_LO - 0.02, JNT_HI + 0.02)
         v = rs.randn(12)*np.array([2]*6 + [0.1]*3 + [1]*3)
         cz = 0.0095 + 0.0004*rs.rand()
         cq = np.array([1, 0.02*rs.randn(), 0.02*rs.randn(), 0.3*rs.randn()])
@@ -236,14 +182,14 @@ def test_newton_kkt_with_pad_contacts_and_against_pgs():
     for q in floor_poses(12, 11):
         v = np.concatenate([rs.randn(6)*1.0, np.zeros(6)])
         d = fresh(q, v, [0.15, -0.2, 0.0099]); O.arr(d.ctrl)[:] = q + rs.randn(6)*0.05
-        fwd(d, REF, -1)
+        fwd(d, REFP, -1)
         npad = sum(1 for i in range(d.ncon) if d.con[i].kind == 1)
         if npad == 0:
             continue
         _kkt(d, 12, 1e-7)
         if d.nefc <= 40:                                     # PGS on the dual reaches the same point (slowly)
             e = fresh(q, v, [0.15, -0.2, 0.0099]); O.arr(e.ctrl)[:] = O.arr(d.ctrl)
-            fwd(e, REF, 20000)
+            fwd(e, REFP, 20000)
             assert np.allclose(O.arr(e.qacc), O.arr(d.qacc), rtol=2e-4, atol=2e-4 * max(1.0, np.abs(O.arr(d.qacc)).max()))
         checked += 1
     assert checked >= 6
@@ -259,7 +205,7 @@ def test_arm_driven_into_the_floor_stops_on_its_pads():
     reward's `end_pos[2] < 0.02` term punishes, env_base_01.py:207-211); without them it does."""
     q0 = np.array([0.0, -1.6, 1.9, 1.5, 0.0, 0.3])          # gripper pointing down, lowest pad corner 28 mm above the floor
     lows = {}
-    for flags in (ARMROWS | O.F_FLOOR, REF):
+    for flags in (ARMROWS | O.F_FLOOR, REFP):
         d = fresh(q0, cube=[0.2, -0.2, 0.0099])
         ctrl = q0.copy(); ctrl[1] += 0.5                     # servo the shoulder 0.5 rad further down
         O.arr(d.ctrl)[:] = ctrl
@@ -272,32 +218,18 @@ def test_arm_driven_into_the_floor_stops_on_its_pads():
         final = min(c[2] - (np.abs(R[2]) * h).sum() for c, R, h in pad_frames(d))
         assert np.all(np.isfinite(O.arr(d.qpos))) and np.abs(O.arr(d.qvel)[:6]).max() < 0.05      # at rest either way
     assert lows[ARMROWS | O.F_FLOOR] < -0.02                 # no arm contact: straight through the floor
-    assert lows[REF] > -0.002                                # the impact at ~0.5 m/s dips < 2 mm into the (soft) contact ...
+    assert lows[REFP] > -0.002                                # the impact at ~0.5 m/s dips < 2 mm into the (soft) contact ...
     assert -0.0003 < final < 0.0                             # ... and the gripper comes to rest on its pads, < 0.3 mm deep
-
-
-def _grasp_state():
-    """gripper horizontal 28 cm above the floor, closing direction along world x, gravity along the pads' short side; the cube
-    floats between the jaws: 0.5 mm from the fixed jaw's pads, ~1.5 mm from the moving jaw's (jaw angle 0.1 rad)"""
-    q = np.array([0.0, -1.9, 1.6, 0.3, 1.5708, 0.1])
-    d = fresh(q); L.so100o_kinematics(C.byref(M), C.byref(d))
-    xp = O.arr(d.xpos)[6].copy(); R = O.arr(d.xmat)[6].reshape(3, 3).copy()
-    centre = xp + R @ np.array([-0.0026, -0.088, 0.0])
-    # cube axes = jaw axes (a 180-degree turn about y here: w ~ 0, so the quaternion is taken from the largest diagonal term)
-    cq = np.array([0.0, 0.0, 1.0, 0.0])
-    Rq = np.array([[-1, 0, 0], [0, 1, 0], [0, 0, -1.0]])
-    assert np.allclose(R, Rq, atol=1e-4)
-    return q, centre, cq
 
 
 def test_closing_jaw_holds_the_cube_against_gravity():
     """BASELINE.json configs[4]: pad/cube box-box contact, arm and cube dofs coupled in one solve.  The cube starts in mid-air
     between the open jaws; the jaw closes on it.  With the pad/cube contacts it is clamped (friction 1, pyramidal) and stays in
     the gripper; without them it falls to the floor."""
-    q, centre, cq = _grasp_state()
+    q, centre, cq = grasp_state()
     assert centre[2] > 0.03
     res = {}
-    for flags in (REF, C5):
+    for flags in (REFP, C5):
         d = fresh(q, cube=centre, cquat=cq)
         ctrl = q.copy(); ctrl[5] = -0.2                      # close the jaw
         O.arr(d.ctrl)[:] = ctrl
@@ -307,7 +239,7 @@ def test_closing_jaw_holds_the_cube_against_gravity():
             maxcon = max(maxcon, sum(1 for i in range(d.ncon) if d.con[i].kind == 2))
         res[flags] = (O.arr(d.qpos)[6:9].copy(), O.arr(d.qvel).copy(), O.arr(d.qpos)[5], maxcon)
         assert np.all(np.isfinite(O.arr(d.qpos)))
-    assert res[REF][0][2] < 0.0105 and res[REF][3] == 0      # fell to the floor
+    assert res[REFP][0][2] < 0.0105 and res[REFP][3] == 0      # fell to the floor
     pos, vel, jaw, ncon = res[C5]
     assert ncon >= 8                                          # face-face manifolds on both sides
     # clamped after sliding ~1 cm while the jaw closed; what remains is the slow creep of soft pyramidal friction (< 5 mm/s)
@@ -325,19 +257,6 @@ def test_closing_jaw_holds_the_cube_against_gravity():
 
 
 # ---- link proxies (stand-in capsules for the arm's collision meshes, SO100_F_LINKS_FLOOR) -------------------------------------
-LINKS = O.F_REFERENCE | O.F_LINKS_FLOOR
-
-
-def proxy_bottoms(d):
-    """world z of the lowest point of the two end spheres of every link proxy (after so100o_kinematics)"""
-    xp = O.arr(d.xpos); xm = O.arr(d.xmat); out = []
-    for k in range(O.NPROX):
-        b = M.prox_body[k]; R = xm[b].reshape(3, 3)
-        for e in range(2):
-            out.append((xp[b] + R @ np.array(M.prox_p[k][e][:]))[2] - M.prox_radius[k])
-    return np.array(out)
-
-
 def test_link_proxy_geometry_follows_its_rule():
     """segments run from a link's joint origin to its child's (links 1-3) or to the far end of the jaw's pads (links 4-5); radii
     from the links' inertia boxes, jaws capped (csrc/so100_model_def.h)"""
@@ -354,26 +273,13 @@ def test_link_proxy_geometry_follows_its_rule():
         assert abs(far[1]) >= max(abs(M.pad_pos[g][1]) for g in pads) and M.prox_radius[k] == pytest.approx(0.008)
 
 
-def _wrist_first_poses(n, seed):
-    """arm poses whose lowest point is a LINK proxy (not a finger pad), within 3 mm above the floor"""
-    rs = np.random.RandomState(seed); out = []
-    while len(out) < n:
-        q = LO + (HI - LO)*rs.rand(6)
-        d = fresh(q); L.so100o_kinematics(C.byref(M), C.byref(d))
-        pb = proxy_bottoms(d)
-        zpad = min(c[2] - (np.abs(R[2])*h).sum() for c, R, h in pad_frames(d))
-        if 0.0 < pb[:6].min() < 0.003 and zpad > pb[:6].min() + 0.02:
-            out.append(q)
-    return out
-
-
 def test_arm_driven_wrist_first_into_the_table_stops_on_its_link_proxies():
     """with the proxies the arm commanded downwards rests with every proxy sphere above -1 mm (a capsule end
     dips < 3 mm during the impact); without them (reference physics: pads only) the same links sink centimetres into the table."""
     sunk = []
-    for q0 in _wrist_first_poses(6, 3):
+    for q0 in wrist_first_poses(6, 3):
         res = {}
-        for flags in (LINKS, REF):
+        for flags in (LINKS, REFP):
             d = fresh(q0)
             low = 1.0
             for t in range(40):
@@ -384,13 +290,13 @@ def test_arm_driven_wrist_first_into_the_table_stops_on_its_link_proxies():
             assert np.all(np.isfinite(O.arr(d.qpos)))
         low, final, vmax, ncon = res[LINKS]
         assert low > -0.003 and final > -0.001 and vmax < 0.5
-        sunk.append(res[REF][1])
+        sunk.append(res[REFP][1])
     assert np.median(sunk) < -0.005 and min(sunk) < -0.01     # without the proxies the same links end up to centimetres under the table
 
 
 def test_link_proxy_rows_satisfy_kkt_and_newton_equals_pgs():
     """the proxy contacts are ordinary pyramidal rows on links 1-5: the Newton solution satisfies the KKT conditions row by row"""
-    for q0 in _wrist_first_poses(4, 5):
+    for q0 in wrist_first_poses(4, 5):
         q = q0.copy(); q[1] += 0.02                          # push the pose a little into the table
         d = fresh(q, v=np.random.RandomState(1).randn(6)*0.3)
         fwd(d, LINKS, -1)
@@ -406,17 +312,6 @@ def test_link_proxy_rows_satisfy_kkt_and_newton_equals_pgs():
 
 
 # ---- link proxies against the cube (SO100_F_LINKS_CUBE: Rotation_Pitch / Upper_Arm, the pairs scene:44-48 leaves live) ---
-LCUBE = O.F_REFERENCE | O.F_LINKS_FLOOR | O.F_LINKS_CUBE
-
-
-def capsule_box(a, b, r, c, R, h):
-    p = lambda x: np.ascontiguousarray(x, np.float64).ctypes.data_as(C.c_void_p)
-    pos = np.zeros(3); n = np.zeros(3); dist = C.c_double(0)
-    L.so100o_capsule_box.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    k = L.so100o_capsule_box(p(a), p(b), float(r), p(c), p(R), p(h), p(pos), p(n), C.byref(dist))
-    return k, pos, n, dist.value
-
-
 def _segment_box_distance(a, b, c, R, h, samples=4001):
     t = np.linspace(0, 1, samples)[:, None]
     s = ((a + t*(b - a)) - c) @ R                            # box frame (R: world <- box, row-major)
@@ -475,39 +370,6 @@ def test_cube_proxy_geometry_follows_its_rule():
         assert np.allclose(xp[b] + xm[b].reshape(3, 3) @ np.array(M.cprox_p[k][1][:]), xp[b + 1], atol=1e-12)
         assert 0.015 < M.cprox_radius[k] < 0.03
     assert M.cprox_radius[1] == M.prox_radius[0]             # the Upper_Arm capsule is the one the floor pairs use
-
-
-def link_cube_states(n, seed, pen=(0.0002, 0.003)):
-    """arm poses with the cube placed against the Rotation_Pitch (even i) or Upper_Arm (odd i) capsule, penetrating by pen[0]..pen[1] metres"""
-    rs = np.random.RandomState(seed); out = []
-    hs = np.full(3, 0.01)
-    while len(out) < n:
-        k = len(out) % 2
-        q = LO + (HI - LO)*rs.rand(6)
-        d = fresh(q); L.so100o_kinematics(C.byref(M), C.byref(d))
-        xp = O.arr(d.xpos); b = M.cprox_body[k]
-        a_, b_ = xp[b].copy(), xp[b + 1].copy()
-        s = a_ + (0.15 + 0.85*rs.rand())*(b_ - a_)
-        u = rs.randn(3); u /= np.linalg.norm(u)
-        Rc, qc = rot(rs)
-        want = -(pen[0] + (pen[1] - pen[0])*rs.rand())
-        lo_, hi_ = 0.0, 0.08                                 # bisection on the cube's offset along u for the wanted penetration
-        for _ in range(40):
-            mid = 0.5*(lo_ + hi_)
-            kk, _, _, dist = capsule_box(a_, b_, M.cprox_radius[k], s + u*mid, Rc, hs)
-            if kk and dist < want: lo_ = mid
-            else: hi_ = mid
-        c = s + u*lo_
-        kk, _, _, dist = capsule_box(a_, b_, M.cprox_radius[k], c, Rc, hs)
-        if not kk or abs(dist - want) > 2e-4 or c[2] < 0.012 + 0.0174:      # (cube clear of the floor: the pair under test alone)
-            continue
-        # no other proxy / pad may touch anything in this pose
-        dd = fresh(q); O.arr(dd.qpos)[6:9] = c; O.arr(dd.qpos)[9:13] = qc
-        fwd(dd, LCUBE | O.F_PADS_CUBE, -1)
-        if dd.ncon != 1 or dd.con[0].kind != 4:
-            continue
-        out.append((q, c, qc))
-    return out
 
 
 def test_link_cube_contact_pushes_the_cube_away_and_satisfies_kkt():

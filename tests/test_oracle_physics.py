@@ -15,20 +15,9 @@ import pytest
 from scipy.spatial.transform import Rotation as R
 
 from oracle import so100_oracle as O
+from scenes import L, M, fresh
 
-L = O.lib()
-M = O.model()
 NV = 12
-
-
-def fresh(q=None, v=None):
-    d = O.Data()
-    L.so100o_reset_data(C.byref(M), C.byref(d))
-    if q is not None:
-        O.arr(d.qpos)[:len(q)] = q
-    if v is not None:
-        O.arr(d.qvel)[:len(v)] = v
-    return d
 
 
 def rand_state(rs, vel=True):

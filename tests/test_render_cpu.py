@@ -3,39 +3,22 @@ ray caster (tests/render_ref.py, poses from the oracle), the wrist camera agains
 (so100o_project_bbox), the scene camera's free-camera formula, and the Motion-JPEG AVI writer.  No GPU needed."""
 import ctypes as C
 import io
-import os
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
 import render_ref as RR
+from hostlibs import rendercheck
 from oracle import so100_oracle as O
+from render_checks import compare, host_render, parse_avi
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 JNT_RANGE = [(-2.2, 2.2), (-3.14158, 0.2), (0.0, 3.14158), (-2.0, 1.8), (-3.14158, 3.14158), (-0.2, 2.0)]
-# depth bound: the scene camera's pose is exact, the wrist camera's comes from fp32 FK (task_poses: 1e-7 m / 2e-7 rad off the
-# oracle), which grazing floor rays and 3 cm-near pads turn into up to 5e-5 relative depth (DESIGN.md "Rendering")
-DEPTH_RTOL = {RR.CAM_END: 1e-4, RR.CAM_SCENE: 1e-5}
 
 
 @pytest.fixture(scope="module")
 def H():
-    subprocess.check_call(["make", "-C", os.path.join(HERE, "_rendercheck"), "-s"])
-    h = C.CDLL(os.path.join(HERE, "_rendercheck", "librendercheck.so"))
-    h.rc_render.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    return h
-
-
-def host_render(H, qpos, camera, W, Hh, mask=0, free_cam=None):
-    """host instantiation: (rgb [n, H, W, 3], depth [n, H, W], seg [n, H, W]) of qpos [n, 13]"""
-    q = np.ascontiguousarray(np.asarray(qpos, np.float32).reshape(-1, 13))
-    n = q.shape[0]
-    rgb = np.zeros((n, Hh, W, 3), np.uint8); dep = np.zeros((n, Hh, W), np.float32); seg = np.zeros((n, Hh, W), np.uint8)
-    fc = None if free_cam is None else np.ascontiguousarray(free_cam, np.float32)
-    H.rc_render(q.ctypes.data, n, camera, W, Hh, mask, None if fc is None else fc.ctypes.data, rgb.ctypes.data, dep.ctypes.data, seg.ctypes.data, None)
-    return rgb, dep, seg
+    return rendercheck()
 
 
 def random_states(n, seed):
@@ -50,27 +33,6 @@ def random_states(n, seed):
             out[i, 8] = rs.uniform(0.05, 0.3)
             qq = rs.randn(4); out[i, 9:13] = qq / np.linalg.norm(qq)
     return out.astype(np.float32).astype(np.float64)
-
-
-def compare(rgb, dep, seg, q, camera, W, Hh, mask, free_cam=None):
-    """the pass conditions against render_ref; returns a short failure string or None"""
-    r2, d2, s2 = RR.render(q, camera, W, Hh, mask, free_cam)
-    eq = seg == s2
-    if eq.mean() < 0.995:
-        return f"segmentation equal on {eq.mean():.4f} of the pixels"
-    bad = ~eq & ~RR.near_edge(s2.astype(np.int64))
-    if bad.any():
-        return f"{int(bad.sum())} segmentation mismatches away from an edge"
-    drel = np.abs(dep[eq].astype(np.float64) - d2[eq]) / d2[eq]
-    if drel.max() > DEPTH_RTOL[camera]:
-        return f"depth off by {drel.max():.2e} relative"
-    # a checker square's edge is an edge of the image too (floor pixels whose 8-neighbourhood spans two squares)
-    par = RR.checker_parity(q, camera, W, Hh, free_cam)
-    ok = eq & ~RR.near_edge(np.where(s2 == 1, par, -2))
-    dr = np.abs(rgb.astype(np.int64) - r2.astype(np.int64)).max(-1)[ok]
-    if dr.size and dr.max() > 1:
-        return f"rgb off by {dr.max()} LSB"
-    return None
 
 
 @pytest.mark.parametrize("camera", [RR.CAM_END, RR.CAM_SCENE])
@@ -175,36 +137,6 @@ def test_scene_camera_overrides_match_reference(H):
     assert compare(rgb[0], dep[0], seg[0], q, RR.CAM_SCENE, 96, 80, 15, fc) is None
 
 
-def _parse_avi(path):
-    data = open(path, "rb").read()
-    assert data[:4] == b"RIFF" and data[8:12] == b"AVI " and struct.unpack("<I", data[4:8])[0] == len(data) - 8
-    chunks = {}
-    frames = []
-    idx = []
-    movi = None
-
-    def walk(lo, hi):
-        nonlocal movi
-        p = lo
-        while p < hi:
-            cid, size = struct.unpack("<4sI", data[p:p + 8])
-            if cid == b"LIST":
-                kind = data[p + 8:p + 12]
-                if kind == b"movi":
-                    movi = p + 8
-                walk(p + 12, p + 8 + size)
-            elif cid == b"00dc":
-                frames.append(data[p + 8:p + 8 + size])
-            elif cid == b"idx1":
-                for k in range(size // 16):
-                    idx.append(struct.unpack("<4sIII", data[p + 8 + 16 * k:p + 24 + 16 * k]))
-            else:
-                chunks[cid] = data[p + 8:p + 8 + size]
-            p += 8 + size + (size & 1)
-    walk(12, len(data))
-    return chunks, frames, idx, movi, data
-
-
 def test_mjpeg_avi_round_trip(tmp_path):
     from PIL import Image
     from so100_mujoco_rl_amd.video import MjpegAviWriter
@@ -216,7 +148,7 @@ def test_mjpeg_avi_round_trip(tmp_path):
     for f in frames:
         w.write(f)
     w.close()
-    chunks, data_frames, idx, movi, raw = _parse_avi(path)
+    chunks, data_frames, idx, movi, raw = parse_avi(path)
     us, _, _, flags, total, _, streams, _, aw, ah = struct.unpack("<10I", chunks[b"avih"][:40])
     assert us == round(1e6 / 31) and total == n and streams == 1 and (aw, ah) == (W, Hh) and flags & 0x10
     fcc_type, handler = struct.unpack("<4s4s", chunks[b"strh"][:8])

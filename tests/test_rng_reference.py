@@ -8,37 +8,21 @@ overlap), the reference sampler as a standard normal sample, the edges of the Bo
 (policy_noise, host twin) over every value of u1 and a dense sweep of u2, and the fp32 task layer stepped WITHOUT injected uniforms
 against the oracle for every env kind -- the CPU half of tests/test_gpu_policy_noise.py::test_uninjected_env_draws_vs_oracle."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 from scipy.special import ndtr
 
+from hostlibs import hostcheck, ptr
 from oracle import so100_oracle as O
+from scenes import UNINJECTED_CASES, UNINJECTED_N, UNINJECTED_SEED, UNINJECTED_STEPS, UNINJECTED_TIMELIMIT
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 u32 = lambda x: np.ascontiguousarray(x, np.uint32)
-
-
-def p(a):
-    return a.ctypes.data_as(C.c_void_p)
 
 
 @pytest.fixture(scope="module")
 def H():
-    subprocess.check_call(["make", "-C", os.path.join(HERE, "_hostcheck"), "-s"])
-    h = C.CDLL(os.path.join(HERE, "_hostcheck", "libhostcheck.so"))
-    h.hc_env_new.restype = C.c_void_p
-    h.hc_env_free.argtypes = [C.c_void_p]
-    h.hc_env_reset.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_uint, C.c_void_p, C.c_void_p]
-    h.hc_env_step.argtypes = [C.c_void_p, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint] + [C.c_void_p] * 7
-    h.hc_env_qpos.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    h.hc_philox4x32.argtypes = [C.c_void_p] * 3
-    h.hc_draw8.argtypes = [C.c_uint64, C.c_uint, C.c_uint, C.c_int, C.c_void_p]
-    h.hc_policy_noise.argtypes = [C.c_uint64, C.c_uint, C.c_uint, C.c_void_p]
-    h.hc_policy_noise_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_void_p]
-    return h
+    return hostcheck()
 
 
 # ---- known answers ------------------------------------------------------------------------------------------------------------
@@ -51,7 +35,7 @@ KAT = [((0x00000000,) * 4, (0x00000000,) * 2, (0x6627e8d5, 0xe169c58d, 0xbc57ac4
 
 def _philox_oracle(c, k):
     out = np.zeros(4, np.uint32)
-    O.lib().so100o_philox4x32(*[C.c_uint32(x) for x in c], *[C.c_uint32(x) for x in k], p(out))
+    O.lib().so100o_philox4x32(*[C.c_uint32(x) for x in c], *[C.c_uint32(x) for x in k], ptr(out))
     return tuple(int(x) for x in out)
 
 
@@ -61,7 +45,7 @@ def _philox_numpy(c, k):
 
 def _philox_device(H, c, k):
     out = np.zeros(4, np.uint32)
-    H.hc_philox4x32(p(u32(c)), p(u32(k)), p(out))
+    H.hc_philox4x32(ptr(u32(c)), ptr(u32(k)), ptr(out))
     return tuple(int(x) for x in out)
 
 
@@ -96,14 +80,13 @@ def test_draw8_is_the_oracles_uniform_stream(H):
     """The env's uniforms, device source on the host, bit for bit: against so100o_uniform4 (the oracle's stream) and against the counter
     layout written out -- counter (env_gid, counter, 2 phase + b, 0), key (seed_lo, seed_hi), u = (r >> 8) 2^-24 in float32."""
     L = O.lib()
-    L.so100o_uniform4.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
     for seed in SEEDS:
         for env in EDGE_U32:
             for counter in EDGE_U32:
                 for phase in (0, 1):
-                    u = np.zeros(8, np.float32); H.hc_draw8(seed, env, counter, phase, p(u))
+                    u = np.zeros(8, np.float32); H.hc_draw8(seed, env, counter, phase, ptr(u))
                     uo = np.zeros(8, np.float32)
-                    L.so100o_uniform4(seed, env, counter, 2*phase, p(uo[:4])); L.so100o_uniform4(seed, env, counter, 2*phase + 1, p(uo[4:]))
+                    L.so100o_uniform4(seed, env, counter, 2*phase, ptr(uo[:4])); L.so100o_uniform4(seed, env, counter, 2*phase + 1, ptr(uo[4:]))
                     assert np.array_equal(u, uo), (hex(seed), env, counter, phase)
                     r = np.concatenate([O.philox4x32_np(env, counter, 2*phase + b, 0, seed & 0xFFFFFFFF, seed >> 32) for b in (0, 1)])
                     want = ((r >> np.uint64(8)).astype(np.float64) * 2.0**-24).astype(np.float32)      # 24 bits: exact in float32
@@ -119,7 +102,7 @@ def test_policy_noise_keying_and_streams_do_not_overlap(H):
     for seed in SEEDS:
         for env in EDGE_U32:
             for step in EDGE_U32:
-                e = np.zeros(8, np.float32); H.hc_policy_noise(seed, env, step, p(e))
+                e = np.zeros(8, np.float32); H.hc_policy_noise(seed, env, step, ptr(e))
                 ref = O.policy_noise_ref(seed, env, step)
                 assert np.abs(e[:6] - ref).max() < HOST_TWIN_EPS, (hex(seed), env, step)
                 if env != step:
@@ -173,7 +156,7 @@ HOST_TWIN_RAD = 1.1e-6                                         # measured 3.5e-7
 def _pairs(H, r_even, r_odd):
     r_even = u32(r_even); r_odd = u32(r_odd)
     e0 = np.empty(r_even.size, np.float32); e1 = np.empty(r_even.size, np.float32)
-    H.hc_policy_noise_pairs(p(r_even), p(r_odd), r_even.size, p(e0), p(e1))
+    H.hc_policy_noise_pairs(ptr(r_even), ptr(r_odd), r_even.size, ptr(e0), ptr(e1))
     return e0, e1
 
 
@@ -222,25 +205,15 @@ def test_policy_noise_is_its_pair_transform_of_the_philox_words(H):
     rs = np.random.RandomState(3)
     for seed in SEEDS:
         for env, step in rs.randint(0, 2**32, (50, 2), dtype=np.uint64):
-            e = np.zeros(8, np.float32); H.hc_policy_noise(seed, int(env), int(step), p(e))
+            e = np.zeros(8, np.float32); H.hc_policy_noise(seed, int(env), int(step), ptr(e))
             r = np.concatenate([O.philox4x32_np(env, step, 16 + b, 0x504F4C, seed & 0xFFFFFFFF, seed >> 32) for b in (0, 1)])
             e0, e1 = _pairs(H, r[0::2], r[1::2])
             assert np.array_equal(e[0::2], e0) and np.array_equal(e[1::2], e1)
 
 
 # ---- the env's own draws, every kind, no injection -------------------------------------------------------------------------------
-NOPADS = O.F_FRICTIONLOSS | O.F_LIMITS | O.F_FLOOR
-ARM = O.F_FRICTIONLOSS | O.F_LIMITS | O.F_CUBE_PINNED
-# shared with tests/test_gpu_policy_noise.py::test_uninjected_env_draws_vs_oracle: (flags, action scale) per kind, seed, envs, steps, TimeLimit.
-# Un-injected, a float32 and a float64 env can take different branches (a lost cube, a pixel on an integer boundary) and no allowance covers
-# that, so the seed is chosen here: with it the float32 host twin already meets every bound the GPU test asserts.  The TimeLimit gives every
-# env two auto-resets; the run ends 10 steps after the second, when Env04's cube has settled again (it is dropped onto the floor by every reset).
-UNINJECTED_CASES = {1: (NOPADS, 1.0), 2: (ARM, 1.0), 3: (NOPADS, 0.6), 4: (NOPADS, 0.6), 5: (NOPADS, 0.6), 6: (ARM, 1.0)}
-UNINJECTED_SEED, UNINJECTED_N, UNINJECTED_STEPS, UNINJECTED_TIMELIMIT = 4, 64, 40, 15
-
-
 def uninjected_actions(kind, seed, n, steps):
-    """the actions test_gpu_parity._run_pair draws for (kind's action scale, seed): same generator, same consumption"""
+    """the actions gpu_support.run_pair draws for (kind's action scale, seed): same generator, same consumption"""
     rs = np.random.RandomState(seed); rs.random_sample((n, 16))
     for _ in range(steps):
         a = np.clip(rs.uniform(-1, 1, (n, 6)) * UNINJECTED_CASES[kind][1], -1, 1).astype(np.float32); rs.random_sample((n, 16))
@@ -260,14 +233,14 @@ def test_uninjected_task_layer_fp32_vs_oracle(H, kind):
     for e in orc:
         e.e.max_episode_steps = tl
     for i in range(n):
-        oh = np.zeros(od, np.float32); H.hc_env_reset(hs[i], kind, seed, i, None, p(oh))
+        oh = np.zeros(od, np.float32); H.hc_env_reset(hs[i], kind, seed, i, None, ptr(oh))
         np.testing.assert_allclose(oh, orc[i].reset(), rtol=0, atol=1e-6)
     n_px = n_px_bad = resets = 0
     for t, a in enumerate(uninjected_actions(kind, seed, n, steps)):
         for i in range(n):
             oo, ro, to, tro, tobo = orc[i].step(a[i], autoreset=True)
             oh = np.zeros(od, np.float32); th = np.zeros(od, np.float32); rh = C.c_float(); dh = C.c_int(); trh = C.c_int()
-            H.hc_env_step(hs[i], kind, flags, 4, 6, tl, seed, i, p(a[i]), None, p(oh), p(th), C.byref(rh), C.byref(dh), C.byref(trh))
+            H.hc_env_step(hs[i], kind, flags, 4, 6, tl, seed, i, ptr(a[i]), None, ptr(oh), ptr(th), C.byref(rh), C.byref(dh), C.byref(trh))
             assert bool(dh.value) == (to or tro) and bool(trh.value) == (tro and not to), (kind, t, i)
             resets += int(to or tro)
             if reach:
@@ -282,7 +255,7 @@ def test_uninjected_task_layer_fp32_vs_oracle(H, kind):
     assert n_px_bad <= 0.01*n_px, (n_px_bad, n_px)
     wq = wv = 0.0
     for i in range(n):
-        q = np.zeros(13); v = np.zeros(12); H.hc_env_qpos(hs[i], p(q), p(v)); H.hc_env_free(hs[i])
+        q = np.zeros(13); v = np.zeros(12); H.hc_env_qpos(hs[i], ptr(q), ptr(v)); H.hc_env_free(hs[i])
         wq = max(wq, np.abs(q - O.arr(orc[i].d.qpos)).max()); wv = max(wv, np.abs(v - O.arr(orc[i].d.qvel)).max())
     print(f"[un-injected host twin vs oracle, kind {kind}] pixel entries off by > 1e-4: {n_px_bad} of {n_px}; qpos {wq:.2e} qvel {wv:.2e}")
     assert wq < (2e-5 if reach else 3e-5) and wv < 5e-4

@@ -13,30 +13,18 @@ Solver residual: < 1e-2 on contact substeps at both settings.  On contact-free s
 the last sweep, not the distance from the converged solve (pad/floor: 0.1 % of them above 1e-2, p99 6e-8): those envs are held to the
 2e-6 bound against the oracle AND against a 64-sweep solve from the same state (tests/substep_harness.py).
 "parity unpinned (physics)": the oracle restates MuJoCo's published algorithm; MuJoCo itself is not available."""
-import ctypes as C
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import substep_harness as SH
+from hostlibs import hostcheck, ptr
 from oracle import so100_oracle as O
-
-HERE = os.path.dirname(os.path.abspath(__file__))
+from scenes import JS, LCUBE, LINKS, SHIPPED, floor_batch, grasp_batch, link_cube_batch, wrist_first_batch
 
 
 @pytest.fixture(scope="module")
 def H():
-    subprocess.check_call(["make", "-C", os.path.join(HERE, "_hostcheck"), "-s"])
-    return C.CDLL(os.path.join(HERE, "_hostcheck", "libhostcheck.so"))
-
-
-def P(a):
-    return a.ctypes.data_as(C.c_void_p)
-
-
-SHIPPED = (2, 20)                                         # (solver_iters, contact_iters): lib.So100Sim, vec_env.So100VecEnv, bench.py
+    return hostcheck()
 
 
 class HostDevice:
@@ -48,9 +36,9 @@ class HostDevice:
         self.warm = np.zeros((n, 49))
 
     def _substep(self, st, q, act, solver_iters):
-        ctrl = (q[:6].astype(np.float32) + act.astype(np.float32)*SH.JS).astype(np.float64)
+        ctrl = (q[:6].astype(np.float32) + act.astype(np.float32)*JS).astype(np.float64)
         stat = np.zeros(5, np.int32); ap = np.zeros(3)
-        self.H.hc_csub_f(P(st), P(ctrl), P(ap), self.flags, solver_iters, self.contact_iters, 1, P(stat))
+        self.H.hc_csub_f(ptr(st), ptr(ctrl), ptr(ap), self.flags, solver_iters, self.contact_iters, 1, ptr(stat))
         return stat
 
     def __call__(self, q32, v32, act):
@@ -77,30 +65,10 @@ class HostDevice:
         return gv
 
 
-def _check(T, n_pairs_min_contact, coupled_min=0, iters=(4, 30)):
-    assert T.contact >= n_pairs_min_contact and T.coupled >= coupled_min          # the batch did exercise the contact path
-    assert T.knife <= 0.02*T.pairs                                                 # poses decided inside fp32 round-off are rare
-    assert T.count_mismatch == 0 and T.set_mismatch == 0
-    assert T.worst_dv < 2e-6
-    assert T.worst_dv_contact < 5e-5 and T.worst_rel < 1e-2
-    check_residual(T, iters)
-
-
-def check_residual(T, iters):
-    """(4, 30): every residual < 1e-2.  2 sweeps: the Newton's residual < 1e-2 on contact substeps; a contact-free residual above 1e-2 is
-    the last sweep's change (stale), so those envs must match the oracle AND a 64-sweep solve from the same state within the free bound"""
-    assert T.worst_res_contact < 1e-2
-    if iters[0] >= 4:
-        assert T.worst_res < 1e-2
-    else:
-        assert T.resolved == T.stale
-        assert T.worst_dv_stale < 2e-6 and T.worst_dv_resolved < 2e-6
-
-
 def test_feature_signature_matches_the_oracle_ids(H):
     """the device's id numbering (pad/floor 8 pad + corner; pad/cube 64 + 8 pad + slot) and its mix function, on single substeps"""
     assert SH.feature_mix(0) != SH.feature_mix(1)
-    qpos, qvel, act = SH.floor_batch(24, 3)
+    qpos, qvel, act = floor_batch(24, 3)
     dev = HostDevice(H, 24, O.F_REFERENCE)
     T = SH.run_substep_parity(dev, qpos, qvel, act, O.F_REFERENCE, 1, "host fp32, floor, 1 substep")
     assert T.contact >= 10 and T.count_mismatch == 0 and T.set_mismatch == 0
@@ -117,9 +85,9 @@ def test_pad_floor_per_substep_host_fp32_at_shipped_settings(H):
 
 def _pad_floor_per_substep_host_fp32(H, iters):
     n = 64
-    qpos, qvel, act = SH.floor_batch(n, 0)
+    qpos, qvel, act = floor_batch(n, 0)
     T = SH.run_substep_parity(HostDevice(H, n, O.F_REFERENCE, iters), qpos, qvel, act, O.F_REFERENCE, 32, f"host fp32 {iters}, pad/floor")
-    _check(T, n_pairs_min_contact=n*32//3, iters=iters)
+    SH.check_tally(T, min_contact=n*32//3, iters=iters)
 
 
 def test_pad_cube_grasp_per_substep_host_fp32(H):
@@ -133,26 +101,12 @@ def test_pad_cube_grasp_per_substep_host_fp32_at_shipped_settings(H):
 
 def _pad_cube_grasp_per_substep_host_fp32(H, iters):
     n = 32
-    qpos, qvel, act = SH.grasp_batch(n, 1)
+    qpos, qvel, act = grasp_batch(n, 1)
     T = SH.run_substep_parity(HostDevice(H, n, O.F_CONTACT5, iters), qpos, qvel, act, O.F_CONTACT5, 48, f"host fp32 {iters}, grasp")
-    _check(T, n_pairs_min_contact=n*48//3, coupled_min=n*48//4, iters=iters)
+    SH.check_tally(T, min_contact=n*48//3, min_coupled=n*48//4, iters=iters)
 
 
 # ---- link proxies (SO100_F_LINKS_FLOOR: stand-in capsules for the arm's collision meshes, contacts on ANY link) ---------------
-LINKS = O.F_REFERENCE | O.F_LINKS_FLOOR
-
-
-def wrist_first_batch(n, seed):
-    """poses whose lowest point is a link proxy (wrist / forearm first), pushed 1e-2 rad into the table; random joint velocities"""
-    from test_oracle_contacts import _wrist_first_poses
-    rs = np.random.RandomState(seed)
-    qpos = np.zeros((n, 13)); qvel = np.zeros((n, 12))
-    for i, q in enumerate(_wrist_first_poses(n, seed + 7)):
-        qpos[i, :6] = q; qpos[i, 1] += 0.01; qpos[i, 6:9] = [0.15, -0.25, 0.0099]; qpos[i, 9] = 1.0; qvel[i, :6] = rs.randn(6)*0.3
-    act = rs.uniform(-1, 1, (n, 6)).astype(np.float32); act[:, 1] = 0.5
-    return qpos, qvel, act
-
-
 def test_link_proxies_per_substep_host_fp32(H):
     _link_proxies_per_substep_host_fp32(H, (4, 30))
 
@@ -166,10 +120,10 @@ def _link_proxies_per_substep_host_fp32(H, iters):
     n = 48
     qpos, qvel, act = wrist_first_batch(n, 0)
     T = SH.run_substep_parity(HostDevice(H, n, LINKS, iters), qpos, qvel, act, LINKS, 32, f"host fp32 {iters}, link proxies, wrist first")
-    _check(T, n_pairs_min_contact=n*32//3, iters=iters)
-    qpos, qvel, act = SH.floor_batch(n, 0)                    # pads AND proxies on the table
+    SH.check_tally(T, min_contact=n*32//3, iters=iters)
+    qpos, qvel, act = floor_batch(n, 0)                    # pads AND proxies on the table
     T = SH.run_substep_parity(HostDevice(H, n, LINKS, iters), qpos, qvel, act, LINKS, 24, f"host fp32 {iters}, link proxies + pads")
-    _check(T, n_pairs_min_contact=n*24//2, iters=iters)
+    SH.check_tally(T, min_contact=n*24//2, iters=iters)
 
 
 def test_link_proxies_with_the_coupled_grasp_per_substep_host_fp32(H):
@@ -183,27 +137,12 @@ def test_link_proxies_with_the_coupled_grasp_per_substep_host_fp32_at_shipped_se
 
 def _link_proxies_with_the_coupled_grasp_per_substep_host_fp32(H, iters):
     n, flags = 24, LINKS | O.F_PADS_CUBE
-    qpos, qvel, act = SH.grasp_batch(n, 1)
+    qpos, qvel, act = grasp_batch(n, 1)
     T = SH.run_substep_parity(HostDevice(H, n, flags, iters), qpos, qvel, act, flags, 40, f"host fp32 {iters}, link proxies + grasp")
-    _check(T, n_pairs_min_contact=n*40//4, coupled_min=n*40//5, iters=iters)
+    SH.check_tally(T, min_contact=n*40//4, min_coupled=n*40//5, iters=iters)
 
 
 # ---- link proxies against the cube (SO100_F_LINKS_CUBE: Rotation_Pitch / Upper_Arm vs block_a) ---------------------------
-LCUBE = O.F_REFERENCE | O.F_LINKS_FLOOR | O.F_LINKS_CUBE
-
-
-def link_cube_batch(n, seed):
-    """the cube placed against the Rotation_Pitch / Upper_Arm capsule (alternating), 0.2-3 mm deep, random joint and cube velocities"""
-    from test_oracle_contacts import link_cube_states
-    rs = np.random.RandomState(seed)
-    qpos = np.zeros((n, 13)); qvel = np.zeros((n, 12))
-    for i, (q, c, qc) in enumerate(link_cube_states(n, seed + 3)):
-        qpos[i, :6] = q; qpos[i, 6:9] = c; qpos[i, 9:13] = qc
-        qvel[i, :6] = rs.randn(6)*0.3; qvel[i, 6:9] = rs.randn(3)*0.02
-    act = rs.uniform(-1, 1, (n, 6)).astype(np.float32)
-    return qpos, qvel, act
-
-
 def test_link_cube_per_substep_host_fp32(H):
     _link_cube_per_substep_host_fp32(H, (4, 30))
 
@@ -217,8 +156,8 @@ def _link_cube_per_substep_host_fp32(H, iters):
     n = 32
     qpos, qvel, act = link_cube_batch(n, 0)
     T = SH.run_substep_parity(HostDevice(H, n, LCUBE, iters), qpos, qvel, act, LCUBE, 12, f"host fp32 {iters}, link proxies vs cube")
-    _check(T, n_pairs_min_contact=n*12//3, coupled_min=n*12//3, iters=iters)
+    SH.check_tally(T, min_contact=n*12//3, min_coupled=n*12//3, iters=iters)
     flags = LCUBE | O.F_PADS_CUBE                            # the closing-jaw grasp with every proxy pair switched on as well
-    qpos, qvel, act = SH.grasp_batch(16, 2)
+    qpos, qvel, act = grasp_batch(16, 2)
     T = SH.run_substep_parity(HostDevice(H, 16, flags, iters), qpos, qvel, act, flags, 32, f"host fp32 {iters}, all proxies + grasp")
-    _check(T, n_pairs_min_contact=16*32//4, coupled_min=16*32//5, iters=iters)
+    SH.check_tally(T, min_contact=16*32//4, min_coupled=16*32//5, iters=iters)

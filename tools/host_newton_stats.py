@@ -2,21 +2,15 @@
 tests/_hostcheck; no GPU): Env01, reference physics, random actions, staggered episodes.  Per solve: histograms of gradient +
 Hessian passes, sign passes, gradient passes, line-search passes.  Used to design the solver; the GPU numbers are in profiles/.
     python tools/host_newton_stats.py [envs] [steps]"""
-import ctypes as C, os, subprocess, sys
+import ctypes as C, os, sys
 import numpy as np
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-subprocess.check_call(["make", "-C", os.path.join(ROOT, "tests", "_hostcheck"), "-s"])
-H = C.CDLL(os.path.join(ROOT, "tests", "_hostcheck", os.environ.get("HC_LIB", "libhostcheck.so")))
-H.hc_env_new.restype = C.c_void_p
-H.hc_env_reset.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_uint, C.c_void_p, C.c_void_p]
-H.hc_env_step.argtypes = [C.c_void_p, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint] + [C.c_void_p] * 7
-for f in ("hc_cdbg_passes", "hc_cdbg_signpasses", "hc_cdbg_gradpasses", "hc_cdbg_lastiter"):
-    getattr(H, f).restype = C.c_long
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+from hostlibs import hostcheck, ptr as P
+H = hostcheck(os.environ.get("HC_LIB", "libhostcheck.so"))            # HC_LIB: another build of tests/_hostcheck/hostcheck.cpp (A/B of the solver)
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 128
 steps = int(sys.argv[2]) if len(sys.argv) > 2 else 400
 FLAGS = 1 | 2 | 4 | 16
 rs = np.random.RandomState(0)
-P = lambda a: a.ctypes.data_as(C.c_void_p)
 envs = [C.c_void_p(H.hc_env_new(1)) for _ in range(n)]
 obs = np.zeros(15, np.float32); tobs = np.zeros(15, np.float32); rew = C.c_float(); done = C.c_int(); trunc = C.c_int()
 for e in envs:

@@ -35,7 +35,7 @@ ra, fa = rate(sim, held, 10, 20); sim.close()
 print(f"(a) held off the table      : {ra:.3f} G env-steps/s, envs in contact {fa:.3f}")
 # (b) every arm at the table: poses with the lowest pad corner within +-1 cm of the floor, random actions, timed over the first 12 steps
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
-from test_oracle_contacts import floor_poses
+from scenes import floor_poses
 poses = np.array(floor_poses(512, 1, band=0.01)); rs = np.random.RandomState(0)
 sim = So100Sim(1, n, flags=F_REFERENCE, seed=2, max_episode_steps=0); sim.reset()
 qp = torch.zeros(13, n, device="cuda"); qp[9] = 1.0; qp[6] = 0.2; qp[7] = -0.2; qp[8] = 0.0099
