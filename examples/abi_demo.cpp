@@ -1,11 +1,13 @@
-// abi_demo.cpp -- a plain C++ consumer of the C ABI (include/so100_sim.h): no Python, no PyTorch.
+// abi_demo.cpp -- a plain C++ consumer of the C ABI (include/so100_sim.h, include/so100_learn.h): no Python, no PyTorch.
 // Build:  hipcc -O2 -o abi_demo examples/abi_demo.cpp -Iinclude -Lso100_mujoco_rl_amd -lso100sim -Wl,-rpath,$PWD/so100_mujoco_rl_amd
-// Run:    ./abi_demo [num_envs] [steps]     (prints a checksum of the final observations)
+// Run:    ./abi_demo [num_envs] [steps]     (prints a checksum of the final observations, then one line from the learner)
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
+#include <cmath>
 #include <vector>
 #include "so100_sim.h"
+#include "so100_learn.h"
 
 #define CHECK(x) do { if ((x) != hipSuccess) { std::fprintf(stderr, "HIP error at %s:%d\n", __FILE__, __LINE__); return 2; } } while (0)
 
@@ -38,6 +40,43 @@ int main(int argc, char** argv) {
     CHECK(hipMemcpy(h_rew.data(), rew, sizeof(float)*n, hipMemcpyDeviceToHost));
     double cs = 0, rs = 0; for (float v : h_obs) cs += v; for (float v : h_rew) rs += v;
     std::printf("envs %d steps %d  %.1f us/step  %.2f M env-steps/s  obs_checksum %.6f  reward_sum %.6f\n", n, steps, ms*1e3/steps, n*(double)steps/ms/1e3, cs, rs);
+    // ---- the learner from plain C++ (so100_learn.h): advantages of a small synthetic chunk, then one PPO minibatch step on all of it
+    {
+        const int T = 4, k = od + 10, P = so100_learner_num_params(od);
+        auto rnd = [](size_t i) { return (float)((i*2654435761u) % 2001) / 1000.0f - 1.0f; };
+        std::vector<float> h_chunk((size_t)T*n*k), h_par(P), h_last((size_t)n*od);
+        for (size_t i = 0; i < h_chunk.size(); i++) h_chunk[i] = rnd(i);
+        for (size_t r = 0; r < (size_t)T*n; r++) { h_chunk[r*k + od + 7] = (float)(r % 7 == 3); h_chunk[r*k + od + 9] = -6.0f; }   // done code 0 / 1, old log-prob
+        for (int i = 0; i < P; i++) h_par[i] = 0.2f*rnd(7919u*(size_t)i + 1);
+        for (size_t i = 0; i < h_last.size(); i++) h_last[i] = rnd(i + 12345);
+        so100_learner_config lc = {};
+        lc.obs_dim = od; lc.device = 0; lc.max_minibatch = T*n; lc.gamma = 0.99f; lc.gae_lambda = 0.95f; lc.clip_range = 0.2f; lc.vf_coef = 0.5f;
+        lc.max_grad_norm = 0.5f; lc.lr = 3e-4; lc.beta1 = 0.9; lc.beta2 = 0.999; lc.adam_eps = 1e-5;
+        so100_learner* learner = nullptr;
+        if (so100_learner_create(&lc, &learner) != 0) { std::fprintf(stderr, "so100_learner_create: %s\n", so100_last_error()); return 1; }
+        float *chunk, *par, *mom, *last, *adv, *ret, *lstat;              // lstat: adv_stats[2] | stats[4]
+        CHECK(hipMalloc(&chunk, sizeof(float)*h_chunk.size())); CHECK(hipMalloc(&par, sizeof(float)*P)); CHECK(hipMalloc(&mom, sizeof(float)*2*P));
+        CHECK(hipMalloc(&last, sizeof(float)*h_last.size())); CHECK(hipMalloc(&adv, sizeof(float)*T*n)); CHECK(hipMalloc(&ret, sizeof(float)*T*n));
+        CHECK(hipMalloc(&lstat, sizeof(float)*6));
+        CHECK(hipMemcpy(chunk, h_chunk.data(), sizeof(float)*h_chunk.size(), hipMemcpyHostToDevice));
+        CHECK(hipMemcpy(par, h_par.data(), sizeof(float)*P, hipMemcpyHostToDevice));
+        CHECK(hipMemcpy(last, h_last.data(), sizeof(float)*h_last.size(), hipMemcpyHostToDevice));
+        CHECK(hipMemset(mom, 0, sizeof(float)*2*P));
+        so100_advantages_io aio = {};
+        aio.rollout_dev = chunk; aio.last_obs_dev = last; aio.params_dev = par; aio.adv_dev = adv; aio.ret_dev = ret; aio.adv_stats_dev = lstat;
+        if (so100_learner_advantages(learner, &aio, T, n, (void*)st) != 0) { std::fprintf(stderr, "so100_learner_advantages: %s\n", so100_last_error()); return 1; }
+        so100_minibatch_io mio = {};
+        mio.rollout_dev = chunk; mio.num_samples = (int64_t)T*n; mio.idx_dev = nullptr; mio.mb = T*n; mio.adam_step = 1;
+        mio.adv_dev = adv; mio.ret_dev = ret; mio.adv_stats_dev = lstat; mio.params_dev = par; mio.adam_m_dev = mom; mio.adam_v_dev = mom + P; mio.stats_dev = lstat + 2;
+        if (so100_learner_minibatch_step(learner, &mio, (void*)st) != 0) { std::fprintf(stderr, "so100_learner_minibatch_step: %s\n", so100_last_error()); return 1; }
+        CHECK(hipStreamSynchronize(st));
+        float h_st[6]; std::vector<float> h_new(P);
+        CHECK(hipMemcpy(h_st, lstat, sizeof h_st, hipMemcpyDeviceToHost)); CHECK(hipMemcpy(h_new.data(), par, sizeof(float)*P, hipMemcpyDeviceToHost));
+        double moved = 0; for (int i = 0; i < P; i++) moved += std::fabs((double)h_new[i] - h_par[i]);
+        std::printf("learner: %d params  adv_mean %.6f adv_std %.6f  policy_loss %.6f value_loss %.6f clip_fraction %.4f grad_norm %.6f  mean_param_step %.3e\n",
+                    P, h_st[0], h_st[1], h_st[2], h_st[3], h_st[4], h_st[5], moved/P);
+        so100_learner_destroy(learner);
+    }
     so100_destroy(sim);
     return 0;
 }

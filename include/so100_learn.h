@@ -1,0 +1,95 @@
+/* so100_learn.h -- C ABI of the on-device PPO learner of libso100sim.so: advantages (GAE with the TimeLimit bootstrap) and one
+ * clipped-surrogate gradient step with gradient-norm clipping and Adam, for the fixed SB3 "MlpPolicy" network the rollout kernels
+ * run (two 2 x 64 tanh towers, state-independent log_std; so100_policy_weights in so100_sim.h).  It replaces, for that network,
+ * stable_baselines3 RolloutBuffer.compute_returns_and_advantage and the body of PPO.train's minibatch loop (here: ppo.py PPO._gae /
+ * PPO._step).  Additive to so100_sim.h: SO100_ABI_VERSION and every declaration there are unchanged; error codes and
+ * so100_last_error() are shared.
+ *
+ * Conventions (those of so100_sim.h)
+ *   - extern "C", plain pointers and sizes; `*_dev` pointers are DEVICE pointers owned by the caller: the parameters, the Adam
+ *     moments and every rollout buffer.  The handle owns scratch only (per-workgroup partial gradients, bounded by max_minibatch).
+ *   - 0 on success, a negative SO100_E_* code otherwise, message in so100_last_error().
+ *   - all work is enqueued on the caller's `hip_stream`; after so100_learner_create nothing allocates, frees or synchronises.
+ *   - there is NO CPU fallback.
+ *   - deterministic: gradients are reduced in a fixed order (per-workgroup partials, then an ordered sum); no floating-point
+ *     atomics.  The same inputs give bit-identical parameters.
+ *
+ * The flat parameter block: so100_learner_num_params(obs_dim) floats holding the 13 tensors of so100_policy_weights in that struct's
+ * order (pi_w0, pi_b0, pi_w1, pi_b1, mu_w, mu_b, log_std, vf_w0, vf_b0, vf_w1, vf_b1, v_w, v_b), each in PyTorch nn.Linear layout
+ * weight[out][in] row-major; so100_learner_param_offset() places them.  A so100_policy_weights may point straight into the block.
+ * adam_m / adam_v / grads have the same layout.
+ */
+#ifndef SO100_LEARN_H
+#define SO100_LEARN_H
+#include <stdint.h>
+#include "so100_sim.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct so100_learner so100_learner;
+
+typedef struct {
+    int32_t obs_dim;              /* 15 or 8 (so100_obs_dim)                                                    */
+    int32_t device;               /* HIP device ordinal                                                         */
+    int32_t max_minibatch;        /* largest mb of so100_learner_minibatch_step (>= 1); bounds the scratch       */
+    float   gamma;                /* 0.99                                                                        */
+    float   gae_lambda;           /* 0.95                                                                        */
+    float   clip_range;           /* 0.2                                                                         */
+    float   vf_coef;              /* 0.5                                                                         */
+    float   max_grad_norm;        /* 0.5                                                                         */
+    double  lr;                   /* 3e-4.  Adam's scalars are doubles: torch forms 1 - beta, lr/(1 - beta1^t) in double      */
+    double  beta1, beta2;         /* 0.9, 0.999   (as a float, 1 - 0.999f is 1.3e-5 away from 0.001)                          */
+    double  adam_eps;             /* 1e-5 (added to sqrt(v_hat), as torch.optim.Adam does)                                    */
+} so100_learner_config;
+
+/* Advantages and returns of one rollout chunk: rollout.bootstrap_truncated followed by PPO._gae.
+ *   r' = r + gamma V(terminal_obs) where the done code is 2 and terminal_obs_chunk_dev is non-null, else r
+ *   nonterm = (code == 0);  next_v = V(last_obs) at t = T-1, else value[t+1]
+ *   delta = r' + gamma next_v nonterm - value[t];  g = delta + gamma lambda nonterm g;  adv = g;  ret = adv + value
+ * The chunk is read only (reward, done-code and value columns) and left unmodified.  The value tower runs on the N last observations
+ * and on the code-2 entries alone.  N is any positive number (it need not be a sim handle's N). */
+typedef struct {
+    const float* rollout_dev;            /* [T][N][obs_dim+10], as so100_rollout wrote it                                  */
+    const float* terminal_obs_chunk_dev; /* [T][N][obs_dim], read where the done code is 2; nullable (then no bootstrap)   */
+    const float* last_obs_dev;           /* [N][obs_dim] observation after the chunk's last step                           */
+    const float* params_dev;             /* the parameter block whose value tower produced the chunk's values              */
+    float*       adv_dev;                /* [T][N] out                                                                     */
+    float*       ret_dev;                /* [T][N] out                                                                     */
+    float*       adv_stats_dev;          /* [2] out: mean and unbiased standard deviation of adv over all T*N entries      */
+} so100_advantages_io;
+
+/* One PPO gradient step on the samples idx_dev names (PPO._step + clip_grad_norm_ + Adam.step):
+ *   A = (adv - mean)/(std + 1e-8);  logp = sum(-((a - mu)/sigma)^2/2 - log sigma - log(2 pi)/2);  ratio = exp(logp - logp_old)
+ *   L = -mean(min(ratio A, clamp(ratio, 1-c, 1+c) A)) + vf_coef mean((ret - V)^2)          (no entropy term, no value clipping)
+ *   g *= min(1, max_grad_norm/(|g|_2 + 1e-6)) over all 13 tensors;  bias-corrected Adam.
+ * Observation, raw action and old log-prob are read in place from the packed chunk through idx. */
+typedef struct {
+    const float*   rollout_dev;    /* [num_samples][obs_dim+10] the packed chunk, rows t*N + n                                  */
+    int64_t        num_samples;    /* T*N: an index outside [0, num_samples) contributes nothing                                */
+    const int64_t* idx_dev;        /* [mb] int64 flat row indices (what torch.randperm yields), any order; NULL = 0..mb-1       */
+    int32_t        mb;             /* 1 <= mb <= max_minibatch                                                                  */
+    int32_t        adam_step;      /* 1-based number of this Adam step                                                          */
+    const float*   adv_dev;        /* [num_samples]  from so100_learner_advantages                                              */
+    const float*   ret_dev;        /* [num_samples]                                                                             */
+    const float*   adv_stats_dev;  /* [2]                                                                                       */
+    float*         params_dev;     /* [P] updated in place                                                                      */
+    float*         adam_m_dev;     /* [P] updated in place                                                                      */
+    float*         adam_v_dev;     /* [P] updated in place                                                                      */
+    float*         stats_dev;      /* [4] out: policy loss, value loss, clip fraction (|ratio - 1| > c), pre-clip gradient norm */
+    float*         grads_dev;      /* [P] out, nullable: the reduced gradient times the clip coefficient (what Adam consumed)    */
+} so100_minibatch_io;
+
+int  so100_learner_num_params(int32_t obs_dim);                          /* 10829 (obs_dim 15), 9933 (8); < 0 otherwise */
+int  so100_learner_param_offset(int32_t obs_dim, const char* name);      /* name: a member of so100_policy_weights; < 0 if unknown */
+int  so100_learner_param_size(int32_t obs_dim, const char* name);        /* elements of that tensor                      */
+int  so100_learner_create(const so100_learner_config* cfg, so100_learner** out);
+void so100_learner_destroy(so100_learner* learner);
+int  so100_learner_advantages(so100_learner* learner, const so100_advantages_io* io, int32_t T, int32_t N, void* hip_stream);
+int  so100_learner_minibatch_step(so100_learner* learner, const so100_minibatch_io* io, void* hip_stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* SO100_LEARN_H */

@@ -17,7 +17,7 @@ from .rollout import RolloutChunk, bootstrap_truncated, gather_rollout, mean_ove
 
 
 class RolloutCollector:
-    def __init__(self, vec_env, state_dict, T=64, persistent=None, gamma=0.99, bootstrap_truncated=True):
+    def __init__(self, vec_env, state_dict, T=64, persistent=None, gamma=0.99, bootstrap_truncated=True, defer_bootstrap=False):
         self.env = vec_env; self.sim = vec_env.sim
         self.T = T
         self.chunk = RolloutChunk(T, self.sim.n, self.sim.obs_dim, self.sim.device)
@@ -25,6 +25,9 @@ class RolloutCollector:
         # (OnPolicyAlgorithm.collect_rollouts); every episode end of Env01/02/06 is such a truncation.  The kernels mark them
         # (done column == 2) and deliver the terminal observations; the value net is applied here, before any gather.
         self.gamma = gamma; self.bootstrap = bootstrap_truncated
+        # defer_bootstrap (one GPU, the fused learner): the terminal observations are collected as above but the rewards are left alone;
+        # they travel in collect()'s dict as "terminal_obs" and so100_learner_advantages applies gamma * V to the code-2 steps itself
+        self.defer = bool(defer_bootstrap) and bootstrap_truncated
         self.tobs = torch.zeros(T, self.sim.n, self.sim.obs_dim, device=self.sim.device) if bootstrap_truncated else None
         self.act = torch.zeros(self.sim.n, 6, device=self.sim.device)
         self.counter = 0
@@ -103,7 +106,9 @@ class RolloutCollector:
         # statistics are taken from the ENV's rewards, before the bootstrap adds the critic's gamma * V(terminal_observation) to the
         # truncated steps: model selection / early stopping / the "reward/step" log line must not depend on the value estimates
         raw_mean = buf[..., o + 6].mean()
-        if self.bootstrap:
+        if self.defer and gather_dst is not None:
+            raise ValueError("defer_bootstrap is for one GPU: a gathered chunk is bootstrapped before the gather")
+        if self.bootstrap and not self.defer:
             bootstrap_truncated(buf[..., o + 6], buf[..., o + 7], self.tobs[:T], self._value, self.gamma)
         last_obs = self.sim.obs
         if gather_dst is not None:
@@ -115,5 +120,8 @@ class RolloutCollector:
             last_obs = last_obs[0]
         out = self.chunk.unpack(buf)
         out["last_obs"] = last_obs
+        out["packed"] = buf                                  # the [T, N, obs_dim+10] chunk itself (the entries above are views of it): what the fused learner reads in place
+        if self.defer:
+            out["terminal_obs"] = self.tobs[:T]
         out["raw_reward_mean"] = raw_mean                    # 0-d tensor: mean env reward per step of this chunk (all ranks), bootstrap excluded
         return out

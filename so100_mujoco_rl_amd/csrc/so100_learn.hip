@@ -1,0 +1,520 @@
+// so100_learn.hip -- the on-device PPO learner behind include/so100_learn.h: advantages (three launches) and one minibatch gradient
+// step (three launches), for the fixed 2 x 64 tanh towers of so100_policy.hpp.  The per-sample and per-parameter arithmetic is in
+// so100_learn.hpp (host-compilable templates, held to an fp64 reference by tests/_learncheck); this file holds the data movement.
+//
+// Gradient kernel (so100_learn_grad): a bounded persistent grid of 256-thread workgroups; each owns tiles of 64 samples gathered
+// through idx.  One tower at a time (the towers meet only in the sum of the loss).  In the sample-major phases lane = sample and wave
+// q owns hidden units 16q..16q+15: the weights are wave-uniform, read straight from the parameter block through the scalar cache,
+// the activations of a sample stay in its lane's registers or go through LDS images [sample][unit] with a row stride of 68 words
+// (16-byte rows: every image access is a ds_read/write_b128; lanes 0..15 of a b128 group then cover all 64 banks).  The weight
+// gradients dW = dZ^T . X need the reduction over samples, so that phase is unit-major: every thread owns a 4 x 4 block of dW1, four
+// entries of dW0 and of the head, accumulates them in REGISTERS over all samples of all its tiles (two b128 LDS reads per 16 FMAs)
+// and writes them once, as this workgroup's partial.  Plain FMA throughout: fp32-input MFMA runs at the VALU's rate on gfx950, and the
+// unit-major products have the samples on the reduced axis, which the MFMA operand layout would want transposed once more.
+// Reduction (so100_learn_reduce): one thread per parameter sums the partials in workgroup order and leaves each block's sum of
+// squares; so100_learn_adam sums those in block order (every thread the same sum), decides the clip and applies Adam.
+// No floating-point atomics anywhere; every sum has a fixed order => bit-identical results for identical inputs.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <string.h>
+#include <math.h>
+#include <new>
+#include "../../include/so100_learn.h"
+#include "so100_policy.hpp"
+#include "so100_learn.hpp"
+
+namespace so100 {
+int set_last_error(int code, const char* msg);            // so100_sim.hip: the thread-local message behind so100_last_error()
+
+namespace learn {
+
+constexpr int LT = 64;                 // samples per tile
+constexpr int LLD = 68;                // row stride (words) of the [sample][unit] LDS images
+constexpr int XLD = 17, DOLD = 13, HPLD = 7;      // odd strides of the small images (scalar accesses, lane = sample)
+constexpr int GRID_MAX = 256;          // workgroups of the gradient kernel = partials to reduce (one per CU of an MI355X)
+constexpr int NSTAT = 3;               // sums riding behind a partial's P gradients: policy loss, value loss, clipped count
+constexpr int ADV_THREADS = 1024;
+
+__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+__device__ __forceinline__ void st4(float* p, float a, float b, float c, float d) { *reinterpret_cast<float4*>(p) = make_float4(a, b, c, d); }
+
+struct GradArgs {
+    const float* chunk; long num_samples; const int64_t* idx; int mb;
+    const float* adv; const float* ret; const float* adv_stats; const float* params; float* partial;
+    float clip, vf_coef;
+};
+
+struct GradSmem {
+    alignas(16) float H1[LT*LLD], H2[LT*LLD], D2[LT*LLD], D1[LT*LLD];
+    float X[LT*XLD], DO[LT*DOLD], HP[4*LT*HPLD];
+};
+
+// one tower's forward and backward pass over this workgroup's tiles; writes the tower's slice of the workgroup's partial
+template <int OD, int TW>
+__device__ __forceinline__ void tower_pass(const GradArgs& A, GradSmem& S) {
+    constexpr int ROW = OD + ROW_EXTRA, NH = TW ? 1 : ACT_DIM, P = num_params(OD);
+    constexpr int oW0 = tensor_offset(TW ? T_VF_W0 : T_PI_W0, OD), oB0 = tensor_offset(TW ? T_VF_B0 : T_PI_B0, OD);
+    constexpr int oW1 = tensor_offset(TW ? T_VF_W1 : T_PI_W1, OD), oB1 = tensor_offset(TW ? T_VF_B1 : T_PI_B1, OD);
+    constexpr int oWH = tensor_offset(TW ? T_V_W : T_MU_W, OD), oBH = tensor_offset(TW ? T_V_B : T_MU_B, OD), oLS = tensor_offset(T_LOG_STD, OD);
+    const float* __restrict__ prm = A.params;
+    const float* __restrict__ W0 = prm + oW0; const float* __restrict__ B0 = prm + oB0;
+    const float* __restrict__ W1 = prm + oW1; const float* __restrict__ B1 = prm + oB1;
+    const float* __restrict__ WH = prm + oWH; const float* __restrict__ BH = prm + oBH;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int q = __builtin_amdgcn_readfirstlane(tid >> 6);                // wave-uniform: weight addresses stay scalar
+    const int u0 = 16*q;                                                    // first hidden unit of this wave in the sample-major phases
+    const int jb = tid & 15, kb = tid >> 4;                                 // unit-major phase: rows 4jb.. x columns 4kb.. of dW1
+    const int xi = kb < OD ? kb : OD - 1, hi = kb < NH ? kb : NH - 1, ci = tid < 2*ACT_DIM ? tid : 2*ACT_DIM;
+    const float inv_mb = 1.0f/(float)A.mb;
+    const float a_mean = A.adv_stats[0], a_scale = 1.0f/(A.adv_stats[1] + 1e-8f);
+    float gW1[16], gW0[4], gB1[4], gB0[4], gWh[4], gcol = 0.0f;
+#pragma unroll
+    for (int i = 0; i < 16; i++) gW1[i] = 0.0f;
+#pragma unroll
+    for (int i = 0; i < 4; i++) gW0[i] = gB1[i] = gB0[i] = gWh[i] = 0.0f;
+    float s_loss = 0.0f, s_clip = 0.0f;                                     // wave 0, lane = sample: sums over this lane's samples
+    const int ntiles = (A.mb + LT - 1)/LT;
+    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const int sm = tile*LT + lane;
+        bool valid = sm < A.mb;
+        long row = valid ? (A.idx ? (long)A.idx[sm] : (long)sm) : 0;
+        if (row < 0 || row >= A.num_samples) { valid = false; row = 0; }  // an index outside the chunk contributes nothing
+        const float* __restrict__ r = A.chunk + row*ROW;
+        float x[OD];
+#pragma unroll
+        for (int i = 0; i < OD; i++) x[i] = valid ? r[i] : 0.0f;
+        // ---- layer 1, units u0..u0+15 of this lane's sample
+        float h1[16];
+#pragma unroll
+        for (int jj = 0; jj < 16; jj++) {
+            float acc = B0[u0 + jj];
+#pragma unroll
+            for (int i = 0; i < OD; i++) acc = fmaf(W0[(u0 + jj)*OD + i], x[i], acc);
+            h1[jj] = fast_tanh(acc);
+        }
+#pragma unroll
+        for (int c = 0; c < 4; c++) st4(&S.H1[lane*LLD + u0 + 4*c], h1[4*c], h1[4*c + 1], h1[4*c + 2], h1[4*c + 3]);
+        if (q == 0) {
+#pragma unroll
+            for (int i = 0; i < OD; i++) S.X[lane*XLD + i] = x[i];
+        }
+        __syncthreads();
+        // ---- layer 2
+        float h2[16];
+#pragma unroll
+        for (int jj = 0; jj < 16; jj++) h2[jj] = B1[u0 + jj];
+#pragma unroll 2
+        for (int k = 0; k < HID; k += 4) {
+            const float4 hv = ld4(&S.H1[lane*LLD + k]);
+#pragma unroll
+            for (int jj = 0; jj < 16; jj++) {
+                const float* w = W1 + (u0 + jj)*HID + k;
+                h2[jj] = fmaf(w[3], hv.w, fmaf(w[2], hv.z, fmaf(w[1], hv.y, fmaf(w[0], hv.x, h2[jj]))));
+            }
+        }
+#pragma unroll
+        for (int jj = 0; jj < 16; jj++) h2[jj] = fast_tanh(h2[jj]);
+#pragma unroll
+        for (int c = 0; c < 4; c++) st4(&S.H2[lane*LLD + u0 + 4*c], h2[4*c], h2[4*c + 1], h2[4*c + 2], h2[4*c + 3]);
+        // ---- head: this wave's 16 units' share of each output
+#pragma unroll
+        for (int i = 0; i < NH; i++) {
+            float p = 0.0f;
+#pragma unroll
+            for (int jj = 0; jj < 16; jj++) p = fmaf(WH[i*HID + u0 + jj], h2[jj], p);
+            S.HP[(q*LT + lane)*HPLD + i] = p;
+        }
+        __syncthreads();
+        // ---- loss head of this lane's sample (every wave computes it: each needs the output derivatives for its units)
+        float out[NH], dout[NH];
+#pragma unroll
+        for (int i = 0; i < NH; i++)
+            out[i] = (((BH[i] + S.HP[(0*LT + lane)*HPLD + i]) + S.HP[(1*LT + lane)*HPLD + i]) + S.HP[(2*LT + lane)*HPLD + i]) + S.HP[(3*LT + lane)*HPLD + i];
+        LossHead<float> L;
+        if constexpr (TW == 0) {
+            float a[ACT_DIM], ls[ACT_DIM];
+#pragma unroll
+            for (int i = 0; i < ACT_DIM; i++) { a[i] = valid ? r[OD + ROW_ACT + i] : 0.0f; ls[i] = prm[oLS + i]; }
+            const float logp_old = valid ? r[OD + ROW_LOGP] : 0.0f;
+            const float adv_n = valid ? (A.adv[row] - a_mean)*a_scale : 0.0f;
+            policy_loss_head<float>(out, ls, a, logp_old, adv_n, A.clip, inv_mb, L);
+#pragma unroll
+            for (int i = 0; i < ACT_DIM; i++) { dout[i] = valid ? L.dmu[i] : 0.0f; L.dlog_std[i] = valid ? L.dlog_std[i] : 0.0f; }
+            s_loss += valid ? L.pg_loss : 0.0f; s_clip += valid ? L.clipped : 0.0f;
+            if (q == 0) {
+#pragma unroll
+                for (int i = 0; i < ACT_DIM; i++) { S.DO[lane*DOLD + i] = dout[i]; S.DO[lane*DOLD + ACT_DIM + i] = L.dlog_std[i]; }
+                S.DO[lane*DOLD + 2*ACT_DIM] = 0.0f;
+            }
+        } else {
+            value_loss_head<float>(out[0], valid ? A.ret[row] : 0.0f, A.vf_coef, inv_mb, L);
+            dout[0] = valid ? L.dV : 0.0f;
+            s_loss += valid ? L.v_loss : 0.0f;
+            if (q == 0) {
+                S.DO[lane*DOLD] = dout[0];
+#pragma unroll
+                for (int i = 1; i <= 2*ACT_DIM; i++) S.DO[lane*DOLD + i] = 0.0f;
+            }
+        }
+        // ---- dZ2 of this wave's units
+        float d2[16];
+#pragma unroll
+        for (int jj = 0; jj < 16; jj++) {
+            float d = 0.0f;
+#pragma unroll
+            for (int i = 0; i < NH; i++) d = fmaf(WH[i*HID + u0 + jj], dout[i], d);
+            d2[jj] = d*(1.0f - h2[jj]*h2[jj]);
+        }
+#pragma unroll
+        for (int c = 0; c < 4; c++) st4(&S.D2[lane*LLD + u0 + 4*c], d2[4*c], d2[4*c + 1], d2[4*c + 2], d2[4*c + 3]);
+        __syncthreads();
+        // ---- dZ1 of this wave's units: dH1 = dZ2 . W1
+        float d1[16];
+#pragma unroll
+        for (int kk = 0; kk < 16; kk++) d1[kk] = 0.0f;
+#pragma unroll 2
+        for (int j = 0; j < HID; j += 4) {
+            const float4 dv = ld4(&S.D2[lane*LLD + j]);
+#pragma unroll
+            for (int kk = 0; kk < 16; kk++) {
+                const float* w = W1 + j*HID + u0 + kk;
+                d1[kk] = fmaf(w[3*HID], dv.w, fmaf(w[2*HID], dv.z, fmaf(w[HID], dv.y, fmaf(w[0], dv.x, d1[kk]))));
+            }
+        }
+#pragma unroll
+        for (int kk = 0; kk < 16; kk++) d1[kk] *= 1.0f - h1[kk]*h1[kk];
+#pragma unroll
+        for (int c = 0; c < 4; c++) st4(&S.D1[lane*LLD + u0 + 4*c], d1[4*c], d1[4*c + 1], d1[4*c + 2], d1[4*c + 3]);
+        __syncthreads();
+        // ---- weight gradients, unit-major: sums over the tile's samples in sample order.  Every thread forms every kind of sum (clamped
+        // indices); the write-out below keeps the ones it owns.
+#pragma unroll 2
+        for (int s = 0; s < LT; s++) {
+            const float4 dj = ld4(&S.D2[s*LLD + 4*jb]), hk = ld4(&S.H1[s*LLD + 4*kb]);
+            const float4 dk = ld4(&S.D1[s*LLD + 4*jb]), hj = ld4(&S.H2[s*LLD + 4*jb]);
+            const float xs = S.X[s*XLD + xi], ds = S.DO[s*DOLD + hi];
+            const float dja[4] = { dj.x, dj.y, dj.z, dj.w }, hka[4] = { hk.x, hk.y, hk.z, hk.w };
+            const float dka[4] = { dk.x, dk.y, dk.z, dk.w }, hja[4] = { hj.x, hj.y, hj.z, hj.w };
+#pragma unroll
+            for (int a = 0; a < 4; a++) {
+#pragma unroll
+                for (int b = 0; b < 4; b++) gW1[4*a + b] = fmaf(dja[a], hka[b], gW1[4*a + b]);
+                gB1[a] += dja[a];
+                gW0[a] = fmaf(dka[a], xs, gW0[a]);
+                gB0[a] += dka[a];
+                gWh[a] = fmaf(ds, hja[a], gWh[a]);
+            }
+            gcol += S.DO[s*DOLD + ci];
+        }
+        __syncthreads();                                                    // the images are rewritten by the next tile
+    }
+    // ---- this workgroup's partial: [P gradients | NSTAT sums]
+    float* __restrict__ pp = A.partial + (size_t)blockIdx.x*(P + NSTAT);
+#pragma unroll
+    for (int a = 0; a < 4; a++) {
+#pragma unroll
+        for (int b = 0; b < 4; b++) pp[oW1 + (4*jb + a)*HID + 4*kb + b] = gW1[4*a + b];
+        if (kb < OD) pp[oW0 + (4*jb + a)*OD + kb] = gW0[a];
+        if (kb == 0) { pp[oB1 + 4*jb + a] = gB1[a]; pp[oB0 + 4*jb + a] = gB0[a]; }
+        if (kb < NH) pp[oWH + kb*HID + 4*jb + a] = gWh[a];
+    }
+    if (tid < NH) pp[oBH + tid] = gcol;
+    if (TW == 0 && tid >= ACT_DIM && tid < 2*ACT_DIM) pp[oLS + tid - ACT_DIM] = gcol;
+    // the loss sums of wave 0's lanes, added in lane order by one thread
+    if (q == 0) { S.HP[lane] = s_loss; S.HP[LT + lane] = s_clip; }
+    __syncthreads();
+    if (tid == 0) {
+        float a = 0.0f, c = 0.0f;
+        for (int l = 0; l < LT; l++) { a += S.HP[l]; c += S.HP[LT + l]; }
+        if (TW == 0) { pp[P + 0] = a; pp[P + 2] = c; } else pp[P + 1] = a;
+    }
+    __syncthreads();
+}
+
+template <int OD>
+__global__ __launch_bounds__(256) void so100_learn_grad(GradArgs A) {
+    __shared__ GradSmem S;
+    tower_pass<OD, 0>(A, S);
+    tower_pass<OD, 1>(A, S);
+}
+
+// one thread per entry of a partial: the sum over the G workgroups in workgroup order; each block leaves the sum of squares of its gradients
+__global__ __launch_bounds__(256) void so100_learn_reduce(const float* __restrict__ partial, int G, int P, float* __restrict__ gsum, float* __restrict__ sq_block) {
+    __shared__ float sq[256];
+    const int p = blockIdx.x*256 + threadIdx.x, PS = P + NSTAT;
+    float s = 0.0f;
+    if (p < PS) {
+        int g = 0;
+        for (; g + 8 <= G; g += 8) {                                       // eight loads in flight, added in workgroup order
+            float t[8];
+#pragma unroll
+            for (int i = 0; i < 8; i++) t[i] = partial[(size_t)(g + i)*PS + p];
+#pragma unroll
+            for (int i = 0; i < 8; i++) s += t[i];
+        }
+        for (; g < G; g++) s += partial[(size_t)g*PS + p];
+        gsum[p] = s;
+    }
+    sq[threadIdx.x] = p < P ? s*s : 0.0f;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) sq[threadIdx.x] += sq[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) sq_block[blockIdx.x] = sq[0];
+}
+
+struct AdamArgs { float max_grad_norm, step_size, omb1, beta2, omb2, eps, bc2_sqrt, inv_mb; };     // formed in double on the host (clip_adam_update)
+
+__global__ __launch_bounds__(256) void so100_learn_adam(const float* __restrict__ gsum, const float* __restrict__ sq_block, int nblk, int P,
+                                                        float* __restrict__ params, float* __restrict__ m, float* __restrict__ v,
+                                                        float* __restrict__ grads_out, float* __restrict__ stats_out, AdamArgs a) {
+    float ss = 0.0f;
+    for (int b = 0; b < nblk; b++) ss += sq_block[b];                      // the same ordered sum in every thread
+    const float norm = lsqrt(ss), coef = clip_coefficient<float>(norm, a.max_grad_norm);
+    const int p = blockIdx.x*256 + threadIdx.x;
+    if (p < P) {
+        float pv = params[p], mv = m[p], vv = v[p];
+        const float g = clip_adam_update<float>(gsum[p], coef, pv, mv, vv, a.step_size, a.omb1, a.beta2, a.omb2, a.eps, a.bc2_sqrt);
+        params[p] = pv; m[p] = mv; v[p] = vv;
+        if (grads_out) grads_out[p] = g;
+    }
+    if (p == 0) {
+        stats_out[0] = gsum[P + 0]*a.inv_mb; stats_out[1] = gsum[P + 1]*a.inv_mb; stats_out[2] = gsum[P + 2]*a.inv_mb; stats_out[3] = norm;
+    }
+}
+
+// ---- advantages -------------------------------------------------------------------------------------------------------------------------
+// V(obs) of one row in one lane: the weights are wave-uniform (scalar cache), the activations stay in registers
+template <int OD>
+__device__ __forceinline__ float value_tower(const float* __restrict__ prm, const float* __restrict__ obs) {
+    const float* __restrict__ W0 = prm + tensor_offset(T_VF_W0, OD); const float* __restrict__ B0 = prm + tensor_offset(T_VF_B0, OD);
+    const float* __restrict__ W1 = prm + tensor_offset(T_VF_W1, OD); const float* __restrict__ B1 = prm + tensor_offset(T_VF_B1, OD);
+    const float* __restrict__ VW = prm + tensor_offset(T_V_W, OD);
+    float x[OD], h1[HID];
+#pragma unroll
+    for (int i = 0; i < OD; i++) x[i] = obs[i];
+#pragma unroll
+    for (int j = 0; j < HID; j++) {
+        float acc = B0[j];
+#pragma unroll
+        for (int i = 0; i < OD; i++) acc = fmaf(W0[j*OD + i], x[i], acc);
+        h1[j] = fast_tanh(acc);
+    }
+    float v = prm[tensor_offset(T_V_B, OD)];
+#pragma unroll 2
+    for (int j = 0; j < HID; j++) {
+        float acc = B1[j];
+#pragma unroll
+        for (int k = 0; k < HID; k++) acc = fmaf(W1[j*HID + k], h1[k], acc);
+        v = fmaf(VW[j], fast_tanh(acc), v);
+    }
+    return v;
+}
+
+// The value tower where the scan needs it and nowhere else: rows [0, TN) are the chunk's entries, of which those with done code 2 get
+// V(terminal_obs) parked in ret (the scan reads it before it writes ret); rows [TN, TN + N) are the last observations, V parked in adv[T-1].
+template <int OD>
+__global__ __launch_bounds__(256) void so100_learn_values(const float* __restrict__ chunk, const float* __restrict__ tobs, const float* __restrict__ last_obs,
+                                                          const float* __restrict__ prm, long TN, int N, float* __restrict__ adv, float* __restrict__ ret) {
+    constexpr int ROW = OD + ROW_EXTRA;
+    const long r = (long)blockIdx.x*256 + threadIdx.x;
+    if (r < TN) {
+        if (tobs != nullptr && chunk[r*ROW + OD + ROW_DONE] == 2.0f) ret[r] = value_tower<OD>(prm, tobs + r*OD);
+    } else if (r < TN + N) {
+        adv[TN - N + (r - TN)] = value_tower<OD>(prm, last_obs + (r - TN)*OD);
+    }
+}
+
+template <int OD>
+__global__ __launch_bounds__(64) void so100_learn_gae(const float* chunk, int T, int N, bool bootstrap, float gamma, float lam, float* adv, float* ret) {
+    constexpr int ROW = OD + ROW_EXTRA;
+    const int n = blockIdx.x*64 + threadIdx.x;
+    if (n >= N) return;
+    const float* c = chunk + (size_t)n*ROW + OD;
+    const float next_v_last = adv[(size_t)(T - 1)*N + n];
+    gae_scan_env<float>(T, c + ROW_REWARD, c + ROW_DONE, c + ROW_VALUE, (long)N*ROW, bootstrap ? ret + n : nullptr, next_v_last, gamma, lam, adv + n, ret + n, (long)N);
+}
+
+__device__ __forceinline__ float block_sum_1024(float v, float* sh) {      // fixed tree: the same order every run
+    sh[threadIdx.x] = v;
+    __syncthreads();
+    for (int w = ADV_THREADS/2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w];
+        __syncthreads();
+    }
+    const float r = sh[0];
+    __syncthreads();
+    return r;
+}
+
+// mean and unbiased standard deviation of adv (torch: a.mean(), a.std()), two passes, one workgroup
+__global__ __launch_bounds__(ADV_THREADS) void so100_learn_adv_stats(const float* __restrict__ adv, long n, float* __restrict__ stats) {
+    __shared__ float sh[ADV_THREADS];
+    float s = 0.0f;
+    for (long i = threadIdx.x; i < n; i += ADV_THREADS) s += adv[i];
+    const float mean = block_sum_1024(s, sh)/(float)n;
+    float q = 0.0f;
+    for (long i = threadIdx.x; i < n; i += ADV_THREADS) { const float d = adv[i] - mean; q = fmaf(d, d, q); }
+    const float ss = block_sum_1024(q, sh);
+    if (threadIdx.x == 0) { stats[0] = mean; stats[1] = lsqrt(ss/(float)(n - 1)); }       // n = 1: 0/0 = NaN, as torch
+}
+
+const char* const kTensorNames[NUM_TENSORS] = { "pi_w0", "pi_b0", "pi_w1", "pi_b1", "mu_w", "mu_b", "log_std", "vf_w0", "vf_b0", "vf_w1", "vf_b1", "v_w", "v_b" };
+
+int tensor_index(const char* name) {
+    if (!name) return -1;
+    for (int t = 0; t < NUM_TENSORS; t++) if (strcmp(kTensorNames[t], name) == 0) return t;
+    return -1;
+}
+
+int fail(int code, const char* fmt, long a = 0) {
+    char msg[512];
+    snprintf(msg, sizeof msg, fmt, a);
+    return set_last_error(code, msg);
+}
+
+struct DeviceScope {
+    int prev = -1, target = -1; bool ok = true;
+    explicit DeviceScope(int dev) : target(dev) {
+        if (hipGetDevice(&prev) != hipSuccess) { ok = false; return; }
+        if (prev != dev && hipSetDevice(dev) != hipSuccess) ok = false;
+    }
+    ~DeviceScope() { if (ok && prev != target) (void)hipSetDevice(prev); }
+};
+
+}  // namespace learn
+}  // namespace so100
+
+using namespace so100;
+using namespace so100::learn;
+
+struct so100_learner {
+    so100_learner_config cfg;
+    int P = 0, grid_max = 0, nblk = 0;
+    float* partial = nullptr;      // [grid_max][P + NSTAT] per-workgroup partial gradients
+    float* gsum = nullptr;         // [P + NSTAT] their ordered sum
+    float* sq_block = nullptr;     // [nblk] sum of squares per block of the reduction
+};
+
+#define LEARN_HIP_TRY(expr, what) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { char m_[256]; \
+    snprintf(m_, sizeof m_, "%s: %s (HIP error %ld)", what, hipGetErrorString(e_), (long)e_); return set_last_error(SO100_E_LAUNCH, m_); } } while (0)
+
+extern "C" {
+
+int so100_learner_num_params(int32_t obs_dim) { return obs_dim == 15 ? num_params(15) : obs_dim == 8 ? num_params(8) : SO100_E_INVALID; }
+
+int so100_learner_param_offset(int32_t obs_dim, const char* name) {
+    const int t = tensor_index(name);
+    if (t < 0 || (obs_dim != 15 && obs_dim != 8)) return SO100_E_INVALID;
+    return tensor_offset(t, obs_dim);
+}
+
+int so100_learner_param_size(int32_t obs_dim, const char* name) {
+    const int t = tensor_index(name);
+    if (t < 0 || (obs_dim != 15 && obs_dim != 8)) return SO100_E_INVALID;
+    return tensor_size(t, obs_dim);
+}
+
+int so100_learner_create(const so100_learner_config* cfg, so100_learner** out) {
+    if (!cfg || !out) return fail(SO100_E_INVALID, "so100_learner_create: null argument");
+    *out = nullptr;
+    if (cfg->obs_dim != 15 && cfg->obs_dim != 8) return fail(SO100_E_INVALID, "so100_learner_create: obs_dim must be 15 or 8, got %ld", cfg->obs_dim);
+    if (cfg->max_minibatch < 1) return fail(SO100_E_INVALID, "so100_learner_create: max_minibatch must be >= 1, got %ld", cfg->max_minibatch);
+    if (!(cfg->gamma >= 0.0f && cfg->gamma <= 1.0f)) return fail(SO100_E_INVALID, "so100_learner_create: gamma must be in [0, 1]");
+    if (!(cfg->gae_lambda >= 0.0f && cfg->gae_lambda <= 1.0f)) return fail(SO100_E_INVALID, "so100_learner_create: gae_lambda must be in [0, 1]");
+    if (!(cfg->clip_range > 0.0f)) return fail(SO100_E_INVALID, "so100_learner_create: clip_range must be > 0");
+    if (!(cfg->vf_coef >= 0.0f)) return fail(SO100_E_INVALID, "so100_learner_create: vf_coef must be >= 0");
+    if (!(cfg->max_grad_norm > 0.0f)) return fail(SO100_E_INVALID, "so100_learner_create: max_grad_norm must be > 0");
+    if (!(cfg->lr >= 0.0)) return fail(SO100_E_INVALID, "so100_learner_create: lr must be >= 0");
+    if (!(cfg->beta1 >= 0.0 && cfg->beta1 < 1.0) || !(cfg->beta2 >= 0.0 && cfg->beta2 < 1.0))
+        return fail(SO100_E_INVALID, "so100_learner_create: beta1 and beta2 must be in [0, 1)");
+    if (!(cfg->adam_eps > 0.0)) return fail(SO100_E_INVALID, "so100_learner_create: adam_eps must be > 0");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
+        return fail(SO100_E_NODEVICE, "so100_learner_create: no HIP device available (this library has no CPU fallback)");
+    if (cfg->device < 0 || cfg->device >= ndev) return fail(SO100_E_INVALID, "so100_learner_create: device ordinal out of range");
+    DeviceScope g(cfg->device);
+    if (!g.ok) return fail(SO100_E_NODEVICE, "so100_learner_create: cannot select the device");
+    so100_learner* L = new (std::nothrow) so100_learner();
+    if (!L) return fail(SO100_E_NOMEM, "so100_learner_create: out of host memory");
+    L->cfg = *cfg;
+    L->P = num_params(cfg->obs_dim == 15 ? 15 : 8);
+    const long tiles = ((long)cfg->max_minibatch + LT - 1)/LT;
+    L->grid_max = (int)(tiles < GRID_MAX ? tiles : GRID_MAX);
+    L->nblk = (L->P + NSTAT + 255)/256;
+    const size_t ps = (size_t)(L->P + NSTAT);
+    if (hipMalloc(&L->partial, (size_t)L->grid_max*ps*sizeof(float)) != hipSuccess || hipMalloc(&L->gsum, ps*sizeof(float)) != hipSuccess ||
+        hipMalloc(&L->sq_block, (size_t)L->nblk*sizeof(float)) != hipSuccess) {
+        so100_learner_destroy(L);
+        return fail(SO100_E_NOMEM, "so100_learner_create: hipMalloc of the partial-gradient scratch failed");
+    }
+    *out = L;
+    return 0;
+}
+
+void so100_learner_destroy(so100_learner* L) {
+    if (!L) return;
+    DeviceScope g(L->cfg.device);
+    if (L->partial) (void)hipFree(L->partial);
+    if (L->gsum) (void)hipFree(L->gsum);
+    if (L->sq_block) (void)hipFree(L->sq_block);
+    delete L;
+}
+
+int so100_learner_advantages(so100_learner* L, const so100_advantages_io* io, int32_t T, int32_t N, void* stream) {
+    if (!L || !io) return fail(SO100_E_INVALID, "so100_learner_advantages: null argument");
+    if (T < 1) return fail(SO100_E_INVALID, "so100_learner_advantages: T must be >= 1, got %ld", T);
+    if (N < 1) return fail(SO100_E_INVALID, "so100_learner_advantages: N must be >= 1, got %ld", N);
+    if (!io->rollout_dev || !io->last_obs_dev || !io->params_dev || !io->adv_dev || !io->ret_dev || !io->adv_stats_dev)
+        return fail(SO100_E_INVALID, "so100_learner_advantages: rollout/last_obs/params/adv/ret/adv_stats pointers are required");
+    DeviceScope g(L->cfg.device);
+    if (!g.ok) return fail(SO100_E_NODEVICE, "so100_learner_advantages: cannot select the device");
+    const long TN = (long)T*(long)N;
+    const long vblocks = (TN + N + 255)/256;
+    if (vblocks > 0x7fffffffL) return fail(SO100_E_INVALID, "so100_learner_advantages: T*N is too large");
+    const hipStream_t st = (hipStream_t)stream;
+    const bool boot = io->terminal_obs_chunk_dev != nullptr;
+    if (L->cfg.obs_dim == 15) {
+        hipLaunchKernelGGL((so100_learn_values<15>), dim3((unsigned)vblocks), dim3(256), 0, st, io->rollout_dev, io->terminal_obs_chunk_dev, io->last_obs_dev, io->params_dev, TN, N, io->adv_dev, io->ret_dev);
+        hipLaunchKernelGGL((so100_learn_gae<15>), dim3((unsigned)((N + 63)/64)), dim3(64), 0, st, io->rollout_dev, T, N, boot, L->cfg.gamma, L->cfg.gae_lambda, io->adv_dev, io->ret_dev);
+    } else {
+        hipLaunchKernelGGL((so100_learn_values<8>), dim3((unsigned)vblocks), dim3(256), 0, st, io->rollout_dev, io->terminal_obs_chunk_dev, io->last_obs_dev, io->params_dev, TN, N, io->adv_dev, io->ret_dev);
+        hipLaunchKernelGGL((so100_learn_gae<8>), dim3((unsigned)((N + 63)/64)), dim3(64), 0, st, io->rollout_dev, T, N, boot, L->cfg.gamma, L->cfg.gae_lambda, io->adv_dev, io->ret_dev);
+    }
+    hipLaunchKernelGGL(so100_learn_adv_stats, dim3(1), dim3(ADV_THREADS), 0, st, (const float*)io->adv_dev, TN, io->adv_stats_dev);
+    LEARN_HIP_TRY(hipGetLastError(), "so100_learner_advantages");
+    return 0;
+}
+
+int so100_learner_minibatch_step(so100_learner* L, const so100_minibatch_io* io, void* stream) {
+    if (!L || !io) return fail(SO100_E_INVALID, "so100_learner_minibatch_step: null argument");
+    if (io->mb < 1 || io->mb > L->cfg.max_minibatch) return fail(SO100_E_INVALID, "so100_learner_minibatch_step: mb must be in 1..max_minibatch, got %ld", io->mb);
+    if (io->num_samples < 1) return fail(SO100_E_INVALID, "so100_learner_minibatch_step: num_samples must be >= 1, got %ld", (long)io->num_samples);
+    if (io->adam_step < 1) return fail(SO100_E_INVALID, "so100_learner_minibatch_step: adam_step is 1-based, got %ld", io->adam_step);
+    if (!io->rollout_dev || !io->adv_dev || !io->ret_dev || !io->adv_stats_dev || !io->params_dev || !io->adam_m_dev || !io->adam_v_dev || !io->stats_dev)
+        return fail(SO100_E_INVALID, "so100_learner_minibatch_step: rollout/adv/ret/adv_stats/params/adam_m/adam_v/stats pointers are required");
+    DeviceScope g(L->cfg.device);
+    if (!g.ok) return fail(SO100_E_NODEVICE, "so100_learner_minibatch_step: cannot select the device");
+    const hipStream_t st = (hipStream_t)stream;
+    const int tiles = (io->mb + LT - 1)/LT, G = tiles < L->grid_max ? tiles : L->grid_max;
+    GradArgs A;
+    A.chunk = io->rollout_dev; A.num_samples = (long)io->num_samples; A.idx = io->idx_dev; A.mb = io->mb;
+    A.adv = io->adv_dev; A.ret = io->ret_dev; A.adv_stats = io->adv_stats_dev; A.params = io->params_dev; A.partial = L->partial;
+    A.clip = L->cfg.clip_range; A.vf_coef = L->cfg.vf_coef;
+    if (L->cfg.obs_dim == 15) hipLaunchKernelGGL((so100_learn_grad<15>), dim3((unsigned)G), dim3(256), 0, st, A);
+    else hipLaunchKernelGGL((so100_learn_grad<8>), dim3((unsigned)G), dim3(256), 0, st, A);
+    hipLaunchKernelGGL(so100_learn_reduce, dim3((unsigned)L->nblk), dim3(256), 0, st, (const float*)L->partial, G, L->P, L->gsum, L->sq_block);
+    AdamArgs a;
+    a.max_grad_norm = L->cfg.max_grad_norm;
+    a.step_size = (float)(L->cfg.lr/(1.0 - pow(L->cfg.beta1, (double)io->adam_step))); a.bc2_sqrt = (float)sqrt(1.0 - pow(L->cfg.beta2, (double)io->adam_step));
+    a.omb1 = (float)(1.0 - L->cfg.beta1); a.beta2 = (float)L->cfg.beta2; a.omb2 = (float)(1.0 - L->cfg.beta2); a.eps = (float)L->cfg.adam_eps;
+    a.inv_mb = 1.0f/(float)io->mb;
+    hipLaunchKernelGGL(so100_learn_adam, dim3((unsigned)((L->P + 255)/256)), dim3(256), 0, st, (const float*)L->gsum, (const float*)L->sq_block, L->nblk, L->P,
+                       io->params_dev, io->adam_m_dev, io->adam_v_dev, io->grads_dev, io->stats_dev, a);
+    LEARN_HIP_TRY(hipGetLastError(), "so100_learner_minibatch_step");
+    return 0;
+}
+
+}  // extern "C"

@@ -1,0 +1,129 @@
+// so100_learn.hpp -- the per-sample / per-parameter arithmetic of the on-device PPO learner (include/so100_learn.h), as templates on the
+// scalar type: the HIP kernels of so100_learn.hip instantiate them in float, tests/_learncheck instantiates them on the host in double and
+// float and holds them to an fp64 PyTorch reference.  Nothing here touches memory layouts beyond a stride, a device builtin or a header
+// of the simulator: the file compiles with a plain host compiler.
+//   gae_scan_env        rollout.bootstrap_truncated + PPO._gae for one env (SB3 RolloutBuffer.compute_returns_and_advantage)
+//   ppo_loss_head       the PPO._step loss of one sample with its derivatives towards the network outputs
+//   clip_adam_update    clip_grad_norm_'s scaling + one torch.optim.Adam step of one parameter
+#pragma once
+
+#ifndef SO100_LHD
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define SO100_LHD __host__ __device__ __forceinline__
+#else
+#define SO100_LHD inline
+#endif
+#endif
+
+namespace so100 {
+namespace learn {
+
+constexpr int ACT_DIM = 6, HID = 64;
+constexpr int NUM_TENSORS = 13;
+// the flat parameter block: the 13 tensors in the order of so100_policy_weights, each in nn.Linear layout weight[out][in]
+constexpr int tensor_rows(int t, int /*od*/) { return (t == 4 || t == 5 || t == 6) ? ACT_DIM : (t == 11 || t == 12) ? 1 : HID; }
+constexpr int tensor_cols(int t, int od) { return (t == 0 || t == 7) ? od : (t == 2 || t == 9 || t == 4 || t == 11) ? HID : 1; }
+constexpr int tensor_size(int t, int od) { return tensor_rows(t, od)*tensor_cols(t, od); }
+constexpr int tensor_offset(int t, int od) { return t == 0 ? 0 : tensor_offset(t - 1, od) + tensor_size(t - 1, od); }
+constexpr int num_params(int od) { return tensor_offset(NUM_TENSORS - 1, od) + tensor_size(NUM_TENSORS - 1, od); }
+enum { T_PI_W0, T_PI_B0, T_PI_W1, T_PI_B1, T_MU_W, T_MU_B, T_LOG_STD, T_VF_W0, T_VF_B0, T_VF_W1, T_VF_B1, T_V_W, T_V_B };
+static_assert(num_params(15) == 10829 && num_params(8) == 9933, "SB3 MlpPolicy, 2 x 64 towers");
+
+SO100_LHD float  lexp(float x)   { return __builtin_expf(x); }
+SO100_LHD double lexp(double x)  { return __builtin_exp(x); }
+SO100_LHD float  lsqrt(float x)  { return __builtin_sqrtf(x); }
+SO100_LHD double lsqrt(double x) { return __builtin_sqrt(x); }
+
+// ---- advantages ---------------------------------------------------------------------------------------------------------------------------
+// One env, backwards over its T steps.  reward / code / value: the env's columns of the packed chunk, `in_stride` scalars between steps.
+// boot: gamma-less V(terminal_observation) of the steps whose done code is 2, `out_stride` between steps, or null (no bootstrap); it may
+// alias `ret` (entry t is read before ret[t] is written).  next_v_last = V(last_obs).  Returns nothing; adv / ret get T entries each.
+template <class S>
+SO100_LHD void gae_scan_env(int T, const S* reward, const S* code, const S* value, long in_stride, const S* boot, S next_v_last,
+                            S gamma, S lam, S* adv, S* ret, long out_stride) {
+    S g = S(0), next_v = next_v_last;
+    for (int t = T - 1; t >= 0; t--) {
+        const S c = code[t*in_stride], v = value[t*in_stride];
+        S r = reward[t*in_stride];
+        if (boot != nullptr && c == S(2)) r += gamma*boot[t*out_stride];          // TimeLimit truncation only: not a terminal state
+        const S nonterm = c == S(0) ? S(1) : S(0);
+        const S delta = r + gamma*next_v*nonterm - v;
+        g = delta + gamma*lam*nonterm*g;
+        adv[t*out_stride] = g;
+        ret[t*out_stride] = g + v;
+        next_v = v;
+    }
+}
+
+// ---- loss head ----------------------------------------------------------------------------------------------------------------------------
+template <class S>
+struct LossHead {
+    S pg_loss, v_loss;             // this sample's -min(ratio A, clamp(ratio) A) and (ret - V)^2: the means over the minibatch are the stats
+    S clipped;                     // 1 where |ratio - 1| > clip_range (SB3's clip_fraction), else 0
+    S dmu[ACT_DIM], dlog_std[ACT_DIM], dV;     // d(minibatch loss)/d(this sample's outputs): already scaled by inv_mb (and vf_coef)
+};
+
+// The two towers meet only in the sum of the loss, so the head has a policy half and a value half; the kernels run one tower at a time and
+// call the halves, ppo_loss_head is both.  adv_n = (adv - mean)/(std + 1e-8), formed by the caller.  torch's derivative conventions:
+// min() splits a tie evenly, clamp() passes the gradient on its closed interval.
+template <class S>
+SO100_LHD void policy_loss_head(const S* mu, const S* log_std, const S* a, S logp_old, S adv_n, S clip, S inv_mb, LossHead<S>& o) {
+    S z[ACT_DIM], inv_sigma[ACT_DIM], logp = S(0);
+    for (int i = 0; i < ACT_DIM; i++) {
+        inv_sigma[i] = lexp(-log_std[i]);
+        z[i] = (a[i] - mu[i])*inv_sigma[i];
+        logp += S(-0.5)*z[i]*z[i] - log_std[i] - S(0.9189385332046727);
+    }
+    const S ratio = lexp(logp - logp_old);
+    const S lo = S(1) - clip, hi = S(1) + clip;
+    const bool inside = ratio >= lo && ratio <= hi;
+    const S s1 = ratio*adv_n, s2 = (ratio < lo ? lo : ratio > hi ? hi : ratio)*adv_n;
+    o.pg_loss = -(s1 < s2 ? s1 : s2);
+    o.clipped = (ratio - S(1) > clip || S(1) - ratio > clip) ? S(1) : S(0);
+    const S w1 = s1 < s2 ? S(1) : s1 == s2 ? S(0.5) : S(0);
+    const S dratio = -(w1*adv_n + (inside ? (S(1) - w1)*adv_n : S(0)));
+    const S dlogp = dratio*ratio*inv_mb;
+    for (int i = 0; i < ACT_DIM; i++) {
+        o.dmu[i] = dlogp*z[i]*inv_sigma[i];
+        o.dlog_std[i] = dlogp*(z[i]*z[i] - S(1));
+    }
+}
+
+template <class S>
+SO100_LHD void value_loss_head(S V, S ret, S vf_coef, S inv_mb, LossHead<S>& o) {
+    const S e = V - ret;
+    o.v_loss = e*e;
+    o.dV = S(2)*vf_coef*e*inv_mb;
+}
+
+template <class S>
+SO100_LHD LossHead<S> ppo_loss_head(const S* mu, const S* log_std, const S* a, S logp_old, S adv_n, S V, S ret, S clip, S vf_coef, S inv_mb) {
+    LossHead<S> o;
+    policy_loss_head(mu, log_std, a, logp_old, adv_n, clip, inv_mb, o);
+    value_loss_head(V, ret, vf_coef, inv_mb, o);
+    return o;
+}
+
+// ---- optimiser ----------------------------------------------------------------------------------------------------------------------------
+// clip_grad_norm_: every gradient is multiplied by min(1, max_norm/(norm + 1e-6)), norm = the L2 norm over all parameters
+template <class S>
+SO100_LHD S clip_coefficient(S grad_norm, S max_grad_norm) {
+    const S c = max_grad_norm/(grad_norm + S(1e-6));
+    return c < S(1) ? c : S(1);
+}
+
+// torch.optim.Adam (no weight decay, no amsgrad) with its scalars as torch forms them, in double on the host, before they meet the
+// tensor's type: omb1 = 1 - beta1, omb2 = 1 - beta2 (0.999f is 1.3e-5 away from a (1 - beta2) of 0.001), step_size = lr/(1 - beta1^step),
+// bc2_sqrt = sqrt(1 - beta2^step), step 1-based.  g is the reduced, not yet clipped gradient; returns the clipped one (what Adam consumed).
+template <class S>
+SO100_LHD S clip_adam_update(S g, S clip_coef, S& p, S& m, S& v, S step_size, S omb1, S beta2, S omb2, S eps, S bc2_sqrt) {
+    g *= clip_coef;
+    m = m + (g - m)*omb1;
+    v = v*beta2 + omb2*g*g;
+    const S denom = lsqrt(v)/bc2_sqrt + eps;
+    p = p - step_size*(m/denom);
+    return g;
+}
+
+}  // namespace learn
+}  // namespace so100

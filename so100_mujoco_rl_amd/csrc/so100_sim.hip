@@ -31,6 +31,11 @@ const char* const kFieldNames[] = {
 
 }  // namespace
 
+namespace so100 {
+// the message behind so100_last_error() for the library's other translation units (so100_learn.hip); returns `code`
+int set_last_error(int code, const char* msg) { return fail(code, "%s", msg); }
+}
+
 struct so100_sim {
     so100_config cfg;
     SimParams prm;

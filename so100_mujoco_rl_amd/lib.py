@@ -84,6 +84,28 @@ EXPORTS = ["so100_abi_version", "so100_obs_dim", "so100_num_state_fields", "so10
            "so100_set_field", "so100_last_error", "so100_policy_forward", "so100_rollout", "so100_render"]
 
 
+# ---- include/so100_learn.h: the on-device PPO learner (additive: EXPORTS above is the list of so100_sim.h alone) -----------------------
+class LearnerConfig(C.Structure):
+    _fields_ = [("obs_dim", C.c_int32), ("device", C.c_int32), ("max_minibatch", C.c_int32), ("gamma", C.c_float), ("gae_lambda", C.c_float),
+                ("clip_range", C.c_float), ("vf_coef", C.c_float), ("max_grad_norm", C.c_float), ("lr", C.c_double), ("beta1", C.c_double),
+                ("beta2", C.c_double), ("adam_eps", C.c_double)]
+
+
+class AdvantagesIO(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("rollout_dev", "terminal_obs_chunk_dev", "last_obs_dev", "params_dev", "adv_dev", "ret_dev", "adv_stats_dev")]
+
+
+class MinibatchIO(C.Structure):
+    _fields_ = [("rollout_dev", C.c_void_p), ("num_samples", C.c_int64), ("idx_dev", C.c_void_p), ("mb", C.c_int32), ("adam_step", C.c_int32),
+                ("adv_dev", C.c_void_p), ("ret_dev", C.c_void_p), ("adv_stats_dev", C.c_void_p), ("params_dev", C.c_void_p), ("adam_m_dev", C.c_void_p),
+                ("adam_v_dev", C.c_void_p), ("stats_dev", C.c_void_p), ("grads_dev", C.c_void_p)]
+
+
+LEARN_EXPORTS = ["so100_learner_num_params", "so100_learner_param_offset", "so100_learner_param_size", "so100_learner_create", "so100_learner_destroy",
+                 "so100_learner_advantages", "so100_learner_minibatch_step"]
+LEARNER_STATS = ["policy_loss", "value_loss", "clip_fraction", "grad_norm"]          # stats_dev[4] of so100_learner_minibatch_step
+
+
 def build(verbose=False):
     """Compile libso100sim.so for gfx950 (hipcc cross-compiles without a GPU)."""
     out = subprocess.run(["make", "-j7", "-C", os.path.join(_HERE, "csrc")], capture_output=True, text=True)
@@ -121,6 +143,14 @@ def load():
         L.so100_get_field.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
         L.so100_set_field.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
         L.so100_render.argtypes = [C.c_void_p, C.POINTER(RenderIO), C.c_void_p]
+        L.so100_learner_num_params.argtypes = [C.c_int32]
+        L.so100_learner_param_offset.argtypes = [C.c_int32, C.c_char_p]
+        L.so100_learner_param_size.argtypes = [C.c_int32, C.c_char_p]
+        L.so100_learner_create.argtypes = [C.POINTER(LearnerConfig), C.POINTER(C.c_void_p)]
+        L.so100_learner_destroy.argtypes = [C.c_void_p]
+        L.so100_learner_destroy.restype = None
+        L.so100_learner_advantages.argtypes = [C.c_void_p, C.POINTER(AdvantagesIO), C.c_int32, C.c_int32, C.c_void_p]
+        L.so100_learner_minibatch_step.argtypes = [C.c_void_p, C.POINTER(MinibatchIO), C.c_void_p]
         if L.so100_abi_version() != ABI_VERSION:
             raise So100Error("libso100sim.so ABI version mismatch")
         _lib = L
@@ -422,3 +452,71 @@ class So100Sim:
         assert value.element_size() == 4
         _check(self.L.so100_set_field(self.h, self.field_index(name), _ptr(value, value.dtype, (self.n,), self.device),
                                       self._stream()), "so100_set_field")
+
+
+def learner_layout(obs_dim):
+    """{name: (offset, shape)} of the flat parameter block of include/so100_learn.h (names: POLICY_TENSORS, PyTorch nn.Linear shapes) and
+    its length.  Metadata only: answers without a GPU."""
+    L = load()
+    n = L.so100_learner_num_params(obs_dim)
+    if n < 0:
+        raise So100Error(f"the learner's network takes obs_dim 15 or 8, got {obs_dim}")
+    shapes = {"pi_w0": (64, obs_dim), "pi_b0": (64,), "pi_w1": (64, 64), "pi_b1": (64,), "mu_w": (6, 64), "mu_b": (6,), "log_std": (6,),
+              "vf_w0": (64, obs_dim), "vf_b0": (64,), "vf_w1": (64, 64), "vf_b1": (64,), "v_w": (1, 64), "v_b": (1,)}
+    return {k: (L.so100_learner_param_offset(obs_dim, k.encode()), shapes[k]) for k in POLICY_TENSORS}, n
+
+
+class So100Learner:
+    """One handle of the on-device PPO learner (include/so100_learn.h): advantages and minibatch steps as raw launches on torch's CURRENT
+    stream -- the stream So100Sim's launches go to, so a rollout that follows an update is ordered behind it.  The caller owns every
+    tensor (parameters, Adam moments, buffers); the handle owns its partial-gradient scratch."""
+
+    def __init__(self, obs_dim, device=None, max_minibatch=32768, gamma=0.99, gae_lambda=0.95, clip_range=0.2, vf_coef=0.5, max_grad_norm=0.5,
+                 lr=3e-4, beta1=0.9, beta2=0.999, adam_eps=1e-5):
+        self.L = load()
+        if not torch.cuda.is_available():
+            raise So100Error("no HIP device visible to PyTorch: the so100 learner has no CPU fallback")
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if self.device.type != "cuda":
+            raise So100Error(f"the so100 learner runs on a HIP device, not on {self.device}")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.cfg = LearnerConfig(obs_dim, self.device.index, max_minibatch, gamma, gae_lambda, clip_range, vf_coef, max_grad_norm, lr, beta1, beta2, adam_eps)
+        h = C.c_void_p()
+        _check(self.L.so100_learner_create(C.byref(self.cfg), C.byref(h)), "so100_learner_create")
+        self.h = h
+        self.obs_dim = obs_dim
+        self.num_params = self.L.so100_learner_num_params(obs_dim)
+
+    def _stream(self):
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.so100_learner_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def advantages(self, rollout, last_obs, params, adv, ret, adv_stats, terminal_obs=None):
+        """rollout: float32 [T, N, obs_dim+10] packed chunk (read only); terminal_obs: [T, N, obs_dim] or None (no TimeLimit bootstrap);
+        writes adv [T, N], ret [T, N], adv_stats [2] (mean, unbiased std)."""
+        T, N = rollout.shape[0], rollout.shape[1]
+        f, d, o = torch.float32, self.device, self.obs_dim
+        io = AdvantagesIO(_ptr(rollout, f, (T, N, o + 10), d), _ptr(terminal_obs, f, (T, N, o), d), _ptr(last_obs, f, (N, o), d),
+                          _ptr(params, f, (self.num_params,), d), _ptr(adv, f, (T, N), d), _ptr(ret, f, (T, N), d), _ptr(adv_stats, f, (2,), d))
+        _check(self.L.so100_learner_advantages(self.h, C.byref(io), T, N, self._stream()), "so100_learner_advantages")
+
+    def minibatch_step(self, rollout, idx, adv, ret, adv_stats, params, adam_m, adam_v, adam_step, stats, grads=None):
+        """One PPO gradient step on the rows idx of the packed chunk: an int64 [mb] tensor of flat indices t*N + n in any order, or an int mb
+        for rows 0..mb-1.  params / adam_m / adam_v are updated in place; stats [4] (LEARNER_STATS) and optionally grads [P] are written."""
+        T, N = rollout.shape[0], rollout.shape[1]
+        f, d, o, P = torch.float32, self.device, self.obs_dim, self.num_params
+        if isinstance(idx, int):
+            mb, ip = idx, None
+        else:
+            mb = idx.numel(); ip = _ptr(idx, torch.int64, (mb,), d)
+        io = MinibatchIO(_ptr(rollout, f, (T, N, o + 10), d), T * N, ip, mb, adam_step, _ptr(adv, f, (T, N), d), _ptr(ret, f, (T, N), d),
+                         _ptr(adv_stats, f, (2,), d), _ptr(params, f, (P,), d), _ptr(adam_m, f, (P,), d), _ptr(adam_v, f, (P,), d),
+                         _ptr(stats, f, (4,), d), _ptr(grads, f, (P,), d))
+        _check(self.L.so100_learner_minibatch_step(self.h, C.byref(io), self._stream()), "so100_learner_minibatch_step")

@@ -1,6 +1,6 @@
 """Experiment driver with the reference's CLI surface (ref: /root/reference/src/so100_mujoco_rl/main.py:241-284):
 
-    python -m so100_mujoco_rl_amd.main -a PPO [-m MODEL] train  -e Env01-v1 [--envs 4096] [--iters N]
+    python -m so100_mujoco_rl_amd.main -a PPO [-m MODEL] train  -e Env01-v1 [--envs 4096] [--iters N] [--learner torch|fused]
     python -m so100_mujoco_rl_amd.main -a PPO [-m MODEL] test   -e Env01-v1 [--show-io] [--show-i]
     python -m so100_mujoco_rl_amd.main -a PPO [-m MODEL] record -e Env01-v1 [--steps 3000] [--video/--no-video]
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 -m so100_mujoco_rl_amd.main -a PPO train -e Env01-v1     # 8 x 4096 envs
@@ -27,7 +27,7 @@ from .callbacks import EvalCallback, StopTrainingOnNoModelImprovement, StopTrain
 from .collector import RolloutCollector
 from .ddpg import DDPG, DDPGPolicy
 from .lib import F_REFERENCE
-from .ppo import PPO, ActorCritic
+from .ppo import PPO, ActorCritic, FusedPPO
 from .rollout import broadcast_policy
 from .vec_env import So100VecEnv, kind_from_id
 
@@ -77,8 +77,10 @@ def cli(ctx, algorithm, model):
 @click.option("--envs", default=4096, type=int, help="envs stepped in parallel on the GPU")
 @click.option("--iters", default=0, type=int, help="PPO updates (0 = until the reward threshold / no improvement)")
 @click.option("--seed", default=0, type=int)
+@click.option("--learner", "learner_kind", default="torch", type=click.Choice(["torch", "fused"]),
+              help="built-in PPO update: PyTorch autograd (torch) or the library's HIP kernels (fused; include/so100_learn.h)")
 @click.pass_context
-def train(ctx, environment, envs, iters, seed):
+def train(ctx, environment, envs, iters, seed, learner_kind):
     algorithm = ctx.obj["ALGORITHM_NAME"]
     kind = kind_from_id(environment)
     # Multi-GPU (one process per GPU under torchrun): rank r steps global envs [r*envs, (r+1)*envs); once per rollout chunk the
@@ -99,6 +101,8 @@ def train(ctx, environment, envs, iters, seed):
     os.makedirs(save_dir, exist_ok=True)
     if lead:
         logger.info("Starting training process"); logger.info(f"Algorithm: {algorithm}"); logger.info(f"Environment: {environment} x {envs}" + (f" x {world} GPUs" if distributed else ""))
+    if learner_kind == "fused" and (_have_sb3() or algorithm != "PPO"):
+        raise RuntimeError("--learner fused selects the built-in PPO learner's kernels; it does not apply to " + ("stable-baselines3" if _have_sb3() else algorithm))
     if _have_sb3():                                          # unchanged SB3 learner over the batched VecEnv (ref: main.py:199-238)
         import stable_baselines3
         from stable_baselines3.common.callbacks import CheckpointCallback
@@ -113,7 +117,7 @@ def train(ctx, environment, envs, iters, seed):
         if distributed:
             raise RuntimeError("multi-GPU training uses the built-in PPO learner; DDPG runs on one GPU")
         return _train_ddpg(env, environment, ctx.obj["MODEL_PATH"], save_dir, iters, seed, kind)
-    learner = PPO(env.sim.obs_dim, env.device, seed=seed)
+    learner = make_ppo_learner(learner_kind, env.sim.obs_dim, env.device, seed)
     if ctx.obj["MODEL_PATH"]:
         if not os.path.isfile(ctx.obj["MODEL_PATH"]):
             raise RuntimeError(f"Model file {ctx.obj['MODEL_PATH']} does not exist")
@@ -123,7 +127,9 @@ def train(ctx, environment, envs, iters, seed):
         logger.info("Model: starting with new model")
     if distributed:
         broadcast_policy(list(learner.net.state_dict().values()), src=0)          # every rank starts from rank 0's weights
-    col = RolloutCollector(env, learner.net.state_dict(), T=64)
+    # fused on one GPU: the advantage kernel applies the TimeLimit bootstrap (the chunk keeps the env's rewards); a gathered chunk is bootstrapped
+    # by each rank before the gather, as with the torch learner
+    col = RolloutCollector(env, learner.net.state_dict(), T=64, defer_bootstrap=learner_kind == "fused" and not distributed)
     threshold = K.REWARD_THRESHOLD[kind]                     # StopTrainingOnRewardThreshold (ref: main.py:211; the registered threshold of the env id)
     steps, t0, it = 0, time.time(), 0
     ep_sum = ep_cnt = 0.0
@@ -172,6 +178,19 @@ def train(ctx, environment, envs, iters, seed):
         logger.info(f"done: {steps/1e6:.1f} M timesteps in {time.time()-t0:.1f} s; best evaluation reward {eval_cb.best_mean_reward:.1f} ({eval_cb.n_evals} evaluations); models in {save_dir}")
     if distributed:
         dist.barrier(); dist.destroy_process_group()
+
+
+def make_ppo_learner(kind, obs_dim, device, seed):
+    """the built-in PPO learner `train --learner` names: "torch" (ppo.PPO, the default) or "fused" (ppo.FusedPPO, HIP kernels)"""
+    if kind == "torch":
+        return PPO(obs_dim, device, seed=seed)
+    if kind != "fused":
+        raise RuntimeError(f"unknown learner {kind!r}: torch or fused")
+    if torch.device(device).type != "cuda":
+        raise RuntimeError(f"--learner fused runs on a HIP device, not on {device}: there is no CPU fallback (use --learner torch)")
+    if obs_dim not in (15, 8):
+        raise RuntimeError(f"--learner fused is built for the so100 observations (obs_dim 15 or 8), not obs_dim {obs_dim}")
+    return FusedPPO(obs_dim, device, seed=seed)
 
 
 def _train_ddpg(env, environment, model_path, save_dir, iters, seed, kind):

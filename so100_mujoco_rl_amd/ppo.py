@@ -7,7 +7,8 @@ TimeLimit truncations are bootstrapped by the collector exactly as SB3 does (rew
 `dones` below ends the GAE recursion with the right target for both terminations and truncations.  (Round 1's
 hipGraph-replayed update is gone: see PPO.__init__.)
 The network's state_dict keys equal SB3's ActorCriticPolicy keys, so checkpoints and RolloutCollector.load_policy()
-interoperate with an SB3 policy."""
+interoperate with an SB3 policy.
+FusedPPO is the same learner on the library's own kernels (include/so100_learn.h): same constructor, same update(b), same state_dict."""
 import os
 
 import torch
@@ -114,3 +115,88 @@ class PPO:
         raw = b.get("raw_reward_mean")
         return {"value_loss": S["vl"].item(), "mean_reward": (raw if raw is not None else S["rewards"].mean()).item(),
                 "mean_bootstrapped_reward": S["rewards"].mean().item()}
+
+
+class FusedPPO:
+    """PPO with the advantages and the whole minibatch step (forward, backward, gradient-norm clip, Adam) in the library's HIP kernels
+    (include/so100_learn.h; DESIGN.md "On-device learner"): 3 launches per update + 3 per minibatch instead of ~100 per minibatch.
+    Constructor arguments and update(b) are PPO's.  `.net` is an ActorCritic whose 13 parameters are VIEWS of one flat float32 block
+    (`.params`, the layout of so100_learner_param_offset), so state_dict(), checkpoints, RolloutCollector.load_policy and export.py see an
+    ordinary policy while the kernels update the block in place.  All launches go to torch's current stream, as So100Sim's do."""
+
+    def __init__(self, obs_dim, device, lr=3e-4, gamma=0.99, gae_lambda=0.95, clip=0.2, epochs=4, minibatch=32768,
+                 vf_coef=0.5, max_grad_norm=0.5, seed=0, use_graph=False):
+        from . import lib
+        del use_graph
+        torch.manual_seed(seed)
+        self.net = ActorCritic(obs_dim)                          # the draws of PPO's initialisation for the same seed
+        layout, P = lib.learner_layout(obs_dim)
+        self.device = torch.device(device)
+        self.params = torch.zeros(P, dtype=torch.float32, device=self.device)
+        named = dict(self.net.named_parameters())
+        for k, (off, shape) in layout.items():
+            p = named[lib.SB3_STATE_DICT_KEYS[k]]
+            view = self.params[off:off + p.numel()].view(shape)
+            view.copy_(p.data)
+            p.data = view                                        # from here on the module's parameter IS this slice of the block
+        self.net.requires_grad_(False)                           # nothing here goes through autograd
+        self.adam_m = torch.zeros_like(self.params); self.adam_v = torch.zeros_like(self.params)
+        self.adam_step = 0
+        self.obs_dim, self.epochs, self.mb = obs_dim, epochs, minibatch
+        self._hyper = dict(gamma=gamma, gae_lambda=gae_lambda, clip_range=clip, vf_coef=vf_coef, max_grad_norm=max_grad_norm, lr=lr, adam_eps=1e-5)
+        self._learner = None
+        self._shape = None
+
+    def _handle(self):
+        if self._learner is None:
+            from . import lib
+            if self.device.type != "cuda":
+                raise lib.So100Error(f"FusedPPO runs on a HIP device, not on {self.device}: there is no CPU fallback (use PPO)")
+            self._learner = lib.So100Learner(self.obs_dim, self.device, max_minibatch=self.mb, **self._hyper)
+        return self._learner
+
+    def _packed(self, b):
+        """the [T, N, obs_dim+10] chunk: b["packed"] as RolloutCollector.collect() hands it over (read in place, no copy); a dict without it
+        (separate tensors, e.g. from another collector) is packed here, once per update"""
+        obs = b["obs"]; T, N, o = obs.shape
+        if o != self.obs_dim:
+            raise ValueError(f"this learner was built for obs_dim {self.obs_dim}, the rollout has {o}")
+        buf = b.get("packed")
+        if buf is not None:
+            if tuple(buf.shape) != (T, N, o + 10) or buf.dtype != torch.float32 or not buf.is_contiguous() or buf.device != obs.device:
+                raise ValueError(f"packed chunk: want contiguous float32 {(T, N, o + 10)}, got {buf.dtype} {tuple(buf.shape)}")
+            return buf
+        code = b["dones"] * (1.0 + b["truncated"].to(b["dones"].dtype)) if "truncated" in b else b["dones"]
+        return torch.cat([obs, b["actions"], b["rewards"].unsqueeze(-1), code.unsqueeze(-1), b["values"].unsqueeze(-1), b["log_probs"].unsqueeze(-1)],
+                         dim=-1).to(self.device, torch.float32).contiguous()
+
+    def update(self, b, perms=None):
+        """b: RolloutCollector.collect() output.  With b["terminal_obs"] (RolloutCollector(defer_bootstrap=True)) the TimeLimit bootstrap is
+        applied by the advantage kernel; otherwise the rewards are taken as they are (the collector's eager bootstrap has been added).
+        perms: one int64 permutation of range(T*N) per epoch (tests); default torch.randperm, drawn as PPO.update draws them.
+        Returns PPO.update's keys plus policy_loss, clip_fraction and grad_norm of the last minibatch.  mean_bootstrapped_reward is the
+        mean of the chunk's reward column: with a deferred bootstrap that column keeps the env's own rewards (the bootstrapped ones are
+        never materialised), so it then equals the raw mean."""
+        L = self._handle()
+        buf = self._packed(b)
+        T, N = buf.shape[0], buf.shape[1]
+        if self._shape != (T, N):
+            dev = self.device
+            self._adv = torch.zeros(T, N, device=dev); self._ret = torch.zeros(T, N, device=dev)
+            self._adv_stats = torch.zeros(2, device=dev); self._stats = torch.zeros(4, device=dev)
+            self._shape = (T, N)
+        tobs = b.get("terminal_obs")
+        L.advantages(buf, b["last_obs"].contiguous(), self.params, self._adv, self._ret, self._adv_stats, terminal_obs=tobs)
+        n = T * N; mb = min(self.mb, n)
+        for e in range(self.epochs):
+            perm = torch.randperm(n, device=self.device) if perms is None else perms[e]
+            for i in range(0, n, mb):
+                self.adam_step += 1
+                L.minibatch_step(buf, perm[i:i + mb], self._adv, self._ret, self._adv_stats, self.params, self.adam_m, self.adam_v, self.adam_step, self._stats)
+        o = self.obs_dim
+        rew = buf[..., o + 6].mean()
+        raw = b.get("raw_reward_mean")
+        st = self._stats.tolist()
+        # mean_bootstrapped_reward: the mean of the chunk's reward column -- with a deferred bootstrap that column holds the env's own rewards
+        return {"value_loss": st[1], "mean_reward": (raw if raw is not None else rew).item(), "mean_bootstrapped_reward": rew.item(),
+                "policy_loss": st[0], "clip_fraction": st[2], "grad_norm": st[3]}

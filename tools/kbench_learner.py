@@ -1,0 +1,131 @@
+#!/usr/bin/env python3
+"""One full PPO update, PyTorch learner against the library's kernels, and `main.py train` end to end with either (needs a GPU).
+
+    python tools/kbench_learner.py [--out profiles/learner_update_kbench.json] [--commit LABEL] [--iters 100]
+
+Update: T = 64, N = 4096, 4 epochs of 32 768-sample minibatches (the PPO defaults), obs_dim 15 and 8; ppo.PPO.update and ppo.FusedPPO.update in
+one process on ONE synthetic chunk (no terminal observations: both take the rewards as they are).  First both learners make one update from
+the same initial weights with the same permutations and the largest parameter difference is reported (relative to each tensor's largest
+entry): the timed path is a compared path.  Then the two are timed in alternation, `--rounds` times each, HIP events around `reps` updates
+after a warm-up (every update ends in the .item() of its statistics, so the events bracket finished work); every round's figure is kept.
+Train: `main.py -a PPO train -e Env01-v1 --iters N --learner torch|fused`, alternating, twice each.  timesteps/s covers the window from the
+driver's first progress line (iteration 10: code objects loaded, buffers allocated) to its `done:` line, on the host clock -- rollouts,
+updates, the evaluations that fall into the run and the final saves; the driver's own summary line (whole run, 0.1 s resolution) is kept too.
+Every GPU step runs in a child process under its own time limit; the first one that fails ends the run.  One JSON document is written.
+
+    python tools/kbench_learner.py --part update --obs-dim 15 [--rounds 1]      # one step by hand (e.g. under rocprofv3)
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+T, N, EPOCHS, MB = 64, 4096, 4, 32768
+
+
+def part_update(obs_dim, rounds, reps, warmup):
+    import torch
+    from so100_mujoco_rl_amd.ppo import PPO, FusedPPO
+    from so100_mujoco_rl_amd.rollout import RolloutChunk
+    dev = torch.device("cuda", 0)
+    g = torch.Generator(device=dev); g.manual_seed(obs_dim)
+    o = obs_dim
+    learners = {"torch": PPO(o, dev, seed=0), "fused": FusedPPO(o, dev, seed=0)}          # the same initial weights
+    c = RolloutChunk(T, N, o, dev)
+    c.buf.copy_(torch.randn(c.buf.shape, device=dev, generator=g))
+    with torch.no_grad():                                        # a chunk the policy could have produced: its own values and log-probs, rare episode ends
+        v, lp = learners["torch"].net.evaluate(c.buf[..., :o].reshape(-1, o), c.buf[..., o:o + 6].reshape(-1, 6))
+        c.buf[..., o + 8] = v.reshape(T, N); c.buf[..., o + 9] = lp.reshape(T, N)
+        c.buf[..., o + 7] = (torch.rand(T, N, device=dev, generator=g) < 1e-3).float() * 2.0
+    b = c.unpack(); b["last_obs"] = torch.randn(N, o, device=dev, generator=g); b["packed"] = c.buf
+    res = {"obs_dim": o, "T": T, "N": N, "epochs": EPOCHS, "minibatch": MB, "samples": T * N, "card": torch.cuda.get_device_name(0)}
+    # ---- the timed path is a compared path: one update each from the same weights, the same permutations
+    stats = {}
+    for name, learner in learners.items():
+        torch.manual_seed(1234)
+        stats[name] = learner.update(b)
+    sd_t, sd_f = learners["torch"].net.state_dict(), learners["fused"].net.state_dict()
+    res["first_update_max_param_difference"] = max(float((sd_f[k] - sd_t[k]).abs().max() / sd_t[k].abs().max()) for k in sd_t)
+    res["first_update_value_loss"] = {k: stats[k]["value_loss"] for k in stats}
+    for learner in learners.values():
+        for _ in range(warmup):
+            learner.update(b)
+    ms = {"torch": [], "fused": []}
+    for _ in range(rounds):                                      # alternating: what drifts on a shared host hits both
+        for name, learner in learners.items():
+            e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize(); e0.record()
+            for _ in range(reps[name]):
+                learner.update(b)
+            e1.record(); torch.cuda.synchronize()
+            ms[name].append(round(e0.elapsed_time(e1) / reps[name], 4))
+    for name in ms:
+        med = sorted(ms[name])[len(ms[name]) // 2]
+        res[name] = {"ms_per_update_rounds": ms[name], "ms_per_update": med, "updates_per_round": reps[name], "samples_per_s": round(T * N * EPOCHS / med * 1e3)}
+    res["torch_over_fused"] = round(res["torch"]["ms_per_update"] / res["fused"]["ms_per_update"], 2)
+    print("KBENCH " + json.dumps(res), flush=True)
+
+
+def part_train(learner, iters):
+    import logging
+    import time
+    from click.testing import CliRunner
+    from so100_mujoco_rl_amd import main as drv
+    lines = []
+    h = logging.Handler(); h.emit = lambda rec: lines.append((time.perf_counter(), rec.getMessage()))
+    drv.logger.addHandler(h)
+    with tempfile.TemporaryDirectory() as d:
+        os.chdir(d)
+        r = CliRunner().invoke(drv.cli, ["-a", "PPO", "train", "-e", "Env01-v1", "--envs", str(N), "--iters", str(iters), "--learner", learner], catch_exceptions=False)
+        os.chdir(ROOT)
+    assert r.exit_code == 0, r.output
+    t10 = [t for t, l in lines if l.startswith("iter    10 ")][0]
+    t_done, summary = [(t, l) for t, l in lines if l.startswith("done:")][-1]
+    steps = (iters - 10) * T * N
+    print("KBENCH " + json.dumps({"learner": learner, "envs": N, "iters": iters, "window": "first progress line (iteration 10) to the driver's done line",
+                                  "window_timesteps": steps, "window_s": round(t_done - t10, 4), "timesteps_per_s": round(steps / (t_done - t10)),
+                                  "driver_summary": summary}), flush=True)
+
+
+def child(args, limit):
+    """one GPU step in a process of its own, under its own time limit; returns its KBENCH document"""
+    out = subprocess.run([sys.executable, os.path.abspath(__file__)] + args, capture_output=True, text=True, timeout=limit, cwd=ROOT)
+    if out.returncode != 0:
+        raise SystemExit(f"step {args} failed ({out.returncode}); nothing further is started\n{out.stdout[-2000:]}{out.stderr[-2000:]}")
+    return json.loads([l for l in out.stdout.splitlines() if l.startswith("KBENCH ")][-1][7:])
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--part", choices=("all", "update", "train"), default="all")
+    ap.add_argument("--obs-dim", type=int, default=15); ap.add_argument("--learner", default="fused")
+    ap.add_argument("--rounds", type=int, default=5); ap.add_argument("--warmup", type=int, default=3); ap.add_argument("--iters", type=int, default=100)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "learner_update_kbench.json")); ap.add_argument("--commit", default="unknown")
+    a = ap.parse_args()
+    if a.part == "update":
+        return part_update(a.obs_dim, a.rounds, {"torch": 10, "fused": 100}, a.warmup)      # >= 0.5 s per timed window
+    if a.part == "train":
+        return part_train(a.learner, a.iters)
+    doc = {"what": "one PPO update (4 epochs x 8 minibatches of 32768 over 64 x 4096 samples) and main.py train end to end, PyTorch learner vs the HIP learner",
+           "commit": a.commit, "update": [], "train": []}
+    for od in (15, 8):
+        doc["update"].append(child(["--part", "update", "--obs-dim", str(od), "--rounds", str(a.rounds)], 300))
+    for learner in ("torch", "fused", "torch", "fused"):
+        doc["train"].append(child(["--part", "train", "--learner", learner, "--iters", str(a.iters)], 300))
+    doc["card"] = doc["update"][0]["card"]
+    tr = {k: [t["timesteps_per_s"] for t in doc["train"] if t["learner"] == k] for k in ("torch", "fused")}
+    doc["train_timesteps_per_s"] = tr
+    doc["train_fused_over_torch"] = round((sum(tr["fused"]) / len(tr["fused"])) / (sum(tr["torch"]) / len(tr["torch"])), 2)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(doc, f, indent=1); f.write("\n")
+    print(json.dumps(doc, indent=1))
+
+
+if __name__ == "__main__":
+    main()
