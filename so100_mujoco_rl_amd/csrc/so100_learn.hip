@@ -23,9 +23,9 @@
 #include "../../include/so100_learn.h"
 #include "so100_policy.hpp"
 #include "so100_learn.hpp"
+#include "so100_host.hpp"
 
 namespace so100 {
-int set_last_error(int code, const char* msg);            // so100_sim.hip: the thread-local message behind so100_last_error()
 
 namespace learn {
 
@@ -54,9 +54,9 @@ struct GradSmem {
 template <int OD, int TW>
 __device__ __forceinline__ void tower_pass(const GradArgs& A, GradSmem& S) {
     constexpr int ROW = OD + ROW_EXTRA, NH = TW ? 1 : ACT_DIM, P = num_params(OD);
-    constexpr int oW0 = tensor_offset(TW ? T_VF_W0 : T_PI_W0, OD), oB0 = tensor_offset(TW ? T_VF_B0 : T_PI_B0, OD);
-    constexpr int oW1 = tensor_offset(TW ? T_VF_W1 : T_PI_W1, OD), oB1 = tensor_offset(TW ? T_VF_B1 : T_PI_B1, OD);
-    constexpr int oWH = tensor_offset(TW ? T_V_W : T_MU_W, OD), oBH = tensor_offset(TW ? T_V_B : T_MU_B, OD), oLS = tensor_offset(T_LOG_STD, OD);
+    constexpr int oW0 = tensor_offset(TW ? T_vf_w0 : T_pi_w0, OD), oB0 = tensor_offset(TW ? T_vf_b0 : T_pi_b0, OD);
+    constexpr int oW1 = tensor_offset(TW ? T_vf_w1 : T_pi_w1, OD), oB1 = tensor_offset(TW ? T_vf_b1 : T_pi_b1, OD);
+    constexpr int oWH = tensor_offset(TW ? T_v_w : T_mu_w, OD), oBH = tensor_offset(TW ? T_v_b : T_mu_b, OD), oLS = tensor_offset(T_log_std, OD);
     const float* __restrict__ prm = A.params;
     const float* __restrict__ W0 = prm + oW0; const float* __restrict__ B0 = prm + oB0;
     const float* __restrict__ W1 = prm + oW1; const float* __restrict__ B1 = prm + oB1;
@@ -289,9 +289,9 @@ __global__ __launch_bounds__(256) void so100_learn_adam(const float* __restrict_
 // V(obs) of one row in one lane: the weights are wave-uniform (scalar cache), the activations stay in registers
 template <int OD>
 __device__ __forceinline__ float value_tower(const float* __restrict__ prm, const float* __restrict__ obs) {
-    const float* __restrict__ W0 = prm + tensor_offset(T_VF_W0, OD); const float* __restrict__ B0 = prm + tensor_offset(T_VF_B0, OD);
-    const float* __restrict__ W1 = prm + tensor_offset(T_VF_W1, OD); const float* __restrict__ B1 = prm + tensor_offset(T_VF_B1, OD);
-    const float* __restrict__ VW = prm + tensor_offset(T_V_W, OD);
+    const float* __restrict__ W0 = prm + tensor_offset(T_vf_w0, OD); const float* __restrict__ B0 = prm + tensor_offset(T_vf_b0, OD);
+    const float* __restrict__ W1 = prm + tensor_offset(T_vf_w1, OD); const float* __restrict__ B1 = prm + tensor_offset(T_vf_b1, OD);
+    const float* __restrict__ VW = prm + tensor_offset(T_v_w, OD);
     float x[OD], h1[HID];
 #pragma unroll
     for (int i = 0; i < OD; i++) x[i] = obs[i];
@@ -302,7 +302,7 @@ __device__ __forceinline__ float value_tower(const float* __restrict__ prm, cons
         for (int i = 0; i < OD; i++) acc = fmaf(W0[j*OD + i], x[i], acc);
         h1[j] = fast_tanh(acc);
     }
-    float v = prm[tensor_offset(T_V_B, OD)];
+    float v = prm[tensor_offset(T_v_b, OD)];
 #pragma unroll 2
     for (int j = 0; j < HID; j++) {
         float acc = B1[j];
@@ -361,28 +361,17 @@ __global__ __launch_bounds__(ADV_THREADS) void so100_learn_adv_stats(const float
     if (threadIdx.x == 0) { stats[0] = mean; stats[1] = lsqrt(ss/(float)(n - 1)); }       // n = 1: 0/0 = NaN, as torch
 }
 
-const char* const kTensorNames[NUM_TENSORS] = { "pi_w0", "pi_b0", "pi_w1", "pi_b1", "mu_w", "mu_b", "log_std", "vf_w0", "vf_b0", "vf_w1", "vf_b1", "v_w", "v_b" };
+const char* const kTensorNames[NUM_TENSORS] = {
+#define X(name, rows, cols) #name,
+    SO100_POLICY_TENSORS(X)
+#undef X
+};
 
 int tensor_index(const char* name) {
     if (!name) return -1;
     for (int t = 0; t < NUM_TENSORS; t++) if (strcmp(kTensorNames[t], name) == 0) return t;
     return -1;
 }
-
-int fail(int code, const char* fmt, long a = 0) {
-    char msg[512];
-    snprintf(msg, sizeof msg, fmt, a);
-    return set_last_error(code, msg);
-}
-
-struct DeviceScope {
-    int prev = -1, target = -1; bool ok = true;
-    explicit DeviceScope(int dev) : target(dev) {
-        if (hipGetDevice(&prev) != hipSuccess) { ok = false; return; }
-        if (prev != dev && hipSetDevice(dev) != hipSuccess) ok = false;
-    }
-    ~DeviceScope() { if (ok && prev != target) (void)hipSetDevice(prev); }
-};
 
 }  // namespace learn
 }  // namespace so100
@@ -397,9 +386,6 @@ struct so100_learner {
     float* gsum = nullptr;         // [P + NSTAT] their ordered sum
     float* sq_block = nullptr;     // [nblk] sum of squares per block of the reduction
 };
-
-#define LEARN_HIP_TRY(expr, what) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { char m_[256]; \
-    snprintf(m_, sizeof m_, "%s: %s (HIP error %ld)", what, hipGetErrorString(e_), (long)e_); return set_last_error(SO100_E_LAUNCH, m_); } } while (0)
 
 extern "C" {
 
@@ -420,8 +406,8 @@ int so100_learner_param_size(int32_t obs_dim, const char* name) {
 int so100_learner_create(const so100_learner_config* cfg, so100_learner** out) {
     if (!cfg || !out) return fail(SO100_E_INVALID, "so100_learner_create: null argument");
     *out = nullptr;
-    if (cfg->obs_dim != 15 && cfg->obs_dim != 8) return fail(SO100_E_INVALID, "so100_learner_create: obs_dim must be 15 or 8, got %ld", cfg->obs_dim);
-    if (cfg->max_minibatch < 1) return fail(SO100_E_INVALID, "so100_learner_create: max_minibatch must be >= 1, got %ld", cfg->max_minibatch);
+    if (cfg->obs_dim != 15 && cfg->obs_dim != 8) return fail(SO100_E_INVALID, "so100_learner_create: obs_dim must be 15 or 8, got %d", cfg->obs_dim);
+    if (cfg->max_minibatch < 1) return fail(SO100_E_INVALID, "so100_learner_create: max_minibatch must be >= 1, got %d", cfg->max_minibatch);
     if (!(cfg->gamma >= 0.0f && cfg->gamma <= 1.0f)) return fail(SO100_E_INVALID, "so100_learner_create: gamma must be in [0, 1]");
     if (!(cfg->gae_lambda >= 0.0f && cfg->gae_lambda <= 1.0f)) return fail(SO100_E_INVALID, "so100_learner_create: gae_lambda must be in [0, 1]");
     if (!(cfg->clip_range > 0.0f)) return fail(SO100_E_INVALID, "so100_learner_create: clip_range must be > 0");
@@ -435,8 +421,7 @@ int so100_learner_create(const so100_learner_config* cfg, so100_learner** out) {
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
         return fail(SO100_E_NODEVICE, "so100_learner_create: no HIP device available (this library has no CPU fallback)");
     if (cfg->device < 0 || cfg->device >= ndev) return fail(SO100_E_INVALID, "so100_learner_create: device ordinal out of range");
-    DeviceScope g(cfg->device);
-    if (!g.ok) return fail(SO100_E_NODEVICE, "so100_learner_create: cannot select the device");
+    SO100_ON_DEVICE(cfg->device, "so100_learner_create");
     so100_learner* L = new (std::nothrow) so100_learner();
     if (!L) return fail(SO100_E_NOMEM, "so100_learner_create: out of host memory");
     L->cfg = *cfg;
@@ -456,7 +441,7 @@ int so100_learner_create(const so100_learner_config* cfg, so100_learner** out) {
 
 void so100_learner_destroy(so100_learner* L) {
     if (!L) return;
-    DeviceScope g(L->cfg.device);
+    DeviceGuard g(L->cfg.device);
     if (L->partial) (void)hipFree(L->partial);
     if (L->gsum) (void)hipFree(L->gsum);
     if (L->sq_block) (void)hipFree(L->sq_block);
@@ -465,46 +450,39 @@ void so100_learner_destroy(so100_learner* L) {
 
 int so100_learner_advantages(so100_learner* L, const so100_advantages_io* io, int32_t T, int32_t N, void* stream) {
     if (!L || !io) return fail(SO100_E_INVALID, "so100_learner_advantages: null argument");
-    if (T < 1) return fail(SO100_E_INVALID, "so100_learner_advantages: T must be >= 1, got %ld", T);
-    if (N < 1) return fail(SO100_E_INVALID, "so100_learner_advantages: N must be >= 1, got %ld", N);
+    if (T < 1) return fail(SO100_E_INVALID, "so100_learner_advantages: T must be >= 1, got %d", T);
+    if (N < 1) return fail(SO100_E_INVALID, "so100_learner_advantages: N must be >= 1, got %d", N);
     if (!io->rollout_dev || !io->last_obs_dev || !io->params_dev || !io->adv_dev || !io->ret_dev || !io->adv_stats_dev)
         return fail(SO100_E_INVALID, "so100_learner_advantages: rollout/last_obs/params/adv/ret/adv_stats pointers are required");
-    DeviceScope g(L->cfg.device);
-    if (!g.ok) return fail(SO100_E_NODEVICE, "so100_learner_advantages: cannot select the device");
+    SO100_ON_DEVICE(L->cfg.device, "so100_learner_advantages");
     const long TN = (long)T*(long)N;
     const long vblocks = (TN + N + 255)/256;
     if (vblocks > 0x7fffffffL) return fail(SO100_E_INVALID, "so100_learner_advantages: T*N is too large");
     const hipStream_t st = (hipStream_t)stream;
     const bool boot = io->terminal_obs_chunk_dev != nullptr;
-    if (L->cfg.obs_dim == 15) {
-        hipLaunchKernelGGL((so100_learn_values<15>), dim3((unsigned)vblocks), dim3(256), 0, st, io->rollout_dev, io->terminal_obs_chunk_dev, io->last_obs_dev, io->params_dev, TN, N, io->adv_dev, io->ret_dev);
-        hipLaunchKernelGGL((so100_learn_gae<15>), dim3((unsigned)((N + 63)/64)), dim3(64), 0, st, io->rollout_dev, T, N, boot, L->cfg.gamma, L->cfg.gae_lambda, io->adv_dev, io->ret_dev);
-    } else {
-        hipLaunchKernelGGL((so100_learn_values<8>), dim3((unsigned)vblocks), dim3(256), 0, st, io->rollout_dev, io->terminal_obs_chunk_dev, io->last_obs_dev, io->params_dev, TN, N, io->adv_dev, io->ret_dev);
-        hipLaunchKernelGGL((so100_learn_gae<8>), dim3((unsigned)((N + 63)/64)), dim3(64), 0, st, io->rollout_dev, T, N, boot, L->cfg.gamma, L->cfg.gae_lambda, io->adv_dev, io->ret_dev);
-    }
+    SO100_WITH_OBS_DIM(L->cfg.obs_dim,
+        hipLaunchKernelGGL((so100_learn_values<OD>), dim3((unsigned)vblocks), dim3(256), 0, st, io->rollout_dev, io->terminal_obs_chunk_dev, io->last_obs_dev, io->params_dev, TN, N, io->adv_dev, io->ret_dev);
+        hipLaunchKernelGGL((so100_learn_gae<OD>), dim3((unsigned)((N + 63)/64)), dim3(64), 0, st, io->rollout_dev, T, N, boot, L->cfg.gamma, L->cfg.gae_lambda, io->adv_dev, io->ret_dev););
     hipLaunchKernelGGL(so100_learn_adv_stats, dim3(1), dim3(ADV_THREADS), 0, st, (const float*)io->adv_dev, TN, io->adv_stats_dev);
-    LEARN_HIP_TRY(hipGetLastError(), "so100_learner_advantages");
+    HIP_TRY(hipGetLastError(), SO100_E_LAUNCH, "so100_learner_advantages: ");
     return 0;
 }
 
 int so100_learner_minibatch_step(so100_learner* L, const so100_minibatch_io* io, void* stream) {
     if (!L || !io) return fail(SO100_E_INVALID, "so100_learner_minibatch_step: null argument");
-    if (io->mb < 1 || io->mb > L->cfg.max_minibatch) return fail(SO100_E_INVALID, "so100_learner_minibatch_step: mb must be in 1..max_minibatch, got %ld", io->mb);
+    if (io->mb < 1 || io->mb > L->cfg.max_minibatch) return fail(SO100_E_INVALID, "so100_learner_minibatch_step: mb must be in 1..max_minibatch, got %d", io->mb);
     if (io->num_samples < 1) return fail(SO100_E_INVALID, "so100_learner_minibatch_step: num_samples must be >= 1, got %ld", (long)io->num_samples);
-    if (io->adam_step < 1) return fail(SO100_E_INVALID, "so100_learner_minibatch_step: adam_step is 1-based, got %ld", io->adam_step);
+    if (io->adam_step < 1) return fail(SO100_E_INVALID, "so100_learner_minibatch_step: adam_step is 1-based, got %d", io->adam_step);
     if (!io->rollout_dev || !io->adv_dev || !io->ret_dev || !io->adv_stats_dev || !io->params_dev || !io->adam_m_dev || !io->adam_v_dev || !io->stats_dev)
         return fail(SO100_E_INVALID, "so100_learner_minibatch_step: rollout/adv/ret/adv_stats/params/adam_m/adam_v/stats pointers are required");
-    DeviceScope g(L->cfg.device);
-    if (!g.ok) return fail(SO100_E_NODEVICE, "so100_learner_minibatch_step: cannot select the device");
+    SO100_ON_DEVICE(L->cfg.device, "so100_learner_minibatch_step");
     const hipStream_t st = (hipStream_t)stream;
     const int tiles = (io->mb + LT - 1)/LT, G = tiles < L->grid_max ? tiles : L->grid_max;
     GradArgs A;
     A.chunk = io->rollout_dev; A.num_samples = (long)io->num_samples; A.idx = io->idx_dev; A.mb = io->mb;
     A.adv = io->adv_dev; A.ret = io->ret_dev; A.adv_stats = io->adv_stats_dev; A.params = io->params_dev; A.partial = L->partial;
     A.clip = L->cfg.clip_range; A.vf_coef = L->cfg.vf_coef;
-    if (L->cfg.obs_dim == 15) hipLaunchKernelGGL((so100_learn_grad<15>), dim3((unsigned)G), dim3(256), 0, st, A);
-    else hipLaunchKernelGGL((so100_learn_grad<8>), dim3((unsigned)G), dim3(256), 0, st, A);
+    SO100_WITH_OBS_DIM(L->cfg.obs_dim, hipLaunchKernelGGL((so100_learn_grad<OD>), dim3((unsigned)G), dim3(256), 0, st, A););
     hipLaunchKernelGGL(so100_learn_reduce, dim3((unsigned)L->nblk), dim3(256), 0, st, (const float*)L->partial, G, L->P, L->gsum, L->sq_block);
     AdamArgs a;
     a.max_grad_norm = L->cfg.max_grad_norm;
@@ -513,7 +491,7 @@ int so100_learner_minibatch_step(so100_learner* L, const so100_minibatch_io* io,
     a.inv_mb = 1.0f/(float)io->mb;
     hipLaunchKernelGGL(so100_learn_adam, dim3((unsigned)((L->P + 255)/256)), dim3(256), 0, st, (const float*)L->gsum, (const float*)L->sq_block, L->nblk, L->P,
                        io->params_dev, io->adam_m_dev, io->adam_v_dev, io->grads_dev, io->stats_dev, a);
-    LEARN_HIP_TRY(hipGetLastError(), "so100_learner_minibatch_step");
+    HIP_TRY(hipGetLastError(), SO100_E_LAUNCH, "so100_learner_minibatch_step: ");
     return 0;
 }
 

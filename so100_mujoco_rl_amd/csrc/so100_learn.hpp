@@ -6,6 +6,7 @@
 //   ppo_loss_head       the PPO._step loss of one sample with its derivatives towards the network outputs
 //   clip_adam_update    clip_grad_norm_'s scaling + one torch.optim.Adam step of one parameter
 #pragma once
+#include "so100_policy_tensors.h"
 
 #ifndef SO100_LHD
 #if defined(__HIPCC__) || defined(__CUDACC__)
@@ -19,14 +20,21 @@ namespace so100 {
 namespace learn {
 
 constexpr int ACT_DIM = 6, HID = 64;
-constexpr int NUM_TENSORS = 13;
-// the flat parameter block: the 13 tensors in the order of so100_policy_weights, each in nn.Linear layout weight[out][in]
-constexpr int tensor_rows(int t, int /*od*/) { return (t == 4 || t == 5 || t == 6) ? ACT_DIM : (t == 11 || t == 12) ? 1 : HID; }
-constexpr int tensor_cols(int t, int od) { return (t == 0 || t == 7) ? od : (t == 2 || t == 9 || t == 4 || t == 11) ? HID : 1; }
+// the flat parameter block: the tensors of so100_policy_tensors.h in its order, each in nn.Linear layout weight[rows][cols].  The two
+// shape functions stay written as conditions (the advantages kernel evaluates tensor_offset at run time: another body is other device
+// code); the asserts below hold them to the table for both observation widths.
+constexpr int tensor_rows(int t, int /*od*/) { return (t == T_mu_w || t == T_mu_b || t == T_log_std) ? ACT_DIM : (t == T_v_w || t == T_v_b) ? 1 : HID; }
+constexpr int tensor_cols(int t, int od) { return (t == T_pi_w0 || t == T_vf_w0) ? od : (t == T_pi_w1 || t == T_vf_w1 || t == T_mu_w || t == T_v_w) ? HID : 1; }
 constexpr int tensor_size(int t, int od) { return tensor_rows(t, od)*tensor_cols(t, od); }
 constexpr int tensor_offset(int t, int od) { return t == 0 ? 0 : tensor_offset(t - 1, od) + tensor_size(t - 1, od); }
 constexpr int num_params(int od) { return tensor_offset(NUM_TENSORS - 1, od) + tensor_size(NUM_TENSORS - 1, od); }
-enum { T_PI_W0, T_PI_B0, T_PI_W1, T_PI_B1, T_MU_W, T_MU_B, T_LOG_STD, T_VF_W0, T_VF_B0, T_VF_W1, T_VF_B1, T_V_W, T_V_B };
+constexpr bool shapes_match_table(int od) {
+#define X(name, rows, cols) if (tensor_rows(T_##name, od) != (rows) || tensor_cols(T_##name, od) != (cols)) return false;
+    SO100_POLICY_TENSORS(X)
+#undef X
+    return true;
+}
+static_assert(NUM_TENSORS == 13 && shapes_match_table(15) && shapes_match_table(8), "so100_policy_tensors.h");
 static_assert(num_params(15) == 10829 && num_params(8) == 9933, "SB3 MlpPolicy, 2 x 64 towers");
 
 SO100_LHD float  lexp(float x)   { return __builtin_expf(x); }

@@ -3,6 +3,8 @@
 #include "so100_kernels.hpp"
 #include "so100_balance.hpp"
 #include "so100_render.hpp"
+#include "so100_policy_tensors.h"
+#include "so100_host.hpp"
 
 namespace so100 {
 extern template struct KindOps<1>; extern template struct KindOps<2>; extern template struct KindOps<3>;
@@ -13,14 +15,6 @@ namespace {
 
 using namespace so100;
 
-thread_local char g_err[512] = "";
-int fail(int code, const char* fmt, const char* a = "", long b = 0) {
-    snprintf(g_err, sizeof g_err, fmt, a, b);
-    return code;
-}
-#define HIP_TRY(expr, code) do { hipError_t e_ = (expr); if (e_ != hipSuccess) \
-    return fail(code, "%s (HIP error %ld)", hipGetErrorString(e_), (long)e_); } while (0)
-
 const char* const kFieldNames[] = {
 #define X(name, member, kind, group) #name,
     SO100_STATE_FIELDS(X)
@@ -30,11 +24,6 @@ const char* const kFieldNames[] = {
 #include "so100_start_positions.inc"
 
 }  // namespace
-
-namespace so100 {
-// the message behind so100_last_error() for the library's other translation units (so100_learn.hip); returns `code`
-int set_last_error(int code, const char* msg) { return fail(code, "%s", msg); }
-}
 
 struct so100_sim {
     so100_config cfg;
@@ -47,18 +36,82 @@ struct so100_sim {
 };
 
 namespace {
-struct DeviceGuard {
-    int prev = -1; bool ok = true;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) { ok = false; return; }
-        if (prev != dev && hipSetDevice(dev) != hipSuccess) ok = false;
-        target = dev;
-    }
-    ~DeviceGuard() { if (ok && prev != target) (void)hipSetDevice(prev); }
-    int target = -1;
-};
 #define DISPATCH_KIND(kind, fn) \
     ((kind) == 1 ? KindOps<1>::fn : (kind) == 2 ? KindOps<2>::fn : (kind) == 3 ? KindOps<3>::fn : (kind) == 4 ? KindOps<4>::fn : (kind) == 5 ? KindOps<5>::fn : KindOps<6>::fn)
+
+// so100_policy_weights (the ABI) and PolicyWeights (the kernels) are the table of so100_policy_tensors.h, in its order
+#define X(name, rows, cols) static_assert(offsetof(so100_policy_weights, name) == T_##name*sizeof(const float*) && \
+                                          offsetof(PolicyWeights, name) == T_##name*sizeof(const float*), #name " is out of the table's order");
+SO100_POLICY_TENSORS(X)
+#undef X
+static_assert(sizeof(so100_policy_weights) == NUM_TENSORS*sizeof(const float*) && sizeof(PolicyWeights) == sizeof(so100_policy_weights), "layout");
+
+bool any_null(const so100_policy_weights& w) {
+#define X(name, rows, cols) if (!w.name) return true;
+    SO100_POLICY_TENSORS(X)
+#undef X
+    return false;
+}
+
+// Envs per workgroup of the multi-wave kernels.  Their step time is set by the slowest lane of a wave (a cube in a contact transient, a
+// pad hitting the floor: data-dependent Newton iterations), so a batch that leaves CUs idle is spread thinner: 16 or 32 envs per 4-wave
+// workgroup while that still fits one workgroup per CU.  Variants without a data-dependent solve (cube pinned) gain nothing and keep 64.
+int choose_envs_per_workgroup(const so100_config& cfg, int cus) {
+    if (cfg.envs_per_workgroup != 0) return (int)cfg.envs_per_workgroup;          // the caller pins it (validated by so100_create)
+    int epw = 64;
+    if (cfg.flags & (SO100_F_FLOOR | SO100_F_PADS_FLOOR | SO100_F_PADS_CUBE | SO100_F_LINKS_FLOOR | SO100_F_LINKS_CUBE))
+        while (epw > 16 && (cfg.num_envs + epw/2 - 1)/(epw/2) <= cus) epw /= 2;
+    // contact disabled (no data-dependent solve): 32 envs per workgroup while that fits the CUs -- the persistent kernel's policy phase then
+    // runs one 32-row MFMA tile per tower instead of two (so100_rollout_fused<K, 8, 4, 32>: half the matrix-core time per step)
+    if (cfg.flags == SO100_F_CUBE_PINNED && (cfg.num_envs + 31)/32 <= cus) epw = 32;
+    return epw;
+}
+
+// what so100_create does on the device, under its guard; whatever a failure leaves allocated so100_destroy frees
+int create_on_device(so100_sim* s) {
+    const so100_config* cfg = &s->cfg;
+    s->prm.n = cfg->num_envs; s->prm.flags = cfg->flags; s->prm.solver_iters = cfg->solver_iters;
+    s->prm.contact_iters = cfg->contact_iters; s->prm.frame_skip = cfg->frame_skip;
+    s->prm.max_episode_steps = cfg->max_episode_steps;
+    s->prm.seed_lo = (uint32_t)cfg->seed; s->prm.seed_hi = (uint32_t)(cfg->seed >> 32);
+    s->prm.env_id_offset = cfg->env_id_offset;
+    hipDeviceProp_t prop;
+    int cus = 256;
+    if (hipGetDeviceProperties(&prop, cfg->device) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
+    s->prm.epw = choose_envs_per_workgroup(*cfg, cus);
+    s->prm.mw_max = MW_MAX_ENVS;
+    if (const char* ov = getenv("SO100_MW_MAX_ENVS")) { const long v = atol(ov); if (v >= 0) s->prm.mw_max = (int32_t)(v > (1L << 30) ? (1L << 30) : v); }
+    const size_t bytes = (size_t)SF_COUNT*(size_t)cfg->num_envs*sizeof(float);
+    if (hipMalloc(&s->state, bytes) != hipSuccess) return fail(SO100_E_NOMEM, "so100_create: hipMalloc of %ld bytes failed", (long)bytes);
+    float tab[36*6];
+    for (int i = 0; i < 36; i++) for (int j = 0; j < 6; j++) tab[6*i + j] = (float)SO100_VALID_START_POSITIONS[i][j];
+    if (hipMalloc(&s->start_tab, sizeof tab) != hipSuccess || hipMemcpy(s->start_tab, tab, sizeof tab, hipMemcpyHostToDevice) != hipSuccess)
+        return fail(SO100_E_NOMEM, "so100_create: start table upload failed");
+    // workgroup load balancing of the persistent rollout kernel (pad-contact variants, batches it serves; SO100_BALANCE=0 turns it off)
+    const char* bal = getenv("SO100_BALANCE");
+    const bool pads = (cfg->flags & (SO100_F_PADS_FLOOR | SO100_F_PADS_CUBE | SO100_F_LINKS_FLOOR | SO100_F_LINKS_CUBE)) != 0;
+    if (pads && cfg->num_envs <= BALANCE_MAX_ENVS && !(bal && atoi(bal) == 0)) {
+        const size_t slots = (size_t)((cfg->num_envs + s->prm.epw - 1)/s->prm.epw)*(size_t)s->prm.epw;
+        if (hipMalloc(&s->slot_env, slots*sizeof(int32_t)) != hipSuccess) return fail(SO100_E_NOMEM, "so100_create: hipMalloc of the slot map failed");
+    }
+    HIP_TRY(DISPATCH_KIND(cfg->env_kind, init)(s->prm.n, s->state), SO100_E_LAUNCH, "so100_create: ");
+    return 0;
+}
+
+// `rows` rows of the [field][N] state matrix from row `row`: copied to `user` (or, to_state, from it); a null `user` zeroes them
+struct RowCopy { int row, rows; const void* user; };
+int move_rows(so100_sim* s, const char* fn, bool to_state, std::initializer_list<RowCopy> copies, void* stream) {
+    SO100_ON_DEVICE(s->cfg.device, fn);
+    const size_t n = (size_t)s->prm.n;
+    for (const RowCopy& c : copies) {
+        float* mine = s->state + (size_t)c.row*n;
+        const size_t bytes = (size_t)c.rows*n*sizeof(float);
+        if (!c.user) HIP_TRY(hipMemsetAsync(mine, 0, bytes, (hipStream_t)stream), SO100_E_LAUNCH);
+        else if (to_state) HIP_TRY(hipMemcpyAsync(mine, c.user, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream), SO100_E_LAUNCH);
+        else HIP_TRY(hipMemcpyAsync(const_cast<void*>(c.user), mine, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream), SO100_E_LAUNCH);
+    }
+    return 0;
+}
 }  // namespace
 
 extern "C" {
@@ -72,7 +125,7 @@ int so100_state_field_index(const char* name) {
     return -1;
 }
 const char* so100_state_field_name(int32_t field) { return (field >= 0 && field < SF_COUNT) ? kFieldNames[field] : nullptr; }
-const char* so100_last_error(void) { return g_err; }
+const char* so100_last_error(void) { return g_last_error; }
 #ifdef SO100_ROLLOUT_PROF
 int so100_prof_read(int kind, long long* out48) { return DISPATCH_KIND(kind, prof_read)(out48); }
 int so100_prof_read_wg(int kind, long long* wg4096, int* env32768) { return DISPATCH_KIND(kind, prof_read_wg)(wg4096, env32768); }
@@ -80,75 +133,32 @@ int so100_prof_read_hist(int kind, unsigned long long* hist48, int reset) { retu
 #endif
 
 int so100_create(const so100_config* cfg, so100_sim** out) {
-    if (!cfg || !out) return fail(SO100_E_INVALID, "so100_create: null argument%s");
+    if (!cfg || !out) return fail(SO100_E_INVALID, "so100_create: null argument");
     *out = nullptr;
-    if (cfg->env_kind < 1 || cfg->env_kind > 6) return fail(SO100_E_INVALID, "so100_create: env_kind must be 1..6%s");
-    if (cfg->num_envs < 1) return fail(SO100_E_INVALID, "so100_create: num_envs must be >= 1%s");
-    if (cfg->solver_iters < 1 || cfg->solver_iters > 64) return fail(SO100_E_INVALID, "so100_create: solver_iters must be in 1..64%s");
-    if (cfg->contact_iters < 1 || cfg->contact_iters > 64) return fail(SO100_E_INVALID, "so100_create: contact_iters must be in 1..64%s");
-    if (cfg->frame_skip < 1 || cfg->frame_skip > 1024) return fail(SO100_E_INVALID, "so100_create: frame_skip must be in 1..1024%s");
-    if (cfg->max_episode_steps < 0) return fail(SO100_E_INVALID, "so100_create: max_episode_steps must be >= 0%s");
+    if (cfg->env_kind < 1 || cfg->env_kind > 6) return fail(SO100_E_INVALID, "so100_create: env_kind must be 1..6");
+    if (cfg->num_envs < 1) return fail(SO100_E_INVALID, "so100_create: num_envs must be >= 1");
+    if (cfg->solver_iters < 1 || cfg->solver_iters > 64) return fail(SO100_E_INVALID, "so100_create: solver_iters must be in 1..64");
+    if (cfg->contact_iters < 1 || cfg->contact_iters > 64) return fail(SO100_E_INVALID, "so100_create: contact_iters must be in 1..64");
+    if (cfg->frame_skip < 1 || cfg->frame_skip > 1024) return fail(SO100_E_INVALID, "so100_create: frame_skip must be in 1..1024");
+    if (cfg->max_episode_steps < 0) return fail(SO100_E_INVALID, "so100_create: max_episode_steps must be >= 0");
     if (cfg->flags & ~(SO100_F_FRICTIONLOSS | SO100_F_LIMITS | SO100_F_FLOOR | SO100_F_CUBE_PINNED | SO100_F_PADS_FLOOR | SO100_F_PADS_CUBE | SO100_F_LINKS_FLOOR | SO100_F_LINKS_CUBE))
-        return fail(SO100_E_INVALID, "so100_create: unknown flag bits%s");
+        return fail(SO100_E_INVALID, "so100_create: unknown flag bits");
     if ((cfg->flags & (SO100_F_PADS_CUBE | SO100_F_LINKS_CUBE)) && (cfg->flags & SO100_F_CUBE_PINNED))
-        return fail(SO100_E_INVALID, "so100_create: SO100_F_PADS_CUBE / SO100_F_LINKS_CUBE need a dynamic cube (not SO100_F_CUBE_PINNED)%s");
+        return fail(SO100_E_INVALID, "so100_create: SO100_F_PADS_CUBE / SO100_F_LINKS_CUBE need a dynamic cube (not SO100_F_CUBE_PINNED)");
     if (cfg->envs_per_workgroup != 0 && cfg->envs_per_workgroup != 16 && cfg->envs_per_workgroup != 32 && cfg->envs_per_workgroup != 64)
-        return fail(SO100_E_INVALID, "so100_create: envs_per_workgroup must be 0 (automatic), 16, 32 or 64%s");
+        return fail(SO100_E_INVALID, "so100_create: envs_per_workgroup must be 0 (automatic), 16, 32 or 64");
     if ((cfg->flags & SO100_F_FLOOR) && (cfg->flags & SO100_F_CUBE_PINNED))
-        return fail(SO100_E_INVALID, "so100_create: SO100_F_FLOOR and SO100_F_CUBE_PINNED are mutually exclusive%s");
+        return fail(SO100_E_INVALID, "so100_create: SO100_F_FLOOR and SO100_F_CUBE_PINNED are mutually exclusive");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        return fail(SO100_E_NODEVICE, "so100_create: no HIP device available (this library has no CPU fallback)%s");
-    if (cfg->device < 0 || cfg->device >= ndev) return fail(SO100_E_INVALID, "so100_create: device ordinal out of range%s");
-    DeviceGuard g(cfg->device);
-    if (!g.ok) return fail(SO100_E_NODEVICE, "so100_create: cannot select the device%s");
+        return fail(SO100_E_NODEVICE, "so100_create: no HIP device available (this library has no CPU fallback)");
+    if (cfg->device < 0 || cfg->device >= ndev) return fail(SO100_E_INVALID, "so100_create: device ordinal out of range");
+    SO100_ON_DEVICE(cfg->device, "so100_create");
     so100_sim* s = new (std::nothrow) so100_sim();
-    if (!s) return fail(SO100_E_NOMEM, "so100_create: out of host memory%s");
+    if (!s) return fail(SO100_E_NOMEM, "so100_create: out of host memory");
     s->cfg = *cfg;
-    s->prm.n = cfg->num_envs; s->prm.flags = cfg->flags; s->prm.solver_iters = cfg->solver_iters;
-    s->prm.contact_iters = cfg->contact_iters; s->prm.frame_skip = cfg->frame_skip;
-    s->prm.max_episode_steps = cfg->max_episode_steps;
-    s->prm.seed_lo = (uint32_t)cfg->seed; s->prm.seed_hi = (uint32_t)(cfg->seed >> 32);
-    s->prm.env_id_offset = cfg->env_id_offset;
-    {   // envs per workgroup of the multi-wave kernels.  Their step time is set by the slowest lane of a wave (a cube in a contact
-        // transient, a pad hitting the floor: data-dependent Newton iterations), so a batch that leaves CUs idle is spread thinner:
-        // 16 or 32 envs per 4-wave workgroup while that still fits one workgroup per CU.  Variants without a data-dependent solve
-        // (cube pinned) gain nothing and keep 64.
-        hipDeviceProp_t prop;
-        int cus = 256;
-        if (hipGetDeviceProperties(&prop, cfg->device) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
-        int epw = 64;
-        if (cfg->flags & (SO100_F_FLOOR | SO100_F_PADS_FLOOR | SO100_F_PADS_CUBE | SO100_F_LINKS_FLOOR | SO100_F_LINKS_CUBE))
-            while (epw > 16 && (cfg->num_envs + epw/2 - 1)/(epw/2) <= cus) epw /= 2;
-        // contact disabled (no data-dependent solve): 32 envs per workgroup while that fits the CUs -- the persistent kernel's policy phase then
-        // runs one 32-row MFMA tile per tower instead of two (so100_rollout_fused<K, 8, 4, 32>: half the matrix-core time per step)
-        if (cfg->flags == SO100_F_CUBE_PINNED && (cfg->num_envs + 31)/32 <= cus) epw = 32;
-        if (cfg->envs_per_workgroup != 0) epw = (int)cfg->envs_per_workgroup;             // the caller pins it (validated above)
-        s->prm.epw = epw;
-        s->prm.mw_max = MW_MAX_ENVS;
-        if (const char* ov = getenv("SO100_MW_MAX_ENVS")) { const long v = atol(ov); if (v >= 0) s->prm.mw_max = (int32_t)(v > (1L << 30) ? (1L << 30) : v); }
-    }
-    const size_t bytes = (size_t)SF_COUNT*(size_t)cfg->num_envs*sizeof(float);
-    if (hipMalloc(&s->state, bytes) != hipSuccess) { delete s; return fail(SO100_E_NOMEM, "so100_create: hipMalloc of %s%ld bytes failed", "", (long)bytes); }
-    float tab[36*6];
-    for (int i = 0; i < 36; i++) for (int j = 0; j < 6; j++) tab[6*i + j] = (float)SO100_VALID_START_POSITIONS[i][j];
-    if (hipMalloc(&s->start_tab, sizeof tab) != hipSuccess || hipMemcpy(s->start_tab, tab, sizeof tab, hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(s->state); if (s->start_tab) (void)hipFree(s->start_tab); delete s;
-        return fail(SO100_E_NOMEM, "so100_create: start table upload failed%s");
-    }
-    {   // workgroup load balancing of the persistent rollout kernel (pad-contact variants, batches it serves; SO100_BALANCE=0 turns it off)
-        const char* bal = getenv("SO100_BALANCE");
-        const bool pads = (cfg->flags & (SO100_F_PADS_FLOOR | SO100_F_PADS_CUBE | SO100_F_LINKS_FLOOR | SO100_F_LINKS_CUBE)) != 0;
-        if (pads && cfg->num_envs <= BALANCE_MAX_ENVS && !(bal && atoi(bal) == 0)) {
-            const size_t slots = (size_t)((cfg->num_envs + s->prm.epw - 1)/s->prm.epw)*(size_t)s->prm.epw;
-            if (hipMalloc(&s->slot_env, slots*sizeof(int32_t)) != hipSuccess) {
-                (void)hipFree(s->state); (void)hipFree(s->start_tab); delete s;
-                return fail(SO100_E_NOMEM, "so100_create: hipMalloc of the slot map failed%s");
-            }
-        }
-    }
-    const hipError_t he = DISPATCH_KIND(cfg->env_kind, init)(s->prm.n, s->state);
-    if (he != hipSuccess) { (void)hipFree(s->state); (void)hipFree(s->start_tab); if (s->slot_env) (void)hipFree(s->slot_env); delete s; return fail(SO100_E_LAUNCH, "so100_create: %s (HIP error %ld)", hipGetErrorString(he), (long)he); }
+    const int rc = create_on_device(s);
+    if (rc != 0) { so100_destroy(s); return rc; }
     *out = s;
     return 0;
 }
@@ -166,19 +176,17 @@ void so100_destroy(so100_sim* s) {
 }
 
 int so100_reset(so100_sim* s, const uint8_t* mask_dev, const float* inject_dev, float* obs_dev, void* stream) {
-    if (!s) return fail(SO100_E_INVALID, "so100_reset: null handle%s");
-    DeviceGuard g(s->cfg.device);
-    if (!g.ok) return fail(SO100_E_NODEVICE, "so100_reset: cannot select the device%s");
+    if (!s) return fail(SO100_E_INVALID, "so100_reset: null handle");
+    SO100_ON_DEVICE(s->cfg.device, "so100_reset");
     HIP_TRY(DISPATCH_KIND(s->cfg.env_kind, reset)(s->prm, s->state, s->start_tab, mask_dev, inject_dev, obs_dev, (hipStream_t)stream), SO100_E_LAUNCH);
     return 0;
 }
 
 int so100_step(so100_sim* s, const so100_step_io* io, void* stream) {
-    if (!s || !io) return fail(SO100_E_INVALID, "so100_step: null argument%s");
+    if (!s || !io) return fail(SO100_E_INVALID, "so100_step: null argument");
     if (!io->act_dev || !io->obs_dev || !io->rew_dev || !io->done_dev || !io->trunc_dev)
-        return fail(SO100_E_INVALID, "so100_step: act/obs/rew/done/trunc pointers are required%s");
-    DeviceGuard g(s->cfg.device);
-    if (!g.ok) return fail(SO100_E_NODEVICE, "so100_step: cannot select the device%s");
+        return fail(SO100_E_INVALID, "so100_step: act/obs/rew/done/trunc pointers are required");
+    SO100_ON_DEVICE(s->cfg.device, "so100_step");
     StepPtrs p;
     p.state = s->state; p.start_tab = s->start_tab;
     p.act = io->act_dev; p.obs = io->obs_dev; p.rew = io->rew_dev; p.done = io->done_dev; p.trunc = io->trunc_dev;
@@ -188,36 +196,29 @@ int so100_step(so100_sim* s, const so100_step_io* io, void* stream) {
 }
 
 int so100_policy_forward(so100_sim* s, const so100_policy_weights* w, const so100_policy_io* io, uint32_t step_counter, void* stream) {
-    if (!s || !w || !io) return fail(SO100_E_INVALID, "so100_policy_forward: null argument%s");
-    if (!io->obs_dev || !io->act_env_dev) return fail(SO100_E_INVALID, "so100_policy_forward: obs and act_env pointers are required%s");
-    const float* const* wp = reinterpret_cast<const float* const*>(w);
-    for (int i = 0; i < 13; i++) if (!wp[i]) return fail(SO100_E_INVALID, "so100_policy_forward: null weight pointer%s");
-    DeviceGuard g(s->cfg.device);
-    if (!g.ok) return fail(SO100_E_NODEVICE, "so100_policy_forward: cannot select the device%s");
-    PolicyWeights pw; static_assert(sizeof(PolicyWeights) == sizeof(so100_policy_weights), "layout");
-    memcpy(&pw, w, sizeof pw);
+    if (!s || !w || !io) return fail(SO100_E_INVALID, "so100_policy_forward: null argument");
+    if (!io->obs_dev || !io->act_env_dev) return fail(SO100_E_INVALID, "so100_policy_forward: obs and act_env pointers are required");
+    if (any_null(*w)) return fail(SO100_E_INVALID, "so100_policy_forward: null weight pointer");
+    SO100_ON_DEVICE(s->cfg.device, "so100_policy_forward");
+    PolicyWeights pw; memcpy(&pw, w, sizeof pw);
     PolicyIO pio; pio.obs = io->obs_dev; pio.noise = io->noise_dev; pio.act_env = io->act_env_dev; pio.act_raw = io->act_raw_dev;
     pio.value = io->value_dev; pio.logp = io->logp_dev; pio.rollout_row = io->rollout_row_dev;
     // the matrix-core kernel, grid-stride over tiles of 64 envs, two workgroups per CU resident
     const int ntiles = (s->prm.n + 63)/64;
     const dim3 grid((unsigned)(ntiles < 512 ? ntiles : 512));
-    if (so100_obs_dim(s->cfg.env_kind) == 15)
-        hipLaunchKernelGGL((so100_policy_forward_mfma<15>), grid, dim3(256), 0, (hipStream_t)stream, s->prm.n, pw, pio, s->prm.seed_lo, s->prm.seed_hi, s->prm.env_id_offset, step_counter);
-    else
-        hipLaunchKernelGGL((so100_policy_forward_mfma<8>), grid, dim3(256), 0, (hipStream_t)stream, s->prm.n, pw, pio, s->prm.seed_lo, s->prm.seed_hi, s->prm.env_id_offset, step_counter);
+    SO100_WITH_OBS_DIM(so100_obs_dim(s->cfg.env_kind),
+        hipLaunchKernelGGL((so100_policy_forward_mfma<OD>), grid, dim3(256), 0, (hipStream_t)stream, s->prm.n, pw, pio, s->prm.seed_lo, s->prm.seed_hi, s->prm.env_id_offset, step_counter););
     HIP_TRY(hipGetLastError(), SO100_E_LAUNCH);
     return 0;
 }
 
 int so100_rollout(so100_sim* s, const so100_policy_weights* w, const so100_rollout_io* io, int32_t T, uint32_t step_counter0, void* stream) {
-    if (!s || !w || !io) return fail(SO100_E_INVALID, "so100_rollout: null argument%s");
-    if (T < 1) return fail(SO100_E_INVALID, "so100_rollout: T must be >= 1%s");
+    if (!s || !w || !io) return fail(SO100_E_INVALID, "so100_rollout: null argument");
+    if (T < 1) return fail(SO100_E_INVALID, "so100_rollout: T must be >= 1");
     if (!io->rollout_dev || !io->obs_dev || !io->rew_dev || !io->done_dev || !io->trunc_dev)
-        return fail(SO100_E_INVALID, "so100_rollout: rollout/obs/rew/done/trunc pointers are required%s");
-    const float* const* wp = reinterpret_cast<const float* const*>(w);
-    for (int i = 0; i < 13; i++) if (!wp[i]) return fail(SO100_E_INVALID, "so100_rollout: null weight pointer%s");
-    DeviceGuard g(s->cfg.device);
-    if (!g.ok) return fail(SO100_E_NODEVICE, "so100_rollout: cannot select the device%s");
+        return fail(SO100_E_INVALID, "so100_rollout: rollout/obs/rew/done/trunc pointers are required");
+    if (any_null(*w)) return fail(SO100_E_INVALID, "so100_rollout: null weight pointer");
+    SO100_ON_DEVICE(s->cfg.device, "so100_rollout");
     PolicyWeights pw; memcpy(&pw, w, sizeof pw);
     RolloutArgs ra; ra.buf = io->rollout_dev; ra.T = T; ra.step_counter0 = step_counter0; ra.obs_in = io->obs_dev; ra.tobs_chunk = io->terminal_obs_chunk_dev;
     ra.slot_env = s->slot_env;
@@ -233,18 +234,18 @@ int so100_rollout(so100_sim* s, const so100_policy_weights* w, const so100_rollo
 }
 
 int so100_render(so100_sim* s, const so100_render_io* io, void* stream) {
-    if (!s || !io) return fail(SO100_E_INVALID, "so100_render: null argument%s");
+    if (!s || !io) return fail(SO100_E_INVALID, "so100_render: null argument");
     if (io->camera != SO100_CAM_END && io->camera != SO100_CAM_SCENE)
-        return fail(SO100_E_INVALID, "so100_render: camera must be SO100_CAM_END (0) or SO100_CAM_SCENE (1), got %s%ld", "", (long)io->camera);
-    if (io->width < 1 || io->width > 4096) return fail(SO100_E_INVALID, "so100_render: width must be in 1..4096, got %s%ld", "", (long)io->width);
-    if (io->height < 1 || io->height > 4096) return fail(SO100_E_INVALID, "so100_render: height must be in 1..4096, got %s%ld", "", (long)io->height);
-    if (io->env_begin < 0 || io->env_begin >= s->prm.n) return fail(SO100_E_INVALID, "so100_render: env_begin must be in [0, N), got %s%ld", "", (long)io->env_begin);
+        return fail(SO100_E_INVALID, "so100_render: camera must be SO100_CAM_END (0) or SO100_CAM_SCENE (1), got %ld", (long)io->camera);
+    if (io->width < 1 || io->width > 4096) return fail(SO100_E_INVALID, "so100_render: width must be in 1..4096, got %ld", (long)io->width);
+    if (io->height < 1 || io->height > 4096) return fail(SO100_E_INVALID, "so100_render: height must be in 1..4096, got %ld", (long)io->height);
+    if (io->env_begin < 0 || io->env_begin >= s->prm.n) return fail(SO100_E_INVALID, "so100_render: env_begin must be in [0, N), got %ld", (long)io->env_begin);
     if (io->env_count < 1 || io->env_count > s->prm.n - io->env_begin)
-        return fail(SO100_E_INVALID, "so100_render: env_count must be >= 1 with env_begin + env_count <= N, got %s%ld", "", (long)io->env_count);
+        return fail(SO100_E_INVALID, "so100_render: env_count must be >= 1 with env_begin + env_count <= N, got %ld", (long)io->env_count);
     if (io->geom_mask & ~(SO100_GEOM_FLOOR | SO100_GEOM_CUBE | SO100_GEOM_LINKS | SO100_GEOM_PADS))
-        return fail(SO100_E_INVALID, "so100_render: geom_mask has unknown bits (%s%ld)", "", (long)io->geom_mask);
-    if (!io->rgb_dev && !io->depth_dev && !io->seg_dev) return fail(SO100_E_INVALID, "so100_render: rgb_dev, depth_dev and seg_dev are all NULL%s");
-    if (io->free_cam && io->camera != SO100_CAM_SCENE) return fail(SO100_E_INVALID, "so100_render: free_cam is for the scene camera only%s");
+        return fail(SO100_E_INVALID, "so100_render: geom_mask has unknown bits (%ld)", (long)io->geom_mask);
+    if (!io->rgb_dev && !io->depth_dev && !io->seg_dev) return fail(SO100_E_INVALID, "so100_render: rgb_dev, depth_dev and seg_dev are all NULL");
+    if (io->free_cam && io->camera != SO100_CAM_SCENE) return fail(SO100_E_INVALID, "so100_render: free_cam is for the scene camera only");
     RenderLaunch L;
     L.camera = io->camera; L.W = io->width; L.H = io->height; L.begin = io->env_begin; L.count = io->env_count; L.n = s->prm.n;
     L.mask = io->geom_mask != 0 ? io->geom_mask : (io->camera == SO100_CAM_END ? RG_DEFAULT_END : RG_DEFAULT_SCENE);
@@ -256,9 +257,9 @@ int so100_render(so100_sim* s, const so100_render_io* io, void* stream) {
         double dist = RENDER_SCENE_DISTANCE, az = RENDER_SCENE_AZIMUTH, el = RENDER_SCENE_ELEVATION;
         fovy = RENDER_SCENE_FOVY;
         if (const float* fc = io->free_cam) {
-            for (int i = 0; i < 7; i++) if (!std::isfinite(fc[i])) return fail(SO100_E_INVALID, "so100_render: free_cam[%s%ld] is not finite", "", (long)i);
-            if (!(fc[3] > 0.0f)) return fail(SO100_E_INVALID, "so100_render: free_cam distance must be > 0%s");
-            if (!(fc[6] > 0.0f && fc[6] < 180.0f)) return fail(SO100_E_INVALID, "so100_render: free_cam fovy_deg must be in (0, 180)%s");
+            for (int i = 0; i < 7; i++) if (!std::isfinite(fc[i])) return fail(SO100_E_INVALID, "so100_render: free_cam[%ld] is not finite", (long)i);
+            if (!(fc[3] > 0.0f)) return fail(SO100_E_INVALID, "so100_render: free_cam distance must be > 0");
+            if (!(fc[6] > 0.0f && fc[6] < 180.0f)) return fail(SO100_E_INVALID, "so100_render: free_cam fovy_deg must be in (0, 180)");
             lookat[0] = fc[0]; lookat[1] = fc[1]; lookat[2] = fc[2]; dist = fc[3]; az = fc[4]; el = fc[5]; fovy = fc[6];
         }
         double p[3], R[9];
@@ -267,13 +268,12 @@ int so100_render(so100_sim* s, const so100_render_io* io, void* stream) {
         for (int i = 0; i < 9; i++) L.cam_R[i] = (float)R[i];
     }
     L.inv_f = (float)render_inv_focal(fovy, io->height);
-    DeviceGuard g(s->cfg.device);
-    if (!g.ok) return fail(SO100_E_NODEVICE, "so100_render: cannot select the device%s");
+    SO100_ON_DEVICE(s->cfg.device, "so100_render");
     if (io->env_count > s->render_scene_envs) {
         if (s->render_scene) { HIP_TRY(hipStreamSynchronize((hipStream_t)stream), SO100_E_LAUNCH); (void)hipFree(s->render_scene); s->render_scene = nullptr; }
         s->render_scene_envs = 0;
         const size_t bytes = (size_t)io->env_count*RS_STRIDE*sizeof(float);
-        if (hipMalloc(&s->render_scene, bytes) != hipSuccess) { s->render_scene = nullptr; return fail(SO100_E_NOMEM, "so100_render: hipMalloc of %s%ld bytes failed", "", (long)bytes); }
+        if (hipMalloc(&s->render_scene, bytes) != hipSuccess) { s->render_scene = nullptr; return fail(SO100_E_NOMEM, "so100_render: hipMalloc of %ld bytes failed", (long)bytes); }
         s->render_scene_envs = io->env_count;
     }
     HIP_TRY(render_launch(s->state, L, s->render_scene, io->rgb_dev, io->depth_dev, io->seg_dev, (hipStream_t)stream), SO100_E_LAUNCH);
@@ -281,39 +281,20 @@ int so100_render(so100_sim* s, const so100_render_io* io, void* stream) {
 }
 
 int so100_get_state(so100_sim* s, float* qpos_dev, float* qvel_dev, void* stream) {
-    if (!s || !qpos_dev || !qvel_dev) return fail(SO100_E_INVALID, "so100_get_state: null argument%s");
-    DeviceGuard g(s->cfg.device);
-    if (!g.ok) return fail(SO100_E_NODEVICE, "so100_get_state: cannot select the device%s");
-    const size_t n = (size_t)s->prm.n;
-    HIP_TRY(hipMemcpyAsync(qpos_dev, s->state + (size_t)SF_QPOS0*n, 13*n*sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream), SO100_E_LAUNCH);
-    HIP_TRY(hipMemcpyAsync(qvel_dev, s->state + (size_t)SF_QVEL0*n, 12*n*sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream), SO100_E_LAUNCH);
-    return 0;
+    if (!s || !qpos_dev || !qvel_dev) return fail(SO100_E_INVALID, "so100_get_state: null argument");
+    return move_rows(s, "so100_get_state", false, { { SF_QPOS0, 13, qpos_dev }, { SF_QVEL0, 12, qvel_dev } }, stream);
 }
 int so100_set_state(so100_sim* s, const float* qpos_dev, const float* qvel_dev, void* stream) {
-    if (!s || !qpos_dev || !qvel_dev) return fail(SO100_E_INVALID, "so100_set_state: null argument%s");
-    DeviceGuard g(s->cfg.device);
-    if (!g.ok) return fail(SO100_E_NODEVICE, "so100_set_state: cannot select the device%s");
-    const size_t n = (size_t)s->prm.n;
-    HIP_TRY(hipMemcpyAsync(s->state + (size_t)SF_QPOS0*n, qpos_dev, 13*n*sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream), SO100_E_LAUNCH);
-    HIP_TRY(hipMemcpyAsync(s->state + (size_t)SF_QVEL0*n, qvel_dev, 12*n*sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream), SO100_E_LAUNCH);
-    HIP_TRY(hipMemsetAsync(s->state + (size_t)SF_qc0*n, 0, 6*n*sizeof(float), (hipStream_t)stream), SO100_E_LAUNCH);   // new q: drop the compensation
-    return 0;
+    if (!s || !qpos_dev || !qvel_dev) return fail(SO100_E_INVALID, "so100_set_state: null argument");
+    return move_rows(s, "so100_set_state", true, { { SF_QPOS0, 13, qpos_dev }, { SF_QVEL0, 12, qvel_dev }, { SF_qc0, 6, nullptr } }, stream);   // new q: drop the compensation
 }
 int so100_get_field(so100_sim* s, int32_t field, void* out_dev, void* stream) {
-    if (!s || !out_dev || field < 0 || field >= SF_COUNT) return fail(SO100_E_INVALID, "so100_get_field: bad argument%s");
-    DeviceGuard g(s->cfg.device);
-    if (!g.ok) return fail(SO100_E_NODEVICE, "so100_get_field: cannot select the device%s");
-    const size_t n = (size_t)s->prm.n;
-    HIP_TRY(hipMemcpyAsync(out_dev, s->state + (size_t)field*n, n*sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream), SO100_E_LAUNCH);
-    return 0;
+    if (!s || !out_dev || field < 0 || field >= SF_COUNT) return fail(SO100_E_INVALID, "so100_get_field: bad argument");
+    return move_rows(s, "so100_get_field", false, { { field, 1, out_dev } }, stream);
 }
 int so100_set_field(so100_sim* s, int32_t field, const void* in_dev, void* stream) {
-    if (!s || !in_dev || field < 0 || field >= SF_COUNT) return fail(SO100_E_INVALID, "so100_set_field: bad argument%s");
-    DeviceGuard g(s->cfg.device);
-    if (!g.ok) return fail(SO100_E_NODEVICE, "so100_set_field: cannot select the device%s");
-    const size_t n = (size_t)s->prm.n;
-    HIP_TRY(hipMemcpyAsync(s->state + (size_t)field*n, in_dev, n*sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream), SO100_E_LAUNCH);
-    return 0;
+    if (!s || !in_dev || field < 0 || field >= SF_COUNT) return fail(SO100_E_INVALID, "so100_set_field: bad argument");
+    return move_rows(s, "so100_set_field", true, { { field, 1, in_dev } }, stream);
 }
 
 }  // extern "C"

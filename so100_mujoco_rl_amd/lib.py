@@ -59,6 +59,14 @@ class PolicyWeights(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in POLICY_TENSORS]
 
 
+def policy_tensor_shapes(obs_dim):
+    """{name: PyTorch shape} of the policy's tensors (csrc/so100_policy_tensors.h: nn.Linear layout, 2 x 64 towers, 6 actions)"""
+    tower = lambda p: {p + "_w0": (64, obs_dim), p + "_b0": (64,), p + "_w1": (64, 64), p + "_b1": (64,)}
+    shapes = {**tower("pi"), "mu_w": (6, 64), "mu_b": (6,), "log_std": (6,), **tower("vf"), "v_w": (1, 64), "v_b": (1,)}
+    assert list(shapes) == POLICY_TENSORS
+    return shapes
+
+
 class RolloutIO(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("rollout_dev", "obs_dev", "rew_dev", "done_dev", "trunc_dev", "terminal_obs_dev",
                                           "ep_return_dev", "ep_length_dev", "terminal_obs_chunk_dev")]
@@ -179,25 +187,58 @@ def _ptr(t, dtype, shape, device):
     return t.data_ptr()
 
 
-class So100Sim:
+def _resolve_device(device, what, hip_only=False):
+    """the torch.device (with its ordinal) a handle lives on: `device`, or torch's current HIP device where it names none"""
+    if not torch.cuda.is_available():
+        raise So100Error(f"no HIP device visible to PyTorch: {what} has no CPU fallback")
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if hip_only and device.type != "cuda":
+        raise So100Error(f"{what} runs on a HIP device, not on {device}")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    return device
+
+
+class _Handle:
+    """What the two handle classes share: the library, the device, the configuration struct, the native handle made by `create(cfg, &h)`
+    and freed by `destroy(h)` on close() or collection, and torch's current stream on the device."""
+    _create = _destroy = None        # export names
+
+    def _open(self, device, cfg):
+        self.L = load()
+        self.device, self.cfg = device, cfg
+        h = C.c_void_p()
+        _check(getattr(self.L, self._create)(C.byref(cfg), C.byref(h)), self._create)
+        self.h = h
+
+    def _stream(self):
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def close(self):
+        if getattr(self, "h", None):
+            getattr(self.L, self._destroy)(self.h)
+            self.h = None
+
+    __del__ = close
+
+
+def _refreshed(name):
+    """a device tensor of So100Sim that step_host() may have left stale: brought up to date on its first read"""
+    return property(lambda self: (self._refresh(), getattr(self, name))[1])
+
+
+class So100Sim(_Handle):
     """One batched simulator handle on one GPU (one per process per device)."""
+    _create, _destroy = "so100_create", "so100_destroy"
 
     def __init__(self, env_kind, num_envs, device=None, flags=F_REFERENCE, solver_iters=2, contact_iters=20,
                  frame_skip=16, max_episode_steps=None, seed=0, env_id_offset=0, envs_per_workgroup=0):
-        self.L = load()
-        if not torch.cuda.is_available():
-            raise So100Error("no HIP device visible to PyTorch: so100 has no CPU fallback")
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        device = _resolve_device(device, "so100")
         if max_episode_steps is None:
             max_episode_steps = 4000 if env_kind == ENV01 else 6000       # ref: so100_mujoco_rl/__init__.py:5-45
-        self.cfg = Config(env_kind, num_envs, self.device.index, flags, solver_iters, contact_iters, frame_skip,
-                          max_episode_steps, seed, env_id_offset, envs_per_workgroup)
-        h = C.c_void_p()
-        _check(self.L.so100_create(C.byref(self.cfg), C.byref(h)), "so100_create")
-        self.h = h
-        self.envs_per_workgroup = self.L.so100_envs_per_workgroup(h)     # in use (chosen by the library when 0 was passed): part of a checkpoint's configuration
+        self._open(device, Config(env_kind, num_envs, device.index, flags, solver_iters, contact_iters, frame_skip,
+                                  max_episode_steps, seed, env_id_offset, envs_per_workgroup))
+        self.envs_per_workgroup = self.L.so100_envs_per_workgroup(self.h)     # in use (chosen by the library when 0 was passed): part of a checkpoint's configuration
         self.n = num_envs
         self.kind = env_kind
         self.obs_dim = self.L.so100_obs_dim(env_kind)
@@ -226,23 +267,8 @@ class So100Sim:
                 if src is not None:
                     dst.copy_(src, non_blocking=True)
 
-    obs = property(lambda self: (self._refresh(), self._obs)[1])
-    rew = property(lambda self: (self._refresh(), self._rew)[1])
-    done = property(lambda self: (self._refresh(), self._done)[1])
-    trunc = property(lambda self: (self._refresh(), self._trunc)[1])
-    terminal_obs = property(lambda self: (self._refresh(), self._terminal_obs)[1])
-    ep_return = property(lambda self: (self._refresh(), self._ep_return)[1])
-    ep_length = property(lambda self: (self._refresh(), self._ep_length)[1])
-
-    def _stream(self):
-        return torch.cuda.current_stream(self.device).cuda_stream
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.so100_destroy(self.h)
-            self.h = None
-
-    __del__ = close
+    obs, rew, done, trunc, terminal_obs, ep_return, ep_length = (
+        _refreshed(n) for n in ("_obs", "_rew", "_done", "_trunc", "_terminal_obs", "_ep_return", "_ep_length"))
 
     def reset(self, mask=None, inject=None):
         """Reset all envs (mask None) or those with mask != 0.  Returns the (persistent) obs tensor."""
@@ -281,9 +307,7 @@ class So100Sim:
 
     def set_policy(self, tensors):
         """tensors: dict name -> float32 device tensor (names: POLICY_TENSORS; SB3 keys: SB3_STATE_DICT_KEYS)."""
-        od = self.obs_dim
-        shapes = {"pi_w0": (64, od), "pi_b0": (64,), "pi_w1": (64, 64), "pi_b1": (64,), "mu_w": (6, 64), "mu_b": (6,), "log_std": (6,),
-                  "vf_w0": (64, od), "vf_b0": (64,), "vf_w1": (64, 64), "vf_b1": (64,), "v_w": (1, 64), "v_b": (1,)}
+        shapes = policy_tensor_shapes(self.obs_dim)
         self._policy_tensors = {k: tensors[k] for k in POLICY_TENSORS}          # keep them alive
         self._pw = PolicyWeights(*[_ptr(tensors[k], torch.float32, shapes[k], self.device) for k in POLICY_TENSORS])
         self._pio = PolicyIO()
@@ -461,42 +485,21 @@ def learner_layout(obs_dim):
     n = L.so100_learner_num_params(obs_dim)
     if n < 0:
         raise So100Error(f"the learner's network takes obs_dim 15 or 8, got {obs_dim}")
-    shapes = {"pi_w0": (64, obs_dim), "pi_b0": (64,), "pi_w1": (64, 64), "pi_b1": (64,), "mu_w": (6, 64), "mu_b": (6,), "log_std": (6,),
-              "vf_w0": (64, obs_dim), "vf_b0": (64,), "vf_w1": (64, 64), "vf_b1": (64,), "v_w": (1, 64), "v_b": (1,)}
-    return {k: (L.so100_learner_param_offset(obs_dim, k.encode()), shapes[k]) for k in POLICY_TENSORS}, n
+    return {k: (L.so100_learner_param_offset(obs_dim, k.encode()), shape) for k, shape in policy_tensor_shapes(obs_dim).items()}, n
 
 
-class So100Learner:
+class So100Learner(_Handle):
     """One handle of the on-device PPO learner (include/so100_learn.h): advantages and minibatch steps as raw launches on torch's CURRENT
     stream -- the stream So100Sim's launches go to, so a rollout that follows an update is ordered behind it.  The caller owns every
     tensor (parameters, Adam moments, buffers); the handle owns its partial-gradient scratch."""
+    _create, _destroy = "so100_learner_create", "so100_learner_destroy"
 
     def __init__(self, obs_dim, device=None, max_minibatch=32768, gamma=0.99, gae_lambda=0.95, clip_range=0.2, vf_coef=0.5, max_grad_norm=0.5,
                  lr=3e-4, beta1=0.9, beta2=0.999, adam_eps=1e-5):
-        self.L = load()
-        if not torch.cuda.is_available():
-            raise So100Error("no HIP device visible to PyTorch: the so100 learner has no CPU fallback")
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        if self.device.type != "cuda":
-            raise So100Error(f"the so100 learner runs on a HIP device, not on {self.device}")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        self.cfg = LearnerConfig(obs_dim, self.device.index, max_minibatch, gamma, gae_lambda, clip_range, vf_coef, max_grad_norm, lr, beta1, beta2, adam_eps)
-        h = C.c_void_p()
-        _check(self.L.so100_learner_create(C.byref(self.cfg), C.byref(h)), "so100_learner_create")
-        self.h = h
+        device = _resolve_device(device, "the so100 learner", hip_only=True)
+        self._open(device, LearnerConfig(obs_dim, device.index, max_minibatch, gamma, gae_lambda, clip_range, vf_coef, max_grad_norm, lr, beta1, beta2, adam_eps))
         self.obs_dim = obs_dim
         self.num_params = self.L.so100_learner_num_params(obs_dim)
-
-    def _stream(self):
-        return torch.cuda.current_stream(self.device).cuda_stream
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.so100_learner_destroy(self.h)
-            self.h = None
-
-    __del__ = close
 
     def advantages(self, rollout, last_obs, params, adv, ret, adv_stats, terminal_obs=None):
         """rollout: float32 [T, N, obs_dim+10] packed chunk (read only); terminal_obs: [T, N, obs_dim] or None (no TimeLimit bootstrap);

@@ -1,26 +1,14 @@
 """Cycle accounting of the persistent rollout kernel's phases (waves 0-3 of workgroup 0).
 Build the instrumented side library HERE (no GPU needed), then run on the GPU box:
     python tools/rollout_prof.py build
-    gpurun -- python tools/rollout_prof.py [free|arm|nopads|ref|c5] [random|resting|held]
+    python tools/rollout_prof.py [free|arm|nopads|ref|c5] [random|resting|held]
 The product library is untouched (the instrumentation is compiled out without -DSO100_ROLLOUT_PROF)."""
-import ctypes as C, os, subprocess, sys
+import ctypes as C, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIDE = os.path.join(ROOT, "so100_mujoco_rl_amd", "libso100sim_prof.so")
 if len(sys.argv) > 1 and sys.argv[1] == "build":
-    import torch
-    from concurrent.futures import ThreadPoolExecutor
-    tl = os.path.join(os.path.dirname(torch.__file__), "lib")
-    csrc = os.path.join(ROOT, "so100_mujoco_rl_amd", "csrc")
-    odir = os.path.join(ROOT, "gpurun_out", "prof_obj"); os.makedirs(odir, exist_ok=True)
-    base = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-fno-gpu-rdc", "-ffp-contract=fast",
-            "-fno-slp-vectorize", "-Wno-unused-function", "-DSO100_ROLLOUT_PROF", "-c"]
-    jobs = [(base + ["-o", os.path.join(odir, "sim.o"), os.path.join(csrc, "so100_sim.hip")])]
-    jobs += [(base + [f"-DSO100_KIND={k}", "-o", os.path.join(odir, f"kind{k}.o"), os.path.join(csrc, "so100_kind.hip")]) for k in range(1, 7)]
-    with ThreadPoolExecutor(7) as ex:
-        list(ex.map(subprocess.check_call, jobs))
-    objs = [os.path.join(odir, "sim.o")] + [os.path.join(odir, f"kind{k}.o") for k in range(1, 7)]
-    subprocess.check_call(["g++", "-shared", "-o", SIDE] + objs + ["-L" + tl, "-lamdhip64", "-Wl,-rpath," + tl, "-Wl,-rpath,/opt/rocm/lib", "-lstdc++", "-lm"])
-    print("built", SIDE); sys.exit(0)
+    import subprocess
+    sys.exit(subprocess.call([sys.executable, os.path.join(ROOT, "tools", "side_build.py"), "prof", "-DSO100_ROLLOUT_PROF"]))    # -> SIDE
 os.environ["SO100_LIB"] = SIDE
 sys.path.insert(0, ROOT)
 import torch
