@@ -62,7 +62,8 @@ typedef struct {
 
 /* One PPO gradient step on the samples idx_dev names (PPO._step + clip_grad_norm_ + Adam.step):
  *   A = (adv - mean)/(std + 1e-8);  logp = sum(-((a - mu)/sigma)^2/2 - log sigma - log(2 pi)/2);  ratio = exp(logp - logp_old)
- *   L = -mean(min(ratio A, clamp(ratio, 1-c, 1+c) A)) + vf_coef mean((ret - V)^2)          (no entropy term, no value clipping)
+ *   L = -mean(min(ratio A, clamp(ratio, 1-c, 1+c) A)) + vf_coef mean((ret - V)^2)          (no entropy term, no value clipping:
+ *                                                                                             so100_learner_minibatch_step_ex has them)
  *   g *= min(1, max_grad_norm/(|g|_2 + 1e-6)) over all 13 tensors;  bias-corrected Adam.
  * Observation, raw action and old log-prob are read in place from the packed chunk through idx. */
 typedef struct {
@@ -81,6 +82,29 @@ typedef struct {
     float*         grads_dev;      /* [P] out, nullable: the reduced gradient times the clip coefficient (what Adam consumed)    */
 } so100_minibatch_io;
 
+/* The terms of SB3's PPO loss that so100_learner_minibatch_step leaves out, for so100_learner_minibatch_step_ex.  Per minibatch:
+ *   A            normalize_advantage 0: (adv - mean_chunk)/(std_chunk + 1e-8) from adv_stats_dev, as above
+ *                normalize_advantage 1: (adv - mean)/(std + 1e-8), mean and unbiased std over this minibatch's valid rows (a launch of its
+ *                own into scratch the handle owns); with at most one valid row adv is used as it is
+ *   V_pred       V, or old_V + clamp(V - old_V, -clip_range_vf, +clip_range_vf) with old_V the row's value column; the gradient passes on
+ *                the closed interval and not outside it (torch.clamp); value_loss = mean((ret - V_pred)^2)
+ *   entropy_loss -mean(entropy), entropy = sum_i log_std_i + 6 (0.5 + 0.5 ln 2 pi); its only gradient is -ent_coef on each log_std_i
+ *   L            policy_loss + ent_coef entropy_loss + vf_coef value_loss
+ *   approx_kl    mean((ratio - 1) - (logp - logp_old)), with the parameters before this step
+ * Means are sums over the valid rows divided by mb, as in so100_learner_minibatch_step.
+ * KL stop.  With target_kl > 0 the caller owns an update-state pair int32 {stopped, steps_applied} on the device and zeroes it at the start
+ * of an update.  Every kernel of the step reads `stopped` first and does nothing when it is set.  If approx_kl > 1.5 target_kl the step is
+ * not applied (parameters, moments and grads_dev untouched), `stopped` is set and diag holds the stopping minibatch's values; otherwise
+ * the step is applied and steps_applied is incremented.  No step after the stop is applied, so the applied steps carry the contiguous
+ * adam_step numbers 1..steps_applied the host passed, and nothing synchronises in the middle of an update. */
+typedef struct {
+    float   ent_coef;             /* >= 0; 0: no entropy bonus                                                   */
+    float   clip_range_vf;        /* <= 0: no value clipping                                                     */
+    int32_t normalize_advantage;  /* 0 batch (adv_stats_dev), 1 minibatch                                        */
+    float   target_kl;            /* <= 0: no stop                                                               */
+    double  lr;                   /* this step's learning rate (a schedule, evaluated by the caller); < 0: the handle's */
+} so100_ppo_terms;
+
 int  so100_learner_num_params(int32_t obs_dim);                          /* 10829 (obs_dim 15), 9933 (8); < 0 otherwise */
 int  so100_learner_param_offset(int32_t obs_dim, const char* name);      /* name: a member of so100_policy_weights; < 0 if unknown */
 int  so100_learner_param_size(int32_t obs_dim, const char* name);        /* elements of that tensor                      */
@@ -88,6 +112,18 @@ int  so100_learner_create(const so100_learner_config* cfg, so100_learner** out);
 void so100_learner_destroy(so100_learner* learner);
 int  so100_learner_advantages(so100_learner* learner, const so100_advantages_io* io, int32_t T, int32_t N, void* hip_stream);
 int  so100_learner_minibatch_step(so100_learner* learner, const so100_minibatch_io* io, void* hip_stream);
+/* so100_learner_minibatch_step with the terms above (one more launch when normalize_advantage is 1).  io->stats_dev is not used.
+ * diag_dev [8] out: policy loss, value loss, clip fraction, pre-clip gradient norm (these four as stats_dev), approx_kl, entropy_loss,
+ * total loss, value-clip fraction (|V - old_V| > clip_range_vf).  update_state_dev [2]: see above; nullable when target_kl is off (when
+ * given it is honoured and counted all the same).  With every term off (ent_coef 0, clip_range_vf <= 0, normalize_advantage 0,
+ * target_kl <= 0, lr < 0) parameters, moments, grads and the first four diagnostics equal so100_learner_minibatch_step's to the bit. */
+int  so100_learner_minibatch_step_ex(so100_learner* learner, const so100_minibatch_io* io, const so100_ppo_terms* terms, float* diag_dev,
+                                     int32_t* update_state_dev, void* hip_stream);
+/* out_dev [1] = 1 - var(ret - old_V)/var(ret) over the chunk's num_samples rows (population variances; old_V is the value column of
+ * rollout_dev, row stride obs_dim+10); NaN when var(ret) == 0, i.e. when every ret equals the first.  num_samples <= 2^24.
+ * SB3's explained_variance. */
+int  so100_learner_explained_variance(so100_learner* learner, const float* rollout_dev, const float* ret_dev, int64_t num_samples, float* out_dev,
+                                      void* hip_stream);
 
 #ifdef __cplusplus
 }

@@ -1,5 +1,6 @@
 // so100_learn.hip -- the on-device PPO learner behind include/so100_learn.h: advantages (three launches) and one minibatch gradient
-// step (three launches), for the fixed 2 x 64 tanh towers of so100_policy.hpp.  The per-sample and per-parameter arithmetic is in
+// step (three launches; the extended step with SB3's remaining loss terms and the KL stop is the same three plus, under per-minibatch
+// normalisation, one for the minibatch's advantage statistics), for the fixed 2 x 64 tanh towers of so100_policy.hpp.  The per-sample and per-parameter arithmetic is in
 // so100_learn.hpp (host-compilable templates, held to an fp64 reference by tests/_learncheck); this file holds the data movement.
 //
 // Gradient kernel (so100_learn_grad): a bounded persistent grid of 256-thread workgroups; each owns tiles of 64 samples gathered
@@ -34,6 +35,7 @@ constexpr int LLD = 68;                // row stride (words) of the [sample][uni
 constexpr int XLD = 17, DOLD = 13, HPLD = 7;      // odd strides of the small images (scalar accesses, lane = sample)
 constexpr int GRID_MAX = 256;          // workgroups of the gradient kernel = partials to reduce (one per CU of an MI355X)
 constexpr int NSTAT = 3;               // sums riding behind a partial's P gradients: policy loss, value loss, clipped count
+constexpr int NSTAT_EX = 6;            // the extended step's partials: the three above in their places, then approx_kl, value-clipped count, entropy
 constexpr int ADV_THREADS = 1024;
 
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
@@ -45,15 +47,25 @@ struct GradArgs {
     float clip, vf_coef;
 };
 
+// the extended step (so100_learner_minibatch_step_ex): the old arguments first, so that tower_pass reads them under the same names
+struct GradArgsEx : GradArgs {
+    float ent_coef, clip_vf;           // clip_vf <= 0: no value clipping
+    const int32_t* state;              // the caller's {stopped, steps_applied}, nullable
+};
+
+template <bool EX> struct HeadOf { using type = LossHead<float>; };
+template <> struct HeadOf<true> { using type = LossHeadEx<float>; };
+
 struct GradSmem {
     alignas(16) float H1[LT*LLD], H2[LT*LLD], D2[LT*LLD], D1[LT*LLD];
     float X[LT*XLD], DO[LT*DOLD], HP[4*LT*HPLD];
 };
 
 // one tower's forward and backward pass over this workgroup's tiles; writes the tower's slice of the workgroup's partial
-template <int OD, int TW>
-__device__ __forceinline__ void tower_pass(const GradArgs& A, GradSmem& S) {
-    constexpr int ROW = OD + ROW_EXTRA, NH = TW ? 1 : ACT_DIM, P = num_params(OD);
+// EX selects the extended loss head (entropy bonus, value clipping, approx_kl) and its NSTAT_EX sums; without it the pass is the old one
+template <int OD, int TW, bool EX, class Args>
+__device__ __forceinline__ void tower_pass(const Args& A, GradSmem& S) {
+    constexpr int ROW = OD + ROW_EXTRA, NH = TW ? 1 : ACT_DIM, P = num_params(OD), NS = EX ? NSTAT_EX : NSTAT;
     constexpr int oW0 = tensor_offset(TW ? T_vf_w0 : T_pi_w0, OD), oB0 = tensor_offset(TW ? T_vf_b0 : T_pi_b0, OD);
     constexpr int oW1 = tensor_offset(TW ? T_vf_w1 : T_pi_w1, OD), oB1 = tensor_offset(TW ? T_vf_b1 : T_pi_b1, OD);
     constexpr int oWH = tensor_offset(TW ? T_v_w : T_mu_w, OD), oBH = tensor_offset(TW ? T_v_b : T_mu_b, OD), oLS = tensor_offset(T_log_std, OD);
@@ -74,6 +86,7 @@ __device__ __forceinline__ void tower_pass(const GradArgs& A, GradSmem& S) {
 #pragma unroll
     for (int i = 0; i < 4; i++) gW0[i] = gB1[i] = gB0[i] = gWh[i] = 0.0f;
     float s_loss = 0.0f, s_clip = 0.0f;                                     // wave 0, lane = sample: sums over this lane's samples
+    [[maybe_unused]] float s_kl = 0.0f, s_ent = 0.0f;                       // EX, policy tower: approx_kl and entropy
     const int ntiles = (A.mb + LT - 1)/LT;
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const int sm = tile*LT + lane;
@@ -131,14 +144,19 @@ __device__ __forceinline__ void tower_pass(const GradArgs& A, GradSmem& S) {
 #pragma unroll
         for (int i = 0; i < NH; i++)
             out[i] = (((BH[i] + S.HP[(0*LT + lane)*HPLD + i]) + S.HP[(1*LT + lane)*HPLD + i]) + S.HP[(2*LT + lane)*HPLD + i]) + S.HP[(3*LT + lane)*HPLD + i];
-        LossHead<float> L;
+        typename HeadOf<EX>::type L;
         if constexpr (TW == 0) {
             float a[ACT_DIM], ls[ACT_DIM];
 #pragma unroll
             for (int i = 0; i < ACT_DIM; i++) { a[i] = valid ? r[OD + ROW_ACT + i] : 0.0f; ls[i] = prm[oLS + i]; }
             const float logp_old = valid ? r[OD + ROW_LOGP] : 0.0f;
             const float adv_n = valid ? (A.adv[row] - a_mean)*a_scale : 0.0f;
-            policy_loss_head<float>(out, ls, a, logp_old, adv_n, A.clip, inv_mb, L);
+            if constexpr (EX) {
+                policy_loss_head_ex<float>(out, ls, a, logp_old, adv_n, A.clip, A.ent_coef, inv_mb, L);
+                s_kl += valid ? L.approx_kl : 0.0f; s_ent += valid ? L.entropy : 0.0f;
+            } else {
+                policy_loss_head<float>(out, ls, a, logp_old, adv_n, A.clip, inv_mb, L);
+            }
 #pragma unroll
             for (int i = 0; i < ACT_DIM; i++) { dout[i] = valid ? L.dmu[i] : 0.0f; L.dlog_std[i] = valid ? L.dlog_std[i] : 0.0f; }
             s_loss += valid ? L.pg_loss : 0.0f; s_clip += valid ? L.clipped : 0.0f;
@@ -148,7 +166,12 @@ __device__ __forceinline__ void tower_pass(const GradArgs& A, GradSmem& S) {
                 S.DO[lane*DOLD + 2*ACT_DIM] = 0.0f;
             }
         } else {
-            value_loss_head<float>(out[0], valid ? A.ret[row] : 0.0f, A.vf_coef, inv_mb, L);
+            if constexpr (EX) {
+                value_loss_head_ex<float>(out[0], valid ? r[OD + ROW_VALUE] : 0.0f, valid ? A.ret[row] : 0.0f, A.clip_vf, A.vf_coef, inv_mb, L);
+                s_clip += valid ? L.v_clipped : 0.0f;
+            } else {
+                value_loss_head<float>(out[0], valid ? A.ret[row] : 0.0f, A.vf_coef, inv_mb, L);
+            }
             dout[0] = valid ? L.dV : 0.0f;
             s_loss += valid ? L.v_loss : 0.0f;
             if (q == 0) {
@@ -209,8 +232,8 @@ __device__ __forceinline__ void tower_pass(const GradArgs& A, GradSmem& S) {
         }
         __syncthreads();                                                    // the images are rewritten by the next tile
     }
-    // ---- this workgroup's partial: [P gradients | NSTAT sums]
-    float* __restrict__ pp = A.partial + (size_t)blockIdx.x*(P + NSTAT);
+    // ---- this workgroup's partial: [P gradients | NS sums]
+    float* __restrict__ pp = A.partial + (size_t)blockIdx.x*(P + NS);
 #pragma unroll
     for (int a = 0; a < 4; a++) {
 #pragma unroll
@@ -223,11 +246,23 @@ __device__ __forceinline__ void tower_pass(const GradArgs& A, GradSmem& S) {
     if (TW == 0 && tid >= ACT_DIM && tid < 2*ACT_DIM) pp[oLS + tid - ACT_DIM] = gcol;
     // the loss sums of wave 0's lanes, added in lane order by one thread
     if (q == 0) { S.HP[lane] = s_loss; S.HP[LT + lane] = s_clip; }
+    if constexpr (EX && TW == 0) {
+        if (q == 0) { S.HP[2*LT + lane] = s_kl; S.HP[3*LT + lane] = s_ent; }
+    }
     __syncthreads();
     if (tid == 0) {
         float a = 0.0f, c = 0.0f;
         for (int l = 0; l < LT; l++) { a += S.HP[l]; c += S.HP[LT + l]; }
         if (TW == 0) { pp[P + 0] = a; pp[P + 2] = c; } else pp[P + 1] = a;
+        if constexpr (EX) {
+            if (TW == 0) {
+                float k = 0.0f, e = 0.0f;
+                for (int l = 0; l < LT; l++) { k += S.HP[2*LT + l]; e += S.HP[3*LT + l]; }
+                pp[P + 3] = k; pp[P + 5] = e;
+            } else {
+                pp[P + 4] = c;
+            }
+        }
     }
     __syncthreads();
 }
@@ -235,14 +270,25 @@ __device__ __forceinline__ void tower_pass(const GradArgs& A, GradSmem& S) {
 template <int OD>
 __global__ __launch_bounds__(256) void so100_learn_grad(GradArgs A) {
     __shared__ GradSmem S;
-    tower_pass<OD, 0>(A, S);
-    tower_pass<OD, 1>(A, S);
+    tower_pass<OD, 0, false>(A, S);
+    tower_pass<OD, 1, false>(A, S);
+}
+
+// The extended step's gradient kernel: the same passes with the extended head.  Like every kernel of that step it reads the update's
+// `stopped` word first (set by so100_learn_adam_ex of an earlier step of this update, never by a kernel of this step before this one ran).
+template <int OD>
+__global__ __launch_bounds__(256) void so100_learn_grad_ex(GradArgsEx A) {
+    if (A.state != nullptr && A.state[0] != 0) return;
+    __shared__ GradSmem S;
+    tower_pass<OD, 0, true>(A, S);
+    tower_pass<OD, 1, true>(A, S);
 }
 
 // one thread per entry of a partial: the sum over the G workgroups in workgroup order; each block leaves the sum of squares of its gradients
-__global__ __launch_bounds__(256) void so100_learn_reduce(const float* __restrict__ partial, int G, int P, float* __restrict__ gsum, float* __restrict__ sq_block) {
+template <int NS>
+__device__ __forceinline__ void reduce_partials(const float* __restrict__ partial, int G, int P, float* __restrict__ gsum, float* __restrict__ sq_block) {
     __shared__ float sq[256];
-    const int p = blockIdx.x*256 + threadIdx.x, PS = P + NSTAT;
+    const int p = blockIdx.x*256 + threadIdx.x, PS = P + NS;
     float s = 0.0f;
     if (p < PS) {
         int g = 0;
@@ -265,6 +311,16 @@ __global__ __launch_bounds__(256) void so100_learn_reduce(const float* __restric
     if (threadIdx.x == 0) sq_block[blockIdx.x] = sq[0];
 }
 
+__global__ __launch_bounds__(256) void so100_learn_reduce(const float* __restrict__ partial, int G, int P, float* __restrict__ gsum, float* __restrict__ sq_block) {
+    reduce_partials<NSTAT>(partial, G, P, gsum, sq_block);
+}
+
+__global__ __launch_bounds__(256) void so100_learn_reduce_ex(const float* __restrict__ partial, int G, int P, float* __restrict__ gsum, float* __restrict__ sq_block,
+                                                             const int32_t* __restrict__ state) {
+    if (state != nullptr && state[0] != 0) return;
+    reduce_partials<NSTAT_EX>(partial, G, P, gsum, sq_block);
+}
+
 struct AdamArgs { float max_grad_norm, step_size, omb1, beta2, omb2, eps, bc2_sqrt, inv_mb; };     // formed in double on the host (clip_adam_update)
 
 __global__ __launch_bounds__(256) void so100_learn_adam(const float* __restrict__ gsum, const float* __restrict__ sq_block, int nblk, int P,
@@ -282,6 +338,38 @@ __global__ __launch_bounds__(256) void so100_learn_adam(const float* __restrict_
     }
     if (p == 0) {
         stats_out[0] = gsum[P + 0]*a.inv_mb; stats_out[1] = gsum[P + 1]*a.inv_mb; stats_out[2] = gsum[P + 2]*a.inv_mb; stats_out[3] = norm;
+    }
+}
+
+// The extended step's Adam kernel, with the KL stop.  approx_kl comes from the reduced sums, so every thread of every block forms the same
+// value and takes the same decision.  Stopped: parameters and moments stay as they are, thread 0 sets state[0] and leaves the stopping
+// minibatch's diagnostics.  A block that starts after thread 0 has set the word returns at once -- what it would have decided anyway.
+// Applied: the step of so100_learn_adam, and state[1] counts it.  diag: the eight values of so100_learner_minibatch_step_ex.
+struct TermsArgs { float ent_coef, vf_coef, kl_limit; };               // kl_limit = 1.5 target_kl, <= 0: no stop
+
+__global__ __launch_bounds__(256) void so100_learn_adam_ex(const float* __restrict__ gsum, const float* __restrict__ sq_block, int nblk, int P,
+                                                           float* __restrict__ params, float* __restrict__ m, float* __restrict__ v,
+                                                           float* __restrict__ grads_out, float* __restrict__ diag, int32_t* state, AdamArgs a, TermsArgs t) {
+    if (state != nullptr && state[0] != 0) return;
+    float ss = 0.0f;
+    for (int b = 0; b < nblk; b++) ss += sq_block[b];                      // the same ordered sum in every thread
+    const float norm = lsqrt(ss), coef = clip_coefficient<float>(norm, a.max_grad_norm);
+    const float kl = gsum[P + 3]*a.inv_mb;
+    const bool stop = t.kl_limit > 0.0f && kl > t.kl_limit;
+    const int p = blockIdx.x*256 + threadIdx.x;
+    if (!stop && p < P) {
+        float pv = params[p], mv = m[p], vv = v[p];
+        const float g = clip_adam_update<float>(gsum[p], coef, pv, mv, vv, a.step_size, a.omb1, a.beta2, a.omb2, a.eps, a.bc2_sqrt);
+        params[p] = pv; m[p] = mv; v[p] = vv;
+        if (grads_out) grads_out[p] = g;
+    }
+    if (p == 0) {
+        const float pg = gsum[P + 0]*a.inv_mb, vl = gsum[P + 1]*a.inv_mb, ent_loss = -(gsum[P + 5]*a.inv_mb);
+        diag[0] = pg; diag[1] = vl; diag[2] = gsum[P + 2]*a.inv_mb; diag[3] = norm;
+        diag[4] = kl; diag[5] = ent_loss; diag[6] = pg + t.ent_coef*ent_loss + t.vf_coef*vl; diag[7] = gsum[P + 4]*a.inv_mb;
+        if (state != nullptr) {
+            if (stop) state[0] = 1; else state[1] += 1;
+        }
     }
 }
 
@@ -361,6 +449,87 @@ __global__ __launch_bounds__(ADV_THREADS) void so100_learn_adv_stats(const float
     if (threadIdx.x == 0) { stats[0] = mean; stats[1] = lsqrt(ss/(float)(n - 1)); }       // n = 1: 0/0 = NaN, as torch
 }
 
+// mean and unbiased standard deviation of adv over the valid rows idx names (idx null: rows 0..mb-1), two passes, one workgroup: the
+// statistics of SB3's per-minibatch normalisation.  With at most one valid row SB3 leaves the advantages as they are: the pair (0, 1)
+// does that to the bit, (A - 0)*(1/(1 + 1e-8f)) = A in fp32.
+__global__ __launch_bounds__(ADV_THREADS) void so100_learn_mb_adv_stats(const float* __restrict__ adv, long num_samples, const int64_t* __restrict__ idx, int mb,
+                                                                        float* __restrict__ stats, const int32_t* __restrict__ state) {
+    __shared__ float sh[ADV_THREADS];
+    __shared__ int cnt;
+    if (state != nullptr && state[0] != 0) return;
+    if (threadIdx.x == 0) cnt = 0;
+    __syncthreads();
+    float s = 0.0f; int c = 0;
+    for (int i = threadIdx.x; i < mb; i += ADV_THREADS) {
+        const long row = idx ? (long)idx[i] : (long)i;
+        if (row >= 0 && row < num_samples) { s += adv[row]; c++; }
+    }
+    atomicAdd(&cnt, c);                                                     // an integer count: exact in any order
+    const float sum = block_sum_1024(s, sh);                               // (its barriers publish cnt)
+    const int n = cnt;
+    const float mean = sum/(float)n;
+    float q = 0.0f;
+    for (int i = threadIdx.x; i < mb; i += ADV_THREADS) {
+        const long row = idx ? (long)idx[i] : (long)i;
+        if (row >= 0 && row < num_samples) { const float d = adv[row] - mean; q = fmaf(d, d, q); }
+    }
+    const float ss = block_sum_1024(q, sh);
+    if (threadIdx.x == 0) {
+        if (n > 1) { stats[0] = mean; stats[1] = lsqrt(ss/(float)(n - 1)); }
+        else { stats[0] = 0.0f; stats[1] = 1.0f; }
+    }
+}
+
+// explained_variance = 1 - var(ret - old_V)/var(ret) over the chunk (population variances), NaN when var(ret) == 0.  old_V is the chunk's
+// value column (row stride `row` floats, first entry at chunk + value_col).  Stage 1: workgroup g owns the contiguous rows
+// [g per, (g+1) per) and leaves their count, the two means and the two sums of squared deviations from those means (two passes, fixed trees).
+// Stage 2: one thread merges the workgroups' moments in workgroup order (Chan et al.'s pairwise update).  The same bits every run.
+// A thread keeps its first row in registers across the two passes: with at most 1024 rows per slice (any chunk up to 262 144 rows) the packed
+// chunk is read once.  A constant ret has variance 0 by definition, whatever rounding leaves in the sum of squares: each slice also records
+// whether any of its rows differs from ret[0], and the merge returns NaN when none does.
+constexpr int EV_GRID_MAX = 256, EV_PART = 6;
+__global__ __launch_bounds__(ADV_THREADS) void so100_learn_ev_moments(const float* __restrict__ chunk, int row, int value_col, const float* __restrict__ ret,
+                                                                      long n, long per, float* __restrict__ part) {
+    __shared__ float sh[ADV_THREADS];
+    const long lo = (long)blockIdx.x*per, hi = lo + per < n ? lo + per : n;
+    const float cnt = (float)(hi - lo), first = ret[0];
+    const long i0 = lo + threadIdx.x;
+    const bool own = i0 < hi;
+    const float r0 = own ? ret[i0] : 0.0f, d0 = own ? r0 - chunk[i0*row + value_col] : 0.0f;
+    float sr = r0, sd = d0;
+    int differs = own && r0 != first;
+    for (long i = i0 + ADV_THREADS; i < hi; i += ADV_THREADS) { const float r = ret[i]; sr += r; sd += r - chunk[i*row + value_col]; differs |= r != first; }
+    const float mr = block_sum_1024(sr, sh)/cnt, md = block_sum_1024(sd, sh)/cnt;
+    float qr = 0.0f, qd = 0.0f;
+    if (own) { const float a = r0 - mr, b = d0 - md; qr = a*a; qd = b*b; }
+    for (long i = i0 + ADV_THREADS; i < hi; i += ADV_THREADS) {
+        const float r = ret[i], a = r - mr, b = (r - chunk[i*row + value_col]) - md;
+        qr = fmaf(a, a, qr); qd = fmaf(b, b, qd);
+    }
+    const float m2r = block_sum_1024(qr, sh), m2d = block_sum_1024(qd, sh);
+    const int any = __syncthreads_or(differs);
+    if (threadIdx.x == 0) {
+        float* o = part + (size_t)blockIdx.x*EV_PART;
+        o[0] = cnt; o[1] = mr; o[2] = m2r; o[3] = md; o[4] = m2d; o[5] = any ? 1.0f : 0.0f;
+    }
+}
+
+__global__ __launch_bounds__(256) void so100_learn_ev_merge(const float* __restrict__ gpart, int G, float* __restrict__ out) {
+    __shared__ float part[EV_GRID_MAX*EV_PART];                            // fetched by all threads at once; the merge itself is one thread's, in order
+    for (int i = threadIdx.x; i < G*EV_PART; i += 256) part[i] = gpart[i];
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    float n = part[0], mr = part[1], m2r = part[2], md = part[3], m2d = part[4], differs = part[5];
+    for (int g = 1; g < G; g++) {
+        const float* p = part + g*EV_PART;
+        const float ng = p[0], tot = n + ng, w = ng/tot, dr = p[1] - mr, dd = p[3] - md;
+        mr = fmaf(dr, w, mr); m2r += p[2] + dr*dr*n*w;
+        md = fmaf(dd, w, md); m2d += p[4] + dd*dd*n*w;
+        n = tot; differs += p[5];
+    }
+    out[0] = (differs == 0.0f || m2r == 0.0f) ? __builtin_nanf("") : 1.0f - m2d/m2r;
+}
+
 const char* const kTensorNames[NUM_TENSORS] = {
 #define X(name, rows, cols) #name,
     SO100_POLICY_TENSORS(X)
@@ -381,10 +550,12 @@ using namespace so100::learn;
 
 struct so100_learner {
     so100_learner_config cfg;
-    int P = 0, grid_max = 0, nblk = 0;
-    float* partial = nullptr;      // [grid_max][P + NSTAT] per-workgroup partial gradients
-    float* gsum = nullptr;         // [P + NSTAT] their ordered sum
-    float* sq_block = nullptr;     // [nblk] sum of squares per block of the reduction
+    int P = 0, grid_max = 0, nblk = 0, nblk_ex = 0;
+    float* partial = nullptr;      // [grid_max][P + NSTAT_EX] per-workgroup partial gradients (the old step strides them by P + NSTAT)
+    float* gsum = nullptr;         // [P + NSTAT_EX] their ordered sum
+    float* sq_block = nullptr;     // [nblk_ex] sum of squares per block of the reduction
+    float* mb_stats = nullptr;     // [2] mean and std of the minibatch's advantages (normalize_advantage = 1)
+    float* ev_part = nullptr;      // [EV_GRID_MAX][EV_PART] per-workgroup moments of so100_learner_explained_variance
 };
 
 extern "C" {
@@ -429,9 +600,11 @@ int so100_learner_create(const so100_learner_config* cfg, so100_learner** out) {
     const long tiles = ((long)cfg->max_minibatch + LT - 1)/LT;
     L->grid_max = (int)(tiles < GRID_MAX ? tiles : GRID_MAX);
     L->nblk = (L->P + NSTAT + 255)/256;
-    const size_t ps = (size_t)(L->P + NSTAT);
+    L->nblk_ex = (L->P + NSTAT_EX + 255)/256;
+    const size_t ps = (size_t)(L->P + NSTAT_EX);
     if (hipMalloc(&L->partial, (size_t)L->grid_max*ps*sizeof(float)) != hipSuccess || hipMalloc(&L->gsum, ps*sizeof(float)) != hipSuccess ||
-        hipMalloc(&L->sq_block, (size_t)L->nblk*sizeof(float)) != hipSuccess) {
+        hipMalloc(&L->sq_block, (size_t)L->nblk_ex*sizeof(float)) != hipSuccess || hipMalloc(&L->mb_stats, 2*sizeof(float)) != hipSuccess ||
+        hipMalloc(&L->ev_part, (size_t)EV_GRID_MAX*EV_PART*sizeof(float)) != hipSuccess) {
         so100_learner_destroy(L);
         return fail(SO100_E_NOMEM, "so100_learner_create: hipMalloc of the partial-gradient scratch failed");
     }
@@ -445,6 +618,8 @@ void so100_learner_destroy(so100_learner* L) {
     if (L->partial) (void)hipFree(L->partial);
     if (L->gsum) (void)hipFree(L->gsum);
     if (L->sq_block) (void)hipFree(L->sq_block);
+    if (L->mb_stats) (void)hipFree(L->mb_stats);
+    if (L->ev_part) (void)hipFree(L->ev_part);
     delete L;
 }
 
@@ -492,6 +667,70 @@ int so100_learner_minibatch_step(so100_learner* L, const so100_minibatch_io* io,
     hipLaunchKernelGGL(so100_learn_adam, dim3((unsigned)((L->P + 255)/256)), dim3(256), 0, st, (const float*)L->gsum, (const float*)L->sq_block, L->nblk, L->P,
                        io->params_dev, io->adam_m_dev, io->adam_v_dev, io->grads_dev, io->stats_dev, a);
     HIP_TRY(hipGetLastError(), SO100_E_LAUNCH, "so100_learner_minibatch_step: ");
+    return 0;
+}
+
+int so100_learner_minibatch_step_ex(so100_learner* L, const so100_minibatch_io* io, const so100_ppo_terms* terms, float* diag_dev, int32_t* update_state_dev, void* stream) {
+    if (!L || !io || !terms) return fail(SO100_E_INVALID, "so100_learner_minibatch_step_ex: null argument");
+    if (io->mb < 1 || io->mb > L->cfg.max_minibatch) return fail(SO100_E_INVALID, "so100_learner_minibatch_step_ex: mb must be in 1..max_minibatch, got %d", io->mb);
+    if (io->num_samples < 1) return fail(SO100_E_INVALID, "so100_learner_minibatch_step_ex: num_samples must be >= 1, got %ld", (long)io->num_samples);
+    if (io->adam_step < 1) return fail(SO100_E_INVALID, "so100_learner_minibatch_step_ex: adam_step is 1-based, got %d", io->adam_step);
+    if (!io->rollout_dev || !io->adv_dev || !io->ret_dev || !io->adv_stats_dev || !io->params_dev || !io->adam_m_dev || !io->adam_v_dev || !diag_dev)
+        return fail(SO100_E_INVALID, "so100_learner_minibatch_step_ex: rollout/adv/ret/adv_stats/params/adam_m/adam_v/diag pointers are required");
+    if (!(terms->ent_coef >= 0.0f)) return fail(SO100_E_INVALID, "so100_learner_minibatch_step_ex: ent_coef must be >= 0");
+    if (terms->clip_range_vf != terms->clip_range_vf) return fail(SO100_E_INVALID, "so100_learner_minibatch_step_ex: clip_range_vf is NaN (<= 0 means off)");
+    if (terms->target_kl != terms->target_kl) return fail(SO100_E_INVALID, "so100_learner_minibatch_step_ex: target_kl is NaN (<= 0 means off)");
+    if (terms->normalize_advantage != 0 && terms->normalize_advantage != 1)
+        return fail(SO100_E_INVALID, "so100_learner_minibatch_step_ex: normalize_advantage must be 0 (batch) or 1 (minibatch), got %d", terms->normalize_advantage);
+    if (terms->lr != terms->lr) return fail(SO100_E_INVALID, "so100_learner_minibatch_step_ex: lr is NaN (negative means the handle's)");
+    if (terms->target_kl > 0.0f && !update_state_dev)
+        return fail(SO100_E_INVALID, "so100_learner_minibatch_step_ex: target_kl needs the update-state pointer");
+    if (L->cfg.obs_dim != 15 && L->cfg.obs_dim != 8)
+        return fail(SO100_E_INVALID, "so100_learner_minibatch_step_ex: no extended gradient kernel for obs_dim %d", L->cfg.obs_dim);
+    SO100_ON_DEVICE(L->cfg.device, "so100_learner_minibatch_step_ex");
+    const hipStream_t st = (hipStream_t)stream;
+    const int tiles = (io->mb + LT - 1)/LT, G = tiles < L->grid_max ? tiles : L->grid_max;
+    const int32_t* state = update_state_dev;
+    GradArgsEx A;
+    A.chunk = io->rollout_dev; A.num_samples = (long)io->num_samples; A.idx = io->idx_dev; A.mb = io->mb;
+    A.adv = io->adv_dev; A.ret = io->ret_dev; A.adv_stats = io->adv_stats_dev; A.params = io->params_dev; A.partial = L->partial;
+    A.clip = L->cfg.clip_range; A.vf_coef = L->cfg.vf_coef;
+    A.ent_coef = terms->ent_coef; A.clip_vf = terms->clip_range_vf > 0.0f ? terms->clip_range_vf : 0.0f; A.state = state;
+    if (terms->normalize_advantage == 1) {
+        hipLaunchKernelGGL(so100_learn_mb_adv_stats, dim3(1), dim3(ADV_THREADS), 0, st, io->adv_dev, (long)io->num_samples, io->idx_dev, io->mb, L->mb_stats, state);
+        A.adv_stats = L->mb_stats;
+    }
+    SO100_WITH_OBS_DIM(L->cfg.obs_dim, hipLaunchKernelGGL((so100_learn_grad_ex<OD>), dim3((unsigned)G), dim3(256), 0, st, A););
+    hipLaunchKernelGGL(so100_learn_reduce_ex, dim3((unsigned)L->nblk_ex), dim3(256), 0, st, (const float*)L->partial, G, L->P, L->gsum, L->sq_block, state);
+    const double lr = terms->lr < 0.0 ? L->cfg.lr : terms->lr;
+    AdamArgs a;
+    a.max_grad_norm = L->cfg.max_grad_norm;
+    a.step_size = (float)(lr/(1.0 - pow(L->cfg.beta1, (double)io->adam_step))); a.bc2_sqrt = (float)sqrt(1.0 - pow(L->cfg.beta2, (double)io->adam_step));
+    a.omb1 = (float)(1.0 - L->cfg.beta1); a.beta2 = (float)L->cfg.beta2; a.omb2 = (float)(1.0 - L->cfg.beta2); a.eps = (float)L->cfg.adam_eps;
+    a.inv_mb = 1.0f/(float)io->mb;
+    TermsArgs t;
+    t.ent_coef = terms->ent_coef; t.vf_coef = L->cfg.vf_coef; t.kl_limit = terms->target_kl > 0.0f ? (float)(1.5*(double)terms->target_kl) : 0.0f;
+    hipLaunchKernelGGL(so100_learn_adam_ex, dim3((unsigned)((L->P + 255)/256)), dim3(256), 0, st, (const float*)L->gsum, (const float*)L->sq_block, L->nblk_ex, L->P,
+                       io->params_dev, io->adam_m_dev, io->adam_v_dev, io->grads_dev, diag_dev, update_state_dev, a, t);
+    HIP_TRY(hipGetLastError(), SO100_E_LAUNCH, "so100_learner_minibatch_step_ex: ");
+    return 0;
+}
+
+int so100_learner_explained_variance(so100_learner* L, const float* rollout_dev, const float* ret_dev, int64_t num_samples, float* out_dev, void* stream) {
+    if (!L) return fail(SO100_E_INVALID, "so100_learner_explained_variance: null argument");
+    if (num_samples < 1) return fail(SO100_E_INVALID, "so100_learner_explained_variance: num_samples must be >= 1, got %ld", (long)num_samples);
+    if (num_samples > (1L << 24))                                           // the row counts are carried as floats: exact up to 2^24
+        return fail(SO100_E_INVALID, "so100_learner_explained_variance: num_samples must be <= 16777216, got %ld", (long)num_samples);
+    if (!rollout_dev || !ret_dev || !out_dev) return fail(SO100_E_INVALID, "so100_learner_explained_variance: rollout/ret/out pointers are required");
+    SO100_ON_DEVICE(L->cfg.device, "so100_learner_explained_variance");
+    const int od = L->cfg.obs_dim;
+    const long n = (long)num_samples, want = (n + ADV_THREADS - 1)/ADV_THREADS, G0 = want < EV_GRID_MAX ? want : EV_GRID_MAX;
+    const long per = (n + G0 - 1)/G0;
+    const int G = (int)((n + per - 1)/per);                                  // every workgroup owns at least one row
+    hipLaunchKernelGGL(so100_learn_ev_moments, dim3((unsigned)G), dim3(ADV_THREADS), 0, (hipStream_t)stream, rollout_dev, od + ROW_EXTRA, od + ROW_VALUE, ret_dev,
+                       n, per, L->ev_part);
+    hipLaunchKernelGGL(so100_learn_ev_merge, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)L->ev_part, G, out_dev);
+    HIP_TRY(hipGetLastError(), SO100_E_LAUNCH, "so100_learner_explained_variance: ");
     return 0;
 }
 

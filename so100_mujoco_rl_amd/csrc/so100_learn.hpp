@@ -4,6 +4,7 @@
 // of the simulator: the file compiles with a plain host compiler.
 //   gae_scan_env        rollout.bootstrap_truncated + PPO._gae for one env (SB3 RolloutBuffer.compute_returns_and_advantage)
 //   ppo_loss_head       the PPO._step loss of one sample with its derivatives towards the network outputs
+//   ppo_loss_head_ex    the same with SB3's entropy bonus, value clipping and approx_kl
 //   clip_adam_update    clip_grad_norm_'s scaling + one torch.optim.Adam step of one parameter
 #pragma once
 #include "so100_policy_tensors.h"
@@ -74,8 +75,10 @@ struct LossHead {
 // The two towers meet only in the sum of the loss, so the head has a policy half and a value half; the kernels run one tower at a time and
 // call the halves, ppo_loss_head is both.  adv_n = (adv - mean)/(std + 1e-8), formed by the caller.  torch's derivative conventions:
 // min() splits a tie evenly, clamp() passes the gradient on its closed interval.
+// policy_loss_core is policy_loss_head's arithmetic with the two intermediates the extended head needs handed out as well: the ratio and
+// logp - logp_old.  policy_loss_head is the core with those dropped: the same expressions, the same results.
 template <class S>
-SO100_LHD void policy_loss_head(const S* mu, const S* log_std, const S* a, S logp_old, S adv_n, S clip, S inv_mb, LossHead<S>& o) {
+SO100_LHD void policy_loss_core(const S* mu, const S* log_std, const S* a, S logp_old, S adv_n, S clip, S inv_mb, LossHead<S>& o, S& ratio_out, S& log_ratio_out) {
     S z[ACT_DIM], inv_sigma[ACT_DIM], logp = S(0);
     for (int i = 0; i < ACT_DIM; i++) {
         inv_sigma[i] = lexp(-log_std[i]);
@@ -95,6 +98,13 @@ SO100_LHD void policy_loss_head(const S* mu, const S* log_std, const S* a, S log
         o.dmu[i] = dlogp*z[i]*inv_sigma[i];
         o.dlog_std[i] = dlogp*(z[i]*z[i] - S(1));
     }
+    ratio_out = ratio; log_ratio_out = logp - logp_old;
+}
+
+template <class S>
+SO100_LHD void policy_loss_head(const S* mu, const S* log_std, const S* a, S logp_old, S adv_n, S clip, S inv_mb, LossHead<S>& o) {
+    S ratio, log_ratio;
+    policy_loss_core(mu, log_std, a, logp_old, adv_n, clip, inv_mb, o, ratio, log_ratio);
 }
 
 template <class S>
@@ -109,6 +119,58 @@ SO100_LHD LossHead<S> ppo_loss_head(const S* mu, const S* log_std, const S* a, S
     LossHead<S> o;
     policy_loss_head(mu, log_std, a, logp_old, adv_n, clip, inv_mb, o);
     value_loss_head(V, ret, vf_coef, inv_mb, o);
+    return o;
+}
+
+// ---- extended loss head (so100_learner_minibatch_step_ex): SB3's remaining terms --------------------------------------------------------
+// loss = policy_loss + ent_coef entropy_loss + vf_coef value_loss with
+//   entropy_loss = -mean(entropy), entropy = sum_i log_std_i + 6 (0.5 + 0.5 ln 2 pi): state-independent, its only gradient is -ent_coef on each log_std_i
+//   value_loss = mean((ret - V_pred)^2), V_pred = old_V + clamp(V - old_V, -clip_vf, +clip_vf) when clip_vf > 0, else V
+//   approx_kl = mean((ratio - 1) - (logp - logp_old))                  (a diagnostic: no gradient)
+template <class S>
+struct LossHeadEx : LossHead<S> {
+    S approx_kl;                   // this sample's (ratio - 1) - (logp - logp_old)
+    S entropy;                     // the Gaussian's entropy (the same for every sample)
+    S v_clipped;                   // 1 where |V - old_V| > clip_vf (the clamp is active: no gradient reaches V), else 0; 0 with value clipping off
+};
+
+// entropy and the -ent_coef inv_mb it adds to every d/dlog_std ride on the policy half.  With ent_coef = 0 the derivatives are
+// policy_loss_head's to the bit (x - 0 = x).
+template <class S>
+SO100_LHD void policy_loss_head_ex(const S* mu, const S* log_std, const S* a, S logp_old, S adv_n, S clip, S ent_coef, S inv_mb, LossHeadEx<S>& o) {
+    S ratio, log_ratio;
+    policy_loss_core<S>(mu, log_std, a, logp_old, adv_n, clip, inv_mb, o, ratio, log_ratio);
+    o.approx_kl = (ratio - S(1)) - log_ratio;
+    S h = S(0);
+    for (int i = 0; i < ACT_DIM; i++) h += log_std[i];
+    o.entropy = h + S(ACT_DIM)*S(1.4189385332046727);
+    const S de = ent_coef*inv_mb;
+    for (int i = 0; i < ACT_DIM; i++) o.dlog_std[i] -= de;
+}
+
+// torch's clamp passes the gradient on the closed interval [-clip_vf, +clip_vf] and none outside it.  clip_vf <= 0: value_loss_head.
+template <class S>
+SO100_LHD void value_loss_head_ex(S V, S old_V, S ret, S clip_vf, S vf_coef, S inv_mb, LossHeadEx<S>& o) {
+    if (!(clip_vf > S(0))) {
+        value_loss_head<S>(V, ret, vf_coef, inv_mb, o);
+        o.v_clipped = S(0);
+        return;
+    }
+    const S d = V - old_V;
+    const bool outside = d > clip_vf || -d > clip_vf;
+    const S v_pred = old_V + (d < -clip_vf ? -clip_vf : d > clip_vf ? clip_vf : d);
+    const S e = v_pred - ret;
+    o.v_loss = e*e;
+    o.dV = outside ? S(0) : S(2)*vf_coef*e*inv_mb;
+    o.v_clipped = outside ? S(1) : S(0);
+}
+
+template <class S>
+SO100_LHD LossHeadEx<S> ppo_loss_head_ex(const S* mu, const S* log_std, const S* a, S logp_old, S adv_n, S V, S old_V, S ret, S clip, S clip_vf,
+                                         S ent_coef, S vf_coef, S inv_mb) {
+    LossHeadEx<S> o;
+    policy_loss_head_ex(mu, log_std, a, logp_old, adv_n, clip, ent_coef, inv_mb, o);
+    value_loss_head_ex(V, old_V, ret, clip_vf, vf_coef, inv_mb, o);
     return o;
 }
 

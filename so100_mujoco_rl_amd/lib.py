@@ -109,9 +109,15 @@ class MinibatchIO(C.Structure):
                 ("adam_v_dev", C.c_void_p), ("stats_dev", C.c_void_p), ("grads_dev", C.c_void_p)]
 
 
+class PpoTerms(C.Structure):
+    _fields_ = [("ent_coef", C.c_float), ("clip_range_vf", C.c_float), ("normalize_advantage", C.c_int32), ("target_kl", C.c_float), ("lr", C.c_double)]
+
+
 LEARN_EXPORTS = ["so100_learner_num_params", "so100_learner_param_offset", "so100_learner_param_size", "so100_learner_create", "so100_learner_destroy",
-                 "so100_learner_advantages", "so100_learner_minibatch_step"]
+                 "so100_learner_advantages", "so100_learner_minibatch_step", "so100_learner_minibatch_step_ex", "so100_learner_explained_variance"]
 LEARNER_STATS = ["policy_loss", "value_loss", "clip_fraction", "grad_norm"]          # stats_dev[4] of so100_learner_minibatch_step
+LEARNER_DIAG = LEARNER_STATS + ["approx_kl", "entropy_loss", "loss", "value_clip_fraction"]       # diag_dev[8] of so100_learner_minibatch_step_ex
+NORMALIZE_ADVANTAGE = {"batch": 0, "minibatch": 1}                                   # so100_ppo_terms.normalize_advantage
 
 
 def build(verbose=False):
@@ -159,6 +165,8 @@ def load():
         L.so100_learner_destroy.restype = None
         L.so100_learner_advantages.argtypes = [C.c_void_p, C.POINTER(AdvantagesIO), C.c_int32, C.c_int32, C.c_void_p]
         L.so100_learner_minibatch_step.argtypes = [C.c_void_p, C.POINTER(MinibatchIO), C.c_void_p]
+        L.so100_learner_minibatch_step_ex.argtypes = [C.c_void_p, C.POINTER(MinibatchIO), C.POINTER(PpoTerms), C.c_void_p, C.c_void_p, C.c_void_p]
+        L.so100_learner_explained_variance.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         if L.so100_abi_version() != ABI_VERSION:
             raise So100Error("libso100sim.so ABI version mismatch")
         _lib = L
@@ -523,3 +531,31 @@ class So100Learner(_Handle):
                          _ptr(adv_stats, f, (2,), d), _ptr(params, f, (P,), d), _ptr(adam_m, f, (P,), d), _ptr(adam_v, f, (P,), d),
                          _ptr(stats, f, (4,), d), _ptr(grads, f, (P,), d))
         _check(self.L.so100_learner_minibatch_step(self.h, C.byref(io), self._stream()), "so100_learner_minibatch_step")
+
+    def minibatch_step_ex(self, rollout, idx, adv, ret, adv_stats, params, adam_m, adam_v, adam_step, diag, ent_coef=0.0, clip_range_vf=None,
+                          normalize_advantage="batch", target_kl=None, lr=None, update_state=None, grads=None):
+        """minibatch_step with SB3's remaining loss terms (so100_ppo_terms): diag [8] (LEARNER_DIAG) is written instead of stats.
+        clip_range_vf / target_kl None: off; lr None: the handle's.  update_state: int32 [2] {stopped, steps_applied}, zeroed by the caller
+        at the start of an update; required with target_kl."""
+        T, N = rollout.shape[0], rollout.shape[1]
+        f, d, o, P = torch.float32, self.device, self.obs_dim, self.num_params
+        if isinstance(idx, int):
+            mb, ip = idx, None
+        else:
+            mb = idx.numel(); ip = _ptr(idx, torch.int64, (mb,), d)
+        if normalize_advantage not in NORMALIZE_ADVANTAGE:
+            raise So100Error(f"normalize_advantage must be one of {sorted(NORMALIZE_ADVANTAGE)}, got {normalize_advantage!r}")
+        io = MinibatchIO(_ptr(rollout, f, (T, N, o + 10), d), T * N, ip, mb, adam_step, _ptr(adv, f, (T, N), d), _ptr(ret, f, (T, N), d),
+                         _ptr(adv_stats, f, (2,), d), _ptr(params, f, (P,), d), _ptr(adam_m, f, (P,), d), _ptr(adam_v, f, (P,), d),
+                         None, _ptr(grads, f, (P,), d))
+        terms = PpoTerms(ent_coef, 0.0 if clip_range_vf is None else clip_range_vf, NORMALIZE_ADVANTAGE[normalize_advantage],
+                         0.0 if target_kl is None else target_kl, -1.0 if lr is None else lr)
+        _check(self.L.so100_learner_minibatch_step_ex(self.h, C.byref(io), C.byref(terms), _ptr(diag, f, (8,), d), _ptr(update_state, torch.int32, (2,), d),
+                                                      self._stream()), "so100_learner_minibatch_step_ex")
+
+    def explained_variance(self, rollout, ret, out):
+        """out [1] = 1 - var(ret - old_V)/var(ret) over the chunk (old_V: the value column of the packed chunk); NaN when var(ret) is 0"""
+        T, N = rollout.shape[0], rollout.shape[1]
+        f, d = torch.float32, self.device
+        _check(self.L.so100_learner_explained_variance(self.h, _ptr(rollout, f, (T, N, self.obs_dim + 10), d), _ptr(ret, f, (T, N), d), T * N,
+                                                       _ptr(out, f, (1,), d), self._stream()), "so100_learner_explained_variance")

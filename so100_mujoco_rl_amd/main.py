@@ -1,6 +1,8 @@
 """Experiment driver with the reference's CLI surface (ref: /root/reference/src/so100_mujoco_rl/main.py:241-284):
 
     python -m so100_mujoco_rl_amd.main -a PPO [-m MODEL] train  -e Env01-v1 [--envs 4096] [--iters N] [--learner torch|fused]
+                                                               [--ent-coef C] [--clip-range-vf C] [--target-kl K]
+                                                               [--normalize-advantage batch|minibatch] [--lr-schedule constant|linear]
     python -m so100_mujoco_rl_amd.main -a PPO [-m MODEL] test   -e Env01-v1 [--show-io] [--show-i]
     python -m so100_mujoco_rl_amd.main -a PPO [-m MODEL] record -e Env01-v1 [--steps 3000] [--video/--no-video]
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 -m so100_mujoco_rl_amd.main -a PPO train -e Env01-v1     # 8 x 4096 envs
@@ -79,9 +81,26 @@ def cli(ctx, algorithm, model):
 @click.option("--seed", default=0, type=int)
 @click.option("--learner", "learner_kind", default="torch", type=click.Choice(["torch", "fused"]),
               help="built-in PPO update: PyTorch autograd (torch) or the library's HIP kernels (fused; include/so100_learn.h)")
+@click.option("--ent-coef", default=None, type=float, help="entropy bonus coefficient (SB3 ent_coef; default 0)")
+@click.option("--clip-range-vf", default=None, type=float, help="value clipping range (SB3 clip_range_vf; default none)")
+@click.option("--target-kl", default=None, type=float, help="stop an update once approx_kl exceeds 1.5 x this (SB3 target_kl; default none)")
+@click.option("--normalize-advantage", default=None, type=click.Choice(["batch", "minibatch"]),
+              help="advantage normalisation over the whole rollout chunk (batch, the default) or per minibatch as SB3 does")
+@click.option("--lr-schedule", default=None, type=click.Choice(["constant", "linear"]), help="learning rate 3e-4 (constant, the default) or 3e-4 x remaining progress (linear; needs --iters)")
 @click.pass_context
-def train(ctx, environment, envs, iters, seed, learner_kind):
+def train(ctx, environment, envs, iters, seed, learner_kind, ent_coef, clip_range_vf, target_kl, normalize_advantage, lr_schedule):
     algorithm = ctx.obj["ALGORITHM_NAME"]
+    if lr_schedule == "linear" and iters <= 0:
+        raise RuntimeError("--lr-schedule linear needs --iters > 0: the schedule runs over a known number of updates")
+    # SB3's remaining PPO options: given on the command line, they reach whichever learner runs and a second log line shows their diagnostics.
+    # `--normalize-advantage batch` and `--lr-schedule constant` name what runs anyway: they select nothing and print nothing more.
+    terms = {k: v for k, v in (("ent_coef", ent_coef), ("clip_range_vf", clip_range_vf), ("target_kl", target_kl)) if v is not None}
+    if normalize_advantage == "minibatch":
+        terms["normalize_advantage"] = "minibatch"
+    if lr_schedule == "linear":
+        terms["lr_schedule"] = lambda progress: PPO_LR * progress
+    if terms and algorithm != "PPO":
+        raise RuntimeError("--ent-coef, --clip-range-vf, --target-kl, --normalize-advantage and --lr-schedule are PPO's options")
     kind = kind_from_id(environment)
     # Multi-GPU (one process per GPU under torchrun): rank r steps global envs [r*envs, (r+1)*envs); once per rollout chunk the
     # packed rollout goes to rank 0 over RCCL (the path's ONE collective), rank 0 learns, the policy is broadcast back.
@@ -108,7 +127,12 @@ def train(ctx, environment, envs, iters, seed, learner_kind):
         from stable_baselines3.common.callbacks import CheckpointCallback
         cls = getattr(stable_baselines3, algorithm)
         model_file = ctx.obj["MODEL_PATH"]
-        model = cls.load(model_file, env=env, tensorboard_log=LOG_DIR) if model_file else cls("MlpPolicy", env, verbose=1, device="cuda", tensorboard_log=LOG_DIR)
+        sb3_terms = {k: v for k, v in terms.items() if k in ("ent_coef", "clip_range_vf", "target_kl")}
+        if "normalize_advantage" in terms:
+            sb3_terms["normalize_advantage"] = True          # "minibatch" is SB3's own normalisation (and its default); it has no per-chunk one
+        if "lr_schedule" in terms:
+            sb3_terms["learning_rate"] = terms["lr_schedule"]
+        model = cls.load(model_file, env=env, tensorboard_log=LOG_DIR) if model_file else cls("MlpPolicy", env, verbose=1, device="cuda", tensorboard_log=LOG_DIR, **sb3_terms)
         cb = CheckpointCallback(save_freq=max(1, 40000 // envs), save_path=save_dir, name_prefix=f"{environment}_{algorithm}_cp_", verbose=2)
         model.learn(total_timesteps=int(1e10) if iters == 0 else iters * 64 * envs, tb_log_name=f"{environment}_{algorithm}", callback=cb)
         model.save(os.path.join(save_dir, "best_model"))
@@ -117,7 +141,7 @@ def train(ctx, environment, envs, iters, seed, learner_kind):
         if distributed:
             raise RuntimeError("multi-GPU training uses the built-in PPO learner; DDPG runs on one GPU")
         return _train_ddpg(env, environment, ctx.obj["MODEL_PATH"], save_dir, iters, seed, kind)
-    learner = make_ppo_learner(learner_kind, env.sim.obs_dim, env.device, seed)
+    learner = make_ppo_learner(learner_kind, env.sim.obs_dim, env.device, seed, **terms)
     if ctx.obj["MODEL_PATH"]:
         if not os.path.isfile(ctx.obj["MODEL_PATH"]):
             raise RuntimeError(f"Model file {ctx.obj['MODEL_PATH']} does not exist")
@@ -150,7 +174,7 @@ def train(ctx, environment, envs, iters, seed, learner_kind):
             done = (b["dones"] > 0).any(0)[:envs]            # episode statistics from this rank's own envs
             if done.any():                                   # ep_return holds the return of the latest episode that ended in the chunk
                 ep_sum += env.sim.ep_return[done].sum().item(); ep_cnt += int(done.sum().item())
-            stats = learner.update(b)
+            stats = learner.update(b, progress_remaining=1.0 - it / iters) if iters else learner.update(b)      # SB3's progress_remaining at the time of train()
             steps += b["rewards"].numel()
             if it % 10 == 0:
                 mean_ep = ep_sum / ep_cnt if ep_cnt else float("nan")
@@ -160,6 +184,10 @@ def train(ctx, environment, envs, iters, seed, learner_kind):
                 if dropped > 0:                              # over the contact budget: this step deviates from the reference model (MuJoCo keeps every contact)
                     logger.warning(f"contact budget exceeded: up to {dropped} contacts dropped in an env of the last step")
                 ep_sum = ep_cnt = 0.0
+            if terms and (it % 10 == 0 or (iters and it >= iters)):
+                logger.info(f"iter {it:5d}  approx_kl {stats['approx_kl']:.5f}  entropy_loss {stats['entropy_loss']:.4f}  loss {stats['loss']:.4f}  "
+                            f"explained_variance {stats['explained_variance']:.4f}  std {stats['std']:.4f}  n_updates {stats['n_updates']}"
+                            + ("  (early stop)" if stats["early_stop"] else ""))
             if not eval_cb.step():
                 logger.info(f"Stopping training: best evaluation reward {eval_cb.best_mean_reward:.1f} (threshold {threshold})"); stop.fill_(1.0)
             if it % 40 == 0:                                 # CheckpointCallback (ref: main.py:227-232)
@@ -180,17 +208,21 @@ def train(ctx, environment, envs, iters, seed, learner_kind):
         dist.barrier(); dist.destroy_process_group()
 
 
-def make_ppo_learner(kind, obs_dim, device, seed):
-    """the built-in PPO learner `train --learner` names: "torch" (ppo.PPO, the default) or "fused" (ppo.FusedPPO, HIP kernels)"""
+PPO_LR = 3e-4                                                # the learners' default learning rate: where --lr-schedule linear starts
+
+
+def make_ppo_learner(kind, obs_dim, device, seed, **terms):
+    """the built-in PPO learner `train --learner` names: "torch" (ppo.PPO, the default) or "fused" (ppo.FusedPPO, HIP kernels); terms: SB3's
+    remaining options (ent_coef, clip_range_vf, target_kl, normalize_advantage, lr_schedule), the same for both"""
     if kind == "torch":
-        return PPO(obs_dim, device, seed=seed)
+        return PPO(obs_dim, device, lr=PPO_LR, seed=seed, **terms)
     if kind != "fused":
         raise RuntimeError(f"unknown learner {kind!r}: torch or fused")
     if torch.device(device).type != "cuda":
         raise RuntimeError(f"--learner fused runs on a HIP device, not on {device}: there is no CPU fallback (use --learner torch)")
     if obs_dim not in (15, 8):
         raise RuntimeError(f"--learner fused is built for the so100 observations (obs_dim 15 or 8), not obs_dim {obs_dim}")
-    return FusedPPO(obs_dim, device, seed=seed)
+    return FusedPPO(obs_dim, device, lr=PPO_LR, seed=seed, **terms)
 
 
 def _train_ddpg(env, environment, model_path, save_dir, iters, seed, kind):

@@ -8,7 +8,10 @@ TimeLimit truncations are bootstrapped by the collector exactly as SB3 does (rew
 hipGraph-replayed update is gone: see PPO.__init__.)
 The network's state_dict keys equal SB3's ActorCriticPolicy keys, so checkpoints and RolloutCollector.load_policy()
 interoperate with an SB3 policy.
-FusedPPO is the same learner on the library's own kernels (include/so100_learn.h): same constructor, same update(b), same state_dict."""
+FusedPPO is the same learner on the library's own kernels (include/so100_learn.h): same constructor, same update(b), same state_dict.
+Both take SB3's remaining options -- ent_coef, clip_range_vf, per-minibatch advantage normalisation, target_kl, a learning-rate schedule --
+all off by default (then the loss is the one above, to the bit), and return SB3's per-update diagnostics."""
+import math
 import os
 
 import torch
@@ -40,9 +43,29 @@ class ActorCritic(nn.Module):
         return self.value(obs), logp
 
 
+ENTROPY_CONST = 0.5 + 0.5 * math.log(2.0 * math.pi)      # entropy of a unit Gaussian, per action dimension
+
+
+def _check_terms(ent_coef, clip_range_vf, normalize_advantage, target_kl):
+    if not ent_coef >= 0:
+        raise ValueError(f"ent_coef must be >= 0, got {ent_coef}")
+    if clip_range_vf is not None and not clip_range_vf > 0:
+        raise ValueError(f"clip_range_vf must be > 0 (None: no value clipping), got {clip_range_vf}")
+    if normalize_advantage not in ("batch", "minibatch"):
+        raise ValueError(f"normalize_advantage must be 'batch' or 'minibatch', got {normalize_advantage!r}")
+    if target_kl is not None and not target_kl > 0:
+        raise ValueError(f"target_kl must be > 0 (None: no early stop), got {target_kl}")
+
+
 class PPO:
+    """ent_coef, clip_range_vf, target_kl as in stable_baselines3.PPO; normalize_advantage "batch" normalises over the whole chunk (this
+    driver's default), "minibatch" per minibatch as SB3 does; lr_schedule(progress_remaining) as in SB3, evaluated once per update."""
+
     def __init__(self, obs_dim, device, lr=3e-4, gamma=0.99, gae_lambda=0.95, clip=0.2, epochs=4, minibatch=32768,
-                 vf_coef=0.5, max_grad_norm=0.5, seed=0, use_graph=False):
+                 vf_coef=0.5, max_grad_norm=0.5, seed=0, use_graph=False, ent_coef=0.0, clip_range_vf=None, normalize_advantage="batch",
+                 target_kl=None, lr_schedule=None):
+        _check_terms(ent_coef, clip_range_vf, normalize_advantage, target_kl)
+        self.ent_coef, self.clip_range_vf, self.normalize_advantage, self.target_kl, self.lr_schedule = ent_coef, clip_range_vf, normalize_advantage, target_kl, lr_schedule
         torch.manual_seed(seed)
         self.net = ActorCritic(obs_dim).to(device)
         on_gpu = torch.device(device).type == "cuda"
@@ -73,30 +96,57 @@ class PPO:
             S["ret"].copy_((S["adv"] + S["values"]).reshape(-1))
             a = S["adv"].reshape(-1)
             S["adv_n"].copy_((a - a.mean()) / (a.std() + 1e-8))
+            old_v = S["values"].reshape(-1)
+            var_ret = S["ret"].var(unbiased=False)
+            S["ev"].copy_(torch.where(var_ret == 0, torch.full_like(var_ret, float("nan")), 1 - (S["ret"] - old_v).var(unbiased=False) / var_ret))
 
     def _step(self):
+        """one minibatch step on the rows S["idx"]; returns False (and leaves parameters and optimiser alone) when target_kl stops the update.
+        S["diag"]: policy loss, value loss, approx_kl, entropy_loss, total loss of this minibatch."""
         S = self._s; net = self.net; idx = S["idx"]
         obs = S["obs"].reshape(-1, S["obs"].shape[-1]); act = S["actions"].reshape(-1, S["actions"].shape[-1])
         v, lp = net.evaluate(obs.index_select(0, idx), act.index_select(0, idx))
-        adv = S["adv_n"].index_select(0, idx)
-        ratio = (lp - S["log_probs"].reshape(-1).index_select(0, idx)).exp()
+        if self.normalize_advantage == "batch":
+            adv = S["adv_n"].index_select(0, idx)
+        else:
+            adv = S["adv"].reshape(-1).index_select(0, idx)
+            if adv.numel() > 1:
+                adv = (adv - adv.mean()) / (adv.std() + 1e-8)
+        log_ratio = lp - S["log_probs"].reshape(-1).index_select(0, idx)
+        ratio = log_ratio.exp()
         pg = -torch.min(ratio * adv, ratio.clamp(1 - self.clip, 1 + self.clip) * adv).mean()
+        if self.clip_range_vf is not None:
+            old_v = S["values"].reshape(-1).index_select(0, idx)
+            v = old_v + (v - old_v).clamp(-self.clip_range_vf, self.clip_range_vf)
         vl = (S["ret"].index_select(0, idx) - v).pow(2).mean()
-        loss = pg + self.vf_coef * vl
+        ent_loss = -(net.log_std.sum() + net.log_std.numel() * ENTROPY_CONST)         # -mean(entropy): the entropy is the same for every sample
+        loss = pg + self.vf_coef * vl if self.ent_coef == 0 else pg + self.ent_coef * ent_loss + self.vf_coef * vl
+        with torch.no_grad():
+            kl = ((ratio - 1) - log_ratio).mean()
+            S["diag"].copy_(torch.stack([pg, vl, kl, ent_loss, pg + self.ent_coef * ent_loss + self.vf_coef * vl]))
+        S["vl"].copy_(vl.detach())
+        if self.target_kl is not None and kl.item() > 1.5 * self.target_kl:
+            return False
         loss.backward()
         nn.utils.clip_grad_norm_(net.parameters(), self.max_grad_norm); self.opt.step()
-        S["vl"].copy_(vl.detach())
+        return True
 
     def _alloc(self, b):
         dev = self.device
         self._s = {k: torch.empty(b[k].shape, dtype=torch.float32, device=dev) for k in ("obs", "actions", "rewards", "dones", "values", "log_probs", "last_obs")}
         T, N = b["rewards"].shape
         self._s.update(adv=torch.zeros(T, N, device=dev), ret=torch.zeros(T * N, device=dev), adv_n=torch.zeros(T * N, device=dev),
-                       idx=torch.zeros(min(self.mb, T * N), dtype=torch.long, device=dev), vl=torch.zeros((), device=dev))
+                       idx=torch.zeros(min(self.mb, T * N), dtype=torch.long, device=dev), vl=torch.zeros((), device=dev),
+                       ev=torch.zeros((), device=dev), diag=torch.zeros(5, device=dev))
         self._shape = tuple(b["obs"].shape)
 
-    def update(self, b):
-        """b: RolloutCollector.collect() output ([T, N, ...] device tensors + last_obs)."""
+    def update(self, b, progress_remaining=1.0):
+        """b: RolloutCollector.collect() output ([T, N, ...] device tensors + last_obs).  progress_remaining: 1 at the start of training, 0 at
+        its end; the argument of lr_schedule.  Returns value_loss, approx_kl, entropy_loss and loss of the last minibatch evaluated (the one
+        that stopped the update, if target_kl did), explained_variance of the chunk, std after the update, n_updates (steps applied)."""
+        if self.lr_schedule is not None:
+            for g in self.opt.param_groups:
+                g["lr"] = float(self.lr_schedule(progress_remaining))
         if getattr(self, "_s", None) is None or self._shape != tuple(b["obs"].shape):
             self._alloc(b)
         S = self._s
@@ -104,17 +154,26 @@ class PPO:
             S[k].copy_(b[k])
         n = S["ret"].numel(); mb = S["idx"].numel()
         self._gae()
+        applied, stopped = 0, False
         for _ in range(self.epochs):
             perm = torch.randperm(n, device=self.device)
             for i in range(0, n, mb):
                 S["idx"] = perm[i:i + mb]
-                self.opt.zero_grad(set_to_none=True); self._step()
+                self.opt.zero_grad(set_to_none=True)
+                if not self._step():
+                    stopped = True
+                    break
+                applied += 1
+            if stopped:
+                break
         S["idx"] = torch.zeros(mb, dtype=torch.long, device=self.device)
         # mean_reward = the ENV's mean reward per step (the collector takes it before its TimeLimit bootstrap adds gamma * V to the
         # truncated steps); S["rewards"] holds the bootstrapped rewards the advantages are computed from
         raw = b.get("raw_reward_mean")
+        d = S["diag"].tolist()
         return {"value_loss": S["vl"].item(), "mean_reward": (raw if raw is not None else S["rewards"].mean()).item(),
-                "mean_bootstrapped_reward": S["rewards"].mean().item()}
+                "mean_bootstrapped_reward": S["rewards"].mean().item(), "approx_kl": d[2], "entropy_loss": d[3], "loss": d[4],
+                "explained_variance": S["ev"].item(), "std": self.net.log_std.detach().exp().mean().item(), "n_updates": applied, "early_stop": stopped}
 
 
 class FusedPPO:
@@ -125,9 +184,15 @@ class FusedPPO:
     ordinary policy while the kernels update the block in place.  All launches go to torch's current stream, as So100Sim's do."""
 
     def __init__(self, obs_dim, device, lr=3e-4, gamma=0.99, gae_lambda=0.95, clip=0.2, epochs=4, minibatch=32768,
-                 vf_coef=0.5, max_grad_norm=0.5, seed=0, use_graph=False):
+                 vf_coef=0.5, max_grad_norm=0.5, seed=0, use_graph=False, ent_coef=0.0, clip_range_vf=None, normalize_advantage="batch",
+                 target_kl=None, lr_schedule=None):
         from . import lib
         del use_graph
+        _check_terms(ent_coef, clip_range_vf, normalize_advantage, target_kl)
+        self.ent_coef, self.clip_range_vf, self.normalize_advantage, self.target_kl, self.lr_schedule = ent_coef, clip_range_vf, normalize_advantage, target_kl, lr_schedule
+        # any option on: the extended step (so100_learner_minibatch_step_ex); none: the step as it always was
+        self._extended = ent_coef != 0 or clip_range_vf is not None or normalize_advantage != "batch" or target_kl is not None or lr_schedule is not None
+        self.vf_coef = vf_coef
         torch.manual_seed(seed)
         self.net = ActorCritic(obs_dim)                          # the draws of PPO's initialisation for the same seed
         layout, P = lib.learner_layout(obs_dim)
@@ -146,6 +211,7 @@ class FusedPPO:
         self._hyper = dict(gamma=gamma, gae_lambda=gae_lambda, clip_range=clip, vf_coef=vf_coef, max_grad_norm=max_grad_norm, lr=lr, adam_eps=1e-5)
         self._learner = None
         self._shape = None
+        self._side = None
 
     def _handle(self):
         if self._learner is None:
@@ -170,33 +236,82 @@ class FusedPPO:
         return torch.cat([obs, b["actions"], b["rewards"].unsqueeze(-1), code.unsqueeze(-1), b["values"].unsqueeze(-1), b["log_probs"].unsqueeze(-1)],
                          dim=-1).to(self.device, torch.float32).contiguous()
 
-    def update(self, b, perms=None):
+    def update(self, b, perms=None, *, progress_remaining=1.0):
         """b: RolloutCollector.collect() output.  With b["terminal_obs"] (RolloutCollector(defer_bootstrap=True)) the TimeLimit bootstrap is
         applied by the advantage kernel; otherwise the rewards are taken as they are (the collector's eager bootstrap has been added).
         perms: one int64 permutation of range(T*N) per epoch (tests); default torch.randperm, drawn as PPO.update draws them.
         Returns PPO.update's keys plus policy_loss, clip_fraction and grad_norm of the last minibatch.  mean_bootstrapped_reward is the
         mean of the chunk's reward column: with a deferred bootstrap that column keeps the env's own rewards (the bootstrapped ones are
-        never materialised), so it then equals the raw mean."""
+        never materialised), so it then equals the raw mean.
+        Also PPO.update's diagnostics.  With an option on they come from the extended step: the last minibatch's, or the stopping one's if
+        target_kl stopped the update; the applied steps are counted on the device and read here, once, with the statistics -- nothing
+        synchronises in the middle of an update.  At the defaults the old step runs and approx_kl, which only the extended step forms, is NaN.
+        progress_remaining (keyword only, after perms: PPO.update(b, progress_remaining) has no perms) is the argument of lr_schedule.
+        The explained-variance launches go to a side stream, beside the minibatch steps, and are joined before the one read of the results."""
         L = self._handle()
         buf = self._packed(b)
         T, N = buf.shape[0], buf.shape[1]
         if self._shape != (T, N):
             dev = self.device
             self._adv = torch.zeros(T, N, device=dev); self._ret = torch.zeros(T, N, device=dev)
-            self._adv_stats = torch.zeros(2, device=dev); self._stats = torch.zeros(4, device=dev)
+            self._adv_stats = torch.zeros(2, device=dev)
+            # everything an update leaves for the host, in one buffer read in one transfer: [0:8] the step's statistics (the old step writes four,
+            # the extended one eight), [8] explained variance, [9:15] log_std before the last step (old step only), [15:21] log_std after the update,
+            # [21] mean of the reward column, [22] the env's own mean reward, [23:25] the update state (extended step only)
+            self._out = torch.zeros(25, device=dev)
+            self._stats, self._diag, self._ev = self._out[0:4], self._out[0:8], self._out[8:9]
+            self._state = torch.zeros(2, dtype=torch.int32, device=dev)
             self._shape = (T, N)
         tobs = b.get("terminal_obs")
         L.advantages(buf, b["last_obs"].contiguous(), self.params, self._adv, self._ret, self._adv_stats, terminal_obs=tobs)
+        cur = torch.cuda.current_stream(self.device)
+        if self._side is None:
+            self._side = torch.cuda.Stream(device=self.device)
+        self._side.wait_stream(cur)                                      # behind the advantages ...
+        with torch.cuda.stream(self._side):
+            L.explained_variance(buf, self._ret, self._ev)               # ... and beside the minibatch steps, which read the same buffers
         n = T * N; mb = min(self.mb, n)
-        for e in range(self.epochs):
-            perm = torch.randperm(n, device=self.device) if perms is None else perms[e]
-            for i in range(0, n, mb):
-                self.adam_step += 1
-                L.minibatch_step(buf, perm[i:i + mb], self._adv, self._ret, self._adv_stats, self.params, self.adam_m, self.adam_v, self.adam_step, self._stats)
         o = self.obs_dim
-        rew = buf[..., o + 6].mean()
-        raw = b.get("raw_reward_mean")
-        st = self._stats.tolist()
+        first_step = self.adam_step
+        if self._extended:
+            lr = None if self.lr_schedule is None else float(self.lr_schedule(progress_remaining))
+            self._state.zero_()
+            step = first_step
+            for e in range(self.epochs):
+                perm = torch.randperm(n, device=self.device) if perms is None else perms[e]
+                for i in range(0, n, mb):
+                    step += 1           # the number this step carries if it is applied: after a stop none is, so the applied ones are contiguous
+                    L.minibatch_step_ex(buf, perm[i:i + mb], self._adv, self._ret, self._adv_stats, self.params, self.adam_m, self.adam_v, step, self._diag,
+                                        ent_coef=self.ent_coef, clip_range_vf=self.clip_range_vf, normalize_advantage=self.normalize_advantage,
+                                        target_kl=self.target_kl, lr=lr, update_state=self._state)
+            total = step - first_step
+            self._out[23:25].copy_(self._state)
+            st = self._read_out(b, buf, cur)                             # the update's only synchronisation
+            stopped, applied = int(st[23]), int(st[24])
+            self.adam_step = first_step + applied
+            assert applied == total or stopped
+            extra = {"approx_kl": st[4], "entropy_loss": st[5], "loss": st[6], "value_clip_fraction": st[7], "n_updates": applied, "early_stop": bool(stopped)}
+        else:
+            last = self.epochs * ((n + mb - 1) // mb)
+            for e in range(self.epochs):
+                perm = torch.randperm(n, device=self.device) if perms is None else perms[e]
+                for i in range(0, n, mb):
+                    self.adam_step += 1
+                    if self.adam_step - first_step == last:
+                        self._out[9:15].copy_(self.net.log_std.detach())    # the entropy of the policy the last minibatch was evaluated with
+                    L.minibatch_step(buf, perm[i:i + mb], self._adv, self._ret, self._adv_stats, self.params, self.adam_m, self.adam_v, self.adam_step, self._stats)
+            st = self._read_out(b, buf, cur)
+            ent_loss = -(math.fsum(st[9:15]) + 6 * ENTROPY_CONST)
+            extra = {"approx_kl": float("nan"), "entropy_loss": ent_loss, "loss": st[0] + self.vf_coef * st[1], "n_updates": last, "early_stop": False}
         # mean_bootstrapped_reward: the mean of the chunk's reward column -- with a deferred bootstrap that column holds the env's own rewards
-        return {"value_loss": st[1], "mean_reward": (raw if raw is not None else rew).item(), "mean_bootstrapped_reward": rew.item(),
-                "policy_loss": st[0], "clip_fraction": st[2], "grad_norm": st[3]}
+        return {"value_loss": st[1], "mean_reward": st[22], "mean_bootstrapped_reward": st[21],
+                "policy_loss": st[0], "clip_fraction": st[2], "grad_norm": st[3], "explained_variance": st[8], "std": math.fsum(math.exp(x) for x in st[15:21]) / 6, **extra}
+
+    def _read_out(self, b, buf, cur):
+        """log_std after the update and the two reward means join the statistics in self._out (one small launch), the side stream is joined,
+        and the whole buffer comes to the host in one transfer"""
+        rew = buf[..., self.obs_dim + 6].mean().view(1)
+        raw = b.get("raw_reward_mean")
+        torch.cat([self.net.log_std.detach(), rew, rew if raw is None else raw.detach().to(torch.float32).view(1)], out=self._out[15:23])
+        cur.wait_stream(self._side)
+        return self._out.tolist()

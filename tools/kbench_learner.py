@@ -14,6 +14,12 @@ updates, the evaluations that fall into the run and the final saves; the driver'
 Every GPU step runs in a child process under its own time limit; the first one that fails ends the run.  One JSON document is written.
 
     python tools/kbench_learner.py --part update --obs-dim 15 [--rounds 1]      # one step by hand (e.g. under rocprofv3)
+    python tools/kbench_learner.py --terms [--out profiles/learner_terms_kbench.json] [--commit LABEL]
+
+--terms: the extended step (so100_learner_minibatch_step_ex, SB3's remaining loss terms) against the old one, per minibatch of 32 768 on the
+same chunk through the C ABI: the old step, the extended step with every term off, with entropy bonus and value clipping, with per-minibatch
+normalisation as well (one more launch: the difference is the cost of the statistics launch), and a skipped step (the update stopped by
+target_kl: every kernel returns at once).  Timed in alternation, `--rounds` times each, HIP events around 200 steps.
 """
 import argparse
 import json
@@ -71,6 +77,59 @@ def part_update(obs_dim, rounds, reps, warmup):
     print("KBENCH " + json.dumps(res), flush=True)
 
 
+def part_terms(obs_dim, rounds, reps=200, warmup=20):
+    import torch
+    from so100_mujoco_rl_amd.lib import So100Learner
+    from so100_mujoco_rl_amd.ppo import FusedPPO
+    dev = torch.device("cuda", 0)
+    g = torch.Generator(device=dev); g.manual_seed(obs_dim)
+    o = obs_dim
+    f = FusedPPO(o, dev, seed=0)
+    buf = torch.randn(T, N, o + 10, device=dev, generator=g)
+    with torch.no_grad():
+        v, lp = f.net.evaluate(buf[..., :o].reshape(-1, o), buf[..., o:o + 6].reshape(-1, 6))
+        buf[..., o + 8] = v.reshape(T, N) + 0.5 * torch.randn(T, N, device=dev, generator=g); buf[..., o + 9] = lp.reshape(T, N)
+        buf[..., o + 7] = (torch.rand(T, N, device=dev, generator=g) < 1e-3).float() * 2.0
+    L = So100Learner(o, dev, max_minibatch=MB)
+    P = L.num_params
+    adv = torch.zeros(T, N, device=dev); ret = torch.zeros(T, N, device=dev); adv_stats = torch.zeros(2, device=dev)
+    L.advantages(buf, torch.randn(N, o, device=dev, generator=g), f.params, adv, ret, adv_stats)
+    perm = torch.randperm(T * N, device=dev, generator=g)
+    idx = [perm[i:i + MB] for i in range(0, T * N, MB)]
+    stats = torch.zeros(4, device=dev); diag = torch.zeros(8, device=dev)
+    live = torch.zeros(2, dtype=torch.int32, device=dev); stopped = torch.tensor([1, 0], dtype=torch.int32, device=dev)
+    on = dict(ent_coef=0.01, clip_range_vf=0.3)
+    variants = {"old_step": None, "extended_every_term_off": {}, "extended_entropy_value_clip": dict(on, update_state=live, target_kl=1e9),
+                "extended_all_terms": dict(on, normalize_advantage="minibatch", update_state=live, target_kl=1e9),
+                "extended_skipped": dict(on, normalize_advantage="minibatch", update_state=stopped, target_kl=1e9)}
+
+    def run(kw, count):
+        p = f.params.clone(); m = torch.zeros(P, device=dev); v = torch.zeros(P, device=dev)          # every window starts from the same weights
+        e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize(); e0.record()
+        for i in range(count):
+            if kw is None:
+                L.minibatch_step(buf, idx[i % len(idx)], adv, ret, adv_stats, p, m, v, i + 1, stats)
+            else:
+                L.minibatch_step_ex(buf, idx[i % len(idx)], adv, ret, adv_stats, p, m, v, i + 1, diag, **kw)
+        e1.record(); torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / count
+
+    for kw in variants.values():
+        run(kw, warmup)
+    us = {k: [] for k in variants}
+    for _ in range(rounds):
+        for k, kw in variants.items():
+            us[k].append(round(run(kw, reps) * 1e3, 2))
+    med = {k: sorted(x)[len(x) // 2] for k, x in us.items()}
+    assert stopped.tolist() == [1, 0]
+    res = {"obs_dim": o, "minibatch": MB, "steps_per_window": reps, "card": torch.cuda.get_device_name(0), "us_per_minibatch_rounds": us, "us_per_minibatch": med,
+           "extended_all_terms_over_old_step": round(med["extended_all_terms"] / med["old_step"], 4),
+           "extended_every_term_off_over_old_step": round(med["extended_every_term_off"] / med["old_step"], 4),
+           "statistics_launch_us": round(med["extended_all_terms"] - med["extended_entropy_value_clip"], 2), "skipped_step_us": med["extended_skipped"]}
+    print("KBENCH " + json.dumps(res), flush=True)
+
+
 def part_train(learner, iters):
     import logging
     import time
@@ -102,7 +161,8 @@ def child(args, limit):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--part", choices=("all", "update", "train"), default="all")
+    ap.add_argument("--part", choices=("all", "update", "train", "terms"), default="all")
+    ap.add_argument("--terms", action="store_true", help="time the extended step with all terms on against the old one; writes profiles/learner_terms_kbench.json")
     ap.add_argument("--obs-dim", type=int, default=15); ap.add_argument("--learner", default="fused")
     ap.add_argument("--rounds", type=int, default=5); ap.add_argument("--warmup", type=int, default=3); ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "learner_update_kbench.json")); ap.add_argument("--commit", default="unknown")
@@ -111,6 +171,17 @@ def main():
         return part_update(a.obs_dim, a.rounds, {"torch": 10, "fused": 100}, a.warmup)      # >= 0.5 s per timed window
     if a.part == "train":
         return part_train(a.learner, a.iters)
+    if a.part == "terms":
+        return part_terms(a.obs_dim, a.rounds)
+    if a.terms:
+        doc = {"what": "one minibatch step of 32768 samples (64 x 4096 chunk): so100_learner_minibatch_step against so100_learner_minibatch_step_ex",
+               "commit": a.commit, "steps": [child(["--part", "terms", "--obs-dim", str(od), "--rounds", str(a.rounds)], 300) for od in (15, 8)]}
+        doc["card"] = doc["steps"][0]["card"]
+        out = a.out if a.out != ap.get_default("out") else os.path.join(ROOT, "profiles", "learner_terms_kbench.json")
+        with open(out, "w") as f:
+            json.dump(doc, f, indent=1); f.write("\n")
+        print(json.dumps(doc, indent=1))
+        return
     doc = {"what": "one PPO update (4 epochs x 8 minibatches of 32768 over 64 x 4096 samples) and main.py train end to end, PyTorch learner vs the HIP learner",
            "commit": a.commit, "update": [], "train": []}
     for od in (15, 8):
