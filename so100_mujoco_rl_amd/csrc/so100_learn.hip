@@ -1,6 +1,8 @@
 // so100_learn.hip -- the on-device PPO learner behind include/so100_learn.h: advantages (three launches) and one minibatch gradient
-// step (three launches; the extended step with SB3's remaining loss terms and the KL stop is the same three plus, under per-minibatch
-// normalisation, one for the minibatch's advantage statistics), for the fixed 2 x 64 tanh towers of so100_policy.hpp.  The per-sample and per-parameter arithmetic is in
+// step (three launches: gradient, reduction, Adam) for the fixed 2 x 64 tanh towers of so100_policy.hpp.  The step has two loss heads, chosen at
+// compile time (EX): the plain one of so100_learner_minibatch_step and the extended one of so100_learner_minibatch_step_ex with SB3's remaining
+// loss terms and the KL stop (under per-minibatch normalisation one more launch, for the minibatch's advantage statistics).  Everything around the
+// head -- checks, arguments, launches, kernels -- is written once.  The per-sample and per-parameter arithmetic is in
 // so100_learn.hpp (host-compilable templates, held to an fp64 reference by tests/_learncheck); this file holds the data movement.
 //
 // Gradient kernel (so100_learn_grad): a bounded persistent grid of 256-thread workgroups; each owns tiles of 64 samples gathered
@@ -13,7 +15,7 @@
 // and writes them once, as this workgroup's partial.  Plain FMA throughout: fp32-input MFMA runs at the VALU's rate on gfx950, and the
 // unit-major products have the samples on the reduced axis, which the MFMA operand layout would want transposed once more.
 // Reduction (so100_learn_reduce): one thread per parameter sums the partials in workgroup order and leaves each block's sum of
-// squares; so100_learn_adam sums those in block order (every thread the same sum), decides the clip and applies Adam.
+// squares; so100_learn_adam sums those in block order (every thread the same sum), decides the clip (EX: and the KL stop) and applies Adam.
 // No floating-point atomics anywhere; every sum has a fixed order => bit-identical results for identical inputs.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -21,6 +23,7 @@
 #include <string.h>
 #include <math.h>
 #include <new>
+#include <type_traits>
 #include "../../include/so100_learn.h"
 #include "so100_policy.hpp"
 #include "so100_learn.hpp"
@@ -47,11 +50,13 @@ struct GradArgs {
     float clip, vf_coef;
 };
 
-// the extended step (so100_learner_minibatch_step_ex): the old arguments first, so that tower_pass reads them under the same names
+// the extended head's arguments behind the plain ones, so that tower_pass reads those under the same names
 struct GradArgsEx : GradArgs {
     float ent_coef, clip_vf;           // clip_vf <= 0: no value clipping
     const int32_t* state;              // the caller's {stopped, steps_applied}, nullable
 };
+template <bool EX> using GradArgsOf = std::conditional_t<EX, GradArgsEx, GradArgs>;
+
 
 template <bool EX> struct HeadOf { using type = LossHead<float>; };
 template <> struct HeadOf<true> { using type = LossHeadEx<float>; };
@@ -62,7 +67,7 @@ struct GradSmem {
 };
 
 // one tower's forward and backward pass over this workgroup's tiles; writes the tower's slice of the workgroup's partial
-// EX selects the extended loss head (entropy bonus, value clipping, approx_kl) and its NSTAT_EX sums; without it the pass is the old one
+// EX selects the extended loss head (entropy bonus, value clipping, approx_kl) and its NSTAT_EX sums
 template <int OD, int TW, bool EX, class Args>
 __device__ __forceinline__ void tower_pass(const Args& A, GradSmem& S) {
     constexpr int ROW = OD + ROW_EXTRA, NH = TW ? 1 : ACT_DIM, P = num_params(OD), NS = EX ? NSTAT_EX : NSTAT;
@@ -267,26 +272,22 @@ __device__ __forceinline__ void tower_pass(const Args& A, GradSmem& S) {
     __syncthreads();
 }
 
-template <int OD>
-__global__ __launch_bounds__(256) void so100_learn_grad(GradArgs A) {
+// Like every kernel of an extended step, the EX one reads the update's `stopped` word first (set by so100_learn_adam_ex of an earlier step of
+// this update, never by a kernel of this step before this one ran).
+template <int OD, bool EX>
+__global__ __launch_bounds__(256) void so100_learn_grad(GradArgsOf<EX> A) {
+    if constexpr (EX) { if (A.state != nullptr && A.state[0] != 0) return; }
     __shared__ GradSmem S;
-    tower_pass<OD, 0, false>(A, S);
-    tower_pass<OD, 1, false>(A, S);
-}
-
-// The extended step's gradient kernel: the same passes with the extended head.  Like every kernel of that step it reads the update's
-// `stopped` word first (set by so100_learn_adam_ex of an earlier step of this update, never by a kernel of this step before this one ran).
-template <int OD>
-__global__ __launch_bounds__(256) void so100_learn_grad_ex(GradArgsEx A) {
-    if (A.state != nullptr && A.state[0] != 0) return;
-    __shared__ GradSmem S;
-    tower_pass<OD, 0, true>(A, S);
-    tower_pass<OD, 1, true>(A, S);
+    tower_pass<OD, 0, EX>(A, S);
+    tower_pass<OD, 1, EX>(A, S);
 }
 
 // one thread per entry of a partial: the sum over the G workgroups in workgroup order; each block leaves the sum of squares of its gradients
+// (state: the extended step's, read by it alone)
 template <int NS>
-__device__ __forceinline__ void reduce_partials(const float* __restrict__ partial, int G, int P, float* __restrict__ gsum, float* __restrict__ sq_block) {
+__global__ __launch_bounds__(256) void so100_learn_reduce(const float* __restrict__ partial, int G, int P, float* __restrict__ gsum, float* __restrict__ sq_block,
+                                                          const int32_t* __restrict__ state) {
+    if constexpr (NS == NSTAT_EX) { if (state != nullptr && state[0] != 0) return; }
     __shared__ float sq[256];
     const int p = blockIdx.x*256 + threadIdx.x, PS = P + NS;
     float s = 0.0f;
@@ -311,51 +312,27 @@ __device__ __forceinline__ void reduce_partials(const float* __restrict__ partia
     if (threadIdx.x == 0) sq_block[blockIdx.x] = sq[0];
 }
 
-__global__ __launch_bounds__(256) void so100_learn_reduce(const float* __restrict__ partial, int G, int P, float* __restrict__ gsum, float* __restrict__ sq_block) {
-    reduce_partials<NSTAT>(partial, G, P, gsum, sq_block);
-}
-
-__global__ __launch_bounds__(256) void so100_learn_reduce_ex(const float* __restrict__ partial, int G, int P, float* __restrict__ gsum, float* __restrict__ sq_block,
-                                                             const int32_t* __restrict__ state) {
-    if (state != nullptr && state[0] != 0) return;
-    reduce_partials<NSTAT_EX>(partial, G, P, gsum, sq_block);
-}
+constexpr int reduce_blocks(int P, int NS) { return (P + NS + 255)/256; }
 
 struct AdamArgs { float max_grad_norm, step_size, omb1, beta2, omb2, eps, bc2_sqrt, inv_mb; };     // formed in double on the host (clip_adam_update)
-
-__global__ __launch_bounds__(256) void so100_learn_adam(const float* __restrict__ gsum, const float* __restrict__ sq_block, int nblk, int P,
-                                                        float* __restrict__ params, float* __restrict__ m, float* __restrict__ v,
-                                                        float* __restrict__ grads_out, float* __restrict__ stats_out, AdamArgs a) {
-    float ss = 0.0f;
-    for (int b = 0; b < nblk; b++) ss += sq_block[b];                      // the same ordered sum in every thread
-    const float norm = lsqrt(ss), coef = clip_coefficient<float>(norm, a.max_grad_norm);
-    const int p = blockIdx.x*256 + threadIdx.x;
-    if (p < P) {
-        float pv = params[p], mv = m[p], vv = v[p];
-        const float g = clip_adam_update<float>(gsum[p], coef, pv, mv, vv, a.step_size, a.omb1, a.beta2, a.omb2, a.eps, a.bc2_sqrt);
-        params[p] = pv; m[p] = mv; v[p] = vv;
-        if (grads_out) grads_out[p] = g;
-    }
-    if (p == 0) {
-        stats_out[0] = gsum[P + 0]*a.inv_mb; stats_out[1] = gsum[P + 1]*a.inv_mb; stats_out[2] = gsum[P + 2]*a.inv_mb; stats_out[3] = norm;
-    }
-}
-
-// The extended step's Adam kernel, with the KL stop.  approx_kl comes from the reduced sums, so every thread of every block forms the same
-// value and takes the same decision.  Stopped: parameters and moments stay as they are, thread 0 sets state[0] and leaves the stopping
-// minibatch's diagnostics.  A block that starts after thread 0 has set the word returns at once -- what it would have decided anyway.
-// Applied: the step of so100_learn_adam, and state[1] counts it.  diag: the eight values of so100_learner_minibatch_step_ex.
 struct TermsArgs { float ent_coef, vf_coef, kl_limit; };               // kl_limit = 1.5 target_kl, <= 0: no stop
 
-__global__ __launch_bounds__(256) void so100_learn_adam_ex(const float* __restrict__ gsum, const float* __restrict__ sq_block, int nblk, int P,
-                                                           float* __restrict__ params, float* __restrict__ m, float* __restrict__ v,
-                                                           float* __restrict__ grads_out, float* __restrict__ diag, int32_t* state, AdamArgs a, TermsArgs t) {
-    if (state != nullptr && state[0] != 0) return;
+// Sums the blocks' sums of squares (every thread the same sum), decides the clip, applies Adam and leaves the step's statistics in out: the four
+// of so100_learner_minibatch_step, or (EX) the eight of so100_learner_minibatch_step_ex.
+// EX adds the KL stop.  approx_kl comes from the reduced sums, so every thread of every block forms the same value and takes the same
+// decision.  Stopped: parameters and moments stay as they are, thread 0 sets state[0] and leaves the stopping minibatch's diagnostics.  A block
+// that starts after thread 0 has set the word returns at once -- what it would have decided anyway.  Applied: state[1] counts the step.
+template <bool EX>
+__device__ __forceinline__ void adam_step(const float* __restrict__ gsum, const float* __restrict__ sq_block, int nblk, int P,
+                                          float* __restrict__ params, float* __restrict__ m, float* __restrict__ v,
+                                          float* __restrict__ grads_out, float* __restrict__ out, int32_t* state, const AdamArgs& a, const TermsArgs& t) {
+    if constexpr (EX) { if (state != nullptr && state[0] != 0) return; }
     float ss = 0.0f;
     for (int b = 0; b < nblk; b++) ss += sq_block[b];                      // the same ordered sum in every thread
     const float norm = lsqrt(ss), coef = clip_coefficient<float>(norm, a.max_grad_norm);
-    const float kl = gsum[P + 3]*a.inv_mb;
-    const bool stop = t.kl_limit > 0.0f && kl > t.kl_limit;
+    [[maybe_unused]] float kl = 0.0f;
+    bool stop = false;
+    if constexpr (EX) { kl = gsum[P + 3]*a.inv_mb; stop = t.kl_limit > 0.0f && kl > t.kl_limit; }
     const int p = blockIdx.x*256 + threadIdx.x;
     if (!stop && p < P) {
         float pv = params[p], mv = m[p], vv = v[p];
@@ -364,13 +341,30 @@ __global__ __launch_bounds__(256) void so100_learn_adam_ex(const float* __restri
         if (grads_out) grads_out[p] = g;
     }
     if (p == 0) {
-        const float pg = gsum[P + 0]*a.inv_mb, vl = gsum[P + 1]*a.inv_mb, ent_loss = -(gsum[P + 5]*a.inv_mb);
-        diag[0] = pg; diag[1] = vl; diag[2] = gsum[P + 2]*a.inv_mb; diag[3] = norm;
-        diag[4] = kl; diag[5] = ent_loss; diag[6] = pg + t.ent_coef*ent_loss + t.vf_coef*vl; diag[7] = gsum[P + 4]*a.inv_mb;
-        if (state != nullptr) {
-            if (stop) state[0] = 1; else state[1] += 1;
+        const float pg = gsum[P + 0]*a.inv_mb, vl = gsum[P + 1]*a.inv_mb;
+        [[maybe_unused]] float ent_loss = 0.0f;
+        if constexpr (EX) ent_loss = -(gsum[P + 5]*a.inv_mb);
+        out[0] = pg; out[1] = vl; out[2] = gsum[P + 2]*a.inv_mb; out[3] = norm;
+        if constexpr (EX) {
+            out[4] = kl; out[5] = ent_loss; out[6] = pg + t.ent_coef*ent_loss + t.vf_coef*vl; out[7] = gsum[P + 4]*a.inv_mb;
+            if (state != nullptr) {
+                if (stop) state[0] = 1; else state[1] += 1;
+            }
         }
     }
+}
+
+// the two argument lists differ in the middle (state lies before a), so each head keeps its own kernel around the one body
+__global__ __launch_bounds__(256) void so100_learn_adam(const float* __restrict__ gsum, const float* __restrict__ sq_block, int nblk, int P,
+                                                        float* __restrict__ params, float* __restrict__ m, float* __restrict__ v,
+                                                        float* __restrict__ grads_out, float* __restrict__ stats_out, AdamArgs a) {
+    adam_step<false>(gsum, sq_block, nblk, P, params, m, v, grads_out, stats_out, nullptr, a, TermsArgs{});
+}
+
+__global__ __launch_bounds__(256) void so100_learn_adam_ex(const float* __restrict__ gsum, const float* __restrict__ sq_block, int nblk, int P,
+                                                           float* __restrict__ params, float* __restrict__ m, float* __restrict__ v,
+                                                           float* __restrict__ grads_out, float* __restrict__ diag, int32_t* state, AdamArgs a, TermsArgs t) {
+    adam_step<true>(gsum, sq_block, nblk, P, params, m, v, grads_out, diag, state, a, t);
 }
 
 // ---- advantages -------------------------------------------------------------------------------------------------------------------------
@@ -550,13 +544,74 @@ using namespace so100::learn;
 
 struct so100_learner {
     so100_learner_config cfg;
-    int P = 0, grid_max = 0, nblk = 0, nblk_ex = 0;
-    float* partial = nullptr;      // [grid_max][P + NSTAT_EX] per-workgroup partial gradients (the old step strides them by P + NSTAT)
+    int P = 0, grid_max = 0;
+    float* partial = nullptr;      // [grid_max][P + NSTAT_EX] per-workgroup partial gradients (the plain head strides them by P + NSTAT)
     float* gsum = nullptr;         // [P + NSTAT_EX] their ordered sum
-    float* sq_block = nullptr;     // [nblk_ex] sum of squares per block of the reduction
+    float* sq_block = nullptr;     // [reduce_blocks(P, NSTAT_EX)] sum of squares per block of the reduction
     float* mb_stats = nullptr;     // [2] mean and std of the minibatch's advantages (normalize_advantage = 1)
     float* ev_part = nullptr;      // [EV_GRID_MAX][EV_PART] per-workgroup moments of so100_learner_explained_variance
 };
+
+static AdamArgs adam_args(const so100_learner_config& c, double lr, int adam_step, int mb) {
+    AdamArgs a;
+    a.max_grad_norm = c.max_grad_norm;
+    a.step_size = (float)(lr/(1.0 - pow(c.beta1, (double)adam_step))); a.bc2_sqrt = (float)sqrt(1.0 - pow(c.beta2, (double)adam_step));
+    a.omb1 = (float)(1.0 - c.beta1); a.beta2 = (float)c.beta2; a.omb2 = (float)(1.0 - c.beta2); a.eps = (float)c.adam_eps;
+    a.inv_mb = 1.0f/(float)mb;
+    return a;
+}
+
+// The step behind both entry points.  terms null: the plain head, out_dev takes its four statistics; given: the extended head, out_dev takes
+// the eight diagnostics and state_dev (nullable) is the update's {stopped, steps_applied}.  fn: the entry point's name, for the messages.
+static int minibatch_step(so100_learner* L, const so100_minibatch_io* io, const so100_ppo_terms* terms, float* out_dev, int32_t* state_dev, void* stream, const char* fn) {
+    if (!L || !io) return fail(SO100_E_INVALID, "%s: null argument", fn);
+    if (io->mb < 1 || io->mb > L->cfg.max_minibatch) return fail(SO100_E_INVALID, "%s: mb must be in 1..max_minibatch, got %d", fn, io->mb);
+    if (io->num_samples < 1) return fail(SO100_E_INVALID, "%s: num_samples must be >= 1, got %ld", fn, (long)io->num_samples);
+    if (io->adam_step < 1) return fail(SO100_E_INVALID, "%s: adam_step is 1-based, got %d", fn, io->adam_step);
+    if (!io->rollout_dev || !io->adv_dev || !io->ret_dev || !io->adv_stats_dev || !io->params_dev || !io->adam_m_dev || !io->adam_v_dev || !out_dev)
+        return fail(SO100_E_INVALID, "%s: rollout/adv/ret/adv_stats/params/adam_m/adam_v/%s pointers are required", fn, terms ? "diag" : "stats");
+    if (terms) {
+        if (!(terms->ent_coef >= 0.0f)) return fail(SO100_E_INVALID, "%s: ent_coef must be >= 0", fn);
+        if (terms->clip_range_vf != terms->clip_range_vf) return fail(SO100_E_INVALID, "%s: clip_range_vf is NaN (<= 0 means off)", fn);
+        if (terms->target_kl != terms->target_kl) return fail(SO100_E_INVALID, "%s: target_kl is NaN (<= 0 means off)", fn);
+        if (terms->normalize_advantage != 0 && terms->normalize_advantage != 1)
+            return fail(SO100_E_INVALID, "%s: normalize_advantage must be 0 (batch) or 1 (minibatch), got %d", fn, terms->normalize_advantage);
+        if (terms->lr != terms->lr) return fail(SO100_E_INVALID, "%s: lr is NaN (negative means the handle's)", fn);
+        if (terms->target_kl > 0.0f && !state_dev) return fail(SO100_E_INVALID, "%s: target_kl needs the update-state pointer", fn);
+    }
+    SO100_ON_DEVICE(L->cfg.device, fn);
+    const hipStream_t st = (hipStream_t)stream;
+    const int tiles = (io->mb + LT - 1)/LT, G = tiles < L->grid_max ? tiles : L->grid_max;
+    const dim3 pblocks((unsigned)((L->P + 255)/256)), threads(256);
+    GradArgsEx A;
+    A.chunk = io->rollout_dev; A.num_samples = (long)io->num_samples; A.idx = io->idx_dev; A.mb = io->mb;
+    A.adv = io->adv_dev; A.ret = io->ret_dev; A.adv_stats = io->adv_stats_dev; A.params = io->params_dev; A.partial = L->partial;
+    A.clip = L->cfg.clip_range; A.vf_coef = L->cfg.vf_coef;
+    if (terms) {
+        A.ent_coef = terms->ent_coef; A.clip_vf = terms->clip_range_vf > 0.0f ? terms->clip_range_vf : 0.0f; A.state = state_dev;
+        if (terms->normalize_advantage == 1) {
+            hipLaunchKernelGGL(so100_learn_mb_adv_stats, dim3(1), dim3(ADV_THREADS), 0, st, io->adv_dev, (long)io->num_samples, io->idx_dev, io->mb, L->mb_stats, A.state);
+            A.adv_stats = L->mb_stats;
+        }
+        const int nblk = reduce_blocks(L->P, NSTAT_EX);
+        const AdamArgs a = adam_args(L->cfg, terms->lr < 0.0 ? L->cfg.lr : terms->lr, io->adam_step, io->mb);
+        const TermsArgs t = { terms->ent_coef, L->cfg.vf_coef, terms->target_kl > 0.0f ? (float)(1.5*(double)terms->target_kl) : 0.0f };
+        SO100_WITH_OBS_DIM(L->cfg.obs_dim, hipLaunchKernelGGL((so100_learn_grad<OD, true>), dim3((unsigned)G), threads, 0, st, A););
+        hipLaunchKernelGGL(so100_learn_reduce<NSTAT_EX>, dim3((unsigned)nblk), threads, 0, st, (const float*)L->partial, G, L->P, L->gsum, L->sq_block, A.state);
+        hipLaunchKernelGGL(so100_learn_adam_ex, pblocks, threads, 0, st, (const float*)L->gsum, (const float*)L->sq_block, nblk, L->P,
+                           io->params_dev, io->adam_m_dev, io->adam_v_dev, io->grads_dev, out_dev, state_dev, a, t);
+    } else {
+        const int nblk = reduce_blocks(L->P, NSTAT);
+        const AdamArgs a = adam_args(L->cfg, L->cfg.lr, io->adam_step, io->mb);
+        SO100_WITH_OBS_DIM(L->cfg.obs_dim, hipLaunchKernelGGL((so100_learn_grad<OD, false>), dim3((unsigned)G), threads, 0, st, static_cast<const GradArgs&>(A)););
+        hipLaunchKernelGGL(so100_learn_reduce<NSTAT>, dim3((unsigned)nblk), threads, 0, st, (const float*)L->partial, G, L->P, L->gsum, L->sq_block, (const int32_t*)nullptr);
+        hipLaunchKernelGGL(so100_learn_adam, pblocks, threads, 0, st, (const float*)L->gsum, (const float*)L->sq_block, nblk, L->P,
+                           io->params_dev, io->adam_m_dev, io->adam_v_dev, io->grads_dev, out_dev, a);
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(SO100_E_LAUNCH, "%s: %s (HIP error %ld)", fn, hipGetErrorString(e), (long)e);
+    return 0;
+}
 
 extern "C" {
 
@@ -599,11 +654,9 @@ int so100_learner_create(const so100_learner_config* cfg, so100_learner** out) {
     L->P = num_params(cfg->obs_dim == 15 ? 15 : 8);
     const long tiles = ((long)cfg->max_minibatch + LT - 1)/LT;
     L->grid_max = (int)(tiles < GRID_MAX ? tiles : GRID_MAX);
-    L->nblk = (L->P + NSTAT + 255)/256;
-    L->nblk_ex = (L->P + NSTAT_EX + 255)/256;
     const size_t ps = (size_t)(L->P + NSTAT_EX);
     if (hipMalloc(&L->partial, (size_t)L->grid_max*ps*sizeof(float)) != hipSuccess || hipMalloc(&L->gsum, ps*sizeof(float)) != hipSuccess ||
-        hipMalloc(&L->sq_block, (size_t)L->nblk_ex*sizeof(float)) != hipSuccess || hipMalloc(&L->mb_stats, 2*sizeof(float)) != hipSuccess ||
+        hipMalloc(&L->sq_block, (size_t)reduce_blocks(L->P, NSTAT_EX)*sizeof(float)) != hipSuccess || hipMalloc(&L->mb_stats, 2*sizeof(float)) != hipSuccess ||
         hipMalloc(&L->ev_part, (size_t)EV_GRID_MAX*EV_PART*sizeof(float)) != hipSuccess) {
         so100_learner_destroy(L);
         return fail(SO100_E_NOMEM, "so100_learner_create: hipMalloc of the partial-gradient scratch failed");
@@ -644,76 +697,12 @@ int so100_learner_advantages(so100_learner* L, const so100_advantages_io* io, in
 }
 
 int so100_learner_minibatch_step(so100_learner* L, const so100_minibatch_io* io, void* stream) {
-    if (!L || !io) return fail(SO100_E_INVALID, "so100_learner_minibatch_step: null argument");
-    if (io->mb < 1 || io->mb > L->cfg.max_minibatch) return fail(SO100_E_INVALID, "so100_learner_minibatch_step: mb must be in 1..max_minibatch, got %d", io->mb);
-    if (io->num_samples < 1) return fail(SO100_E_INVALID, "so100_learner_minibatch_step: num_samples must be >= 1, got %ld", (long)io->num_samples);
-    if (io->adam_step < 1) return fail(SO100_E_INVALID, "so100_learner_minibatch_step: adam_step is 1-based, got %d", io->adam_step);
-    if (!io->rollout_dev || !io->adv_dev || !io->ret_dev || !io->adv_stats_dev || !io->params_dev || !io->adam_m_dev || !io->adam_v_dev || !io->stats_dev)
-        return fail(SO100_E_INVALID, "so100_learner_minibatch_step: rollout/adv/ret/adv_stats/params/adam_m/adam_v/stats pointers are required");
-    SO100_ON_DEVICE(L->cfg.device, "so100_learner_minibatch_step");
-    const hipStream_t st = (hipStream_t)stream;
-    const int tiles = (io->mb + LT - 1)/LT, G = tiles < L->grid_max ? tiles : L->grid_max;
-    GradArgs A;
-    A.chunk = io->rollout_dev; A.num_samples = (long)io->num_samples; A.idx = io->idx_dev; A.mb = io->mb;
-    A.adv = io->adv_dev; A.ret = io->ret_dev; A.adv_stats = io->adv_stats_dev; A.params = io->params_dev; A.partial = L->partial;
-    A.clip = L->cfg.clip_range; A.vf_coef = L->cfg.vf_coef;
-    SO100_WITH_OBS_DIM(L->cfg.obs_dim, hipLaunchKernelGGL((so100_learn_grad<OD>), dim3((unsigned)G), dim3(256), 0, st, A););
-    hipLaunchKernelGGL(so100_learn_reduce, dim3((unsigned)L->nblk), dim3(256), 0, st, (const float*)L->partial, G, L->P, L->gsum, L->sq_block);
-    AdamArgs a;
-    a.max_grad_norm = L->cfg.max_grad_norm;
-    a.step_size = (float)(L->cfg.lr/(1.0 - pow(L->cfg.beta1, (double)io->adam_step))); a.bc2_sqrt = (float)sqrt(1.0 - pow(L->cfg.beta2, (double)io->adam_step));
-    a.omb1 = (float)(1.0 - L->cfg.beta1); a.beta2 = (float)L->cfg.beta2; a.omb2 = (float)(1.0 - L->cfg.beta2); a.eps = (float)L->cfg.adam_eps;
-    a.inv_mb = 1.0f/(float)io->mb;
-    hipLaunchKernelGGL(so100_learn_adam, dim3((unsigned)((L->P + 255)/256)), dim3(256), 0, st, (const float*)L->gsum, (const float*)L->sq_block, L->nblk, L->P,
-                       io->params_dev, io->adam_m_dev, io->adam_v_dev, io->grads_dev, io->stats_dev, a);
-    HIP_TRY(hipGetLastError(), SO100_E_LAUNCH, "so100_learner_minibatch_step: ");
-    return 0;
+    return minibatch_step(L, io, nullptr, io ? io->stats_dev : nullptr, nullptr, stream, "so100_learner_minibatch_step");
 }
 
 int so100_learner_minibatch_step_ex(so100_learner* L, const so100_minibatch_io* io, const so100_ppo_terms* terms, float* diag_dev, int32_t* update_state_dev, void* stream) {
-    if (!L || !io || !terms) return fail(SO100_E_INVALID, "so100_learner_minibatch_step_ex: null argument");
-    if (io->mb < 1 || io->mb > L->cfg.max_minibatch) return fail(SO100_E_INVALID, "so100_learner_minibatch_step_ex: mb must be in 1..max_minibatch, got %d", io->mb);
-    if (io->num_samples < 1) return fail(SO100_E_INVALID, "so100_learner_minibatch_step_ex: num_samples must be >= 1, got %ld", (long)io->num_samples);
-    if (io->adam_step < 1) return fail(SO100_E_INVALID, "so100_learner_minibatch_step_ex: adam_step is 1-based, got %d", io->adam_step);
-    if (!io->rollout_dev || !io->adv_dev || !io->ret_dev || !io->adv_stats_dev || !io->params_dev || !io->adam_m_dev || !io->adam_v_dev || !diag_dev)
-        return fail(SO100_E_INVALID, "so100_learner_minibatch_step_ex: rollout/adv/ret/adv_stats/params/adam_m/adam_v/diag pointers are required");
-    if (!(terms->ent_coef >= 0.0f)) return fail(SO100_E_INVALID, "so100_learner_minibatch_step_ex: ent_coef must be >= 0");
-    if (terms->clip_range_vf != terms->clip_range_vf) return fail(SO100_E_INVALID, "so100_learner_minibatch_step_ex: clip_range_vf is NaN (<= 0 means off)");
-    if (terms->target_kl != terms->target_kl) return fail(SO100_E_INVALID, "so100_learner_minibatch_step_ex: target_kl is NaN (<= 0 means off)");
-    if (terms->normalize_advantage != 0 && terms->normalize_advantage != 1)
-        return fail(SO100_E_INVALID, "so100_learner_minibatch_step_ex: normalize_advantage must be 0 (batch) or 1 (minibatch), got %d", terms->normalize_advantage);
-    if (terms->lr != terms->lr) return fail(SO100_E_INVALID, "so100_learner_minibatch_step_ex: lr is NaN (negative means the handle's)");
-    if (terms->target_kl > 0.0f && !update_state_dev)
-        return fail(SO100_E_INVALID, "so100_learner_minibatch_step_ex: target_kl needs the update-state pointer");
-    if (L->cfg.obs_dim != 15 && L->cfg.obs_dim != 8)
-        return fail(SO100_E_INVALID, "so100_learner_minibatch_step_ex: no extended gradient kernel for obs_dim %d", L->cfg.obs_dim);
-    SO100_ON_DEVICE(L->cfg.device, "so100_learner_minibatch_step_ex");
-    const hipStream_t st = (hipStream_t)stream;
-    const int tiles = (io->mb + LT - 1)/LT, G = tiles < L->grid_max ? tiles : L->grid_max;
-    const int32_t* state = update_state_dev;
-    GradArgsEx A;
-    A.chunk = io->rollout_dev; A.num_samples = (long)io->num_samples; A.idx = io->idx_dev; A.mb = io->mb;
-    A.adv = io->adv_dev; A.ret = io->ret_dev; A.adv_stats = io->adv_stats_dev; A.params = io->params_dev; A.partial = L->partial;
-    A.clip = L->cfg.clip_range; A.vf_coef = L->cfg.vf_coef;
-    A.ent_coef = terms->ent_coef; A.clip_vf = terms->clip_range_vf > 0.0f ? terms->clip_range_vf : 0.0f; A.state = state;
-    if (terms->normalize_advantage == 1) {
-        hipLaunchKernelGGL(so100_learn_mb_adv_stats, dim3(1), dim3(ADV_THREADS), 0, st, io->adv_dev, (long)io->num_samples, io->idx_dev, io->mb, L->mb_stats, state);
-        A.adv_stats = L->mb_stats;
-    }
-    SO100_WITH_OBS_DIM(L->cfg.obs_dim, hipLaunchKernelGGL((so100_learn_grad_ex<OD>), dim3((unsigned)G), dim3(256), 0, st, A););
-    hipLaunchKernelGGL(so100_learn_reduce_ex, dim3((unsigned)L->nblk_ex), dim3(256), 0, st, (const float*)L->partial, G, L->P, L->gsum, L->sq_block, state);
-    const double lr = terms->lr < 0.0 ? L->cfg.lr : terms->lr;
-    AdamArgs a;
-    a.max_grad_norm = L->cfg.max_grad_norm;
-    a.step_size = (float)(lr/(1.0 - pow(L->cfg.beta1, (double)io->adam_step))); a.bc2_sqrt = (float)sqrt(1.0 - pow(L->cfg.beta2, (double)io->adam_step));
-    a.omb1 = (float)(1.0 - L->cfg.beta1); a.beta2 = (float)L->cfg.beta2; a.omb2 = (float)(1.0 - L->cfg.beta2); a.eps = (float)L->cfg.adam_eps;
-    a.inv_mb = 1.0f/(float)io->mb;
-    TermsArgs t;
-    t.ent_coef = terms->ent_coef; t.vf_coef = L->cfg.vf_coef; t.kl_limit = terms->target_kl > 0.0f ? (float)(1.5*(double)terms->target_kl) : 0.0f;
-    hipLaunchKernelGGL(so100_learn_adam_ex, dim3((unsigned)((L->P + 255)/256)), dim3(256), 0, st, (const float*)L->gsum, (const float*)L->sq_block, L->nblk_ex, L->P,
-                       io->params_dev, io->adam_m_dev, io->adam_v_dev, io->grads_dev, diag_dev, update_state_dev, a, t);
-    HIP_TRY(hipGetLastError(), SO100_E_LAUNCH, "so100_learner_minibatch_step_ex: ");
-    return 0;
+    if (!terms) return fail(SO100_E_INVALID, "so100_learner_minibatch_step_ex: null argument");
+    return minibatch_step(L, io, terms, diag_dev, update_state_dev, stream, "so100_learner_minibatch_step_ex");
 }
 
 int so100_learner_explained_variance(so100_learner* L, const float* rollout_dev, const float* ret_dev, int64_t num_samples, float* out_dev, void* stream) {

@@ -518,18 +518,22 @@ class So100Learner(_Handle):
                           _ptr(params, f, (self.num_params,), d), _ptr(adv, f, (T, N), d), _ptr(ret, f, (T, N), d), _ptr(adv_stats, f, (2,), d))
         _check(self.L.so100_learner_advantages(self.h, C.byref(io), T, N, self._stream()), "so100_learner_advantages")
 
-    def minibatch_step(self, rollout, idx, adv, ret, adv_stats, params, adam_m, adam_v, adam_step, stats, grads=None):
-        """One PPO gradient step on the rows idx of the packed chunk: an int64 [mb] tensor of flat indices t*N + n in any order, or an int mb
-        for rows 0..mb-1.  params / adam_m / adam_v are updated in place; stats [4] (LEARNER_STATS) and optionally grads [P] are written."""
+    def _minibatch_io(self, rollout, idx, adv, ret, adv_stats, params, adam_m, adam_v, adam_step, stats, grads):
+        """the so100_minibatch_io of both steps.  idx: an int64 [mb] tensor of flat indices t*N + n in any order, or an int mb for rows 0..mb-1"""
         T, N = rollout.shape[0], rollout.shape[1]
         f, d, o, P = torch.float32, self.device, self.obs_dim, self.num_params
         if isinstance(idx, int):
             mb, ip = idx, None
         else:
             mb = idx.numel(); ip = _ptr(idx, torch.int64, (mb,), d)
-        io = MinibatchIO(_ptr(rollout, f, (T, N, o + 10), d), T * N, ip, mb, adam_step, _ptr(adv, f, (T, N), d), _ptr(ret, f, (T, N), d),
-                         _ptr(adv_stats, f, (2,), d), _ptr(params, f, (P,), d), _ptr(adam_m, f, (P,), d), _ptr(adam_v, f, (P,), d),
-                         _ptr(stats, f, (4,), d), _ptr(grads, f, (P,), d))
+        return MinibatchIO(_ptr(rollout, f, (T, N, o + 10), d), T * N, ip, mb, adam_step, _ptr(adv, f, (T, N), d), _ptr(ret, f, (T, N), d),
+                           _ptr(adv_stats, f, (2,), d), _ptr(params, f, (P,), d), _ptr(adam_m, f, (P,), d), _ptr(adam_v, f, (P,), d),
+                           _ptr(stats, f, (4,), d), _ptr(grads, f, (P,), d))
+
+    def minibatch_step(self, rollout, idx, adv, ret, adv_stats, params, adam_m, adam_v, adam_step, stats, grads=None):
+        """One PPO gradient step on the rows idx of the packed chunk: an int64 [mb] tensor of flat indices t*N + n in any order, or an int mb
+        for rows 0..mb-1.  params / adam_m / adam_v are updated in place; stats [4] (LEARNER_STATS) and optionally grads [P] are written."""
+        io = self._minibatch_io(rollout, idx, adv, ret, adv_stats, params, adam_m, adam_v, adam_step, stats, grads)
         _check(self.L.so100_learner_minibatch_step(self.h, C.byref(io), self._stream()), "so100_learner_minibatch_step")
 
     def minibatch_step_ex(self, rollout, idx, adv, ret, adv_stats, params, adam_m, adam_v, adam_step, diag, ent_coef=0.0, clip_range_vf=None,
@@ -537,21 +541,13 @@ class So100Learner(_Handle):
         """minibatch_step with SB3's remaining loss terms (so100_ppo_terms): diag [8] (LEARNER_DIAG) is written instead of stats.
         clip_range_vf / target_kl None: off; lr None: the handle's.  update_state: int32 [2] {stopped, steps_applied}, zeroed by the caller
         at the start of an update; required with target_kl."""
-        T, N = rollout.shape[0], rollout.shape[1]
-        f, d, o, P = torch.float32, self.device, self.obs_dim, self.num_params
-        if isinstance(idx, int):
-            mb, ip = idx, None
-        else:
-            mb = idx.numel(); ip = _ptr(idx, torch.int64, (mb,), d)
+        io = self._minibatch_io(rollout, idx, adv, ret, adv_stats, params, adam_m, adam_v, adam_step, None, grads)
         if normalize_advantage not in NORMALIZE_ADVANTAGE:
             raise So100Error(f"normalize_advantage must be one of {sorted(NORMALIZE_ADVANTAGE)}, got {normalize_advantage!r}")
-        io = MinibatchIO(_ptr(rollout, f, (T, N, o + 10), d), T * N, ip, mb, adam_step, _ptr(adv, f, (T, N), d), _ptr(ret, f, (T, N), d),
-                         _ptr(adv_stats, f, (2,), d), _ptr(params, f, (P,), d), _ptr(adam_m, f, (P,), d), _ptr(adam_v, f, (P,), d),
-                         None, _ptr(grads, f, (P,), d))
         terms = PpoTerms(ent_coef, 0.0 if clip_range_vf is None else clip_range_vf, NORMALIZE_ADVANTAGE[normalize_advantage],
                          0.0 if target_kl is None else target_kl, -1.0 if lr is None else lr)
-        _check(self.L.so100_learner_minibatch_step_ex(self.h, C.byref(io), C.byref(terms), _ptr(diag, f, (8,), d), _ptr(update_state, torch.int32, (2,), d),
-                                                      self._stream()), "so100_learner_minibatch_step_ex")
+        _check(self.L.so100_learner_minibatch_step_ex(self.h, C.byref(io), C.byref(terms), _ptr(diag, torch.float32, (8,), self.device),
+                                                      _ptr(update_state, torch.int32, (2,), self.device), self._stream()), "so100_learner_minibatch_step_ex")
 
     def explained_variance(self, rollout, ret, out):
         """out [1] = 1 - var(ret - old_V)/var(ret) over the chunk (old_V: the value column of the packed chunk); NaN when var(ret) is 0"""

@@ -46,7 +46,8 @@ class ActorCritic(nn.Module):
 ENTROPY_CONST = 0.5 + 0.5 * math.log(2.0 * math.pi)      # entropy of a unit Gaussian, per action dimension
 
 
-def _check_terms(ent_coef, clip_range_vf, normalize_advantage, target_kl):
+def _set_terms(learner, ent_coef, clip_range_vf, normalize_advantage, target_kl, lr_schedule):
+    """checks SB3's optional terms and stores them on a PPO / FusedPPO"""
     if not ent_coef >= 0:
         raise ValueError(f"ent_coef must be >= 0, got {ent_coef}")
     if clip_range_vf is not None and not clip_range_vf > 0:
@@ -55,6 +56,7 @@ def _check_terms(ent_coef, clip_range_vf, normalize_advantage, target_kl):
         raise ValueError(f"normalize_advantage must be 'batch' or 'minibatch', got {normalize_advantage!r}")
     if target_kl is not None and not target_kl > 0:
         raise ValueError(f"target_kl must be > 0 (None: no early stop), got {target_kl}")
+    learner.ent_coef, learner.clip_range_vf, learner.normalize_advantage, learner.target_kl, learner.lr_schedule = ent_coef, clip_range_vf, normalize_advantage, target_kl, lr_schedule
 
 
 class PPO:
@@ -64,8 +66,7 @@ class PPO:
     def __init__(self, obs_dim, device, lr=3e-4, gamma=0.99, gae_lambda=0.95, clip=0.2, epochs=4, minibatch=32768,
                  vf_coef=0.5, max_grad_norm=0.5, seed=0, use_graph=False, ent_coef=0.0, clip_range_vf=None, normalize_advantage="batch",
                  target_kl=None, lr_schedule=None):
-        _check_terms(ent_coef, clip_range_vf, normalize_advantage, target_kl)
-        self.ent_coef, self.clip_range_vf, self.normalize_advantage, self.target_kl, self.lr_schedule = ent_coef, clip_range_vf, normalize_advantage, target_kl, lr_schedule
+        _set_terms(self, ent_coef, clip_range_vf, normalize_advantage, target_kl, lr_schedule)
         torch.manual_seed(seed)
         self.net = ActorCritic(obs_dim).to(device)
         on_gpu = torch.device(device).type == "cuda"
@@ -188,8 +189,7 @@ class FusedPPO:
                  target_kl=None, lr_schedule=None):
         from . import lib
         del use_graph
-        _check_terms(ent_coef, clip_range_vf, normalize_advantage, target_kl)
-        self.ent_coef, self.clip_range_vf, self.normalize_advantage, self.target_kl, self.lr_schedule = ent_coef, clip_range_vf, normalize_advantage, target_kl, lr_schedule
+        _set_terms(self, ent_coef, clip_range_vf, normalize_advantage, target_kl, lr_schedule)
         # any option on: the extended step (so100_learner_minibatch_step_ex); none: the step as it always was
         self._extended = ent_coef != 0 or clip_range_vf is not None or normalize_advantage != "batch" or target_kl is not None or lr_schedule is not None
         self.vf_coef = vf_coef
@@ -271,38 +271,36 @@ class FusedPPO:
         with torch.cuda.stream(self._side):
             L.explained_variance(buf, self._ret, self._ev)               # ... and beside the minibatch steps, which read the same buffers
         n = T * N; mb = min(self.mb, n)
-        o = self.obs_dim
         first_step = self.adam_step
+        last = first_step + self.epochs * ((n + mb - 1) // mb)
         if self._extended:
             lr = None if self.lr_schedule is None else float(self.lr_schedule(progress_remaining))
             self._state.zero_()
-            step = first_step
-            for e in range(self.epochs):
-                perm = torch.randperm(n, device=self.device) if perms is None else perms[e]
-                for i in range(0, n, mb):
-                    step += 1           # the number this step carries if it is applied: after a stop none is, so the applied ones are contiguous
+        step = first_step
+        for e in range(self.epochs):
+            perm = torch.randperm(n, device=self.device) if perms is None else perms[e]
+            for i in range(0, n, mb):
+                step += 1               # the number this step carries if it is applied: after a stop none is, so the applied ones are contiguous
+                if self._extended:
                     L.minibatch_step_ex(buf, perm[i:i + mb], self._adv, self._ret, self._adv_stats, self.params, self.adam_m, self.adam_v, step, self._diag,
                                         ent_coef=self.ent_coef, clip_range_vf=self.clip_range_vf, normalize_advantage=self.normalize_advantage,
                                         target_kl=self.target_kl, lr=lr, update_state=self._state)
-            total = step - first_step
+                else:
+                    if step == last:
+                        self._out[9:15].copy_(self.net.log_std.detach())    # the entropy of the policy the last minibatch was evaluated with
+                    L.minibatch_step(buf, perm[i:i + mb], self._adv, self._ret, self._adv_stats, self.params, self.adam_m, self.adam_v, step, self._stats)
+        if self._extended:
             self._out[23:25].copy_(self._state)
-            st = self._read_out(b, buf, cur)                             # the update's only synchronisation
+        st = self._read_out(b, buf, cur)                                 # the update's only synchronisation
+        if self._extended:
             stopped, applied = int(st[23]), int(st[24])
-            self.adam_step = first_step + applied
-            assert applied == total or stopped
+            assert applied == last - first_step or stopped
             extra = {"approx_kl": st[4], "entropy_loss": st[5], "loss": st[6], "value_clip_fraction": st[7], "n_updates": applied, "early_stop": bool(stopped)}
         else:
-            last = self.epochs * ((n + mb - 1) // mb)
-            for e in range(self.epochs):
-                perm = torch.randperm(n, device=self.device) if perms is None else perms[e]
-                for i in range(0, n, mb):
-                    self.adam_step += 1
-                    if self.adam_step - first_step == last:
-                        self._out[9:15].copy_(self.net.log_std.detach())    # the entropy of the policy the last minibatch was evaluated with
-                    L.minibatch_step(buf, perm[i:i + mb], self._adv, self._ret, self._adv_stats, self.params, self.adam_m, self.adam_v, self.adam_step, self._stats)
-            st = self._read_out(b, buf, cur)
+            applied = last - first_step
             ent_loss = -(math.fsum(st[9:15]) + 6 * ENTROPY_CONST)
-            extra = {"approx_kl": float("nan"), "entropy_loss": ent_loss, "loss": st[0] + self.vf_coef * st[1], "n_updates": last, "early_stop": False}
+            extra = {"approx_kl": float("nan"), "entropy_loss": ent_loss, "loss": st[0] + self.vf_coef * st[1], "n_updates": applied, "early_stop": False}
+        self.adam_step = first_step + applied
         # mean_bootstrapped_reward: the mean of the chunk's reward column -- with a deferred bootstrap that column holds the env's own rewards
         return {"value_loss": st[1], "mean_reward": st[22], "mean_bootstrapped_reward": st[21],
                 "policy_loss": st[0], "clip_fraction": st[2], "grad_norm": st[3], "explained_variance": st[8], "std": math.fsum(math.exp(x) for x in st[15:21]) / 6, **extra}

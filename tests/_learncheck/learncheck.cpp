@@ -1,5 +1,5 @@
 // learncheck.cpp -- so100_learn.hpp (the arithmetic the learner's HIP kernels call) instantiated on the host in double and float, behind a
-// C interface for ctypes (tests/learn_support.py).  Test scaffolding only.
+// C interface for ctypes (tests/hostlibs.py).  Test scaffolding only.
 #include "../../so100_mujoco_rl_amd/csrc/so100_learn.hpp"
 
 using namespace so100::learn;
@@ -10,6 +10,15 @@ template <class S> static void head(const S* in, S* out) {
     out[0] = h.pg_loss; out[1] = h.v_loss; out[2] = h.clipped;
     for (int i = 0; i < 6; i++) { out[3 + i] = h.dmu[i]; out[9 + i] = h.dlog_std[i]; }
     out[15] = h.dV;
+}
+
+// the extended head (entropy bonus, value clipping, approx_kl): in = mu[6] log_std[6] a[6] logp_old adv_n V old_V ret clip clip_vf ent_coef vf_coef inv_mb (28);
+// out = head_out, then approx_kl entropy v_clipped (19)
+template <class S> static void head_ex(const S* in, S* out) {
+    const LossHeadEx<S> h = ppo_loss_head_ex<S>(in, in + 6, in + 12, in[18], in[19], in[20], in[21], in[22], in[23], in[24], in[25], in[26], in[27]);
+    out[0] = h.pg_loss; out[1] = h.v_loss; out[2] = h.clipped;
+    for (int i = 0; i < 6; i++) { out[3 + i] = h.dmu[i]; out[9 + i] = h.dlog_std[i]; }
+    out[15] = h.dV; out[16] = h.approx_kl; out[17] = h.entropy; out[18] = h.v_clipped;
 }
 
 // hyper = max_grad_norm step_size (1 - beta1) beta2 (1 - beta2) eps sqrt(bc2) (7); g is replaced by the clipped gradient
@@ -34,6 +43,8 @@ void lc_gae_f(int T, const float* reward, const float* code, const float* value,
 }
 void lc_head_d(const double* in25, double* out16) { head<double>(in25, out16); }
 void lc_head_f(const float* in25, float* out16) { head<float>(in25, out16); }
+void lc_head_ex_d(const double* in28, double* out19) { head_ex<double>(in28, out19); }
+void lc_head_ex_f(const float* in28, float* out19) { head_ex<float>(in28, out19); }
 void lc_adam_d(int n, double* g, double* p, double* m, double* v, double grad_norm, const double* hyper7) { adam<double>(n, g, p, m, v, grad_norm, hyper7); }
 void lc_adam_f(int n, float* g, float* p, float* m, float* v, float grad_norm, const float* hyper7) { adam<float>(n, g, p, m, v, grad_norm, hyper7); }
 

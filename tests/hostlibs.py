@@ -1,7 +1,8 @@
 """The one place that builds and loads the host twins of the device code: tests/_hostcheck/libhostcheck.so (physics, contacts, task
-layer, random draws) and tests/_rendercheck/librendercheck.so (render).  Each is made once per process and cached; argtypes and restype
-are declared here for EVERY exported symbol (tests/test_hostlibs.py holds the tables to the extern "C" definitions), so that no call
-depends on which test ran first: a `long` result without its restype is silently cut to 32 bits, a Python float without argtypes raises."""
+layer, random draws), tests/_rendercheck/librendercheck.so (render) and tests/_learncheck/liblearncheck.so (the learner's arithmetic).
+Each is made once per process and cached; argtypes and restype are declared here for EVERY exported symbol (tests/test_hostlibs.py holds
+the tables to the extern "C" definitions), so that no call depends on which test ran first: a `long` result without its restype is
+silently cut to 32 bits, a Python float without argtypes raises."""
 import ctypes as C
 import os
 import subprocess
@@ -42,6 +43,18 @@ RENDERCHECK = {
     "rc_render": (_i, [_p, _i, _i, _i, _i, _u] + [_p]*5),
 }
 
+LEARNCHECK = {
+    "lc_num_params": (_i, [_i]),
+    "lc_tensor_offset": (_i, [_i, _i]),
+    "lc_tensor_size": (_i, [_i, _i]),
+    "lc_gae_d": (None, [_i, _p, _p, _p, _l, _p, _d, _d, _d, _p, _p, _l]),
+    "lc_gae_f": (None, [_i, _p, _p, _p, _l, _p, _f, _f, _f, _p, _p, _l]),
+    "lc_head_d": (None, [_p, _p]), "lc_head_f": (None, [_p, _p]),
+    "lc_head_ex_d": (None, [_p, _p]), "lc_head_ex_f": (None, [_p, _p]),
+    "lc_adam_d": (None, [_i, _p, _p, _p, _p, _d, _p]),
+    "lc_adam_f": (None, [_i, _p, _p, _p, _p, _f, _p]),
+}
+
 _libs = {}
 
 
@@ -66,6 +79,11 @@ def hostcheck(out="libhostcheck.so", extra=""):
 def rendercheck():
     d = os.path.join(HERE, "_rendercheck")
     return _load(os.path.join(d, "librendercheck.so"), d, [], RENDERCHECK)
+
+
+def learncheck():
+    d = os.path.join(HERE, "_learncheck")
+    return _load(os.path.join(d, "liblearncheck.so"), d, [], LEARNCHECK)
 
 
 def ptr(a):

@@ -15,6 +15,7 @@ import pytest
 import torch
 
 import learn_support as LS
+from learn_support import make_learner, minibatch_indices, rel_err, state_dict
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -37,22 +38,6 @@ def report(name, value):
     return value
 
 
-def rel_err(got, want):
-    """max |got - want| / max |want| (float64 on the CPU)"""
-    got, want = got.detach().cpu().double(), want.detach().cpu().double()
-    return float((got - want).abs().max() / want.abs().max().clamp_min(1e-300))
-
-
-def make_learner(od, max_minibatch=1024, **kw):
-    from so100_mujoco_rl_amd.lib import So100Learner
-    return So100Learner(od, DEV, max_minibatch=max_minibatch, **kw)
-
-
-@functools.lru_cache(maxsize=None)
-def state_dict(od):
-    return LS.make_state_dict(od, seed=od)
-
-
 @functools.lru_cache(maxsize=None)
 def chunk(od, T, N):
     """(packed chunk, terminal obs, last obs) float32 on the CPU; shared, never modified"""
@@ -62,7 +47,7 @@ def chunk(od, T, N):
 @functools.lru_cache(maxsize=None)
 def reference_advantages(od, T, N, bootstrap):
     buf, tobs, last_obs = chunk(od, T, N)
-    return LS.ref_advantages(buf, last_obs, LS.ref_net(od, state_dict(od)), terminal_obs=tobs if bootstrap else None)
+    return LS.ref_advantages(buf, last_obs, LS.RefNet(od, state_dict(od)), terminal_obs=tobs if bootstrap else None)
 
 
 def gpu_advantages(L, od, buf, last_obs, tobs):
@@ -114,16 +99,6 @@ def grad_inputs(od):
     buf, _, _ = chunk(od, GT, GN)
     adv, ret, mean, std = reference_advantages(od, GT, GN, True)
     return buf, adv.float(), ret.float(), torch.stack([mean, std]).float()
-
-
-def minibatch_indices(mb, n, seed):
-    """mb distinct indices in random order, index 0 and index n - 1 among them (mb = 1: the last index)"""
-    g = torch.Generator().manual_seed(seed)
-    if mb == 1:
-        return torch.tensor([n - 1])
-    inner = (torch.randperm(n - 2, generator=g) + 1)[:mb - 2]
-    idx = torch.cat([torch.tensor([0, n - 1]), inner])
-    return idx[torch.randperm(mb, generator=g)]
 
 
 def check_gradient(od, mb, idx, max_minibatch):

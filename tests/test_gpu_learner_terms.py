@@ -1,5 +1,5 @@
 """The learner's extended step on the GPU (so100_learner_minibatch_step_ex, so100_learner_explained_variance, ppo.FusedPPO with SB3's
-remaining options) against the fp64 autograd reference of learn_terms_support.py: gradients and diagnostics per option, bitwise identity
+remaining options) against the fp64 autograd reference of learn_support.py: gradients and diagnostics per option, bitwise identity
 with the old step when every term is off, whole updates with the target_kl stop, explained variance, one training iteration against the
 PyTorch learner and the command line.
 
@@ -13,7 +13,8 @@ import math
 import pytest
 import torch
 
-import learn_terms_support as TS
+import learn_support as LS
+from learn_support import make_learner, minibatch_indices, state_dict
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -32,7 +33,7 @@ assert max(GRAD_TOL, STAT_TOL, PARAM_TOL, MOMENT_TOL, EV_TOL, E2E_PARAM_TOL, E2E
 
 CT, CN = 6, 130                                   # the chunk: 780 rows
 TERM_CASES = {"ent_coef": dict(ent_coef=0.01), "clip_range_vf": dict(clip_range_vf=0.3), "minibatch": dict(normalize_advantage="minibatch"),
-              "all": TS.ALL_TERMS}
+              "all": LS.ALL_TERMS}
 
 
 def report(name, value):
@@ -40,26 +41,16 @@ def report(name, value):
     return value
 
 
-def make_learner(od, max_minibatch=1024, **kw):
-    from so100_mujoco_rl_amd.lib import So100Learner
-    return So100Learner(od, DEV, max_minibatch=max_minibatch, **kw)
-
-
-@functools.lru_cache(maxsize=None)
-def state_dict(od):
-    return TS.make_state_dict(od, seed=od)
-
-
 @functools.lru_cache(maxsize=None)
 def chunk(od, T=CT, N=CN):
     """(packed chunk, terminal obs, last obs) float32 on the CPU; shared, never modified"""
-    return TS.make_chunk(T, N, od, seed=3, state_dict=state_dict(od))
+    return LS.make_chunk(T, N, od, seed=3, state_dict=state_dict(od))
 
 
 @functools.lru_cache(maxsize=None)
 def reference_advantages(od):
     buf, tobs, last_obs = chunk(od)
-    return TS.ref_advantages(buf, last_obs, TS.RefNet(od, state_dict(od)), terminal_obs=tobs)
+    return LS.ref_advantages(buf, last_obs, LS.RefNet(od, state_dict(od)), terminal_obs=tobs)
 
 
 def step_inputs(od):
@@ -68,22 +59,12 @@ def step_inputs(od):
     return chunk(od)[0], adv.float(), ret.float(), torch.stack([mean, std]).float()
 
 
-def minibatch_indices(mb, n, seed):
-    """mb distinct indices in random order, index 0 and index n - 1 among them (mb = 1: the last index)"""
-    g = torch.Generator().manual_seed(seed)
-    if mb == 1:
-        return torch.tensor([n - 1])
-    inner = (torch.randperm(n - 2, generator=g) + 1)[:mb - 2]
-    idx = torch.cat([torch.tensor([0, n - 1]), inner])
-    return idx[torch.randperm(mb, generator=g)]
-
-
 def gpu_step(L, od, idx, terms, target_kl=None, use_state=True, start=None):
     """one extended step from the shared initial weights (or from `start` = (params, m, v, adam_step)); returns params, m, v, diag, grads, state"""
     buf, adv, ret, adv_stats = (t.to(DEV) for t in step_inputs(od))
     P = L.num_params
     if start is None:
-        params = TS.flat_params(state_dict(od), od, DEV); m = torch.zeros(P, device=DEV); v = torch.zeros(P, device=DEV); step = 1
+        params = LS.flat_params(state_dict(od), od, DEV); m = torch.zeros(P, device=DEV); v = torch.zeros(P, device=DEV); step = 1
     else:
         params, m, v, step = start
     diag = torch.full((8,), float("nan"), device=DEV); grads = torch.full((P,), float("nan"), device=DEV)
@@ -95,13 +76,13 @@ def gpu_step(L, od, idx, terms, target_kl=None, use_state=True, start=None):
 def check_step(od, mb, idx, terms, name):
     from so100_mujoco_rl_amd import lib
     buf, adv, ret, adv_stats = step_inputs(od)
-    ref = TS.RefLearner(od, state_dict(od), **terms)
+    ref = LS.RefLearner(od, state_dict(od), **terms)
     st_r, grads_r = ref.step(buf, idx, adv.double(), ret.double(), adv_stats[0].double(), adv_stats[1].double())
     L = make_learner(od)
     _, _, _, diag, grads, state = gpu_step(L, od, idx, terms)
     assert state.tolist() == [0, 1]
-    got = TS.split_flat(grads, od)
-    errs = {k: TS.rel_err(got[k], g_r) for k, g_r in grads_r.items()}
+    got = LS.split_flat(grads, od)
+    errs = {k: LS.rel_err(got[k], g_r) for k, g_r in grads_r.items()}
     worst = max(errs, key=errs.get)
     report(f"grad od{od} mb{mb} {name} ({worst})", errs[worst])
     d = dict(zip(lib.LEARNER_DIAG, diag.tolist()))
@@ -135,11 +116,11 @@ def test_out_of_range_indices_are_left_out_of_the_statistics_and_every_sum(od):
     good = minibatch_indices(40, n, seed=9)
     bad = torch.tensor([-1, n, -7, n + 5, 2 ** 40, -2 ** 40] * 5)[:25]
     idx = torch.cat([good, bad])[torch.randperm(65, generator=torch.Generator().manual_seed(4))]
-    st_r = check_step(od, 65, idx, TS.ALL_TERMS, "all+bad-indices")
+    st_r = check_step(od, 65, idx, LS.ALL_TERMS, "all+bad-indices")
     assert st_r["valid"] == 40
     # a minibatch whose only valid row is one sample: its advantage is used as it is
     one = torch.cat([bad[:3], torch.tensor([17]), bad[3:6]])
-    check_step(od, 7, one, TS.ALL_TERMS, "all+one-valid-row")
+    check_step(od, 7, one, LS.ALL_TERMS, "all+one-valid-row")
 
 
 @pytest.mark.parametrize("od", [15, 8])
@@ -149,7 +130,7 @@ def test_every_term_off_gives_the_bits_of_the_old_step(od):
     buf, adv, ret, adv_stats = (t.to(DEV) for t in step_inputs(od))
     L = make_learner(od)
     P = L.num_params
-    params = TS.flat_params(state_dict(od), od, DEV); m = torch.zeros(P, device=DEV); v = torch.zeros(P, device=DEV)
+    params = LS.flat_params(state_dict(od), od, DEV); m = torch.zeros(P, device=DEV); v = torch.zeros(P, device=DEV)
     stats = torch.zeros(4, device=DEV); grads = torch.full((P,), float("nan"), device=DEV)
     for step in (1, 2):                                          # the second step starts from non-zero moments
         L.minibatch_step(buf, idx.to(DEV), adv, ret, adv_stats, params, m, v, step, stats, grads=grads)
@@ -159,9 +140,9 @@ def test_every_term_off_gives_the_bits_of_the_old_step(od):
         start = (p2, m2, v2, 2)
     assert state is None
     assert torch.equal(p2, params) and torch.equal(m2, m) and torch.equal(v2, v) and torch.equal(g2, grads) and torch.equal(diag[:4], stats)
-    assert float((p2 - TS.flat_params(state_dict(od), od, DEV)).abs().max()) > 1e-4
-    a = gpu_step(L, od, idx, TS.ALL_TERMS, target_kl=10.0)
-    b = gpu_step(L, od, idx, TS.ALL_TERMS, target_kl=10.0)
+    assert float((p2 - LS.flat_params(state_dict(od), od, DEV)).abs().max()) > 1e-4
+    a = gpu_step(L, od, idx, LS.ALL_TERMS, target_kl=10.0)
+    b = gpu_step(L, od, idx, LS.ALL_TERMS, target_kl=10.0)
     assert all(torch.equal(x, y) for x, y in zip(a, b))
     assert not torch.equal(a[0], p2)
 
@@ -201,7 +182,7 @@ def update_minibatches():
 
 def reference_update(od, target_kl):
     buf = chunk(od)[0]
-    ref = TS.RefLearner(od, state_dict(od), lr=UPD_LR, target_kl=target_kl, **TS.ALL_TERMS)
+    ref = LS.RefLearner(od, state_dict(od), lr=UPD_LR, target_kl=target_kl, **LS.ALL_TERMS)
     adv, ret, mean, std = reference_advantages(od)
     steps = [ref.step(buf, idx, adv, ret, mean, std)[0] for idx in update_minibatches()]
     return ref, [st for st in steps if st is not None]
@@ -222,7 +203,7 @@ def update_batch(od):
 
 def fused_update(od, target_kl):
     from so100_mujoco_rl_amd.ppo import FusedPPO
-    f = FusedPPO(od, DEV, lr=UPD_LR, epochs=UPD_EPOCHS, minibatch=UPD_MB, seed=1, target_kl=target_kl, **TS.ALL_TERMS)
+    f = FusedPPO(od, DEV, lr=UPD_LR, epochs=UPD_EPOCHS, minibatch=UPD_MB, seed=1, target_kl=target_kl, **LS.ALL_TERMS)
     f.net.load_state_dict({k: v.to(DEV) for k, v in state_dict(od).items()})
     return f, f.update(update_batch(od), perms=[p.to(DEV) for p in update_perms()])
 
@@ -232,11 +213,11 @@ def fused_steps(od, count):
     L = make_learner(od, UPD_MB, lr=UPD_LR)
     b = update_batch(od)
     P = L.num_params
-    params = TS.flat_params(state_dict(od), od, DEV); m = torch.zeros(P, device=DEV); v = torch.zeros(P, device=DEV)
+    params = LS.flat_params(state_dict(od), od, DEV); m = torch.zeros(P, device=DEV); v = torch.zeros(P, device=DEV)
     adv = torch.zeros(CT, CN, device=DEV); ret = torch.zeros(CT, CN, device=DEV); adv_stats = torch.zeros(2, device=DEV); diag = torch.zeros(8, device=DEV)
     L.advantages(b["packed"], b["last_obs"], params, adv, ret, adv_stats, terminal_obs=b["terminal_obs"])
     for step, idx in enumerate(update_minibatches()[:count], 1):
-        L.minibatch_step_ex(b["packed"], idx.to(DEV), adv, ret, adv_stats, params, m, v, step, diag, **TS.ALL_TERMS)
+        L.minibatch_step_ex(b["packed"], idx.to(DEV), adv, ret, adv_stats, params, m, v, step, diag, **LS.ALL_TERMS)
     return params, m, v
 
 
@@ -262,14 +243,14 @@ def test_update_with_a_stop(od, later):
     e_kl = report(f"stop-approx_kl od{od} s{s}", abs(stats["approx_kl"] - k[s - 1]) / max(k[s - 1], 1e-2))
     assert e_kl <= STAT_TOL
     want = ref.net.state_dict(); mom = ref.moments()
-    got_p, got_m, got_v = TS.split_flat(f.params, od), TS.split_flat(f.adam_m, od), TS.split_flat(f.adam_v, od)
-    ep = max(TS.rel_err(got_p[n], want[n]) for n in want)
-    em = max(TS.rel_err(got_m[n], mom[n][0]) for n in want); ev = max(TS.rel_err(got_v[n], mom[n][1]) for n in want)
+    got_p, got_m, got_v = LS.split_flat(f.params, od), LS.split_flat(f.adam_m, od), LS.split_flat(f.adam_v, od)
+    ep = max(LS.rel_err(got_p[n], want[n]) for n in want)
+    em = max(LS.rel_err(got_m[n], mom[n][0]) for n in want); ev = max(LS.rel_err(got_v[n], mom[n][1]) for n in want)
     report(f"stop-params od{od} s{s}", ep); report(f"stop-exp_avg od{od} s{s}", em); report(f"stop-exp_avg_sq od{od} s{s}", ev)
     assert ep <= PARAM_TOL and em <= MOMENT_TOL and ev <= MOMENT_TOL
     p, m, v = fused_steps(od, s - 1)                             # a run that was simply given s - 1 steps: the same bits
     assert torch.equal(f.params, p) and torch.equal(f.adam_m, m) and torch.equal(f.adam_v, v)
-    assert float((f.params - TS.flat_params(state_dict(od), od, DEV)).abs().max()) > 1e-3
+    assert float((f.params - LS.flat_params(state_dict(od), od, DEV)).abs().max()) > 1e-3
     # without target_kl all nine steps are applied
     if not later:
         g, st = fused_update(od, None)
@@ -296,7 +277,7 @@ def test_default_fused_update_keeps_the_old_bits_and_reports_the_diagnostics(od)
     L = make_learner(od, UPD_MB, vf_coef=vf)
     b = update_batch(od)
     P = L.num_params
-    params = TS.flat_params(state_dict(od), od, DEV); m = torch.zeros(P, device=DEV); v = torch.zeros(P, device=DEV)
+    params = LS.flat_params(state_dict(od), od, DEV); m = torch.zeros(P, device=DEV); v = torch.zeros(P, device=DEV)
     adv = torch.zeros(CT, CN, device=DEV); ret = torch.zeros(CT, CN, device=DEV); adv_stats = torch.zeros(2, device=DEV); st4 = torch.zeros(4, device=DEV)
     L.advantages(b["packed"], b["last_obs"], params, adv, ret, adv_stats, terminal_obs=b["terminal_obs"])
     for step, idx in enumerate(batches, 1):
@@ -304,12 +285,12 @@ def test_default_fused_update_keeps_the_old_bits_and_reports_the_diagnostics(od)
     assert torch.equal(f.params, params) and torch.equal(f.adam_m, m) and torch.equal(f.adam_v, v) and f.adam_step == 6
     assert [stats[k] for k in ("policy_loss", "value_loss", "clip_fraction", "grad_norm")] == st4.tolist()
     # the fp64 reference
-    ref = TS.RefLearner(od, state_dict(od), vf_coef=vf)
+    ref = LS.RefLearner(od, state_dict(od), vf_coef=vf)
     adv_r, ret_r, mean_r, std_r = reference_advantages(od)
     for idx in batches:
         last, _ = ref.step(chunk(od)[0], idx, adv_r, ret_r, mean_r, std_r)
     want = {"value_loss": last["value_loss"], "policy_loss": last["policy_loss"], "entropy_loss": last["entropy_loss"], "loss": last["loss"],
-            "explained_variance": TS.ref_explained_variance(ret_r.numpy(), chunk(od)[0][..., od + 8].double().numpy()),
+            "explained_variance": LS.ref_explained_variance(ret_r.numpy(), chunk(od)[0][..., od + 8].double().numpy()),
             "std": ref.net.log_std.detach().exp().mean().item()}
     assert abs(last["loss"] - (last["policy_loss"] + vf * last["value_loss"])) < 1e-12 and abs(want["entropy_loss"]) > 1.0
     for k, w in want.items():
@@ -339,7 +320,7 @@ def test_explained_variance_matches_numpy(od, T, N):
         assert L.L.so100_learner_explained_variance(L.h, buf.to(DEV).data_ptr(), ret.to(DEV).data_ptr(), 2 ** 24 + 1, out.data_ptr(), L._stream()) == -1
         assert b"num_samples" in L.L.so100_last_error()
     L.explained_variance(buf.to(DEV), ret.to(DEV), out)
-    want = TS.ref_explained_variance(ret.numpy(), buf[..., od + 8].numpy())
+    want = LS.ref_explained_variance(ret.numpy(), buf[..., od + 8].numpy())
     if T * N == 1:
         assert math.isnan(want) and math.isnan(out.item())
         return
@@ -357,7 +338,7 @@ def test_one_training_iteration_with_all_options_against_the_torch_learner():
     from so100_mujoco_rl_amd.collector import RolloutCollector
     from so100_mujoco_rl_amd.ppo import PPO, FusedPPO
     from so100_mujoco_rl_amd.vec_env import So100VecEnv
-    opts = dict(target_kl=0.5, lr_schedule=lambda progress: 3e-4 * progress, **TS.ALL_TERMS)
+    opts = dict(target_kl=0.5, lr_schedule=lambda progress: 3e-4 * progress, **LS.ALL_TERMS)
     out = {}
     for name, cls, defer in (("torch", PPO, False), ("fused", FusedPPO, True)):
         learner = cls(15, DEV, seed=3, **opts)
@@ -368,7 +349,7 @@ def test_one_training_iteration_with_all_options_against_the_torch_learner():
         stats = learner.update(b, progress_remaining=0.5)
         out[name] = ({k: v.detach().clone() for k, v in learner.net.state_dict().items()}, stats)
     (p_t, s_t), (p_f, s_f) = out["torch"], out["fused"]
-    worst = max(TS.rel_err(p_f[k], p_t[k]) for k in p_t)
+    worst = max(LS.rel_err(p_f[k], p_t[k]) for k in p_t)
     report("end-to-end params fused vs torch, all options", worst)
     assert worst <= E2E_PARAM_TOL
     assert s_f["n_updates"] == s_t["n_updates"] == 4 and s_f["early_stop"] is False and s_t["early_stop"] is False

@@ -1,6 +1,6 @@
 """The on-device learner without a device: include/so100_learn.h is exported and bound, argument checks and the missing-device error are loud,
 the flat parameter block is laid out as documented, the arithmetic templates of csrc/so100_learn.hpp (instantiated on the host in double by
-tests/_learncheck) agree with the fp64 PyTorch reference, and FusedPPO's network is an ordinary ActorCritic over views of one block.  CPU only."""
+tests/_learncheck) agree with the fp64 reference of learn_support.py, and FusedPPO's network is an ordinary ActorCritic over views of one block.  CPU only."""
 import ctypes as C
 import os
 import re
@@ -75,7 +75,7 @@ def test_parameter_block_layout(L):
     from so100_mujoco_rl_amd.ppo import ActorCritic
     assert L.so100_learner_num_params(15) == 10829 and L.so100_learner_num_params(8) == 9933
     assert L.so100_learner_num_params(7) < 0 and L.so100_learner_param_offset(15, b"nope") < 0 and L.so100_learner_param_offset(3, b"pi_w0") < 0
-    tw = LS.learncheck()
+    tw = hostlibs.learncheck()
     for od in (15, 8):
         shapes = {k: tuple(v.shape) for k, v in ActorCritic(od).state_dict().items()}
         layout, P = lib.learner_layout(od)
@@ -90,15 +90,15 @@ def test_parameter_block_layout(L):
 
 
 def test_every_twin_symbol_has_its_signature_declared():
-    """what test_hostlibs.py checks for the other twins: the extern "C" definitions of learncheck.cpp against learn_support.LEARNCHECK"""
+    """what test_hostlibs.py checks for the other twins: the extern "C" definitions of learncheck.cpp against hostlibs.LEARNCHECK"""
     scalars = {"int": C.c_int, "long": C.c_long, "float": C.c_float, "double": C.c_double}
     src = re.sub(r"//[^\n]*", "", open(os.path.join(hostlibs.HERE, "_learncheck", "learncheck.cpp")).read())
     want = {}
     for ret, name, params in re.findall(r'^(void|int)\s+(lc_\w+)\s*\(([^)]*)\)\s*\{', src, flags=re.M):
         args = [C.c_void_p if "*" in prm else scalars[" ".join(prm.split()[:-1])] for prm in (x.strip() for x in params.split(",")) if prm]
         want[name] = ({"void": None, "int": C.c_int}[ret], args)
-    assert len(want) >= 9 and sorted(want) == sorted(LS.LEARNCHECK)
-    lib = LS.learncheck()
+    assert len(want) >= 9 and sorted(want) == sorted(hostlibs.LEARNCHECK)
+    lib = hostlibs.learncheck()
     for name, (restype, argtypes) in want.items():
         fn = getattr(lib, name)
         assert list(fn.argtypes) == argtypes and fn.restype is restype, name
@@ -115,11 +115,11 @@ def _close(got, want, what):
 
 @pytest.mark.parametrize("od", [15, 8])
 def test_gae_scan_in_double_matches_the_reference(od):
-    tw = LS.learncheck()
+    tw = hostlibs.learncheck()
     T, N = 7, 9
     sd = LS.make_state_dict(od, 3)
     buf, tobs, last_obs = LS.make_chunk(T, N, od, 3, sd)
-    net = LS.ref_net(od, sd)
+    net = LS.RefNet(od, sd)
     b = buf.double().numpy(); k = od + 10
     with torch.no_grad():
         last_v = net.value(last_obs.double()).numpy()
@@ -157,7 +157,7 @@ def adv_with_boot(tw, b, boot, last_v, T, N, od):
 def test_loss_head_in_double_matches_autograd():
     """per sample: the loss terms and d(minibatch loss)/d(mu, log_std, V) against autograd on the PPO._step expression; samples inside the clip
     range, clipped on either side with either sign of the advantage, and exactly on the tie ratio*A == clamp(ratio)*A"""
-    tw = LS.learncheck()
+    tw = hostlibs.learncheck()
     rs = np.random.RandomState(5)
     clip, vf, inv_mb = 0.2, 0.5, 1.0 / 37
     seen = set()
@@ -181,7 +181,7 @@ def test_loss_head_in_double_matches_autograd():
 
 
 def test_clip_and_adam_in_double_match_torch():
-    tw = LS.learncheck()
+    tw = hostlibs.learncheck()
     rs = np.random.RandomState(6)
     n = 50
     for max_norm in (0.05, 100.0):                                # clipping engaged / not engaged
@@ -205,7 +205,7 @@ def test_clip_and_adam_in_double_match_torch():
 
 def test_float_instantiation_is_the_double_one_rounded():
     """the float twin (what the kernels instantiate) follows the double one to fp32 rounding"""
-    tw = LS.learncheck()
+    tw = hostlibs.learncheck()
     rs = np.random.RandomState(8)
     inp = np.concatenate([rs.randn(6) * 0.5, rs.randn(6) * 0.3, rs.randn(6), [-8.0, 0.7, 0.2, -0.4, 0.2, 0.5, 1.0 / 64]])
     out_d = np.zeros(16); out_f = np.zeros(16, np.float32)

@@ -1,5 +1,5 @@
 """SB3's remaining PPO terms without a device: the extended loss-head templates of csrc/so100_learn.hpp (instantiated on the host by
-tests/_learnterms) and ppo.PPO with each new option against the fp64 autograd reference of learn_terms_support.py; the new struct and the two
+tests/_learncheck) and ppo.PPO with each new option against the fp64 autograd reference of learn_support.py; the new struct and the two
 new calls of include/so100_learn.h are bound, check their arguments and have no CPU fallback.  CPU only.
 
 Bounds.  Twin in double: 1e-12, the existing twin's bound for the same kind of arithmetic; float twin against the double one: 2e-5 (likewise).
@@ -18,8 +18,9 @@ import pytest
 import torch
 import torch.nn as nn
 
-import learn_terms_support as TS
-from learn_terms_support import ptr
+import hostlibs
+import learn_support as LS
+from learn_support import ptr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REL = 1e-12
@@ -45,7 +46,7 @@ def test_extended_head_in_double_matches_autograd(clip_vf, ent_coef):
     """per sample: every output derivative, approx_kl, the entropy and the value-clipped flag against autograd on the formulas of SB3's
     PPO.train; samples inside and outside either clip range, with V == old_V (case % 7 == 0) and, at clip_vf 0.25, exactly on the value
     clip's closed boundary, V - old_V == +-0.25 in binary (case % 9 == 1, 2): there the gradient passes and the sample does not count as clipped"""
-    tw = TS.learnterms()
+    tw = hostlibs.learncheck()
     rs = np.random.RandomState(11)
     clip, vf, inv_mb = 0.2, 0.5, 1.0 / 37
     seen = set(); seen_boundary = False
@@ -63,10 +64,10 @@ def test_extended_head_in_double_matches_autograd(clip_vf, ent_coef):
         policy = -torch.minimum(ratio * adv_n, ratio.clamp(1 - clip, 1 + clip) * adv_n)
         v_pred = old_V + (tV - old_V).clamp(-clip_vf, clip_vf) if clip_vf > 0 else tV
         value = (ret - v_pred) ** 2
-        entropy = tls.sum() + 6 * TS.GAUSS_ENTROPY
+        entropy = tls.sum() + 6 * LS.GAUSS_ENTROPY
         ((policy - ent_coef * entropy + vf * value) * inv_mb).backward()
         inp = np.concatenate([mu, ls, a, [logp_old, adv_n, V, old_V, ret, clip, clip_vf, ent_coef, vf, inv_mb]]); out = np.zeros(19)
-        tw.lt_head_ex_d(ptr(inp), ptr(out))
+        tw.lc_head_ex_d(ptr(inp), ptr(out))
         _close(out[0], policy.item(), "policy loss"); _close(out[1], value.item(), "value loss")
         assert out[2] == float(abs(ratio.item() - 1) > clip)
         _close(out[3:9], tmu.grad.numpy(), "dmu"); _close(out[9:15], tls.grad.numpy(), "dlog_std")
@@ -82,25 +83,25 @@ def test_extended_head_in_double_matches_autograd(clip_vf, ent_coef):
 
 def test_extended_head_with_every_term_off_is_the_old_head():
     """clip_vf 0 and ent_coef 0: the same loss terms and derivatives as ppo_loss_head's formulas give, whatever old_V is"""
-    tw = TS.learnterms()
+    tw = hostlibs.learncheck()
     rs = np.random.RandomState(12)
     base = np.concatenate([rs.randn(6) * 0.5, rs.randn(6) * 0.3, rs.randn(6), [-8.0, 0.7, 0.2, 0.0, -0.4, 0.2, 0.0, 0.0, 0.5, 1.0 / 64]])
     outs = []
     for old_V in (0.2, 5.0, -3.0):
         inp = base.copy(); inp[21] = old_V; out = np.zeros(19)
-        tw.lt_head_ex_d(ptr(inp), ptr(out)); outs.append(out)
+        tw.lc_head_ex_d(ptr(inp), ptr(out)); outs.append(out)
     assert all(np.array_equal(o, outs[0]) for o in outs) and outs[0][18] == 0.0
     assert outs[0][15] == 2 * 0.5 * (0.2 - -0.4) / 64
 
 
 def test_float_instantiation_of_the_extended_head_is_the_double_one_rounded():
-    tw = TS.learnterms()
+    tw = hostlibs.learncheck()
     rs = np.random.RandomState(13)
     for old_V in (0.1, 0.9):                                     # inside / outside the value clip
         inp = np.concatenate([rs.randn(6) * 0.5, rs.randn(6) * 0.3, rs.randn(6), [-8.0, 0.7, 0.2, old_V, -0.4, 0.2, 0.3, 0.01, 0.5, 1.0 / 64]])
         out_d = np.zeros(19); out_f = np.zeros(19, np.float32)
         inp_f = inp.astype(np.float32)
-        tw.lt_head_ex_d(ptr(inp_f.astype(np.float64)), ptr(out_d)); tw.lt_head_ex_f(ptr(inp_f), ptr(out_f))
+        tw.lc_head_ex_d(ptr(inp_f.astype(np.float64)), ptr(out_d)); tw.lc_head_ex_f(ptr(inp_f), ptr(out_f))
         assert out_d[18] == out_f[18] == float(old_V == 0.9)
         assert np.abs(out_f - out_d).max() <= 2e-5 * max(1.0, np.abs(out_d).max())
 
@@ -110,8 +111,8 @@ OD, T, N = 15, 6, 130
 
 
 def _inputs(od=OD, t=T, n=N):
-    sd = TS.make_state_dict(od, seed=od)
-    buf, _, last_obs = TS.make_chunk(t, n, od, seed=3, state_dict=sd)
+    sd = LS.make_state_dict(od, seed=od)
+    buf, _, last_obs = LS.make_chunk(t, n, od, seed=3, state_dict=sd)
     b = {"obs": buf[..., :od], "actions": buf[..., od:od + 6], "rewards": buf[..., od + 6], "dones": (buf[..., od + 7] != 0).float(),
          "values": buf[..., od + 8], "log_probs": buf[..., od + 9], "last_obs": last_obs}
     # PPO's GAE ends an episode on every done and adds no bootstrap: the reference's code-1 behaviour on every episode end
@@ -127,8 +128,8 @@ def _run_both(terms, epochs, mb, lr=3e-4, target_kl=None, od=OD, t=T, n=N, lr_sc
     ppo.net.load_state_dict(sd)
     torch.manual_seed(5)
     stats = ppo.update(b, progress) if lr_schedule is not None else ppo.update(b)
-    ref = TS.RefLearner(od, sd, lr=lr if lr_schedule is None else lr_schedule(progress), target_kl=target_kl, **terms)
-    adv, ret, mean, std = TS.ref_advantages(rbuf, b["last_obs"], ref.net)
+    ref = LS.RefLearner(od, sd, lr=lr if lr_schedule is None else lr_schedule(progress), target_kl=target_kl, **terms)
+    adv, ret, mean, std = LS.ref_advantages(rbuf, b["last_obs"], ref.net)
     torch.manual_seed(5)
     steps, grads = [], None
     for _ in range(epochs):
@@ -145,21 +146,21 @@ def _run_both(terms, epochs, mb, lr=3e-4, target_kl=None, od=OD, t=T, n=N, lr_sc
 def _compare(ppo, stats, ref, steps, grads, chunk, stopped=False):
     want = ref.net.state_dict()
     for k, p in ppo.net.named_parameters():
-        assert TS.rel_err(p.data, want[k]) <= PARAM_TOL, k
+        assert LS.rel_err(p.data, want[k]) <= PARAM_TOL, k
         if not stopped:                                          # the module keeps the last applied step's clipped gradient
-            assert TS.rel_err(p.grad, grads[k]) <= GRAD_TOL, k
+            assert LS.rel_err(p.grad, grads[k]) <= GRAD_TOL, k
     last = steps[-1]
     for k in ("value_loss", "approx_kl", "entropy_loss", "loss"):
         assert abs(stats[k] - last[k]) <= STAT_TOL * max(abs(last[k]), 1e-2), (k, stats[k], last[k])
     rbuf, ret = chunk
-    ev = TS.ref_explained_variance(ret.numpy(), rbuf[..., OD + 8].double().numpy())
+    ev = LS.ref_explained_variance(ret.numpy(), rbuf[..., OD + 8].double().numpy())
     assert abs(stats["explained_variance"] - ev) <= STAT_TOL * max(abs(ev), 1e-2)
     assert abs(stats["std"] - want["log_std"].exp().mean().item()) <= STAT_TOL
     assert stats["n_updates"] == ref.applied and stats["early_stop"] == ref.stopped
 
 
 TERM_CASES = {"ent_coef": dict(ent_coef=0.01), "clip_range_vf": dict(clip_range_vf=0.3), "minibatch": dict(normalize_advantage="minibatch"),
-              "all": TS.ALL_TERMS, "none": {}}
+              "all": LS.ALL_TERMS, "none": {}}
 
 
 @pytest.mark.parametrize("case", list(TERM_CASES))
@@ -173,7 +174,7 @@ def test_ppo_with_each_option_matches_the_reference(case):
     # the option changes the step: against the plain loss the last gradient differs by far more than the tolerance
     if case != "none":
         plain = _run_both({}, epochs=1, mb=260)[4]
-        assert max(TS.rel_err(grads[k], plain[k]) for k in grads) > 100 * GRAD_TOL
+        assert max(LS.rel_err(grads[k], plain[k]) for k in grads) > 100 * GRAD_TOL
 
 
 @pytest.mark.parametrize("mb", [1, 2])
@@ -184,7 +185,7 @@ def test_minibatch_normalisation_with_one_and_two_samples(mb):
     assert len(steps) == 6 // mb
     want = ref.net.state_dict()
     for k, p in ppo.net.named_parameters():
-        assert TS.rel_err(p.data, want[k]) <= PARAM_TOL and TS.rel_err(p.grad, grads[k]) <= GRAD_TOL, k
+        assert LS.rel_err(p.data, want[k]) <= PARAM_TOL and LS.rel_err(p.grad, grads[k]) <= GRAD_TOL, k
     assert all(torch.isfinite(p).all() for p in ppo.net.parameters())
 
 
@@ -199,21 +200,21 @@ def test_target_kl_stops_the_update():
     """3 epochs x 3 minibatches at lr 3e-3.  The reference, run without a stop, yields approx_kl k_1..k_9; s is the first step (2 <= s <= 8)
     whose k_s is at least 1.2 x every earlier one, and 1.5 target_kl is put at the geometric mean of k_s and that maximum: the steps
     before s are applied, step s and every later one are not."""
-    _, _, _, free, _, _ = _run_both(TS.ALL_TERMS, epochs=3, mb=260, lr=3e-3)
+    _, _, _, free, _, _ = _run_both(LS.ALL_TERMS, epochs=3, mb=260, lr=3e-3)
     k = [st["approx_kl"] for st in free]
     assert len(k) == 9
     picks = [s for s in range(2, 9) if k[s - 1] >= 1.2 * max(k[:s - 1])]
     assert picks, k
     s = picks[0]
     target = math.sqrt(k[s - 1] * max(k[:s - 1])) / 1.5
-    out = _run_both(TS.ALL_TERMS, epochs=3, mb=260, lr=3e-3, target_kl=target)
+    out = _run_both(LS.ALL_TERMS, epochs=3, mb=260, lr=3e-3, target_kl=target)
     ppo, stats, ref, steps, grads, _ = out
     assert ref.stopped and ref.applied == s - 1 and len(steps) == s
     assert stats["n_updates"] == s - 1 and stats["early_stop"] is True
     assert abs(stats["approx_kl"] - k[s - 1]) <= STAT_TOL * max(k[s - 1], 1e-2)
     _compare(*out, stopped=True)
     # and the s - 1 applied steps really moved the parameters
-    assert max(float((p.data.double() - TS.make_state_dict(OD, OD)[n_].double()).abs().max()) for n_, p in ppo.net.named_parameters()) > 1e-3
+    assert max(float((p.data.double() - LS.make_state_dict(OD, OD)[n_].double()).abs().max()) for n_, p in ppo.net.named_parameters()) > 1e-3
 
 
 def test_defaults_give_the_bits_of_the_loss_as_it_was():
