@@ -151,7 +151,9 @@ __device__ __forceinline__ void cube_from_lds(float (*xc)[64], int col, Cube<flo
 // with constants (`forget`, the caller's `forget_caller_state` for what lives outside this function): every path from the
 // Newton to a use passes that definition, so the old values are dead during the solve and their registers are free.
 // PK: the arm dynamics in pair form (so100_physics.hpp); the callers choose it where it costs the kernel no scratch
-template <bool PADS, bool LINKS, bool PK, class Hook, class Forget>
+// LOCAL: the mass matrix and its factor in loop-local storage (see the first half of the substep); the callers choose it where no
+// scratch or spill row of the kernel grows
+template <bool PADS, bool LINKS, bool PK, bool LOCAL, class Hook, class Forget>
 __device__ __forceinline__ void physics_phase_mw(const SimParams& p, int wave, int lane, EnvState& e, float ctrl[6], float cstale[3],
                                                  Arm<float>& A, const PhaseLds& L, ContactMemo& memo, Prof& prof_, Hook after_first_barrier, Forget forget_caller_state) {
     float (*xq)[64] = L.xq; float (*xc)[64] = L.xc; float (*xb)[64] = L.xb; float (*xa)[64] = L.xa; float (*xk)[64] = L.xk; float (*xm)[64] = L.xm;
@@ -215,7 +217,29 @@ __device__ __forceinline__ void physics_phase_mw(const SimParams& p, int wave, i
         cs3.prev_n = memo.prev_n;
         float Rc3[9] = { 1.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 1.0f }, cpos3[3] = { 0.0f, 0.0f, 0.0f };
         bool coupled3 = false, any3 = false;
-        if (wave == 1) {
+        // The mass matrix and its factor live for ONE substep: wave 0 defines them here and uses them behind the mid-substep barrier.
+        // Kept in A (the caller's, which outlives the loop) the allocator carried the 21 values of the factor round the loop on every
+        // wave's path: 21 copies at the back edge, 21 in front of CRBA, 21 behind RNEA.  LOCAL: they live in a
+        // loop-local Arm, wave 1 has a workspace of its own, and wave 0's branch comes FIRST in the chain -- the compiler lays the
+        // first branch of the chain out last, next to the barrier, so the factor meets the barrier in the registers CRBA left it in
+        // and no path copies it.  Without LOCAL the kernel keeps the shape it had (the callers say which: section 8f).
+        static_assert(!LOCAL || !PADS, "the loop-local factor is written for the variants without pad contacts (nothing publishes M)");
+        Arm<float> Fl; Arm<float>& F = LOCAL ? Fl : A;
+        if (LOCAL && wave == 0) {
+#pragma unroll
+            for (int i = 0; i < 6; i++) { F.s[i] = A.s[i]; F.c[i] = A.c[i]; }
+            arm_mass<float, PK>(F);
+            arm_factor<float>(p.flags, F);
+            SO100_PROF(4);                                 // CRBA + factor (wave 0)
+        } else if (LOCAL && wave == 1) {
+            Arm<float> R; float v1[6];
+#pragma unroll
+            for (int i = 0; i < 6; i++) { R.s[i] = xq[i][lane]; R.c[i] = xq[6 + i][lane]; v1[i] = xq[12 + i][lane]; }
+            arm_bias<float, PK>(v1, R);
+#pragma unroll
+            for (int i = 0; i < 6; i++) xb[i][lane] = R.bias[i];
+            SO100_PROF(4);                                 // RNEA (wave 1)
+        } else if (wave == 1) {
             float v1[6], q1[6] = { 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f }, c1[6] = { 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f };
 #pragma unroll
             for (int i = 0; i < 6; i++) { A.s[i] = xq[i][lane]; A.c[i] = xq[6 + i][lane]; v1[i] = xq[12 + i][lane]; }
@@ -285,18 +309,18 @@ __device__ __forceinline__ void physics_phase_mw(const SimParams& p, int wave, i
         if (wave == 2 && cube_live) { cube_solve<float>(cb, p.flags, p.contact_iters, cprep, cal, caa); SO100_PROF(6); }   // Newton behind the arm's solve
         if (wave == 0) {
 #pragma unroll
-            for (int i = 0; i < 6; i++) A.bias[i] = xb[i][lane];
+            for (int i = 0; i < 6; i++) F.bias[i] = xb[i][lane];
             float tau[6];
-            arm_tau<float>(e.q, e.v, ctrl, A, tau);
+            arm_tau<float>(e.q, e.v, ctrl, F, tau);
             if ((p.flags & (F_FRICTIONLOSS | F_LIMITS)) != 0u) {
-                arm_rows<float>(e.q, e.v, tau, e.ff, e.fl, p.flags, A, r0);
-                arm_pgs<float>(e.ff, e.fl, p.solver_iters, A, r0, acc0, pgs_res);
+                arm_rows<float>(e.q, e.v, tau, e.ff, e.fl, p.flags, F, r0);
+                arm_pgs<float>(e.ff, e.fl, p.solver_iters, F, r0, acc0, pgs_res);
                 if (!pads) e.res = tmax(e.res, pgs_res);   // with pads: after barrier 3, only if no contact Newton replaced this solve
             } else {
                 if (pads) arm_row_consts<float>(e.q, e.v, p.flags, r0);
 #pragma unroll
                 for (int i = 0; i < 6; i++) acc0[i] = tau[i];
-                ldl6_solve<float>(A.M, A.Dinv, acc0);
+                ldl6_solve<float>(F.M, F.Dinv, acc0);
             }
             SO100_PROF(6);                                 // solve (wave 0)
         }
@@ -746,7 +770,10 @@ __global__ void __launch_bounds__(64*NW) so100_rollout_fused(SimParams p, float*
         {
             Arm<float> A;
             const PhaseLds lds{ xq, xc, xb, pool, xa, xk, xm, pbuf, xw };
-            physics_phase_mw<PADS, LINKS, !PADS && FL != 7>(p, wave, lane, e, ctx.ctrl, cstale, A, lds, memo, prof_, [&](int sub) {
+            // (pair form: see above.  Loop-local factor: wherever the pair form runs, except Env03 / Env04 -- their task layer is the
+            //  largest, and with 21 registers held round the substep loop three values of it are parked in AGPRs)
+            constexpr bool PKF = !PADS && FL != 7;
+            physics_phase_mw<PADS, LINKS, PKF, PKF && KIND != 3 && KIND != 4>(p, wave, lane, e, ctx.ctrl, cstale, A, lds, memo, prof_, [&](int sub) {
                 if (wave == 3 && sub == 0 && t + 1 < ra.T) {       // wave 0 has consumed xn before this barrier
                     float eps[8];
                     policy_noise(p.env_id_offset + (uint32_t)env, ra.step_counter0 + (uint32_t)(t + 1), p.seed_lo, p.seed_hi, eps);
