@@ -4,9 +4,11 @@ is a learnable stand-in for the reference's `main.py -a PPO train -e Env01-v1` l
 is not installed in this image, so the learner here is ~80 lines of plain PyTorch with SB3's PPO defaults
 (MlpPolicy 2x64 tanh towers, gamma 0.99, gae_lambda 0.95, clip 0.2, lr 3e-4, 10 epochs are reduced to 4 for speed).
 
-    python examples/train_ppo.py [--env Env01-v1] [--envs 4096] [--iters 150] [--learner torch|fused]
+    python examples/train_ppo.py [--env Env01-v1] [--envs 4096] [--iters 150] [--learner torch|fused] [--shuffle torch|device]
 
---learner fused runs the update in the library's own kernels (include/so100_learn.h) instead of PyTorch autograd.
+--learner fused runs the update in the library's own kernels (include/so100_learn.h) instead of PyTorch autograd; with --shuffle device
+the minibatch permutations are the library's too and the whole update is one so100_learner_update call (examples/train_ppo.cpp is that
+loop without Python).
 """
 import argparse
 import os
@@ -29,11 +31,14 @@ def main():
     ap.add_argument("--env", default="Env01-v1"); ap.add_argument("--envs", type=int, default=4096)
     ap.add_argument("--iters", type=int, default=150); ap.add_argument("--T", type=int, default=64)
     ap.add_argument("--learner", choices=("torch", "fused"), default="torch")
+    ap.add_argument("--shuffle", choices=("torch", "device"), default="torch")
     args = ap.parse_args()
+    if args.shuffle == "device" and args.learner != "fused":
+        ap.error("--shuffle device needs --learner fused")
     env = So100VecEnv(args.env, args.envs, flags=F_REFERENCE, seed=0, stagger_episodes=True)
     dev = env.device
     fused = args.learner == "fused"
-    learner = (FusedPPO if fused else PPO)(env.sim.obs_dim, dev, seed=0)
+    learner = FusedPPO(env.sim.obs_dim, dev, seed=0, shuffle=args.shuffle) if fused else PPO(env.sim.obs_dim, dev, seed=0)
     col = RolloutCollector(env, learner.net.state_dict(), T=args.T, defer_bootstrap=fused)     # fused: the advantage kernel applies the TimeLimit bootstrap
     t0 = time.time(); steps = 0
     for it in range(args.iters):

@@ -1,5 +1,5 @@
-/* so100_learn.h -- C ABI of the on-device PPO learner of libso100sim.so: advantages (GAE with the TimeLimit bootstrap) and one
- * clipped-surrogate gradient step with gradient-norm clipping and Adam, for the fixed SB3 "MlpPolicy" network the rollout kernels
+/* so100_learn.h -- C ABI of the on-device PPO learner of libso100sim.so: advantages (GAE with the TimeLimit bootstrap), one
+ * clipped-surrogate gradient step with gradient-norm clipping and Adam, and a whole update (epochs of shuffled minibatch steps) in one call, for the fixed SB3 "MlpPolicy" network the rollout kernels
  * run (two 2 x 64 tanh towers, state-independent log_std; so100_policy_weights in so100_sim.h).  It replaces, for that network,
  * stable_baselines3 RolloutBuffer.compute_returns_and_advantage and the body of PPO.train's minibatch loop (here: ppo.py PPO._gae /
  * PPO._step).  Additive to so100_sim.h: SO100_ABI_VERSION and every declaration there are unchanged; error codes and
@@ -105,6 +105,57 @@ typedef struct {
     double  lr;                   /* this step's learning rate (a schedule, evaluated by the caller); < 0: the handle's */
 } so100_ppo_terms;
 
+/* The permutation of one epoch: a pure function of (seed, epoch, n), the same on every device and in every version of this library.
+ * A 6-round balanced Feistel network over 2h bits whose round function is Philox4x32-10 (the simulator's generator: multipliers 0xD2511F53 /
+ * 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85, ten rounds), cycle-walked back into [0, n):
+ *   perm(i), 0 <= i < n:
+ *     n == 1: 0
+ *     bits = bit length of n-1 (>= 1);  h = (bits + 1) / 2;  mask = 2^h - 1                  (the domain is 4^h, n <= 4^h < 4n)
+ *     x = i
+ *     do { L = x >> h;  R = x & mask
+ *          for r = 0 .. 5:  f = philox4x32(counter (R, r, epoch, 0x53484633), key (seed & 0xffffffff, seed >> 32))[0] & mask
+ *                           (L, R) = (R, L ^ f)
+ *          x = (L << h) | R
+ *     } while (x >= n)
+ *     perm(i) = x
+ * perm(i) is the row at position i of the epoch; minibatch k of size mb is the positions [k mb, min(n, (k+1) mb)).  The Feistel map is a
+ * bijection of [0, 4^h) and i < n, so the walk ends and perm is a bijection of [0, n).  The counter word 0x53484633 keeps the stream apart
+ * from the simulator's (0 and 0x504F4C) under equal seeds. */
+
+/* so100_learner_update: one whole PPO update (SB3's PPO.train on one rollout chunk) enqueued by one call, in this order:
+ *   1. so100_learner_advantages on the chunk                         -> adv_dev, ret_dev, adv_stats_dev
+ *   2. so100_learner_explained_variance                              -> out_dev[8]
+ *   3. update_state_dev (when given) is zeroed
+ *   4. for e in 0 .. epochs-1: perm_dev = the permutation of (shuffle_seed, shuffle_epoch0 + e, T*N), then ceil(T*N/mb) minibatch steps, step k on
+ *      idx = perm_dev + k mb with min(mb, T*N - k mb) rows; the steps carry adam_step = adam_step0 + 1, adam_step0 + 2, ...
+ * terms null: so100_learner_minibatch_step, its four statistics in out_dev[0:4]; given: so100_learner_minibatch_step_ex, its eight diagnostics in
+ * out_dev[0:8], the KL stop as documented there (the steps after a stop do nothing; steps_applied in update_state_dev says how many were applied,
+ * and the caller's next adam_step0 is this one plus that).  Before the last enqueued step the six log_std it is about to read are copied to
+ * out_dev[9:15].  Every buffer is the caller's; adv / ret / adv_stats / perm are outputs too (perm_dev ends holding the last epoch's
+ * permutation).  Nothing allocates, frees or synchronises, no stream is created; a rejected call enqueues nothing. */
+#define SO100_UPDATE_OUT 15
+typedef struct {
+    const float*           rollout_dev;            /* [T][N][obs_dim+10], as so100_rollout wrote it                                  */
+    const float*           terminal_obs_chunk_dev; /* [T][N][obs_dim]; nullable (then no TimeLimit bootstrap)                        */
+    const float*           last_obs_dev;           /* [N][obs_dim]                                                                   */
+    int32_t                T, N;                   /* >= 1; T*N <= 2^24 (so100_learner_explained_variance)                           */
+    float*                 params_dev;             /* [P] updated in place                                                           */
+    float*                 adam_m_dev;             /* [P] updated in place                                                           */
+    float*                 adam_v_dev;             /* [P] updated in place                                                           */
+    float*                 adv_dev;                /* [T][N] out                                                                     */
+    float*                 ret_dev;                /* [T][N] out                                                                     */
+    float*                 adv_stats_dev;          /* [2] out                                                                        */
+    int64_t*               perm_dev;               /* [T*N] out: the last epoch's permutation                                        */
+    int32_t                epochs;                 /* >= 1                                                                           */
+    int32_t                mb;                     /* 1 <= mb <= max_minibatch; the last minibatch of an epoch holds the remainder   */
+    int32_t                adam_step0;             /* >= 0: Adam steps applied before this update                                    */
+    uint32_t               shuffle_epoch0;         /* epoch e of this update shuffles with shuffle_epoch0 + e (mod 2^32)             */
+    uint64_t               shuffle_seed;
+    const so100_ppo_terms* terms;                  /* nullable: the plain step                                                       */
+    int32_t*               update_state_dev;       /* [2] {stopped, steps_applied}; required with terms->target_kl > 0, else nullable */
+    float*                 out_dev;                /* [SO100_UPDATE_OUT]: [0:8] statistics / diagnostics, [8] explained variance, [9:15] log_std */
+} so100_update_io;
+
 int  so100_learner_num_params(int32_t obs_dim);                          /* 10829 (obs_dim 15), 9933 (8); < 0 otherwise */
 int  so100_learner_param_offset(int32_t obs_dim, const char* name);      /* name: a member of so100_policy_weights; < 0 if unknown */
 int  so100_learner_param_size(int32_t obs_dim, const char* name);        /* elements of that tensor                      */
@@ -124,6 +175,10 @@ int  so100_learner_minibatch_step_ex(so100_learner* learner, const so100_minibat
  * SB3's explained_variance. */
 int  so100_learner_explained_variance(so100_learner* learner, const float* rollout_dev, const float* ret_dev, int64_t num_samples, float* out_dev,
                                       void* hip_stream);
+
+/* perm_dev [n] int64 = the permutation of (seed, epoch, n) specified above, 1 <= n <= 2^30.  One launch. */
+int  so100_learner_shuffle(so100_learner* learner, uint64_t seed, uint32_t epoch, int64_t n, int64_t* perm_dev, void* hip_stream);
+int  so100_learner_update(so100_learner* learner, const so100_update_io* io, void* hip_stream);
 
 #ifdef __cplusplus
 }

@@ -1,5 +1,6 @@
-// so100_learn.hip -- the on-device PPO learner behind include/so100_learn.h: advantages (three launches) and one minibatch gradient
-// step (three launches: gradient, reduction, Adam) for the fixed 2 x 64 tanh towers of so100_policy.hpp.  The step has two loss heads, chosen at
+// so100_learn.hip -- the on-device PPO learner behind include/so100_learn.h: advantages (three launches), one minibatch gradient
+// step (three launches: gradient, reduction, Adam) and, on top of those, a whole update with its shuffle (so100_learner_update), for the
+// fixed 2 x 64 tanh towers of so100_policy.hpp.  The step has two loss heads, chosen at
 // compile time (EX): the plain one of so100_learner_minibatch_step and the extended one of so100_learner_minibatch_step_ex with SB3's remaining
 // loss terms and the KL stop (under per-minibatch normalisation one more launch, for the minibatch's advantage statistics).  Everything around the
 // head -- checks, arguments, launches, kernels -- is written once.  The per-sample and per-parameter arithmetic is in
@@ -524,6 +525,24 @@ __global__ __launch_bounds__(256) void so100_learn_ev_merge(const float* __restr
     out[0] = (differs == 0.0f || m2r == 0.0f) ? __builtin_nanf("") : 1.0f - m2d/m2r;
 }
 
+// ---- the whole update (so100_learner_update) ---------------------------------------------------------------------------------------------
+// One thread per position of the epoch, grid-stride; the only traffic is the store.  The walk of shuffle_index diverges (fewer than 4 maps
+// per position on average, 26 at the worst seen), which costs a wave its longest lane's maps and nothing else: no LDS, no atomics.
+constexpr int SHUFFLE_GRID_MAX = 1024;
+__global__ __launch_bounds__(256) void so100_learn_shuffle(uint32_t n, uint32_t seed_lo, uint32_t seed_hi, uint32_t epoch, int64_t* __restrict__ perm) {
+    const uint64_t seed = ((uint64_t)seed_hi << 32) | seed_lo;
+    for (uint64_t i = (uint64_t)blockIdx.x*256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x*256) perm[i] = (int64_t)shuffle_index((uint32_t)i, n, seed, epoch);
+}
+
+// the two small stream-ordered writes of an update: the zeroed {stopped, steps_applied} pair, and log_std as the last step is about to read it
+__global__ __launch_bounds__(64) void so100_learn_zero_state(int32_t* __restrict__ state) {
+    if (threadIdx.x < 2) state[threadIdx.x] = 0;
+}
+
+__global__ __launch_bounds__(64) void so100_learn_copy_log_std(const float* __restrict__ log_std, float* __restrict__ out) {
+    if (threadIdx.x < ACT_DIM) out[threadIdx.x] = log_std[threadIdx.x];
+}
+
 const char* const kTensorNames[NUM_TENSORS] = {
 #define X(name, rows, cols) #name,
     SO100_POLICY_TENSORS(X)
@@ -561,6 +580,18 @@ static AdamArgs adam_args(const so100_learner_config& c, double lr, int adam_ste
     return a;
 }
 
+// the extended step's own argument checks (so100_learner_update runs them before it enqueues anything)
+static int check_terms(const so100_ppo_terms* terms, const int32_t* state_dev, const char* fn) {
+    if (!(terms->ent_coef >= 0.0f)) return fail(SO100_E_INVALID, "%s: ent_coef must be >= 0", fn);
+    if (terms->clip_range_vf != terms->clip_range_vf) return fail(SO100_E_INVALID, "%s: clip_range_vf is NaN (<= 0 means off)", fn);
+    if (terms->target_kl != terms->target_kl) return fail(SO100_E_INVALID, "%s: target_kl is NaN (<= 0 means off)", fn);
+    if (terms->normalize_advantage != 0 && terms->normalize_advantage != 1)
+        return fail(SO100_E_INVALID, "%s: normalize_advantage must be 0 (batch) or 1 (minibatch), got %d", fn, terms->normalize_advantage);
+    if (terms->lr != terms->lr) return fail(SO100_E_INVALID, "%s: lr is NaN (negative means the handle's)", fn);
+    if (terms->target_kl > 0.0f && !state_dev) return fail(SO100_E_INVALID, "%s: target_kl needs the update-state pointer", fn);
+    return 0;
+}
+
 // The step behind both entry points.  terms null: the plain head, out_dev takes its four statistics; given: the extended head, out_dev takes
 // the eight diagnostics and state_dev (nullable) is the update's {stopped, steps_applied}.  fn: the entry point's name, for the messages.
 static int minibatch_step(so100_learner* L, const so100_minibatch_io* io, const so100_ppo_terms* terms, float* out_dev, int32_t* state_dev, void* stream, const char* fn) {
@@ -571,13 +602,8 @@ static int minibatch_step(so100_learner* L, const so100_minibatch_io* io, const 
     if (!io->rollout_dev || !io->adv_dev || !io->ret_dev || !io->adv_stats_dev || !io->params_dev || !io->adam_m_dev || !io->adam_v_dev || !out_dev)
         return fail(SO100_E_INVALID, "%s: rollout/adv/ret/adv_stats/params/adam_m/adam_v/%s pointers are required", fn, terms ? "diag" : "stats");
     if (terms) {
-        if (!(terms->ent_coef >= 0.0f)) return fail(SO100_E_INVALID, "%s: ent_coef must be >= 0", fn);
-        if (terms->clip_range_vf != terms->clip_range_vf) return fail(SO100_E_INVALID, "%s: clip_range_vf is NaN (<= 0 means off)", fn);
-        if (terms->target_kl != terms->target_kl) return fail(SO100_E_INVALID, "%s: target_kl is NaN (<= 0 means off)", fn);
-        if (terms->normalize_advantage != 0 && terms->normalize_advantage != 1)
-            return fail(SO100_E_INVALID, "%s: normalize_advantage must be 0 (batch) or 1 (minibatch), got %d", fn, terms->normalize_advantage);
-        if (terms->lr != terms->lr) return fail(SO100_E_INVALID, "%s: lr is NaN (negative means the handle's)", fn);
-        if (terms->target_kl > 0.0f && !state_dev) return fail(SO100_E_INVALID, "%s: target_kl needs the update-state pointer", fn);
+        const int rc = check_terms(terms, state_dev, fn);
+        if (rc != 0) return rc;
     }
     SO100_ON_DEVICE(L->cfg.device, fn);
     const hipStream_t st = (hipStream_t)stream;
@@ -720,6 +746,62 @@ int so100_learner_explained_variance(so100_learner* L, const float* rollout_dev,
                        n, per, L->ev_part);
     hipLaunchKernelGGL(so100_learn_ev_merge, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)L->ev_part, G, out_dev);
     HIP_TRY(hipGetLastError(), SO100_E_LAUNCH, "so100_learner_explained_variance: ");
+    return 0;
+}
+
+int so100_learner_shuffle(so100_learner* L, uint64_t seed, uint32_t epoch, int64_t n, int64_t* perm_dev, void* stream) {
+    if (!L) return fail(SO100_E_INVALID, "so100_learner_shuffle: null argument");
+    if (n < 1 || n > SHUFFLE_MAX_N) return fail(SO100_E_INVALID, "so100_learner_shuffle: n must be in 1..1073741824, got %ld", (long)n);
+    if (!perm_dev) return fail(SO100_E_INVALID, "so100_learner_shuffle: the perm pointer is required");
+    SO100_ON_DEVICE(L->cfg.device, "so100_learner_shuffle");
+    const long want = ((long)n + 255)/256;
+    hipLaunchKernelGGL(so100_learn_shuffle, dim3((unsigned)(want < SHUFFLE_GRID_MAX ? want : SHUFFLE_GRID_MAX)), dim3(256), 0, (hipStream_t)stream,
+                       (uint32_t)n, (uint32_t)seed, (uint32_t)(seed >> 32), epoch, perm_dev);
+    HIP_TRY(hipGetLastError(), SO100_E_LAUNCH, "so100_learner_shuffle: ");
+    return 0;
+}
+
+int so100_learner_update(so100_learner* L, const so100_update_io* io, void* stream) {
+    const char* const fn = "so100_learner_update";
+    if (!L || !io) return fail(SO100_E_INVALID, "%s: null argument", fn);
+    if (io->T < 1) return fail(SO100_E_INVALID, "%s: T must be >= 1, got %d", fn, io->T);
+    if (io->N < 1) return fail(SO100_E_INVALID, "%s: N must be >= 1, got %d", fn, io->N);
+    if (io->epochs < 1) return fail(SO100_E_INVALID, "%s: epochs must be >= 1, got %d", fn, io->epochs);
+    if (io->mb < 1 || io->mb > L->cfg.max_minibatch) return fail(SO100_E_INVALID, "%s: mb must be in 1..max_minibatch, got %d", fn, io->mb);
+    if (io->adam_step0 < 0) return fail(SO100_E_INVALID, "%s: adam_step0 must be >= 0, got %d", fn, io->adam_step0);
+    const long n = (long)io->T*(long)io->N;
+    if (n > (1L << 24)) return fail(SO100_E_INVALID, "%s: T*N must be <= 16777216, got %ld", fn, n);          // the explained variance's limit
+    const long per_epoch = (n + io->mb - 1)/io->mb, steps = per_epoch*(long)io->epochs;
+    if ((long)io->adam_step0 + steps > 0x7fffffffL) return fail(SO100_E_INVALID, "%s: adam_step0 + epochs*ceil(T*N/mb) must fit 31 bits", fn);
+    if (!io->rollout_dev || !io->last_obs_dev || !io->params_dev || !io->adam_m_dev || !io->adam_v_dev || !io->adv_dev || !io->ret_dev || !io->adv_stats_dev ||
+        !io->perm_dev || !io->out_dev)
+        return fail(SO100_E_INVALID, "%s: rollout/last_obs/params/adam_m/adam_v/adv/ret/adv_stats/perm/out pointers are required", fn);
+    if (io->terms) {
+        const int rc = check_terms(io->terms, io->update_state_dev, fn);
+        if (rc != 0) return rc;
+    }
+    SO100_ON_DEVICE(L->cfg.device, fn);
+    const hipStream_t st = (hipStream_t)stream;
+    int rc;
+    so100_advantages_io aio = { io->rollout_dev, io->terminal_obs_chunk_dev, io->last_obs_dev, io->params_dev, io->adv_dev, io->ret_dev, io->adv_stats_dev };
+    if ((rc = so100_learner_advantages(L, &aio, io->T, io->N, stream)) != 0) return rc;
+    if ((rc = so100_learner_explained_variance(L, io->rollout_dev, io->ret_dev, n, io->out_dev + 8, stream)) != 0) return rc;
+    if (io->update_state_dev) hipLaunchKernelGGL(so100_learn_zero_state, dim3(1), dim3(64), 0, st, io->update_state_dev);
+    so100_minibatch_io mio;
+    mio.rollout_dev = io->rollout_dev; mio.num_samples = n; mio.adv_dev = io->adv_dev; mio.ret_dev = io->ret_dev; mio.adv_stats_dev = io->adv_stats_dev;
+    mio.params_dev = io->params_dev; mio.adam_m_dev = io->adam_m_dev; mio.adam_v_dev = io->adam_v_dev; mio.stats_dev = io->out_dev; mio.grads_dev = nullptr;
+    const float* log_std = io->params_dev + tensor_offset(T_log_std, L->cfg.obs_dim);
+    int step = io->adam_step0;
+    const int last = io->adam_step0 + (int)steps;
+    for (int e = 0; e < io->epochs; e++) {
+        if ((rc = so100_learner_shuffle(L, io->shuffle_seed, io->shuffle_epoch0 + (uint32_t)e, n, io->perm_dev, stream)) != 0) return rc;
+        for (long k = 0; k < per_epoch; k++) {
+            const long left = n - k*io->mb;
+            mio.idx_dev = io->perm_dev + k*io->mb; mio.mb = (int32_t)(left < io->mb ? left : io->mb); mio.adam_step = ++step;
+            if (step == last) hipLaunchKernelGGL(so100_learn_copy_log_std, dim3(1), dim3(64), 0, st, log_std, io->out_dev + 9);
+            if ((rc = minibatch_step(L, &mio, io->terms, io->out_dev, io->update_state_dev, stream, fn)) != 0) return rc;
+        }
+    }
     return 0;
 }
 

@@ -1,12 +1,14 @@
 // so100_learn.hpp -- the per-sample / per-parameter arithmetic of the on-device PPO learner (include/so100_learn.h), as templates on the
 // scalar type: the HIP kernels of so100_learn.hip instantiate them in float, tests/_learncheck instantiates them on the host in double and
-// float and holds them to an fp64 PyTorch reference.  Nothing here touches memory layouts beyond a stride, a device builtin or a header
-// of the simulator: the file compiles with a plain host compiler.
+// float and holds them to an fp64 PyTorch reference.  Nothing here touches memory layouts beyond a stride or a device builtin, and nothing
+// but the shuffle at the end reads a header of the simulator: the file compiles with a plain host compiler.
 //   gae_scan_env        rollout.bootstrap_truncated + PPO._gae for one env (SB3 RolloutBuffer.compute_returns_and_advantage)
 //   ppo_loss_head       the PPO._step loss of one sample with its derivatives towards the network outputs
 //   ppo_loss_head_ex    the same with SB3's entropy bonus, value clipping and approx_kl
 //   clip_adam_update    clip_grad_norm_'s scaling + one torch.optim.Adam step of one parameter
+//   shuffle_index       one entry of an epoch's permutation (the one piece that reads the simulator: see there)
 #pragma once
+#include <stdint.h>
 #include "so100_policy_tensors.h"
 
 #ifndef SO100_LHD
@@ -197,3 +199,41 @@ SO100_LHD S clip_adam_update(S g, S clip_coef, S& p, S& m, S& v, S step_size, S 
 
 }  // namespace learn
 }  // namespace so100
+
+// ---- shuffle ------------------------------------------------------------------------------------------------------------------------------
+// The permutation of include/so100_learn.h ("The permutation"): a 6-round balanced Feistel network over 2h bits whose round function is the
+// simulator's Philox4x32-10, cycle-walked back into [0, n).  philox4x32 lives in so100_task.hpp, so this section exists where that header came
+// first (so100_learn.hip through so100_policy.hpp, tests/_shufflecheck); tests/_learncheck compiles the arithmetic above without it.
+#ifdef SO100_HD
+namespace so100 {
+namespace learn {
+
+constexpr uint32_t SHUFFLE_STREAM = 0x53484633u;       // counter word c3: the simulator's streams use 0 and 0x504F4C
+constexpr int SHUFFLE_ROUNDS = 6;
+constexpr int64_t SHUFFLE_MAX_N = (int64_t)1 << 30;    // the walk's x stays below 4^15
+
+// the row at position i (0 <= i < n, 1 <= n <= 2^30) of epoch `epoch` under `seed`.  The Feistel map permutes [0, 4^h) and i < n <= 4^h,
+// so the walk returns into [0, n) (at the latest at i itself); the domain is smaller than 4n, so it takes fewer than 4 maps on average.
+SO100_HD uint32_t shuffle_index(uint32_t i, uint32_t n, uint64_t seed, uint32_t epoch) {
+    if (n <= 1u) return 0u;
+    int bits = 0;
+    for (uint32_t m = n - 1u; m != 0u; m >>= 1) bits++;
+    const int h = (bits + 1)/2;
+    const uint32_t mask = (1u << h) - 1u, k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    uint32_t x = i;
+    do {
+        uint32_t L = x >> h, R = x & mask;
+        for (int r = 0; r < SHUFFLE_ROUNDS; r++) {
+            uint32_t o[4];
+            philox4x32(R, (uint32_t)r, epoch, SHUFFLE_STREAM, k0, k1, o);
+            const uint32_t t = L ^ (o[0] & mask);
+            L = R; R = t;
+        }
+        x = (L << h) | R;
+    } while (x >= n);
+    return x;
+}
+
+}  // namespace learn
+}  // namespace so100
+#endif

@@ -113,8 +113,20 @@ class PpoTerms(C.Structure):
     _fields_ = [("ent_coef", C.c_float), ("clip_range_vf", C.c_float), ("normalize_advantage", C.c_int32), ("target_kl", C.c_float), ("lr", C.c_double)]
 
 
+UPDATE_OUT = 15              # include/so100_learn.h: SO100_UPDATE_OUT
+
+
+class UpdateIO(C.Structure):
+    _fields_ = [("rollout_dev", C.c_void_p), ("terminal_obs_chunk_dev", C.c_void_p), ("last_obs_dev", C.c_void_p), ("T", C.c_int32), ("N", C.c_int32),
+                ("params_dev", C.c_void_p), ("adam_m_dev", C.c_void_p), ("adam_v_dev", C.c_void_p), ("adv_dev", C.c_void_p), ("ret_dev", C.c_void_p),
+                ("adv_stats_dev", C.c_void_p), ("perm_dev", C.c_void_p), ("epochs", C.c_int32), ("mb", C.c_int32), ("adam_step0", C.c_int32),
+                ("shuffle_epoch0", C.c_uint32), ("shuffle_seed", C.c_uint64), ("terms", C.POINTER(PpoTerms)), ("update_state_dev", C.c_void_p),
+                ("out_dev", C.c_void_p)]
+
+
 LEARN_EXPORTS = ["so100_learner_num_params", "so100_learner_param_offset", "so100_learner_param_size", "so100_learner_create", "so100_learner_destroy",
-                 "so100_learner_advantages", "so100_learner_minibatch_step", "so100_learner_minibatch_step_ex", "so100_learner_explained_variance"]
+                 "so100_learner_advantages", "so100_learner_minibatch_step", "so100_learner_minibatch_step_ex", "so100_learner_explained_variance",
+                 "so100_learner_shuffle", "so100_learner_update"]
 LEARNER_STATS = ["policy_loss", "value_loss", "clip_fraction", "grad_norm"]          # stats_dev[4] of so100_learner_minibatch_step
 LEARNER_DIAG = LEARNER_STATS + ["approx_kl", "entropy_loss", "loss", "value_clip_fraction"]       # diag_dev[8] of so100_learner_minibatch_step_ex
 NORMALIZE_ADVANTAGE = {"batch": 0, "minibatch": 1}                                   # so100_ppo_terms.normalize_advantage
@@ -167,6 +179,8 @@ def load():
         L.so100_learner_minibatch_step.argtypes = [C.c_void_p, C.POINTER(MinibatchIO), C.c_void_p]
         L.so100_learner_minibatch_step_ex.argtypes = [C.c_void_p, C.POINTER(MinibatchIO), C.POINTER(PpoTerms), C.c_void_p, C.c_void_p, C.c_void_p]
         L.so100_learner_explained_variance.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        L.so100_learner_shuffle.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_int64, C.c_void_p, C.c_void_p]
+        L.so100_learner_update.argtypes = [C.c_void_p, C.POINTER(UpdateIO), C.c_void_p]
         if L.so100_abi_version() != ABI_VERSION:
             raise So100Error("libso100sim.so ABI version mismatch")
         _lib = L
@@ -536,16 +550,20 @@ class So100Learner(_Handle):
         io = self._minibatch_io(rollout, idx, adv, ret, adv_stats, params, adam_m, adam_v, adam_step, stats, grads)
         _check(self.L.so100_learner_minibatch_step(self.h, C.byref(io), self._stream()), "so100_learner_minibatch_step")
 
+    @staticmethod
+    def _terms(ent_coef, clip_range_vf, normalize_advantage, target_kl, lr):
+        if normalize_advantage not in NORMALIZE_ADVANTAGE:
+            raise So100Error(f"normalize_advantage must be one of {sorted(NORMALIZE_ADVANTAGE)}, got {normalize_advantage!r}")
+        return PpoTerms(ent_coef, 0.0 if clip_range_vf is None else clip_range_vf, NORMALIZE_ADVANTAGE[normalize_advantage],
+                        0.0 if target_kl is None else target_kl, -1.0 if lr is None else lr)
+
     def minibatch_step_ex(self, rollout, idx, adv, ret, adv_stats, params, adam_m, adam_v, adam_step, diag, ent_coef=0.0, clip_range_vf=None,
                           normalize_advantage="batch", target_kl=None, lr=None, update_state=None, grads=None):
         """minibatch_step with SB3's remaining loss terms (so100_ppo_terms): diag [8] (LEARNER_DIAG) is written instead of stats.
         clip_range_vf / target_kl None: off; lr None: the handle's.  update_state: int32 [2] {stopped, steps_applied}, zeroed by the caller
         at the start of an update; required with target_kl."""
         io = self._minibatch_io(rollout, idx, adv, ret, adv_stats, params, adam_m, adam_v, adam_step, None, grads)
-        if normalize_advantage not in NORMALIZE_ADVANTAGE:
-            raise So100Error(f"normalize_advantage must be one of {sorted(NORMALIZE_ADVANTAGE)}, got {normalize_advantage!r}")
-        terms = PpoTerms(ent_coef, 0.0 if clip_range_vf is None else clip_range_vf, NORMALIZE_ADVANTAGE[normalize_advantage],
-                         0.0 if target_kl is None else target_kl, -1.0 if lr is None else lr)
+        terms = self._terms(ent_coef, clip_range_vf, normalize_advantage, target_kl, lr)
         _check(self.L.so100_learner_minibatch_step_ex(self.h, C.byref(io), C.byref(terms), _ptr(diag, torch.float32, (8,), self.device),
                                                       _ptr(update_state, torch.int32, (2,), self.device), self._stream()), "so100_learner_minibatch_step_ex")
 
@@ -555,3 +573,28 @@ class So100Learner(_Handle):
         f, d = torch.float32, self.device
         _check(self.L.so100_learner_explained_variance(self.h, _ptr(rollout, f, (T, N, self.obs_dim + 10), d), _ptr(ret, f, (T, N), d), T * N,
                                                        _ptr(out, f, (1,), d), self._stream()), "so100_learner_explained_variance")
+
+    def shuffle(self, seed, epoch, n, out):
+        """out: int64 [n] on the device = the permutation of (seed, epoch, n) that include/so100_learn.h specifies (1 <= n <= 2^30); one launch"""
+        _check(self.L.so100_learner_shuffle(self.h, int(seed) & 0xFFFFFFFFFFFFFFFF, int(epoch) & 0xFFFFFFFF, n, _ptr(out, torch.int64, (n,), self.device),
+                                            self._stream()), "so100_learner_shuffle")
+
+    def update(self, rollout, last_obs, params, adam_m, adam_v, adv, ret, adv_stats, perm, out, *, epochs, mb, adam_step0, shuffle_seed, shuffle_epoch0=0,
+               terminal_obs=None, terms=None, update_state=None):
+        """One whole PPO update enqueued by one call (so100_learner_update): the advantages, the explained variance, then `epochs` epochs of
+        {device shuffle, ceil(T*N/mb) minibatch steps numbered from adam_step0 + 1}.  adv / ret [T, N], adv_stats [2], perm int64 [T*N] and
+        out float32 [UPDATE_OUT] are the caller's and are written: out[0:8] the last step's statistics (terms None: the plain step's four) or
+        diagnostics, out[8] the explained variance, out[9:15] log_std as the last step read it.  terms: None for the plain step, or a dict of
+        minibatch_step_ex's options (ent_coef, clip_range_vf, normalize_advantage, target_kl, lr); update_state: int32 [2], zeroed by the call,
+        required with target_kl."""
+        T, N = rollout.shape[0], rollout.shape[1]
+        f, d, o, P = torch.float32, self.device, self.obs_dim, self.num_params
+        t = None
+        if terms is not None:
+            t = self._terms(terms.get("ent_coef", 0.0), terms.get("clip_range_vf"), terms.get("normalize_advantage", "batch"), terms.get("target_kl"), terms.get("lr"))
+        io = UpdateIO(_ptr(rollout, f, (T, N, o + 10), d), _ptr(terminal_obs, f, (T, N, o), d), _ptr(last_obs, f, (N, o), d), T, N,
+                      _ptr(params, f, (P,), d), _ptr(adam_m, f, (P,), d), _ptr(adam_v, f, (P,), d), _ptr(adv, f, (T, N), d), _ptr(ret, f, (T, N), d),
+                      _ptr(adv_stats, f, (2,), d), _ptr(perm, torch.int64, (T * N,), d), epochs, mb, adam_step0, int(shuffle_epoch0) & 0xFFFFFFFF,
+                      int(shuffle_seed) & 0xFFFFFFFFFFFFFFFF, C.pointer(t) if t is not None else None, _ptr(update_state, torch.int32, (2,), d),
+                      _ptr(out, f, (UPDATE_OUT,), d))
+        _check(self.L.so100_learner_update(self.h, C.byref(io), self._stream()), "so100_learner_update")

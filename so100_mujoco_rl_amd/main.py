@@ -1,6 +1,6 @@
 """Experiment driver with the reference's CLI surface (ref: /root/reference/src/so100_mujoco_rl/main.py:241-284):
 
-    python -m so100_mujoco_rl_amd.main -a PPO [-m MODEL] train  -e Env01-v1 [--envs 4096] [--iters N] [--learner torch|fused]
+    python -m so100_mujoco_rl_amd.main -a PPO [-m MODEL] train  -e Env01-v1 [--envs 4096] [--iters N] [--learner torch|fused] [--shuffle torch|device]
                                                                [--ent-coef C] [--clip-range-vf C] [--target-kl K]
                                                                [--normalize-advantage batch|minibatch] [--lr-schedule constant|linear]
     python -m so100_mujoco_rl_amd.main -a PPO [-m MODEL] test   -e Env01-v1 [--show-io] [--show-i]
@@ -87,9 +87,13 @@ def cli(ctx, algorithm, model):
 @click.option("--normalize-advantage", default=None, type=click.Choice(["batch", "minibatch"]),
               help="advantage normalisation over the whole rollout chunk (batch, the default) or per minibatch as SB3 does")
 @click.option("--lr-schedule", default=None, type=click.Choice(["constant", "linear"]), help="learning rate 3e-4 (constant, the default) or 3e-4 x remaining progress (linear; needs --iters)")
+@click.option("--shuffle", default="torch", type=click.Choice(["torch", "device"]),
+              help="minibatch permutations of --learner fused: torch.randperm (torch) or the library's, a function of seed and epoch; the whole update is then one call (device)")
 @click.pass_context
-def train(ctx, environment, envs, iters, seed, learner_kind, ent_coef, clip_range_vf, target_kl, normalize_advantage, lr_schedule):
+def train(ctx, environment, envs, iters, seed, learner_kind, ent_coef, clip_range_vf, target_kl, normalize_advantage, lr_schedule, shuffle):
     algorithm = ctx.obj["ALGORITHM_NAME"]
+    if shuffle == "device" and learner_kind != "fused":
+        raise RuntimeError("--shuffle device is the fused learner's on-device shuffle: it needs --learner fused")
     if lr_schedule == "linear" and iters <= 0:
         raise RuntimeError("--lr-schedule linear needs --iters > 0: the schedule runs over a known number of updates")
     # SB3's remaining PPO options: given on the command line, they reach whichever learner runs and a second log line shows their diagnostics.
@@ -141,6 +145,8 @@ def train(ctx, environment, envs, iters, seed, learner_kind, ent_coef, clip_rang
         if distributed:
             raise RuntimeError("multi-GPU training uses the built-in PPO learner; DDPG runs on one GPU")
         return _train_ddpg(env, environment, ctx.obj["MODEL_PATH"], save_dir, iters, seed, kind)
+    if shuffle == "device":
+        terms["shuffle"] = "device"
     learner = make_ppo_learner(learner_kind, env.sim.obs_dim, env.device, seed, **terms)
     if ctx.obj["MODEL_PATH"]:
         if not os.path.isfile(ctx.obj["MODEL_PATH"]):
@@ -213,7 +219,7 @@ PPO_LR = 3e-4                                                # the learners' def
 
 def make_ppo_learner(kind, obs_dim, device, seed, **terms):
     """the built-in PPO learner `train --learner` names: "torch" (ppo.PPO, the default) or "fused" (ppo.FusedPPO, HIP kernels); terms: SB3's
-    remaining options (ent_coef, clip_range_vf, target_kl, normalize_advantage, lr_schedule), the same for both"""
+    remaining options (ent_coef, clip_range_vf, target_kl, normalize_advantage, lr_schedule), the same for both, and the fused learner's shuffle"""
     if kind == "torch":
         return PPO(obs_dim, device, lr=PPO_LR, seed=seed, **terms)
     if kind != "fused":

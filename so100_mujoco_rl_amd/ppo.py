@@ -186,10 +186,15 @@ class FusedPPO:
 
     def __init__(self, obs_dim, device, lr=3e-4, gamma=0.99, gae_lambda=0.95, clip=0.2, epochs=4, minibatch=32768,
                  vf_coef=0.5, max_grad_norm=0.5, seed=0, use_graph=False, ent_coef=0.0, clip_range_vf=None, normalize_advantage="batch",
-                 target_kl=None, lr_schedule=None):
+                 target_kl=None, lr_schedule=None, shuffle="torch"):
         from . import lib
         del use_graph
         _set_terms(self, ent_coef, clip_range_vf, normalize_advantage, target_kl, lr_schedule)
+        if shuffle not in ("torch", "device"):
+            raise ValueError(f"shuffle must be 'torch' or 'device', got {shuffle!r}")
+        # "device": the whole update is one so100_learner_update call and the minibatches are a function of (seed, shuffle_epoch) alone --
+        # torch's generator has no part in them.  shuffle_epoch counts the epochs shuffled so far; a resumed run sets it.
+        self.shuffle, self.shuffle_seed, self.shuffle_epoch = shuffle, seed, 0
         # any option on: the extended step (so100_learner_minibatch_step_ex); none: the step as it always was
         self._extended = ent_coef != 0 or clip_range_vf is not None or normalize_advantage != "batch" or target_kl is not None or lr_schedule is not None
         self.vf_coef = vf_coef
@@ -247,7 +252,11 @@ class FusedPPO:
         target_kl stopped the update; the applied steps are counted on the device and read here, once, with the statistics -- nothing
         synchronises in the middle of an update.  At the defaults the old step runs and approx_kl, which only the extended step forms, is NaN.
         progress_remaining (keyword only, after perms: PPO.update(b, progress_remaining) has no perms) is the argument of lr_schedule.
-        The explained-variance launches go to a side stream, beside the minibatch steps, and are joined before the one read of the results."""
+        The explained-variance launches go to a side stream, beside the minibatch steps, and are joined before the one read of the results.
+        With shuffle="device" (constructor) the same update is one so100_learner_update call: the permutations are the library's, a function of
+        (seed, shuffle_epoch), everything runs on the current stream, and the returned keys mean what they mean above."""
+        if self.shuffle == "device" and perms is not None:
+            raise ValueError("perms= injects torch-side permutations: with shuffle='device' the library draws them from (seed, shuffle_epoch)")
         L = self._handle()
         buf = self._packed(b)
         T, N = buf.shape[0], buf.shape[1]
@@ -261,8 +270,11 @@ class FusedPPO:
             self._out = torch.zeros(25, device=dev)
             self._stats, self._diag, self._ev = self._out[0:4], self._out[0:8], self._out[8:9]
             self._state = torch.zeros(2, dtype=torch.int32, device=dev)
+            self._perm = torch.zeros(T * N, dtype=torch.int64, device=dev) if self.shuffle == "device" else None
             self._shape = (T, N)
         tobs = b.get("terminal_obs")
+        if self.shuffle == "device":
+            return self._update_on_device(L, b, buf, tobs, progress_remaining)
         L.advantages(buf, b["last_obs"].contiguous(), self.params, self._adv, self._ret, self._adv_stats, terminal_obs=tobs)
         cur = torch.cuda.current_stream(self.device)
         if self._side is None:
@@ -292,6 +304,27 @@ class FusedPPO:
         if self._extended:
             self._out[23:25].copy_(self._state)
         st = self._read_out(b, buf, cur)                                 # the update's only synchronisation
+        return self._results(st, first_step, last)
+
+    def _update_on_device(self, L, b, buf, tobs, progress_remaining):
+        """shuffle="device": everything update() enqueues above, the permutations included, by one so100_learner_update call on the current stream"""
+        n = buf.shape[0] * buf.shape[1]; mb = min(self.mb, n)
+        first_step = self.adam_step
+        last = first_step + self.epochs * ((n + mb - 1) // mb)
+        terms = None
+        if self._extended:
+            terms = dict(ent_coef=self.ent_coef, clip_range_vf=self.clip_range_vf, normalize_advantage=self.normalize_advantage, target_kl=self.target_kl,
+                         lr=None if self.lr_schedule is None else float(self.lr_schedule(progress_remaining)))
+        L.update(buf, b["last_obs"].contiguous(), self.params, self.adam_m, self.adam_v, self._adv, self._ret, self._adv_stats, self._perm, self._out[0:15],
+                 epochs=self.epochs, mb=mb, adam_step0=first_step, shuffle_seed=self.shuffle_seed, shuffle_epoch0=self.shuffle_epoch, terminal_obs=tobs,
+                 terms=terms, update_state=self._state if self._extended else None)
+        self.shuffle_epoch += self.epochs
+        if self._extended:
+            self._out[23:25].copy_(self._state)
+        return self._results(self._read_out(b, buf, None), first_step, last)
+
+    def _results(self, st, first_step, last):
+        """update()'s dict from the values of self._out on the host; advances adam_step by the steps applied"""
         if self._extended:
             stopped, applied = int(st[23]), int(st[24])
             assert applied == last - first_step or stopped
@@ -307,9 +340,10 @@ class FusedPPO:
 
     def _read_out(self, b, buf, cur):
         """log_std after the update and the two reward means join the statistics in self._out (one small launch), the side stream is joined,
-        and the whole buffer comes to the host in one transfer"""
+        (cur: the stream it ran beside; None when nothing went there) and the whole buffer comes to the host in one transfer"""
         rew = buf[..., self.obs_dim + 6].mean().view(1)
         raw = b.get("raw_reward_mean")
         torch.cat([self.net.log_std.detach(), rew, rew if raw is None else raw.detach().to(torch.float32).view(1)], out=self._out[15:23])
-        cur.wait_stream(self._side)
+        if cur is not None:
+            cur.wait_stream(self._side)
         return self._out.tolist()

@@ -14,6 +14,7 @@ updates, the evaluations that fall into the run and the final saves; the driver'
 Every GPU step runs in a child process under its own time limit; the first one that fails ends the run.  One JSON document is written.
 
     python tools/kbench_learner.py --part update --obs-dim 15 [--rounds 1]      # one step by hand (e.g. under rocprofv3)
+    python tools/kbench_learner.py --part update --obs-dim 15 --shuffle device   # FusedPPO(shuffle="device") against FusedPPO's default path
     python tools/kbench_learner.py --terms [--out profiles/learner_terms_kbench.json] [--commit LABEL]
 
 --terms: the extended step (so100_learner_minibatch_step_ex, SB3's remaining loss terms) against the old one, per minibatch of 32 768 on the
@@ -34,7 +35,9 @@ sys.path.insert(0, ROOT)
 T, N, EPOCHS, MB = 64, 4096, 4, 32768
 
 
-def part_update(obs_dim, rounds, reps, warmup):
+def part_update(obs_dim, rounds, reps, warmup, shuffle="torch"):
+    if shuffle == "device":
+        return part_update_shuffle(obs_dim, rounds, reps["fused"], warmup)
     import torch
     from so100_mujoco_rl_amd.ppo import PPO, FusedPPO
     from so100_mujoco_rl_amd.rollout import RolloutChunk
@@ -74,6 +77,42 @@ def part_update(obs_dim, rounds, reps, warmup):
         med = sorted(ms[name])[len(ms[name]) // 2]
         res[name] = {"ms_per_update_rounds": ms[name], "ms_per_update": med, "updates_per_round": reps[name], "samples_per_s": round(T * N * EPOCHS / med * 1e3)}
     res["torch_over_fused"] = round(res["torch"]["ms_per_update"] / res["fused"]["ms_per_update"], 2)
+    print("KBENCH " + json.dumps(res), flush=True)
+
+
+def part_update_shuffle(obs_dim, rounds, reps, warmup):
+    """--part update --shuffle device: FusedPPO.update with the one-call update and the device shuffle against the default path (torch.randperm,
+    the steps enqueued from Python), on the chunk of part_update, in alternation"""
+    import torch
+    from so100_mujoco_rl_amd.ppo import FusedPPO
+    from so100_mujoco_rl_amd.rollout import RolloutChunk
+    dev = torch.device("cuda", 0)
+    g = torch.Generator(device=dev); g.manual_seed(obs_dim)
+    o = obs_dim
+    learners = {"torch": FusedPPO(o, dev, seed=0), "device": FusedPPO(o, dev, seed=0, shuffle="device")}
+    c = RolloutChunk(T, N, o, dev)
+    c.buf.copy_(torch.randn(c.buf.shape, device=dev, generator=g))
+    with torch.no_grad():
+        v, lp = learners["torch"].net.evaluate(c.buf[..., :o].reshape(-1, o), c.buf[..., o:o + 6].reshape(-1, 6))
+        c.buf[..., o + 8] = v.reshape(T, N); c.buf[..., o + 9] = lp.reshape(T, N)
+        c.buf[..., o + 7] = (torch.rand(T, N, device=dev, generator=g) < 1e-3).float() * 2.0
+    b = c.unpack(); b["last_obs"] = torch.randn(N, o, device=dev, generator=g); b["packed"] = c.buf
+    res = {"obs_dim": o, "T": T, "N": N, "epochs": EPOCHS, "minibatch": MB, "samples": T * N, "card": torch.cuda.get_device_name(0)}
+    for learner in learners.values():
+        for _ in range(warmup):
+            learner.update(b)
+    ms = {k: [] for k in learners}
+    for _ in range(rounds):
+        for name, learner in learners.items():
+            e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize(); e0.record()
+            for _ in range(reps):
+                learner.update(b)
+            e1.record(); torch.cuda.synchronize()
+            ms[name].append(round(e0.elapsed_time(e1) / reps, 4))
+    for name in ms:
+        res["shuffle_" + name] = {"ms_per_update_rounds": ms[name], "ms_per_update": sorted(ms[name])[len(ms[name]) // 2], "updates_per_round": reps}
+    res["device_over_torch"] = round(res["shuffle_device"]["ms_per_update"] / res["shuffle_torch"]["ms_per_update"], 4)
     print("KBENCH " + json.dumps(res), flush=True)
 
 
@@ -164,11 +203,12 @@ def main():
     ap.add_argument("--part", choices=("all", "update", "train", "terms"), default="all")
     ap.add_argument("--terms", action="store_true", help="time the extended step with all terms on against the old one; writes profiles/learner_terms_kbench.json")
     ap.add_argument("--obs-dim", type=int, default=15); ap.add_argument("--learner", default="fused")
+    ap.add_argument("--shuffle", choices=("torch", "device"), default="torch", help="--part update: device times FusedPPO(shuffle='device') against FusedPPO's default path")
     ap.add_argument("--rounds", type=int, default=5); ap.add_argument("--warmup", type=int, default=3); ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "learner_update_kbench.json")); ap.add_argument("--commit", default="unknown")
     a = ap.parse_args()
     if a.part == "update":
-        return part_update(a.obs_dim, a.rounds, {"torch": 10, "fused": 100}, a.warmup)      # >= 0.5 s per timed window
+        return part_update(a.obs_dim, a.rounds, {"torch": 10, "fused": 100}, a.warmup, a.shuffle)      # >= 0.5 s per timed window
     if a.part == "train":
         return part_train(a.learner, a.iters)
     if a.part == "terms":
