@@ -75,6 +75,21 @@ int main(int argc, char** argv) {
         double moved = 0; for (int i = 0; i < P; i++) moved += std::fabs((double)h_new[i] - h_par[i]);
         std::printf("learner: %d params  adv_mean %.6f adv_std %.6f  policy_loss %.6f value_loss %.6f clip_fraction %.4f grad_norm %.6f  mean_param_step %.3e\n",
                     P, h_st[0], h_st[1], h_st[2], h_st[3], h_st[4], h_st[5], moved/P);
+        // ---- reward normalisation (SB3 VecNormalize's reward half): the chunk's rewards normalised into a dense array, the advantages read from it
+        {
+            const int64_t ws_bytes = so100_learner_reward_norm_workspace(T, n);
+            double* rn_state; float* rn_rew; void* rn_ws;
+            CHECK(hipMalloc(&rn_state, sizeof(double)*(3 + (size_t)n))); CHECK(hipMalloc(&rn_rew, sizeof(float)*T*n)); CHECK(hipMalloc(&rn_ws, (size_t)ws_bytes));
+            so100_reward_norm_io nio = {};
+            nio.rollout_dev = chunk; nio.state_dev = rn_state; nio.reward_dev = rn_rew; nio.workspace_dev = rn_ws; nio.workspace_bytes = ws_bytes;
+            nio.clip_reward = 10.0; nio.epsilon = 1e-8;
+            if (so100_learner_reward_norm_init(learner, rn_state, n, (void*)st) != 0 || so100_learner_normalize_rewards(learner, &nio, T, n, (void*)st) != 0 ||
+                so100_learner_advantages_r(learner, &aio, rn_rew, T, n, (void*)st) != 0) { std::fprintf(stderr, "reward normalisation: %s\n", so100_last_error()); return 1; }
+            double h_mom[3]; float h_adv[2];
+            CHECK(hipStreamSynchronize(st));
+            CHECK(hipMemcpy(h_mom, rn_state, sizeof h_mom, hipMemcpyDeviceToHost)); CHECK(hipMemcpy(h_adv, lstat, sizeof h_adv, hipMemcpyDeviceToHost));
+            std::printf("reward normalisation: return_mean %.6f return_std %.6f count %.4f  adv_std %.6f (of the normalised rewards)\n", h_mom[0], std::sqrt(h_mom[1]), h_mom[2], h_adv[1]);
+        }
         so100_learner_destroy(learner);
     }
     so100_destroy(sim);

@@ -3,9 +3,12 @@
 // step); the policy the simulator runs is a so100_policy_weights pointing into the learner's flat parameter block, so nothing is copied
 // between the two.
 // Build:  hipcc -O2 -o train_ppo examples/train_ppo.cpp -Iinclude -Lso100_mujoco_rl_amd -lso100sim -Wl,-rpath,$PWD/so100_mujoco_rl_amd
-// Run:    ./train_ppo [num_envs] [iters] [seed]
-//         one line per iteration (mean reward per step, the update's out_dev), then "param_checksum": the fp64 sum of the parameters
+// Run:    ./train_ppo [num_envs] [iters] [seed] [normalize_reward]
+//         one line per iteration (mean reward per step, the update's out_dev), then "param_checksum": the fp64 sum of the parameters.
+//         normalize_reward 1: the update normalises the rewards first (SB3 VecNormalize's reward half, so100_learner_update_r) and each
+//         line ends with return_std, the running standard deviation of the envs' discounted returns
 #include <hip/hip_runtime.h>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -24,6 +27,7 @@ static const float kScale[13] = { 0.25f, 0.0f, 0.125f, 0.0f, 0.01f, 0.0f, 0.0f, 
 int main(int argc, char** argv) {
     const int n = argc > 1 ? std::atoi(argv[1]) : 4096, iters = argc > 2 ? std::atoi(argv[2]) : 100;
     const unsigned long long seed = argc > 3 ? std::strtoull(argv[3], nullptr, 10) : 0;
+    const bool normalize_reward = argc > 4 && std::atoi(argv[4]) != 0;
     const int T = 64, epochs = 4;
     const long rows = (long)T*n;
     const int mb = (int)(rows/4 < 32768 ? rows/4 : 32768);
@@ -73,12 +77,23 @@ int main(int argc, char** argv) {
     uio.params_dev = par; uio.adam_m_dev = mom; uio.adam_v_dev = mom + P; uio.adv_dev = adv; uio.ret_dev = ret; uio.adv_stats_dev = adv_stats; uio.perm_dev = perm;
     uio.epochs = epochs; uio.mb = mb; uio.shuffle_seed = seed; uio.terms = nullptr; uio.update_state_dev = nullptr; uio.out_dev = out;
 
+    // reward normalisation: the running state, the dense normalised rewards and the workspace are this program's, like every other buffer
+    so100_reward_norm_io nio = {};
+    if (normalize_reward) {
+        const int64_t ws_bytes = so100_learner_reward_norm_workspace(T, n);
+        double* rn_state; float* rn_rewards; void* rn_ws;
+        CHECK(hipMalloc(&rn_state, sizeof(double)*(3 + (size_t)n))); CHECK(hipMalloc(&rn_rewards, sizeof(float)*rows)); CHECK(hipMalloc(&rn_ws, (size_t)ws_bytes));
+        CALL(so100_learner_reward_norm_init(learner, rn_state, n, (void*)st));
+        nio.rollout_dev = chunk; nio.state_dev = rn_state; nio.reward_dev = rn_rewards; nio.workspace_dev = rn_ws; nio.workspace_bytes = ws_bytes;
+        nio.clip_reward = 10.0; nio.epsilon = 1e-8;
+    }
+
     std::vector<float> h_chunk((size_t)rows*row);
     float h_out[SO100_UPDATE_OUT];
     for (int it = 0; it < iters; it++) {
         CALL(so100_rollout(sim, &w, &rio, T, (uint32_t)(it*T), (void*)st));
         uio.adam_step0 = it*epochs*per_epoch; uio.shuffle_epoch0 = (uint32_t)(it*epochs);
-        CALL(so100_learner_update(learner, &uio, (void*)st));
+        CALL(so100_learner_update_r(learner, &uio, normalize_reward ? &nio : nullptr, (void*)st));      // a null norm_io: so100_learner_update
         CHECK(hipMemcpyAsync(h_chunk.data(), chunk, sizeof(float)*h_chunk.size(), hipMemcpyDeviceToHost, st));     // for the reward column alone: an example's shortcut
         CHECK(hipMemcpyAsync(h_out, out, sizeof h_out, hipMemcpyDeviceToHost, st));
         CHECK(hipStreamSynchronize(st));
@@ -87,6 +102,11 @@ int main(int argc, char** argv) {
         std::printf("iter %4d  mean_reward %+.6f  policy_loss %+.6f value_loss %.6f clip_fraction %.4f grad_norm %.6f  explained_variance %+.4f  log_std",
                     it, r/rows, h_out[0], h_out[1], h_out[2], h_out[3], h_out[8]);
         for (int i = 9; i < 15; i++) std::printf(" %+.4f", h_out[i]);
+        if (normalize_reward) {
+            double moments[3];
+            CHECK(hipMemcpy(moments, nio.state_dev, sizeof moments, hipMemcpyDeviceToHost));
+            std::printf("  return_std %.4f", std::sqrt(moments[1]));
+        }
         std::printf("\n");
     }
     CHECK(hipMemcpy(h_par.data(), par, sizeof(float)*P, hipMemcpyDeviceToHost));

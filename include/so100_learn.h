@@ -156,6 +156,37 @@ typedef struct {
     float*                 out_dev;                /* [SO100_UPDATE_OUT]: [0:8] statistics / diagnostics, [8] explained variance, [9:15] log_std */
 } so100_update_io;
 
+/* Reward normalisation: the reward half of SB3's VecNormalize(norm_reward=True) with its RunningMeanStd, on the device and before the
+ * advantages (the TimeLimit bootstrap gamma V(terminal_obs) is added to the NORMALISED reward by the advantage pass, so V lives in the
+ * normalised scale).  Off unless asked for: every entry point above is untouched by it.
+ * State (state_dev, fp64, the caller's, carried from chunk to chunk): mean, var, count -- the running moments of the envs' discounted
+ * returns, initially 0, 1, 1e-4 -- then one running discounted return R[n] per env, initially 0 (so100_learner_reward_norm_init).
+ * For t = 0 .. T-1, with r[t][n] the chunk's reward column and c[t][n] its done code, everything in fp64:
+ *   R[n]   = R[n] gamma + r[t][n]                                    (gamma: the handle's, widened from float)
+ *   bm     = mean_n R[n];  bv = population variance_n R[n];  bc = N
+ *   d      = bm - mean;  tot = count + bc
+ *   mean'  = mean + d bc/tot
+ *   var'   = (var count + bv bc + d d count bc/tot)/tot
+ *   count' = tot
+ *   out[t][n] = (float) clamp(r[t][n]/sqrt(var' + epsilon), -clip_reward, +clip_reward)       (SB3: epsilon 1e-8, clip_reward 10)
+ *   R[n]   = 0 where c[t][n] != 0                                    (after the update; terminated or truncated)
+ * The variance used at step t includes step t.  Two chunks processed one after the other equal one chunk of 2T.  The chunk is read only.
+ * Order of the sums (the same bits every run, no floating-point atomics): the envs are cut into blocks of 64 in index order; a block's
+ * mean is its sum by a fixed binary tree (slot i += slot i + w, w = 32, 16 .. 1) over its count, its M2 the same tree over the squared
+ * deviations from that mean; the blocks' (n, mean, M2) are merged in block order by Chan et al.'s update; the steps follow in t order.
+ * Three launches: the R recurrence and the block moments for every t (one workgroup per block), the merge with the T running-moment
+ * updates, the elementwise scale.  workspace_dev holds the block moments and the T denominators between them; it is the caller's, at least
+ * so100_learner_reward_norm_workspace(T, N) bytes, 8-byte aligned. */
+typedef struct {
+    const float* rollout_dev;      /* [T][N][obs_dim+10]: the reward and done-code columns are read                              */
+    double*      state_dev;        /* [3 + N] in/out: mean, var, count, then R[N]                                                */
+    float*       reward_dev;       /* [T][N] out: the normalised rewards                                                         */
+    void*        workspace_dev;    /* scratch of this call                                                                       */
+    int64_t      workspace_bytes;  /* >= so100_learner_reward_norm_workspace(T, N)                                               */
+    double       clip_reward;      /* > 0; SB3: 10                                                                               */
+    double       epsilon;          /* >= 0; SB3: 1e-8                                                                            */
+} so100_reward_norm_io;
+
 int  so100_learner_num_params(int32_t obs_dim);                          /* 10829 (obs_dim 15), 9933 (8); < 0 otherwise */
 int  so100_learner_param_offset(int32_t obs_dim, const char* name);      /* name: a member of so100_policy_weights; < 0 if unknown */
 int  so100_learner_param_size(int32_t obs_dim, const char* name);        /* elements of that tensor                      */
@@ -179,6 +210,19 @@ int  so100_learner_explained_variance(so100_learner* learner, const float* rollo
 /* perm_dev [n] int64 = the permutation of (seed, epoch, n) specified above, 1 <= n <= 2^30.  One launch. */
 int  so100_learner_shuffle(so100_learner* learner, uint64_t seed, uint32_t epoch, int64_t n, int64_t* perm_dev, void* hip_stream);
 int  so100_learner_update(so100_learner* learner, const so100_update_io* io, void* hip_stream);
+
+/* bytes of so100_reward_norm_io.workspace_dev for a chunk of T steps x N envs; < 0 when T or N is not positive.  Needs no handle. */
+int64_t so100_learner_reward_norm_workspace(int32_t T, int32_t N);
+/* state_dev [3 + N] = 0, 1, 1e-4 and N zero returns.  One launch. */
+int  so100_learner_reward_norm_init(so100_learner* learner, double* state_dev, int32_t N, void* hip_stream);
+/* the normalisation specified above on one chunk: reward_dev [T][N] out, state_dev advanced by T steps.  Three launches. */
+int  so100_learner_normalize_rewards(so100_learner* learner, const so100_reward_norm_io* io, int32_t T, int32_t N, void* hip_stream);
+/* so100_learner_advantages reading the step's reward from reward_dev [T][N] (step stride N) instead of the chunk's reward column; the
+ * TimeLimit bootstrap is added to it as there.  reward_dev null: exactly so100_learner_advantages. */
+int  so100_learner_advantages_r(so100_learner* learner, const so100_advantages_io* io, const float* reward_dev, int32_t T, int32_t N, void* hip_stream);
+/* so100_learner_update with so100_learner_normalize_rewards(norm_io, io->T, io->N) enqueued first and the advantages reading
+ * norm_io->reward_dev: still one call, nothing synchronises, and a rejected call enqueues nothing.  norm_io null: so100_learner_update. */
+int  so100_learner_update_r(so100_learner* learner, const so100_update_io* io, const so100_reward_norm_io* norm_io, void* hip_stream);
 
 #ifdef __cplusplus
 }

@@ -18,6 +18,8 @@
 // Reduction (so100_learn_reduce): one thread per parameter sums the partials in workgroup order and leaves each block's sum of
 // squares; so100_learn_adam sums those in block order (every thread the same sum), decides the clip (EX: and the KL stop) and applies Adam.
 // No floating-point atomics anywhere; every sum has a fixed order => bit-identical results for identical inputs.
+// Reward normalisation (so100_learner_normalize_rewards, SB3's VecNormalize reward half): three launches in fp64 ahead of the advantages, which
+// then read the normalised rewards from a dense array instead of the chunk's column; see "reward normalisation" below.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -410,14 +412,17 @@ __global__ __launch_bounds__(256) void so100_learn_values(const float* __restric
     }
 }
 
+// rewards: null, the chunk's reward column; else [T][N] dense (so100_learner_advantages_r), the step's reward in place of that column
 template <int OD>
-__global__ __launch_bounds__(64) void so100_learn_gae(const float* chunk, int T, int N, bool bootstrap, float gamma, float lam, float* adv, float* ret) {
+__global__ __launch_bounds__(64) void so100_learn_gae(const float* chunk, const float* rewards, int T, int N, bool bootstrap, float gamma, float lam, float* adv, float* ret) {
     constexpr int ROW = OD + ROW_EXTRA;
     const int n = blockIdx.x*64 + threadIdx.x;
     if (n >= N) return;
     const float* c = chunk + (size_t)n*ROW + OD;
     const float next_v_last = adv[(size_t)(T - 1)*N + n];
-    gae_scan_env<float>(T, c + ROW_REWARD, c + ROW_DONE, c + ROW_VALUE, (long)N*ROW, bootstrap ? ret + n : nullptr, next_v_last, gamma, lam, adv + n, ret + n, (long)N);
+    const float* rew = rewards ? rewards + n : c + ROW_REWARD;
+    const long rew_stride = rewards ? (long)N : (long)N*ROW;
+    gae_scan_env<float>(T, rew, rew_stride, c + ROW_DONE, c + ROW_VALUE, (long)N*ROW, bootstrap ? ret + n : nullptr, next_v_last, gamma, lam, adv + n, ret + n, (long)N);
 }
 
 __device__ __forceinline__ float block_sum_1024(float v, float* sh) {      // fixed tree: the same order every run
@@ -523,6 +528,99 @@ __global__ __launch_bounds__(256) void so100_learn_ev_merge(const float* __restr
         n = tot; differs += p[5];
     }
     out[0] = (differs == 0.0f || m2r == 0.0f) ? __builtin_nanf("") : 1.0f - m2d/m2r;
+}
+
+// ---- reward normalisation (so100_learner_normalize_rewards) -------------------------------------------------------------------------------
+// The dependency between steps runs through three scalars only (mean, var, count); each env's discounted return is a recurrence of its own.
+// So the pass is three launches.  Scan: one wave per block of RN_BLOCK envs, lane = env, walks t with its R in a register and leaves the
+// block's (mean, M2) of R for every t (two wave tree sums per step over DPP/permute lanes: no LDS, no barrier), all blocks side by side over
+// the CUs; rewards and codes are fetched RN_AHEAD steps ahead of the sums that wait on nothing else.  Merge: one workgroup; thread t merges
+// the blocks' moments of step t in block order (the steps are independent there), then one thread runs the T running-moment updates in t
+// order from LDS and leaves the T denominators sqrt(var' + epsilon).  Scale: one thread per entry.  fp64 throughout, rounded at the store.
+constexpr int RN_AHEAD = 8, RN_MERGE_THREADS = 256;
+
+// workspace: [T][G][2] doubles (mean, M2 of block g at step t), then [T] denominators
+__host__ __device__ constexpr long rn_blocks(long N) { return (N + RN_BLOCK - 1)/RN_BLOCK; }
+constexpr long rn_workspace_doubles(long T, long N) { return T*rn_blocks(N)*2 + T; }
+
+// lane 0 ends with block_tree_sum's sum: lane i += lane i + w for w = 32 .. 1 (a lane past 63 - w adds its own value: never read by lane 0's tree)
+__device__ __forceinline__ double wave_tree_sum(double v) {
+#pragma unroll
+    for (int w = RN_BLOCK/2; w > 0; w >>= 1) v += __shfl_down(v, w, RN_BLOCK);
+    return __shfl(v, 0, RN_BLOCK);
+}
+
+__global__ __launch_bounds__(RN_BLOCK) void so100_learn_rn_scan(const float* __restrict__ chunk, int row, int rew_col, int code_col, int T, int N, double gamma,
+                                                               double* __restrict__ state, double* __restrict__ part) {
+    const int g = blockIdx.x, G = gridDim.x, lane = threadIdx.x, n = g*RN_BLOCK + lane;
+    const bool own = n < N;
+    const int count = N - g*RN_BLOCK < RN_BLOCK ? N - g*RN_BLOCK : RN_BLOCK;
+    double* __restrict__ Rn = state + 3 + (own ? n : 0);
+    double R = own ? *Rn : 0.0;
+    for (int t0 = 0; t0 < T; t0 += RN_AHEAD) {
+        float r[RN_AHEAD], c[RN_AHEAD];
+#pragma unroll
+        for (int k = 0; k < RN_AHEAD; k++) {
+            const bool in = own && t0 + k < T;
+            const float* p = chunk + ((size_t)(in ? t0 + k : 0)*N + (in ? n : 0))*row;
+            r[k] = in ? p[rew_col] : 0.0f; c[k] = in ? p[code_col] : 0.0f;
+        }
+#pragma unroll
+        for (int k = 0; k < RN_AHEAD; k++) {
+            const int t = t0 + k;
+            if (t < T) {                                                     // uniform over the wave
+                R = own ? return_step<double>(R, gamma, (double)r[k]) : 0.0;
+                const double mean = block_mean<double>(wave_tree_sum(R), count);
+                const double m2 = wave_tree_sum(own ? squared_deviation<double>(R, mean) : 0.0);
+                if (lane == 0) { double* o = part + ((size_t)t*G + g)*2; o[0] = mean; o[1] = m2; }
+                if (c[k] != 0.0f) R = 0.0;
+            }
+        }
+    }
+    if (own) *Rn = R;
+}
+
+__global__ __launch_bounds__(RN_MERGE_THREADS) void so100_learn_rn_merge(const double* __restrict__ part, int T, int N, int G, double epsilon,
+                                                                         double* __restrict__ state, double* __restrict__ denom) {
+    __shared__ double bm[RN_MERGE_THREADS], bv[RN_MERGE_THREADS];
+    const int tid = threadIdx.x;
+    double mean = 0.0, var = 0.0, cnt = 0.0;
+    if (tid == 0) { mean = state[0]; var = state[1]; cnt = state[2]; }
+    for (int base = 0; base < T; base += RN_MERGE_THREADS) {
+        const int t = base + tid;
+        if (t < T) {
+            const double* p = part + (size_t)t*G*2;
+            double na = (double)(N < RN_BLOCK ? N : RN_BLOCK), m = p[0], m2 = p[1];
+            for (int g = 1; g < G; g++) {
+                const int left = N - g*RN_BLOCK;
+                chan_merge<double>(na, m, m2, (double)(left < RN_BLOCK ? left : RN_BLOCK), p[2*g], p[2*g + 1]);
+            }
+            bm[tid] = m; bv[tid] = m2/(double)N;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            const int steps = T - base < RN_MERGE_THREADS ? T - base : RN_MERGE_THREADS;
+            for (int i = 0; i < steps; i++) {
+                running_moment_update<double>(mean, var, cnt, bm[i], bv[i], (double)N);
+                bm[i] = reward_denominator<double>(var, epsilon);
+            }
+        }
+        __syncthreads();
+        if (t < T) denom[t] = bm[tid];
+        __syncthreads();
+    }
+    if (tid == 0) { state[0] = mean; state[1] = var; state[2] = cnt; }
+}
+
+constexpr int RN_SCALE_GRID_MAX = 2048;
+__global__ __launch_bounds__(256) void so100_learn_rn_scale(const float* __restrict__ chunk, int row, int rew_col, long TN, int N, const double* __restrict__ denom,
+                                                            double clip, float* __restrict__ out) {
+    for (long i = (long)blockIdx.x*256 + threadIdx.x; i < TN; i += (long)gridDim.x*256)
+        out[i] = reward_scale<float, double>((double)chunk[i*row + rew_col], denom[i/N], clip);
+}
+
+__global__ __launch_bounds__(256) void so100_learn_rn_init(double* __restrict__ state, long len) {
+    for (long i = (long)blockIdx.x*256 + threadIdx.x; i < len; i += (long)gridDim.x*256) state[i] = i == 1 ? 1.0 : i == 2 ? 1e-4 : 0.0;
 }
 
 // ---- the whole update (so100_learner_update) ---------------------------------------------------------------------------------------------
@@ -639,6 +737,54 @@ static int minibatch_step(so100_learner* L, const so100_minibatch_io* io, const 
     return 0;
 }
 
+// so100_reward_norm_io's checks and launches, apart: so100_learner_update_r runs every check of the update before it enqueues the first launch
+static int check_reward_norm(const so100_reward_norm_io* io, int T, int N, const char* fn) {
+    if (T < 1) return fail(SO100_E_INVALID, "%s: T must be >= 1, got %d", fn, T);
+    if (N < 1) return fail(SO100_E_INVALID, "%s: N must be >= 1, got %d", fn, N);
+    if (!io->rollout_dev || !io->state_dev || !io->reward_dev || !io->workspace_dev)
+        return fail(SO100_E_INVALID, "%s: rollout/state/reward/workspace pointers are required", fn);
+    if (!(io->clip_reward > 0.0)) return fail(SO100_E_INVALID, "%s: clip_reward must be > 0", fn);
+    if (!(io->epsilon >= 0.0)) return fail(SO100_E_INVALID, "%s: epsilon must be >= 0", fn);
+    const long need = rn_workspace_doubles(T, N)*(long)sizeof(double);
+    if (io->workspace_bytes < need) return fail(SO100_E_INVALID, "%s: the workspace holds %ld bytes, T = %d and N = %d need %ld", fn, (long)io->workspace_bytes, T, N, need);
+    if (((uintptr_t)io->workspace_dev & 7u) != 0) return fail(SO100_E_INVALID, "%s: the workspace must be 8-byte aligned", fn);
+    return 0;
+}
+
+static void enqueue_reward_norm(const so100_learner* L, const so100_reward_norm_io* io, int T, int N, hipStream_t st) {
+    const int od = L->cfg.obs_dim, row = od + ROW_EXTRA, G = (int)rn_blocks(N);
+    const long TN = (long)T*(long)N, want = (TN + 255)/256;
+    double* part = (double*)io->workspace_dev;
+    double* denom = part + (size_t)T*G*2;
+    hipLaunchKernelGGL(so100_learn_rn_scan, dim3((unsigned)G), dim3(RN_BLOCK), 0, st, io->rollout_dev, row, od + ROW_REWARD, od + ROW_DONE, T, N, (double)L->cfg.gamma,
+                       io->state_dev, part);
+    hipLaunchKernelGGL(so100_learn_rn_merge, dim3(1), dim3(RN_MERGE_THREADS), 0, st, (const double*)part, T, N, G, io->epsilon, io->state_dev, denom);
+    hipLaunchKernelGGL(so100_learn_rn_scale, dim3((unsigned)(want < RN_SCALE_GRID_MAX ? want : RN_SCALE_GRID_MAX)), dim3(256), 0, st, io->rollout_dev, row, od + ROW_REWARD,
+                       TN, N, (const double*)denom, io->clip_reward, io->reward_dev);
+}
+
+// so100_learner_advantages and so100_learner_advantages_r: reward_dev null reads the chunk's reward column
+static int advantages(so100_learner* L, const so100_advantages_io* io, const float* reward_dev, int32_t T, int32_t N, void* stream, const char* fn) {
+    if (!L || !io) return fail(SO100_E_INVALID, "%s: null argument", fn);
+    if (T < 1) return fail(SO100_E_INVALID, "%s: T must be >= 1, got %d", fn, T);
+    if (N < 1) return fail(SO100_E_INVALID, "%s: N must be >= 1, got %d", fn, N);
+    if (!io->rollout_dev || !io->last_obs_dev || !io->params_dev || !io->adv_dev || !io->ret_dev || !io->adv_stats_dev)
+        return fail(SO100_E_INVALID, "%s: rollout/last_obs/params/adv/ret/adv_stats pointers are required", fn);
+    SO100_ON_DEVICE(L->cfg.device, fn);
+    const long TN = (long)T*(long)N;
+    const long vblocks = (TN + N + 255)/256;
+    if (vblocks > 0x7fffffffL) return fail(SO100_E_INVALID, "%s: T*N is too large", fn);
+    const hipStream_t st = (hipStream_t)stream;
+    const bool boot = io->terminal_obs_chunk_dev != nullptr;
+    SO100_WITH_OBS_DIM(L->cfg.obs_dim,
+        hipLaunchKernelGGL((so100_learn_values<OD>), dim3((unsigned)vblocks), dim3(256), 0, st, io->rollout_dev, io->terminal_obs_chunk_dev, io->last_obs_dev, io->params_dev, TN, N, io->adv_dev, io->ret_dev);
+        hipLaunchKernelGGL((so100_learn_gae<OD>), dim3((unsigned)((N + 63)/64)), dim3(64), 0, st, io->rollout_dev, reward_dev, T, N, boot, L->cfg.gamma, L->cfg.gae_lambda, io->adv_dev, io->ret_dev););
+    hipLaunchKernelGGL(so100_learn_adv_stats, dim3(1), dim3(ADV_THREADS), 0, st, (const float*)io->adv_dev, TN, io->adv_stats_dev);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(SO100_E_LAUNCH, "%s: %s (HIP error %ld)", fn, hipGetErrorString(e), (long)e);
+    return 0;
+}
+
 extern "C" {
 
 int so100_learner_num_params(int32_t obs_dim) { return obs_dim == 15 ? num_params(15) : obs_dim == 8 ? num_params(8) : SO100_E_INVALID; }
@@ -703,23 +849,11 @@ void so100_learner_destroy(so100_learner* L) {
 }
 
 int so100_learner_advantages(so100_learner* L, const so100_advantages_io* io, int32_t T, int32_t N, void* stream) {
-    if (!L || !io) return fail(SO100_E_INVALID, "so100_learner_advantages: null argument");
-    if (T < 1) return fail(SO100_E_INVALID, "so100_learner_advantages: T must be >= 1, got %d", T);
-    if (N < 1) return fail(SO100_E_INVALID, "so100_learner_advantages: N must be >= 1, got %d", N);
-    if (!io->rollout_dev || !io->last_obs_dev || !io->params_dev || !io->adv_dev || !io->ret_dev || !io->adv_stats_dev)
-        return fail(SO100_E_INVALID, "so100_learner_advantages: rollout/last_obs/params/adv/ret/adv_stats pointers are required");
-    SO100_ON_DEVICE(L->cfg.device, "so100_learner_advantages");
-    const long TN = (long)T*(long)N;
-    const long vblocks = (TN + N + 255)/256;
-    if (vblocks > 0x7fffffffL) return fail(SO100_E_INVALID, "so100_learner_advantages: T*N is too large");
-    const hipStream_t st = (hipStream_t)stream;
-    const bool boot = io->terminal_obs_chunk_dev != nullptr;
-    SO100_WITH_OBS_DIM(L->cfg.obs_dim,
-        hipLaunchKernelGGL((so100_learn_values<OD>), dim3((unsigned)vblocks), dim3(256), 0, st, io->rollout_dev, io->terminal_obs_chunk_dev, io->last_obs_dev, io->params_dev, TN, N, io->adv_dev, io->ret_dev);
-        hipLaunchKernelGGL((so100_learn_gae<OD>), dim3((unsigned)((N + 63)/64)), dim3(64), 0, st, io->rollout_dev, T, N, boot, L->cfg.gamma, L->cfg.gae_lambda, io->adv_dev, io->ret_dev););
-    hipLaunchKernelGGL(so100_learn_adv_stats, dim3(1), dim3(ADV_THREADS), 0, st, (const float*)io->adv_dev, TN, io->adv_stats_dev);
-    HIP_TRY(hipGetLastError(), SO100_E_LAUNCH, "so100_learner_advantages: ");
-    return 0;
+    return advantages(L, io, nullptr, T, N, stream, "so100_learner_advantages");
+}
+
+int so100_learner_advantages_r(so100_learner* L, const so100_advantages_io* io, const float* reward_dev, int32_t T, int32_t N, void* stream) {
+    return advantages(L, io, reward_dev, T, N, stream, "so100_learner_advantages_r");
 }
 
 int so100_learner_minibatch_step(so100_learner* L, const so100_minibatch_io* io, void* stream) {
@@ -761,8 +895,10 @@ int so100_learner_shuffle(so100_learner* L, uint64_t seed, uint32_t epoch, int64
     return 0;
 }
 
-int so100_learner_update(so100_learner* L, const so100_update_io* io, void* stream) {
-    const char* const fn = "so100_learner_update";
+}  // extern "C"
+
+// so100_learner_update (nio null) and so100_learner_update_r
+static int update(so100_learner* L, const so100_update_io* io, const so100_reward_norm_io* nio, void* stream, const char* fn) {
     if (!L || !io) return fail(SO100_E_INVALID, "%s: null argument", fn);
     if (io->T < 1) return fail(SO100_E_INVALID, "%s: T must be >= 1, got %d", fn, io->T);
     if (io->N < 1) return fail(SO100_E_INVALID, "%s: N must be >= 1, got %d", fn, io->N);
@@ -780,11 +916,17 @@ int so100_learner_update(so100_learner* L, const so100_update_io* io, void* stre
         const int rc = check_terms(io->terms, io->update_state_dev, fn);
         if (rc != 0) return rc;
     }
+    if (nio) {
+        const int rc = check_reward_norm(nio, io->T, io->N, fn);
+        if (rc != 0) return rc;
+        if (nio->rollout_dev != io->rollout_dev) return fail(SO100_E_INVALID, "%s: the reward normalisation reads another chunk than the update", fn);
+    }
     SO100_ON_DEVICE(L->cfg.device, fn);
     const hipStream_t st = (hipStream_t)stream;
     int rc;
+    if (nio) enqueue_reward_norm(L, nio, io->T, io->N, st);
     so100_advantages_io aio = { io->rollout_dev, io->terminal_obs_chunk_dev, io->last_obs_dev, io->params_dev, io->adv_dev, io->ret_dev, io->adv_stats_dev };
-    if ((rc = so100_learner_advantages(L, &aio, io->T, io->N, stream)) != 0) return rc;
+    if ((rc = advantages(L, &aio, nio ? nio->reward_dev : nullptr, io->T, io->N, stream, fn)) != 0) return rc;
     if ((rc = so100_learner_explained_variance(L, io->rollout_dev, io->ret_dev, n, io->out_dev + 8, stream)) != 0) return rc;
     if (io->update_state_dev) hipLaunchKernelGGL(so100_learn_zero_state, dim3(1), dim3(64), 0, st, io->update_state_dev);
     so100_minibatch_io mio;
@@ -802,6 +944,42 @@ int so100_learner_update(so100_learner* L, const so100_update_io* io, void* stre
             if ((rc = minibatch_step(L, &mio, io->terms, io->out_dev, io->update_state_dev, stream, fn)) != 0) return rc;
         }
     }
+    return 0;
+}
+
+extern "C" {
+
+int so100_learner_update(so100_learner* L, const so100_update_io* io, void* stream) { return update(L, io, nullptr, stream, "so100_learner_update"); }
+
+int so100_learner_update_r(so100_learner* L, const so100_update_io* io, const so100_reward_norm_io* norm_io, void* stream) {
+    return update(L, io, norm_io, stream, "so100_learner_update_r");
+}
+
+int64_t so100_learner_reward_norm_workspace(int32_t T, int32_t N) {
+    if (T < 1 || N < 1) return (int64_t)fail(SO100_E_INVALID, "so100_learner_reward_norm_workspace: T and N must be >= 1, got %d and %d", T, N);
+    return (int64_t)(rn_workspace_doubles(T, N)*(long)sizeof(double));
+}
+
+int so100_learner_reward_norm_init(so100_learner* L, double* state_dev, int32_t N, void* stream) {
+    const char* const fn = "so100_learner_reward_norm_init";
+    if (!L) return fail(SO100_E_INVALID, "%s: null argument", fn);
+    if (N < 1) return fail(SO100_E_INVALID, "%s: N must be >= 1, got %d", fn, N);
+    if (!state_dev) return fail(SO100_E_INVALID, "%s: the state pointer is required", fn);
+    SO100_ON_DEVICE(L->cfg.device, fn);
+    const long len = 3 + (long)N, want = (len + 255)/256;
+    hipLaunchKernelGGL(so100_learn_rn_init, dim3((unsigned)(want < 1024 ? want : 1024)), dim3(256), 0, (hipStream_t)stream, state_dev, len);
+    HIP_TRY(hipGetLastError(), SO100_E_LAUNCH, "so100_learner_reward_norm_init: ");
+    return 0;
+}
+
+int so100_learner_normalize_rewards(so100_learner* L, const so100_reward_norm_io* io, int32_t T, int32_t N, void* stream) {
+    const char* const fn = "so100_learner_normalize_rewards";
+    if (!L || !io) return fail(SO100_E_INVALID, "%s: null argument", fn);
+    const int rc = check_reward_norm(io, T, N, fn);
+    if (rc != 0) return rc;
+    SO100_ON_DEVICE(L->cfg.device, fn);
+    enqueue_reward_norm(L, io, T, N, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError(), SO100_E_LAUNCH, "so100_learner_normalize_rewards: ");
     return 0;
 }
 

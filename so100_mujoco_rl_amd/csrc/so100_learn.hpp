@@ -6,6 +6,7 @@
 //   ppo_loss_head       the PPO._step loss of one sample with its derivatives towards the network outputs
 //   ppo_loss_head_ex    the same with SB3's entropy bonus, value clipping and approx_kl
 //   clip_adam_update    clip_grad_norm_'s scaling + one torch.optim.Adam step of one parameter
+//   return_step .. reward_scale   SB3's VecNormalize(norm_reward=True): the running return, block moments, Chan merge, running moments, scale
 //   shuffle_index       one entry of an epoch's permutation (the one piece that reads the simulator: see there)
 #pragma once
 #include <stdint.h>
@@ -49,13 +50,14 @@ SO100_LHD double lsqrt(double x) { return __builtin_sqrt(x); }
 // One env, backwards over its T steps.  reward / code / value: the env's columns of the packed chunk, `in_stride` scalars between steps.
 // boot: gamma-less V(terminal_observation) of the steps whose done code is 2, `out_stride` between steps, or null (no bootstrap); it may
 // alias `ret` (entry t is read before ret[t] is written).  next_v_last = V(last_obs).  Returns nothing; adv / ret get T entries each.
+// The reward has a stride of its own: with reward normalisation it comes from a dense [T][N] array, not from the chunk.
 template <class S>
-SO100_LHD void gae_scan_env(int T, const S* reward, const S* code, const S* value, long in_stride, const S* boot, S next_v_last,
+SO100_LHD void gae_scan_env(int T, const S* reward, long reward_stride, const S* code, const S* value, long in_stride, const S* boot, S next_v_last,
                             S gamma, S lam, S* adv, S* ret, long out_stride) {
     S g = S(0), next_v = next_v_last;
     for (int t = T - 1; t >= 0; t--) {
         const S c = code[t*in_stride], v = value[t*in_stride];
-        S r = reward[t*in_stride];
+        S r = reward[t*reward_stride];
         if (boot != nullptr && c == S(2)) r += gamma*boot[t*out_stride];          // TimeLimit truncation only: not a terminal state
         const S nonterm = c == S(0) ? S(1) : S(0);
         const S delta = r + gamma*next_v*nonterm - v;
@@ -64,6 +66,13 @@ SO100_LHD void gae_scan_env(int T, const S* reward, const S* code, const S* valu
         ret[t*out_stride] = g + v;
         next_v = v;
     }
+}
+
+// the three columns of one packed chunk: one stride
+template <class S>
+SO100_LHD void gae_scan_env(int T, const S* reward, const S* code, const S* value, long in_stride, const S* boot, S next_v_last,
+                            S gamma, S lam, S* adv, S* ret, long out_stride) {
+    gae_scan_env<S>(T, reward, in_stride, code, value, in_stride, boot, next_v_last, gamma, lam, adv, ret, out_stride);
 }
 
 // ---- loss head ----------------------------------------------------------------------------------------------------------------------------
@@ -195,6 +204,56 @@ SO100_LHD S clip_adam_update(S g, S clip_coef, S& p, S& m, S& v, S step_size, S 
     const S denom = lsqrt(v)/bc2_sqrt + eps;
     p = p - step_size*(m/denom);
     return g;
+}
+
+// ---- reward normalisation -----------------------------------------------------------------------------------------------------------------
+// SB3's VecNormalize(norm_reward=True) / RunningMeanStd as include/so100_learn.h ("Reward normalisation") specifies it.  S is double in both
+// instantiations that ship (the kernels and tests/_rewnormcheck); only reward_scale's result is rounded, to OUT.
+constexpr int RN_BLOCK = 64;       // envs per block of the moments: one wave, one workgroup of the scan
+
+// the running discounted return of one env after this step's reward
+template <class S>
+SO100_LHD S return_step(S R, S gamma, S r) { return R*gamma + r; }
+
+// The block moments' fixed tree over RN_BLOCK slots: slot i += slot i + w for w = 32, 16 .. 1; slot 0 ends as the sum.  The kernel runs
+// the same additions across a wave's lanes (lane i takes lane i + w's value); slots past the block's count hold 0.
+template <class S>
+SO100_LHD S block_tree_sum(S* slot) {
+    for (int w = RN_BLOCK/2; w > 0; w >>= 1)
+        for (int i = 0; i < w; i++) slot[i] += slot[i + w];
+    return slot[0];
+}
+template <class S>
+SO100_LHD S block_mean(S sum, int count) { return sum/S(count); }
+template <class S>
+SO100_LHD S squared_deviation(S R, S mean) { const S d = R - mean; return d*d; }
+
+// Chan et al.: (na, mean, m2) absorbs (nb, mean_b, m2_b); both counts positive
+template <class S>
+SO100_LHD void chan_merge(S& na, S& mean, S& m2, S nb, S mean_b, S m2_b) {
+    const S tot = na + nb, d = mean_b - mean;
+    mean = mean + d*nb/tot;
+    m2 = m2 + m2_b + d*d*na*nb/tot;
+    na = tot;
+}
+
+// RunningMeanStd.update_from_moments: (mean, var, count) absorbs one step's batch moments
+template <class S>
+SO100_LHD void running_moment_update(S& mean, S& var, S& count, S bm, S bv, S bc) {
+    const S d = bm - mean, tot = count + bc;
+    const S m_a = var*count, m_b = bv*bc;
+    mean = mean + d*bc/tot;
+    var = (m_a + m_b + d*d*count*bc/tot)/tot;
+    count = tot;
+}
+
+template <class S>
+SO100_LHD S reward_denominator(S var, S epsilon) { return lsqrt(var + epsilon); }
+
+template <class OUT, class S>
+SO100_LHD OUT reward_scale(S r, S denom, S clip) {
+    const S x = r/denom;
+    return (OUT)(x < -clip ? -clip : x > clip ? clip : x);
 }
 
 }  // namespace learn

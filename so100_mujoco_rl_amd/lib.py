@@ -124,9 +124,18 @@ class UpdateIO(C.Structure):
                 ("out_dev", C.c_void_p)]
 
 
+class RewardNormIO(C.Structure):
+    _fields_ = [("rollout_dev", C.c_void_p), ("state_dev", C.c_void_p), ("reward_dev", C.c_void_p), ("workspace_dev", C.c_void_p),
+                ("workspace_bytes", C.c_int64), ("clip_reward", C.c_double), ("epsilon", C.c_double)]
+
+
+REWARD_NORM_EPSILON, REWARD_NORM_CLIP = 1e-8, 10.0     # SB3 VecNormalize's epsilon and clip_reward
+REWARD_NORM_INIT = (0.0, 1.0, 1e-4)                    # mean, var, count of a fresh RunningMeanStd (so100_learner_reward_norm_init)
+
 LEARN_EXPORTS = ["so100_learner_num_params", "so100_learner_param_offset", "so100_learner_param_size", "so100_learner_create", "so100_learner_destroy",
                  "so100_learner_advantages", "so100_learner_minibatch_step", "so100_learner_minibatch_step_ex", "so100_learner_explained_variance",
-                 "so100_learner_shuffle", "so100_learner_update"]
+                 "so100_learner_shuffle", "so100_learner_update", "so100_learner_reward_norm_workspace", "so100_learner_reward_norm_init",
+                 "so100_learner_normalize_rewards", "so100_learner_advantages_r", "so100_learner_update_r"]
 LEARNER_STATS = ["policy_loss", "value_loss", "clip_fraction", "grad_norm"]          # stats_dev[4] of so100_learner_minibatch_step
 LEARNER_DIAG = LEARNER_STATS + ["approx_kl", "entropy_loss", "loss", "value_clip_fraction"]       # diag_dev[8] of so100_learner_minibatch_step_ex
 NORMALIZE_ADVANTAGE = {"batch": 0, "minibatch": 1}                                   # so100_ppo_terms.normalize_advantage
@@ -181,6 +190,11 @@ def load():
         L.so100_learner_explained_variance.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         L.so100_learner_shuffle.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_int64, C.c_void_p, C.c_void_p]
         L.so100_learner_update.argtypes = [C.c_void_p, C.POINTER(UpdateIO), C.c_void_p]
+        L.so100_learner_reward_norm_workspace.argtypes = [C.c_int32, C.c_int32]; L.so100_learner_reward_norm_workspace.restype = C.c_int64
+        L.so100_learner_reward_norm_init.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+        L.so100_learner_normalize_rewards.argtypes = [C.c_void_p, C.POINTER(RewardNormIO), C.c_int32, C.c_int32, C.c_void_p]
+        L.so100_learner_advantages_r.argtypes = [C.c_void_p, C.POINTER(AdvantagesIO), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+        L.so100_learner_update_r.argtypes = [C.c_void_p, C.POINTER(UpdateIO), C.POINTER(RewardNormIO), C.c_void_p]
         if L.so100_abi_version() != ABI_VERSION:
             raise So100Error("libso100sim.so ABI version mismatch")
         _lib = L
@@ -523,14 +537,47 @@ class So100Learner(_Handle):
         self.obs_dim = obs_dim
         self.num_params = self.L.so100_learner_num_params(obs_dim)
 
-    def advantages(self, rollout, last_obs, params, adv, ret, adv_stats, terminal_obs=None):
+    def advantages(self, rollout, last_obs, params, adv, ret, adv_stats, terminal_obs=None, rewards=None):
         """rollout: float32 [T, N, obs_dim+10] packed chunk (read only); terminal_obs: [T, N, obs_dim] or None (no TimeLimit bootstrap);
-        writes adv [T, N], ret [T, N], adv_stats [2] (mean, unbiased std)."""
+        writes adv [T, N], ret [T, N], adv_stats [2] (mean, unbiased std).  rewards: float32 [T, N] read in place of the chunk's reward
+        column (normalize_rewards' output; so100_learner_advantages_r), or None."""
         T, N = rollout.shape[0], rollout.shape[1]
         f, d, o = torch.float32, self.device, self.obs_dim
         io = AdvantagesIO(_ptr(rollout, f, (T, N, o + 10), d), _ptr(terminal_obs, f, (T, N, o), d), _ptr(last_obs, f, (N, o), d),
                           _ptr(params, f, (self.num_params,), d), _ptr(adv, f, (T, N), d), _ptr(ret, f, (T, N), d), _ptr(adv_stats, f, (2,), d))
-        _check(self.L.so100_learner_advantages(self.h, C.byref(io), T, N, self._stream()), "so100_learner_advantages")
+        if rewards is None:
+            _check(self.L.so100_learner_advantages(self.h, C.byref(io), T, N, self._stream()), "so100_learner_advantages")
+        else:
+            _check(self.L.so100_learner_advantages_r(self.h, C.byref(io), _ptr(rewards, f, (T, N), d), T, N, self._stream()), "so100_learner_advantages_r")
+
+    # ---- reward normalisation (SB3 VecNormalize's reward half; include/so100_learn.h "Reward normalisation") ------------------------------
+    @staticmethod
+    def reward_norm_workspace_bytes(T, N):
+        n = load().so100_learner_reward_norm_workspace(T, N)
+        if n < 0:
+            raise So100Error(f"so100_learner_reward_norm_workspace failed ({n}): {load().so100_last_error().decode()}")
+        return n
+
+    def reward_norm_init(self, state):
+        """state: float64 [3 + N] on the device <- mean 0, var 1, count 1e-4 and N zero running returns"""
+        N = state.numel() - 3
+        _check(self.L.so100_learner_reward_norm_init(self.h, _ptr(state, torch.float64, (3 + N,), self.device), N, self._stream()), "so100_learner_reward_norm_init")
+
+    def _reward_norm_io(self, rollout, state, rewards, workspace, clip_reward, epsilon):
+        T, N = rollout.shape[0], rollout.shape[1]
+        d = self.device
+        if workspace.dtype != torch.float64 or workspace.dim() != 1:
+            raise So100Error("the reward-normalisation workspace is a 1-d float64 tensor (reward_norm_workspace_bytes(T, N) // 8 elements)")
+        return RewardNormIO(_ptr(rollout, torch.float32, (T, N, self.obs_dim + 10), d), _ptr(state, torch.float64, (3 + N,), d),
+                            _ptr(rewards, torch.float32, (T, N), d), _ptr(workspace, torch.float64, (workspace.numel(),), d), workspace.numel() * 8,
+                            clip_reward, epsilon)
+
+    def normalize_rewards(self, rollout, state, rewards, workspace, clip_reward=REWARD_NORM_CLIP, epsilon=REWARD_NORM_EPSILON):
+        """rewards [T, N] float32 <- the chunk's reward column normalised as SB3's VecNormalize(norm_reward=True) does; state float64 [3 + N]
+        (mean, var, count, running returns) is advanced by the chunk's T steps; workspace: float64, reward_norm_workspace_bytes(T, N) // 8
+        elements.  The chunk is read only.  Three launches."""
+        io = self._reward_norm_io(rollout, state, rewards, workspace, clip_reward, epsilon)
+        _check(self.L.so100_learner_normalize_rewards(self.h, C.byref(io), rollout.shape[0], rollout.shape[1], self._stream()), "so100_learner_normalize_rewards")
 
     def _minibatch_io(self, rollout, idx, adv, ret, adv_stats, params, adam_m, adam_v, adam_step, stats, grads):
         """the so100_minibatch_io of both steps.  idx: an int64 [mb] tensor of flat indices t*N + n in any order, or an int mb for rows 0..mb-1"""
@@ -580,13 +627,14 @@ class So100Learner(_Handle):
                                             self._stream()), "so100_learner_shuffle")
 
     def update(self, rollout, last_obs, params, adam_m, adam_v, adv, ret, adv_stats, perm, out, *, epochs, mb, adam_step0, shuffle_seed, shuffle_epoch0=0,
-               terminal_obs=None, terms=None, update_state=None):
+               terminal_obs=None, terms=None, update_state=None, reward_norm=None):
         """One whole PPO update enqueued by one call (so100_learner_update): the advantages, the explained variance, then `epochs` epochs of
         {device shuffle, ceil(T*N/mb) minibatch steps numbered from adam_step0 + 1}.  adv / ret [T, N], adv_stats [2], perm int64 [T*N] and
         out float32 [UPDATE_OUT] are the caller's and are written: out[0:8] the last step's statistics (terms None: the plain step's four) or
         diagnostics, out[8] the explained variance, out[9:15] log_std as the last step read it.  terms: None for the plain step, or a dict of
         minibatch_step_ex's options (ent_coef, clip_range_vf, normalize_advantage, target_kl, lr); update_state: int32 [2], zeroed by the call,
-        required with target_kl."""
+        required with target_kl.  reward_norm: None, or a dict of normalize_rewards' arguments (state, rewards, workspace and optionally
+        clip_reward, epsilon): the normalisation is enqueued first and the advantages read its output (so100_learner_update_r)."""
         T, N = rollout.shape[0], rollout.shape[1]
         f, d, o, P = torch.float32, self.device, self.obs_dim, self.num_params
         t = None
@@ -597,4 +645,9 @@ class So100Learner(_Handle):
                       _ptr(adv_stats, f, (2,), d), _ptr(perm, torch.int64, (T * N,), d), epochs, mb, adam_step0, int(shuffle_epoch0) & 0xFFFFFFFF,
                       int(shuffle_seed) & 0xFFFFFFFFFFFFFFFF, C.pointer(t) if t is not None else None, _ptr(update_state, torch.int32, (2,), d),
                       _ptr(out, f, (UPDATE_OUT,), d))
-        _check(self.L.so100_learner_update(self.h, C.byref(io), self._stream()), "so100_learner_update")
+        if reward_norm is None:
+            _check(self.L.so100_learner_update(self.h, C.byref(io), self._stream()), "so100_learner_update")
+        else:
+            nio = self._reward_norm_io(rollout, reward_norm["state"], reward_norm["rewards"], reward_norm["workspace"],
+                                       reward_norm.get("clip_reward", REWARD_NORM_CLIP), reward_norm.get("epsilon", REWARD_NORM_EPSILON))
+            _check(self.L.so100_learner_update_r(self.h, C.byref(io), C.byref(nio), self._stream()), "so100_learner_update_r")

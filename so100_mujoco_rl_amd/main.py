@@ -3,6 +3,7 @@
     python -m so100_mujoco_rl_amd.main -a PPO [-m MODEL] train  -e Env01-v1 [--envs 4096] [--iters N] [--learner torch|fused] [--shuffle torch|device]
                                                                [--ent-coef C] [--clip-range-vf C] [--target-kl K]
                                                                [--normalize-advantage batch|minibatch] [--lr-schedule constant|linear]
+                                                               [--normalize-reward]
     python -m so100_mujoco_rl_amd.main -a PPO [-m MODEL] test   -e Env01-v1 [--show-io] [--show-i]
     python -m so100_mujoco_rl_amd.main -a PPO [-m MODEL] record -e Env01-v1 [--steps 3000] [--video/--no-video]
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 -m so100_mujoco_rl_amd.main -a PPO train -e Env01-v1     # 8 x 4096 envs
@@ -89,8 +90,10 @@ def cli(ctx, algorithm, model):
 @click.option("--lr-schedule", default=None, type=click.Choice(["constant", "linear"]), help="learning rate 3e-4 (constant, the default) or 3e-4 x remaining progress (linear; needs --iters)")
 @click.option("--shuffle", default="torch", type=click.Choice(["torch", "device"]),
               help="minibatch permutations of --learner fused: torch.randperm (torch) or the library's, a function of seed and epoch; the whole update is then one call (device)")
+@click.option("--normalize-reward", is_flag=True, default=False,
+              help="train on rewards divided by the running std of the envs' discounted returns (SB3 VecNormalize(norm_reward=True)); the state is saved beside each model")
 @click.pass_context
-def train(ctx, environment, envs, iters, seed, learner_kind, ent_coef, clip_range_vf, target_kl, normalize_advantage, lr_schedule, shuffle):
+def train(ctx, environment, envs, iters, seed, learner_kind, ent_coef, clip_range_vf, target_kl, normalize_advantage, lr_schedule, shuffle, normalize_reward):
     algorithm = ctx.obj["ALGORITHM_NAME"]
     if shuffle == "device" and learner_kind != "fused":
         raise RuntimeError("--shuffle device is the fused learner's on-device shuffle: it needs --learner fused")
@@ -103,13 +106,19 @@ def train(ctx, environment, envs, iters, seed, learner_kind, ent_coef, clip_rang
         terms["normalize_advantage"] = "minibatch"
     if lr_schedule == "linear":
         terms["lr_schedule"] = lambda progress: PPO_LR * progress
+    if normalize_reward:
+        terms["normalize_reward"] = True
     if terms and algorithm != "PPO":
-        raise RuntimeError("--ent-coef, --clip-range-vf, --target-kl, --normalize-advantage and --lr-schedule are PPO's options")
+        raise RuntimeError("--ent-coef, --clip-range-vf, --target-kl, --normalize-advantage, --lr-schedule and --normalize-reward are PPO's options")
     kind = kind_from_id(environment)
     # Multi-GPU (one process per GPU under torchrun): rank r steps global envs [r*envs, (r+1)*envs); once per rollout chunk the
     # packed rollout goes to rank 0 over RCCL (the path's ONE collective), rank 0 learns, the policy is broadcast back.
     world = int(os.environ.get("WORLD_SIZE", "1")); rank = int(os.environ.get("RANK", "0")); local = int(os.environ.get("LOCAL_RANK", "0"))
     distributed = world > 1 or os.environ.get("SO100_FORCE_DIST") == "1"      # SO100_FORCE_DIST: the same code path on a one-GPU box
+    if normalize_reward and distributed:
+        # a gathered chunk is bootstrapped by each rank before the gather, which would put gamma * V under the normalisation
+        raise RuntimeError("--normalize-reward runs on one GPU: with WORLD_SIZE > 1 the TimeLimit bootstrap is applied before the gather, ahead of the "
+                           "normalisation (the multi-GPU order cannot be tested on one card, so it is not offered)")
     if distributed:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1"); os.environ.setdefault("MASTER_PORT", "29544")
         os.environ.setdefault("RANK", "0"); os.environ.setdefault("WORLD_SIZE", "1")
@@ -132,6 +141,9 @@ def train(ctx, environment, envs, iters, seed, learner_kind, ent_coef, clip_rang
         cls = getattr(stable_baselines3, algorithm)
         model_file = ctx.obj["MODEL_PATH"]
         sb3_terms = {k: v for k, v in terms.items() if k in ("ent_coef", "clip_range_vf", "target_kl")}
+        if normalize_reward:
+            from stable_baselines3.common.vec_env import VecNormalize
+            env = VecNormalize(env, norm_obs=False, norm_reward=True)
         if "normalize_advantage" in terms:
             sb3_terms["normalize_advantage"] = True          # "minibatch" is SB3's own normalisation (and its default); it has no per-chunk one
         if "lr_schedule" in terms:
@@ -153,13 +165,23 @@ def train(ctx, environment, envs, iters, seed, learner_kind, ent_coef, clip_rang
             raise RuntimeError(f"Model file {ctx.obj['MODEL_PATH']} does not exist")
         learner.net.load_state_dict(torch.load(ctx.obj["MODEL_PATH"], map_location=env.device, weights_only=True))
         logger.info(f"Model: starting with {ctx.obj['MODEL_PATH']}")
+        if normalize_reward:
+            side = _reward_norm_path(ctx.obj["MODEL_PATH"])
+            if os.path.isfile(side):
+                learner.load_reward_norm_state(torch.load(side, map_location="cpu", weights_only=True))
+                logger.info(f"Reward normalisation: reloaded the running state from {side}")
+            else:
+                logger.info(f"Reward normalisation: no saved state at {side}, starting from a fresh one")
     else:
         logger.info("Model: starting with new model")
+    if normalize_reward:
+        logger.info(f"Reward normalisation: on (running std of the discounted returns, clip {learner.clip_reward:g}); evaluation and reward/step stay in the env's scale")
     if distributed:
         broadcast_policy(list(learner.net.state_dict().values()), src=0)          # every rank starts from rank 0's weights
     # fused on one GPU: the advantage kernel applies the TimeLimit bootstrap (the chunk keeps the env's rewards); a gathered chunk is bootstrapped
     # by each rank before the gather, as with the torch learner
-    col = RolloutCollector(env, learner.net.state_dict(), T=64, defer_bootstrap=learner_kind == "fused" and not distributed)
+    # --normalize-reward, either learner: the bootstrap must follow the normalisation, so it is deferred to the learner as well
+    col = RolloutCollector(env, learner.net.state_dict(), T=64, defer_bootstrap=(learner_kind == "fused" or normalize_reward) and not distributed)
     threshold = K.REWARD_THRESHOLD[kind]                     # StopTrainingOnRewardThreshold (ref: main.py:211; the registered threshold of the env id)
     steps, t0, it = 0, time.time(), 0
     ep_sum = ep_cnt = 0.0
@@ -171,7 +193,7 @@ def train(ctx, environment, envs, iters, seed, learner_kind, ent_coef, clip_rang
         # evaluates every 20 000 timesteps of ONE env; here an update is 64 x envs timesteps, so an evaluation every EVAL_EVERY updates.
         eval_env = So100VecEnv(environment, N_EVAL_EPISODES, device=env.device, flags=F_REFERENCE, seed=seed + 1000)
         eval_col = RolloutCollector(eval_env, learner.net.state_dict(), T=64, bootstrap_truncated=False)
-        eval_cb = EvalCallback(lambda: _evaluate(eval_env, eval_col, learner), lambda: torch.save(learner.net.state_dict(), os.path.join(save_dir, "best_model.pt")),
+        eval_cb = EvalCallback(lambda: _evaluate(eval_env, eval_col, learner), lambda: _save_model(learner, os.path.join(save_dir, "best_model.pt")),
                                EVAL_EVERY, on_new_best=StopTrainingOnRewardThreshold(threshold), after_eval=StopTrainingOnNoModelImprovement(5, 10000), log=logger.info)
     while True:
         b = col.collect(gather_dst=0 if distributed else None)
@@ -193,11 +215,11 @@ def train(ctx, environment, envs, iters, seed, learner_kind, ent_coef, clip_rang
             if terms and (it % 10 == 0 or (iters and it >= iters)):
                 logger.info(f"iter {it:5d}  approx_kl {stats['approx_kl']:.5f}  entropy_loss {stats['entropy_loss']:.4f}  loss {stats['loss']:.4f}  "
                             f"explained_variance {stats['explained_variance']:.4f}  std {stats['std']:.4f}  n_updates {stats['n_updates']}"
-                            + ("  (early stop)" if stats["early_stop"] else ""))
+                            + (f"  return_std {stats['return_var'] ** 0.5:.4f}" if normalize_reward else "") + ("  (early stop)" if stats["early_stop"] else ""))
             if not eval_cb.step():
                 logger.info(f"Stopping training: best evaluation reward {eval_cb.best_mean_reward:.1f} (threshold {threshold})"); stop.fill_(1.0)
             if it % 40 == 0:                                 # CheckpointCallback (ref: main.py:227-232)
-                torch.save(learner.net.state_dict(), os.path.join(save_dir, f"{environment}_{algorithm}_cp__{steps}_steps.pt"))
+                _save_model(learner, os.path.join(save_dir, f"{environment}_{algorithm}_cp__{steps}_steps.pt"))
             if iters and it >= iters:
                 stop.fill_(1.0)
         if distributed:
@@ -208,10 +230,21 @@ def train(ctx, environment, envs, iters, seed, learner_kind, ent_coef, clip_rang
     if lead and eval_cb.n_evals == 0:                        # a short run (--iters): one evaluation at the end, so that best_model exists
         eval_cb.eval_every = 1; eval_cb.step()
     if lead:
-        torch.save(learner.net.state_dict(), os.path.join(save_dir, "last_model.pt"))
+        _save_model(learner, os.path.join(save_dir, "last_model.pt"))
         logger.info(f"done: {steps/1e6:.1f} M timesteps in {time.time()-t0:.1f} s; best evaluation reward {eval_cb.best_mean_reward:.1f} ({eval_cb.n_evals} evaluations); models in {save_dir}")
     if distributed:
         dist.barrier(); dist.destroy_process_group()
+
+
+def _reward_norm_path(model_path):
+    """<model>.reward_norm.pt beside <model>.pt: the running state of --normalize-reward (the model file stays a plain state_dict)"""
+    return os.path.splitext(model_path)[0] + ".reward_norm.pt"
+
+
+def _save_model(learner, path):
+    torch.save(learner.net.state_dict(), path)
+    if getattr(learner, "normalize_reward", False):
+        torch.save(learner.reward_norm_state(), _reward_norm_path(path))
 
 
 PPO_LR = 3e-4                                                # the learners' default learning rate: where --lr-schedule linear starts
@@ -219,7 +252,8 @@ PPO_LR = 3e-4                                                # the learners' def
 
 def make_ppo_learner(kind, obs_dim, device, seed, **terms):
     """the built-in PPO learner `train --learner` names: "torch" (ppo.PPO, the default) or "fused" (ppo.FusedPPO, HIP kernels); terms: SB3's
-    remaining options (ent_coef, clip_range_vf, target_kl, normalize_advantage, lr_schedule), the same for both, and the fused learner's shuffle"""
+    remaining options (ent_coef, clip_range_vf, target_kl, normalize_advantage, lr_schedule) and normalize_reward, the same for both, and the
+    fused learner's shuffle"""
     if kind == "torch":
         return PPO(obs_dim, device, lr=PPO_LR, seed=seed, **terms)
     if kind != "fused":

@@ -10,7 +10,10 @@ The network's state_dict keys equal SB3's ActorCriticPolicy keys, so checkpoints
 interoperate with an SB3 policy.
 FusedPPO is the same learner on the library's own kernels (include/so100_learn.h): same constructor, same update(b), same state_dict.
 Both take SB3's remaining options -- ent_coef, clip_range_vf, per-minibatch advantage normalisation, target_kl, a learning-rate schedule --
-all off by default (then the loss is the one above, to the bit), and return SB3's per-update diagnostics."""
+all off by default (then the loss is the one above, to the bit), and return SB3's per-update diagnostics.
+normalize_reward=True is the reward half of SB3's VecNormalize(norm_reward=True): the rewards an update trains on are divided by the running
+standard deviation of the envs' discounted returns (include/so100_learn.h "Reward normalisation" is the specification); the state carries
+over from update to update and is saved and restored with reward_norm_state() / load_reward_norm_state()."""
 import math
 import os
 
@@ -59,14 +62,51 @@ def _set_terms(learner, ent_coef, clip_range_vf, normalize_advantage, target_kl,
     learner.ent_coef, learner.clip_range_vf, learner.normalize_advantage, learner.target_kl, learner.lr_schedule = ent_coef, clip_range_vf, normalize_advantage, target_kl, lr_schedule
 
 
+REWARD_NORM_EPSILON = 1e-8                                # VecNormalize's epsilon
+
+
+def _set_reward_norm(learner, normalize_reward, clip_reward):
+    """checks the reward-normalisation options and stores them on a PPO / FusedPPO"""
+    if not clip_reward > 0:
+        raise ValueError(f"clip_reward must be > 0, got {clip_reward}")
+    learner.normalize_reward, learner.clip_reward = bool(normalize_reward), float(clip_reward)
+    learner._rn = None                                    # the running state, made at the first update (it is sized by the envs)
+
+
+def _fresh_reward_norm(n, device):
+    """[3 + n] float64: mean 0, var 1, count 1e-4 (a fresh RunningMeanStd), then n zero running returns"""
+    st = torch.zeros(3 + n, dtype=torch.float64, device=device)
+    st[1] = 1.0; st[2] = 1e-4
+    return st
+
+
+def _reward_norm_state_dict(st):
+    st = _fresh_reward_norm(0, "cpu") if st is None else st.detach().cpu()
+    return {"mean": st[0].clone(), "var": st[1].clone(), "count": st[2].clone(), "returns": st[3:].clone()}
+
+
+def _reward_norm_from_state_dict(sd, device):
+    """the [3 + N] state of a saved dict; None when it was saved before the first update (no env count yet)"""
+    ret = torch.as_tensor(sd["returns"], dtype=torch.float64).reshape(-1)
+    head = torch.stack([torch.as_tensor(sd[k], dtype=torch.float64).reshape(()) for k in ("mean", "var", "count")])
+    fresh = ret.numel() == 0 and head.tolist() == _fresh_reward_norm(0, "cpu").tolist()
+    return None if fresh else torch.cat([head, ret]).to(device)
+
+
+def _done_code(b):
+    """the chunk's done code as a tensor: 0 running, 1 terminated, 2 TimeLimit-truncated only"""
+    return b["dones"] * (1.0 + b["truncated"].to(b["dones"].dtype)) if "truncated" in b else b["dones"]
+
+
 class PPO:
     """ent_coef, clip_range_vf, target_kl as in stable_baselines3.PPO; normalize_advantage "batch" normalises over the whole chunk (this
     driver's default), "minibatch" per minibatch as SB3 does; lr_schedule(progress_remaining) as in SB3, evaluated once per update."""
 
     def __init__(self, obs_dim, device, lr=3e-4, gamma=0.99, gae_lambda=0.95, clip=0.2, epochs=4, minibatch=32768,
                  vf_coef=0.5, max_grad_norm=0.5, seed=0, use_graph=False, ent_coef=0.0, clip_range_vf=None, normalize_advantage="batch",
-                 target_kl=None, lr_schedule=None):
+                 target_kl=None, lr_schedule=None, normalize_reward=False, clip_reward=10.0):
         _set_terms(self, ent_coef, clip_range_vf, normalize_advantage, target_kl, lr_schedule)
+        _set_reward_norm(self, normalize_reward, clip_reward)
         torch.manual_seed(seed)
         self.net = ActorCritic(obs_dim).to(device)
         on_gpu = torch.device(device).type == "cuda"
@@ -132,6 +172,42 @@ class PPO:
         nn.utils.clip_grad_norm_(net.parameters(), self.max_grad_norm); self.opt.step()
         return True
 
+    # ---- reward normalisation: include/so100_learn.h's arithmetic in torch fp64 on this learner's device ----------------------------------
+    def reward_norm_state(self):
+        """{"mean", "var", "count": 0-d float64, "returns": float64 [N]} on the CPU (returns is empty before the first update)"""
+        return _reward_norm_state_dict(self._rn)
+
+    def load_reward_norm_state(self, sd):
+        self._rn = _reward_norm_from_state_dict(sd, self.device)
+
+    @torch.no_grad()
+    def _normalized_rewards(self, rewards, ended):
+        """rewards [T, N] float32 and ended [T, N] bool (the done code != 0) -> the normalised rewards, float32; advances self._rn"""
+        T, N = rewards.shape
+        if self._rn is None:
+            self._rn = _fresh_reward_norm(N, self.device)
+        if self._rn.numel() != 3 + N:
+            raise ValueError(f"the reward-normalisation state holds {self._rn.numel() - 3} envs, the rollout has {N}")
+        gamma = torch.tensor(self.gamma, dtype=torch.float32).double().item()        # the learner's gamma is a float in the library: widened from it
+        r = rewards.double()
+        R = self._rn[3:].clone()
+        Rs = torch.empty(T, N, dtype=torch.float64, device=rewards.device)
+        for t in range(T):
+            R = R * gamma + r[t]
+            Rs[t] = R
+            R = torch.where(ended[t], torch.zeros_like(R), R)
+        bms, bvs = Rs.mean(1).tolist(), Rs.var(1, unbiased=False).tolist()
+        mean, var, count = self._rn[:3].tolist()
+        denom = []
+        for bm, bv in zip(bms, bvs):                         # RunningMeanStd.update_from_moments, one vector step at a time
+            d, tot = bm - mean, count + N
+            mean, var, count = mean + d * N / tot, (var * count + bv * N + d * d * count * N / tot) / tot, tot
+            denom.append(math.sqrt(var + REWARD_NORM_EPSILON))
+        self._rn[:3] = torch.tensor([mean, var, count], dtype=torch.float64)
+        self._rn[3:] = R
+        den = torch.tensor(denom, dtype=torch.float64, device=rewards.device).unsqueeze(1)
+        return (r / den).clamp(-self.clip_reward, self.clip_reward).float()
+
     def _alloc(self, b):
         dev = self.device
         self._s = {k: torch.empty(b[k].shape, dtype=torch.float32, device=dev) for k in ("obs", "actions", "rewards", "dones", "values", "log_probs", "last_obs")}
@@ -144,7 +220,10 @@ class PPO:
     def update(self, b, progress_remaining=1.0):
         """b: RolloutCollector.collect() output ([T, N, ...] device tensors + last_obs).  progress_remaining: 1 at the start of training, 0 at
         its end; the argument of lr_schedule.  Returns value_loss, approx_kl, entropy_loss and loss of the last minibatch evaluated (the one
-        that stopped the update, if target_kl did), explained_variance of the chunk, std after the update, n_updates (steps applied)."""
+        that stopped the update, if target_kl did), explained_variance of the chunk, std after the update, n_updates (steps applied); with
+        normalize_reward also return_var and return_count, the running variance of the discounted returns and its sample count.
+        With b["terminal_obs"] (RolloutCollector(defer_bootstrap=True)) the TimeLimit bootstrap is applied here, after the normalisation;
+        mean_reward stays the env's raw mean."""
         if self.lr_schedule is not None:
             for g in self.opt.param_groups:
                 g["lr"] = float(self.lr_schedule(progress_remaining))
@@ -153,6 +232,12 @@ class PPO:
         S = self._s
         for k in ("obs", "actions", "rewards", "dones", "values", "log_probs", "last_obs"):
             S[k].copy_(b[k])
+        if self.normalize_reward:
+            S["rewards"].copy_(self._normalized_rewards(S["rewards"], S["dones"] != 0))
+        if "terminal_obs" in b:                               # a deferred TimeLimit bootstrap (RolloutCollector(defer_bootstrap=True)): after the normalisation
+            from .rollout import bootstrap_truncated
+            with torch.no_grad():
+                bootstrap_truncated(S["rewards"], _done_code(b), b["terminal_obs"], self.net.value, self.gamma)
         n = S["ret"].numel(); mb = S["idx"].numel()
         self._gae()
         applied, stopped = 0, False
@@ -171,8 +256,11 @@ class PPO:
         # mean_reward = the ENV's mean reward per step (the collector takes it before its TimeLimit bootstrap adds gamma * V to the
         # truncated steps); S["rewards"] holds the bootstrapped rewards the advantages are computed from
         raw = b.get("raw_reward_mean")
+        if raw is None and (self.normalize_reward or "terminal_obs" in b):       # S["rewards"] no longer holds the env's rewards: the chunk does
+            raw = b["rewards"].mean()
         d = S["diag"].tolist()
-        return {"value_loss": S["vl"].item(), "mean_reward": (raw if raw is not None else S["rewards"].mean()).item(),
+        rn = {"return_var": self._rn[1].item(), "return_count": self._rn[2].item()} if self.normalize_reward else {}
+        return {**rn, "value_loss": S["vl"].item(), "mean_reward": (raw if raw is not None else S["rewards"].mean()).item(),
                 "mean_bootstrapped_reward": S["rewards"].mean().item(), "approx_kl": d[2], "entropy_loss": d[3], "loss": d[4],
                 "explained_variance": S["ev"].item(), "std": self.net.log_std.detach().exp().mean().item(), "n_updates": applied, "early_stop": stopped}
 
@@ -186,10 +274,11 @@ class FusedPPO:
 
     def __init__(self, obs_dim, device, lr=3e-4, gamma=0.99, gae_lambda=0.95, clip=0.2, epochs=4, minibatch=32768,
                  vf_coef=0.5, max_grad_norm=0.5, seed=0, use_graph=False, ent_coef=0.0, clip_range_vf=None, normalize_advantage="batch",
-                 target_kl=None, lr_schedule=None, shuffle="torch"):
+                 target_kl=None, lr_schedule=None, shuffle="torch", normalize_reward=False, clip_reward=10.0):
         from . import lib
         del use_graph
         _set_terms(self, ent_coef, clip_range_vf, normalize_advantage, target_kl, lr_schedule)
+        _set_reward_norm(self, normalize_reward, clip_reward)
         if shuffle not in ("torch", "device"):
             raise ValueError(f"shuffle must be 'torch' or 'device', got {shuffle!r}")
         # "device": the whole update is one so100_learner_update call and the minibatches are a function of (seed, shuffle_epoch) alone --
@@ -216,6 +305,7 @@ class FusedPPO:
         self._hyper = dict(gamma=gamma, gae_lambda=gae_lambda, clip_range=clip, vf_coef=vf_coef, max_grad_norm=max_grad_norm, lr=lr, adam_eps=1e-5)
         self._learner = None
         self._shape = None
+        self._rn_shape = None
         self._side = None
 
     def _handle(self):
@@ -225,6 +315,27 @@ class FusedPPO:
                 raise lib.So100Error(f"FusedPPO runs on a HIP device, not on {self.device}: there is no CPU fallback (use PPO)")
             self._learner = lib.So100Learner(self.obs_dim, self.device, max_minibatch=self.mb, **self._hyper)
         return self._learner
+
+    def reward_norm_state(self):
+        """PPO.reward_norm_state: the device state [mean, var, count, returns] as a dict of CPU tensors"""
+        return _reward_norm_state_dict(self._rn)
+
+    def load_reward_norm_state(self, sd):
+        self._rn = _reward_norm_from_state_dict(sd, self.device)
+
+    def _reward_norm(self, L, T, N):
+        """the arguments of the normalisation kernels for a [T, N] chunk: the running state (made at the first update), the dense rewards they
+        write and their workspace"""
+        if self._rn is None:
+            self._rn = torch.empty(3 + N, dtype=torch.float64, device=self.device)
+            L.reward_norm_init(self._rn)
+        if self._rn.numel() != 3 + N:
+            raise ValueError(f"the reward-normalisation state holds {self._rn.numel() - 3} envs, the rollout has {N}")
+        if self._rn_shape != (T, N):
+            self._rn_rewards = torch.zeros(T, N, device=self.device)
+            self._rn_ws = torch.zeros(L.reward_norm_workspace_bytes(T, N) // 8, dtype=torch.float64, device=self.device)
+            self._rn_shape = (T, N)
+        return dict(state=self._rn, rewards=self._rn_rewards, workspace=self._rn_ws, clip_reward=self.clip_reward, epsilon=REWARD_NORM_EPSILON)
 
     def _packed(self, b):
         """the [T, N, obs_dim+10] chunk: b["packed"] as RolloutCollector.collect() hands it over (read in place, no copy); a dict without it
@@ -245,6 +356,8 @@ class FusedPPO:
         """b: RolloutCollector.collect() output.  With b["terminal_obs"] (RolloutCollector(defer_bootstrap=True)) the TimeLimit bootstrap is
         applied by the advantage kernel; otherwise the rewards are taken as they are (the collector's eager bootstrap has been added).
         perms: one int64 permutation of range(T*N) per epoch (tests); default torch.randperm, drawn as PPO.update draws them.
+        With normalize_reward the chunk's rewards are normalised by the library's kernels first (the chunk itself stays as it is) and the
+        advantages read the normalised rewards; the bootstrap is added to those.
         Returns PPO.update's keys plus policy_loss, clip_fraction and grad_norm of the last minibatch.  mean_bootstrapped_reward is the
         mean of the chunk's reward column: with a deferred bootstrap that column keeps the env's own rewards (the bootstrapped ones are
         never materialised), so it then equals the raw mean.
@@ -273,9 +386,13 @@ class FusedPPO:
             self._perm = torch.zeros(T * N, dtype=torch.int64, device=dev) if self.shuffle == "device" else None
             self._shape = (T, N)
         tobs = b.get("terminal_obs")
+        rn = self._reward_norm(L, T, N) if self.normalize_reward else None
         if self.shuffle == "device":
-            return self._update_on_device(L, b, buf, tobs, progress_remaining)
-        L.advantages(buf, b["last_obs"].contiguous(), self.params, self._adv, self._ret, self._adv_stats, terminal_obs=tobs)
+            return self._update_on_device(L, b, buf, tobs, progress_remaining, rn)
+        if rn is not None:
+            L.normalize_rewards(buf, rn["state"], rn["rewards"], rn["workspace"], clip_reward=rn["clip_reward"], epsilon=rn["epsilon"])
+        L.advantages(buf, b["last_obs"].contiguous(), self.params, self._adv, self._ret, self._adv_stats, terminal_obs=tobs,
+                     rewards=None if rn is None else rn["rewards"])
         cur = torch.cuda.current_stream(self.device)
         if self._side is None:
             self._side = torch.cuda.Stream(device=self.device)
@@ -306,7 +423,7 @@ class FusedPPO:
         st = self._read_out(b, buf, cur)                                 # the update's only synchronisation
         return self._results(st, first_step, last)
 
-    def _update_on_device(self, L, b, buf, tobs, progress_remaining):
+    def _update_on_device(self, L, b, buf, tobs, progress_remaining, rn):
         """shuffle="device": everything update() enqueues above, the permutations included, by one so100_learner_update call on the current stream"""
         n = buf.shape[0] * buf.shape[1]; mb = min(self.mb, n)
         first_step = self.adam_step
@@ -317,7 +434,7 @@ class FusedPPO:
                          lr=None if self.lr_schedule is None else float(self.lr_schedule(progress_remaining)))
         L.update(buf, b["last_obs"].contiguous(), self.params, self.adam_m, self.adam_v, self._adv, self._ret, self._adv_stats, self._perm, self._out[0:15],
                  epochs=self.epochs, mb=mb, adam_step0=first_step, shuffle_seed=self.shuffle_seed, shuffle_epoch0=self.shuffle_epoch, terminal_obs=tobs,
-                 terms=terms, update_state=self._state if self._extended else None)
+                 terms=terms, update_state=self._state if self._extended else None, reward_norm=rn)
         self.shuffle_epoch += self.epochs
         if self._extended:
             self._out[23:25].copy_(self._state)
@@ -334,6 +451,9 @@ class FusedPPO:
             ent_loss = -(math.fsum(st[9:15]) + 6 * ENTROPY_CONST)
             extra = {"approx_kl": float("nan"), "entropy_loss": ent_loss, "loss": st[0] + self.vf_coef * st[1], "n_updates": applied, "early_stop": False}
         self.adam_step = first_step + applied
+        if self.normalize_reward:                                 # the running moments in full precision: a second small read, after the one that synchronised
+            _, var, count = self._rn[:3].tolist()
+            extra = {**extra, "return_var": var, "return_count": count}
         # mean_bootstrapped_reward: the mean of the chunk's reward column -- with a deferred bootstrap that column holds the env's own rewards
         return {"value_loss": st[1], "mean_reward": st[22], "mean_bootstrapped_reward": st[21],
                 "policy_loss": st[0], "clip_fraction": st[2], "grad_norm": st[3], "explained_variance": st[8], "std": math.fsum(math.exp(x) for x in st[15:21]) / 6, **extra}

@@ -21,6 +21,12 @@ Every GPU step runs in a child process under its own time limit; the first one t
 same chunk through the C ABI: the old step, the extended step with every term off, with entropy bonus and value clipping, with per-minibatch
 normalisation as well (one more launch: the difference is the cost of the statistics launch), and a skipped step (the update stopped by
 target_kl: every kernel returns at once).  Timed in alternation, `--rounds` times each, HIP events around 200 steps.
+
+    python tools/kbench_learner.py --normalize-reward [--out profiles/learner_rewnorm_kbench.json] [--commit LABEL]
+
+--normalize-reward: FusedPPO.update with and without normalize_reward, in both of its paths (the steps enqueued from Python; the one-call update),
+the four in alternation on the chunk of --part update, and the normalisation pass alone (so100_learner_normalize_rewards, three launches) per
+call.  The added time per update is held against one minibatch step of the same run (the update without the option / 32).
 """
 import argparse
 import json
@@ -116,6 +122,58 @@ def part_update_shuffle(obs_dim, rounds, reps, warmup):
     print("KBENCH " + json.dumps(res), flush=True)
 
 
+def part_rewnorm(obs_dim, rounds, reps, warmup):
+    """--part rewnorm: FusedPPO.update off / on in both paths, in alternation, and so100_learner_normalize_rewards alone"""
+    import torch
+    from so100_mujoco_rl_amd.ppo import FusedPPO
+    from so100_mujoco_rl_amd.rollout import RolloutChunk
+    dev = torch.device("cuda", 0)
+    g = torch.Generator(device=dev); g.manual_seed(obs_dim)
+    o = obs_dim
+    learners = {f"{path}_{'on' if on else 'off'}": FusedPPO(o, dev, seed=0, shuffle=shuffle, normalize_reward=on)
+                for path, shuffle in (("three_call", "torch"), ("one_call", "device")) for on in (False, True)}
+    c = RolloutChunk(T, N, o, dev)
+    c.buf.copy_(torch.randn(c.buf.shape, device=dev, generator=g))
+    with torch.no_grad():
+        v, lp = learners["three_call_off"].net.evaluate(c.buf[..., :o].reshape(-1, o), c.buf[..., o:o + 6].reshape(-1, 6))
+        c.buf[..., o + 6] = 1.5 + 0.5 * c.buf[..., o + 6]         # the tasks pay 1-2 per step
+        c.buf[..., o + 8] = v.reshape(T, N); c.buf[..., o + 9] = lp.reshape(T, N)
+        c.buf[..., o + 7] = (torch.rand(T, N, device=dev, generator=g) < 1e-3).float() * 2.0
+    b = c.unpack(); b["last_obs"] = torch.randn(N, o, device=dev, generator=g); b["packed"] = c.buf
+    res = {"obs_dim": o, "T": T, "N": N, "epochs": EPOCHS, "minibatch": MB, "samples": T * N, "card": torch.cuda.get_device_name(0)}
+
+    def window(fn, count):
+        e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize(); e0.record()
+        for _ in range(count):
+            fn()
+        e1.record(); torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / count
+
+    L = learners["three_call_on"]._handle()
+    rn = learners["three_call_on"]._reward_norm(L, T, N)
+    alone = lambda: L.normalize_rewards(c.buf, rn["state"], rn["rewards"], rn["workspace"])
+    for learner in learners.values():
+        for _ in range(warmup):
+            learner.update(b)
+    window(alone, 20)
+    ms = {k: [] for k in learners}; us_alone = []
+    for _ in range(rounds):
+        for name, learner in learners.items():
+            ms[name].append(round(window(lambda: learner.update(b), reps), 4))
+        us_alone.append(round(window(alone, 200) * 1e3, 2))
+    med = lambda x: sorted(x)[len(x) // 2]
+    for name in ms:
+        res[name] = {"ms_per_update_rounds": ms[name], "ms_per_update": med(ms[name]), "updates_per_round": reps}
+    res["normalize_rewards_alone"] = {"us_per_call_rounds": us_alone, "us_per_call": med(us_alone), "calls_per_window": 200, "launches": 3}
+    for path in ("three_call", "one_call"):
+        off, on = res[path + "_off"]["ms_per_update"], res[path + "_on"]["ms_per_update"]
+        res[path + "_added_us_per_update"] = round((on - off) * 1e3, 1)
+        res[path + "_one_minibatch_step_us"] = round(off * 1e3 / (EPOCHS * (T * N // MB)), 1)
+    res["return_std"] = float(rn["state"][1].sqrt().item())
+    print("KBENCH " + json.dumps(res), flush=True)
+
+
 def part_terms(obs_dim, rounds, reps=200, warmup=20):
     import torch
     from so100_mujoco_rl_amd.lib import So100Learner
@@ -200,7 +258,8 @@ def child(args, limit):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--part", choices=("all", "update", "train", "terms"), default="all")
+    ap.add_argument("--part", choices=("all", "update", "train", "terms", "rewnorm"), default="all")
+    ap.add_argument("--normalize-reward", action="store_true", help="time FusedPPO.update with and without normalize_reward; writes profiles/learner_rewnorm_kbench.json")
     ap.add_argument("--terms", action="store_true", help="time the extended step with all terms on against the old one; writes profiles/learner_terms_kbench.json")
     ap.add_argument("--obs-dim", type=int, default=15); ap.add_argument("--learner", default="fused")
     ap.add_argument("--shuffle", choices=("torch", "device"), default="torch", help="--part update: device times FusedPPO(shuffle='device') against FusedPPO's default path")
@@ -213,6 +272,17 @@ def main():
         return part_train(a.learner, a.iters)
     if a.part == "terms":
         return part_terms(a.obs_dim, a.rounds)
+    if a.part == "rewnorm":
+        return part_rewnorm(a.obs_dim, a.rounds, 100, a.warmup)
+    if a.normalize_reward:
+        doc = {"what": "FusedPPO.update (4 epochs x 8 minibatches of 32768 over 64 x 4096 samples) with and without normalize_reward, both paths, and the pass alone",
+               "commit": a.commit, "steps": [child(["--part", "rewnorm", "--obs-dim", str(od), "--rounds", str(a.rounds)], 300) for od in (15, 8)]}
+        doc["card"] = doc["steps"][0]["card"]
+        out = a.out if a.out != ap.get_default("out") else os.path.join(ROOT, "profiles", "learner_rewnorm_kbench.json")
+        with open(out, "w") as f:
+            json.dump(doc, f, indent=1); f.write("\n")
+        print(json.dumps(doc, indent=1))
+        return
     if a.terms:
         doc = {"what": "one minibatch step of 32768 samples (64 x 4096 chunk): so100_learner_minibatch_step against so100_learner_minibatch_step_ex",
                "commit": a.commit, "steps": [child(["--part", "terms", "--obs-dim", str(od), "--rounds", str(a.rounds)], 300) for od in (15, 8)]}
