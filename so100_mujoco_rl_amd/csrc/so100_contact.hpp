@@ -132,21 +132,21 @@ template <typename T> struct ContactsLds {                  // [record][field][l
 
 // ---- world-frame kinematics of the six joint frames (axis z_k, origin o_k) and of the two jaw links ------------------------
 template <typename T> struct WorldFK { T z[6][3], o[6][3], oz[6][3], R4[9], R5[9]; };      // oz_k = o_k x z_k: the linear part of joint k's screw about the world origin
-template <int K, typename T> SO100_HD void wfk_step(const T s[6], const T c[6], T pos[3], T R[9], WorldFK<T>& W) {
-    fk_link<K>(s, c, pos, R);
+template <int K, bool Z, typename T> SO100_HD void wfk_step(const T s[6], const T c[6], T pos[3], T R[9], WorldFK<T>& W) {
+    fk_link<K, Z>(s, c, pos, R);
     constexpr int AX = so100g::LINK_AXIS[K];
 #pragma unroll
     for (int i = 0; i < 3; i++) { W.z[K][i] = R[3*i + AX]; W.o[K][i] = pos[i]; }
     cross(W.o[K], W.z[K], W.oz[K]);
 }
-template <typename T> SO100_HD void world_fk(const T s[6], const T c[6], WorldFK<T>& W) {
+template <typename T, bool Z = false> SO100_HD void world_fk(const T s[6], const T c[6], WorldFK<T>& W) {
     T pos[3] = { T(0), T(0), T(0) };
     T R[9] = { T(1), T(0), T(0), T(0), T(1), T(0), T(0), T(0), T(1) };
-    wfk_step<0>(s, c, pos, R, W); wfk_step<1>(s, c, pos, R, W); wfk_step<2>(s, c, pos, R, W); wfk_step<3>(s, c, pos, R, W);
-    wfk_step<4>(s, c, pos, R, W);
+    wfk_step<0, Z>(s, c, pos, R, W); wfk_step<1, Z>(s, c, pos, R, W); wfk_step<2, Z>(s, c, pos, R, W); wfk_step<3, Z>(s, c, pos, R, W);
+    wfk_step<4, Z>(s, c, pos, R, W);
 #pragma unroll
     for (int i = 0; i < 9; i++) W.R4[i] = R[i];
-    wfk_step<5>(s, c, pos, R, W);
+    wfk_step<5, Z>(s, c, pos, R, W);
 #pragma unroll
     for (int i = 0; i < 9; i++) W.R5[i] = R[i];
 }

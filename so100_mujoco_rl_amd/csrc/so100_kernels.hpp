@@ -138,7 +138,7 @@ __global__ void __launch_bounds__(256) so100_step_mw(SimParams p, StepPtrs io) {
     Arm<float> A; Prof prof_;
     const PhaseLds lds{ xq, xc, xb, cbuf, xa, xk, xm, pbuf, PADS ? xw : nullptr };
     ContactMemo memo;                                             // (reset by physics_phase_mw: the memory lives for the env step's substeps)
-    physics_phase_mw<PADS, LINKS, !PADS && FL != 7, !PADS && FL != 7>(p, wave, lane, e, ctx.ctrl, cstale, A, lds, memo, prof_, [](int) {}, [&]() {
+    physics_phase_mw<PADS, LINKS, !PADS && FL != 7, !PADS && FL != 7, !PADS && FL != 7>(p, wave, lane, e, ctx.ctrl, cstale, A, lds, memo, prof_, [](int) {}, [&]() {
         ctx = StepCtx{};
 #pragma unroll
         for (int k = 0; k < 8; k++) u[k] = 0.0f;
@@ -146,7 +146,7 @@ __global__ void __launch_bounds__(256) so100_step_mw(SimParams p, StepPtrs io) {
     if (wave != 0 || !live) return;
     e.nsub += p.frame_skip;
     TaskPoses<float> P;
-    task_poses<float>(A.s, A.c, !reach_kind<KIND>(), P);
+    task_poses<float, !PADS && FL != 7>(A.s, A.c, !reach_kind<KIND>(), P);
     float obs[OD], tobs[OD]; bool term;
     const float reward = env_step_post<KIND>(e, ctx, u, P, cstale, obs, term);
     const StepResult r = env_step_finish<KIND>(e, reward, term, p, p.env_id_offset + (uint32_t)env, inj, io.start_tab, obs, tobs);

@@ -86,80 +86,6 @@ template <> SO100_HD void tsincos<double>(double x, double& s, double& c) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// small vector helpers (everything is fully unrolled; arrays live in registers)
-// ---------------------------------------------------------------------------------------------
-template <typename T> SO100_HD void cross(const T a[3], const T b[3], T r[3]) {
-    const T x = a[1]*b[2] - a[2]*b[1], y = a[2]*b[0] - a[0]*b[2], z = a[0]*b[1] - a[1]*b[0];
-    r[0] = x; r[1] = y; r[2] = z;
-}
-template <typename T> SO100_HD T dot(const T a[3], const T b[3]) { return a[0]*b[0] + a[1]*b[1] + a[2]*b[2]; }
-
-// rotation about coordinate axis A by (s,c): y = Rot x   and   y = Rot^T x
-template <int A, typename T> SO100_HD void rot_axis(const T x[3], T s, T c, T y[3]) {
-    constexpr int B = (A + 1) % 3, C = (A + 2) % 3;
-    const T xb = x[B], xc = x[C];
-    y[A] = x[A]; y[B] = c*xb - s*xc; y[C] = s*xb + c*xc;
-}
-template <int A, typename T> SO100_HD void rot_axis_T(const T x[3], T s, T c, T y[3]) {
-    constexpr int B = (A + 1) % 3, C = (A + 2) % 3;
-    const T xb = x[B], xc = x[C];
-    y[A] = x[A]; y[B] = c*xb + s*xc; y[C] = -s*xb + c*xc;
-}
-// Compile-time-sparse products with model constants.  The link rotations are (nearly) axis-aligned: five exact
-// zeros per matrix for links 0-4, and most link offsets have a zero x component.  `0.0f * x` cannot be folded by the
-// compiler under IEEE rules, so exact zeros are skipped here with `if constexpr` (x * 1.0f and x * -1.0f fold anyway).
-template <int K, int A, int B, int C_, typename T> SO100_HD T cdot3(T x0, T x1, T x2) {     // sum of LINK_C[K][.] * x.
-    constexpr double a = so100g::LINK_C[K][A], b = so100g::LINK_C[K][B], c = so100g::LINK_C[K][C_];
-    if constexpr (a != 0 && b != 0 && c != 0) return T(a)*x0 + T(b)*x1 + T(c)*x2;
-    else if constexpr (a != 0 && b != 0) return T(a)*x0 + T(b)*x1;
-    else if constexpr (a != 0 && c != 0) return T(a)*x0 + T(c)*x2;
-    else if constexpr (b != 0 && c != 0) return T(b)*x1 + T(c)*x2;
-    else if constexpr (a != 0) return T(a)*x0;
-    else if constexpr (b != 0) return T(b)*x1;
-    else if constexpr (c != 0) return T(c)*x2;
-    else return T(0);
-}
-template <int K, int IA, int IB, typename T> SO100_HD T pdiff(T xa, T xb) {                  // P[IA]*xa - P[IB]*xb
-    constexpr double a = so100g::LINK_P[K][IA], b = so100g::LINK_P[K][IB];
-    if constexpr (a != 0 && b != 0) return T(a)*xa - T(b)*xb;
-    else if constexpr (a != 0) return T(a)*xa;
-    else if constexpr (b != 0) return -(T(b)*xb);
-    else return T(0);
-}
-template <int K, int I, typename T> SO100_HD T pmul(T x) {                                      // P[I] * x
-    constexpr double a = so100g::LINK_P[K][I];
-    if constexpr (a != 0) return T(a)*x; else return T(0);
-}
-template <int K, int I, int J, typename T> SO100_HD T ppmul(T x) {                              // P[I] P[J] * x
-    constexpr double a = so100g::LINK_P[K][I]*so100g::LINK_P[K][J];
-    if constexpr (a != 0) return T(a)*x; else return T(0);
-}
-template <int K, typename T> SO100_HD void pcross(const T v[3], T r[3]) {                    // r = p_K x v
-    const T v0 = v[0], v1 = v[1], v2 = v[2];
-    r[0] = pdiff<K, 1, 2>(v2, v1); r[1] = pdiff<K, 2, 0>(v0, v2); r[2] = pdiff<K, 0, 1>(v1, v0);
-}
-template <int K, typename T> SO100_HD void crossp(const T v[3], T r[3]) {                    // r = v x p_K
-    const T v0 = v[0], v1 = v[1], v2 = v[2];
-    r[0] = pdiff<K, 2, 1>(v1, v2); r[1] = pdiff<K, 0, 2>(v2, v0); r[2] = pdiff<K, 1, 0>(v0, v1);
-}
-// constant link rotation C_K (child->parent) and its transpose
-template <int K, typename T> SO100_HD void cmat(const T x[3], T y[3]) {
-    const T x0 = x[0], x1 = x[1], x2 = x[2];
-    y[0] = cdot3<K, 0, 1, 2>(x0, x1, x2); y[1] = cdot3<K, 3, 4, 5>(x0, x1, x2); y[2] = cdot3<K, 6, 7, 8>(x0, x1, x2);
-}
-template <int K, typename T> SO100_HD void cmat_T(const T x[3], T y[3]) {
-    const T x0 = x[0], x1 = x[1], x2 = x[2];
-    y[0] = cdot3<K, 0, 3, 6>(x0, x1, x2); y[1] = cdot3<K, 1, 4, 7>(x0, x1, x2); y[2] = cdot3<K, 2, 5, 8>(x0, x1, x2);
-}
-// parent coords -> link K coords (E_K^T) and back (E_K), E_K = C_K Rot(axis_K, q_K)
-template <int K, typename T> SO100_HD void to_child(const T x[3], T s, T c, T y[3]) {
-    T t[3]; cmat_T<K>(x, t); rot_axis_T<so100g::LINK_AXIS[K]>(t, s, c, y);
-}
-template <int K, typename T> SO100_HD void to_parent(const T x[3], T s, T c, T y[3]) {
-    T t[3]; rot_axis<so100g::LINK_AXIS[K]>(x, s, c, t); cmat<K>(t, y);
-}
-
-// ---------------------------------------------------------------------------------------------
 // pairs: two values of T carried through the same arithmetic.  On the device V2<float> is a native two-float vector, so
 // `*`, `+`, `-` become v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32 (two IEEE fp32 operations per instruction, issued at
 // the rate of one scalar v_fma_f32).  Elsewhere it is a two-member struct with the same operators.  Each half is computed
@@ -183,31 +109,145 @@ template <> struct V2sel<float> { using type = float __attribute__((ext_vector_t
 #endif
 template <typename T> using V2 = typename V2sel<T>::type;
 
+// ---------------------------------------------------------------------------------------------
+// products and sums with an operand the COMPILER knows to be zero.  IEEE arithmetic lets it fold neither `0*x` (x may be negative, infinite
+// or NaN) nor `x + 0` (x may be -0), and once the templates below are inlined and unrolled many operands are literal zeros: the base at
+// rest (w = wd = 0, a = (0, 0, g)), a velocity with the joint axis as its only component, the axis component of a CRBA column's force,
+// the rows of the identity in the pose recursion, the zero half of a pair.  known_zero(x) holds only where the optimiser has proved x
+// to be the constant 0 (__builtin_constant_p is decided after inlining; where it is not proved, the plain operation runs); zmul / zadd /
+// zsub then leave the term out, for a pair half by half.  For finite inputs that changes no bit of any result, except possibly the
+// sign of a zero; nothing that rounds is reordered (tests/test_arm_zero_terms_cpu.py holds the results to the ones before).
+// Z = false switches it off: every helper below that takes Z then compiles the plain expression.  It is on where the pair form runs
+// (arm_bias / arm_mass / arm_substep: Z = PK unless the caller says otherwise; the multi-wave kernels pass the same switch to their pose
+// recursions); the scalar-form kernels and every caller that names no Z (cross in the contact / cube / render code, task_poses, world_fk)
+// compile the text they had -- with it on everywhere the spill rows of some contact variants grow.
+// ---------------------------------------------------------------------------------------------
+template <typename X> struct is_pair { static constexpr bool value = false; };
+template <typename T> struct is_pair<V2s<T>> { static constexpr bool value = true; };
+#if defined(__HIP_DEVICE_COMPILE__)
+template <> struct is_pair<V2<float>> { static constexpr bool value = true; };
+#endif
+// (conditional expressions on non-short-circuit conditions, not branches: the optimiser then resolves a whole chain of them in one pass)
+template <bool Z, typename X> SO100_HD bool known_zero(X x) {
+    if constexpr (!Z) return false;
+    else if constexpr (is_pair<X>::value) return known_zero<Z>(x.x) & known_zero<Z>(x.y);
+    else return __builtin_constant_p(x) && x == X(0);
+}
+template <bool Z, typename X> SO100_HD bool half_known_zero(X a, X b) {          // some half of a pair operand is
+    return known_zero<Z>(a.x) | known_zero<Z>(a.y) | known_zero<Z>(b.x) | known_zero<Z>(b.y);
+}
+template <bool Z, typename X> SO100_HD X zmul(X a, X b) {
+    if constexpr (is_pair<X>::value) return half_known_zero<Z>(a, b) ? X{ zmul<Z>(a.x, b.x), zmul<Z>(a.y, b.y) } : a*b;
+    else return (known_zero<Z>(a) | known_zero<Z>(b)) ? X(0) : a*b;
+}
+template <bool Z, typename X> SO100_HD X zadd(X a, X b) {
+    if constexpr (is_pair<X>::value) return half_known_zero<Z>(a, b) ? X{ zadd<Z>(a.x, b.x), zadd<Z>(a.y, b.y) } : a + b;
+    else return known_zero<Z>(a) ? b : (known_zero<Z>(b) ? a : a + b);
+}
+template <bool Z, typename X> SO100_HD X zsub(X a, X b) {
+    if constexpr (is_pair<X>::value) return half_known_zero<Z>(a, b) ? X{ zsub<Z>(a.x, b.x), zsub<Z>(a.y, b.y) } : a - b;
+    else return known_zero<Z>(b) ? a : (known_zero<Z>(a) ? -b : a - b);
+}
+
+// ---------------------------------------------------------------------------------------------
+// small vector helpers (everything is fully unrolled; arrays live in registers)
+// ---------------------------------------------------------------------------------------------
+template <bool Z = false, typename T> SO100_HD void cross(const T a[3], const T b[3], T r[3]) {
+    const T x = zsub<Z>(zmul<Z>(a[1], b[2]), zmul<Z>(a[2], b[1])), y = zsub<Z>(zmul<Z>(a[2], b[0]), zmul<Z>(a[0], b[2])), z = zsub<Z>(zmul<Z>(a[0], b[1]), zmul<Z>(a[1], b[0]));
+    r[0] = x; r[1] = y; r[2] = z;
+}
+template <typename T> SO100_HD T dot(const T a[3], const T b[3]) { return a[0]*b[0] + a[1]*b[1] + a[2]*b[2]; }
+
+// rotation about coordinate axis A by (s,c): y = Rot x   and   y = Rot^T x
+template <int A, bool Z, typename T> SO100_HD void rot_axis(const T x[3], T s, T c, T y[3]) {
+    constexpr int B = (A + 1) % 3, C = (A + 2) % 3;
+    const T xb = x[B], xc = x[C];
+    y[A] = x[A]; y[B] = zsub<Z>(zmul<Z>(c, xb), zmul<Z>(s, xc)); y[C] = zadd<Z>(zmul<Z>(s, xb), zmul<Z>(c, xc));
+}
+template <int A, bool Z, typename T> SO100_HD void rot_axis_T(const T x[3], T s, T c, T y[3]) {
+    constexpr int B = (A + 1) % 3, C = (A + 2) % 3;
+    const T xb = x[B], xc = x[C];
+    y[A] = x[A]; y[B] = zadd<Z>(zmul<Z>(c, xb), zmul<Z>(s, xc)); y[C] = zadd<Z>(zmul<Z>(-s, xb), zmul<Z>(c, xc));
+}
+// Compile-time-sparse products with model constants.  The link rotations are (nearly) axis-aligned: five exact
+// zeros per matrix for links 0-4, and most link offsets have a zero x component.  `0.0f * x` cannot be folded by the
+// compiler under IEEE rules, so exact zeros are skipped here with `if constexpr` (x * 1.0f and x * -1.0f fold anyway).
+template <int K, int A, int B, int C_, bool Z, typename T> SO100_HD T cdot3(T x0, T x1, T x2) {     // sum of LINK_C[K][.] * x.
+    constexpr double a = so100g::LINK_C[K][A], b = so100g::LINK_C[K][B], c = so100g::LINK_C[K][C_];
+    if constexpr (a != 0 && b != 0 && c != 0) return zadd<Z>(zadd<Z>(zmul<Z>(T(a), x0), zmul<Z>(T(b), x1)), zmul<Z>(T(c), x2));
+    else if constexpr (a != 0 && b != 0) return zadd<Z>(zmul<Z>(T(a), x0), zmul<Z>(T(b), x1));
+    else if constexpr (a != 0 && c != 0) return zadd<Z>(zmul<Z>(T(a), x0), zmul<Z>(T(c), x2));
+    else if constexpr (b != 0 && c != 0) return zadd<Z>(zmul<Z>(T(b), x1), zmul<Z>(T(c), x2));
+    else if constexpr (a != 0) return zmul<Z>(T(a), x0);
+    else if constexpr (b != 0) return zmul<Z>(T(b), x1);
+    else if constexpr (c != 0) return zmul<Z>(T(c), x2);
+    else return T(0);
+}
+template <int K, int IA, int IB, bool Z, typename T> SO100_HD T pdiff(T xa, T xb) {                  // P[IA]*xa - P[IB]*xb
+    constexpr double a = so100g::LINK_P[K][IA], b = so100g::LINK_P[K][IB];
+    if constexpr (a != 0 && b != 0) return zsub<Z>(zmul<Z>(T(a), xa), zmul<Z>(T(b), xb));
+    else if constexpr (a != 0) return zmul<Z>(T(a), xa);
+    else if constexpr (b != 0) return -zmul<Z>(T(b), xb);
+    else return T(0);
+}
+template <int K, int I, typename T> SO100_HD T pmul(T x) {                                      // P[I] * x
+    constexpr double a = so100g::LINK_P[K][I];
+    if constexpr (a != 0) return T(a)*x; else return T(0);
+}
+template <int K, int I, int J, typename T> SO100_HD T ppmul(T x) {                              // P[I] P[J] * x
+    constexpr double a = so100g::LINK_P[K][I]*so100g::LINK_P[K][J];
+    if constexpr (a != 0) return T(a)*x; else return T(0);
+}
+template <int K, bool Z, typename T> SO100_HD void pcross(const T v[3], T r[3]) {                    // r = p_K x v
+    const T v0 = v[0], v1 = v[1], v2 = v[2];
+    r[0] = pdiff<K, 1, 2, Z>(v2, v1); r[1] = pdiff<K, 2, 0, Z>(v0, v2); r[2] = pdiff<K, 0, 1, Z>(v1, v0);
+}
+template <int K, bool Z, typename T> SO100_HD void crossp(const T v[3], T r[3]) {                    // r = v x p_K
+    const T v0 = v[0], v1 = v[1], v2 = v[2];
+    r[0] = pdiff<K, 2, 1, Z>(v1, v2); r[1] = pdiff<K, 0, 2, Z>(v2, v0); r[2] = pdiff<K, 1, 0, Z>(v0, v1);
+}
+// constant link rotation C_K (child->parent) and its transpose
+template <int K, bool Z, typename T> SO100_HD void cmat(const T x[3], T y[3]) {
+    const T x0 = x[0], x1 = x[1], x2 = x[2];
+    y[0] = cdot3<K, 0, 1, 2, Z>(x0, x1, x2); y[1] = cdot3<K, 3, 4, 5, Z>(x0, x1, x2); y[2] = cdot3<K, 6, 7, 8, Z>(x0, x1, x2);
+}
+template <int K, bool Z, typename T> SO100_HD void cmat_T(const T x[3], T y[3]) {
+    const T x0 = x[0], x1 = x[1], x2 = x[2];
+    y[0] = cdot3<K, 0, 3, 6, Z>(x0, x1, x2); y[1] = cdot3<K, 1, 4, 7, Z>(x0, x1, x2); y[2] = cdot3<K, 2, 5, 8, Z>(x0, x1, x2);
+}
+// parent coords -> link K coords (E_K^T) and back (E_K), E_K = C_K Rot(axis_K, q_K)
+template <int K, bool Z, typename T> SO100_HD void to_child(const T x[3], T s, T c, T y[3]) {
+    T t[3]; cmat_T<K, Z>(x, t); rot_axis_T<so100g::LINK_AXIS[K], Z>(t, s, c, y);
+}
+template <int K, bool Z, typename T> SO100_HD void to_parent(const T x[3], T s, T c, T y[3]) {
+    T t[3]; rot_axis<so100g::LINK_AXIS[K], Z>(x, s, c, t); cmat<K, Z>(t, y);
+}
+
 // symmetric 3x3 stored (xx, yy, zz, xy, xz, yz)
-template <typename T> SO100_HD void sym_mul(const T I[6], const T v[3], T r[3]) {
-    const T x = I[0]*v[0] + I[3]*v[1] + I[4]*v[2];
-    const T y = I[3]*v[0] + I[1]*v[1] + I[5]*v[2];
-    const T z = I[4]*v[0] + I[5]*v[1] + I[2]*v[2];
+template <bool Z, typename T> SO100_HD void sym_mul(const T I[6], const T v[3], T r[3]) {
+    const T x = zadd<Z>(zadd<Z>(zmul<Z>(I[0], v[0]), zmul<Z>(I[3], v[1])), zmul<Z>(I[4], v[2]));
+    const T y = zadd<Z>(zadd<Z>(zmul<Z>(I[3], v[0]), zmul<Z>(I[1], v[1])), zmul<Z>(I[5], v[2]));
+    const T z = zadd<Z>(zadd<Z>(zmul<Z>(I[4], v[0]), zmul<Z>(I[5], v[1])), zmul<Z>(I[2], v[2]));
     r[0] = x; r[1] = y; r[2] = z;
 }
 SO100_HD constexpr int sym_idx(int i, int j) {
     return i == j ? i : ((i + j == 1) ? 3 : ((i + j == 2) ? 4 : 5));
 }
 // B = C_K A C_K^T with the constant, sparse link rotation C_K
-template <int K, typename T> SO100_HD void sym_similarity_c(const T A[6], T Bm[6]) {
+template <int K, bool Z, typename T> SO100_HD void sym_similarity_c(const T A[6], T Bm[6]) {
     T t[9];                                                   // t = C A
 #define SO100_ROW(i) \
-    t[3*i]   = cdot3<K, 3*i, 3*i+1, 3*i+2>(A[0], A[3], A[4]); \
-    t[3*i+1] = cdot3<K, 3*i, 3*i+1, 3*i+2>(A[3], A[1], A[5]); \
-    t[3*i+2] = cdot3<K, 3*i, 3*i+1, 3*i+2>(A[4], A[5], A[2]);
+    t[3*i]   = cdot3<K, 3*i, 3*i+1, 3*i+2, Z>(A[0], A[3], A[4]); \
+    t[3*i+1] = cdot3<K, 3*i, 3*i+1, 3*i+2, Z>(A[3], A[1], A[5]); \
+    t[3*i+2] = cdot3<K, 3*i, 3*i+1, 3*i+2, Z>(A[4], A[5], A[2]);
     SO100_ROW(0) SO100_ROW(1) SO100_ROW(2)
 #undef SO100_ROW
-    Bm[0] = cdot3<K, 0, 1, 2>(t[0], t[1], t[2]);
-    Bm[1] = cdot3<K, 3, 4, 5>(t[3], t[4], t[5]);
-    Bm[2] = cdot3<K, 6, 7, 8>(t[6], t[7], t[8]);
-    Bm[3] = cdot3<K, 3, 4, 5>(t[0], t[1], t[2]);
-    Bm[4] = cdot3<K, 6, 7, 8>(t[0], t[1], t[2]);
-    Bm[5] = cdot3<K, 6, 7, 8>(t[3], t[4], t[5]);
+    Bm[0] = cdot3<K, 0, 1, 2, Z>(t[0], t[1], t[2]);
+    Bm[1] = cdot3<K, 3, 4, 5, Z>(t[3], t[4], t[5]);
+    Bm[2] = cdot3<K, 6, 7, 8, Z>(t[6], t[7], t[8]);
+    Bm[3] = cdot3<K, 3, 4, 5, Z>(t[0], t[1], t[2]);
+    Bm[4] = cdot3<K, 6, 7, 8, Z>(t[0], t[1], t[2]);
+    Bm[5] = cdot3<K, 6, 7, 8, Z>(t[3], t[4], t[5]);
 }
 // similarity by a rotation about coordinate axis A: B = Rot A Rot^T
 template <int AX, typename T> SO100_HD void sym_rot_axis(const T A[6], T s, T c, T Bm[6]) {
@@ -233,7 +273,7 @@ template <typename T> struct Arm {
     T Dinv[6], Minv[21];   // arm_factor: 1/D of the factor; explicit inverse (constrained variants only)
 };
 
-template <int K, typename T> struct LinkFwd {            // RNEA forward step for link K
+template <int K, typename T, bool Z> struct LinkFwd {            // RNEA forward step for link K
     SO100_HD static void run(const T s[6], const T c[6], const T v[6], T w[3], T wd[3], T a[3],
                              T f[6][3], T n[6][3]) {
         constexpr int AX = so100g::LINK_AXIS[K];
@@ -243,21 +283,22 @@ template <int K, typename T> struct LinkFwd {            // RNEA forward step fo
             // the base is at rest: w_p = wd_p = 0, so the origin acceleration is the base's (gravity) and
             // w = axis qd, wd = 0 (the generic code below would spend ~40 instructions multiplying zeros)
             T ao[3] = { a[0], a[1], a[2] };
-            to_child<K>(ao, s[K], c[K], a);
+            to_child<K, Z>(ao, s[K], c[K], a);
             w[AX] = qd; w[B] = T(0); w[C] = T(0);
             wd[0] = T(0); wd[1] = T(0); wd[2] = T(0);
         } else {
             // acceleration of this link's origin, in parent coords: a + wd x p + w x (w x p)
             T t1[3], t2[3], ao[3];
-            crossp<K>(wd, t1); crossp<K>(w, t2); cross(w, t2, t2);
-            ao[0] = a[0] + t1[0] + t2[0]; ao[1] = a[1] + t1[1] + t2[1]; ao[2] = a[2] + t1[2] + t2[2];
+            crossp<K, Z>(wd, t1); crossp<K, Z>(w, t2); cross<Z>(w, t2, t2);
+#pragma unroll
+            for (int i = 0; i < 3; i++) ao[i] = zadd<Z>(zadd<Z>(a[i], t1[i]), t2[i]);
             T wc[3], wdc[3];
-            to_child<K>(w, s[K], c[K], wc);
-            to_child<K>(wd, s[K], c[K], wdc);
-            to_child<K>(ao, s[K], c[K], a);
+            to_child<K, Z>(w, s[K], c[K], wc);
+            to_child<K, Z>(wd, s[K], c[K], wdc);
+            to_child<K, Z>(ao, s[K], c[K], a);
             // wd_k = E^T wd_p + (E^T w_p) x (axis qd);  w_k = E^T w_p + axis qd
-            wdc[B] += wc[C]*qd; wdc[C] -= wc[B]*qd;
-            wc[AX] += qd;
+            wdc[B] = zadd<Z>(wdc[B], zmul<Z>(wc[C], qd)); wdc[C] = zsub<Z>(wdc[C], zmul<Z>(wc[B], qd));
+            wc[AX] = zadd<Z>(wc[AX], qd);
             w[0] = wc[0]; w[1] = wc[1]; w[2] = wc[2];
             wd[0] = wdc[0]; wd[1] = wdc[1]; wd[2] = wdc[2];
         }
@@ -267,24 +308,26 @@ template <int K, typename T> struct LinkFwd {            // RNEA forward step fo
                           T(so100g::LINK_IORG[K][3]), T(so100g::LINK_IORG[K][4]), T(so100g::LINK_IORG[K][5]) };
         const T m = T(so100g::LINK_MASS[K]);
         T u1[3], u2[3], Iw[3];
-        cross(wd, h, u1); cross(w, h, u2); cross(w, u2, u2);
-        f[K][0] = m*a[0] + u1[0] + u2[0]; f[K][1] = m*a[1] + u1[1] + u2[1]; f[K][2] = m*a[2] + u1[2] + u2[2];
-        sym_mul(Io, wd, u1); sym_mul(Io, w, Iw); cross(w, Iw, u2);
-        T u3[3]; cross(h, a, u3);
-        n[K][0] = u1[0] + u2[0] + u3[0]; n[K][1] = u1[1] + u2[1] + u3[1]; n[K][2] = u1[2] + u2[2] + u3[2];
+        cross<Z>(wd, h, u1); cross<Z>(w, h, u2); cross<Z>(w, u2, u2);
+#pragma unroll
+        for (int i = 0; i < 3; i++) f[K][i] = zadd<Z>(zadd<Z>(zmul<Z>(m, a[i]), u1[i]), u2[i]);
+        sym_mul<Z>(Io, wd, u1); sym_mul<Z>(Io, w, Iw); cross<Z>(w, Iw, u2);
+        T u3[3]; cross<Z>(h, a, u3);
+#pragma unroll
+        for (int i = 0; i < 3; i++) n[K][i] = zadd<Z>(zadd<Z>(u1[i], u2[i]), u3[i]);
     }
 };
 
-template <int K, typename T> struct LinkBwd {            // RNEA backward step: project, pass to parent
+template <int K, typename T, bool Z> struct LinkBwd {            // RNEA backward step: project, pass to parent
     SO100_HD static void run(const T s[6], const T c[6], T f[6][3], T n[6][3], T bias[6]) {
         bias[K] = n[K][so100g::LINK_AXIS[K]];
         if constexpr (K > 0) {
             T fp[3], np[3], t[3];
-            to_parent<K>(f[K], s[K], c[K], fp);
-            to_parent<K>(n[K], s[K], c[K], np);
-            pcross<K>(fp, t);
+            to_parent<K, Z>(f[K], s[K], c[K], fp);
+            to_parent<K, Z>(n[K], s[K], c[K], np);
+            pcross<K, Z>(fp, t);
 #pragma unroll
-            for (int i = 0; i < 3; i++) { f[K-1][i] += fp[i]; n[K-1][i] += np[i] + t[i]; }
+            for (int i = 0; i < 3; i++) { f[K-1][i] += fp[i]; n[K-1][i] += zadd<Z>(np[i], t[i]); }
         }
     }
 };
@@ -292,7 +335,7 @@ template <int K, typename T> struct LinkBwd {            // RNEA backward step: 
 // composite inertia of the subtree rooted at link K, in link-K coords about the link-K origin
 template <typename T> struct Composite { T m, h[3], I[6]; };
 
-template <int K, typename T> struct LinkCrb {
+template <int K, typename T, bool Z> struct LinkCrb {
     // add link K's composite (already complete) into its parent's, then emit column K of M
     SO100_HD static void run(const T s[6], const T c[6], Composite<T> cmp[6], T M[21]) {
         constexpr int AX = so100g::LINK_AXIS[K];
@@ -313,13 +356,13 @@ template <int K, typename T> struct LinkCrb {
         constexpr int AX = so100g::LINK_AXIS[K];
         {
             T hp[3], Ir[6], Ip[6];
-            to_parent<K>(cmp[K].h, s[K], c[K], hp);
+            to_parent<K, Z>(cmp[K].h, s[K], c[K], hp);
             sym_rot_axis<AX>(cmp[K].I, s[K], c[K], Ir);
-            sym_similarity_c<K>(Ir, Ip);
+            sym_similarity_c<K, Z>(Ir, Ip);
             const T m = cmp[K].m;
             constexpr double pp_c = so100g::LINK_P[K][0]*so100g::LINK_P[K][0] + so100g::LINK_P[K][1]*so100g::LINK_P[K][1]
                                   + so100g::LINK_P[K][2]*so100g::LINK_P[K][2];
-            const T ph = pmul<K, 0>(hp[0]) + pmul<K, 1>(hp[1]) + pmul<K, 2>(hp[2]);
+            const T ph = zadd<Z>(zadd<Z>(pmul<K, 0>(hp[0]), pmul<K, 1>(hp[1])), pmul<K, 2>(hp[2]));
             const T dg = m*T(pp_c) + T(2)*ph;
             Composite<T>& P = cmp[K-1];
             P.I[0] += Ip[0] + dg - ppmul<K, 0, 0>(m) - T(2)*pmul<K, 0>(hp[0]);
@@ -328,7 +371,7 @@ template <int K, typename T> struct LinkCrb {
             P.I[3] += Ip[3] - ppmul<K, 0, 1>(m) - pmul<K, 0>(hp[1]) - pmul<K, 1>(hp[0]);
             P.I[4] += Ip[4] - ppmul<K, 0, 2>(m) - pmul<K, 0>(hp[2]) - pmul<K, 2>(hp[0]);
             P.I[5] += Ip[5] - ppmul<K, 1, 2>(m) - pmul<K, 1>(hp[2]) - pmul<K, 2>(hp[1]);
-            P.h[0] += hp[0] + pmul<K, 0>(m); P.h[1] += hp[1] + pmul<K, 1>(m); P.h[2] += hp[2] + pmul<K, 2>(m);
+            P.h[0] += zadd<Z>(hp[0], pmul<K, 0>(m)); P.h[1] += zadd<Z>(hp[1], pmul<K, 1>(m)); P.h[2] += zadd<Z>(hp[2], pmul<K, 2>(m));
             P.m += m;
         }
     }
@@ -336,11 +379,11 @@ template <int K, typename T> struct LinkCrb {
     template <int J1> SO100_HD static void walk(const T s[6], const T c[6], T f[3], T n[3], T M[21]) {
         if constexpr (J1 > 0) {
             T fp[3], np[3], t[3];
-            to_parent<J1>(f, s[J1], c[J1], fp);
-            to_parent<J1>(n, s[J1], c[J1], np);
-            pcross<J1>(fp, t);
+            to_parent<J1, Z>(f, s[J1], c[J1], fp);
+            to_parent<J1, Z>(n, s[J1], c[J1], np);
+            pcross<J1, Z>(fp, t);
             f[0] = fp[0]; f[1] = fp[1]; f[2] = fp[2];
-            n[0] = np[0] + t[0]; n[1] = np[1] + t[1]; n[2] = np[2] + t[2];
+            n[0] = zadd<Z>(np[0], t[0]); n[1] = zadd<Z>(np[1], t[1]); n[2] = zadd<Z>(np[2], t[2]);
             M[K*(K+1)/2 + (J1-1)] = n[so100g::LINK_AXIS[J1-1]];
             walk<J1-1>(s, c, f, n, M);
         }
@@ -350,7 +393,7 @@ template <int K, typename T> struct LinkCrb {
 // The same recursions in pair form (arm_bias / arm_mass with PK = true): every transform that two 3-vectors take with the
 // same s, c and constants runs once on a V2[3].  RNEA carries W = (wd, w) forward and FN = (f, n) backward; the CRBA column walk
 // carries (f, n).  A half is unpacked only where it feeds a term of its own (w x (w x p), h x a, p x f).
-template <int K, typename T> struct LinkFwdP {
+template <int K, typename T, bool Z> struct LinkFwdP {
     using V = V2<T>;
     SO100_HD static void run(const T s[6], const T c[6], const T v[6], V W[3], T a[3], V FN[6][3]) {
         constexpr int AX = so100g::LINK_AXIS[K];
@@ -358,20 +401,21 @@ template <int K, typename T> struct LinkFwdP {
         const T qd = v[K];
         if constexpr (K == 0) {
             T ao[3] = { a[0], a[1], a[2] };
-            to_child<K>(ao, s[K], c[K], a);
+            to_child<K, Z>(ao, s[K], c[K], a);
             W[AX] = V{ T(0), qd }; W[B] = V{ T(0), T(0) }; W[C] = V{ T(0), T(0) };
         } else {
             V t[3];
-            crossp<K>(W, t);                                   // (wd x p, w x p)
+            crossp<K, Z>(W, t);                                   // (wd x p, w x p)
             const T w[3] = { W[0].y, W[1].y, W[2].y }, t2p[3] = { t[0].y, t[1].y, t[2].y };
             T t2[3], ao[3];
-            cross(w, t2p, t2);
-            ao[0] = a[0] + t[0].x + t2[0]; ao[1] = a[1] + t[1].x + t2[1]; ao[2] = a[2] + t[2].x + t2[2];
+            cross<Z>(w, t2p, t2);
+#pragma unroll
+            for (int i = 0; i < 3; i++) ao[i] = zadd<Z>(zadd<Z>(a[i], t[i].x), t2[i]);
             V Wc[3];
-            to_child<K>(W, V(s[K]), V(c[K]), Wc);
-            to_child<K>(ao, s[K], c[K], a);
-            Wc[B].x += Wc[C].y*qd; Wc[C].x -= Wc[B].y*qd;
-            Wc[AX].y += qd;
+            to_child<K, Z>(W, V(s[K]), V(c[K]), Wc);
+            to_child<K, Z>(ao, s[K], c[K], a);
+            Wc[B].x = zadd<Z>(Wc[B].x, zmul<Z>(Wc[C].y, qd)); Wc[C].x = zsub<Z>(Wc[C].x, zmul<Z>(Wc[B].y, qd));
+            Wc[AX].y = zadd<Z>(Wc[AX].y, qd);
             W[0] = Wc[0]; W[1] = Wc[1]; W[2] = Wc[2];
         }
         const V h[3] = { V(so100g::LINK_H[K][0]), V(so100g::LINK_H[K][1]), V(so100g::LINK_H[K][2]) };
@@ -380,28 +424,28 @@ template <int K, typename T> struct LinkFwdP {
         const T hs[3] = { T(so100g::LINK_H[K][0]), T(so100g::LINK_H[K][1]), T(so100g::LINK_H[K][2]) };
         const T m = T(so100g::LINK_MASS[K]);
         V U[3], S[3];
-        cross(W, h, U);                                        // (wd x h, w x h)
-        sym_mul(Io, W, S);                                     // (Io wd, Io w)
+        cross<Z>(W, h, U);                                        // (wd x h, w x h)
+        sym_mul<Z>(Io, W, S);                                     // (Io wd, Io w)
         const T w[3] = { W[0].y, W[1].y, W[2].y };
         const T u2p[3] = { U[0].y, U[1].y, U[2].y }, Iw[3] = { S[0].y, S[1].y, S[2].y };
         T u2[3], v2[3], u3[3];
-        cross(w, u2p, u2); cross(w, Iw, v2); cross(hs, a, u3);
+        cross<Z>(w, u2p, u2); cross<Z>(w, Iw, v2); cross<Z>(hs, a, u3);
 #pragma unroll
-        for (int i = 0; i < 3; i++) FN[K][i] = V{ m*a[i] + U[i].x + u2[i], S[i].x + v2[i] + u3[i] };
+        for (int i = 0; i < 3; i++) FN[K][i] = V{ zadd<Z>(zadd<Z>(zmul<Z>(m, a[i]), U[i].x), u2[i]), zadd<Z>(zadd<Z>(S[i].x, v2[i]), u3[i]) };
     }
 };
 
-template <int K, typename T> struct LinkBwdP {
+template <int K, typename T, bool Z> struct LinkBwdP {
     using V = V2<T>;
     SO100_HD static void run(const T s[6], const T c[6], V FN[6][3], T bias[6]) {
         bias[K] = FN[K][so100g::LINK_AXIS[K]].y;
         if constexpr (K > 0) {
             V P[3]; T t[3];
-            to_parent<K>(FN[K], V(s[K]), V(c[K]), P);
+            to_parent<K, Z>(FN[K], V(s[K]), V(c[K]), P);
             const T fp[3] = { P[0].x, P[1].x, P[2].x };
-            pcross<K>(fp, t);
+            pcross<K, Z>(fp, t);
 #pragma unroll
-            for (int i = 0; i < 3; i++) { P[i].y = P[i].y + t[i]; FN[K-1][i] += P[i]; }
+            for (int i = 0; i < 3; i++) { P[i].y = zadd<Z>(P[i].y, t[i]); FN[K-1][i] += P[i]; }
         }
     }
 };
@@ -409,7 +453,7 @@ template <int K, typename T> struct LinkBwdP {
 // CRBA in pair form: columns K and K-1 of M take the same to_parent / pcross for every frame J < K-1, so they walk those
 // frames together as F = (f_K, f_K-1), N = (n_K, n_K-1); column K takes its first frame (J = K-1) alone, before link K's
 // composite is added into its parent's (column K-1 needs the complete composite of link K-1).
-template <typename T> struct CrbP {
+template <typename T, bool Z> struct CrbP {
     using V = V2<T>;
     // f = axis x h, n = Ic[:, axis] of link K's composite; the diagonal entry of M
     template <int K> SO100_HD static void column(const Composite<T> cmp[6], T f[3], T n[3], T M[21]) {
@@ -421,11 +465,11 @@ template <typename T> struct CrbP {
     // carry (f, n) of one column from frame J1 to frame J1-1 (LinkCrb::walk's step) and read M[K][J1-1]
     template <int K, int J1> SO100_HD static void step(const T s[6], const T c[6], T f[3], T n[3], T M[21]) {
         T fp[3], np[3], t[3];
-        to_parent<J1>(f, s[J1], c[J1], fp);
-        to_parent<J1>(n, s[J1], c[J1], np);
-        pcross<J1>(fp, t);
+        to_parent<J1, Z>(f, s[J1], c[J1], fp);
+        to_parent<J1, Z>(n, s[J1], c[J1], np);
+        pcross<J1, Z>(fp, t);
         f[0] = fp[0]; f[1] = fp[1]; f[2] = fp[2];
-        n[0] = np[0] + t[0]; n[1] = np[1] + t[1]; n[2] = np[2] + t[2];
+        n[0] = zadd<Z>(np[0], t[0]); n[1] = zadd<Z>(np[1], t[1]); n[2] = zadd<Z>(np[2], t[2]);
         M[K*(K+1)/2 + (J1-1)] = n[so100g::LINK_AXIS[J1-1]];
     }
     // the same step for columns K (.x) and K-1 (.y) together, for frames J1 .. 1
@@ -433,11 +477,11 @@ template <typename T> struct CrbP {
         if constexpr (J1 > 0) {
             V fp[3], np[3], t[3];
             const V sv = V(s[J1]), cv = V(c[J1]);
-            to_parent<J1>(F, sv, cv, fp);
-            to_parent<J1>(N, sv, cv, np);
-            pcross<J1>(fp, t);
+            to_parent<J1, Z>(F, sv, cv, fp);
+            to_parent<J1, Z>(N, sv, cv, np);
+            pcross<J1, Z>(fp, t);
 #pragma unroll
-            for (int i = 0; i < 3; i++) { F[i] = fp[i]; N[i] = np[i] + t[i]; }
+            for (int i = 0; i < 3; i++) { F[i] = fp[i]; N[i] = zadd<Z>(np[i], t[i]); }
             constexpr int AXJ = so100g::LINK_AXIS[J1-1];
             M[K*(K+1)/2 + (J1-1)] = N[AXJ].x;
             M[(K-1)*K/2 + (J1-1)] = N[AXJ].y;
@@ -449,12 +493,12 @@ template <typename T> struct CrbP {
         T fa[3], na[3], fb[3], nb[3];
         column<K>(cmp, fa, na, M);
         step<K, K>(s, c, fa, na, M);
-        LinkCrb<K, T>::accumulate(s, c, cmp);
+        LinkCrb<K, T, Z>::accumulate(s, c, cmp);
         column<K-1>(cmp, fb, nb, M);
         V F[3] = { V{ fa[0], fb[0] }, V{ fa[1], fb[1] }, V{ fa[2], fb[2] } };
         V N[3] = { V{ na[0], nb[0] }, V{ na[1], nb[1] }, V{ na[2], nb[2] } };
         walk2<K, K-1>(s, c, F, N, M);
-        if constexpr (K - 1 > 0) LinkCrb<K-1, T>::accumulate(s, c, cmp);
+        if constexpr (K - 1 > 0) LinkCrb<K-1, T, Z>::accumulate(s, c, cmp);
     }
 };
 
@@ -494,44 +538,44 @@ template <typename T, bool PK = true> SO100_HD void arm_trig_update(const T q[6]
 }
 // PK = true: the pair form (LinkFwdP / LinkBwdP / CrbP); PK = false: one 3-vector at a time.  Both compute every value by
 // the same expression (tests/test_pair_bitwise.py: bitwise equal without FMA contraction).
-template <typename T, bool PK = true> SO100_HD void arm_bias(const T v[6], Arm<T>& A) {
+template <typename T, bool PK = true, bool Z = PK> SO100_HD void arm_bias(const T v[6], Arm<T>& A) {
     // RNEA (bias): base at rest, gravity folded in as a base acceleration of +g along world z
     if constexpr (PK) {
         using V = V2<T>;
         V W[3] = { V{ T(0), T(0) }, V{ T(0), T(0) }, V{ T(0), T(0) } };      // (wd, w)
         T a[3] = { T(0), T(0), T(so100g::GRAVITY) };
         V FN[6][3];                                                           // (f, n)
-        LinkFwdP<0, T>::run(A.s, A.c, v, W, a, FN);
-        LinkFwdP<1, T>::run(A.s, A.c, v, W, a, FN);
-        LinkFwdP<2, T>::run(A.s, A.c, v, W, a, FN);
-        LinkFwdP<3, T>::run(A.s, A.c, v, W, a, FN);
-        LinkFwdP<4, T>::run(A.s, A.c, v, W, a, FN);
-        LinkFwdP<5, T>::run(A.s, A.c, v, W, a, FN);
-        LinkBwdP<5, T>::run(A.s, A.c, FN, A.bias);
-        LinkBwdP<4, T>::run(A.s, A.c, FN, A.bias);
-        LinkBwdP<3, T>::run(A.s, A.c, FN, A.bias);
-        LinkBwdP<2, T>::run(A.s, A.c, FN, A.bias);
-        LinkBwdP<1, T>::run(A.s, A.c, FN, A.bias);
-        LinkBwdP<0, T>::run(A.s, A.c, FN, A.bias);
+        LinkFwdP<0, T, Z>::run(A.s, A.c, v, W, a, FN);
+        LinkFwdP<1, T, Z>::run(A.s, A.c, v, W, a, FN);
+        LinkFwdP<2, T, Z>::run(A.s, A.c, v, W, a, FN);
+        LinkFwdP<3, T, Z>::run(A.s, A.c, v, W, a, FN);
+        LinkFwdP<4, T, Z>::run(A.s, A.c, v, W, a, FN);
+        LinkFwdP<5, T, Z>::run(A.s, A.c, v, W, a, FN);
+        LinkBwdP<5, T, Z>::run(A.s, A.c, FN, A.bias);
+        LinkBwdP<4, T, Z>::run(A.s, A.c, FN, A.bias);
+        LinkBwdP<3, T, Z>::run(A.s, A.c, FN, A.bias);
+        LinkBwdP<2, T, Z>::run(A.s, A.c, FN, A.bias);
+        LinkBwdP<1, T, Z>::run(A.s, A.c, FN, A.bias);
+        LinkBwdP<0, T, Z>::run(A.s, A.c, FN, A.bias);
         return;
     } else {
         T w[3] = { T(0), T(0), T(0) }, wd[3] = { T(0), T(0), T(0) }, a[3] = { T(0), T(0), T(so100g::GRAVITY) };
         T f[6][3], n[6][3];
-        LinkFwd<0, T>::run(A.s, A.c, v, w, wd, a, f, n);
-        LinkFwd<1, T>::run(A.s, A.c, v, w, wd, a, f, n);
-        LinkFwd<2, T>::run(A.s, A.c, v, w, wd, a, f, n);
-        LinkFwd<3, T>::run(A.s, A.c, v, w, wd, a, f, n);
-        LinkFwd<4, T>::run(A.s, A.c, v, w, wd, a, f, n);
-        LinkFwd<5, T>::run(A.s, A.c, v, w, wd, a, f, n);
-        LinkBwd<5, T>::run(A.s, A.c, f, n, A.bias);
-        LinkBwd<4, T>::run(A.s, A.c, f, n, A.bias);
-        LinkBwd<3, T>::run(A.s, A.c, f, n, A.bias);
-        LinkBwd<2, T>::run(A.s, A.c, f, n, A.bias);
-        LinkBwd<1, T>::run(A.s, A.c, f, n, A.bias);
-        LinkBwd<0, T>::run(A.s, A.c, f, n, A.bias);
+        LinkFwd<0, T, Z>::run(A.s, A.c, v, w, wd, a, f, n);
+        LinkFwd<1, T, Z>::run(A.s, A.c, v, w, wd, a, f, n);
+        LinkFwd<2, T, Z>::run(A.s, A.c, v, w, wd, a, f, n);
+        LinkFwd<3, T, Z>::run(A.s, A.c, v, w, wd, a, f, n);
+        LinkFwd<4, T, Z>::run(A.s, A.c, v, w, wd, a, f, n);
+        LinkFwd<5, T, Z>::run(A.s, A.c, v, w, wd, a, f, n);
+        LinkBwd<5, T, Z>::run(A.s, A.c, f, n, A.bias);
+        LinkBwd<4, T, Z>::run(A.s, A.c, f, n, A.bias);
+        LinkBwd<3, T, Z>::run(A.s, A.c, f, n, A.bias);
+        LinkBwd<2, T, Z>::run(A.s, A.c, f, n, A.bias);
+        LinkBwd<1, T, Z>::run(A.s, A.c, f, n, A.bias);
+        LinkBwd<0, T, Z>::run(A.s, A.c, f, n, A.bias);
     }
 }
-template <typename T, bool PK = true> SO100_HD void arm_mass(Arm<T>& A) {
+template <typename T, bool PK = true, bool Z = PK> SO100_HD void arm_mass(Arm<T>& A) {
     // CRBA
     Composite<T> cmp[6];
 #pragma unroll
@@ -543,16 +587,16 @@ template <typename T, bool PK = true> SO100_HD void arm_mass(Arm<T>& A) {
         for (int i = 0; i < 6; i++) cmp[k].I[i] = T(so100g::LINK_IORG[k][i]);
     }
     if constexpr (PK) {
-        CrbP<T>::template columns<5>(A.s, A.c, cmp, A.M);
-        CrbP<T>::template columns<3>(A.s, A.c, cmp, A.M);
-        CrbP<T>::template columns<1>(A.s, A.c, cmp, A.M);
+        CrbP<T, Z>::template columns<5>(A.s, A.c, cmp, A.M);
+        CrbP<T, Z>::template columns<3>(A.s, A.c, cmp, A.M);
+        CrbP<T, Z>::template columns<1>(A.s, A.c, cmp, A.M);
     } else {
-        LinkCrb<5, T>::run(A.s, A.c, cmp, A.M);
-        LinkCrb<4, T>::run(A.s, A.c, cmp, A.M);
-        LinkCrb<3, T>::run(A.s, A.c, cmp, A.M);
-        LinkCrb<2, T>::run(A.s, A.c, cmp, A.M);
-        LinkCrb<1, T>::run(A.s, A.c, cmp, A.M);
-        LinkCrb<0, T>::run(A.s, A.c, cmp, A.M);
+        LinkCrb<5, T, Z>::run(A.s, A.c, cmp, A.M);
+        LinkCrb<4, T, Z>::run(A.s, A.c, cmp, A.M);
+        LinkCrb<3, T, Z>::run(A.s, A.c, cmp, A.M);
+        LinkCrb<2, T, Z>::run(A.s, A.c, cmp, A.M);
+        LinkCrb<1, T, Z>::run(A.s, A.c, cmp, A.M);
+        LinkCrb<0, T, Z>::run(A.s, A.c, cmp, A.M);
     }
 }
 template <typename T> SO100_HD void arm_dynamics(const T q[6], const T v[6], Arm<T>& A) {
@@ -869,13 +913,13 @@ SO100_HD void arm_finish(T q[6], T v[6], T qc[6], const T ctrl[6], T ff[6], T fl
     arm_solve_integrate(q, v, qc, ctrl, ff, fl, flags, iters, A, dq, residual);
 }
 
-template <typename T, bool PK = true>
+template <typename T, bool PK = true, bool Z = PK>
 SO100_HD void arm_substep(T q[6], T v[6], T qc[6], const T ctrl[6], T ff[6], T fl[6], unsigned flags, int iters, Arm<T>& A,
                           bool first, T dq[6], T* residual = nullptr) {
     // first substep of an env step: exact sin/cos; later ones: incremental update by the previous substep's increment
     if (first) arm_trig(q, A); else arm_trig_update<T, PK>(q, dq, A);
-    arm_bias<T, PK>(v, A);
-    arm_mass<T, PK>(A);
+    arm_bias<T, PK, Z>(v, A);
+    arm_mass<T, PK, Z>(A);
     arm_finish(q, v, qc, ctrl, ff, fl, flags, iters, A, dq, residual);
 }
 
@@ -888,25 +932,25 @@ template <typename T> struct TaskPoses {
     T jaw_mat[9];          // xmat of Fixed_Jaw, row-major
     T cam_pos[3], cam_mat[9];
 };
-template <int K, typename T> SO100_HD void fk_link(const T s[6], const T c[6], T pos[3], T R[9]) {
+template <int K, bool Z, typename T> SO100_HD void fk_link(const T s[6], const T c[6], T pos[3], T R[9]) {
     // pos += R p_K ; R <- R C_K Rot_K
     const T p[3] = { T(so100g::LINK_P[K][0]), T(so100g::LINK_P[K][1]), T(so100g::LINK_P[K][2]) };
 #pragma unroll
-    for (int i = 0; i < 3; i++) pos[i] += R[3*i]*p[0] + R[3*i+1]*p[1] + R[3*i+2]*p[2];
+    for (int i = 0; i < 3; i++) pos[i] = zadd<Z>(pos[i], zadd<Z>(zadd<Z>(zmul<Z>(R[3*i], p[0]), zmul<Z>(R[3*i+1], p[1])), zmul<Z>(R[3*i+2], p[2])));
 #pragma unroll
     for (int i = 0; i < 3; i++) {          // each row r of R: r <- (r C) Rot  == to_child applied to the row
         T row[3] = { R[3*i], R[3*i+1], R[3*i+2] }, out[3];
-        to_child<K>(row, s[K], c[K], out);
+        to_child<K, Z>(row, s[K], c[K], out);
         R[3*i] = out[0]; R[3*i+1] = out[1]; R[3*i+2] = out[2];
     }
 }
-template <typename T> SO100_HD void task_poses(const T s[6], const T c[6], bool want_cam, TaskPoses<T>& P) {
+template <typename T, bool Z = false> SO100_HD void task_poses(const T s[6], const T c[6], bool want_cam, TaskPoses<T>& P) {
     T pos[3] = { T(0), T(0), T(0) };
     T R[9] = { T(1), T(0), T(0), T(0), T(1), T(0), T(0), T(0), T(1) };
-    fk_link<0>(s, c, pos, R); fk_link<1>(s, c, pos, R); fk_link<2>(s, c, pos, R);
-    fk_link<3>(s, c, pos, R);
+    fk_link<0, Z>(s, c, pos, R); fk_link<1, Z>(s, c, pos, R); fk_link<2, Z>(s, c, pos, R);
+    fk_link<3, Z>(s, c, pos, R);
     P.wrist[0] = pos[0]; P.wrist[1] = pos[1]; P.wrist[2] = pos[2];
-    fk_link<4>(s, c, pos, R);
+    fk_link<4, Z>(s, c, pos, R);
 #pragma unroll
     for (int i = 0; i < 3; i++) P.jaw_pos[i] = pos[i];
 #pragma unroll

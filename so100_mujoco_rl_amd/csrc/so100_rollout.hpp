@@ -153,7 +153,9 @@ __device__ __forceinline__ void cube_from_lds(float (*xc)[64], int col, Cube<flo
 // PK: the arm dynamics in pair form (so100_physics.hpp); the callers choose it where it costs the kernel no scratch
 // LOCAL: the mass matrix and its factor in loop-local storage (see the first half of the substep); the callers choose it where no
 // scratch or spill row of the kernel grows
-template <bool PADS, bool LINKS, bool PK, bool LOCAL, class Hook, class Forget>
+// Z: the arm dynamics and the pose recursions leave out the terms the compiler knows to be zero (so100_physics.hpp: known_zero); the callers
+// switch it on where the pair form runs, every other kernel compiles the text it had
+template <bool PADS, bool LINKS, bool PK, bool LOCAL, bool Z, class Hook, class Forget>
 __device__ __forceinline__ void physics_phase_mw(const SimParams& p, int wave, int lane, EnvState& e, float ctrl[6], float cstale[3],
                                                  Arm<float>& A, const PhaseLds& L, ContactMemo& memo, Prof& prof_, Hook after_first_barrier, Forget forget_caller_state) {
     float (*xq)[64] = L.xq; float (*xc)[64] = L.xc; float (*xb)[64] = L.xb; float (*xa)[64] = L.xa; float (*xk)[64] = L.xk; float (*xm)[64] = L.xm;
@@ -228,14 +230,14 @@ __device__ __forceinline__ void physics_phase_mw(const SimParams& p, int wave, i
         if (LOCAL && wave == 0) {
 #pragma unroll
             for (int i = 0; i < 6; i++) { F.s[i] = A.s[i]; F.c[i] = A.c[i]; }
-            arm_mass<float, PK>(F);
+            arm_mass<float, PK, Z>(F);
             arm_factor<float>(p.flags, F);
             SO100_PROF(4);                                 // CRBA + factor (wave 0)
         } else if (LOCAL && wave == 1) {
             Arm<float> R; float v1[6];
 #pragma unroll
             for (int i = 0; i < 6; i++) { R.s[i] = xq[i][lane]; R.c[i] = xq[6 + i][lane]; v1[i] = xq[12 + i][lane]; }
-            arm_bias<float, PK>(v1, R);
+            arm_bias<float, PK, Z>(v1, R);
 #pragma unroll
             for (int i = 0; i < 6; i++) xb[i][lane] = R.bias[i];
             SO100_PROF(4);                                 // RNEA (wave 1)
@@ -247,7 +249,7 @@ __device__ __forceinline__ void physics_phase_mw(const SimParams& p, int wave, i
 #pragma unroll
                 for (int i = 0; i < 6; i++) { q1[i] = xq[18 + i][lane]; c1[i] = xk[i][lane]; }
             }
-            arm_bias<float, PK>(v1, A);
+            arm_bias<float, PK, Z>(v1, A);
 #pragma unroll
             for (int i = 0; i < 6; i++) xb[i][lane] = A.bias[i];
             if (pads) {                                    // what the contact wave's primal solve needs of q, ctrl and the bias (see "LDS" above)
@@ -259,7 +261,7 @@ __device__ __forceinline__ void physics_phase_mw(const SimParams& p, int wave, i
             }
             SO100_PROF(4);                                 // RNEA (wave 1)
         } else if (wave == 0) {
-            arm_mass<float, PK>(A);
+            arm_mass<float, PK, Z>(A);
             if (pads) {                                    // the contact wave's primal solve needs M itself
 #pragma unroll
                 for (int i = 0; i < 21; i++) xm[i][lane] = A.M[i];
@@ -274,7 +276,7 @@ __device__ __forceinline__ void physics_phase_mw(const SimParams& p, int wave, i
             float v3[6];
 #pragma unroll
             for (int i = 0; i < 6; i++) { A3.s[i] = xq[i][el]; A3.c[i] = xq[6 + i][el]; v3[i] = xq[12 + i][el]; }
-            world_fk<float>(A3.s, A3.c, W3);
+            world_fk<float, Z>(A3.s, A3.c, W3);
             SO100_PROF(10);                                // world FK (wave 3)
             Cube<float> c3b;
 #pragma unroll
@@ -338,7 +340,7 @@ __device__ __forceinline__ void physics_phase_mw(const SimParams& p, int wave, i
                 } else {
 #pragma unroll
                     for (int i = 0; i < 6; i++) { A3.s[i] = xq[i][el]; A3.c[i] = xq[6 + i][el]; }
-                    world_fk<float>(A3.s, A3.c, W3);
+                    world_fk<float, Z>(A3.s, A3.c, W3);
                 }
                 if (padcube) {
 #pragma unroll
@@ -773,7 +775,7 @@ __global__ void __launch_bounds__(64*NW) so100_rollout_fused(SimParams p, float*
             // (pair form: see above.  Loop-local factor: wherever the pair form runs, except Env03 / Env04 -- their task layer is the
             //  largest, and with 21 registers held round the substep loop three values of it are parked in AGPRs)
             constexpr bool PKF = !PADS && FL != 7;
-            physics_phase_mw<PADS, LINKS, PKF, PKF && KIND != 3 && KIND != 4>(p, wave, lane, e, ctx.ctrl, cstale, A, lds, memo, prof_, [&](int sub) {
+            physics_phase_mw<PADS, LINKS, PKF, PKF && KIND != 3 && KIND != 4, PKF>(p, wave, lane, e, ctx.ctrl, cstale, A, lds, memo, prof_, [&](int sub) {
                 if (wave == 3 && sub == 0 && t + 1 < ra.T) {       // wave 0 has consumed xn before this barrier
                     float eps[8];
                     policy_noise(p.env_id_offset + (uint32_t)env, ra.step_counter0 + (uint32_t)(t + 1), p.seed_lo, p.seed_hi, eps);
@@ -790,7 +792,7 @@ __global__ void __launch_bounds__(64*NW) so100_rollout_fused(SimParams p, float*
             if (wave == 0) {
                 e.nsub += p.frame_skip;
                 TaskPoses<float> P;
-                task_poses<float>(A.s, A.c, !reach_kind<KIND>(), P);
+                task_poses<float, PKF>(A.s, A.c, !reach_kind<KIND>(), P);
                 float obs[OD], tobs[OD]; bool term;
                 const float reward = env_step_post<KIND>(e, ctx, ustep, P, cstale, obs, term);
                 const StepResult r = env_step_finish<KIND>(e, reward, term, p, p.env_id_offset + (uint32_t)env, nullptr, start_tab, obs, tobs);

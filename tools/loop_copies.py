@@ -2,7 +2,11 @@
     python tools/loop_copies.py [--targs "1, 8, 4, 32"] [--flags "-DNAME=VALUE ..."] [--keep DIR] [--json]
 Builds a translation unit that instantiates ONE so100_rollout_fused<targs> with the product's HIPFLAGS (read from csrc/Makefile) plus
 -S --cuda-device-only, splits the kernel's ISA into basic blocks and reports, per region and per block, how many instructions are
-VALU / packed VALU / copies (v_mov*, v_accvgpr_*, v_readlane / v_writelane) / LDS / SALU / s_nop / waits:
+VALU / packed VALU / copies (v_mov*, v_accvgpr_*, v_readlane / v_writelane) / LDS / SALU / s_nop / waits, and beside them two
+kinds of issue slot that compute nothing (counted inside the categories above, not in addition to them): `lit`, an s_mov_b32 / s_mov_b64
+of a literal (a constant re-materialised for a packed instruction, which takes no literal operand), and `zero`, fp32 VALU arithmetic
+(mul / add / sub / fma / fmac ..., packed or not) with a literal +0 / -0 source (a product or sum the compiler may not fold without
+fast-math):
   * the substep loop between its barriers: the loop is the shortest cycle of workgroup barriers in the kernel's control-flow graph
     (two per substep, three with pad contacts); region "b1->b2" is the first half of a substep (RNEA || CRBA + factor), "b2->b1" the
     second half, the back edge and the sin/cos update of the next substep;
@@ -17,6 +21,10 @@ import argparse, json, os, re, shutil, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "so100_mujoco_rl_amd", "csrc")
 CATS = ("valu", "pk", "copy", "lds", "salu", "nop", "wait", "other")
+SUBS = ("lit", "zero")                                        # subsets of salu / of valu + pk
+ARITH = re.compile(r"v_(pk_)?(mul|add|sub|subrev|fma|fmac|fmaak|fmamk|mad|mac)_f32")
+NUMBER = re.compile(r"-?(0x[0-9a-fA-F]+|\d+(\.\d*)?(e[-+]?\d+)?)$")
+ZEROS = ("0", "-0", "0.0", "-0.0", "0x0", "0x80000000")
 SIG = ("so100::SimParams, float*, const float*, float*, float*, uint8_t*, uint8_t*, float*, float*, int32_t*, "
        "so100::PolicyWeights, so100::RolloutArgs")
 
@@ -62,6 +70,22 @@ def classify(op):
     return "other"
 
 
+def operands(ins):
+    """the operands of one instruction line, destination first, without trailing modifiers (op_sel:[..], neg_lo:[..], clamp, ...)"""
+    rest = ins.split(None, 1)[1] if " " in ins or "\t" in ins else ""
+    rest = re.sub(r"\s+\w+:\[[^\]]*\]", "", rest)
+    return [o.strip() for o in rest.split(",")]
+
+
+def is_lit(ins):
+    op = ins.split()[0]
+    return op in ("s_mov_b32", "s_mov_b64") and bool(NUMBER.match(operands(ins)[-1].split()[0]))
+
+
+def is_zero(ins):
+    return bool(ARITH.match(ins.split()[0])) and any(o.split()[0] in ZEROS for o in operands(ins)[1:] if o)
+
+
 class Block:
     def __init__(self, name):
         self.name, self.ins, self.succ, self.barrier = name, [], [], False
@@ -70,6 +94,8 @@ class Block:
         for i in self.ins: c[classify(i.split()[0])] += 1
         c["total"] = len(self.ins)
         c["accw"] = sum(i.startswith("v_accvgpr_write") for i in self.ins)
+        c["lit"] = sum(is_lit(i) for i in self.ins)
+        c["zero"] = sum(is_zero(i) for i in self.ins)
         return c
 
 
@@ -182,7 +208,7 @@ def analyse(txt):
 
 
 def total(by, names):
-    c = dict.fromkeys(CATS + ("total", "accw"), 0)
+    c = dict.fromkeys(CATS + SUBS + ("total", "accw"), 0)
     for n in names:
         for k, v in by[n].counts().items(): c[k] += v
     return c
@@ -209,7 +235,7 @@ def summary(txt, usage=None):
 
 
 def fmt(c):
-    return "  ".join(f"{k} {c[k]:4d}" for k in ("total",) + CATS)
+    return "  ".join(f"{k} {c[k]:4d}" for k in ("total",) + CATS + SUBS)
 
 
 def main():
