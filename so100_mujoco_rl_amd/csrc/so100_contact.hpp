@@ -1139,7 +1139,10 @@ __device__ unsigned long long so100_cstats[8];          // calls, iterations, li
 // Fallback stop in fp32.  The pad rows are stiff (1/R = 3e3 against M ~ 0.1): a row's force is D * jar with jar = J.x + b a
 // small difference of O(10) terms, so forces carry a relative round-off of ~3e-4 and rows at a kink may flicker between
 // passes.  TWO consecutive steps of at most 1e-3 relative size without progress in E end the solve (one is not enough: x may
-// sit at a kink whose other side wants to go elsewhere).
+// sit at a kink whose other side wants to go elsewhere).  Both are judged AFTER the pass at their trial point: a small second
+// step that does bring E down has crossed the last kink of a row of them, and the step after it can be large (a pad that
+// touches an airborne cube with four records of which one carries force: 1e-3 m/s and 0.2 rad/s of the cube's h * qacc were
+// lost when the second step ended the solve on its size alone, tests/test_substep_parity.py).
 template <int ND, typename T> SO100_HD T grad_merit(const T g[ND]) {
     T E = T(0);
 #pragma unroll
@@ -1282,7 +1285,7 @@ SO100_HD T primal_newton(const PrimalProblem<ND, T, Store, LINKS>& P, int iters,
 #endif
         const T tol = (f32 ? T(1e-4) : T(1e-11))*(T(1) + T(0.01)*xmax);
         const bool small = dmax < (f32 ? T(1e-3) : T(1e-10))*(T(1) + xmax);
-        if (dmax < tol || onq || (small_prev && small)) {     // converged: the step no longer changes the acceleration
+        if (dmax < tol || onq) {                              // converged: the step no longer changes the acceleration
 #pragma unroll
             for (int i = 0; i < ND; i++) x[i] += dx[i];
             last = T(0);
@@ -1337,6 +1340,7 @@ SO100_HD T primal_newton(const PrimalProblem<ND, T, Store, LINKS>& P, int iters,
             // next step tells -- a second small one ends the solve, a large one carries on from the trial point.
 #pragma unroll
             for (int i = 0; i < ND; i++) { x[i] = xn[i]; g[i] = gn[i]; }
+            if (small_prev) { last = T(0); break; }           // the second in a row, itself evaluated: working precision
             E0 = E1; small_prev = true;
             continue;
         }

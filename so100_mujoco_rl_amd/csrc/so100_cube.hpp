@@ -63,14 +63,15 @@ template <typename T> struct CubeRows {
     T b[4][4], R[4], arinv[4][4];
 };
 
-// row (S,E): jar = b + J x,  J = [dir_E ; rl[S] x dl[E]];  accumulates cost / gradient / Hessian
+// row (S,E): jar = b + J x,  J = [dir_E ; rl[S] x dl[E]];  accumulates cost / gradient / Hessian and the row's bit of the active set
 template <int S, int E, typename T>
-SO100_HD void cube_row_accum(const CubeRows<T>& r, const T x[6], T& cost, T g[6], T Hm[21], bool want_gh) {
+SO100_HD void cube_row_accum(const CubeRows<T>& r, const T x[6], T& cost, T g[6], T Hm[21], bool want_gh, unsigned& onset) {
     constexpr int A = EdgeAxis<E>::A; constexpr bool pos = EdgeAxis<E>::pos;
     T ja[3]; cross(r.rl[S], r.dl[E], ja);
     T jar = r.b[S][E] + edge_dot<E>(x);
     jar += ja[0]*x[3]; jar += ja[1]*x[4]; jar += ja[2]*x[5];
     const bool on = r.act[S] && jar < T(0);
+    onset |= on ? 1u << (4*S + E) : 0u;
     const T D = on ? r.arinv[S][E] : T(0);             // 1/R of the row when active
     cost += T(0.5)*D*jar*jar;
     if (want_gh) {
@@ -88,7 +89,8 @@ SO100_HD void cube_row_accum(const CubeRows<T>& r, const T x[6], T& cost, T g[6]
     }
 }
 template <typename T>
-SO100_HD T cube_rows_eval(const CubeRows<T>& r, const T x[6], T g[6], T Hm[21], bool want_gh) {
+SO100_HD T cube_rows_eval(const CubeRows<T>& r, const T x[6], T g[6], T Hm[21], bool want_gh, unsigned& onset) {
+    onset = 0u;                                        // bit 4 S + E: row (S, E) is active at x
     const T m = T(so100g::CUBE_MASS), I = T(so100g::CUBE_INERTIA);
     T cost = T(0.5)*(m*(x[0]*x[0] + x[1]*x[1] + x[2]*x[2]) + I*(x[3]*x[3] + x[4]*x[4] + x[5]*x[5]));
     if (want_gh) {
@@ -97,8 +99,8 @@ SO100_HD T cube_rows_eval(const CubeRows<T>& r, const T x[6], T g[6], T Hm[21], 
 #pragma unroll
         for (int i = 0; i < 3; i++) { g[i] = m*x[i]; g[3+i] = I*x[3+i]; Hm[SO100_TRI(i, i)] = m; Hm[SO100_TRI(3+i, 3+i)] = I; }
     }
-#define SO100_ACC(S) cube_row_accum<S, 0>(r, x, cost, g, Hm, want_gh); cube_row_accum<S, 1>(r, x, cost, g, Hm, want_gh); \
-                     cube_row_accum<S, 2>(r, x, cost, g, Hm, want_gh); cube_row_accum<S, 3>(r, x, cost, g, Hm, want_gh);
+#define SO100_ACC(S) cube_row_accum<S, 0>(r, x, cost, g, Hm, want_gh, onset); cube_row_accum<S, 1>(r, x, cost, g, Hm, want_gh, onset); \
+                     cube_row_accum<S, 2>(r, x, cost, g, Hm, want_gh, onset); cube_row_accum<S, 3>(r, x, cost, g, Hm, want_gh, onset);
     SO100_ACC(0) SO100_ACC(1) SO100_ACC(2) SO100_ACC(3)
 #undef SO100_ACC
     return cost;
@@ -241,7 +243,8 @@ SO100_HD void cube_solve(Cube<T>& c, unsigned flags, int iters, const CubePrep<T
 #if !defined(__HIPCC__)
                 g_dbg_newton_iters++;
 #endif
-                const T cost = cube_rows_eval(r, x, g, Hm, true);
+                unsigned on0, on1;
+                const T cost = cube_rows_eval(r, x, g, Hm, true, on0);
 #pragma unroll
                 for (int i = 0; i < 6; i++) dx[i] = -g[i];
                 ldl6(Hm, Dinv);
@@ -256,25 +259,24 @@ SO100_HD void cube_solve(Cube<T>& c, unsigned flags, int iters, const CubePrep<T
                     for (int i = 0; i < 6; i++) x[i] += dx[i];
                     break;
                 }
-                // end game: a full Newton step, accepted when it achieves the decrease a quadratic model predicts (near the
-                // optimum the exact fp32 line search below dithers for up to 9 evaluations per substep); otherwise fall through
-                // Full Newton step first.  It is accepted when it achieves (80 % of) the decrease g.dx/2 that the quadratic
-                // model predicts; if the cost at x + dx even MATCHES the model, no row switched on or off along the step, the
-                // problem was quadratic and x + dx is its exact minimiser: stop without a confirming iteration (a cube that
-                // is settling after a reset would otherwise pay two full evaluations per substep and hold up its wave).
+                // Full Newton step first.  It is accepted when it achieves (80 % of) the decrease g.dx/2 that the quadratic model
+                // predicts.  If the SAME rows are active at x and at x + dx, the cost is one quadratic on a region that holds both,
+                // x + dx is its exact minimiser and, the cost being convex, the optimum: stop without a confirming iteration (a cube
+                // that is settling after a reset would otherwise pay two full evaluations per substep and hold up its wave).  The
+                // active sets are compared bit by bit: that the cost at x + dx matches the model is no substitute -- a row that switches
+                // on along the step adds only second order to the cost, and the cube's inertia (5e-7 kg m^2) turns a cost difference
+                // at fp32 round-off into 100 rad/s^2 (a sliding, tumbling cube: tests/test_substep_parity.py; fp64 lost 2e-6 m/s).
                 // Otherwise: exact line search (big active-set changes: impacts, tumbling).
                 {
                     T xn[6], gt[6], Ht[21];
 #pragma unroll
                     for (int i = 0; i < 6; i++) xn[i] = x[i] + dx[i];
-                    const T cn = cube_rows_eval(r, xn, gt, Ht, false);
+                    const T cn = cube_rows_eval(r, xn, gt, Ht, false, on1);
                     const T gdx = g[0]*dx[0] + g[1]*dx[1] + g[2]*dx[2] + g[3]*dx[3] + g[4]*dx[4] + g[5]*dx[5];
                     if (cn <= cost + T(0.4)*gdx) {
 #pragma unroll
                         for (int i = 0; i < 6; i++) x[i] = xn[i];
-                        const T model = cost + T(0.5)*gdx;
-                        // (the second term is the round-off of the two cost evaluations themselves)
-                        if (tabs(cn - model) <= (sizeof(T) == 4 ? T(1e-5) : T(1e-9))*tabs(gdx) + (sizeof(T) == 4 ? T(4e-7) : T(1e-15))*cost) break;
+                        if (on1 == on0) break;
                         continue;
                     }
                 }

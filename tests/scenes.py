@@ -165,6 +165,33 @@ def link_cube_states(n, seed, pen=(0.0002, 0.003)):
     return out
 
 
+def floor_cube_states(n, seed, pen=(5e-5, 2e-3)):
+    """arm poses with a finger pad 0.5 .. 30 mm above the floor and the cube LYING on the floor (z = 0.0099) at a random yaw, walked towards
+    one of the 8 pads along a random horizontal direction until the oracle reports a pad/cube record (kind 2) that is pen[0] .. pen[1]
+    metres deep: the pad knocks the cube, which then slides and tumbles on one to four corners (what F_CONTACT5 training meets)"""
+    rs = np.random.RandomState(seed); out = []
+    while len(out) < n:
+        q = JNT_LO + (JNT_HI - JNT_LO)*rs.rand(6)
+        d = fresh(q); L.so100o_kinematics(C.byref(M), C.byref(d))
+        frames = pad_frames(d)
+        z = min(c[2] - (np.abs(R[2])*h).sum() for c, R, h in frames)
+        if not 0.0005 < z < 0.03:
+            continue
+        centre = frames[rs.randint(8)][0]
+        yaw = rs.uniform(-np.pi, np.pi); phi = rs.uniform(-np.pi, np.pi)
+        qc = np.array([np.cos(yaw/2), 0.0, 0.0, np.sin(yaw/2)]); u = np.array([np.cos(phi), np.sin(phi), 0.0])
+        for s in np.arange(60, -1, -1)*0.0005:             # 30 mm .. 0 in 0.5 mm steps: the first offset at which the pad touches
+            c = np.array([centre[0], centre[1], 0.0099]) + u*s
+            dd = fresh(q, cube=c, cquat=qc)
+            L.so100o_forward(C.byref(M), C.byref(dd), C5, -1)
+            deep = [dd.con[i].dist for i in range(dd.ncon) if dd.con[i].kind == 2]
+            if deep:
+                if -pen[1] < min(deep) < -pen[0]:
+                    out.append((q, c, qc))
+                break
+    return out
+
+
 # ---- batches: (qpos [n, 13], qvel [n, 12], act [n, 6]) ------------------------------------------------------------------------
 def floor_batch(n, seed, band=0.002):
     """arm poses with the lowest pad corner within `band` of the floor, moderate joint velocities, cube resting on the floor"""
@@ -213,6 +240,18 @@ def link_cube_batch(n, seed):
     for i, (q, c, qc) in enumerate(link_cube_states(n, seed + 3)):
         qpos[i, :6] = q; qpos[i, 6:9] = c; qpos[i, 9:13] = qc
         qvel[i, :6] = rs.randn(6)*0.3; qvel[i, 6:9] = rs.randn(3)*0.02
+    act = rs.uniform(-1, 1, (n, 6)).astype(np.float32)
+    return qpos, qvel, act
+
+
+def floor_cube_batch(n, seed):
+    """the cube on the floor at a random yaw with a finger pad 0.05-2 mm inside it (floor_cube_states): random joint velocities and actions,
+    the cube at rest -- cube/floor, pad/cube and sometimes pad/floor records in one coupled solve, then a cube sliding on 1-4 corners"""
+    rs = np.random.RandomState(seed)
+    qpos = np.zeros((n, 13)); qvel = np.zeros((n, 12))
+    for i, (q, c, qc) in enumerate(floor_cube_states(n, seed + 11)):
+        qpos[i, :6] = q; qpos[i, 6:9] = c; qpos[i, 9:13] = qc
+        qvel[i, :6] = rs.randn(6)*0.3
     act = rs.uniform(-1, 1, (n, 6)).astype(np.float32)
     return qpos, qvel, act
 

@@ -3,7 +3,8 @@ oracle: EVERY env in EVERY substep -- same contact count, same contact features 
 so100o_contact.feat), h * qacc within the stated fp32 bound, solver residual (tests/substep_harness.py; the host-instantiation
 twin of this test is tests/test_substep_parity.py).  All four step kernels are covered through the batch size: 4-wave latency
 kernel with 16 / 32 / 64 envs per workgroup (4 / 2 / 1 cooperating contact lanes per env) and the one-wave throughput kernel; plus
-a flag set WITHOUT a compile-time instantiation (run-time-flags kernels so100_step_mw / so100_step_fused<K, -1>).
+a flag set WITHOUT a compile-time instantiation (run-time-flags kernels so100_step_mw / so100_step_fused<K, -1>).  The cube pushed along
+the floor by a finger pad (mixed contact sets, then a cube sliding and tumbling on 1-4 corners) runs on the 4-wave, one-wave and <K, -1> kernels.
 
 Every case runs at the shipped solver settings (2, 20) and at (4, 30), with the same bounds (the residual check of the 2-sweep leg is
 split: tests/substep_harness.py check_residual).  Stated fp32 bound on h * qacc from identical fp32-rounded states (h = 2 ms):
@@ -18,8 +19,8 @@ pytestmark = pytest.mark.gpu
 import substep_harness as SH                              # noqa: E402
 from gpu_support import inject_state, make_sim            # noqa: E402
 from oracle import so100_oracle as O                      # noqa: E402  (the checker)
-from scenes import (C5, LCUBE, LINKS, REFP, SHIPPED, UNINSTANTIATED, floor_batch, grasp_batch, idle_batch, link_cube_batch,   # noqa: E402
-                    wrist_first_batch)
+from scenes import (C5, LCUBE, LINKS, PROXIES, REFP, SHIPPED, UNINSTANTIATED, floor_batch, floor_cube_batch, grasp_batch,   # noqa: E402
+                    idle_batch, link_cube_batch, wrist_first_batch)
 
 
 class HipDevice:
@@ -133,3 +134,31 @@ def _link_cube_per_substep(n, iters):
         qpos, qvel, act = grasp_batch(m, 2)
         T = SH.run_substep_parity(HipDevice(n, m, flags, iters), qpos, qvel, act, flags, 32, f"HIP {iters} n={n} all proxies + grasp")
         SH.check_tally(T, m*32//4, m*32//5, iters=iters)
+
+
+FLOOR_CUBE_CASES = [(64, C5), (16384 + 64, C5), (64, C5 | PROXIES)]      # 4-wave kernel, 16 envs per workgroup / one-wave kernel / <K, -1> kernels
+
+
+@pytest.mark.parametrize("n,flags", FLOOR_CUBE_CASES)
+def test_floor_cube_per_substep(n, flags):
+    _floor_cube_per_substep(n, flags, (4, 30))
+
+
+@pytest.mark.parametrize("n,flags", FLOOR_CUBE_CASES)
+def test_floor_cube_per_substep_at_shipped_settings(n, flags):
+    """test_floor_cube_per_substep at the shipped solver settings (solver_iters, contact_iters) = SHIPPED = (2, 20), with the same bounds"""
+    _floor_cube_per_substep(n, flags, SHIPPED)
+
+
+def _floor_cube_per_substep(n, flags, iters):
+    """The cube lying on the floor at a random yaw, knocked by a finger pad (scenes.floor_cube_batch: what F_CONTACT5 training and bench.py's
+    env01_contact meet): cube/floor, pad/cube and pad/floor records in one coupled 12-unknown solve, then the cube/floor Newton alone on a
+    cube that slides and tumbles on 1-4 corners.  The same conditions and bounds as the host twin's
+    tests/test_substep_parity.py::test_floor_cube_per_substep_host_fp32, against the oracle: both classes populated, knife-edge poses (pad-free
+    ones included) <= 2 %, h * qacc within 2e-6 without pad contact and 5e-5 / 1e-2 relative with, the cube's angular h * alpha within the
+    same at the cube's corner (SH.check_moving_cube)."""
+    m, nsub = 64, 24
+    qpos, qvel, act = floor_cube_batch(m, 0)
+    T = SH.run_substep_parity(HipDevice(n, m, flags, iters), qpos, qvel, act, flags, nsub, f"HIP {iters} n={n} flags={flags} cube on the floor")
+    SH.check_tally(T, m*nsub//3, m*nsub//4, iters=iters)
+    SH.check_moving_cube(T)

@@ -19,7 +19,7 @@ import pytest
 import substep_harness as SH
 from hostlibs import hostcheck, ptr
 from oracle import so100_oracle as O
-from scenes import JS, LCUBE, LINKS, SHIPPED, floor_batch, grasp_batch, link_cube_batch, wrist_first_batch
+from scenes import C5, JS, LCUBE, LINKS, PROXIES, SHIPPED, floor_batch, floor_cube_batch, grasp_batch, link_cube_batch, wrist_first_batch
 
 
 @pytest.fixture(scope="module")
@@ -161,3 +161,38 @@ def _link_cube_per_substep_host_fp32(H, iters):
     qpos, qvel, act = grasp_batch(16, 2)
     T = SH.run_substep_parity(HostDevice(H, 16, flags, iters), qpos, qvel, act, flags, 32, f"host fp32 {iters}, all proxies + grasp")
     SH.check_tally(T, min_contact=16*32//4, min_coupled=16*32//5, iters=iters)
+
+
+# ---- the cube lying on the floor, knocked by a finger pad: mixed contact sets, then a cube that slides and tumbles on 1-4 corners ----------
+def test_floor_cube_per_substep_host_fp32(H):
+    _floor_cube_per_substep_host_fp32(H, (4, 30))
+
+
+def test_floor_cube_per_substep_host_fp32_at_shipped_settings(H):
+    """test_floor_cube_per_substep_host_fp32 at the shipped solver settings (solver_iters, contact_iters) = SHIPPED = (2, 20), with the same bounds"""
+    _floor_cube_per_substep_host_fp32(H, SHIPPED)
+
+
+def _floor_cube_per_substep_host_fp32(H, iters):
+    """What F_CONTACT5 training and bench.py's env01_contact meet: cube/floor, pad/cube and pad/floor records in ONE coupled 12-unknown
+    solve, then -- the pad gone -- the cube/floor Newton of so100_cube.hpp alone on a cube that moves on 1-4 corners.  Both classes must be
+    populated (check_tally's minima, check_moving_cube's), a pad-free pose whose corner count is decided inside fp32 round-off counts as
+    knife-edge under the same 2 % cap, and the moving cube is held to the bounds of every other pair: 2e-6 without pad contact, 5e-5 and 1e-2
+    relative with; its angular h * alpha to the same at the cube's corner (check_moving_cube).
+    Measured, seeds 0-4, the same at both settings (per 1536 pairs): pad contact 600-749, coupled 565-726, pad-free moving 619-767, on 1-3
+    corners 374-497, knife-edge 1-5; worst |d(h qacc)| pad-free 3.5e-7 .. 9.6e-7, with pad contact 1.6e-6 .. 3.5e-6 (relative 2e-4); worst
+    |d(h alpha)| pad-free 1.1e-6 .. 5.5e-6 rad/s, with pad contact 3.4e-5 .. 8.4e-5 rad/s.  Before the cube/floor Newton compared active
+    sets instead of costs to stop early: pad-free 7.4e-5 .. 9.7e-4 m/s and 1.4e-2 .. 3.7e-2 rad/s."""
+    n, nsub = 64, 24
+    qpos, qvel, act = floor_cube_batch(n, 0)
+    T = SH.run_substep_parity(HostDevice(H, n, C5, iters), qpos, qvel, act, C5, nsub, f"host fp32 {iters}, cube on the floor")
+    SH.check_tally(T, min_contact=n*nsub//3, min_coupled=n*nsub//4, iters=iters)
+    SH.check_moving_cube(T)
+    # every proxy pair switched on as well: the run-time-flags path.  (Seed 1 holds, in env 4 at substep 6, the pad that touches an airborne
+    # cube with four records of which one carries force: 1.1e-3 m/s and 0.17 rad/s off while primal_newton's fp32 fallback judged its second
+    # small step by size alone; 1.2e-6 and 2.8e-5 now.  Measured: pad contact 379, coupled 243, pad-free moving 153, on 1-3 corners 159 of 576.)
+    n, flags = 24, C5 | PROXIES
+    qpos, qvel, act = floor_cube_batch(n, 1)
+    T = SH.run_substep_parity(HostDevice(H, n, flags, iters), qpos, qvel, act, flags, nsub, f"host fp32 {iters}, cube on the floor + all proxies")
+    SH.check_tally(T, min_contact=n*nsub//3, min_coupled=n*nsub//4, iters=iters)
+    SH.check_moving_cube(T)
