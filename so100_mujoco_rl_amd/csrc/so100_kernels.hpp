@@ -138,7 +138,7 @@ __global__ void __launch_bounds__(256) so100_step_mw(SimParams p, StepPtrs io) {
     Arm<float> A; Prof prof_;
     const PhaseLds lds{ xq, xc, xb, cbuf, xa, xk, xm, pbuf, PADS ? xw : nullptr };
     ContactMemo memo;                                             // (reset by physics_phase_mw: the memory lives for the env step's substeps)
-    physics_phase_mw<PADS, LINKS, !PADS && FL != 7, !PADS && FL != 7, !PADS && FL != 7>(p, wave, lane, e, ctx.ctrl, cstale, A, lds, memo, prof_, [](int) {}, [&]() {
+    physics_phase_mw<PADS, LINKS, !PADS && FL != 7, !PADS && FL != 7, !PADS && FL != 7, false>(p, wave, lane, e, ctx.ctrl, cstale, A, lds, memo, prof_, [](int) {}, [&]() {
         ctx = StepCtx{};
 #pragma unroll
         for (int k = 0; k < 8; k++) u[k] = 0.0f;
@@ -225,14 +225,14 @@ template <int KIND> struct KindOps {
     static hipError_t init(int n, float* state);
     static hipError_t rollout(const SimParams& prm, float* state, const float* start_tab, const RolloutPtrs& io, const PolicyWeights& pw, const RolloutArgs& ra, hipStream_t st);
 #ifdef SO100_ROLLOUT_PROF
-    static int prof_read(long long* out48);       // the cycle counters live in the kind's own code object
+    static int prof_read(long long* out64);       // the cycle counters live in the kind's own code object
     static int prof_read_wg(long long* wg4096, int* env32768);
     static int prof_read_hist(unsigned long long* hist48, int reset);
 #endif
 };
 #ifdef SO100_ROLLOUT_PROF
-template <int KIND> int KindOps<KIND>::prof_read(long long* out48) {
-    return hipMemcpyFromSymbol(out48, HIP_SYMBOL(so100_prof), sizeof(long long)*48) == hipSuccess ? 0 : -1;
+template <int KIND> int KindOps<KIND>::prof_read(long long* out64) {
+    return hipMemcpyFromSymbol(out64, HIP_SYMBOL(so100_prof), sizeof(long long)*64) == hipSuccess ? 0 : -1;
 }
 template <int KIND> int KindOps<KIND>::prof_read_hist(unsigned long long* h, int reset) {
     if (hipMemcpyFromSymbol(h, HIP_SYMBOL(so100_prof_hist), sizeof(unsigned long long)*48) != hipSuccess) return -1;

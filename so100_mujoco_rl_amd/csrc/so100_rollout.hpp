@@ -7,7 +7,8 @@
 //   physics phase: the same fused env step as so100_step_fused (reward -> ctrl -> 16 substeps -> obs -> TimeLimit ->
 //                 auto-reset) for env = lane of wave 0, with each substep's RNEA bias force computed concurrently on
 //                 wave 1 and, when the cube is simulated, its free-body / floor-contact substep on wave 2 (two workgroup
-//                 barriers per substep; sin/cos, q-dot, the bias and the cube state cross through LDS).
+//                 barriers per substep; sin/cos, q-dot, the bias and the cube state cross through LDS).  In the contact-disabled variants
+//                 the action-independent half of the FIRST substep runs on waves 1 and 2 while wave 0 still samples (physics_phase_mw: PRE).
 // The env state lives in wave 0's registers across all T steps (loaded once, stored once per launch), the
 // observation goes to the next policy phase through LDS, and the only per-step HBM traffic is the rollout-buffer row
 // (obs | action | reward | done | value | logp = (obs_dim+10) words per env).  Compared with one policy launch + one
@@ -32,7 +33,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // Optional cycle accounting of the persistent kernel's phases (tools/rollout_prof.py builds a side library with
 // -DSO100_ROLLOUT_PROF; the product library compiles these to nothing).  Slots: see tools/rollout_prof.py.
 #ifdef SO100_ROLLOUT_PROF
-__device__ long long so100_prof[48];
+__device__ long long so100_prof[64];
 __device__ long long so100_prof_wg[1024*4];    // per workgroup: wave 0 total, wave 3 narrowphase, wave 3 contact Newton, wave 0 barrier-3 wait
 __device__ int so100_prof_env[16384*2];        // per env: row passes of the contact Newton, substeps with a pad contact (this launch)
 // per (workgroup, substep): [0..15] histogram of the slowest lane's gradient + Hessian passes (where any lane solved), [16..32] histogram of the number of
@@ -40,7 +41,7 @@ __device__ int so100_prof_env[16384*2];        // per env: row passes of the con
 // count (970 / 140 / 520 / 300 per pass type), [38] (workgroup, substep) pairs with a solve, [39] all pairs, [40] sum over ENVS of that estimate
 __device__ unsigned long long so100_prof_hist[48];
 struct Prof {
-    long long t[12] = {}, c = __builtin_readcyclecounter();
+    long long t[16] = {}, c = __builtin_readcyclecounter();
     int work = 0, insub = 0, sub = 0;
     // wave 3, once per substep (all its lanes): `sub` holds this substep's typed pass counts of the lane's env (0 if it did not solve)
     __device__ __forceinline__ void substep_stats(bool solved, bool first_of_env) {
@@ -64,10 +65,10 @@ struct Prof {
         sub = 0;
     }
     __device__ __forceinline__ void mark(int slot) { const long long n = __builtin_readcyclecounter(); t[slot] += n - c; c = n; }
-    __device__ __forceinline__ void flush(int base, bool who) const { if (who) for (int i = 0; i < 12; i++) so100_prof[base + i] = t[i]; }
+    __device__ __forceinline__ void flush(int base, bool who) const { if (who) for (int i = 0; i < 16; i++) so100_prof[base + i] = t[i]; }
     __device__ __forceinline__ void flush_wg(int wave, int lane, int env, bool live) const {
         if (blockIdx.x < 1024 && lane == 0) {
-            long long tot = 0; for (int i = 0; i < 12; i++) tot += t[i];
+            long long tot = 0; for (int i = 0; i < 16; i++) tot += t[i];
             if (wave == 0) { so100_prof_wg[blockIdx.x*4 + 0] = tot; so100_prof_wg[blockIdx.x*4 + 3] = t[8]; }
             if (wave == 3) { so100_prof_wg[blockIdx.x*4 + 1] = t[4] + t[10]; so100_prof_wg[blockIdx.x*4 + 2] = t[6] + t[11]; }
         }
@@ -118,6 +119,8 @@ struct Prof {
 // q rows of xq (18-23) carry, from wave 1 to the contact wave, the arm's smooth force tau (xa 0-5), the limit rows' constants clv (xa 6-11) and
 // sg / R_limit (xq 18-23): wave 1 forms them behind RNEA (it is the short leg of that half), the contact wave then needs no q, ctrl or bias.
 // xm [21][64] = the arm's mass matrix (packed lower, unfactored), published by wave 0 before it factorises it in place.
+// With PRE (no pad contacts: nothing publishes M) the xm pointer carries xf [21][64] instead, an array of its own = the LDL^T factor of substep 0 (15 strict-lower entries of L row by row, then Dinv), from the wave that
+// factorised it beside the policy heads to wave 0 (see PRE below).
 // xw [36][64] (nullable) = the six joint axes z_k and screw terms o_k x z_k in the world frame (all the solve needs of the world FK), from the
 // contact wave's detection to its solve; without it the solve rebuilds the frames from sin / cos (330 instructions per substep in contact).
 struct PhaseLds { float (*xq)[64]; float (*xc)[64]; float (*xb)[64]; float* cbuf; float (*xa)[64]; float (*xk)[64]; float (*xm)[64]; unsigned char* pbuf; float (*xw)[64]; };
@@ -155,7 +158,13 @@ __device__ __forceinline__ void cube_from_lds(float (*xc)[64], int col, Cube<flo
 // scratch or spill row of the kernel grows
 // Z: the arm dynamics and the pose recursions leave out the terms the compiler knows to be zero (so100_physics.hpp: known_zero); the callers
 // switch it on where the pair form runs, every other kernel compiles the text it had
-template <bool PADS, bool LINKS, bool PK, bool LOCAL, bool Z, class Hook, class Forget>
+// PRE: substep 0's first half is not run here.  Exact sin/cos, the mass matrix, its factor and the RNEA bias are functions of (q, v) at the
+// start of the env step alone; a caller whose waves 1 and 2 would otherwise idle (the rollout kernel, while wave 0 samples the action) runs
+// them there with the same helpers and switches and leaves s, c in xq, the bias in xb and the factor where L.xm points (xf, see "LDS" above).
+// Substep 0 is then peeled: ONE barrier, wave 0 solves and integrates, and the loop runs substeps 1 ... as it is.  `after_first_barrier(0)`
+// moves behind the first barrier of substep 1 (behind the peeled barrier when frame_skip = 1).  so100_step_mw gets its action from
+// outside and has nothing to overlap: it compiles the text it had.
+template <bool PADS, bool LINKS, bool PK, bool LOCAL, bool Z, bool PRE, class Hook, class Forget>
 __device__ __forceinline__ void physics_phase_mw(const SimParams& p, int wave, int lane, EnvState& e, float ctrl[6], float cstale[3],
                                                  Arm<float>& A, const PhaseLds& L, ContactMemo& memo, Prof& prof_, Hook after_first_barrier, Forget forget_caller_state) {
     float (*xq)[64] = L.xq; float (*xc)[64] = L.xc; float (*xb)[64] = L.xb; float (*xa)[64] = L.xa; float (*xk)[64] = L.xk; float (*xm)[64] = L.xm;
@@ -197,11 +206,42 @@ __device__ __forceinline__ void physics_phase_mw(const SimParams& p, int wave, i
     // (Tried: letting wave 2 run the cube's 16 substeps back to back ahead of the arm when no pad can touch it.  A workgroup
     // barrier needs every wave, so the others simply waited for it at the first one: 72 -> 101 us per step.  The cube stays in
     // step with the arm: detection + row set-up in the first half-substep, Newton in the second.)
+    static_assert(!PRE || (LOCAL && !PADS), "the pre-computed first half is written for the loop-local factor without pad contacts");
+    if constexpr (PRE) {
+        __syncthreads();                                   // s, c, the bias and the factor of substep 0 are in LDS
+        SO100_PROF(15);                                    // substep 0's one barrier wait
+        if (p.frame_skip == 1) after_first_barrier(0);
+        if (wave == 0) {
+            Arm<float> F0; float tau[6], acc0[6];
+#pragma unroll
+            for (int i = 0; i < 6; i++) { A.s[i] = xq[i][lane]; A.c[i] = xq[6 + i][lane]; F0.bias[i] = xb[i][lane]; F0.Dinv[i] = xm[15 + i][lane]; }
+#pragma unroll
+            for (int i = 1; i < 6; i++)
+#pragma unroll
+                for (int k = 0; k < i; k++) F0.M[SO100_TRI(i, k)] = xm[SO100_TRI(i - 1, k)][lane];
+            // arm_tau, rounded as the substep loop rounds it.  There kp*u is loop-invariant: the compiler hoists the rounded product and
+            // contracts the rest round it, f = fma(-kv, v, fma(-kp, q, kp*u)).  Outside the loop it fused kp*u instead (fma(kp, u, -(kp*q))):
+            // one ulp in the servo force, found in the output dumps.  Written out, so that substep 0 keeps the bits it had inside the loop.
+#pragma unroll
+            for (int i = 0; i < 6; i++) {
+                const float u = tclamp(ctrl[i], (float)-so100g::ACT_CTRL, (float)so100g::ACT_CTRL), ku = (float)so100g::ACT_KP*u;
+                float f = __builtin_fmaf(-(float)so100g::ACT_KP, e.q[i], ku);
+                f = __builtin_fmaf(-(float)so100g::ACT_KV[i], e.v[i], f);
+                tau[i] = tclamp(f, (float)-so100g::ACT_FORCE, (float)so100g::ACT_FORCE) - F0.bias[i];
+            }
+#pragma unroll
+            for (int i = 0; i < 6; i++) acc0[i] = tau[i];
+            ldl6_solve<float>(F0.M, F0.Dinv, acc0);
+            SO100_PROF(6);                                 // solve (wave 0)
+            arm_integrate<float>(e.q, e.v, e.qc, acc0, dq);
+            SO100_PROF(9);                                 // integrate
+        }
+    }
 #pragma unroll 1
-    for (int sub = 0; sub < p.frame_skip; sub++) {
+    for (int sub = PRE ? 1 : 0; sub < p.frame_skip; sub++) {
         if (wave == 0) {
             // sin/cos: exact at the first substep, then rotated by the integration increment (arm_substep does the same)
-            if (sub == 0) arm_trig<float>(e.q, A); else arm_trig_update<float, PK>(e.q, dq, A);
+            if (!PRE && sub == 0) arm_trig<float>(e.q, A); else arm_trig_update<float, PK>(e.q, dq, A);
 #pragma unroll
             for (int i = 0; i < 6; i++) { xq[i][lane] = A.s[i]; xq[6 + i][lane] = A.c[i]; xq[12 + i][lane] = e.v[i]; }
             if (pads) {
@@ -213,7 +253,7 @@ __device__ __forceinline__ void physics_phase_mw(const SimParams& p, int wave, i
         if (padcube && wave == 2 && sub > 0) cube_to_lds(xc, lane, cb);       // the cube's pose for this substep's narrowphase / coupled solve
         __syncthreads();
         SO100_PROF(3);                                     // barrier 1 wait
-        after_first_barrier(sub);
+        after_first_barrier(PRE && sub == 1 ? 0 : sub);
         // ---- first half of the substep: everything that does not need the other waves' results
         WorldFK<float> W3; Arm<float> A3; ContactsLds<float> cs3{ L.cbuf, el, L.pbuf, part3, np3 };     // contact wave only
         cs3.prev_n = memo.prev_n;
@@ -599,7 +639,6 @@ __global__ void __launch_bounds__(64*NW) so100_rollout_fused(SimParams p, float*
     static_assert(!XW || MAXPADC*CF*64 + 36*64 <= MAXC*CF*64, "joint frames must fit in the unused tail of the contact store");
     float (*xw)[64] = XW ? reinterpret_cast<float (*)[64]>(pool + MAXPADC*CF*64) : nullptr;
     constexpr bool PADS = FL < 0 || (FL & (int)F_ANY_CONTACT) != 0;
-    // (the arm dynamics in pair form unless that costs scratch: the contact variants and FL = 7 keep the scalar form)
     constexpr bool LINKS = FL < 0 || (FL & (int)F_ANY_LINKS) != 0;
     __shared__ float xa[PADS ? 15 : 1][64];                       // pad contacts: the contact wave's accelerations, contact code, residual, set signature
     __shared__ float xk[PADS ? 12 : 1][64];                       //               ctrl and arm warm start of the env step
@@ -608,6 +647,16 @@ __global__ void __launch_bounds__(64*NW) so100_rollout_fused(SimParams p, float*
     __shared__ float xc[24][64];                                  //                cube state hand-over (wave 0 <-> wave 2)
     __shared__ float xb[6][64];                                   //                bias force          (wave 1 -> wave 0)
     __shared__ unsigned char pbuf[PADS ? MAXC*64 : 1];            // pad contacts: (feature hash | edge mask) per record of the last solve
+    // (the arm dynamics in pair form unless that costs scratch: the contact variants and FL = 7 keep the scalar form.  Loop-local factor:
+    //  wherever the pair form runs, except Env03 / Env04 -- their task layer is the largest, and with 21 registers held round the substep
+    //  loop three values of it are parked in AGPRs)
+    constexpr bool PKF = !PADS && FL != 7, LOCALF = PKF && KIND != 3 && KIND != 4;
+    // Substep 0's first half beside the sampling (physics_phase_mw: PRE): the contact-disabled variants with the loop-local factor.  Wave 0
+    // publishes q, v of env = lane at the end of every step (behind the auto-reset) and once behind load_env_state; not from oxt: obs[0..5] = q
+    // holds for the reach kinds only.  The factor has an array of its own: xm aliases h2t, which the heads are still reading.
+    constexpr bool PRE = LOCALF && FL == (int)F_CUBE_PINNED;
+    __shared__ float xs[PRE ? 12 : 1][64];                        // q, v at the start of the step (wave 0 -> waves 1, 2)
+    __shared__ float xf[PRE ? 21 : 1][64];                        // substep 0's factor            (wave 2 -> wave 0)
     ContactMemo memo;                                             // ... and the rest of the contact wave's active-set memory
     if (FL >= 0) p.flags = (unsigned)FL;
     const int lane = threadIdx.x & 63;
@@ -650,6 +699,10 @@ __global__ void __launch_bounds__(64*NW) so100_rollout_fused(SimParams p, float*
         if (live) load_env_state<KIND, FL>(state, p.n, env, e); else idle_lane_state(e);
 #pragma unroll
         for (int k = 0; k < ODP; k++) oxt[lane][k] = (live && k < OD) ? ra.obs_in[(size_t)env*OD + k] : 0.0f;
+        if constexpr (PRE) {
+#pragma unroll
+            for (int i = 0; i < 6; i++) { xs[i][lane] = e.q[i]; xs[6 + i][lane] = e.v[i]; }
+        }
     }
     if (wave == 3 && ra.T > 0) {
         float eps[8];
@@ -741,6 +794,7 @@ __global__ void __launch_bounds__(64*NW) so100_rollout_fused(SimParams p, float*
             if (live) row[OD + ROW_VALUE] = v;
         }
         __syncthreads();
+        SO100_PROF(12);                                            // heads + their barrier
         if (wave == 0) {
             // ---- sample -> clip -> rollout row; then the physics phase.  The noise was drawn by wave 3 a step ago.
             float mean[6], eps[6];
@@ -756,14 +810,52 @@ __global__ void __launch_bounds__(64*NW) so100_rollout_fused(SimParams p, float*
                 if (live) row[OD + ROW_ACT + a] = raw;
             }
             if (live) {
+                if constexpr (!PRE) {
 #pragma unroll
-                for (int k = 0; k < OD; k++) row[k] = oxt[lane][k];
+                    for (int k = 0; k < OD; k++) row[k] = oxt[lane][k];
+                }
                 row[OD + ROW_LOGP] = lp;
             }
             draw8(p, p.env_id_offset + (uint32_t)env, (uint32_t)e.rngc, 0, nullptr, ustep);
             e.rngc++;
             env_step_pre<KIND>(e, act, ustep, p, ctx);
-            SO100_PROF(1);                                         // head + noise + row + env_step_pre (wave 0)
+            SO100_PROF(1);                                         // sample + row + env_step_pre (wave 0)
+        } else if constexpr (PRE) {
+          // ---- substep 0's first half, meanwhile: nothing in it depends on the action (physics_phase_mw: PRE).  Wave 1: sin/cos -> xq, RNEA -> xb
+          if (wave == 1) {
+            Arm<float> R; float q1[6], v1[6];
+#pragma unroll
+            for (int i = 0; i < 6; i++) { q1[i] = xs[i][lane]; v1[i] = xs[6 + i][lane]; }
+            arm_trig<float>(q1, R);
+#pragma unroll
+            for (int i = 0; i < 6; i++) { xq[i][lane] = R.s[i]; xq[6 + i][lane] = R.c[i]; }
+            SO100_PROF(13);                                        // pre-step sin/cos (waves 1, 2)
+            arm_bias<float, PKF, PKF>(v1, R);
+#pragma unroll
+            for (int i = 0; i < 6; i++) xb[i][lane] = R.bias[i];
+            SO100_PROF(14);                                        // pre-step RNEA (wave 1) / CRBA + factor (wave 2)
+          } else if (wave == 2) {
+            // wave 2: sin/cos (its own: no barrier between the two waves), CRBA + factor -> xf
+            Arm<float> F; float q2[6];
+#pragma unroll
+            for (int i = 0; i < 6; i++) q2[i] = xs[i][lane];
+            arm_trig<float>(q2, F);
+            SO100_PROF(13);
+            arm_mass<float, PKF, PKF>(F);
+            arm_factor<float>(p.flags, F);
+#pragma unroll
+            for (int i = 1; i < 6; i++)
+#pragma unroll
+                for (int k = 0; k < i; k++) xf[SO100_TRI(i - 1, k)][lane] = F.M[SO100_TRI(i, k)];
+#pragma unroll
+            for (int i = 0; i < 6; i++) xf[15 + i][lane] = F.Dinv[i];
+            SO100_PROF(14);
+          } else if (live) {
+            // wave 3: the observation columns of the rollout row (oxt has been final since the previous step's end; the stand-alone policy
+            // kernel stores them from an idle wave too)
+#pragma unroll
+            for (int k = 0; k < OD; k++) row[k] = oxt[lane][k];
+          }
         }
         // ---- physics phase, split over the waves: per substep wave 1 computes the RNEA bias force while wave 0
         //      computes the CRBA mass matrix and factorises it; wave 0 then solves, integrates and publishes q, v.
@@ -771,11 +863,8 @@ __global__ void __launch_bounds__(64*NW) so100_rollout_fused(SimParams p, float*
         //      lanes with pad contacts to the solver tolerance (same warm start and active-set memory, differently rounded inputs).
         {
             Arm<float> A;
-            const PhaseLds lds{ xq, xc, xb, pool, xa, xk, xm, pbuf, xw };
-            // (pair form: see above.  Loop-local factor: wherever the pair form runs, except Env03 / Env04 -- their task layer is the
-            //  largest, and with 21 registers held round the substep loop three values of it are parked in AGPRs)
-            constexpr bool PKF = !PADS && FL != 7;
-            physics_phase_mw<PADS, LINKS, PKF, PKF && KIND != 3 && KIND != 4, PKF>(p, wave, lane, e, ctx.ctrl, cstale, A, lds, memo, prof_, [&](int sub) {
+            const PhaseLds lds{ xq, xc, xb, pool, xa, xk, PRE ? xf : xm, pbuf, xw };
+            physics_phase_mw<PADS, LINKS, PKF, LOCALF, PKF, PRE>(p, wave, lane, e, ctx.ctrl, cstale, A, lds, memo, prof_, [&](int sub) {
                 if (wave == 3 && sub == 0 && t + 1 < ra.T) {       // wave 0 has consumed xn before this barrier
                     float eps[8];
                     policy_noise(p.env_id_offset + (uint32_t)env, ra.step_counter0 + (uint32_t)(t + 1), p.seed_lo, p.seed_hi, eps);
@@ -798,6 +887,10 @@ __global__ void __launch_bounds__(64*NW) so100_rollout_fused(SimParams p, float*
                 const StepResult r = env_step_finish<KIND>(e, reward, term, p, p.env_id_offset + (uint32_t)env, nullptr, start_tab, obs, tobs);
 #pragma unroll
                 for (int k = 0; k < OD; k++) { oxt[lane][k] = obs[k]; last_obs[k] = obs[k]; }
+                if constexpr (PRE) {                               // the next step's start state: behind the auto-reset
+#pragma unroll
+                    for (int i = 0; i < 6; i++) { xs[i][lane] = e.q[i]; xs[6 + i][lane] = e.v[i]; }
+                }
                 last = r;
                 if (live) {
                     row[OD + ROW_REWARD] = r.reward; row[OD + ROW_DONE] = done_code(r.done, r.trunc_only);
@@ -818,7 +911,7 @@ __global__ void __launch_bounds__(64*NW) so100_rollout_fused(SimParams p, float*
         }
         __syncthreads();
     }
-    SO100_PROF_FLUSH(12*wave);
+    SO100_PROF_FLUSH(16*wave);
     {
         const int np = 64/p.epw, e3 = blockIdx.x*p.epw + lane/np;      // the contact wave's lanes are grouped per env
         if (wave == 3) prof_.flush_wg(wave, lane, e3, (lane % np) == 0 && e3 < p.n); else prof_.flush_wg(wave, lane, env, live);

@@ -127,7 +127,7 @@ int so100_state_field_index(const char* name) {
 const char* so100_state_field_name(int32_t field) { return (field >= 0 && field < SF_COUNT) ? kFieldNames[field] : nullptr; }
 const char* so100_last_error(void) { return g_last_error; }
 #ifdef SO100_ROLLOUT_PROF
-int so100_prof_read(int kind, long long* out48) { return DISPATCH_KIND(kind, prof_read)(out48); }
+int so100_prof_read(int kind, long long* out64) { return DISPATCH_KIND(kind, prof_read)(out64); }
 int so100_prof_read_wg(int kind, long long* wg4096, int* env32768) { return DISPATCH_KIND(kind, prof_read_wg)(wg4096, env32768); }
 int so100_prof_read_hist(int kind, unsigned long long* hist48, int reset) { return DISPATCH_KIND(kind, prof_read_hist)(hist48, reset); }
 #endif

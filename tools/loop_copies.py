@@ -15,6 +15,10 @@ fast-math):
     fall-through of s_cbranch_execz (the reset of finished episodes) is marked: a wave skips it unless one of its lanes takes the branch.
 Wave 0's path through a substep is every block of the loop but the RNEA block (the big block of the first half without a reciprocal)
 and the first substep's exact sin/cos block (the one with v_floor); wave 1's leg is the RNEA block.
+  * the pre-step region, in the variants that run substep 0's first half beside the sampling (physics_phase_mw: PRE; recognised by a loop
+    without an exact sin/cos block): from the barrier behind the policy heads to substep 0's one barrier, per block; the two blocks with
+    v_floor are wave 1's (sin/cos + RNEA) and wave 2's (sin/cos + CRBA + factor: the one with a reciprocal), the rest is wave 0's
+    sampling, rollout row and env_step_pre.
 The same kind of tool as tools/rnea_count.sh."""
 import argparse, json, os, re, shutil, subprocess, sys, tempfile
 
@@ -202,9 +206,19 @@ def analyse(txt):
     big = [n for n in first if "v_rcp_f32_e32" not in " ".join(by[n].ins)]
     rnea = max(big, key=lambda n: len(by[n].ins)) if big else None
     exact = [n for n in loop if any(i.startswith("v_floor_f32") for i in by[n].ins)]
+    # pre-step region (PRE variants: no exact sin/cos inside the loop): between the two barriers in front of the loop's first one
+    pre, pre_roles = [], {}
+    if not exact:
+        entry = [b for b in bars if b not in best and best[0] in fwd[b]]
+        heads = [b for e in entry for b in bars if b not in best and b != e and e in fwd[b]]
+        if entry and heads:
+            pre = region(heads[0], entry[0])
+            for n in pre:
+                txt_ = " ".join(by[n].ins)
+                if "v_floor_f32" in txt_: pre_roles[n] = "wave 2: sin/cos + CRBA + factor" if "v_rcp_f32" in txt_ else "wave 1: sin/cos + RNEA"
     # blocks a wave skips when none of its lanes takes the branch: the fall-through of a block that ends in s_cbranch_execz
     guarded = {n for n in by for q in pred[n] if by[q].ins and by[q].ins[-1].startswith("s_cbranch_execz") and by[q].ins[-1].split()[1] != n}
-    return dict(by=by, order=order, regions=regions, loop=loop, landing=landing, tail=tail, rnea=rnea, exact=exact, barriers=best, guarded=guarded)
+    return dict(by=by, order=order, regions=regions, loop=loop, landing=landing, tail=tail, rnea=rnea, exact=exact, barriers=best, guarded=guarded, pre=pre, pre_roles=pre_roles)
 
 
 def total(by, names):
@@ -226,6 +240,10 @@ def summary(txt, usage=None):
                               **(by[a["landing"]].counts() if a["landing"] else total(by, []))}
     out["tail"] = total(by, a["tail"])
     out["blocks"]["tail"] = [(n, by[n].counts()) for n in a["tail"] if by[n].ins]
+    out["pre"] = total(by, a["pre"])
+    out["blocks"]["pre"] = [(n, by[n].counts()) for n in a["pre"] if by[n].ins]
+    out["pre_roles"] = a["pre_roles"]
+    out["pre_wave0"] = total(by, [n for n in a["pre"] if n not in a["pre_roles"]])
     out["guarded"] = sorted(a["guarded"], key=a["order"].get)
     out["tail_unguarded"] = total(by, [n for n in a["tail"] if n not in a["guarded"]])
     out["rnea_block"] = {"name": a["rnea"], **(by[a["rnea"]].counts() if a["rnea"] else total(by, []))}
@@ -261,6 +279,11 @@ def main():
     print(f"wave 1's RNEA block {fmt(s['rnea_block'])}")
     be = s["back_edge_block"]
     print(f"back-edge block {be['name']}{' (holds barrier 1: no block of its own)' if be['holds_barrier'] else ''}  {fmt(be)}  v_accvgpr_write {be['accw']}")
+    if s["blocks"]["pre"]:
+        print(f"pre-step region    {fmt(s['pre'])}")
+        for n, bc in s["blocks"]["pre"]:
+            if bc["total"] >= 8 or n in s["pre_roles"]: print(f"    {n:22s} {fmt(bc)}{' (' + s['pre_roles'][n] + ')' if n in s['pre_roles'] else ''}")
+        print(f"pre-step region without the blocks of waves 1 and 2 (wave 0: sample, row, env_step_pre; wave 3: the row's observation columns)  {fmt(s['pre_wave0'])}")
     print(f"step tail          {fmt(s['tail'])}")
     for n, bc in s["blocks"]["tail"]:
         if bc["total"] >= 8:

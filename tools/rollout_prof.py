@@ -1,7 +1,7 @@
 """Cycle accounting of the persistent rollout kernel's phases (waves 0-3 of workgroup 0).
 Build the instrumented side library HERE (no GPU needed), then run on the GPU box:
     python tools/rollout_prof.py build
-    python tools/rollout_prof.py [free|arm|nopads|ref|c5] [random|resting|held]
+    python tools/rollout_prof.py [free|arm|nopads|ref|c5] [random|resting|held] [envs per workgroup: 0 = the library's choice]
 The product library is untouched (the instrumentation is compiled out without -DSO100_ROLLOUT_PROF)."""
 import ctypes as C, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -19,7 +19,8 @@ which = sys.argv[1] if len(sys.argv) > 1 else "free"
 mode = sys.argv[2] if len(sys.argv) > 2 else "random"
 flags = {"free": F_CUBE_PINNED, "arm": F_FRICTIONLOSS | F_LIMITS | F_CUBE_PINNED, "nopads": F_NOPADS, "ref": F_REFERENCE, "c5": F_CONTACT5}[which]
 n, T = 4096, 64
-sim = So100Sim(1, n, flags=flags, seed=1); sim.reset()
+sim = So100Sim(1, n, flags=flags, seed=1, envs_per_workgroup=int(sys.argv[3]) if len(sys.argv) > 3 else 0); sim.reset()
+epw = sim.envs_per_workgroup
 sd = RolloutCollector.random_policy_state(sim.obs_dim, sim.device, seed=0)
 if mode in ("resting", "held"):             # zero action: Env01's ctrl = measured angle lets every arm sag onto the floor and rest there
     sd["action_net.weight"].zero_(); sd["action_net.bias"].zero_(); sd["log_std"].fill_(-30.0)
@@ -41,15 +42,18 @@ for i in range(4):
     sim.rollout(buf, i * T)
 torch.cuda.synchronize()
 sim.L.so100_prof_read_hist(1, hist, 0)
-out = (C.c_longlong * 48)()
+NS = 16                                     # slots per wave (csrc/so100_rollout.hpp: Prof)
+out = (C.c_longlong * (4 * NS))()
 assert sim.L.so100_prof_read(1, out) == 0
-names = ["policy layers (MFMA+tanh, 2 barriers)", "head+noise+row+env_step_pre", "trig + publish", "barrier-1 wait",
+names = ["policy layers (MFMA+tanh, 2 barriers)", "sample+row+env_step_pre (w0)", "trig + publish", "barrier-1 wait",
          "phase 1: CRBA+factor (w0) / RNEA (w1) / cube_prepare (w2) / FK+narrowphase (w3)", "barrier-2 wait",
          "phase 2: PGS (w0) / cube Newton (w2) / contact Newton (w3)", "step tail: poses, obs, reset, end barrier", "barrier-3 wait", "integrate",
-         "  (w3) world FK, before the narrowphase", "  (w3) contact-solve set-up, before the Newton"]
-print(f"# tools/rollout_prof.py {which} {mode}   (Env01 x {n}, epw {16 if flags & 4 else 64})")
+         "  (w3) world FK, before the narrowphase", "  (w3) contact-solve set-up, before the Newton",
+         "heads + their barrier", "pre-step: exact sin/cos of substep 0 (w1, w2)", "pre-step: RNEA (w1) / CRBA+factor (w2) of substep 0",
+         "substep 0's one barrier wait (pre-step variants)"]
+print(f"# tools/rollout_prof.py {which} {mode}   (Env01 x {n}, epw {epw})")
 for w in range(4):
-    v = [out[12 * w + i] for i in range(12)]; tot = sum(v)
+    v = [out[NS * w + i] for i in range(NS)]; tot = sum(v)
     print(f"wave {w}: total {tot / T:9.0f} ticks/step")
     for nm, x in zip(names, v):
         per = "  (%.0f / substep)" % (x / T / 16) if nm.split()[0] in ("trig", "barrier-1", "phase", "barrier-2", "barrier-3", "integrate", "(w3)") else ""
@@ -60,7 +64,6 @@ import numpy as np
 wg = (C.c_longlong * 4096)(); envw = (C.c_int * 32768)()
 sim.L.so100_prof_read_wg.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
 if sim.L.so100_prof_read_wg(1, wg, envw) == 0:
-    epw = 16 if flags & 4 else 64
     nwg = (n + epw - 1)//epw
     W = np.array(wg[:4*nwg], dtype=np.float64).reshape(nwg, 4)/T
     E = np.array(envw[:2*n]).reshape(n, 2)
