@@ -8,7 +8,8 @@
 //   action = mean + exp(log_std) * eps, eps ~ N(0,1) (Philox4x32-10 + Box-Muller, or injected), log_prob, clip to [-1,1]
 // Two kernels in so100_rollout.hpp run it: so100_policy_forward_mfma (its own launch) and the policy phase of
 // so100_rollout_fused.  The two 64-wide hidden layers run on the matrix cores (exact-fp32 v_mfma_f32_32x32x2_f32), heads /
-// sampling on the VALU.  This header holds what the two share: the weight / IO structs, the LDS and rollout-row layouts and the
+// sampling on the VALU (the 32-row contact-disabled rollout kernels run the heads on the matrix cores as well: v_mfma_f32_4x4x1_16b_f32,
+// the same fmaf chain).  This header holds what the two share: the weight / IO structs, the LDS and rollout-row layouts and the
 // tanh (the Philox + Box-Muller noise, policy_noise, is in so100_task.hpp).  The network itself is written out in each kernel, the same operations in the same
 // order, and test_persistent_rollout_equals_stepwise holds the two together to 1e-6.  (It was also built as shared functions
 // here; each of them, even the once-per-launch weight loading, changed the register allocation or scratch size of some
@@ -24,6 +25,9 @@ constexpr int POLICY_LD = 65;                          // LDS row stride of the 
 constexpr int policy_odp(int od) { return (od + 3) & ~3; }     // K of layer 1: obs_dim padded with zero weights to whole k steps
 // hd[]: the head weights in LDS, mu_w[6][64] | v_w[64] | mu_b[6] | log_std[6] | v_b
 constexpr int HD_MU_W = 0, HD_V_W = 6*64, HD_MU_B = 7*64, HD_LOG_STD = HD_MU_B + 6, HD_V_B = HD_LOG_STD + 6, HD_WORDS = 7*64 + 16;
+// hm[]: mu_w once more for the matrix-core mean head (so100_rollout.hpp: head_mfma), rows HM_LD floats apart.  One ds_read_b128 of that head
+// touches the four rows (lane & 3) + 4*(lane >> 5) within a 16-lane group: 64 floats apart they share four banks, 68 apart they take sixteen.
+constexpr int HM_LD = 68, HM_WORDS = 6*HM_LD;
 // rollout-buffer row of one env and step: obs[OD] | raw action[6] | reward | done code | value | log-prob (columns past the observation)
 constexpr int ROW_ACT = 0, ROW_REWARD = 6, ROW_DONE = 7, ROW_VALUE = 8, ROW_LOGP = 9, ROW_EXTRA = 10;
 __device__ __forceinline__ float done_code(bool done, bool trunc_only) { return done ? (trunc_only ? 2.0f : 1.0f) : 0.0f; }     // 2 = TimeLimit truncation only

@@ -2,13 +2,16 @@
 //
 // One workgroup = NW waves = 64 envs.  Each step has two phases:
 //   policy phase  (all 4 waves): the two hidden layers of both towers on the matrix cores (fp32 MFMA, weight
-//                 fragments resident in VGPRs for the whole launch, activations through LDS); the heads on the VALU:
-//                 wave 0 ends with the action of env = lane in registers.
+//                 fragments resident in VGPRs for the whole launch, activations through LDS); the heads on the VALU, all four waves and a
+//                 barrier -- or, in the 32-row contact-disabled kernels, on the matrix cores too (head_mfma): the mean head on wave 0 and the
+//                 value head on wave 3, no barrier, while waves 1 and 2 are already in the physics phase (below).
+//                 Wave 0 ends with the action of env = lane in registers.
 //   physics phase: the same fused env step as so100_step_fused (reward -> ctrl -> 16 substeps -> obs -> TimeLimit ->
 //                 auto-reset) for env = lane of wave 0, with each substep's RNEA bias force computed concurrently on
 //                 wave 1 and, when the cube is simulated, its free-body / floor-contact substep on wave 2 (two workgroup
 //                 barriers per substep; sin/cos, q-dot, the bias and the cube state cross through LDS).  In the contact-disabled variants
-//                 the action-independent half of the FIRST substep runs on waves 1 and 2 while wave 0 still samples (physics_phase_mw: PRE).
+//                 the action-independent half of the FIRST substep runs on waves 1 and 2 while wave 0 still samples (physics_phase_mw: PRE);
+//                 in the 32-row kernels it starts right behind layer 2's barrier, beside the heads.
 // The env state lives in wave 0's registers across all T steps (loaded once, stored once per launch), the
 // observation goes to the next policy phase through LDS, and the only per-step HBM traffic is the rollout-buffer row
 // (obs | action | reward | done | value | logp = (obs_dim+10) words per env).  Compared with one policy launch + one
@@ -603,6 +606,53 @@ __global__ void __launch_bounds__(256, 2) so100_policy_forward_mfma(int n, Polic
     }
 }
 
+// A 64-deep head over ONE 32-row activation image on the matrix cores, by one wave: v_mfma_f32_4x4x1_16b_f32 computes, per instruction, sixteen
+// independent 4 x 4 blocks D[i][j] += A[i] * B[j] with k = 1, so 64 of them chained over one accumulator are, element by element, the k-ordered
+// chain m = bias; m = fmaf(w[k], x[k], m) of the VALU heads (the hidden layers rely on the same property of the 32x32x2 form).  Operands: lane
+// 4b + i supplies A = act[4(b & 7) + i][k] = act[lane & 31][k] (blocks b and b + 8 take the same four envs) and B = wrow[k], the caller's choice of
+// weight row for output column (lane & 3) + 4(lane >> 5) of this lane; register i of lane 4b + j returns env 4(b & 7) + i, output j + 4(b >> 3).
+// Columns are independent of each other: a caller with fewer than eight outputs points the spare columns at any row and never reads them.
+// Call it in wave-uniform control flow, all lanes enabled.  act rows are LD floats apart (65: lanes of a half hit 32 banks), wrow is 16-byte aligned.
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+template <int LD>
+__device__ __forceinline__ f32x4 head_mfma(const float (*act)[LD], const float* wrow, float bias, int lane) {
+    f32x4 acc = { bias, bias, bias, bias };
+    const float* x = act[lane & 31];
+    // Operands in batches of KB k, the next batch's LDS reads issued in front of this batch's MFMAs: left to itself the scheduler (in a kernel at
+    // its register limit) reads two k at a time and waits out the whole LDS latency in front of every other MFMA.
+    constexpr int KB = 16;
+    float xk[2][KB]; float4 wk[2][KB/4];
+    auto load = [&](int b, int k0) {
+#pragma unroll
+        for (int k = 0; k < KB; k += 4) wk[b][k/4] = *reinterpret_cast<const float4*>(wrow + k0 + k);
+#pragma unroll
+        for (int k = 0; k < KB; k++) xk[b][k] = x[k0 + k];
+    };
+    load(0, 0);
+#pragma unroll
+    for (int k0 = 0; k0 < 64; k0 += KB) {
+        const int b = (k0/KB) & 1;
+        if (k0 + KB < 64) load(b ^ 1, k0 + KB);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int k = 0; k < KB; k += 4) {
+            acc = __builtin_amdgcn_mfma_f32_4x4x1f32(xk[b][k], wk[b][k/4].x, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_4x4x1f32(xk[b][k + 1], wk[b][k/4].y, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_4x4x1f32(xk[b][k + 2], wk[b][k/4].z, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_4x4x1f32(xk[b][k + 3], wk[b][k/4].w, acc, 0, 0, 0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    return acc;
+}
+// One wave hands values to other lanes of ITSELF through LDS: the hardware serves a wave's LDS operations in order, so all this has to do is keep the
+// compiler from moving the reads above the writes.
+__device__ __forceinline__ void wave_lds_handoff() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 // Policy hidden layers on the matrix cores: per tower and layer, H[64 envs][64 units] = tanh(X[64][K] W^T + b) is a genuine
 // contraction (K = 16 / 64).  v_mfma_f32_32x32x2_f32 is exact fp32 (a k-ordered fmaf chain, so results are bit-compatible
 // with the VALU policy kernel).  4 waves = one per SIMD: wave w owns tower w>>1, env rows [32(w&1), +32) and both 32-unit
@@ -657,6 +707,12 @@ __global__ void __launch_bounds__(64*NW) so100_rollout_fused(SimParams p, float*
     constexpr bool PRE = LOCALF && FL == (int)F_CUBE_PINNED;
     __shared__ float xs[PRE ? 12 : 1][64];                        // q, v at the start of the step (wave 0 -> waves 1, 2)
     __shared__ float xf[PRE ? 21 : 1][64];                        // substep 0's factor            (wave 2 -> wave 0)
+    // The 32-row PRE kernels run the heads on the matrix cores (head_mfma: one wave holds a whole 32-row tile), the mean head on wave 0 and the
+    // value head on wave 3, with no workgroup barrier behind them: waves 1 and 2 start the pre-step right behind layer 2's barrier.  The 64-row
+    // kernels would need two accumulators or two waves for the means and a barrier to collect them; they and every other variant keep the VALU heads.
+    constexpr bool MH = PRE && HALF;
+    __shared__ __attribute__((aligned(16))) float hm[MH ? HM_WORDS : 4];  // mu_w, rows HM_LD apart (written once per launch beside hd)
+    __shared__ float xv[MH ? 32 : 1];                             // value of env = index (wave 3's accumulator layout -> its lane = env)
     ContactMemo memo;                                             // ... and the rest of the contact wave's active-set memory
     if (FL >= 0) p.flags = (unsigned)FL;
     const int lane = threadIdx.x & 63;
@@ -693,6 +749,9 @@ __global__ void __launch_bounds__(64*NW) so100_rollout_fused(SimParams p, float*
         hd[HD_V_W + lane] = w.v_w[lane];
         if (lane < 6) { hd[HD_MU_B + lane] = w.mu_b[lane]; hd[HD_LOG_STD + lane] = w.log_std[lane]; }
         if (lane == 0) hd[HD_V_B] = w.v_b[0];
+        if constexpr (MH) {
+            for (int i = lane; i < 6*64; i += 64) hm[(i >> 6)*HM_LD + (i & 63)] = w.mu_w[i];
+        }
     }
     EnvState e;
     if (wave == 0) {
@@ -773,6 +832,37 @@ __global__ void __launch_bounds__(64*NW) so100_rollout_fused(SimParams p, float*
         __syncthreads();
         SO100_PROF(0);                                             // policy hidden layers (MFMA + tanh + 2 barriers)
         float* row = ra.buf + ((size_t)t*p.n + (size_t)env)*(OD + ROW_EXTRA);
+        if constexpr (MH) {
+            // ---- heads (matrix cores, head_mfma): wave 0 the 6 x 64 mean head, wave 3 the value head, each the k-ordered fmaf chain of the
+            //      stand-alone policy kernel; waves 1 and 2 go straight on to the pre-step below.  No workgroup barrier behind the heads.  Why each
+            //      LDS array is safe between layer 2's barrier and substep 0's:
+            //        xs          read by waves 1, 2; written by wave 0 in front of the previous end-of-step (or prologue) barrier
+            //        xq, xb, xf  written by waves 1, 2; their last readers ran in the previous step's last substep, in front of that same barrier
+            //        h2t         read by waves 0, 3; next written behind the NEXT step's layer-1 barrier (nothing of the physics phase aliases it here)
+            //        hm, hd      written once per launch
+            //        xmean, xv   one wave each (0 / 3) writes and reads its own: wave_lds_handoff
+            //        xn          read by wave 0 below; pre-drawn by wave 3 behind the first barrier of substep 1 (the peeled barrier for frame_skip 1)
+            //        oxt         read by wave 3 for the row; final since the previous step's end-of-step barrier
+            if (wave == 0) {
+                // output column of this lane: means 0..3 in blocks 0..7, means 4, 5 in blocks 8..15, whose two spare columns repeat mean 5 (finite, never read)
+                const int col = (lane & 3) + 4*(lane >> 5), a = col < 6 ? col : 5;
+                const f32x4 m = head_mfma<LD>(h2t[0], hm + a*HM_LD, hd[HD_MU_B + a], lane);
+                if (col < 6) {
+#pragma unroll
+                    for (int i = 0; i < 4; i++) xmean[col][(lane & 28) + i] = m[i];
+                }
+                wave_lds_handoff();
+            } else if (wave == 3) {
+                // one output: every column is the value (all lanes read the same weight row: a broadcast); column 0 of blocks 0..7 is stored
+                const f32x4 v = head_mfma<LD>(h2t[1], hd + HD_V_W, hd[HD_V_B], lane);
+                if ((lane & 35) == 0) {
+#pragma unroll
+                    for (int i = 0; i < 4; i++) xv[lane + i] = v[i];
+                }
+                wave_lds_handoff();
+                if (live) row[OD + ROW_VALUE] = xv[lane & 31];
+            }
+        } else {
         // ---- heads (VALU, lane = env): the 6 x 64 mean head is split two actions per wave over waves 0, 1, 3 and the
         //      value head runs on wave 2; each mean is the same k-ordered fmaf chain as in the stand-alone policy kernel
         if (wave != 2) {
@@ -794,7 +884,8 @@ __global__ void __launch_bounds__(64*NW) so100_rollout_fused(SimParams p, float*
             if (live) row[OD + ROW_VALUE] = v;
         }
         __syncthreads();
-        SO100_PROF(12);                                            // heads + their barrier
+        }
+        SO100_PROF(12);                                            // heads + their barrier (matrix-core heads: wave 0 / wave 3 only, no barrier)
         if (wave == 0) {
             // ---- sample -> clip -> rollout row; then the physics phase.  The noise was drawn by wave 3 a step ago.
             float mean[6], eps[6];

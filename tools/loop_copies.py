@@ -16,9 +16,10 @@ fast-math):
 Wave 0's path through a substep is every block of the loop but the RNEA block (the big block of the first half without a reciprocal)
 and the first substep's exact sin/cos block (the one with v_floor); wave 1's leg is the RNEA block.
   * the pre-step region, in the variants that run substep 0's first half beside the sampling (physics_phase_mw: PRE; recognised by a loop
-    without an exact sin/cos block): from the barrier behind the policy heads to substep 0's one barrier, per block; the two blocks with
+    without an exact sin/cos block): from the last barrier in front of it to substep 0's one barrier, per block; the two blocks with
     v_floor are wave 1's (sin/cos + RNEA) and wave 2's (sin/cos + CRBA + factor: the one with a reciprocal), the rest is wave 0's
-    sampling, rollout row and env_step_pre.
+    sampling, rollout row and env_step_pre.  That last barrier is the one behind the VALU heads in the 64-row kernels and layer 2's in the
+    32-row kernels, whose heads (the two blocks with v_mfma_f32_4x4x1) run inside the region, on waves 0 and 3.
 The same kind of tool as tools/rnea_count.sh."""
 import argparse, json, os, re, shutil, subprocess, sys, tempfile
 
@@ -216,6 +217,7 @@ def analyse(txt):
             for n in pre:
                 txt_ = " ".join(by[n].ins)
                 if "v_floor_f32" in txt_: pre_roles[n] = "wave 2: sin/cos + CRBA + factor" if "v_rcp_f32" in txt_ else "wave 1: sin/cos + RNEA"
+                elif "v_mfma_f32_4x4x1" in txt_: pre_roles[n] = "a head on the matrix cores: wave 0 the means, wave 3 the value"
     # blocks a wave skips when none of its lanes takes the branch: the fall-through of a block that ends in s_cbranch_execz
     guarded = {n for n in by for q in pred[n] if by[q].ins and by[q].ins[-1].startswith("s_cbranch_execz") and by[q].ins[-1].split()[1] != n}
     return dict(by=by, order=order, regions=regions, loop=loop, landing=landing, tail=tail, rnea=rnea, exact=exact, barriers=best, guarded=guarded, pre=pre, pre_roles=pre_roles)
@@ -283,7 +285,7 @@ def main():
         print(f"pre-step region    {fmt(s['pre'])}")
         for n, bc in s["blocks"]["pre"]:
             if bc["total"] >= 8 or n in s["pre_roles"]: print(f"    {n:22s} {fmt(bc)}{' (' + s['pre_roles'][n] + ')' if n in s['pre_roles'] else ''}")
-        print(f"pre-step region without the blocks of waves 1 and 2 (wave 0: sample, row, env_step_pre; wave 3: the row's observation columns)  {fmt(s['pre_wave0'])}")
+        print(f"pre-step region without the blocks of waves 1 and 2 and the matrix-core heads (wave 0: sample, row, env_step_pre; wave 3: the row's observation columns)  {fmt(s['pre_wave0'])}")
     print(f"step tail          {fmt(s['tail'])}")
     for n, bc in s["blocks"]["tail"]:
         if bc["total"] >= 8:

@@ -49,7 +49,7 @@ names = ["policy layers (MFMA+tanh, 2 barriers)", "sample+row+env_step_pre (w0)"
          "phase 1: CRBA+factor (w0) / RNEA (w1) / cube_prepare (w2) / FK+narrowphase (w3)", "barrier-2 wait",
          "phase 2: PGS (w0) / cube Newton (w2) / contact Newton (w3)", "step tail: poses, obs, reset, end barrier", "barrier-3 wait", "integrate",
          "  (w3) world FK, before the narrowphase", "  (w3) contact-solve set-up, before the Newton",
-         "heads + their barrier", "pre-step: exact sin/cos of substep 0 (w1, w2)", "pre-step: RNEA (w1) / CRBA+factor (w2) of substep 0",
+         "heads + their barrier / matrix-core heads: mean + hand-off (w0), value (w3)", "pre-step: exact sin/cos of substep 0 (w1, w2)", "pre-step: RNEA (w1) / CRBA+factor (w2) of substep 0",
          "substep 0's one barrier wait (pre-step variants)"]
 print(f"# tools/rollout_prof.py {which} {mode}   (Env01 x {n}, epw {epw})")
 for w in range(4):
