@@ -187,6 +187,54 @@ typedef struct {
     double       epsilon;          /* >= 0; SB3: 1e-8                                                                            */
 } so100_reward_norm_io;
 
+/* Observation normalisation: the observation half of SB3's VecNormalize(norm_obs=True) with its RunningMeanStd, folded into the policy.
+ * Off unless asked for: with no normaliser set every entry point above computes what it always did, to the bit.
+ * State (state_dev, fp64 [2 obs_dim + 1], the caller's, carried from chunk to chunk): mean[obs_dim], var[obs_dim], count -- initially 0, 1,
+ * 1e-4 (so100_learner_obs_norm_init).
+ * Moment update of one chunk (so100_learner_obs_norm_update).  The batch is the T*N observation columns of the chunk's rows (row r = t N + n,
+ * observation i of row r at rollout_dev[r (obs_dim + 10) + i]): what the policy was fed, reset observations included.  Per dimension i, in fp64:
+ *   bm = mean over the batch;  bv = population variance over the batch;  bc = T*N
+ *   d = bm - mean;  tot = count + bc
+ *   mean'  = mean + d bc/tot
+ *   var'   = (var count + bv bc + d d count bc/tot)/tot
+ *   count' = tot
+ * Order of the sums -- a function of (T, N) alone, never of the grid; no floating-point atomics; the same inputs give the same bits:
+ *   1. the rows are cut into blocks of 256 in row order (the last block holds the remainder).  A block's mean is its sum by a fixed binary
+ *      tree over 256 slots (slot j holds the block's row j widened to fp64, 0 past the block's count; slot j += slot j + w for w = 128, 64 .. 1)
+ *      divided by its count; its M2 is the same tree over the squared deviations (x - mean)(x - mean) from that mean.
+ *   2. the blocks are cut into groups of 64 in block order.  A group's (n, mean, M2) starts as its first block's and absorbs its other blocks in
+ *      block order by Chan et al.'s update:  tot = na + nb;  d = mean_b - mean;  mean += d nb/tot;  M2 += M2_b + d d na nb/tot;  na = tot.
+ *   3. the groups are merged in group order by the same update, starting from the first group's; bm = mean, bv = M2/(T*N).
+ * Two chunks in a row are not bit-equal to one chunk of 2T (the statistics of a chunk are merged as ONE batch), but equal it within rounding.
+ * Two launches: the block moments (one workgroup per block), the merge with the update.  workspace_dev holds the blocks' and the groups'
+ * moments between them; the caller's, at least so100_learner_obs_norm_workspace(T, N) bytes, 8-byte aligned.
+ * Fold (so100_learner_obs_norm_fold).  For a frozen (mean, inv_std) the first layer of each tower on the normalised input equals a first layer
+ * with folded weights on the raw input.  In fp64, rounded once to float at the store:
+ *   inv_std[i] = 1/sqrt(var[i] + epsilon)                                             (SB3: epsilon 1e-8)
+ *   W0'[j][i]  = W0[j][i] inv_std[i]
+ *   b0'[j]     = b0[j] - sum_i W0'[j][i] mean[i]        (the unrounded W0'; the sum starts at 0 and runs in index order)
+ * for (W0, b0) = (pi_w0, pi_b0) and (vf_w0, vf_b0).  folded_params_dev [P] gets the folded four tensors and copies of the other nine: a
+ * so100_policy_weights may point into it, as into the plain block.  norm_dev, float [2 obs_dim], gets (float) mean[i], then (float) inv_std[i].
+ * The rollout kernels, so100_policy_forward and an exported policy then run on RAW observations with the folded block and compute the policy of
+ * the normalised ones; the rollout rows keep the raw observations, which the moment update needs.
+ * Learner (so100_learner_set_obs_norm).  With a normaliser set, every observation the learner reads -- the chunk's rows, the terminal
+ * observations, the last observations, in so100_learner_advantages(_r), both minibatch steps and both updates -- enters the towers as
+ *   x[i] = (obs[i] - norm[i]) * norm[obs_dim + i]
+ * in fp32: one subtraction, then one multiplication, each rounded (not a fused multiply-add).  params_dev is the PLAIN block there.
+ * Deviations from SB3: the statistics are frozen while a chunk is collected and updated once per chunk (SB3 updates them every step);
+ * clip_obs is not applied (a clamp cannot be folded, and the sampling policy and the trained policy must be the same function); the observation
+ * after the final chunk is never counted.  A dimension that never varies gets inv_std 1/sqrt(epsilon) = 1e4: its folded weights grow by that factor.
+ * Known answer: obs_dim 2, a fresh state, one chunk of two rows with the observations (1, 10) and (3, 14):
+ *   mean' = (1.9999000049997500, 11.999400029998500)   var' = (1.0001999800014999, 4.0070492875536214)   count' = 2.0001
+ *   inv_std = (0.99990001999525112, 0.49956000038410525)                             (epsilon 1e-8)
+ *   W0 = [[0.5, -0.25]], b0 = [0.125]  ->  W0' = [[0.49995000999762556, -0.12489000009602631]], b0' = [0.62375504340489438] */
+typedef struct {
+    const float* rollout_dev;      /* [T][N][obs_dim+10]: the observation columns are read                                       */
+    double*      state_dev;        /* [2 obs_dim + 1] in/out: mean, var, count                                                   */
+    void*        workspace_dev;    /* scratch of this call                                                                       */
+    int64_t      workspace_bytes;  /* >= so100_learner_obs_norm_workspace(T, N)                                                  */
+} so100_obs_norm_io;
+
 int  so100_learner_num_params(int32_t obs_dim);                          /* 10829 (obs_dim 15), 9933 (8); < 0 otherwise */
 int  so100_learner_param_offset(int32_t obs_dim, const char* name);      /* name: a member of so100_policy_weights; < 0 if unknown */
 int  so100_learner_param_size(int32_t obs_dim, const char* name);        /* elements of that tensor                      */
@@ -223,6 +271,22 @@ int  so100_learner_advantages_r(so100_learner* learner, const so100_advantages_i
 /* so100_learner_update with so100_learner_normalize_rewards(norm_io, io->T, io->N) enqueued first and the advantages reading
  * norm_io->reward_dev: still one call, nothing synchronises, and a rejected call enqueues nothing.  norm_io null: so100_learner_update. */
 int  so100_learner_update_r(so100_learner* learner, const so100_update_io* io, const so100_reward_norm_io* norm_io, void* hip_stream);
+
+/* Observation normalisation (specified above).  obs_dim is the handle's throughout. */
+/* state_dev [2 obs_dim + 1] = obs_dim zeros, obs_dim ones, 1e-4.  One launch. */
+int  so100_learner_obs_norm_init(so100_learner* learner, double* state_dev, void* hip_stream);
+/* bytes of so100_obs_norm_io.workspace_dev for a chunk of T steps x N envs (sized for obs_dim 15); < 0 when T or N is not positive or
+ * T*N > 2^24.  Needs no handle. */
+int64_t so100_learner_obs_norm_workspace(int32_t T, int32_t N);
+/* the moment update of one chunk: state_dev absorbs the T*N observation rows.  The chunk is read only.  Two launches.  T*N <= 2^24. */
+int  so100_learner_obs_norm_update(so100_learner* learner, const so100_obs_norm_io* io, int32_t T, int32_t N, void* hip_stream);
+/* the fold: folded_params_dev [P] and norm_dev [2 obs_dim] from state_dev (read only), params_dev [P] (read only) and epsilon >= 0.
+ * folded_params_dev must not alias params_dev.  One launch. */
+int  so100_learner_obs_norm_fold(so100_learner* learner, const double* state_dev, double epsilon, const float* params_dev, float* folded_params_dev,
+                                 float* norm_dev, void* hip_stream);
+/* norm_dev: float [2 obs_dim] (mean, inv_std), the caller's; only the pointer is kept, its contents are read when the kernels run (a fold
+ * enqueued on the same stream between two updates is seen by the second).  NULL: off, the state after so100_learner_create.  Enqueues nothing. */
+int  so100_learner_set_obs_norm(so100_learner* learner, const float* norm_dev);
 
 #ifdef __cplusplus
 }

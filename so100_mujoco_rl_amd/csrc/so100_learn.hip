@@ -20,6 +20,10 @@
 // No floating-point atomics anywhere; every sum has a fixed order => bit-identical results for identical inputs.
 // Reward normalisation (so100_learner_normalize_rewards, SB3's VecNormalize reward half): three launches in fp64 ahead of the advantages, which
 // then read the normalised rewards from a dense array instead of the chunk's column; see "reward normalisation" below.
+// Observation normalisation (SB3's VecNormalize observation half, folded into the policy): two fp64 launches merge a chunk's observation rows into
+// the running moments, one folds them into a second parameter block for the collector; with a normaliser set (so100_learner_set_obs_norm) the
+// gradient step launches so100_learn_grad_norm and the advantages the NORM value kernel, which read every observation as (x - mean)*inv_std; see
+// "observation normalisation".
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -71,8 +75,13 @@ struct GradSmem {
 
 // one tower's forward and backward pass over this workgroup's tiles; writes the tower's slice of the workgroup's partial
 // EX selects the extended loss head (entropy bonus, value clipping, approx_kl) and its NSTAT_EX sums
-template <int OD, int TW, bool EX, class Args>
-__device__ __forceinline__ void tower_pass(const Args& A, GradSmem& S) {
+// NORM: the observations enter as (x - mean)*inv_std (so100_learner_set_obs_norm).  The normaliser's 2 OD floats are wave-uniform and are read
+// through a __restrict__ PARAMETER, the kernel's own (so100_learn_grad_norm): that keeps them on the scalar path in the second tower too,
+// behind the first tower's stores to the partial.  (Read through a member of the argument struct they became per-lane vector loads there;
+// read once into registers at the kernel's entry they stayed scalar but lived in spilled SGPRs, which cost more than the vector loads did.)
+// Without NORM the body is the one it always was.
+template <int OD, int TW, bool EX, bool NORM, class Args>
+__device__ __forceinline__ void tower_pass(const Args& A, GradSmem& S, [[maybe_unused]] const float* __restrict__ nrm) {
     constexpr int ROW = OD + ROW_EXTRA, NH = TW ? 1 : ACT_DIM, P = num_params(OD), NS = EX ? NSTAT_EX : NSTAT;
     constexpr int oW0 = tensor_offset(TW ? T_vf_w0 : T_pi_w0, OD), oB0 = tensor_offset(TW ? T_vf_b0 : T_pi_b0, OD);
     constexpr int oW1 = tensor_offset(TW ? T_vf_w1 : T_pi_w1, OD), oB1 = tensor_offset(TW ? T_vf_b1 : T_pi_b1, OD);
@@ -104,7 +113,12 @@ __device__ __forceinline__ void tower_pass(const Args& A, GradSmem& S) {
         const float* __restrict__ r = A.chunk + row*ROW;
         float x[OD];
 #pragma unroll
-        for (int i = 0; i < OD; i++) x[i] = valid ? r[i] : 0.0f;
+        for (int i = 0; i < OD; i++) {
+            // NORM: each entry compiles to a block of its own under `valid` (one vector load, two scalar loads, a wait).  Forming the value for
+            // every lane and selecting it removes the blocks and was measured slower at obs_dim 15, so the form stays.
+            if constexpr (NORM) x[i] = valid ? obs_normalized(r[i], nrm[i], nrm[OD + i]) : 0.0f;
+            else x[i] = valid ? r[i] : 0.0f;
+        }
         // ---- layer 1, units u0..u0+15 of this lane's sample
         float h1[16];
 #pragma unroll
@@ -281,8 +295,18 @@ template <int OD, bool EX>
 __global__ __launch_bounds__(256) void so100_learn_grad(GradArgsOf<EX> A) {
     if constexpr (EX) { if (A.state != nullptr && A.state[0] != 0) return; }
     __shared__ GradSmem S;
-    tower_pass<OD, 0, EX>(A, S);
-    tower_pass<OD, 1, EX>(A, S);
+    tower_pass<OD, 0, EX, false>(A, S, nullptr);
+    tower_pass<OD, 1, EX, false>(A, S, nullptr);
+}
+
+// the same with the observation normaliser (mean[OD], inv_std[OD]): a kernel of its own, so that so100_learn_grad keeps the argument block
+// it always had and the normaliser is a __restrict__ parameter
+template <int OD, bool EX>
+__global__ __launch_bounds__(256) void so100_learn_grad_norm(GradArgsOf<EX> A, const float* __restrict__ norm) {
+    if constexpr (EX) { if (A.state != nullptr && A.state[0] != 0) return; }
+    __shared__ GradSmem S;
+    tower_pass<OD, 0, EX, true>(A, S, norm);
+    tower_pass<OD, 1, EX, true>(A, S, norm);
 }
 
 // one thread per entry of a partial: the sum over the G workgroups in workgroup order; each block leaves the sum of squares of its gradients
@@ -372,14 +396,18 @@ __global__ __launch_bounds__(256) void so100_learn_adam_ex(const float* __restri
 
 // ---- advantages -------------------------------------------------------------------------------------------------------------------------
 // V(obs) of one row in one lane: the weights are wave-uniform (scalar cache), the activations stay in registers
-template <int OD>
-__device__ __forceinline__ float value_tower(const float* __restrict__ prm, const float* __restrict__ obs) {
+// NORM: nm is the observation normaliser (mean[OD], inv_std[OD]), wave-uniform like the weights
+template <int OD, bool NORM>
+__device__ __forceinline__ float value_tower(const float* __restrict__ prm, const float* __restrict__ obs, const float* __restrict__ nm) {
     const float* __restrict__ W0 = prm + tensor_offset(T_vf_w0, OD); const float* __restrict__ B0 = prm + tensor_offset(T_vf_b0, OD);
     const float* __restrict__ W1 = prm + tensor_offset(T_vf_w1, OD); const float* __restrict__ B1 = prm + tensor_offset(T_vf_b1, OD);
     const float* __restrict__ VW = prm + tensor_offset(T_v_w, OD);
     float x[OD], h1[HID];
 #pragma unroll
-    for (int i = 0; i < OD; i++) x[i] = obs[i];
+    for (int i = 0; i < OD; i++) {
+        if constexpr (NORM) x[i] = obs_normalized(obs[i], nm[i], nm[OD + i]);
+        else x[i] = obs[i];
+    }
 #pragma unroll
     for (int j = 0; j < HID; j++) {
         float acc = B0[j];
@@ -400,15 +428,16 @@ __device__ __forceinline__ float value_tower(const float* __restrict__ prm, cons
 
 // The value tower where the scan needs it and nowhere else: rows [0, TN) are the chunk's entries, of which those with done code 2 get
 // V(terminal_obs) parked in ret (the scan reads it before it writes ret); rows [TN, TN + N) are the last observations, V parked in adv[T-1].
-template <int OD>
+template <int OD, bool NORM>
 __global__ __launch_bounds__(256) void so100_learn_values(const float* __restrict__ chunk, const float* __restrict__ tobs, const float* __restrict__ last_obs,
-                                                          const float* __restrict__ prm, long TN, int N, float* __restrict__ adv, float* __restrict__ ret) {
+                                                          const float* __restrict__ prm, long TN, int N, float* __restrict__ adv, float* __restrict__ ret,
+                                                          const float* __restrict__ nm) {
     constexpr int ROW = OD + ROW_EXTRA;
     const long r = (long)blockIdx.x*256 + threadIdx.x;
     if (r < TN) {
-        if (tobs != nullptr && chunk[r*ROW + OD + ROW_DONE] == 2.0f) ret[r] = value_tower<OD>(prm, tobs + r*OD);
+        if (tobs != nullptr && chunk[r*ROW + OD + ROW_DONE] == 2.0f) ret[r] = value_tower<OD, NORM>(prm, tobs + r*OD, nm);
     } else if (r < TN + N) {
-        adv[TN - N + (r - TN)] = value_tower<OD>(prm, last_obs + (r - TN)*OD);
+        adv[TN - N + (r - TN)] = value_tower<OD, NORM>(prm, last_obs + (r - TN)*OD, nm);
     }
 }
 
@@ -623,6 +652,101 @@ __global__ __launch_bounds__(256) void so100_learn_rn_init(double* __restrict__ 
     for (long i = (long)blockIdx.x*256 + threadIdx.x; i < len; i += (long)gridDim.x*256) state[i] = i == 1 ? 1.0 : i == 2 ? 1e-4 : 0.0;
 }
 
+// ---- observation normalisation (so100_learner_obs_norm_update / _fold) ----------------------------------------------------------------------
+// Moments: one workgroup per block of ON_BLOCK rows, thread j = row j of the block.  A thread widens its row's observations to fp64 and parks
+// them in LDS [dimension][slot]; the trees of all dimensions run side by side (one barrier per level, not per dimension), first over the values,
+// then over the squared deviations.  Merge: one workgroup; a thread per (dimension, group) folds its group's blocks in block order, then a thread
+// per dimension folds the groups in group order and applies the running update; thread 0 stores the count all dimensions share.  At 262 144
+// rows that is 1024 blocks, 16 groups: chains of 64 and of 16 merges.  Fold: one thread per first-layer row or copied parameter.
+constexpr int ON_MAX_OD = 15, ON_MERGE_THREADS = 256;
+constexpr long ON_MAX_ROWS = 1L << 24;
+
+// workspace: [B][od][2] doubles (mean, M2 of block b, dimension i), then [G][od][3] (n, mean, M2 of group g); sized for ON_MAX_OD
+constexpr long on_workspace_doubles(long rows) { return on_blocks(rows)*ON_MAX_OD*2 + on_groups(rows)*ON_MAX_OD*3; }
+
+__device__ __forceinline__ void on_tree(double* sh, int od, int tid) {
+    for (int w = ON_BLOCK/2; w > 0; w >>= 1) {
+        __syncthreads();
+        if (tid < w)
+            for (int i = 0; i < od; i++) sh[i*ON_BLOCK + tid] += sh[i*ON_BLOCK + tid + w];
+    }
+    __syncthreads();
+}
+
+template <int OD>
+__global__ __launch_bounds__(ON_BLOCK) void so100_learn_on_moments(const float* __restrict__ chunk, long rows, double* __restrict__ part) {
+    constexpr int od = OD, row = OD + ROW_EXTRA;
+    __shared__ double sh[ON_MAX_OD*ON_BLOCK];
+    __shared__ double bmean[ON_MAX_OD];
+    const int tid = threadIdx.x;
+    const long b = blockIdx.x, r = b*ON_BLOCK + tid;
+    const bool own = r < rows;
+    const long count = on_block_count(rows, b);
+    double x[OD];
+#pragma unroll
+    for (int i = 0; i < od; i++) { x[i] = own ? (double)chunk[(size_t)r*row + i] : 0.0; sh[i*ON_BLOCK + tid] = x[i]; }
+    on_tree(sh, od, tid);
+    if (tid < od) bmean[tid] = block_mean<double>(sh[tid*ON_BLOCK], (int)count);
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < od; i++) sh[i*ON_BLOCK + tid] = own ? squared_deviation<double>(x[i], bmean[i]) : 0.0;
+    on_tree(sh, od, tid);
+    if (tid < od) { double* o = part + ((size_t)b*od + tid)*2; o[0] = bmean[tid]; o[1] = sh[tid*ON_BLOCK]; }
+}
+
+__global__ __launch_bounds__(ON_MERGE_THREADS) void so100_learn_on_merge(const double* __restrict__ part, double* __restrict__ grp, int od, long rows,
+                                                                         double* __restrict__ state) {
+    const long B = on_blocks(rows), G = on_groups(rows);
+    const int tid = threadIdx.x;
+    for (long k = tid; k < G*od; k += ON_MERGE_THREADS) {
+        const long g = k/od; const int i = (int)(k - g*od);
+        const long b0 = g*ON_GROUP, b1 = b0 + ON_GROUP < B ? b0 + ON_GROUP : B;
+        double n, m, m2;
+        obs_group_merge<double>(part + 2*i, 2L*od, rows, b0, b1, n, m, m2);
+        double* o = grp + (size_t)k*3; o[0] = n; o[1] = m; o[2] = m2;
+    }
+    __threadfence_block();
+    __syncthreads();
+    double count = state[2*od];
+    __syncthreads();                                                        // every thread holds the old count before thread 0 stores the new one
+    if (tid < od) {
+        double mean = state[tid], var = state[od + tid];
+        obs_moment_update<double>(grp + 3*tid, 3L*od, G, rows, mean, var, count);
+        state[tid] = mean; state[od + tid] = var;
+        if (tid == 0) state[2*od] = count;
+    }
+}
+
+struct FoldArgs { int od, P, oW0[2], oB0[2]; };                             // the two towers' first layers in the block
+
+__global__ __launch_bounds__(256) void so100_learn_on_fold(const double* __restrict__ state, double epsilon, const float* __restrict__ params,
+                                                           float* __restrict__ folded, float* __restrict__ norm, FoldArgs a) {
+    __shared__ double mean[ON_MAX_OD], inv[ON_MAX_OD];
+    const int tid = threadIdx.x, od = a.od;
+    if (tid < od) { mean[tid] = state[tid]; inv[tid] = obs_inv_std<double>(state[od + tid], epsilon); }
+    __syncthreads();
+    if (blockIdx.x == 0 && tid < od) { norm[tid] = (float)mean[tid]; norm[od + tid] = (float)inv[tid]; }
+    const int p = blockIdx.x*256 + tid;
+    if (p >= a.P) return;
+    for (int tw = 0; tw < 2; tw++) {
+        if (p >= a.oW0[tw] && p < a.oW0[tw] + HID*od) return;               // written by its row's thread below
+        if (p >= a.oB0[tw] && p < a.oB0[tw] + HID) {
+            const int j = p - a.oB0[tw];
+            float w[ON_MAX_OD], b;
+            obs_fold_row<double>(od, params + a.oW0[tw] + j*od, params[p], mean, inv, w, b);
+            for (int i = 0; i < od; i++) folded[a.oW0[tw] + j*od + i] = w[i];
+            folded[p] = b;
+            return;
+        }
+    }
+    folded[p] = params[p];
+}
+
+__global__ __launch_bounds__(64) void so100_learn_on_init(double* __restrict__ state, int od) {
+    const int i = threadIdx.x;
+    if (i <= 2*od) state[i] = i < od ? 0.0 : i < 2*od ? 1.0 : 1e-4;
+}
+
 // ---- the whole update (so100_learner_update) ---------------------------------------------------------------------------------------------
 // One thread per position of the epoch, grid-stride; the only traffic is the store.  The walk of shuffle_index diverges (fewer than 4 maps
 // per position on average, 26 at the worst seen), which costs a wave its longest lane's maps and nothing else: no LDS, no atomics.
@@ -667,6 +791,7 @@ struct so100_learner {
     float* sq_block = nullptr;     // [reduce_blocks(P, NSTAT_EX)] sum of squares per block of the reduction
     float* mb_stats = nullptr;     // [2] mean and std of the minibatch's advantages (normalize_advantage = 1)
     float* ev_part = nullptr;      // [EV_GRID_MAX][EV_PART] per-workgroup moments of so100_learner_explained_variance
+    const float* obs_norm = nullptr;       // the caller's [2 obs_dim] normaliser (so100_learner_set_obs_norm); null: off
 };
 
 static AdamArgs adam_args(const so100_learner_config& c, double lr, int adam_step, int mb) {
@@ -711,6 +836,7 @@ static int minibatch_step(so100_learner* L, const so100_minibatch_io* io, const 
     A.chunk = io->rollout_dev; A.num_samples = (long)io->num_samples; A.idx = io->idx_dev; A.mb = io->mb;
     A.adv = io->adv_dev; A.ret = io->ret_dev; A.adv_stats = io->adv_stats_dev; A.params = io->params_dev; A.partial = L->partial;
     A.clip = L->cfg.clip_range; A.vf_coef = L->cfg.vf_coef;
+    const bool norm = L->obs_norm != nullptr;
     if (terms) {
         A.ent_coef = terms->ent_coef; A.clip_vf = terms->clip_range_vf > 0.0f ? terms->clip_range_vf : 0.0f; A.state = state_dev;
         if (terms->normalize_advantage == 1) {
@@ -720,14 +846,16 @@ static int minibatch_step(so100_learner* L, const so100_minibatch_io* io, const 
         const int nblk = reduce_blocks(L->P, NSTAT_EX);
         const AdamArgs a = adam_args(L->cfg, terms->lr < 0.0 ? L->cfg.lr : terms->lr, io->adam_step, io->mb);
         const TermsArgs t = { terms->ent_coef, L->cfg.vf_coef, terms->target_kl > 0.0f ? (float)(1.5*(double)terms->target_kl) : 0.0f };
-        SO100_WITH_OBS_DIM(L->cfg.obs_dim, hipLaunchKernelGGL((so100_learn_grad<OD, true>), dim3((unsigned)G), threads, 0, st, A););
+        if (norm) { SO100_WITH_OBS_DIM(L->cfg.obs_dim, hipLaunchKernelGGL((so100_learn_grad_norm<OD, true>), dim3((unsigned)G), threads, 0, st, A, L->obs_norm);); }
+        else { SO100_WITH_OBS_DIM(L->cfg.obs_dim, hipLaunchKernelGGL((so100_learn_grad<OD, true>), dim3((unsigned)G), threads, 0, st, A);); }
         hipLaunchKernelGGL(so100_learn_reduce<NSTAT_EX>, dim3((unsigned)nblk), threads, 0, st, (const float*)L->partial, G, L->P, L->gsum, L->sq_block, A.state);
         hipLaunchKernelGGL(so100_learn_adam_ex, pblocks, threads, 0, st, (const float*)L->gsum, (const float*)L->sq_block, nblk, L->P,
                            io->params_dev, io->adam_m_dev, io->adam_v_dev, io->grads_dev, out_dev, state_dev, a, t);
     } else {
         const int nblk = reduce_blocks(L->P, NSTAT);
         const AdamArgs a = adam_args(L->cfg, L->cfg.lr, io->adam_step, io->mb);
-        SO100_WITH_OBS_DIM(L->cfg.obs_dim, hipLaunchKernelGGL((so100_learn_grad<OD, false>), dim3((unsigned)G), threads, 0, st, static_cast<const GradArgs&>(A)););
+        if (norm) { SO100_WITH_OBS_DIM(L->cfg.obs_dim, hipLaunchKernelGGL((so100_learn_grad_norm<OD, false>), dim3((unsigned)G), threads, 0, st, static_cast<const GradArgs&>(A), L->obs_norm);); }
+        else { SO100_WITH_OBS_DIM(L->cfg.obs_dim, hipLaunchKernelGGL((so100_learn_grad<OD, false>), dim3((unsigned)G), threads, 0, st, static_cast<const GradArgs&>(A));); }
         hipLaunchKernelGGL(so100_learn_reduce<NSTAT>, dim3((unsigned)nblk), threads, 0, st, (const float*)L->partial, G, L->P, L->gsum, L->sq_block, (const int32_t*)nullptr);
         hipLaunchKernelGGL(so100_learn_adam, pblocks, threads, 0, st, (const float*)L->gsum, (const float*)L->sq_block, nblk, L->P,
                            io->params_dev, io->adam_m_dev, io->adam_v_dev, io->grads_dev, out_dev, a);
@@ -776,8 +904,10 @@ static int advantages(so100_learner* L, const so100_advantages_io* io, const flo
     if (vblocks > 0x7fffffffL) return fail(SO100_E_INVALID, "%s: T*N is too large", fn);
     const hipStream_t st = (hipStream_t)stream;
     const bool boot = io->terminal_obs_chunk_dev != nullptr;
+    const float* nm = L->obs_norm;
+    if (nm) { SO100_WITH_OBS_DIM(L->cfg.obs_dim, hipLaunchKernelGGL((so100_learn_values<OD, true>), dim3((unsigned)vblocks), dim3(256), 0, st, io->rollout_dev, io->terminal_obs_chunk_dev, io->last_obs_dev, io->params_dev, TN, N, io->adv_dev, io->ret_dev, nm);); }
+    else { SO100_WITH_OBS_DIM(L->cfg.obs_dim, hipLaunchKernelGGL((so100_learn_values<OD, false>), dim3((unsigned)vblocks), dim3(256), 0, st, io->rollout_dev, io->terminal_obs_chunk_dev, io->last_obs_dev, io->params_dev, TN, N, io->adv_dev, io->ret_dev, nm);); }
     SO100_WITH_OBS_DIM(L->cfg.obs_dim,
-        hipLaunchKernelGGL((so100_learn_values<OD>), dim3((unsigned)vblocks), dim3(256), 0, st, io->rollout_dev, io->terminal_obs_chunk_dev, io->last_obs_dev, io->params_dev, TN, N, io->adv_dev, io->ret_dev);
         hipLaunchKernelGGL((so100_learn_gae<OD>), dim3((unsigned)((N + 63)/64)), dim3(64), 0, st, io->rollout_dev, reward_dev, T, N, boot, L->cfg.gamma, L->cfg.gae_lambda, io->adv_dev, io->ret_dev););
     hipLaunchKernelGGL(so100_learn_adv_stats, dim3(1), dim3(ADV_THREADS), 0, st, (const float*)io->adv_dev, TN, io->adv_stats_dev);
     const hipError_t e = hipGetLastError();
@@ -980,6 +1110,68 @@ int so100_learner_normalize_rewards(so100_learner* L, const so100_reward_norm_io
     SO100_ON_DEVICE(L->cfg.device, fn);
     enqueue_reward_norm(L, io, T, N, (hipStream_t)stream);
     HIP_TRY(hipGetLastError(), SO100_E_LAUNCH, "so100_learner_normalize_rewards: ");
+    return 0;
+}
+
+int so100_learner_obs_norm_init(so100_learner* L, double* state_dev, void* stream) {
+    const char* const fn = "so100_learner_obs_norm_init";
+    if (!L) return fail(SO100_E_INVALID, "%s: null argument", fn);
+    if (!state_dev) return fail(SO100_E_INVALID, "%s: the state pointer is required", fn);
+    SO100_ON_DEVICE(L->cfg.device, fn);
+    hipLaunchKernelGGL(so100_learn_on_init, dim3(1), dim3(64), 0, (hipStream_t)stream, state_dev, L->cfg.obs_dim);
+    HIP_TRY(hipGetLastError(), SO100_E_LAUNCH, "so100_learner_obs_norm_init: ");
+    return 0;
+}
+
+int64_t so100_learner_obs_norm_workspace(int32_t T, int32_t N) {
+    if (T < 1 || N < 1) return (int64_t)fail(SO100_E_INVALID, "so100_learner_obs_norm_workspace: T and N must be >= 1, got %d and %d", T, N);
+    if ((long)T*(long)N > ON_MAX_ROWS) return (int64_t)fail(SO100_E_INVALID, "so100_learner_obs_norm_workspace: T*N must be <= 16777216, got %ld", (long)T*(long)N);
+    return (int64_t)(on_workspace_doubles((long)T*(long)N)*(long)sizeof(double));
+}
+
+int so100_learner_obs_norm_update(so100_learner* L, const so100_obs_norm_io* io, int32_t T, int32_t N, void* stream) {
+    const char* const fn = "so100_learner_obs_norm_update";
+    if (!L || !io) return fail(SO100_E_INVALID, "%s: null argument", fn);
+    if (T < 1) return fail(SO100_E_INVALID, "%s: T must be >= 1, got %d", fn, T);
+    if (N < 1) return fail(SO100_E_INVALID, "%s: N must be >= 1, got %d", fn, N);
+    const long rows = (long)T*(long)N;
+    if (rows > ON_MAX_ROWS) return fail(SO100_E_INVALID, "%s: T*N must be <= 16777216, got %ld", fn, rows);
+    if (!io->rollout_dev || !io->state_dev || !io->workspace_dev) return fail(SO100_E_INVALID, "%s: rollout/state/workspace pointers are required", fn);
+    const long need = on_workspace_doubles(rows)*(long)sizeof(double);
+    if (io->workspace_bytes < need) return fail(SO100_E_INVALID, "%s: the workspace holds %ld bytes, T = %d and N = %d need %ld", fn, (long)io->workspace_bytes, T, N, need);
+    if (((uintptr_t)io->workspace_dev & 7u) != 0) return fail(SO100_E_INVALID, "%s: the workspace must be 8-byte aligned", fn);
+    SO100_ON_DEVICE(L->cfg.device, fn);
+    const hipStream_t st = (hipStream_t)stream;
+    const int od = L->cfg.obs_dim;
+    const long B = on_blocks(rows);
+    double* part = (double*)io->workspace_dev;
+    double* grp = part + (size_t)B*od*2;
+    SO100_WITH_OBS_DIM(od, hipLaunchKernelGGL((so100_learn_on_moments<OD>), dim3((unsigned)B), dim3(ON_BLOCK), 0, st, io->rollout_dev, rows, part););
+    hipLaunchKernelGGL(so100_learn_on_merge, dim3(1), dim3(ON_MERGE_THREADS), 0, st, (const double*)part, grp, od, rows, io->state_dev);
+    HIP_TRY(hipGetLastError(), SO100_E_LAUNCH, "so100_learner_obs_norm_update: ");
+    return 0;
+}
+
+int so100_learner_obs_norm_fold(so100_learner* L, const double* state_dev, double epsilon, const float* params_dev, float* folded_params_dev, float* norm_dev,
+                                void* stream) {
+    const char* const fn = "so100_learner_obs_norm_fold";
+    if (!L) return fail(SO100_E_INVALID, "%s: null argument", fn);
+    if (!state_dev || !params_dev || !folded_params_dev || !norm_dev) return fail(SO100_E_INVALID, "%s: state/params/folded_params/norm pointers are required", fn);
+    if (!(epsilon >= 0.0)) return fail(SO100_E_INVALID, "%s: epsilon must be >= 0", fn);
+    if (folded_params_dev == params_dev) return fail(SO100_E_INVALID, "%s: the folded block must not be the plain block", fn);
+    SO100_ON_DEVICE(L->cfg.device, fn);
+    const int od = L->cfg.obs_dim;
+    FoldArgs a;
+    a.od = od; a.P = L->P;
+    a.oW0[0] = tensor_offset(T_pi_w0, od); a.oB0[0] = tensor_offset(T_pi_b0, od); a.oW0[1] = tensor_offset(T_vf_w0, od); a.oB0[1] = tensor_offset(T_vf_b0, od);
+    hipLaunchKernelGGL(so100_learn_on_fold, dim3((unsigned)((L->P + 255)/256)), dim3(256), 0, (hipStream_t)stream, state_dev, epsilon, params_dev, folded_params_dev, norm_dev, a);
+    HIP_TRY(hipGetLastError(), SO100_E_LAUNCH, "so100_learner_obs_norm_fold: ");
+    return 0;
+}
+
+int so100_learner_set_obs_norm(so100_learner* L, const float* norm_dev) {
+    if (!L) return fail(SO100_E_INVALID, "so100_learner_set_obs_norm: null argument");
+    L->obs_norm = norm_dev;
     return 0;
 }
 

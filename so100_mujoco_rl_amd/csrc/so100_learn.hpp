@@ -7,6 +7,7 @@
 //   ppo_loss_head_ex    the same with SB3's entropy bonus, value clipping and approx_kl
 //   clip_adam_update    clip_grad_norm_'s scaling + one torch.optim.Adam step of one parameter
 //   return_step .. reward_scale   SB3's VecNormalize(norm_reward=True): the running return, block moments, Chan merge, running moments, scale
+//   obs_block_tree_sum .. obs_normalized   SB3's VecNormalize(norm_obs=True): block moments, the two-level Chan merge, the fold, the normalised load
 //   shuffle_index       one entry of an epoch's permutation (the one piece that reads the simulator: see there)
 #pragma once
 #include <stdint.h>
@@ -254,6 +255,65 @@ template <class OUT, class S>
 SO100_LHD OUT reward_scale(S r, S denom, S clip) {
     const S x = r/denom;
     return (OUT)(x < -clip ? -clip : x > clip ? clip : x);
+}
+
+// ---- observation normalisation ------------------------------------------------------------------------------------------------------------
+// SB3's VecNormalize(norm_obs=True) folded into the policy, as include/so100_learn.h ("Observation normalisation") specifies it.  The moments
+// and the fold are fp64 (S = double in the kernels and in tests/_obsnormcheck), the load is the learner's fp32.  chan_merge and
+// running_moment_update above are shared with the reward half.
+constexpr int ON_BLOCK = 256;      // rows per block of the moments: one workgroup
+constexpr int ON_GROUP = 64;       // blocks per group of the merge
+
+constexpr long on_blocks(long rows) { return (rows + ON_BLOCK - 1)/ON_BLOCK; }
+constexpr long on_groups(long rows) { return (on_blocks(rows) + ON_GROUP - 1)/ON_GROUP; }
+constexpr long on_block_count(long rows, long b) { return rows - b*ON_BLOCK < ON_BLOCK ? rows - b*ON_BLOCK : ON_BLOCK; }
+
+// The block moments' fixed tree over ON_BLOCK slots: slot j += slot j + w for w = 128, 64 .. 1; slot 0 ends as the sum.  The kernel runs the
+// same additions with thread j owning slot j; slots past the block's count hold 0.
+template <class S>
+SO100_LHD S obs_block_tree_sum(S* slot) {
+    for (int w = ON_BLOCK/2; w > 0; w >>= 1)
+        for (int j = 0; j < w; j++) slot[j] += slot[j + w];
+    return slot[0];
+}
+
+// One group of one dimension: its first block's (n, mean, M2) absorbs the group's other blocks in block order.  part: the blocks' (mean, M2)
+// pairs of this dimension, `stride` scalars from block to block; blocks [b0, b1) of a chunk of `rows` rows.
+template <class S>
+SO100_LHD void obs_group_merge(const S* part, long stride, long rows, long b0, long b1, S& n, S& mean, S& m2) {
+    n = S(on_block_count(rows, b0)); mean = part[b0*stride]; m2 = part[b0*stride + 1];
+    for (long b = b0 + 1; b < b1; b++) chan_merge<S>(n, mean, m2, S(on_block_count(rows, b)), part[b*stride], part[b*stride + 1]);
+}
+
+// One dimension's batch moments from its groups' (n, mean, M2) triples (`stride` scalars from group to group, merged in group order), then the
+// running update with the batch as one sample of `rows` rows.  count is advanced too: the caller stores it once for all dimensions.
+template <class S>
+SO100_LHD void obs_moment_update(const S* grp, long stride, long groups, long rows, S& mean, S& var, S& count) {
+    S n = grp[0], bm = grp[1], m2 = grp[2];
+    for (long g = 1; g < groups; g++) chan_merge<S>(n, bm, m2, grp[g*stride], grp[g*stride + 1], grp[g*stride + 2]);
+    running_moment_update<S>(mean, var, count, bm, m2/S(rows), S(rows));
+}
+
+template <class S>
+SO100_LHD S obs_inv_std(S var, S epsilon) { return S(1)/lsqrt(var + epsilon); }
+
+// the fold of one first-layer row j: w [od] and b of the plain block -> w_out [od], b_out; the fp64 products are rounded once, at the store
+template <class S>
+SO100_LHD void obs_fold_row(int od, const float* w, float b, const S* mean, const S* inv_std, float* w_out, float& b_out) {
+    S s = S(0);
+    for (int i = 0; i < od; i++) {
+        const S wf = S(w[i])*inv_std[i];
+        s += wf*mean[i];
+        w_out[i] = (float)wf;
+    }
+    b_out = (float)(S(b) - s);
+}
+
+// the learner's load of one observation entry: one subtraction, then one multiplication, each rounded (the specification's form: a bitwise test
+// rests on it, so the product is kept from contracting with anything)
+SO100_LHD float obs_normalized(float x, float mean, float inv_std) {
+    const float d = x - mean;
+    return d*inv_std;
 }
 
 }  // namespace learn

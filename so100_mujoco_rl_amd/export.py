@@ -20,8 +20,13 @@ class DeterministicPolicy(nn.Module):
         return self.net(obs).clamp(-1.0, 1.0)
 
 
-def export_policy(state_dict, path):
-    """state_dict: an SB3 ActorCriticPolicy / ppo.ActorCritic state_dict.  Returns the scripted module."""
+def export_policy(state_dict, path, obs_norm=None):
+    """state_dict: an SB3 ActorCriticPolicy / ppo.ActorCritic state_dict.  obs_norm: the observation-normalisation state the policy was trained
+    under (PPO.obs_norm_state(), the <model>.obs_norm.pt side file), folded into the first layer so that the exported module takes RAW
+    observations; None: the policy was trained on raw observations.  Returns the scripted module."""
+    if obs_norm is not None:
+        from .ppo import fold_obs_norm
+        state_dict = fold_obs_norm(state_dict, obs_norm)
     w0 = state_dict["mlp_extractor.policy_net.0.weight"]
     m = DeterministicPolicy(w0.shape[1])
     with torch.no_grad():

@@ -129,13 +129,19 @@ class RewardNormIO(C.Structure):
                 ("workspace_bytes", C.c_int64), ("clip_reward", C.c_double), ("epsilon", C.c_double)]
 
 
+class ObsNormIO(C.Structure):
+    _fields_ = [("rollout_dev", C.c_void_p), ("state_dev", C.c_void_p), ("workspace_dev", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
+OBS_NORM_EPSILON = 1e-8                                # SB3 VecNormalize's epsilon
 REWARD_NORM_EPSILON, REWARD_NORM_CLIP = 1e-8, 10.0     # SB3 VecNormalize's epsilon and clip_reward
 REWARD_NORM_INIT = (0.0, 1.0, 1e-4)                    # mean, var, count of a fresh RunningMeanStd (so100_learner_reward_norm_init)
 
 LEARN_EXPORTS = ["so100_learner_num_params", "so100_learner_param_offset", "so100_learner_param_size", "so100_learner_create", "so100_learner_destroy",
                  "so100_learner_advantages", "so100_learner_minibatch_step", "so100_learner_minibatch_step_ex", "so100_learner_explained_variance",
                  "so100_learner_shuffle", "so100_learner_update", "so100_learner_reward_norm_workspace", "so100_learner_reward_norm_init",
-                 "so100_learner_normalize_rewards", "so100_learner_advantages_r", "so100_learner_update_r"]
+                 "so100_learner_normalize_rewards", "so100_learner_advantages_r", "so100_learner_update_r", "so100_learner_obs_norm_init",
+                 "so100_learner_obs_norm_workspace", "so100_learner_obs_norm_update", "so100_learner_obs_norm_fold", "so100_learner_set_obs_norm"]
 LEARNER_STATS = ["policy_loss", "value_loss", "clip_fraction", "grad_norm"]          # stats_dev[4] of so100_learner_minibatch_step
 LEARNER_DIAG = LEARNER_STATS + ["approx_kl", "entropy_loss", "loss", "value_clip_fraction"]       # diag_dev[8] of so100_learner_minibatch_step_ex
 NORMALIZE_ADVANTAGE = {"batch": 0, "minibatch": 1}                                   # so100_ppo_terms.normalize_advantage
@@ -195,6 +201,11 @@ def load():
         L.so100_learner_normalize_rewards.argtypes = [C.c_void_p, C.POINTER(RewardNormIO), C.c_int32, C.c_int32, C.c_void_p]
         L.so100_learner_advantages_r.argtypes = [C.c_void_p, C.POINTER(AdvantagesIO), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
         L.so100_learner_update_r.argtypes = [C.c_void_p, C.POINTER(UpdateIO), C.POINTER(RewardNormIO), C.c_void_p]
+        L.so100_learner_obs_norm_init.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.so100_learner_obs_norm_workspace.argtypes = [C.c_int32, C.c_int32]; L.so100_learner_obs_norm_workspace.restype = C.c_int64
+        L.so100_learner_obs_norm_update.argtypes = [C.c_void_p, C.POINTER(ObsNormIO), C.c_int32, C.c_int32, C.c_void_p]
+        L.so100_learner_obs_norm_fold.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.so100_learner_set_obs_norm.argtypes = [C.c_void_p, C.c_void_p]
         if L.so100_abi_version() != ABI_VERSION:
             raise So100Error("libso100sim.so ABI version mismatch")
         _lib = L
@@ -578,6 +589,42 @@ class So100Learner(_Handle):
         elements.  The chunk is read only.  Three launches."""
         io = self._reward_norm_io(rollout, state, rewards, workspace, clip_reward, epsilon)
         _check(self.L.so100_learner_normalize_rewards(self.h, C.byref(io), rollout.shape[0], rollout.shape[1], self._stream()), "so100_learner_normalize_rewards")
+
+    # ---- observation normalisation (SB3 VecNormalize's observation half, folded; include/so100_learn.h "Observation normalisation") ------------
+    @staticmethod
+    def obs_norm_workspace_bytes(T, N):
+        n = load().so100_learner_obs_norm_workspace(T, N)
+        if n < 0:
+            raise So100Error(f"so100_learner_obs_norm_workspace failed ({n}): {load().so100_last_error().decode()}")
+        return n
+
+    def obs_norm_init(self, state):
+        """state: float64 [2 obs_dim + 1] on the device <- mean 0, var 1, count 1e-4"""
+        _check(self.L.so100_learner_obs_norm_init(self.h, _ptr(state, torch.float64, (2 * self.obs_dim + 1,), self.device), self._stream()), "so100_learner_obs_norm_init")
+
+    def obs_norm_update(self, rollout, state, workspace):
+        """state float64 [2 obs_dim + 1] (mean, var, count) absorbs the T*N observation rows of the packed chunk (read only); workspace: float64,
+        obs_norm_workspace_bytes(T, N) // 8 elements.  Two launches."""
+        T, N = rollout.shape[0], rollout.shape[1]
+        d = self.device
+        if workspace.dtype != torch.float64 or workspace.dim() != 1:
+            raise So100Error("the observation-normalisation workspace is a 1-d float64 tensor (obs_norm_workspace_bytes(T, N) // 8 elements)")
+        io = ObsNormIO(_ptr(rollout, torch.float32, (T, N, self.obs_dim + 10), d), _ptr(state, torch.float64, (2 * self.obs_dim + 1,), d),
+                       _ptr(workspace, torch.float64, (workspace.numel(),), d), workspace.numel() * 8)
+        _check(self.L.so100_learner_obs_norm_update(self.h, C.byref(io), T, N, self._stream()), "so100_learner_obs_norm_update")
+
+    def obs_norm_fold(self, state, params, folded, norm, epsilon=OBS_NORM_EPSILON):
+        """folded [P] <- params with both towers' first layers folded over (mean, 1/sqrt(var + epsilon)) of state, the other tensors copied;
+        norm float32 [2 obs_dim] <- (mean, inv_std).  One launch."""
+        f, d, P = torch.float32, self.device, self.num_params
+        _check(self.L.so100_learner_obs_norm_fold(self.h, _ptr(state, torch.float64, (2 * self.obs_dim + 1,), d), epsilon, _ptr(params, f, (P,), d),
+                                                  _ptr(folded, f, (P,), d), _ptr(norm, f, (2 * self.obs_dim,), d), self._stream()), "so100_learner_obs_norm_fold")
+
+    def set_obs_norm(self, norm):
+        """norm: float32 [2 obs_dim] on the device (obs_norm_fold's), read by every later advantages / minibatch step / update when its kernels
+        run; None: off.  The handle keeps the tensor alive."""
+        self._obs_norm = norm
+        _check(self.L.so100_learner_set_obs_norm(self.h, _ptr(norm, torch.float32, (2 * self.obs_dim,), self.device)), "so100_learner_set_obs_norm")
 
     def _minibatch_io(self, rollout, idx, adv, ret, adv_stats, params, adam_m, adam_v, adam_step, stats, grads):
         """the so100_minibatch_io of both steps.  idx: an int64 [mb] tensor of flat indices t*N + n in any order, or an int mb for rows 0..mb-1"""

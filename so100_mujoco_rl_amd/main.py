@@ -3,7 +3,7 @@
     python -m so100_mujoco_rl_amd.main -a PPO [-m MODEL] train  -e Env01-v1 [--envs 4096] [--iters N] [--learner torch|fused] [--shuffle torch|device]
                                                                [--ent-coef C] [--clip-range-vf C] [--target-kl K]
                                                                [--normalize-advantage batch|minibatch] [--lr-schedule constant|linear]
-                                                               [--normalize-reward]
+                                                               [--normalize-reward] [--normalize-obs]
     python -m so100_mujoco_rl_amd.main -a PPO [-m MODEL] test   -e Env01-v1 [--show-io] [--show-i]
     python -m so100_mujoco_rl_amd.main -a PPO [-m MODEL] record -e Env01-v1 [--steps 3000] [--video/--no-video]
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 -m so100_mujoco_rl_amd.main -a PPO train -e Env01-v1     # 8 x 4096 envs
@@ -30,7 +30,7 @@ from .callbacks import EvalCallback, StopTrainingOnNoModelImprovement, StopTrain
 from .collector import RolloutCollector
 from .ddpg import DDPG, DDPGPolicy
 from .lib import F_REFERENCE
-from .ppo import PPO, ActorCritic, FusedPPO
+from .ppo import PPO, ActorCritic, FusedPPO, fold_obs_norm
 from .rollout import broadcast_policy
 from .vec_env import So100VecEnv, kind_from_id
 
@@ -56,8 +56,15 @@ NATIVE_ALGORITHMS = ("PPO", "DDPG")
 
 
 def _load_native(path, obs_dim, device, algorithm="PPO"):
+    """the policy of a model file, taking RAW observations: with <model>.obs_norm.pt beside it (train --normalize-obs) the weights are folded over
+    the saved statistics; without it the file's own weights run"""
     net = (DDPGPolicy(obs_dim) if algorithm == "DDPG" else ActorCritic(obs_dim)).to(device)
-    net.load_state_dict(torch.load(path, map_location=device, weights_only=True))
+    sd = torch.load(path, map_location=device, weights_only=True)
+    side = _obs_norm_path(path)
+    if algorithm == "PPO" and os.path.isfile(side):
+        sd = fold_obs_norm(sd, torch.load(side, map_location="cpu", weights_only=True))
+        logger.info(f"Observation normalisation: folded the statistics of {side} into the policy")
+    net.load_state_dict(sd)
     return net
 
 
@@ -92,8 +99,12 @@ def cli(ctx, algorithm, model):
               help="minibatch permutations of --learner fused: torch.randperm (torch) or the library's, a function of seed and epoch; the whole update is then one call (device)")
 @click.option("--normalize-reward", is_flag=True, default=False,
               help="train on rewards divided by the running std of the envs' discounted returns (SB3 VecNormalize(norm_reward=True)); the state is saved beside each model")
+@click.option("--normalize-obs", is_flag=True, default=False,
+              help="train on observations normalised by their running mean and std (SB3 VecNormalize(norm_obs=True), folded into the policy's first layer); "
+                   "the statistics are saved beside each model")
 @click.pass_context
-def train(ctx, environment, envs, iters, seed, learner_kind, ent_coef, clip_range_vf, target_kl, normalize_advantage, lr_schedule, shuffle, normalize_reward):
+def train(ctx, environment, envs, iters, seed, learner_kind, ent_coef, clip_range_vf, target_kl, normalize_advantage, lr_schedule, shuffle, normalize_reward,
+          normalize_obs):
     algorithm = ctx.obj["ALGORITHM_NAME"]
     if shuffle == "device" and learner_kind != "fused":
         raise RuntimeError("--shuffle device is the fused learner's on-device shuffle: it needs --learner fused")
@@ -108,8 +119,10 @@ def train(ctx, environment, envs, iters, seed, learner_kind, ent_coef, clip_rang
         terms["lr_schedule"] = lambda progress: PPO_LR * progress
     if normalize_reward:
         terms["normalize_reward"] = True
+    if normalize_obs:
+        terms["normalize_obs"] = True
     if terms and algorithm != "PPO":
-        raise RuntimeError("--ent-coef, --clip-range-vf, --target-kl, --normalize-advantage, --lr-schedule and --normalize-reward are PPO's options")
+        raise RuntimeError("--ent-coef, --clip-range-vf, --target-kl, --normalize-advantage, --lr-schedule, --normalize-reward and --normalize-obs are PPO's options")
     kind = kind_from_id(environment)
     # Multi-GPU (one process per GPU under torchrun): rank r steps global envs [r*envs, (r+1)*envs); once per rollout chunk the
     # packed rollout goes to rank 0 over RCCL (the path's ONE collective), rank 0 learns, the policy is broadcast back.
@@ -119,6 +132,9 @@ def train(ctx, environment, envs, iters, seed, learner_kind, ent_coef, clip_rang
         # a gathered chunk is bootstrapped by each rank before the gather, which would put gamma * V under the normalisation
         raise RuntimeError("--normalize-reward runs on one GPU: with WORLD_SIZE > 1 the TimeLimit bootstrap is applied before the gather, ahead of the "
                            "normalisation (the multi-GPU order cannot be tested on one card, so it is not offered)")
+    if normalize_obs and distributed:
+        raise RuntimeError("--normalize-obs runs on one GPU: with WORLD_SIZE > 1 every rank's collector would need the folded policy of statistics only "
+                           "rank 0 holds (the multi-GPU order cannot be tested on one card, so it is not offered)")
     if distributed:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1"); os.environ.setdefault("MASTER_PORT", "29544")
         os.environ.setdefault("RANK", "0"); os.environ.setdefault("WORLD_SIZE", "1")
@@ -141,9 +157,9 @@ def train(ctx, environment, envs, iters, seed, learner_kind, ent_coef, clip_rang
         cls = getattr(stable_baselines3, algorithm)
         model_file = ctx.obj["MODEL_PATH"]
         sb3_terms = {k: v for k, v in terms.items() if k in ("ent_coef", "clip_range_vf", "target_kl")}
-        if normalize_reward:
+        if normalize_reward or normalize_obs:
             from stable_baselines3.common.vec_env import VecNormalize
-            env = VecNormalize(env, norm_obs=False, norm_reward=True)
+            env = VecNormalize(env, norm_obs=normalize_obs, norm_reward=normalize_reward)
         if "normalize_advantage" in terms:
             sb3_terms["normalize_advantage"] = True          # "minibatch" is SB3's own normalisation (and its default); it has no per-chunk one
         if "lr_schedule" in terms:
@@ -172,16 +188,29 @@ def train(ctx, environment, envs, iters, seed, learner_kind, ent_coef, clip_rang
                 logger.info(f"Reward normalisation: reloaded the running state from {side}")
             else:
                 logger.info(f"Reward normalisation: no saved state at {side}, starting from a fresh one")
+        if normalize_obs:
+            side = _obs_norm_path(ctx.obj["MODEL_PATH"])
+            if os.path.isfile(side):
+                learner.load_obs_norm_state(torch.load(side, map_location="cpu", weights_only=True))
+                logger.info(f"Observation normalisation: reloaded the running statistics from {side}")
+            else:
+                logger.info(f"Observation normalisation: no saved statistics at {side}, starting from fresh ones")
+        elif os.path.isfile(_obs_norm_path(ctx.obj["MODEL_PATH"])):
+            logger.warning(f"Observation normalisation: {_obs_norm_path(ctx.obj['MODEL_PATH'])} says this model was trained on normalised observations; "
+                           "without --normalize-obs training continues on raw ones")
     else:
         logger.info("Model: starting with new model")
     if normalize_reward:
         logger.info(f"Reward normalisation: on (running std of the discounted returns, clip {learner.clip_reward:g}); evaluation and reward/step stay in the env's scale")
+    if normalize_obs:
+        logger.info("Observation normalisation: on (running mean and std per dimension, updated once per chunk, folded into the first layer; no clipping)")
     if distributed:
         broadcast_policy(list(learner.net.state_dict().values()), src=0)          # every rank starts from rank 0's weights
     # fused on one GPU: the advantage kernel applies the TimeLimit bootstrap (the chunk keeps the env's rewards); a gathered chunk is bootstrapped
     # by each rank before the gather, as with the torch learner
     # --normalize-reward, either learner: the bootstrap must follow the normalisation, so it is deferred to the learner as well
-    col = RolloutCollector(env, learner.net.state_dict(), T=64, defer_bootstrap=(learner_kind == "fused" or normalize_reward) and not distributed)
+    # --normalize-obs: the collectors run the FOLDED policy on raw observations (policy_state_dict(); net.state_dict() without the option)
+    col = RolloutCollector(env, learner.policy_state_dict(), T=64, defer_bootstrap=(learner_kind == "fused" or normalize_reward) and not distributed)
     threshold = K.REWARD_THRESHOLD[kind]                     # StopTrainingOnRewardThreshold (ref: main.py:211; the registered threshold of the env id)
     steps, t0, it = 0, time.time(), 0
     ep_sum = ep_cnt = 0.0
@@ -192,7 +221,7 @@ def train(ctx, environment, envs, iters, seed, learner_kind, ent_coef, clip_rang
         # StopTrainingOnNoModelImprovement(max_no_improvement_evals=5, min_evals=10000)), restated for the built-in learner (callbacks.py).  The reference
         # evaluates every 20 000 timesteps of ONE env; here an update is 64 x envs timesteps, so an evaluation every EVAL_EVERY updates.
         eval_env = So100VecEnv(environment, N_EVAL_EPISODES, device=env.device, flags=F_REFERENCE, seed=seed + 1000)
-        eval_col = RolloutCollector(eval_env, learner.net.state_dict(), T=64, bootstrap_truncated=False)
+        eval_col = RolloutCollector(eval_env, learner.policy_state_dict(), T=64, bootstrap_truncated=False)
         eval_cb = EvalCallback(lambda: _evaluate(eval_env, eval_col, learner), lambda: _save_model(learner, os.path.join(save_dir, "best_model.pt")),
                                EVAL_EVERY, on_new_best=StopTrainingOnRewardThreshold(threshold), after_eval=StopTrainingOnNoModelImprovement(5, 10000), log=logger.info)
     while True:
@@ -224,7 +253,7 @@ def train(ctx, environment, envs, iters, seed, learner_kind, ent_coef, clip_rang
                 stop.fill_(1.0)
         if distributed:
             broadcast_policy(list(learner.net.state_dict().values()) + [stop], src=0)
-        col.load_policy(learner.net.state_dict())
+        col.load_policy(learner.policy_state_dict())
         if stop.item() > 0:
             break
     if lead and eval_cb.n_evals == 0:                        # a short run (--iters): one evaluation at the end, so that best_model exists
@@ -241,10 +270,23 @@ def _reward_norm_path(model_path):
     return os.path.splitext(model_path)[0] + ".reward_norm.pt"
 
 
+def _obs_norm_path(model_path):
+    """<model>.obs_norm.pt beside <model>.pt: the running statistics of --normalize-obs (the model file stays the raw, unfolded state_dict)"""
+    return os.path.splitext(model_path)[0] + ".obs_norm.pt"
+
+
 def _save_model(learner, path):
     torch.save(learner.net.state_dict(), path)
     if getattr(learner, "normalize_reward", False):
         torch.save(learner.reward_norm_state(), _reward_norm_path(path))
+    side = _obs_norm_path(path)
+    if getattr(learner, "normalize_obs", False):
+        torch.save(learner.obs_norm_state(), side)
+    elif os.path.isfile(side):
+        # a side file left by an earlier run with --normalize-obs belongs to the model this one replaces: `test` / `record` would fold its
+        # statistics into a policy trained on raw observations
+        os.remove(side)
+        logger.info(f"Observation normalisation: removed {side}, the statistics of the model this one replaces")
 
 
 PPO_LR = 3e-4                                                # the learners' default learning rate: where --lr-schedule linear starts
@@ -252,8 +294,8 @@ PPO_LR = 3e-4                                                # the learners' def
 
 def make_ppo_learner(kind, obs_dim, device, seed, **terms):
     """the built-in PPO learner `train --learner` names: "torch" (ppo.PPO, the default) or "fused" (ppo.FusedPPO, HIP kernels); terms: SB3's
-    remaining options (ent_coef, clip_range_vf, target_kl, normalize_advantage, lr_schedule) and normalize_reward, the same for both, and the
-    fused learner's shuffle"""
+    remaining options (ent_coef, clip_range_vf, target_kl, normalize_advantage, lr_schedule), normalize_reward and normalize_obs, the same for
+    both, and the fused learner's shuffle"""
     if kind == "torch":
         return PPO(obs_dim, device, lr=PPO_LR, seed=seed, **terms)
     if kind != "fused":
@@ -322,7 +364,7 @@ EVAL_EVERY = 50           # updates between evaluations (an update is 64 x envs 
 def _evaluate(eval_env, eval_col, learner):
     """SB3 evaluate_policy(deterministic=True) over N_EVAL_EPISODES episodes: one env per episode, the policy's MEAN action (log_std -> -30
     in the copy the kernels read), every env's FIRST episode after a reset; returns the mean episode reward."""
-    sd = {k: v.clone() for k, v in learner.net.state_dict().items()}
+    sd = {k: v.clone() for k, v in learner.policy_state_dict().items()}
     sd["log_std"] = torch.full_like(sd["log_std"], -30.0)
     eval_col.load_policy(sd)
     eval_env.reset_tensor(); eval_col._started = True

@@ -13,7 +13,12 @@ Both take SB3's remaining options -- ent_coef, clip_range_vf, per-minibatch adva
 all off by default (then the loss is the one above, to the bit), and return SB3's per-update diagnostics.
 normalize_reward=True is the reward half of SB3's VecNormalize(norm_reward=True): the rewards an update trains on are divided by the running
 standard deviation of the envs' discounted returns (include/so100_learn.h "Reward normalisation" is the specification); the state carries
-over from update to update and is saved and restored with reward_norm_state() / load_reward_norm_state()."""
+over from update to update and is saved and restored with reward_norm_state() / load_reward_norm_state().
+normalize_obs=True is the observation half (norm_obs=True), folded into the policy (include/so100_learn.h "Observation normalisation"): the
+learner normalises the raw observations of a chunk on load with the statistics the chunk was collected under, then merges the chunk into the
+statistics; policy_state_dict() is the state_dict folded over the current statistics, which a collector, an evaluation or an export runs on
+raw observations.  One iteration: update(chunk k), then collector.load_policy(learner.policy_state_dict()).  The state is saved and restored
+with obs_norm_state() / load_obs_norm_state(); net.state_dict() stays the unfolded network."""
 import math
 import os
 
@@ -93,6 +98,51 @@ def _reward_norm_from_state_dict(sd, device):
     return None if fresh else torch.cat([head, ret]).to(device)
 
 
+OBS_NORM_EPSILON = 1e-8                                   # VecNormalize's epsilon
+FIRST_LAYERS = ("mlp_extractor.policy_net.0", "mlp_extractor.value_net.0")       # the two towers' first layers: what the fold rewrites
+
+
+def _fresh_obs_norm(obs_dim, device):
+    """[2 obs_dim + 1] float64: mean 0, var 1, count 1e-4 (a fresh RunningMeanStd per observation dimension)"""
+    st = torch.zeros(2 * obs_dim + 1, dtype=torch.float64, device=device)
+    st[obs_dim:2 * obs_dim] = 1.0; st[2 * obs_dim] = 1e-4
+    return st
+
+
+def _obs_norm_state_dict(st):
+    o = (st.numel() - 1) // 2
+    st = st.detach().cpu()
+    return {"mean": st[:o].clone(), "var": st[o:2 * o].clone(), "count": st[2 * o].clone()}
+
+
+def _obs_norm_from_state_dict(sd, obs_dim, device):
+    mean, var = (torch.as_tensor(sd[k], dtype=torch.float64).reshape(-1) for k in ("mean", "var"))
+    if mean.numel() != obs_dim or var.numel() != obs_dim:
+        raise ValueError(f"the observation-normalisation state holds {mean.numel()} dimensions, the policy has {obs_dim}")
+    return torch.cat([mean, var, torch.as_tensor(sd["count"], dtype=torch.float64).reshape(1)]).to(device)
+
+
+def obs_norm_scale(obs_norm, epsilon=OBS_NORM_EPSILON):
+    """(mean, inv_std) in float64 on the CPU from a saved state ({"mean", "var", "count"}): inv_std = 1/sqrt(var + epsilon)"""
+    mean = torch.as_tensor(obs_norm["mean"], dtype=torch.float64).detach().cpu().reshape(-1)
+    var = torch.as_tensor(obs_norm["var"], dtype=torch.float64).detach().cpu().reshape(-1)
+    return mean, 1.0 / torch.sqrt(var + epsilon)
+
+
+def fold_obs_norm(state_dict, obs_norm, epsilon=OBS_NORM_EPSILON):
+    """The state_dict whose network, fed RAW observations, computes what `state_dict`'s computes on the normalised ones (include/so100_learn.h
+    "Observation normalisation"): in both towers' first layers W0' = W0 inv_std, b0' = b0 - W0' mean, formed in float64 and rounded once; the
+    other tensors are copied.  obs_norm: a saved state ({"mean", "var", "count"}).  The result lives where state_dict does."""
+    mean, inv = obs_norm_scale(obs_norm, epsilon)
+    out = {k: v.detach().clone() for k, v in state_dict.items()}
+    for layer in FIRST_LAYERS:
+        w, b = state_dict[layer + ".weight"].detach(), state_dict[layer + ".bias"].detach()
+        wf = w.double().cpu() * inv
+        out[layer + ".weight"] = wf.to(w.dtype).to(w.device)
+        out[layer + ".bias"] = (b.double().cpu() - (wf * mean).sum(1)).to(b.dtype).to(b.device)
+    return out
+
+
 def _done_code(b):
     """the chunk's done code as a tensor: 0 running, 1 terminated, 2 TimeLimit-truncated only"""
     return b["dones"] * (1.0 + b["truncated"].to(b["dones"].dtype)) if "truncated" in b else b["dones"]
@@ -104,9 +154,11 @@ class PPO:
 
     def __init__(self, obs_dim, device, lr=3e-4, gamma=0.99, gae_lambda=0.95, clip=0.2, epochs=4, minibatch=32768,
                  vf_coef=0.5, max_grad_norm=0.5, seed=0, use_graph=False, ent_coef=0.0, clip_range_vf=None, normalize_advantage="batch",
-                 target_kl=None, lr_schedule=None, normalize_reward=False, clip_reward=10.0):
+                 target_kl=None, lr_schedule=None, normalize_reward=False, clip_reward=10.0, normalize_obs=False):
         _set_terms(self, ent_coef, clip_range_vf, normalize_advantage, target_kl, lr_schedule)
         _set_reward_norm(self, normalize_reward, clip_reward)
+        self.normalize_obs, self.obs_dim = bool(normalize_obs), obs_dim
+        self._on = _fresh_obs_norm(obs_dim, device)           # mean, var, count: float64 on this learner's device
         torch.manual_seed(seed)
         self.net = ActorCritic(obs_dim).to(device)
         on_gpu = torch.device(device).type == "cuda"
@@ -180,6 +232,35 @@ class PPO:
     def load_reward_norm_state(self, sd):
         self._rn = _reward_norm_from_state_dict(sd, self.device)
 
+    # ---- observation normalisation: include/so100_learn.h's arithmetic in torch (fp64 moments and fold, fp32 load) --------------------------------
+    def obs_norm_state(self):
+        """{"mean", "var": float64 [obs_dim], "count": 0-d float64} on the CPU"""
+        return _obs_norm_state_dict(self._on)
+
+    def load_obs_norm_state(self, sd):
+        self._on = _obs_norm_from_state_dict(sd, self.obs_dim, self.device)
+
+    def policy_state_dict(self):
+        """what a collector, an evaluation or an export loads: with normalize_obs the state_dict folded over the current statistics (it takes
+        raw observations), otherwise net.state_dict() itself"""
+        return fold_obs_norm(self.net.state_dict(), self.obs_norm_state()) if self.normalize_obs else self.net.state_dict()
+
+    def _obs_scale(self):
+        """(mean, inv_std) as float32 on the device: the learner's load is (x - mean) * inv_std in fp32"""
+        o = self.obs_dim
+        return self._on[:o].float(), (1.0 / torch.sqrt(self._on[o:2 * o] + OBS_NORM_EPSILON)).float()
+
+    @torch.no_grad()
+    def _absorb_observations(self, obs):
+        """the moment update of one chunk: obs [T, N, obs_dim], the batch is its T*N rows"""
+        o = self.obs_dim
+        x = obs.reshape(-1, o).to(self.device, torch.float64)
+        bc = float(x.shape[0])
+        bm, bv = x.mean(0), x.var(0, unbiased=False)
+        mean, var, count = self._on[:o], self._on[o:2 * o], self._on[2 * o]
+        d, tot = bm - mean, count + bc
+        self._on = torch.cat([mean + d * bc / tot, (var * count + bv * bc + d * d * count * bc / tot) / tot, tot.reshape(1)])
+
     @torch.no_grad()
     def _normalized_rewards(self, rewards, ended):
         """rewards [T, N] float32 and ended [T, N] bool (the done code != 0) -> the normalised rewards, float32; advances self._rn"""
@@ -232,12 +313,18 @@ class PPO:
         S = self._s
         for k in ("obs", "actions", "rewards", "dones", "values", "log_probs", "last_obs"):
             S[k].copy_(b[k])
+        tobs = b.get("terminal_obs")
+        if self.normalize_obs:                                # under the statistics the chunk was collected with; the chunk itself keeps the raw observations
+            m, inv = self._obs_scale()
+            S["obs"].copy_((S["obs"] - m) * inv); S["last_obs"].copy_((S["last_obs"] - m) * inv)
+            if tobs is not None:
+                tobs = (tobs.to(self.device, torch.float32) - m) * inv
         if self.normalize_reward:
             S["rewards"].copy_(self._normalized_rewards(S["rewards"], S["dones"] != 0))
-        if "terminal_obs" in b:                               # a deferred TimeLimit bootstrap (RolloutCollector(defer_bootstrap=True)): after the normalisation
+        if tobs is not None:                                  # a deferred TimeLimit bootstrap (RolloutCollector(defer_bootstrap=True)): after the normalisation
             from .rollout import bootstrap_truncated
             with torch.no_grad():
-                bootstrap_truncated(S["rewards"], _done_code(b), b["terminal_obs"], self.net.value, self.gamma)
+                bootstrap_truncated(S["rewards"], _done_code(b), tobs, self.net.value, self.gamma)
         n = S["ret"].numel(); mb = S["idx"].numel()
         self._gae()
         applied, stopped = 0, False
@@ -253,6 +340,8 @@ class PPO:
             if stopped:
                 break
         S["idx"] = torch.zeros(mb, dtype=torch.long, device=self.device)
+        if self.normalize_obs:                                # after the update: the next chunk is collected, and trained on, under the new statistics
+            self._absorb_observations(b["obs"])
         # mean_reward = the ENV's mean reward per step (the collector takes it before its TimeLimit bootstrap adds gamma * V to the
         # truncated steps); S["rewards"] holds the bootstrapped rewards the advantages are computed from
         raw = b.get("raw_reward_mean")
@@ -274,11 +363,12 @@ class FusedPPO:
 
     def __init__(self, obs_dim, device, lr=3e-4, gamma=0.99, gae_lambda=0.95, clip=0.2, epochs=4, minibatch=32768,
                  vf_coef=0.5, max_grad_norm=0.5, seed=0, use_graph=False, ent_coef=0.0, clip_range_vf=None, normalize_advantage="batch",
-                 target_kl=None, lr_schedule=None, shuffle="torch", normalize_reward=False, clip_reward=10.0):
+                 target_kl=None, lr_schedule=None, shuffle="torch", normalize_reward=False, clip_reward=10.0, normalize_obs=False):
         from . import lib
         del use_graph
         _set_terms(self, ent_coef, clip_range_vf, normalize_advantage, target_kl, lr_schedule)
         _set_reward_norm(self, normalize_reward, clip_reward)
+        self.normalize_obs = bool(normalize_obs)
         if shuffle not in ("torch", "device"):
             raise ValueError(f"shuffle must be 'torch' or 'device', got {shuffle!r}")
         # "device": the whole update is one so100_learner_update call and the minibatches are a function of (seed, shuffle_epoch) alone --
@@ -307,6 +397,12 @@ class FusedPPO:
         self._shape = None
         self._rn_shape = None
         self._side = None
+        if self.normalize_obs:
+            # the running moments (float64 [2 obs_dim + 1]), the folded copy of the block the collector and the exports read, and the
+            # (mean, inv_std) pair the learner's kernels read: the fold writes the last two, after every update and whenever the state is loaded
+            self._on = _fresh_obs_norm(obs_dim, self.device)
+            self._folded = torch.zeros_like(self.params); self._norm = torch.zeros(2 * obs_dim, dtype=torch.float32, device=self.device)
+            self._on_shape = None
 
     def _handle(self):
         if self._learner is None:
@@ -314,7 +410,44 @@ class FusedPPO:
             if self.device.type != "cuda":
                 raise lib.So100Error(f"FusedPPO runs on a HIP device, not on {self.device}: there is no CPU fallback (use PPO)")
             self._learner = lib.So100Learner(self.obs_dim, self.device, max_minibatch=self.mb, **self._hyper)
+            if self.normalize_obs:
+                self._learner.obs_norm_fold(self._on, self.params, self._folded, self._norm)
+                self._learner.set_obs_norm(self._norm)
         return self._learner
+
+    def obs_norm_state(self):
+        """PPO.obs_norm_state: the device state as a dict of CPU tensors"""
+        return _obs_norm_state_dict(self._on if self.normalize_obs else _fresh_obs_norm(self.obs_dim, "cpu"))
+
+    def load_obs_norm_state(self, sd):
+        if not self.normalize_obs:
+            raise ValueError("this learner was built without normalize_obs")
+        self._on.copy_(_obs_norm_from_state_dict(sd, self.obs_dim, self.device))
+        if self._learner is not None:
+            self._learner.obs_norm_fold(self._on, self.params, self._folded, self._norm)
+
+    def policy_state_dict(self):
+        """PPO.policy_state_dict.  With normalize_obs: views of the folded block, folded here from the current parameters and statistics (one
+        launch on the current stream); a collector copies them in load_policy.  update() has folded already, so after an update this launch
+        repeats that one; it is kept because the parameters are plain tensors that anything may have written since (net.load_state_dict, a
+        checkpoint copied into .params), which nothing here can observe: a few microseconds buy a folded block that is never stale."""
+        if not self.normalize_obs:
+            return self.net.state_dict()
+        from . import lib
+        self._handle().obs_norm_fold(self._on, self.params, self._folded, self._norm)
+        layout, _ = lib.learner_layout(self.obs_dim)
+        by_key = {lib.SB3_STATE_DICT_KEYS[k]: self._folded[off:off + math.prod(shape)].view(shape) for k, (off, shape) in layout.items()}
+        return {k: by_key[k] for k in self.net.state_dict()}
+
+    def _absorb_observations(self, L, buf):
+        """after an update: the chunk's observations join the running moments and the fold is renewed, so that the next chunk is collected (once
+        policy_state_dict() has been loaded) and trained on under the new statistics.  Three launches, no host round trip."""
+        T, N = buf.shape[0], buf.shape[1]
+        if self._on_shape != (T, N):
+            self._on_ws = torch.zeros(L.obs_norm_workspace_bytes(T, N) // 8, dtype=torch.float64, device=self.device)
+            self._on_shape = (T, N)
+        L.obs_norm_update(buf, self._on, self._on_ws)
+        L.obs_norm_fold(self._on, self.params, self._folded, self._norm)
 
     def reward_norm_state(self):
         """PPO.reward_norm_state: the device state [mean, var, count, returns] as a dict of CPU tensors"""
@@ -420,6 +553,8 @@ class FusedPPO:
                     L.minibatch_step(buf, perm[i:i + mb], self._adv, self._ret, self._adv_stats, self.params, self.adam_m, self.adam_v, step, self._stats)
         if self._extended:
             self._out[23:25].copy_(self._state)
+        if self.normalize_obs:
+            self._absorb_observations(L, buf)
         st = self._read_out(b, buf, cur)                                 # the update's only synchronisation
         return self._results(st, first_step, last)
 
@@ -438,6 +573,8 @@ class FusedPPO:
         self.shuffle_epoch += self.epochs
         if self._extended:
             self._out[23:25].copy_(self._state)
+        if self.normalize_obs:
+            self._absorb_observations(L, buf)
         return self._results(self._read_out(b, buf, None), first_step, last)
 
     def _results(self, st, first_step, last):

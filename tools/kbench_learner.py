@@ -27,6 +27,13 @@ target_kl: every kernel returns at once).  Timed in alternation, `--rounds` time
 --normalize-reward: FusedPPO.update with and without normalize_reward, in both of its paths (the steps enqueued from Python; the one-call update),
 the four in alternation on the chunk of --part update, and the normalisation pass alone (so100_learner_normalize_rewards, three launches) per
 call.  The added time per update is held against one minibatch step of the same run (the update without the option / 32).
+
+    python tools/kbench_learner.py --normalize-obs [--parent-tree DIR] [--out profiles/learner_obsnorm_kbench.json] [--commit LABEL]
+
+--normalize-obs: the same for normalize_obs -- FusedPPO.update with and without it in both paths, in alternation, and the moments + fold passes
+alone (so100_learner_obs_norm_update + so100_learner_obs_norm_fold, three launches) per call.  --parent-tree: a built checkout of the parent
+commit; the update without the option is then timed in child processes of their own in the order parent, this, parent, this (the child
+imports the package of the tree it is given), and the document says whether this commit's figures lie inside the parent's own spread.
 """
 import argparse
 import json
@@ -36,7 +43,7 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.environ.get("SO100_KBENCH_TREE", ROOT))      # --part off_only in another tree (--parent-tree): that tree's package and library
 
 T, N, EPOCHS, MB = 64, 4096, 4, 32768
 
@@ -174,6 +181,81 @@ def part_rewnorm(obs_dim, rounds, reps, warmup):
     print("KBENCH " + json.dumps(res), flush=True)
 
 
+def _kbench_chunk(torch, net, o, dev, g):
+    """the chunk of part_update: noise the policy could have produced, rare episode ends"""
+    from so100_mujoco_rl_amd.rollout import RolloutChunk
+    c = RolloutChunk(T, N, o, dev)
+    c.buf.copy_(torch.randn(c.buf.shape, device=dev, generator=g))
+    with torch.no_grad():
+        v, lp = net.evaluate(c.buf[..., :o].reshape(-1, o), c.buf[..., o:o + 6].reshape(-1, 6))
+        c.buf[..., o + 8] = v.reshape(T, N); c.buf[..., o + 9] = lp.reshape(T, N)
+        c.buf[..., o + 7] = (torch.rand(T, N, device=dev, generator=g) < 1e-3).float() * 2.0
+    b = c.unpack(); b["last_obs"] = torch.randn(N, o, device=dev, generator=g); b["packed"] = c.buf
+    return c, b
+
+
+def _window(torch, fn, count):
+    e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize(); e0.record()
+    for _ in range(count):
+        fn()
+    e1.record(); torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / count
+
+
+def part_obsnorm(obs_dim, rounds, reps, warmup):
+    """--part obsnorm: FusedPPO.update off / on in both paths, in alternation, and the moments + fold passes alone"""
+    import torch
+    from so100_mujoco_rl_amd.ppo import FusedPPO
+    dev = torch.device("cuda", 0)
+    g = torch.Generator(device=dev); g.manual_seed(obs_dim)
+    o = obs_dim
+    learners = {f"{path}_{'on' if on else 'off'}": FusedPPO(o, dev, seed=0, shuffle=shuffle, normalize_obs=on)
+                for path, shuffle in (("three_call", "torch"), ("one_call", "device")) for on in (False, True)}
+    c, b = _kbench_chunk(torch, learners["three_call_off"].net, o, dev, g)
+    res = {"obs_dim": o, "T": T, "N": N, "epochs": EPOCHS, "minibatch": MB, "samples": T * N, "card": torch.cuda.get_device_name(0)}
+    f = learners["three_call_on"]
+    L = f._handle()
+    alone = lambda: f._absorb_observations(L, c.buf)
+    for learner in learners.values():
+        for _ in range(warmup):
+            learner.update(b)
+    _window(torch, alone, 20)
+    ms = {k: [] for k in learners}; us_alone = []
+    for _ in range(rounds):
+        for name, learner in learners.items():
+            ms[name].append(round(_window(torch, lambda: learner.update(b), reps), 4))
+        us_alone.append(round(_window(torch, alone, 200) * 1e3, 2))
+    med = lambda x: sorted(x)[len(x) // 2]
+    for name in ms:
+        res[name] = {"ms_per_update_rounds": ms[name], "ms_per_update": med(ms[name]), "updates_per_round": reps}
+    res["moments_and_fold_alone"] = {"us_per_call_rounds": us_alone, "us_per_call": med(us_alone), "calls_per_window": 200, "launches": 3}
+    for path in ("three_call", "one_call"):
+        off, on = res[path + "_off"]["ms_per_update"], res[path + "_on"]["ms_per_update"]
+        res[path + "_added_us_per_update"] = round((on - off) * 1e3, 1)
+        res[path + "_one_minibatch_step_us"] = round(off * 1e3 / (EPOCHS * (T * N // MB)), 1)
+    print("KBENCH " + json.dumps(res), flush=True)
+
+
+def part_off_only(obs_dim, rounds, reps, warmup):
+    """--part off_only: FusedPPO.update without any option in both paths, in the tree SO100_KBENCH_TREE names (the parent commit's or this one's)"""
+    import torch
+    from so100_mujoco_rl_amd.ppo import FusedPPO
+    dev = torch.device("cuda", 0)
+    g = torch.Generator(device=dev); g.manual_seed(obs_dim)
+    o = obs_dim
+    learners = {"three_call_off": FusedPPO(o, dev, seed=0), "one_call_off": FusedPPO(o, dev, seed=0, shuffle="device")}
+    c, b = _kbench_chunk(torch, learners["three_call_off"].net, o, dev, g)
+    for learner in learners.values():
+        for _ in range(warmup):
+            learner.update(b)
+    res = {"obs_dim": o, "has_normalize_obs": "normalize_obs" in FusedPPO.__init__.__code__.co_varnames}       # tells the two trees apart
+    for name, learner in learners.items():
+        ms = [round(_window(torch, lambda: learner.update(b), reps), 4) for _ in range(rounds)]
+        res[name] = {"ms_per_update_rounds": ms, "ms_per_update": sorted(ms)[len(ms) // 2], "updates_per_round": reps}
+    print("KBENCH " + json.dumps(res), flush=True)
+
+
 def part_terms(obs_dim, rounds, reps=200, warmup=20):
     import torch
     from so100_mujoco_rl_amd.lib import So100Learner
@@ -248,9 +330,10 @@ def part_train(learner, iters):
                                   "driver_summary": summary}), flush=True)
 
 
-def child(args, limit):
-    """one GPU step in a process of its own, under its own time limit; returns its KBENCH document"""
-    out = subprocess.run([sys.executable, os.path.abspath(__file__)] + args, capture_output=True, text=True, timeout=limit, cwd=ROOT)
+def child(args, limit, tree=None):
+    """one GPU step in a process of its own, under its own time limit; returns its KBENCH document.  tree: the checkout whose package it imports"""
+    env = dict(os.environ, SO100_KBENCH_TREE=os.path.abspath(tree)) if tree else None
+    out = subprocess.run([sys.executable, os.path.abspath(__file__)] + args, capture_output=True, text=True, timeout=limit, cwd=ROOT, env=env)
     if out.returncode != 0:
         raise SystemExit(f"step {args} failed ({out.returncode}); nothing further is started\n{out.stdout[-2000:]}{out.stderr[-2000:]}")
     return json.loads([l for l in out.stdout.splitlines() if l.startswith("KBENCH ")][-1][7:])
@@ -258,7 +341,9 @@ def child(args, limit):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--part", choices=("all", "update", "train", "terms", "rewnorm"), default="all")
+    ap.add_argument("--part", choices=("all", "update", "train", "terms", "rewnorm", "obsnorm", "off_only"), default="all")
+    ap.add_argument("--normalize-obs", action="store_true", help="time FusedPPO.update with and without normalize_obs; writes profiles/learner_obsnorm_kbench.json")
+    ap.add_argument("--parent-tree", default=None, help="--normalize-obs: a built checkout of the parent commit, for the option-off comparison")
     ap.add_argument("--normalize-reward", action="store_true", help="time FusedPPO.update with and without normalize_reward; writes profiles/learner_rewnorm_kbench.json")
     ap.add_argument("--terms", action="store_true", help="time the extended step with all terms on against the old one; writes profiles/learner_terms_kbench.json")
     ap.add_argument("--obs-dim", type=int, default=15); ap.add_argument("--learner", default="fused")
@@ -274,6 +359,30 @@ def main():
         return part_terms(a.obs_dim, a.rounds)
     if a.part == "rewnorm":
         return part_rewnorm(a.obs_dim, a.rounds, 100, a.warmup)
+    if a.part == "obsnorm":
+        return part_obsnorm(a.obs_dim, a.rounds, 100, a.warmup)
+    if a.part == "off_only":
+        return part_off_only(a.obs_dim, a.rounds, 100, a.warmup)
+    if a.normalize_obs:
+        doc = {"what": "FusedPPO.update (4 epochs x 8 minibatches of 32768 over 64 x 4096 samples) with and without normalize_obs, both paths, and the moments + fold alone",
+               "commit": a.commit, "steps": [child(["--part", "obsnorm", "--obs-dim", str(od), "--rounds", str(a.rounds)], 300) for od in (15, 8)]}
+        doc["card"] = doc["steps"][0]["card"]
+        if a.parent_tree:
+            order = [("parent", a.parent_tree), ("this", ROOT), ("parent", a.parent_tree), ("this", ROOT)]
+            runs = [dict(child(["--part", "off_only", "--obs-dim", "15", "--rounds", str(a.rounds)], 300, tree=tree), tree=name) for name, tree in order]
+            cmp = {"order": [name for name, _ in order], "runs": runs}
+            for path in ("three_call_off", "one_call_off"):
+                parent = [x for r in runs if r["tree"] == "parent" for x in r[path]["ms_per_update_rounds"]]
+                this = [r[path]["ms_per_update"] for r in runs if r["tree"] == "this"]
+                cmp[path] = {"parent_min_ms": min(parent), "parent_max_ms": max(parent), "this_medians_ms": this,
+                             "this_inside_parent_spread": all(min(parent) <= x <= max(parent) for x in this),
+                             "this_at_most_parent_max": all(x <= max(parent) for x in this)}
+            doc["option_off_against_parent"] = cmp
+        out = a.out if a.out != ap.get_default("out") else os.path.join(ROOT, "profiles", "learner_obsnorm_kbench.json")
+        with open(out, "w") as f:
+            json.dump(doc, f, indent=1); f.write("\n")
+        print(json.dumps(doc, indent=1))
+        return
     if a.normalize_reward:
         doc = {"what": "FusedPPO.update (4 epochs x 8 minibatches of 32768 over 64 x 4096 samples) with and without normalize_reward, both paths, and the pass alone",
                "commit": a.commit, "steps": [child(["--part", "rewnorm", "--obs-dim", str(od), "--rounds", str(a.rounds)], 300) for od in (15, 8)]}
