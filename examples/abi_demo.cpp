@@ -1,6 +1,6 @@
-// abi_demo.cpp -- a plain C++ consumer of the C ABI (include/so100_sim.h, include/so100_learn.h): no Python, no PyTorch.
+// abi_demo.cpp -- a plain C++ consumer of the C ABI (include/so100_sim.h, include/so100_learn.h, include/so100_query.h): no Python, no PyTorch.
 // Build:  hipcc -O2 -o abi_demo examples/abi_demo.cpp -Iinclude -Lso100_mujoco_rl_amd -lso100sim -Wl,-rpath,$PWD/so100_mujoco_rl_amd
-// Run:    ./abi_demo [num_envs] [steps]     (prints a checksum of the final observations, then one line from the learner)
+// Run:    ./abi_demo [num_envs] [steps]     (prints a checksum of the final observations, one line from the model queries, then the learner's)
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -8,6 +8,7 @@
 #include <vector>
 #include "so100_sim.h"
 #include "so100_learn.h"
+#include "so100_query.h"
 
 #define CHECK(x) do { if ((x) != hipSuccess) { std::fprintf(stderr, "HIP error at %s:%d\n", __FILE__, __LINE__); return 2; } } while (0)
 
@@ -40,6 +41,28 @@ int main(int argc, char** argv) {
     CHECK(hipMemcpy(h_rew.data(), rew, sizeof(float)*n, hipMemcpyDeviceToHost));
     double cs = 0, rs = 0; for (float v : h_obs) cs += v; for (float v : h_rew) rs += v;
     std::printf("envs %d steps %d  %.1f us/step  %.2f M env-steps/s  obs_checksum %.6f  reward_sum %.6f\n", n, steps, ms*1e3/steps, n*(double)steps/ms/1e3, cs, rs);
+    // ---- model queries (so100_query.h) on the handle's own state: where every end effector is, and the joints that would put it on its env's cube
+    {
+        float *qpos, *qvel, *ee, *q_ik, *resid; uint8_t* conv;
+        CHECK(hipMalloc(&qpos, sizeof(float)*13*n)); CHECK(hipMalloc(&qvel, sizeof(float)*12*n)); CHECK(hipMalloc(&ee, sizeof(float)*3*n));
+        CHECK(hipMalloc(&q_ik, sizeof(float)*6*n)); CHECK(hipMalloc(&resid, sizeof(float)*n)); CHECK(hipMalloc(&conv, n));
+        if (so100_get_state(sim, qpos, qvel, st) != 0) { std::fprintf(stderr, "so100_get_state: %s\n", so100_last_error()); return 1; }
+        so100_kinematics_io kio = {};
+        kio.ee_dev = ee;                                               // q_dev NULL: the handle's joints, M = N
+        if (so100_query_kinematics(sim, &kio, n, st) != 0) { std::fprintf(stderr, "so100_query_kinematics: %s\n", so100_last_error()); return 1; }
+        so100_ik_io iio = {};
+        iio.target_dev = qpos + 6*(size_t)n;                           // rows 6..8 of qpos [13][N]: the cube's position, already [3][N]
+        iio.link = SO100_EE_LINK; iio.iters = SO100_IK_ITERS; iio.damping = SO100_IK_DAMPING; iio.tol = SO100_IK_TOL; iio.max_step = SO100_IK_MAX_STEP;
+        iio.q_dev = q_ik; iio.residual_dev = resid; iio.converged_dev = conv;
+        if (so100_query_ik(sim, &iio, n, st) != 0) { std::fprintf(stderr, "so100_query_ik: %s\n", so100_last_error()); return 1; }
+        CHECK(hipStreamSynchronize(st));
+        std::vector<float> h_ee(3*(size_t)n), h_res(n); std::vector<uint8_t> h_conv(n);
+        CHECK(hipMemcpy(h_ee.data(), ee, sizeof(float)*h_ee.size(), hipMemcpyDeviceToHost)); CHECK(hipMemcpy(h_res.data(), resid, sizeof(float)*n, hipMemcpyDeviceToHost));
+        CHECK(hipMemcpy(h_conv.data(), conv, n, hipMemcpyDeviceToHost));
+        double ez = 0, rmax = 0; long nconv = 0;
+        for (int i = 0; i < n; i++) { ez += h_ee[2*(size_t)n + i]; rmax = std::fmax(rmax, h_res[i]); nconv += h_conv[i]; }
+        std::printf("queries: mean end-effector height %.4f m  IK onto the cube: %ld of %d converged, worst residual %.2e m\n", ez/n, nconv, n, rmax);
+    }
     // ---- the learner from plain C++ (so100_learn.h): advantages of a small synthetic chunk, then one PPO minibatch step on all of it
     {
         const int T = 4, k = od + 10, P = so100_learner_num_params(od);

@@ -1,0 +1,107 @@
+/* so100_query.h -- model queries of libso100sim.so: what MuJoCo's users read from MjData or get from mj_jac, mj_fullM and
+ * mj_inverse, for M independent problems at once, one GPU lane per problem.
+ *
+ * Additive to so100_sim.h (SO100_ABI_VERSION is unchanged) and under its conventions: extern "C"; `*_dev` pointers are DEVICE
+ * pointers owned by the caller; 0 on success, a negative SO100_E_* code otherwise with the message in so100_last_error(); all
+ * work goes to the caller's `hip_stream`; nothing allocates, frees or synchronises (hipGraph-capturable); a rejected call
+ * enqueues nothing.  Every call only READS the handle's state matrix.
+ *
+ * Layout: every array is component-major (SoA) like so100_get_state: a quantity with k components is [k][M] floats, matrices
+ * row-major in the leading index (xmat [6][9][M]: link, then the 9 row-major entries).  Links are numbered 0..5 as in
+ * csrc/so100_model_def.h: link k is MuJoCo body k + 2 and hangs on hinge joint k.
+ *
+ * State defaults: q_dev == NULL reads rows q0..q5 of the handle's state matrix, and M must then be the handle's N.
+ *
+ * Argument errors (SO100_E_INVALID), in this order: a null handle or io; M < 1 (or M != N where the handle's state is read);
+ * link outside 0..5; iters outside 1..1024; damping, tol or max_step not positive; a required pointer that is NULL; a call
+ * that asks for no output.
+ *
+ * Reference files are cited as "ref:", as in so100_sim.h.
+ */
+#ifndef SO100_QUERY_H
+#define SO100_QUERY_H
+#include "so100_sim.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* the reference's end-effector point (ref: envs/env_base_01.py:118-127): on Fixed_Jaw, 10 cm along its -y axis */
+#define SO100_EE_LINK 4
+#define SO100_EE_OFFSET_Y (-0.1f)
+
+/* Forward kinematics from q [6][M].  ref: the reads of data.body(...).xpos / .xmat, get_end_effector_pos and
+ * data.camera(...).xpos / .xmat in the task code.  Every output is nullable; at least one is required. */
+typedef struct {
+    const float* q_dev;            /* [6][M] joint angles, or NULL (the handle's)                               */
+    float*       xpos_dev;         /* [6][3][M] world position of each link frame (MjData.xpos[k + 2])          */
+    float*       xmat_dev;         /* [6][9][M] world orientation of each link frame (MjData.xmat[k + 2])       */
+    float*       ee_dev;           /* [3][M] xpos_FixedJaw + xmat_FixedJaw (0, -0.1, 0)                         */
+    float*       cam_pos_dev;      /* [3][M] the wrist camera (MjData.cam_xpos)                                 */
+    float*       cam_mat_dev;      /* [9][M] (MjData.cam_xmat)                                                  */
+} so100_kinematics_io;
+
+int so100_query_kinematics(so100_sim* sim, const so100_kinematics_io* io, int32_t M, void* hip_stream);
+
+/* Jacobian of a point fixed to link `link` at `offset` in that link's frame, in the world frame and in mj_jac's convention:
+ * column k is axis_k x (p - anchor_k) in jacp and axis_k in jacr for k <= link, zero for k > link.  link and offset are the
+ * same for every problem of the call.  At least one output is required. */
+typedef struct {
+    const float* q_dev;            /* [6][M] or NULL (the handle's)                                             */
+    int32_t      link;             /* 0..5                                                                      */
+    const float* offset;           /* HOST pointer to 3 floats, or NULL: the link's default point -- the end-effector point
+                                      (0, -0.1, 0) on link 4, the frame origin on every other link                */
+    float*       jacp_dev;         /* [3][6][M] or NULL                                                         */
+    float*       jacr_dev;         /* [3][6][M] or NULL                                                         */
+} so100_jacobian_io;
+
+int so100_query_jacobian(so100_sim* sim, const so100_jacobian_io* io, int32_t M, void* hip_stream);
+
+/* Joint-space dynamics of the arm: M(q) as MuJoCo leaves it in qM (armature on the diagonal), bias = C(q, v) + g(q)
+ * (MjData.qfrc_bias) and the inverse dynamics tau = M qacc + bias (mj_inverse without constraint or passive forces).
+ * tau is written only when qacc_dev is given; at least one output (M, bias, or tau with qacc) is required. */
+typedef struct {
+    const float* q_dev;            /* [6][M] or NULL (the handle's)                                             */
+    const float* v_dev;            /* [6][M] joint velocities, or NULL: zero -- or, with q_dev NULL too, the handle's */
+    const float* qacc_dev;         /* [6][M] or NULL                                                            */
+    float*       M_dev;            /* [36][M] full symmetric 6 x 6, row-major, or NULL                          */
+    float*       bias_dev;         /* [6][M] or NULL                                                            */
+    float*       tau_dev;          /* [6][M] or NULL                                                            */
+} so100_dynamics_io;
+
+int so100_query_dynamics(so100_sim* sim, const so100_dynamics_io* io, int32_t M, void* hip_stream);
+
+/* Batched inverse kinematics: moves the point (link, offset: as in so100_jacobian_io) to target by damped least squares over
+ * the joints 0..link; the joints behind the link keep q0's value.  Per problem:
+ *     q = clamp(q0, joint range) on the joints 0..link
+ *     for it = 0 .. iters:
+ *         e = target - point(q);  r = |e|;   stop if r <= tol or it == iters
+ *         J = jacp columns 0..link;   solve (J J' + damping^2 I) y = e;   dq = J' y
+ *         s = min(1, max_step / max_i |dq_i|);   q = clamp(q + s dq, joint range)
+ * Each lane stops when its own problem is done; the result is the same bits on every run.  q_dev may alias q0_dev.  target_dev
+ * is required, every output is nullable, at least one output is required. */
+#define SO100_IK_ITERS    64
+#define SO100_IK_DAMPING  0.02f
+#define SO100_IK_TOL      1e-4f    /* metres */
+#define SO100_IK_MAX_STEP 0.3f     /* radians per iteration, largest joint */
+typedef struct {
+    const float* target_dev;       /* [3][M] world position                                                     */
+    const float* q0_dev;           /* [6][M] start, or NULL (the handle's current joints)                       */
+    int32_t      link;             /* 0..5                                                                      */
+    const float* offset;           /* HOST pointer to 3 floats or NULL (so100_jacobian_io)                      */
+    int32_t      iters;            /* 1..1024                                                                   */
+    float        damping;          /* > 0                                                                       */
+    float        tol;              /* > 0                                                                       */
+    float        max_step;         /* > 0                                                                       */
+    float*       q_dev;            /* [6][M] or NULL                                                            */
+    float*       residual_dev;     /* [M] |target - point(q)| of the returned q, or NULL                        */
+    int32_t*     iterations_dev;   /* [M] updates taken (0..iters), or NULL                                     */
+    uint8_t*     converged_dev;    /* [M] residual <= tol, or NULL                                              */
+} so100_ik_io;
+
+int so100_query_ik(so100_sim* sim, const so100_ik_io* io, int32_t M, void* hip_stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* SO100_QUERY_H */

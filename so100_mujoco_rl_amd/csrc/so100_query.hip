@@ -1,0 +1,177 @@
+// so100_query.hip -- the four query kernels (gfx950) and their C ABI (include/so100_query.h); the arithmetic is in so100_query.hpp.
+// One lane per problem, any M >= 1.  Every load and store is a row of a component-major array: lane i of a wave touches word i of the
+// row, so a wave's access is one contiguous 256-byte segment.  The kernels only READ the handle's state matrix.
+// Workgroups of one wave: the kernels have no LDS and no barrier, so a larger workgroup would share nothing; with 64 lanes a batch of
+// a few thousand problems is spread over that many more CUs (the latency of one lane's chain is what a small batch pays), and
+// __launch_bounds__(64) leaves the register allocator the whole budget of a lane (no scratch memory).
+// Not a translation unit of its own: so100_sim.hip includes this file at its end (the handle, the host layer and the state rows are
+// in scope there), so the kernels below are part of so100_sim.o.
+#include <cmath>
+#include "so100_query.hpp"
+#include "../../include/so100_query.h"
+
+namespace so100 {
+
+constexpr int QUERY_THREADS = 64;
+
+struct QueryPoint { int link; float o[3]; };
+struct QueryKinOut { float *xpos, *xmat, *ee, *cam_pos, *cam_mat; };
+struct QueryDynIO { const float *v, *qacc; float *M, *bias, *tau; };
+struct QueryIkIO { const float* target; int iters; float damping2, tol, max_step; float *q, *residual; int32_t* iterations; uint8_t* converged; };
+
+// rows: k consecutive rows of `ld` words; lane i reads / writes word i of each
+template <int K> __device__ __forceinline__ void load_rows(const float* p, size_t ld, size_t i, float x[K]) {
+#pragma unroll
+    for (int j = 0; j < K; j++) x[j] = p[(size_t)j*ld + i];
+}
+template <int K> __device__ __forceinline__ void store_rows(float* p, size_t ld, size_t i, const float x[K]) {
+#pragma unroll
+    for (int j = 0; j < K; j++) p[(size_t)j*ld + i] = x[j];
+}
+
+// q: [6][ld] (ld = M for the caller's array, N for rows q0..q5 of the state matrix); every output [k][M]
+__global__ __launch_bounds__(QUERY_THREADS) void so100_query_kinematics_k(const float* __restrict__ q, int ld, int M, QueryKinOut o) {
+    const size_t i = (size_t)blockIdx.x*QUERY_THREADS + threadIdx.x;
+    if (i >= (size_t)M) return;
+    float qi[6];
+    load_rows<6>(q, (size_t)ld, i, qi);
+    QueryPoses<float> Q;
+    query_kinematics<float>(qi, Q);
+    if (o.xpos) store_rows<18>(o.xpos, (size_t)M, i, &Q.F.pos[0][0]);
+    if (o.xmat) store_rows<54>(o.xmat, (size_t)M, i, &Q.F.R[0][0]);
+    if (o.ee) store_rows<3>(o.ee, (size_t)M, i, Q.ee);
+    if (o.cam_pos) store_rows<3>(o.cam_pos, (size_t)M, i, Q.cam_pos);
+    if (o.cam_mat) store_rows<9>(o.cam_mat, (size_t)M, i, Q.cam_mat);
+}
+
+__global__ __launch_bounds__(QUERY_THREADS) void so100_query_jacobian_k(const float* __restrict__ q, int ld, int M, QueryPoint pt,
+                                                                        float* __restrict__ jacp, float* __restrict__ jacr) {
+    const size_t i = (size_t)blockIdx.x*QUERY_THREADS + threadIdx.x;
+    if (i >= (size_t)M) return;
+    float qi[6], jp[18], jr[18];
+    load_rows<6>(q, (size_t)ld, i, qi);
+    query_jacobian<float>(qi, pt.link, pt.o, jp, jr);
+    if (jacp) store_rows<18>(jacp, (size_t)M, i, jp);
+    if (jacr) store_rows<18>(jacr, (size_t)M, i, jr);
+}
+
+// v: [6][ldv] or null (zero); qacc: [6][M] or null
+__global__ __launch_bounds__(QUERY_THREADS) void so100_query_dynamics_k(const float* __restrict__ q, int ld, int ldv, int M, QueryDynIO io) {
+    const size_t i = (size_t)blockIdx.x*QUERY_THREADS + threadIdx.x;
+    if (i >= (size_t)M) return;
+    float qi[6], vi[6] = { 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f }, ai[6] = { 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f }, Mf[36], bias[6], tau[6];
+    load_rows<6>(q, (size_t)ld, i, qi);
+    if (io.v) load_rows<6>(io.v, (size_t)ldv, i, vi);
+    if (io.qacc) load_rows<6>(io.qacc, (size_t)M, i, ai);
+    query_dynamics<float>(qi, vi, ai, Mf, bias, tau);
+    if (io.M) store_rows<36>(io.M, (size_t)M, i, Mf);
+    if (io.bias) store_rows<6>(io.bias, (size_t)M, i, bias);
+    if (io.tau && io.qacc) store_rows<6>(io.tau, (size_t)M, i, tau);
+}
+
+// q0 and io.q may be the same array: a lane reads its column before it writes it, and no lane touches another's
+__global__ __launch_bounds__(QUERY_THREADS) void so100_query_ik_k(const float* q0, int ld, int M, QueryPoint pt, QueryIkIO io) {
+    const size_t i = (size_t)blockIdx.x*QUERY_THREADS + threadIdx.x;
+    if (i >= (size_t)M) return;
+    float qi[6], tg[3];
+    load_rows<6>(q0, (size_t)ld, i, qi);
+    load_rows<3>(io.target, (size_t)M, i, tg);
+    IkParams<float> P;
+    P.link = pt.link; P.iters = io.iters; P.o[0] = pt.o[0]; P.o[1] = pt.o[1]; P.o[2] = pt.o[2];
+    P.damping2 = io.damping2; P.tol = io.tol; P.max_step = io.max_step;
+    IkResult<float> R;
+    query_ik<float>(qi, tg, P, R);
+    if (io.q) store_rows<6>(io.q, (size_t)M, i, R.q);
+    if (io.residual) io.residual[i] = R.residual;
+    if (io.iterations) io.iterations[i] = R.iterations;
+    if (io.converged) io.converged[i] = R.converged ? 1 : 0;
+}
+
+namespace {
+
+// what the four calls check alike and read from the handle: the joint rows (the caller's, or the state matrix's) and their row length
+struct QuerySource { const float* q; int ld; };
+int query_source(const char* fn, const so100_sim* s, const float* q_dev, int32_t M, QuerySource& src) {
+    const int n = s->prm.n;
+    if (M < 1) return fail(SO100_E_INVALID, "%s: M must be >= 1, got %ld", fn, (long)M);
+    if (!q_dev && M != n) return fail(SO100_E_INVALID, "%s: M must be the handle's N (%ld) where its state is read, got %ld", fn, (long)n, (long)M);
+    src.q = q_dev ? q_dev : s->state + (size_t)SF_q0*(size_t)n;
+    src.ld = q_dev ? M : n;
+    return 0;
+}
+int query_point(const char* fn, int32_t link, const float* offset, QueryPoint& pt) {
+    if (link < 0 || link > 5) return fail(SO100_E_INVALID, "%s: link must be in 0..5, got %ld", fn, (long)link);
+    pt.link = link;
+    for (int i = 0; i < 3; i++) pt.o[i] = offset ? offset[i] : (link == EE_LINK ? (float)EE_OFFSET[i] : 0.0f);
+    return 0;
+}
+unsigned query_grid(int M) { return (unsigned)((M + QUERY_THREADS - 1)/QUERY_THREADS); }
+
+}  // namespace
+}  // namespace so100
+
+static_assert(SF_q5 == SF_q0 + 5 && SF_v5 == SF_v0 + 5, "the arm's qpos / qvel rows are contiguous");
+static_assert(SO100_EE_LINK == EE_LINK, "the header names the same end-effector point");
+
+extern "C" {
+
+int so100_query_kinematics(so100_sim* sim, const so100_kinematics_io* io, int32_t M, void* stream) {
+    if (!sim || !io) return fail(SO100_E_INVALID, "so100_query_kinematics: null argument");
+    QuerySource src;
+    if (const int rc = query_source("so100_query_kinematics", sim, io->q_dev, M, src)) return rc;
+    if (!io->xpos_dev && !io->xmat_dev && !io->ee_dev && !io->cam_pos_dev && !io->cam_mat_dev)
+        return fail(SO100_E_INVALID, "so100_query_kinematics: no output requested");
+    SO100_ON_DEVICE(sim->cfg.device, "so100_query_kinematics");
+    const QueryKinOut o{ io->xpos_dev, io->xmat_dev, io->ee_dev, io->cam_pos_dev, io->cam_mat_dev };
+    hipLaunchKernelGGL(so100_query_kinematics_k, dim3(query_grid(M)), dim3(QUERY_THREADS), 0, (hipStream_t)stream, src.q, src.ld, M, o);
+    HIP_TRY(hipGetLastError(), SO100_E_LAUNCH);
+    return 0;
+}
+
+int so100_query_jacobian(so100_sim* sim, const so100_jacobian_io* io, int32_t M, void* stream) {
+    if (!sim || !io) return fail(SO100_E_INVALID, "so100_query_jacobian: null argument");
+    QuerySource src;
+    QueryPoint pt;
+    if (const int rc = query_source("so100_query_jacobian", sim, io->q_dev, M, src)) return rc;
+    if (const int rc = query_point("so100_query_jacobian", io->link, io->offset, pt)) return rc;
+    if (!io->jacp_dev && !io->jacr_dev) return fail(SO100_E_INVALID, "so100_query_jacobian: no output requested");
+    SO100_ON_DEVICE(sim->cfg.device, "so100_query_jacobian");
+    hipLaunchKernelGGL(so100_query_jacobian_k, dim3(query_grid(M)), dim3(QUERY_THREADS), 0, (hipStream_t)stream, src.q, src.ld, M, pt, io->jacp_dev, io->jacr_dev);
+    HIP_TRY(hipGetLastError(), SO100_E_LAUNCH);
+    return 0;
+}
+
+int so100_query_dynamics(so100_sim* sim, const so100_dynamics_io* io, int32_t M, void* stream) {
+    if (!sim || !io) return fail(SO100_E_INVALID, "so100_query_dynamics: null argument");
+    QuerySource src;
+    if (const int rc = query_source("so100_query_dynamics", sim, io->q_dev, M, src)) return rc;
+    if (!io->M_dev && !io->bias_dev && !(io->tau_dev && io->qacc_dev)) return fail(SO100_E_INVALID, "so100_query_dynamics: no output requested");
+    QueryDynIO d{ io->v_dev, io->qacc_dev, io->M_dev, io->bias_dev, io->tau_dev };
+    int ldv = M;
+    if (!io->q_dev && !io->v_dev) { d.v = sim->state + (size_t)SF_v0*(size_t)sim->prm.n; ldv = sim->prm.n; }       // the handle's state: its qvel too
+    SO100_ON_DEVICE(sim->cfg.device, "so100_query_dynamics");
+    hipLaunchKernelGGL(so100_query_dynamics_k, dim3(query_grid(M)), dim3(QUERY_THREADS), 0, (hipStream_t)stream, src.q, src.ld, ldv, M, d);
+    HIP_TRY(hipGetLastError(), SO100_E_LAUNCH);
+    return 0;
+}
+
+int so100_query_ik(so100_sim* sim, const so100_ik_io* io, int32_t M, void* stream) {
+    if (!sim || !io) return fail(SO100_E_INVALID, "so100_query_ik: null argument");
+    QuerySource src;
+    QueryPoint pt;
+    if (const int rc = query_source("so100_query_ik", sim, io->q0_dev, M, src)) return rc;
+    if (const int rc = query_point("so100_query_ik", io->link, io->offset, pt)) return rc;
+    if (io->iters < 1 || io->iters > 1024) return fail(SO100_E_INVALID, "so100_query_ik: iters must be in 1..1024, got %ld", (long)io->iters);
+    if (!(io->damping > 0.0f) || !std::isfinite(io->damping)) return fail(SO100_E_INVALID, "so100_query_ik: damping must be > 0");
+    if (!(io->tol > 0.0f) || !std::isfinite(io->tol)) return fail(SO100_E_INVALID, "so100_query_ik: tol must be > 0");
+    if (!(io->max_step > 0.0f) || !std::isfinite(io->max_step)) return fail(SO100_E_INVALID, "so100_query_ik: max_step must be > 0");
+    if (!io->target_dev) return fail(SO100_E_INVALID, "so100_query_ik: target_dev is required");
+    if (!io->q_dev && !io->residual_dev && !io->iterations_dev && !io->converged_dev) return fail(SO100_E_INVALID, "so100_query_ik: no output requested");
+    SO100_ON_DEVICE(sim->cfg.device, "so100_query_ik");
+    const QueryIkIO k{ io->target_dev, io->iters, io->damping*io->damping, io->tol, io->max_step, io->q_dev, io->residual_dev, io->iterations_dev, io->converged_dev };
+    hipLaunchKernelGGL(so100_query_ik_k, dim3(query_grid(M)), dim3(QUERY_THREADS), 0, (hipStream_t)stream, src.q, src.ld, M, pt, k);
+    HIP_TRY(hipGetLastError(), SO100_E_LAUNCH);
+    return 0;
+}
+
+}  // extern "C"

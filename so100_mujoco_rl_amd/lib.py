@@ -147,6 +147,31 @@ LEARNER_DIAG = LEARNER_STATS + ["approx_kl", "entropy_loss", "loss", "value_clip
 NORMALIZE_ADVANTAGE = {"batch": 0, "minibatch": 1}                                   # so100_ppo_terms.normalize_advantage
 
 
+# ---- include/so100_query.h: model queries (additive like the learner: EXPORTS above is the list of so100_sim.h alone) -------------------------
+class KinematicsIO(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("q_dev", "xpos_dev", "xmat_dev", "ee_dev", "cam_pos_dev", "cam_mat_dev")]
+
+
+class JacobianIO(C.Structure):
+    _fields_ = [("q_dev", C.c_void_p), ("link", C.c_int32), ("offset", C.c_void_p), ("jacp_dev", C.c_void_p), ("jacr_dev", C.c_void_p)]
+
+
+class DynamicsIO(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("q_dev", "v_dev", "qacc_dev", "M_dev", "bias_dev", "tau_dev")]
+
+
+class IkIO(C.Structure):
+    _fields_ = [("target_dev", C.c_void_p), ("q0_dev", C.c_void_p), ("link", C.c_int32), ("offset", C.c_void_p), ("iters", C.c_int32),
+                ("damping", C.c_float), ("tol", C.c_float), ("max_step", C.c_float), ("q_dev", C.c_void_p), ("residual_dev", C.c_void_p),
+                ("iterations_dev", C.c_void_p), ("converged_dev", C.c_void_p)]
+
+
+QUERY_EXPORTS = ["so100_query_kinematics", "so100_query_jacobian", "so100_query_dynamics", "so100_query_ik"]
+QUERY_IO = {"so100_query_kinematics": KinematicsIO, "so100_query_jacobian": JacobianIO, "so100_query_dynamics": DynamicsIO, "so100_query_ik": IkIO}
+EE_LINK = 4                                                    # SO100_EE_LINK: the reference's end-effector point sits on Fixed_Jaw
+IK_ITERS, IK_DAMPING, IK_TOL, IK_MAX_STEP = 64, 0.02, 1e-4, 0.3     # SO100_IK_*
+
+
 def build(verbose=False):
     """Compile libso100sim.so for gfx950 (hipcc cross-compiles without a GPU)."""
     out = subprocess.run(["make", "-j7", "-C", os.path.join(_HERE, "csrc")], capture_output=True, text=True)
@@ -206,6 +231,8 @@ def load():
         L.so100_learner_obs_norm_update.argtypes = [C.c_void_p, C.POINTER(ObsNormIO), C.c_int32, C.c_int32, C.c_void_p]
         L.so100_learner_obs_norm_fold.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.so100_learner_set_obs_norm.argtypes = [C.c_void_p, C.c_void_p]
+        for fn, io in QUERY_IO.items():
+            getattr(L, fn).argtypes = [C.c_void_p, C.POINTER(io), C.c_int32, C.c_void_p]
         if L.so100_abi_version() != ABI_VERSION:
             raise So100Error("libso100sim.so ABI version mismatch")
         _lib = L
@@ -523,6 +550,78 @@ class So100Sim(_Handle):
         assert value.element_size() == 4
         _check(self.L.so100_set_field(self.h, self.field_index(name), _ptr(value, value.dtype, (self.n,), self.device),
                                       self._stream()), "so100_set_field")
+
+
+    # ---- model queries (include/so100_query.h; DESIGN.md section 11): one launch each on the current stream, the state is only read ----------
+    def _soa(self, t, k, what):
+        """[M, k] -> the [k][M] array the kernels read, on the device (None stays None)"""
+        if t is None:
+            return None
+        t = torch.as_tensor(t, dtype=torch.float32, device=self.device)
+        if t.dim() != 2 or t.shape[1] != k:
+            raise So100Error(f"{what}: want a [M, {k}] tensor, got {tuple(t.shape)}")
+        return t.t().contiguous()
+
+    def _problems(self, *soa):
+        """M of a query: the given arrays' common length, or N where the handle's state is read"""
+        ms = {t.shape[1] for t in soa if t is not None}
+        if len(ms) > 1:
+            raise So100Error(f"the arguments of a query hold different numbers of problems: {sorted(ms)}")
+        return ms.pop() if ms else self.n
+
+    def _out(self, M, *lead, dtype=torch.float32):
+        return torch.empty(*lead, M, dtype=dtype, device=self.device)
+
+    @staticmethod
+    def _offset(offset):
+        return None if offset is None else (C.c_float * 3)(*[float(v) for v in offset])
+
+    def kinematics(self, q=None):
+        """World poses from joint angles q [M, 6] (None: the handle's current joints, M = N).  Returns a dict of views, one row per problem:
+        "xpos" [M, 6, 3] and "xmat" [M, 6, 3, 3] of the six link frames (link k = MuJoCo body k + 2), "ee" [M, 3] the reference's
+        end-effector point, "cam_pos" [M, 3] and "cam_mat" [M, 3, 3] of the wrist camera."""
+        qs = self._soa(q, 6, "q"); M = self._problems(qs)
+        xpos, xmat, ee, cp, cm = self._out(M, 6, 3), self._out(M, 6, 9), self._out(M, 3), self._out(M, 3), self._out(M, 9)
+        io = KinematicsIO(qs.data_ptr() if qs is not None else None, xpos.data_ptr(), xmat.data_ptr(), ee.data_ptr(), cp.data_ptr(), cm.data_ptr())
+        _check(self.L.so100_query_kinematics(self.h, C.byref(io), M, self._stream()), "so100_query_kinematics")
+        return {"xpos": xpos.permute(2, 0, 1), "xmat": xmat.permute(2, 0, 1).unflatten(2, (3, 3)), "ee": ee.t(), "cam_pos": cp.t(),
+                "cam_mat": cm.t().unflatten(1, (3, 3))}
+
+    def jacobian(self, q=None, link=EE_LINK, offset=None):
+        """mj_jac of the point at `offset` (3 values, link frame; None: the end-effector point on link 4, the frame origin on another link)
+        of link `link`: "jacp" and "jacr" [M, 3, 6], world frame; columns of the joints behind the link are zero."""
+        qs = self._soa(q, 6, "q"); M = self._problems(qs)
+        jp, jr = self._out(M, 3, 6), self._out(M, 3, 6)
+        off = self._offset(offset)
+        io = JacobianIO(qs.data_ptr() if qs is not None else None, link, C.cast(off, C.c_void_p) if off is not None else None, jp.data_ptr(), jr.data_ptr())
+        _check(self.L.so100_query_jacobian(self.h, C.byref(io), M, self._stream()), "so100_query_jacobian")
+        return {"jacp": jp.permute(2, 0, 1), "jacr": jr.permute(2, 0, 1)}
+
+    def dynamics(self, q=None, v=None, qacc=None):
+        """The arm's joint-space dynamics at q, v [M, 6] (q None: the handle's joints -- and, with v None too, its joint velocities; v None
+        otherwise: zero): "M" [M, 6, 6] (armature included, as MuJoCo's qM), "bias" [M, 6] (qfrc_bias: Coriolis, centrifugal, gravity) and,
+        with qacc [M, 6], "tau" = M qacc + bias."""
+        qs, vs, acs = self._soa(q, 6, "q"), self._soa(v, 6, "v"), self._soa(qacc, 6, "qacc"); M = self._problems(qs, vs, acs)
+        Mm, bias = self._out(M, 36), self._out(M, 6)
+        tau = self._out(M, 6) if acs is not None else None
+        io = DynamicsIO(*[t.data_ptr() if t is not None else None for t in (qs, vs, acs, Mm, bias, tau)])
+        _check(self.L.so100_query_dynamics(self.h, C.byref(io), M, self._stream()), "so100_query_dynamics")
+        res = {"M": Mm.t().unflatten(1, (6, 6)), "bias": bias.t()}
+        if tau is not None:
+            res["tau"] = tau.t()
+        return res
+
+    def ik(self, target, q0=None, link=EE_LINK, offset=None, iters=IK_ITERS, damping=IK_DAMPING, tol=IK_TOL, max_step=IK_MAX_STEP):
+        """Batched damped-least-squares IK: joint angles that put the point (link, offset: as in jacobian()) on target [M, 3], starting from
+        q0 [M, 6] (None: the handle's current joints) and moving the joints 0..link inside their ranges.  Returns "q" [M, 6], "residual" [M]
+        (metres), "iterations" [M] int32 and "converged" [M] uint8 (residual <= tol)."""
+        ts, qs = self._soa(target, 3, "target"), self._soa(q0, 6, "q0"); M = self._problems(ts, qs)
+        q, res, its, conv = self._out(M, 6), self._out(M), self._out(M, dtype=torch.int32), self._out(M, dtype=torch.uint8)
+        off = self._offset(offset)
+        io = IkIO(ts.data_ptr(), qs.data_ptr() if qs is not None else None, link, C.cast(off, C.c_void_p) if off is not None else None, iters, damping,
+                  tol, max_step, q.data_ptr(), res.data_ptr(), its.data_ptr(), conv.data_ptr())
+        _check(self.L.so100_query_ik(self.h, C.byref(io), M, self._stream()), "so100_query_ik")
+        return {"q": q.t(), "residual": res, "iterations": its, "converged": conv}
 
 
 def learner_layout(obs_dim):
