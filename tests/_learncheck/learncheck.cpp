@@ -1,5 +1,5 @@
 // learncheck.cpp -- so100_learn.hpp (the arithmetic the learner's HIP kernels call) instantiated on the host in double and float, behind a
-// C interface for ctypes (tests/hostlibs.py).  Test scaffolding only.
+// C interface for ctypes (tests/hostlibs.py; one library, liblearncheck.so, with the three sources beside it).  Test scaffolding only.
 #include "../../so100_mujoco_rl_amd/csrc/so100_learn.hpp"
 
 using namespace so100::learn;

@@ -1,7 +1,7 @@
 // obsnormcheck.cpp -- the observation normalisation of so100_learn.hpp on the host, in the instantiation the kernels ship (double moments and
 // fold, float load and outputs) and in the kernels' order: blocks of ON_BLOCK rows with the fixed tree inside a block, groups of ON_GROUP blocks
 // merged in block order, the groups merged in group order, then the running update.  Behind a C interface for ctypes
-// (tests/obs_norm_support.py).  Test scaffolding only.
+// (part of liblearncheck.so: tests/hostlibs.py; called by tests/obs_norm_support.py).  Test scaffolding only.
 #include <stddef.h>
 #include <vector>
 #include "../../so100_mujoco_rl_amd/csrc/so100_learn.hpp"

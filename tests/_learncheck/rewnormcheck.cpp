@@ -1,6 +1,6 @@
 // rewnormcheck.cpp -- the reward normalisation of so100_learn.hpp on the host, in the instantiation the kernels ship (double state, float
 // out) and in the kernels' order: blocks of RN_BLOCK envs, the fixed tree inside a block, Chan's merge over the blocks in index order, the
-// steps in t order.  Behind a C interface for ctypes (tests/reward_norm_support.py).  Test scaffolding only.
+// steps in t order.  Behind a C interface for ctypes (part of liblearncheck.so: tests/hostlibs.py; called by tests/reward_norm_support.py).  Test scaffolding only.
 #include <stddef.h>
 #include <vector>
 #include "../../so100_mujoco_rl_amd/csrc/so100_learn.hpp"

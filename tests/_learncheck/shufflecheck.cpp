@@ -1,5 +1,5 @@
 // shufflecheck.cpp -- shuffle_index of so100_learn.hpp (what the kernel so100_learn_shuffle calls per position) on the host, behind a C
-// interface for ctypes (tests/update_support.py).  Test scaffolding only.
+// interface for ctypes (part of liblearncheck.so: tests/hostlibs.py; called by tests/update_support.py).  Test scaffolding only.
 #include "../../so100_mujoco_rl_amd/csrc/so100_task.hpp"       // philox4x32: before so100_learn.hpp, which has the shuffle only behind it
 #include "../../so100_mujoco_rl_amd/csrc/so100_learn.hpp"
 

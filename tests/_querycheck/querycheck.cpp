@@ -1,5 +1,5 @@
 // querycheck.cpp -- the model queries of so100_query.hpp on the host, in double (held to the fp64 oracle) and in float (the arithmetic
-// the kernels ship, without FMA contraction), behind a C interface for ctypes (tests/query_support.py).  Arrays are problem-major here
+// the kernels ship, without FMA contraction), behind a C interface for ctypes (tests/hostlibs.py; called by tests/query_support.py).  Arrays are problem-major here
 // ([n][k]: one problem's components together); the SoA layout is the kernels' matter.  Test scaffolding only.
 #include <stdint.h>
 #include "../../so100_mujoco_rl_amd/csrc/so100_query.hpp"

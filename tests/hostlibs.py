@@ -1,6 +1,7 @@
 """The one place that builds and loads the host twins of the device code: tests/_hostcheck/libhostcheck.so (physics, contacts, task
-layer, random draws), tests/_rendercheck/librendercheck.so (render) and tests/_learncheck/liblearncheck.so (the learner's arithmetic).
-Each is made once per process and cached; argtypes and restype are declared here for EVERY exported symbol (tests/test_hostlibs.py holds
+layer, random draws), tests/_rendercheck/librendercheck.so (render), tests/_learncheck/liblearncheck.so (the learner: lc_ its arithmetic,
+rn_ reward normalisation, on_ observation normalisation, sc_ the shuffle; four sources, one library) and tests/_querycheck/libquerycheck.so
+(the model queries).  tests/Makefile is the one recipe for all of them.  Each is made once per process and cached; argtypes and restype are declared here for EVERY exported symbol (tests/test_hostlibs.py holds
 the tables to the extern "C" definitions), so that no call depends on which test ran first: a `long` result without its restype is
 silently cut to 32 bits, a Python float without argtypes raises."""
 import ctypes as C
@@ -53,14 +54,31 @@ LEARNCHECK = {
     "lc_head_ex_d": (None, [_p, _p]), "lc_head_ex_f": (None, [_p, _p]),
     "lc_adam_d": (None, [_i, _p, _p, _p, _p, _d, _p]),
     "lc_adam_f": (None, [_i, _p, _p, _p, _p, _f, _p]),
+    "rn_block": (_i, []),
+    "rn_normalize": (None, [_i]*5 + [_p, _d, _d, _d, _p, _p]),
+    "on_block": (_i, []), "on_group": (_i, []),
+    "on_update": (None, [_l, _i, _i, _p, _p]),
+    "on_fold": (None, [_i, _i, _p, _p, _d, _p, _p, _p]),
+    "on_normalize": (None, [_l, _i, _p, _p, _p]),
+    "sc_shuffle": (None, [_ull, _u, _l, _p]),
+    "sc_shuffle_epochs": (None, [_ull, _u, _i, _i, _p]),
+}
+QUERYCHECK = {
+    "qc_kinematics_d": (None, [_l] + [_p]*6), "qc_kinematics_f": (None, [_l] + [_p]*6),
+    "qc_jacobian_d": (None, [_l, _p, _i, _p, _p, _p]), "qc_jacobian_f": (None, [_l, _p, _i, _p, _p, _p]),
+    "qc_dynamics_d": (None, [_l] + [_p]*6), "qc_dynamics_f": (None, [_l] + [_p]*6),
+    "qc_ik_d": (None, [_l, _p, _p, _i, _p, _i, _d, _d, _d] + [_p]*4), "qc_ik_f": (None, [_l, _p, _p, _i, _p, _i, _f, _f, _f] + [_p]*4),
+    "qc_joint_range": (None, [_p]),
 }
 
 _libs = {}
 
 
-def _load(path, make_dir, make_vars, signatures):
+def _load(target, signatures, make_vars=()):
+    """`target` of tests/Makefile (a path under tests/ or an absolute one), made and loaded once"""
+    path = os.path.join(HERE, target)
     if path not in _libs:
-        subprocess.check_call(["make", "-C", make_dir, "-s"] + make_vars)
+        subprocess.check_call(["make", "-C", HERE, "-s", target] + list(make_vars))
         lib = C.CDLL(path)
         for name, (restype, argtypes) in signatures.items():
             fn = getattr(lib, name)
@@ -72,20 +90,22 @@ def _load(path, make_dir, make_vars, signatures):
 def hostcheck(out="libhostcheck.so", extra=""):
     """tests/_hostcheck/hostcheck.cpp built into `out` (a name in tests/_hostcheck or an absolute path) with the compiler arguments
     `extra` after the Makefile's own, e.g. -DSO100_MODEL_GEN_HEADER=... for a second generated model"""
-    d = os.path.join(HERE, "_hostcheck")
-    return _load(os.path.join(d, out), d, [f"OUT={out}", f"EXTRA={extra}"], HOSTCHECK)
+    path = os.path.join(HERE, "_hostcheck", out)
+    return _load(path, HOSTCHECK, [f"OUT={path}", f"EXTRA={extra}"])
 
 
 def rendercheck():
-    d = os.path.join(HERE, "_rendercheck")
-    return _load(os.path.join(d, "librendercheck.so"), d, [], RENDERCHECK)
+    return _load("_rendercheck/librendercheck.so", RENDERCHECK)
 
 
 def learncheck():
-    d = os.path.join(HERE, "_learncheck")
-    return _load(os.path.join(d, "liblearncheck.so"), d, [], LEARNCHECK)
+    return _load("_learncheck/liblearncheck.so", LEARNCHECK)
+
+
+def querycheck():
+    return _load("_querycheck/libquerycheck.so", QUERYCHECK)
 
 
 def ptr(a):
-    """the data pointer of a numpy array, for a c_void_p parameter"""
-    return a.ctypes.data_as(C.c_void_p)
+    """the data pointer of a numpy array, for a c_void_p parameter; None (a null pointer) passes through"""
+    return None if a is None else a.ctypes.data_as(C.c_void_p)

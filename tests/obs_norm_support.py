@@ -1,7 +1,7 @@
 """What the observation-normalisation tests share (test_obs_norm_cpu.py, test_gpu_obs_norm.py): the numpy fp64 reference of the section
 "Observation normalisation" of include/so100_learn.h -- SB3's VecNormalize(norm_obs=True) over its RunningMeanStd and the fold into the first
-layers, written from the header's text; it shares no line with csrc/ or ppo.py -- the host twin of csrc/so100_learn.hpp's templates,
-tests/_obsnormcheck/libobsnormcheck.so, built and loaded here, and the inputs and comparisons both modules use.
+layers, written from the header's text; it shares no line with csrc/ or ppo.py -- the calls into the host twin of csrc/so100_learn.hpp's
+templates (tests/_learncheck/obsnormcheck.cpp in hostlibs.learncheck()), and the inputs and comparisons both modules use.
 
 Tolerances (derived, not measured).  The reference sums with numpy's pairwise order, the code under test with blocks of 256, a fixed tree and
 Chan's merge in two levels: fp64 sums in another order differ by about T N 2^-53 relative, so mean and var match to MOMENT_TOL = 1e-10
@@ -10,14 +10,14 @@ are fp64 values rounded once to fp32; two fp64 evaluations a few fp64 ulps apart
 b0' the two evaluations differ by about 1e-15 of the TERMS of the sum (|b0| + sum |W0' mean|); the inputs keep |mean|/std <= 5 and every
 spread non-zero, so b0' stays within a few orders of its terms (it would have to cancel to 1e-8 of them to cost an ulp).  A dimension that
 never varies makes inv_std 1e4 and the terms huge: that is the documentation's matter, not a tolerance's."""
-import ctypes as C
 import functools
-import os
-import subprocess
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
+import hostlibs
+from hostlibs import ptr
+from reward_norm_support import ulp_distance              # noqa: F401  (the tests reach it through either module)
+
 EPSILON = 1e-8
 MOMENT_TOL = 1e-10
 SHAPES = [(3, 1), (5, 67), (16, 134), (64, 300)]
@@ -82,37 +82,13 @@ def ref_normalize(obs, state, epsilon=EPSILON):
 
 
 # ---- the host twin ------------------------------------------------------------------------------------------------------------------------------
-_twin = None
-
-
-def obsnormcheck():
-    """the host twin: on_block(), on_group(), on_update(rows, od, row, chunk, state), on_fold(od, P, first, state, eps, params, folded, norm),
-    on_normalize(n, od, obs, norm, out)"""
-    global _twin
-    if _twin is None:
-        d = os.path.join(HERE, "_obsnormcheck")
-        subprocess.check_call(["make", "-C", d, "-s"])
-        lib = C.CDLL(os.path.join(d, "libobsnormcheck.so"))
-        lib.on_block.restype, lib.on_block.argtypes = C.c_int, []
-        lib.on_group.restype, lib.on_group.argtypes = C.c_int, []
-        lib.on_update.restype, lib.on_update.argtypes = None, [C.c_long, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-        lib.on_fold.restype, lib.on_fold.argtypes = None, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.on_normalize.restype, lib.on_normalize.argtypes = None, [C.c_long, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        _twin = lib
-    return _twin
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
-
-
 def twin_update(obs, state):
     """ref_update's interface on the twin; the observations travel in the first od entries of rows of od + 10 floats, as in the packed chunk"""
     obs = np.asarray(obs, np.float32); od = obs.shape[-1]
     chunk = np.full((obs.shape[0] * obs.shape[1], od + 10), 1e30, np.float32)
     chunk[:, :od] = obs.reshape(-1, od)
     st = np.array(state, np.float64)
-    obsnormcheck().on_update(chunk.shape[0], od, od + 10, _p(chunk), _p(st))
+    hostlibs.learncheck().on_update(chunk.shape[0], od, od + 10, ptr(chunk), ptr(st))
     return st
 
 
@@ -143,7 +119,7 @@ def twin_fold(tensors, state, epsilon=EPSILON):
     folded, norm = np.full(P, 7.0, np.float32), np.full(2 * od, 7.0, np.float32)
     first = np.array([lay[k][0] for k in FIRST], np.int32)
     st = np.array(state, np.float64)
-    obsnormcheck().on_fold(od, P, _p(first), _p(st), epsilon, _p(flat), _p(folded), _p(norm))
+    hostlibs.learncheck().on_fold(od, P, ptr(first), ptr(st), epsilon, ptr(flat), ptr(folded), ptr(norm))
     return unflatten(folded, od), norm
 
 
@@ -151,7 +127,7 @@ def twin_normalize(obs, norm):
     obs = np.ascontiguousarray(obs, np.float32); od = obs.shape[-1]
     out = np.empty_like(obs)
     nm = np.ascontiguousarray(norm, np.float32)
-    obsnormcheck().on_normalize(obs.size // od, od, _p(obs), _p(nm), _p(out))
+    hostlibs.learncheck().on_normalize(obs.size // od, od, ptr(obs), ptr(nm), ptr(out))
     return out
 
 
@@ -194,14 +170,6 @@ def scale_observations(x, od):
 
 
 # ---- comparisons --------------------------------------------------------------------------------------------------------------------------------
-def ulp_distance(a, b):
-    """the largest distance in fp32 units in the last place between two float32 arrays of finite values"""
-    def key(x):
-        i = np.ascontiguousarray(x, np.float32).view(np.int32).astype(np.int64)
-        return np.where(i < 0, -(i & 0x7FFFFFFF), i)
-    return int(np.abs(key(a) - key(b)).max())
-
-
 def check_state(state, want, exact_count=True):
     """mean and var within MOMENT_TOL relative, count exact; returns the two largest relative errors.  exact_count=False, for two chunks against
     one of 2T: 1e-4 + TN + TN and 1e-4 + 2TN round differently, so the count is held to MOMENT_TOL there"""

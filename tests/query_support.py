@@ -1,5 +1,5 @@
 """What the model-query tests share (test_query_cpu.py, test_gpu_query.py): the host twin of csrc/so100_query.hpp
-(tests/_querycheck/libquerycheck.so, built and loaded here), the fp64 oracle's side of every comparison, the cases and the bounds.
+(tests/_querycheck/libquerycheck.so, loaded by hostlibs.querycheck()), the fp64 oracle's side of every comparison, the cases and the bounds.
 
 Cases.  CASES poses with q uniform over the full joint ranges, v uniform in +-2 rad/s, qacc uniform in +-20 rad/s^2, seed 0; every
 input is rounded to fp32 once and the oracle gets those values widened, so a difference is the code's, not the inputs'.  IK: ik_recipe().
@@ -11,14 +11,13 @@ as [query-tol] lines by test_query_cpu.py::test_fp32_twin_against_the_oracle, wh
 the kernels to the same numbers."""
 import ctypes as C
 import functools
-import os
-import subprocess
 
 import numpy as np
 
+import hostlibs
+from hostlibs import ptr
 from oracle import so100_oracle as O
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 CASES = 512
 FP64_BOUND = 1e-12
 # the measured maxima of the fp32 twin against the oracle over the CASES poses (metres; xmat / cam_mat / jacr entries; kg m^2; N m)
@@ -34,37 +33,11 @@ EE_LINK, EE_LOCAL = 4, np.array([0.0, float(np.float32(-0.1)), 0.0])
 
 def joint_range():
     out = np.zeros(12)
-    twin().qc_joint_range(out.ctypes.data_as(C.c_void_p))
+    hostlibs.querycheck().qc_joint_range(ptr(out))
     return out.reshape(6, 2)
 
 
 # ---- the host twin ------------------------------------------------------------------------------------------------------------------------------
-_twin = None
-
-
-def twin():
-    global _twin
-    if _twin is None:
-        d = os.path.join(HERE, "_querycheck")
-        subprocess.check_call(["make", "-C", d, "-s"])
-        lib = C.CDLL(os.path.join(d, "libquerycheck.so"))
-        p = C.c_void_p
-        for s, real in (("d", C.c_double), ("f", C.c_float)):
-            getattr(lib, "qc_kinematics_" + s).argtypes = [C.c_long] + [p] * 6
-            getattr(lib, "qc_jacobian_" + s).argtypes = [C.c_long, p, C.c_int, p, p, p]
-            getattr(lib, "qc_dynamics_" + s).argtypes = [C.c_long] + [p] * 6
-            getattr(lib, "qc_ik_" + s).argtypes = [C.c_long, p, p, C.c_int, p, C.c_int, real, real, real, p, p, p, p]
-            for fn in ("qc_kinematics_", "qc_jacobian_", "qc_dynamics_", "qc_ik_"):
-                getattr(lib, fn + s).restype = None
-        lib.qc_joint_range.argtypes, lib.qc_joint_range.restype = [p], None
-        _twin = lib
-    return _twin
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
 def _as(a, dtype):
     return None if a is None else np.ascontiguousarray(a, dtype)
 
@@ -77,21 +50,21 @@ def twin_kinematics(q, dtype):
     q = _as(q, dtype); n = len(q)
     o = {"xpos": np.zeros((n, 6, 3), dtype), "xmat": np.zeros((n, 6, 9), dtype), "ee": np.zeros((n, 3), dtype),
          "cam_pos": np.zeros((n, 3), dtype), "cam_mat": np.zeros((n, 9), dtype)}
-    getattr(twin(), "qc_kinematics_" + _suffix(dtype))(n, _p(q), *[_p(o[k]) for k in ("xpos", "xmat", "ee", "cam_pos", "cam_mat")])
+    getattr(hostlibs.querycheck(), "qc_kinematics_" + _suffix(dtype))(n, ptr(q), *[ptr(o[k]) for k in ("xpos", "xmat", "ee", "cam_pos", "cam_mat")])
     return o
 
 
 def twin_jacobian(q, dtype, link=EE_LINK, offset=None):
     q = _as(q, dtype); n = len(q); off = _as(offset, dtype)
     o = {"jacp": np.zeros((n, 3, 6), dtype), "jacr": np.zeros((n, 3, 6), dtype)}
-    getattr(twin(), "qc_jacobian_" + _suffix(dtype))(n, _p(q), link, _p(off), _p(o["jacp"]), _p(o["jacr"]))
+    getattr(hostlibs.querycheck(), "qc_jacobian_" + _suffix(dtype))(n, ptr(q), link, ptr(off), ptr(o["jacp"]), ptr(o["jacr"]))
     return o
 
 
 def twin_dynamics(q, v, qacc, dtype):
     q, v, qacc = _as(q, dtype), _as(v, dtype), _as(qacc, dtype); n = len(q)
     o = {"M": np.zeros((n, 6, 6), dtype), "bias": np.zeros((n, 6), dtype), "tau": np.zeros((n, 6), dtype)}
-    getattr(twin(), "qc_dynamics_" + _suffix(dtype))(n, _p(q), _p(v), _p(qacc), _p(o["M"]), _p(o["bias"]), _p(o["tau"]))
+    getattr(hostlibs.querycheck(), "qc_dynamics_" + _suffix(dtype))(n, ptr(q), ptr(v), ptr(qacc), ptr(o["M"]), ptr(o["bias"]), ptr(o["tau"]))
     if qacc is None:
         del o["tau"]
     return o
@@ -100,8 +73,8 @@ def twin_dynamics(q, v, qacc, dtype):
 def twin_ik(q0, target, dtype, link=EE_LINK, offset=None, iters=64, damping=0.02, tol=1e-4, max_step=0.3):
     q0, target, off = _as(q0, dtype), _as(target, dtype), _as(offset, dtype); n = len(q0)
     o = {"q": np.zeros((n, 6), dtype), "residual": np.zeros(n, dtype), "iterations": np.zeros(n, np.int32), "converged": np.zeros(n, np.uint8)}
-    getattr(twin(), "qc_ik_" + _suffix(dtype))(n, _p(q0), _p(target), link, _p(off), iters, damping, tol, max_step,
-                                               _p(o["q"]), _p(o["residual"]), _p(o["iterations"]), _p(o["converged"]))
+    getattr(hostlibs.querycheck(), "qc_ik_" + _suffix(dtype))(n, ptr(q0), ptr(target), link, ptr(off), iters, damping, tol, max_step,
+                                               ptr(o["q"]), ptr(o["residual"]), ptr(o["iterations"]), ptr(o["converged"]))
     return o
 
 
@@ -128,7 +101,7 @@ def oracle_kinematics(q):
         o["cam_pos"][i], o["cam_mat"][i] = O.arr(d.cam_xpos), O.arr(d.cam_xmat)
         o["xaxis"][i], o["xanchor"][i] = O.arr(d.xaxis)[:6], O.arr(d.xanchor)[:6]
         xp, xm = np.array(o["xpos"][i, EE_LINK]), np.array(o["xmat"][i, EE_LINK])
-        L.so100o_end_effector(_p(xp), _p(xm), _p(o["ee"][i]))
+        L.so100o_end_effector(ptr(xp), ptr(xm), ptr(o["ee"][i]))
     return o
 
 

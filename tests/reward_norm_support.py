@@ -1,21 +1,20 @@
 """What the reward-normalisation tests share (test_reward_norm_cpu.py, test_gpu_reward_norm.py): the numpy fp64 reference of the section
 "Reward normalisation" of include/so100_learn.h -- SB3's VecNormalize(norm_reward=True) over its RunningMeanStd, written from the header's
-text; it shares no line with csrc/ or ppo.py -- the host twin of csrc/so100_learn.hpp's templates, tests/_rewnormcheck/librewnormcheck.so,
-built and loaded here, and the inputs and comparisons both modules use.
+text; it shares no line with csrc/ or ppo.py -- the calls into the host twin of csrc/so100_learn.hpp's templates
+(tests/_learncheck/rewnormcheck.cpp in hostlibs.learncheck()), and the inputs and comparisons both modules use.
 
 Tolerances (derived, not measured).  The reference sums with numpy's pairwise order, the code under test with blocks of 64, a fixed tree
 and Chan's merge: in fp64 the two differ by about N 2^-53 relative, far below half an fp32 ulp, so an output differs from the reference's
 only where the fp64 value sits on an fp32 rounding boundary: every output is within 1 fp32 ulp.  mean and var match to 1e-10 relative
 (the linear worst case T N 2^-53 is 3e-11 at 262 144 entries).  count and the final return of an env whose episode ended on the chunk's last
 step (0) are exact."""
-import ctypes as C
 import functools
-import os
-import subprocess
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
+import hostlibs
+from hostlibs import ptr
+
 EPSILON, CLIP = 1e-8, 10.0
 GAMMA = float(np.float32(0.99))                       # the learner's gamma is a float: widened from it
 MOMENT_TOL = 1e-10
@@ -56,23 +55,6 @@ def ref_normalize(rewards, codes, state, gamma=GAMMA, epsilon=EPSILON, clip=CLIP
     return out, np.concatenate([[mean, var, count], ret])
 
 
-_twin = None
-
-
-def rewnormcheck():
-    """the host twin: rn_block(), rn_normalize(T, N, row, rew_col, code_col, chunk, gamma, epsilon, clip, state, out)"""
-    global _twin
-    if _twin is None:
-        d = os.path.join(HERE, "_rewnormcheck")
-        subprocess.check_call(["make", "-C", d, "-s"])
-        lib = C.CDLL(os.path.join(d, "librewnormcheck.so"))
-        lib.rn_block.restype, lib.rn_block.argtypes = C.c_int, []
-        lib.rn_normalize.restype = None
-        lib.rn_normalize.argtypes = [C.c_int] * 5 + [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p]
-        _twin = lib
-    return _twin
-
-
 def twin_normalize(rewards, codes, state, gamma=GAMMA, epsilon=EPSILON, clip=CLIP):
     """ref_normalize's interface on the twin; the two columns travel in rows of 5 floats, as columns 3 and 4 (a stride, as in the packed chunk)"""
     rewards = np.asarray(rewards, np.float32); T, N = rewards.shape
@@ -80,7 +62,7 @@ def twin_normalize(rewards, codes, state, gamma=GAMMA, epsilon=EPSILON, clip=CLI
     chunk[..., 3] = rewards; chunk[..., 4] = codes
     st = np.array(state, np.float64)
     out = np.empty((T, N), np.float32)
-    rewnormcheck().rn_normalize(T, N, 5, 3, 4, chunk.ctypes.data_as(C.c_void_p), gamma, epsilon, clip, st.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p))
+    hostlibs.learncheck().rn_normalize(T, N, 5, 3, 4, ptr(chunk), gamma, epsilon, clip, ptr(st), ptr(out))
     return out, st
 
 

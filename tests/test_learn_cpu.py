@@ -89,21 +89,6 @@ def test_parameter_block_layout(L):
         assert off == P
 
 
-def test_every_twin_symbol_has_its_signature_declared():
-    """what test_hostlibs.py checks for the other twins: the extern "C" definitions of learncheck.cpp against hostlibs.LEARNCHECK"""
-    scalars = {"int": C.c_int, "long": C.c_long, "float": C.c_float, "double": C.c_double}
-    src = re.sub(r"//[^\n]*", "", open(os.path.join(hostlibs.HERE, "_learncheck", "learncheck.cpp")).read())
-    want = {}
-    for ret, name, params in re.findall(r'^(void|int)\s+(lc_\w+)\s*\(([^)]*)\)\s*\{', src, flags=re.M):
-        args = [C.c_void_p if "*" in prm else scalars[" ".join(prm.split()[:-1])] for prm in (x.strip() for x in params.split(",")) if prm]
-        want[name] = ({"void": None, "int": C.c_int}[ret], args)
-    assert len(want) >= 9 and sorted(want) == sorted(hostlibs.LEARNCHECK)
-    lib = hostlibs.learncheck()
-    for name, (restype, argtypes) in want.items():
-        fn = getattr(lib, name)
-        assert list(fn.argtypes) == argtypes and fn.restype is restype, name
-
-
 REL = 1e-12      # fp64 arithmetic on both sides (the hostcheck convention)
 
 

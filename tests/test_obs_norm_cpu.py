@@ -13,6 +13,7 @@ import pytest
 import torch
 from click.testing import CliRunner
 
+import hostlibs
 import learn_support as LS
 import obs_norm_support as OS
 
@@ -43,7 +44,7 @@ def test_reference_reproduces_the_known_answer():
 @pytest.mark.parametrize("od", OS.OBS_DIMS)
 @pytest.mark.parametrize("T,N", OS.SHAPES)
 def test_twin_moments_match_the_reference(T, N, od):
-    assert OS.obsnormcheck().on_block() == 256 and OS.obsnormcheck().on_group() == 64
+    assert hostlibs.learncheck().on_block() == 256 and hostlibs.learncheck().on_group() == 64
     obs = OS.make_obs(T, N, od)
     got = OS.twin_update(obs, OS.fresh_state(od))
     rel = OS.check_state(got, OS.reference(T, N, od))
@@ -225,7 +226,7 @@ def test_struct_and_exports_match_the_header():
     for call, msg in calls:
         assert call() == -1, msg
         assert L.so100_last_error() == msg
-    block, group = OS.obsnormcheck().on_block(), OS.obsnormcheck().on_group()
+    block, group = hostlibs.learncheck().on_block(), hostlibs.learncheck().on_group()
     for T, N in ((1, 1), (64, 4096), (5, 67), (4096, 4096)):                   # [blocks][15] (mean, M2) pairs, then [groups][15] (n, mean, M2) triples, fp64
         blocks = -(-T * N // block)
         assert L.so100_learner_obs_norm_workspace(T, N) == 8 * 15 * (2 * blocks + 3 * -(-blocks // group))

@@ -10,6 +10,7 @@ import pytest
 import torch
 from click.testing import CliRunner
 
+import hostlibs
 import learn_support as LS
 import reward_norm_support as RS
 
@@ -206,7 +207,7 @@ def test_null_arguments_are_refused_without_a_device(L):
     for call, msg in calls:
         assert call() == -1, msg
         assert L.so100_last_error() == msg
-    block = RS.rewnormcheck().rn_block()
+    block = hostlibs.learncheck().rn_block()
     assert block == 64
     for T, N in ((1, 1), (64, 4096), (5, 67)):                                 # [T][blocks] (mean, M2) pairs and T denominators, fp64
         assert L.so100_learner_reward_norm_workspace(T, N) == 8 * (T * -(-N // block) * 2 + T)

@@ -1,44 +1,29 @@
 """What the tests of the one-call update share (test_learn_update_cpu.py, test_gpu_learner_update.py): the numpy reference of the permutation
 that include/so100_learn.h specifies, written from the header's text over oracle.so100_oracle.philox4x32_np -- it shares no line with
-csrc/so100_learn.hpp -- and the host twin of that header's shuffle_index, tests/_shufflecheck/libshufflecheck.so, built and loaded here."""
-import ctypes as C
+csrc/so100_learn.hpp -- and the calls into the host twin of that header's shuffle_index (tests/_learncheck/shufflecheck.cpp in hostlibs.learncheck())."""
 import functools
-import os
-import subprocess
 
 import numpy as np
 
+import hostlibs
+from hostlibs import ptr
 from oracle.so100_oracle import philox4x32_np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 SHUFFLE_STREAM = 0x53484633
 ROUNDS = 6
 
-_twin = None
-
-
-def shufflecheck():
-    """the host twin: sc_shuffle(seed, epoch, n, out int64[n]), sc_shuffle_epochs(seed, epoch0, epochs, n, out int32[epochs][n])"""
-    global _twin
-    if _twin is None:
-        d = os.path.join(HERE, "_shufflecheck")
-        subprocess.check_call(["make", "-C", d, "-s"])
-        lib = C.CDLL(os.path.join(d, "libshufflecheck.so"))
-        lib.sc_shuffle.restype, lib.sc_shuffle.argtypes = None, [C.c_ulonglong, C.c_uint, C.c_long, C.c_void_p]
-        lib.sc_shuffle_epochs.restype, lib.sc_shuffle_epochs.argtypes = None, [C.c_ulonglong, C.c_uint, C.c_int, C.c_int, C.c_void_p]
-        _twin = lib
-    return _twin
-
 
 def twin_perm(seed, epoch, n):
+    """sc_shuffle(seed, epoch, n, out int64[n])"""
     out = np.empty(n, np.int64)
-    shufflecheck().sc_shuffle(seed, epoch, n, out.ctypes.data_as(C.c_void_p))
+    hostlibs.learncheck().sc_shuffle(seed, epoch, n, ptr(out))
     return out
 
 
 def twin_perms(seed, epoch0, epochs, n):
+    """sc_shuffle_epochs(seed, epoch0, epochs, n, out int32[epochs][n])"""
     out = np.empty((epochs, n), np.int32)
-    shufflecheck().sc_shuffle_epochs(seed, epoch0, epochs, n, out.ctypes.data_as(C.c_void_p))
+    hostlibs.learncheck().sc_shuffle_epochs(seed, epoch0, epochs, n, ptr(out))
     return out
 
 
