@@ -62,6 +62,23 @@ int main(int argc, char** argv) {
         double ez = 0, rmax = 0; long nconv = 0;
         for (int i = 0; i < n; i++) { ez += h_ee[2*(size_t)n + i]; rmax = std::fmax(rmax, h_res[i]); nconv += h_conv[i]; }
         std::printf("queries: mean end-effector height %.4f m  IK onto the cube: %ld of %d converged, worst residual %.2e m\n", ez/n, nconv, n, rmax);
+        // forward dynamics on the handle's own state (qpos_dev / qvel_dev NULL), the servos holding the pose: how many envs touch something, and how hard
+        int32_t* ncon; float* padf;
+        CHECK(hipMalloc(&ncon, sizeof(int32_t)*n)); CHECK(hipMalloc(&padf, sizeof(float)*8*n));
+        so100_forward_io fio = {};
+        fio.flags = cfg.flags; fio.solver_iters = SO100_FWD_SOLVER_ITERS; fio.contact_iters = SO100_FWD_CONTACT_ITERS;
+        fio.ncon_dev = ncon; fio.pad_force_dev = padf;
+        if (so100_query_forward(sim, &fio, n, st) != 0) { std::fprintf(stderr, "so100_query_forward: %s\n", so100_last_error()); return 1; }
+        CHECK(hipStreamSynchronize(st));
+        std::vector<int32_t> h_ncon(n); std::vector<float> h_padf(8*(size_t)n);
+        CHECK(hipMemcpy(h_ncon.data(), ncon, sizeof(int32_t)*n, hipMemcpyDeviceToHost)); CHECK(hipMemcpy(h_padf.data(), padf, sizeof(float)*h_padf.size(), hipMemcpyDeviceToHost));
+        long contacts = 0, touching = 0; double fmax = 0;
+        for (int i = 0; i < n; i++) {
+            contacts += h_ncon[i];
+            double f = 0; for (int g = 0; g < 8; g++) f += h_padf[g*(size_t)n + i];
+            touching += f > 0; fmax = std::fmax(fmax, f);
+        }
+        std::printf("forward: %ld contacts in all; %ld of %d envs press a finger pad on something, the hardest with %.3f N\n", contacts, touching, n, fmax);
     }
     // ---- the learner from plain C++ (so100_learn.h): advantages of a small synthetic chunk, then one PPO minibatch step on all of it
     {

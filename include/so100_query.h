@@ -1,5 +1,5 @@
-/* so100_query.h -- model queries of libso100sim.so: what MuJoCo's users read from MjData or get from mj_jac, mj_fullM and
- * mj_inverse, for M independent problems at once, one GPU lane per problem.
+/* so100_query.h -- model queries of libso100sim.so: what MuJoCo's users read from MjData or get from mj_jac, mj_fullM,
+ * mj_inverse and mj_forward, for M independent problems at once, one GPU lane per problem (the forward query: four).
  *
  * Additive to so100_sim.h (SO100_ABI_VERSION is unchanged) and under its conventions: extern "C"; `*_dev` pointers are DEVICE
  * pointers owned by the caller; 0 on success, a negative SO100_E_* code otherwise with the message in so100_last_error(); all
@@ -100,6 +100,53 @@ typedef struct {
 } so100_ik_io;
 
 int so100_query_ik(so100_sim* sim, const so100_ik_io* io, int32_t M, void* hip_stream);
+
+/* Forward dynamics with constraints, without integrating: for each of M states the contacts that exist, the force each carries and the
+ * acceleration the constraint solve settles on -- mj_forward, MjData.contact, mj_contactForce, qfrc_constraint and qacc.  The stages are
+ * the ones a contact substep of so100_step runs (csrc/so100_forward.hpp), cold-started: no previous substep's forces or active set.
+ *
+ * State: qpos [13][M] and qvel [12][M] in so100_get_state's layout (arm 6, cube position 3, cube quaternion 4 / arm 6, cube linear 3 in
+ * the world frame, cube angular 3 in the body frame).  Both NULL: the handle's rows, and M must be N.  qvel alone NULL: zero.
+ * ctrl NULL: ctrl = q, the servo holds the pose (Env01's ctrl under a zero action).  No force is applied to the cube.
+ * flags: SO100_F_*, decided per call (the handle's own flags are not consulted).
+ *
+ * The contact list has SO100_FWD_MAXCON slots per problem; slots at or beyond ncon are zeros with feat = -1.  It holds every contact of
+ * the solve, the cube's own floor contacts included.  kind and feat are numbered as the oracle's so100o_contact: kind 0 cube/floor,
+ * 1 pad/floor, 2 pad/cube, 3 link proxy/floor, 4 link proxy/cube; feat 8 pad + corner, 64 + 8 pad + manifold slot, 128 + corner,
+ * 144 + 2 proxy + capsule end, 160 + proxy.  The order is the detection order: deterministic, otherwise not part of the contract -- match
+ * by feat, which is unique within a problem.  frame rows: normal (geom1 -> geom2), t1, t2 (mju_makeFrame); force = mj_contactForce's first
+ * three numbers, in that frame; dist < 0 in penetration.
+ *
+ * Argument errors, in this order: a null handle or io; M < 1 (or M != N where the state is read); qvel_dev without qpos_dev; flag bits
+ * outside SO100_F_*; SO100_F_PADS_CUBE or SO100_F_LINKS_CUBE with SO100_F_CUBE_PINNED; an iteration count outside 1..64; no output.
+ * residual is that of contact_solve or, without arm contact, of the block PGS; the cube's own floor solve (so100_cube.hpp, run when the
+ * cube is not coupled to the arm) reports none, so residual = 0 says nothing about it -- it is bounded by contact_iters like the rest.
+ * A non-finite input gives that problem ncon = 0 and NaN accelerations.  Every output is nullable; at least one is required. */
+#define SO100_FWD_MAXCON        20
+#define SO100_FWD_SOLVER_ITERS  64     /* block-PGS sweeps of a contact-free arm */
+#define SO100_FWD_CONTACT_ITERS 64     /* Newton iterations (arm with contacts, cube on the floor) */
+typedef struct {
+    const float* qpos_dev;             /* [13][M] or NULL (with qvel_dev NULL: the handle's state)                 */
+    const float* qvel_dev;             /* [12][M] or NULL                                                           */
+    const float* ctrl_dev;             /* [6][M] servo targets (radians), or NULL: the joint angles                 */
+    uint32_t     flags;                /* SO100_F_*                                                                 */
+    int32_t      solver_iters;         /* 1..64                                                                     */
+    int32_t      contact_iters;        /* 1..64                                                                     */
+    float*       qacc_dev;             /* [12][M] arm 6, cube linear (world), cube angular (body): MuJoCo's dofs    */
+    float*       qfrc_constraint_dev;  /* [12][M]                                                                   */
+    int32_t*     ncon_dev;             /* [M]                                                                       */
+    int32_t*     dropped_dev;          /* [M] contacts beyond the budget of 16 arm contacts, not simulated          */
+    int32_t*     con_kind_dev;         /* [20][M]                                                                   */
+    int32_t*     con_feat_dev;         /* [20][M]                                                                   */
+    float*       con_pos_dev;          /* [20][3][M] world, midway between the surfaces                             */
+    float*       con_frame_dev;        /* [20][9][M]                                                                */
+    float*       con_dist_dev;         /* [20][M]                                                                   */
+    float*       con_force_dev;        /* [20][3][M]                                                                */
+    float*       pad_force_dev;        /* [8][M] normal force summed over each finger pad's contacts                */
+    float*       residual_dev;         /* [M] of the arm's solve (with its contacts; coupled: the cube's too): 0 when it converged, else the size of its last step */
+} so100_forward_io;
+
+int so100_query_forward(so100_sim* sim, const so100_forward_io* io, int32_t M, void* hip_stream);
 
 #ifdef __cplusplus
 }

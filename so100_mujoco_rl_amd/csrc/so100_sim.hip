@@ -302,3 +302,4 @@ int so100_set_field(so100_sim* s, int32_t field, const void* in_dev, void* strea
 // the model queries (include/so100_query.h): kernels and ABI functions of their own file, compiled into this object -- they read the
 // handle defined above, and the list of the product's objects stays what the side-build recipe names
 #include "so100_query.hip"
+#include "so100_query_forward.hip"

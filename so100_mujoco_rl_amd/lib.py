@@ -166,10 +166,19 @@ class IkIO(C.Structure):
                 ("iterations_dev", C.c_void_p), ("converged_dev", C.c_void_p)]
 
 
-QUERY_EXPORTS = ["so100_query_kinematics", "so100_query_jacobian", "so100_query_dynamics", "so100_query_ik"]
-QUERY_IO = {"so100_query_kinematics": KinematicsIO, "so100_query_jacobian": JacobianIO, "so100_query_dynamics": DynamicsIO, "so100_query_ik": IkIO}
+class ForwardIO(C.Structure):
+    _fields_ = [("qpos_dev", C.c_void_p), ("qvel_dev", C.c_void_p), ("ctrl_dev", C.c_void_p), ("flags", C.c_uint32), ("solver_iters", C.c_int32),
+                ("contact_iters", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("qacc_dev", "qfrc_constraint_dev", "ncon_dev", "dropped_dev", "con_kind_dev", "con_feat_dev", "con_pos_dev",
+                                          "con_frame_dev", "con_dist_dev", "con_force_dev", "pad_force_dev", "residual_dev")]
+
+
+QUERY_EXPORTS = ["so100_query_kinematics", "so100_query_jacobian", "so100_query_dynamics", "so100_query_ik", "so100_query_forward"]
+QUERY_IO = {"so100_query_kinematics": KinematicsIO, "so100_query_jacobian": JacobianIO, "so100_query_dynamics": DynamicsIO, "so100_query_ik": IkIO,
+            "so100_query_forward": ForwardIO}
 EE_LINK = 4                                                    # SO100_EE_LINK: the reference's end-effector point sits on Fixed_Jaw
 IK_ITERS, IK_DAMPING, IK_TOL, IK_MAX_STEP = 64, 0.02, 1e-4, 0.3     # SO100_IK_*
+FWD_MAXCON, FWD_SOLVER_ITERS, FWD_CONTACT_ITERS = 20, 64, 64        # SO100_FWD_*
 
 
 def build(verbose=False):
@@ -622,6 +631,25 @@ class So100Sim(_Handle):
                   tol, max_step, q.data_ptr(), res.data_ptr(), its.data_ptr(), conv.data_ptr())
         _check(self.L.so100_query_ik(self.h, C.byref(io), M, self._stream()), "so100_query_ik")
         return {"q": q.t(), "residual": res, "iterations": its, "converged": conv}
+
+    def forward(self, qpos=None, qvel=None, ctrl=None, flags=None, solver_iters=FWD_SOLVER_ITERS, contact_iters=FWD_CONTACT_ITERS):
+        """mj_forward for M states without stepping anything: the contacts, their forces and the constrained accelerations.  qpos [M, 13] and
+        qvel [M, 12] as get_state() lays them out (both None: the handle's state, M = N; qvel alone None: zero), ctrl [M, 6] servo targets
+        (None: the joint angles -- hold the pose), flags: SO100_F_* (None: the handle's).  Returns views, one row per problem: "qacc" and
+        "qfrc_constraint" [M, 12] (arm 6, cube linear in the world frame, cube angular in the body frame), "ncon", "dropped" [M] int32,
+        "residual" [M], "pad_force" [M, 8] (normal force per finger pad) and "contacts" = {"kind" (0 cube/floor, 1 pad/floor, 2 pad/cube, 3 proxy/floor,
+        4 proxy/cube), "feat" [M, 20] int32 (feat -1 marks an empty slot), "pos" [M, 20, 3], "frame" [M, 20, 3, 3] (rows normal, t1, t2), "dist" [M, 20], "force" [M, 20, 3] (in the frame)}."""
+        qs, vs, us = self._soa(qpos, 13, "qpos"), self._soa(qvel, 12, "qvel"), self._soa(ctrl, 6, "ctrl"); M = self._problems(qs, vs, us)
+        i32 = dict(dtype=torch.int32)
+        qacc, qfrc, ncon, drop, res, pf = self._out(M, 12), self._out(M, 12), self._out(M, **i32), self._out(M, **i32), self._out(M), self._out(M, 8)
+        kind, feat, pos = self._out(M, FWD_MAXCON, **i32), self._out(M, FWD_MAXCON, **i32), self._out(M, FWD_MAXCON, 3)
+        frame, dist, force = self._out(M, FWD_MAXCON, 9), self._out(M, FWD_MAXCON), self._out(M, FWD_MAXCON, 3)
+        io = ForwardIO(*[t.data_ptr() if t is not None else None for t in (qs, vs, us)], self.cfg.flags if flags is None else flags, solver_iters,
+                       contact_iters, *[t.data_ptr() for t in (qacc, qfrc, ncon, drop, kind, feat, pos, frame, dist, force, pf, res)])
+        _check(self.L.so100_query_forward(self.h, C.byref(io), M, self._stream()), "so100_query_forward")
+        return {"qacc": qacc.t(), "qfrc_constraint": qfrc.t(), "ncon": ncon, "dropped": drop, "residual": res, "pad_force": pf.t(),
+                "contacts": {"kind": kind.t(), "feat": feat.t(), "pos": pos.permute(2, 0, 1), "frame": frame.permute(2, 0, 1).unflatten(2, (3, 3)),
+                             "dist": dist.t(), "force": force.permute(2, 0, 1)}}
 
 
 def learner_layout(obs_dim):

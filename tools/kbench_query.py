@@ -2,12 +2,22 @@
 """Time the model queries (include/so100_query.h) with HIP events, through the C ABI on preallocated buffers (needs a GPU).
 
     python tools/kbench_query.py [--out profiles/query_kbench.json] [--commit LABEL] [--rounds 5]
+    python tools/kbench_query.py --forward [--out profiles/forward_kbench.json] [--commit LABEL] [--rounds 5]
 
 Cases, at M = 4096 and M = 1 048 576 problems: kinematics with every output and with the end-effector point alone, the Jacobian (jacp and
 jacr), the dynamics (M, bias and tau) and the IK.  Poses are uniform over the joint ranges; the IK problems are the 400 of the tests' recipe
 (tests/query_support.py: a reachable target, a start up to 0.3 rad away, the default parameters) repeated to fill M.  The cases are timed
 in alternation, `--rounds` times each; a figure is the median of the rounds, one round the mean over its calls.  There is nothing to
-compare against: the file is a record, not a gate."""
+compare against: the file is a record, not a gate.
+
+--forward times the forward-dynamics query (so100_query_forward, every output, 64 / 64 iterations) instead, at M = 4096 and M = 262 144, on
+three populations: poses drawn uniformly over the joint ranges and kept where no arm geom touches anything (the cube rests on the floor), the
+pad/floor states of the tests' recipe (tests/forward_support.py: family "floor") and its coupled states (family "floor_cube" and the states of
+"grasp" that are in contact), each repeated to fill M.  Beside each figure stands one so100_step of a handle of M envs with frame_skip = 1 and
+the same flags and iteration counts, its state set to the same states before every call.  The two are timed alike (timed_pairs: an event pair
+round each single call, the set_state copies outside the span, the calls enqueued without waiting); the forward query's back-to-back time,
+one event pair round all calls of a round, is recorded as well:
+the existing code doing the same solve from the warm-start rows of its state, plus the integration and the task layer."""
 import argparse
 import ctypes as C
 import json
@@ -28,11 +38,111 @@ import query_support as S             # noqa: E402
 SIZES = [(4096, 200), (1 << 20, 10)]          # (M, calls per timed round)
 
 
+FORWARD_SIZES = [(4096, 200), (262144, 20)]     # (M, calls per timed round)
+
+
+def forward_populations(sim):
+    """{name: (flags, qpos [n, 13], qvel [n, 12], ctrl [n, 6])}, float32"""
+    import forward_support as F
+    import scenes
+    rs = np.random.RandomState(0)
+    rng = S.joint_range()
+    n = 1 << 16
+    qpos = np.zeros((n, 13), np.float32); qpos[:, :6] = rs.uniform(rng[:, 0], rng[:, 1], (n, 6)); qpos[:, 6:9] = [0.15, -0.25, 0.0099]; qpos[:, 9] = 1.0
+    qvel = np.zeros((n, 12), np.float32); qvel[:, :6] = rs.randn(n, 6)*0.3
+    ctrl = (qpos[:, :6] + rs.uniform(-1, 1, (n, 6))*0.075).astype(np.float32)
+    t = lambda x: torch.from_numpy(x).to(sim.device)
+    con = sim.forward(t(qpos), t(qvel), t(ctrl), flags=lib.F_REFERENCE)["contacts"]
+    free = ~((con["kind"] > 0).any(dim=1)).cpu().numpy()
+    floor, cube, grasp = F.family("floor"), F.family("floor_cube"), F.family("grasp")
+    touching = np.array([r["ncon"] > 0 for r in grasp.refs])
+    both = lambda a: np.concatenate([getattr(cube, a), getattr(grasp, a)[touching]])
+    return {"free": (lib.F_REFERENCE, qpos[free], qvel[free], ctrl[free]),
+            "pad_floor": (scenes.REFP, floor.qpos, floor.qvel, floor.ctrl),
+            "coupled": (scenes.C5, both("qpos"), both("qvel"), both("ctrl"))}
+
+
+def forward_main(a):
+    probe = lib.So100Sim(lib.ENV01, 64, device="cuda:0", flags=lib.F_REFERENCE, seed=0)
+    pops = forward_populations(probe)
+    dev, L = probe.device, probe.L
+    doc = {"what": "HIP-event time per call of so100_query_forward (every output, 64 / 64 iterations) and of one so100_step with frame_skip = 1 on the "
+                   "same states, flags and iteration counts, both as an event pair round each single call; forward also back to back; medians of alternated rounds", "commit": a.commit, "card": torch.cuda.get_device_name(0),
+           "rounds": a.rounds, "cases": []}
+    for M, reps in FORWARD_SIZES:
+        for name, (flags, qpos, qvel, ctrl) in pops.items():
+            idx = np.arange(M) % len(qpos)
+            soa = lambda x: torch.from_numpy(np.ascontiguousarray(x[idx].T, np.float32)).to(dev)
+            qs, vs, us_ = soa(qpos), soa(qvel), soa(ctrl)
+            act = ((us_[:6] - qs[:6])/0.075).t().contiguous()          # Env01: ctrl = q + 0.075 action
+            out = torch.empty(12 + 12 + 8 + 1 + 20*(3 + 9 + 1 + 3), M, dtype=torch.float32, device=dev)
+            ints = torch.empty(2 + 40, M, dtype=torch.int32, device=dev)
+            p, pi = (lambda r: out[r].data_ptr()), (lambda r: ints[r].data_ptr())
+            io = lib.ForwardIO(qs.data_ptr(), vs.data_ptr(), us_.data_ptr(), flags, 64, 64, p(0), p(12), pi(0), pi(1), pi(2), pi(22), p(33), p(93), p(273), p(293), p(24), p(32))
+            sim = lib.So100Sim(lib.ENV01, M, device="cuda:0", flags=flags, solver_iters=64, contact_iters=64, frame_skip=1, max_episode_steps=0, seed=0)
+            sim.reset()
+            st = sim._stream()
+
+            def timed_forward(n):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(n):
+                    rc = L.so100_query_forward(sim.h, C.byref(io), M, st)
+                    assert rc == 0, L.so100_last_error()
+                e1.record()
+                torch.cuda.synchronize()
+                return e0.elapsed_time(e1)*1e3/n
+
+            def timed_pairs(call, n):
+                """forward and step timed alike: n times {set_state copies, event, ONE call, event}, enqueued without waiting, one synchronise at
+                the end; the sum of the n event spans.  (A step moves the state, so its calls cannot run back to back on the same states.)"""
+                pairs = []
+                for _ in range(n):
+                    sim.set_state(qs, vs)
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record(); call(); e1.record()
+                    pairs.append((e0, e1))
+                torch.cuda.synchronize()
+                return sum(e0.elapsed_time(e1) for e0, e1 in pairs)*1e3/n
+
+            def one_forward():
+                rc = L.so100_query_forward(sim.h, C.byref(io), M, st)
+                assert rc == 0, L.so100_last_error()
+
+            one_step = lambda: sim.step(act)
+            timed_forward(a.warmup); timed_pairs(one_forward, a.warmup); timed_pairs(one_step, a.warmup)
+            fw, fp, sp = [], [], []
+            for _ in range(a.rounds):
+                fw.append(timed_forward(reps)); fp.append(timed_pairs(one_forward, reps)); sp.append(timed_pairs(one_step, reps))
+            ncon = ints[0].float()
+            med, medp, meds = statistics.median(fw), statistics.median(fp), statistics.median(sp)
+            case = {"case": name, "M": M, "flags": int(flags), "states": int(len(qpos)), "forward_back_to_back_us_per_call": round(med, 2),
+                    "forward_us_per_call": round(medp, 2), "step_us_per_call": round(meds, 2), "forward_over_step": round(medp/meds, 3),
+                    "forward_back_to_back_rounds_us": [round(x, 2) for x in fw], "forward_rounds_us": [round(x, 2) for x in fp],
+                    "step_rounds_us": [round(x, 2) for x in sp],
+                    "calls_per_round": reps, "problems_per_s": round(M/(med*1e-6), 1), "mean_ncon": round(ncon.mean().item(), 3),
+                    "share_in_contact": round((ncon > 0).float().mean().item(), 4), "worst_residual": float(out[32].max().item())}
+            doc["cases"].append(case)
+            print(json.dumps(case), flush=True)
+            sim.close()
+            del out, ints
+    probe.close()
+    with open(a.out, "w") as fh:
+        json.dump(doc, fh, indent=1)
+        fh.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "query_kbench.json")); ap.add_argument("--commit", default="unknown")
+    ap.add_argument("--out", default=None); ap.add_argument("--commit", default="unknown")
     ap.add_argument("--rounds", type=int, default=5); ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--forward", action="store_true", help="time the forward-dynamics query against so100_step (profiles/forward_kbench.json)")
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "forward_kbench.json" if a.forward else "query_kbench.json")
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    if a.forward:
+        return forward_main(a)
     sim = lib.So100Sim(lib.ENV01, 64, device="cuda:0", flags=lib.F_REFERENCE, seed=0)
     dev, L, h = sim.device, sim.L, sim.h
     rs = np.random.RandomState(0)
@@ -83,7 +193,6 @@ def main():
             doc["cases"].append(case)
             print(json.dumps(case), flush=True)
     sim.close()
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as fh:
         json.dump(doc, fh, indent=1)
         fh.write("\n")
