@@ -1,6 +1,8 @@
 """What the test_gpu_* modules share (imported by them only: it needs torch and the HIP library): handles, state injection, the
 GPU / oracle pair stepped on identical inputs, and the float references of the policy."""
+import contextlib
 import ctypes as C
+import os
 
 import numpy as np
 import torch
@@ -14,6 +16,25 @@ LOG2PI_HALF = 0.9189385332046727
 def make_sim(*a, **k):
     from so100_mujoco_rl_amd.lib import So100Sim
     return So100Sim(*a, **k)
+
+
+@contextlib.contextmanager
+def one_wave_step_kernel(on=True):
+    """A handle created inside this block steps through the one-wave kernel so100_step_fused at every batch size instead of the 4-wave
+    so100_step_mw: SO100_MW_MAX_ENVS = 0 is read by so100_create, so only the creation has to be inside.  The variable is put back as
+    it was on the way out; on=False leaves everything alone (callers pass their mode test)."""
+    if not on:
+        yield
+        return
+    old = os.environ.get("SO100_MW_MAX_ENVS")
+    os.environ["SO100_MW_MAX_ENVS"] = "0"
+    try:
+        yield
+    finally:
+        if old is None:
+            del os.environ["SO100_MW_MAX_ENVS"]
+        else:
+            os.environ["SO100_MW_MAX_ENVS"] = old
 
 
 def inject_state(sim, qpos, qvel):

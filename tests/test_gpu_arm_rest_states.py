@@ -7,15 +7,13 @@ into the special states through set_field after the reset; the other 41 keep the
 form of RNEA / CRBA, one wave each) is compared with the stepwise policy_forward + step sequence through the 4-wave step kernel and through
 the one-wave so100_step_fused (the scalar form), under the bounds of test_gpu_substep_loop.py::_close: 1e-6, rewards 2e-5, joint velocities
 1e-5.  Everything must be finite, and two identical launches must agree bit for bit."""
-import os
-
 import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
-from gpu_support import make_sim                          # noqa: E402
+from gpu_support import make_sim, one_wave_step_kernel    # noqa: E402
 from scenes import FREE, JNT_HI, JNT_LO                   # noqa: E402
 from test_gpu_substep_loop import KEYS, _close, _policy   # noqa: E402
 
@@ -42,17 +40,8 @@ def special_states():
 
 def _run(frame_skip, mode):
     """test_gpu_substep_loop._run with the special states written over the first envs between reset and the first step"""
-    old = os.environ.get("SO100_MW_MAX_ENVS")
-    if mode == "one_wave":
-        os.environ["SO100_MW_MAX_ENVS"] = "0"                # read when the handle is created: so100_step_fused instead of the 4-wave kernel
-    try:
+    with one_wave_step_kernel(mode == "one_wave"):          # so100_step_fused instead of the 4-wave kernel
         sim = make_sim(1, N, flags=FREE, frame_skip=frame_skip, seed=4, envs_per_workgroup=32)
-    finally:
-        if mode == "one_wave":
-            if old is None:
-                del os.environ["SO100_MW_MAX_ENVS"]
-            else:
-                os.environ["SO100_MW_MAX_ENVS"] = old
     assert sim.envs_per_workgroup == 32
     sim.set_policy(_policy(sim.obs_dim, sim.device))
     sim.reset()

@@ -635,33 +635,46 @@ def test_multiwave_step_kernel_equals_throughput_kernel(kind, flags):
     torch.testing.assert_close(q1, q2[:, :n], rtol=0, atol=2e-6); torch.testing.assert_close(v1, v2[:, :n], rtol=0, atol=2e-5)
 
 
-def test_dense_throughput_kernel_131072():
-    """N >= 131 072 with friction / limit / cube-floor physics: so100_step takes the 2-waves-per-SIMD build of the throughput kernel
-    (256 registers + scratch).  Same source, so the results must be BIT-IDENTICAL to the 1-wave-per-SIMD build that two half-size
-    handles take (65 536 envs each, env_id_offset keeps the Philox streams), and 32 sampled envs are held to the fp64 oracle."""
+@pytest.mark.parametrize("kind,flags", [(1, NOPADS), (5, ARM)])
+def test_dense_throughput_kernel_131072(kind, flags):
+    """N >= 131 072 with friction / limit (/ cube-floor) physics: so100_step takes the 2-waves-per-SIMD build of the throughput kernel
+    (256 registers + scratch), so100_step_fused<K, FL, true>, for its two flag sets NOPADS and ARM.  Same source, so the results must be
+    BIT-IDENTICAL to the 1-wave-per-SIMD build that two half-size handles take (65 536 envs each, env_id_offset keeps the Philox
+    streams), and 32 sampled envs are held to the fp64 oracle: Env01 with the bounds of test_env01_vs_oracle, Env05 (the 8-wide
+    observation, un-injected pixel noise) with the look-at bounds of _lookat_envs_vs_oracle."""
     n, steps = 131072, 5
     rs = np.random.RandomState(12)
     sample = np.sort(rs.choice(n, 32, replace=False)); sample[0] = 0; sample[-1] = n - 1
-    sim = make_sim(1, n, flags=NOPADS, solver_iters=4, seed=23, max_episode_steps=3)
-    orc = [O.OracleEnv(1, flags=NOPADS, iters=0, seed=23, env_id=int(i)) for i in sample]
+    sim = make_sim(kind, n, flags=flags, solver_iters=4, seed=23, max_episode_steps=3)
+    orc = [O.OracleEnv(kind, flags=flags, iters=0, seed=23, env_id=int(i)) for i in sample]
     for e in orc:
         e.e.max_episode_steps = 3
     sim.reset(); [e.reset() for e in orc]
     g = torch.Generator(device="cuda"); g.manual_seed(6)
     acts = [torch.rand(n, 6, device="cuda", generator=g) * 2 - 1 for _ in range(steps)]
     trace = []
+    n_px = n_px_bad = 0
     for t in range(steps):
         ob, r, d, tr = sim.step(acts[t])
         trace.append(torch.cat([ob, r[:, None], d[:, None].float()], 1).clone())
         a_h = acts[t][sample].cpu().numpy()
         res = [e.step(a_h[j], autoreset=True) for j, e in enumerate(orc)]
-        np.testing.assert_allclose(ob[sample].cpu().numpy(), np.stack([x[0] for x in res]), rtol=0, atol=2e-5)
-        np.testing.assert_allclose(r[sample].cpu().numpy(), np.array([x[1] for x in res]), rtol=0, atol=1e-4)
+        og = ob[sample].cpu().numpy(); oo = np.stack([x[0] for x in res])
+        if kind == 1:
+            np.testing.assert_allclose(og, oo, rtol=0, atol=2e-5)
+            np.testing.assert_allclose(r[sample].cpu().numpy(), np.array([x[1] for x in res]), rtol=0, atol=1e-4)
+        else:
+            np.testing.assert_allclose(og[:, :6], oo[:, :6], rtol=0, atol=1e-6)
+            dp = np.abs(og[:, 6:] - oo[:, 6:])
+            n_px += dp.size; n_px_bad += int((dp > 1e-4).sum())
+            assert dp.max() < 6e-3, (t, dp.max())
+            np.testing.assert_allclose(r[sample].cpu().numpy(), np.array([x[1] for x in res]), rtol=0, atol=2e-3)
         np.testing.assert_array_equal(d[sample].cpu().numpy().astype(bool), np.array([x[2] or x[3] for x in res]))
+    assert n_px_bad <= 0.01 * n_px                       # off-by-one pixels are rare
     full = torch.cat(trace, 1); sim.close()
     halves = []
     for off in (0, n // 2):
-        s2 = make_sim(1, n // 2, flags=NOPADS, solver_iters=4, seed=23, max_episode_steps=3, env_id_offset=off); s2.reset(); tr2 = []
+        s2 = make_sim(kind, n // 2, flags=flags, solver_iters=4, seed=23, max_episode_steps=3, env_id_offset=off); s2.reset(); tr2 = []
         for t in range(steps):
             ob, r, d, _ = s2.step(acts[t][off:off + n // 2].contiguous())
             tr2.append(torch.cat([ob, r[:, None], d[:, None].float()], 1).clone())

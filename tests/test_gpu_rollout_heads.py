@@ -18,14 +18,13 @@ step kernel.  No race: two identical launches, and one T = 3 launch against thre
 rows of n = 33 are bit-equal to the first 33 envs' rows of n = 96 (slot = env in these variants and every random draw is keyed by the env's
 index, so they are the same envs)."""
 import functools
-import os
 
 import pytest
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
-from gpu_support import make_sim, policy_tensors                       # noqa: E402
+from gpu_support import make_sim, one_wave_step_kernel, policy_tensors   # noqa: E402
 from scenes import FREE                                                # noqa: E402
 from test_gpu_rollout_oracle import _saturating_policy                 # noqa: E402
 from test_gpu_rollout_prestep import KEYS, T, _close, _policy          # noqa: E402
@@ -71,18 +70,9 @@ POLICIES = {"random": lambda od, dev, kind, epw: _policy(od, dev),
 def _run(kind, n, epw, frame_skip, policy, mode):
     """test_gpu_rollout_prestep.py's _run with the policy as an argument; results are shared between cases and never written to.
     mode: "persistent" (one so100_rollout launch of T steps), "again" (the same once more), "chunks" (T launches of one step), "stepwise"
-    (policy_forward + step, 4-wave step kernel), "one_wave" (the same with so100_step_fused: SO100_MW_MAX_ENVS = 0 when the handle is created)"""
-    old = os.environ.get("SO100_MW_MAX_ENVS")
-    if mode == "one_wave":
-        os.environ["SO100_MW_MAX_ENVS"] = "0"
-    try:
+    (policy_forward + step, 4-wave step kernel), "one_wave" (the same with so100_step_fused: gpu_support.one_wave_step_kernel)"""
+    with one_wave_step_kernel(mode == "one_wave"):
         sim = make_sim(kind, n, flags=FREE, frame_skip=frame_skip, seed=4, max_episode_steps=2, envs_per_workgroup=epw)
-    finally:
-        if mode == "one_wave":
-            if old is None:
-                del os.environ["SO100_MW_MAX_ENVS"]
-            else:
-                os.environ["SO100_MW_MAX_ENVS"] = old
     assert sim.envs_per_workgroup == epw
     sim.set_policy(POLICIES[policy](sim.obs_dim, sim.device, kind, epw))
     sim.reset()

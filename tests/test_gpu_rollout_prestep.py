@@ -10,14 +10,12 @@ chunk.  The persistent rollout is compared row by row with stepwise policy_forwa
 one-wave kernel (SO100_MW_MAX_ENVS = 0), with the tolerances of test_gpu_parity.py::test_persistent_rollout_equals_stepwise; two
 identical launches, and one T = 3 launch against three T = 1 launches from the same start (prologue path against in-loop path), must
 agree bit for bit."""
-import os
-
 import pytest
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
-from gpu_support import make_sim, policy_tensors          # noqa: E402
+from gpu_support import make_sim, one_wave_step_kernel, policy_tensors   # noqa: E402
 from scenes import FREE                                   # noqa: E402
 
 T = 3
@@ -33,18 +31,9 @@ def _policy(obs_dim, device):
 
 def _run(kind, n, epw, frame_skip, mode):
     """mode: "persistent" (one so100_rollout launch of T steps), "chunks" (T launches of one step), "stepwise" (policy_forward + step,
-    4-wave step kernel), "one_wave" (the same with so100_step_fused: SO100_MW_MAX_ENVS = 0 is read when the handle is created)"""
-    old = os.environ.get("SO100_MW_MAX_ENVS")
-    if mode == "one_wave":
-        os.environ["SO100_MW_MAX_ENVS"] = "0"
-    try:
+    4-wave step kernel), "one_wave" (the same with so100_step_fused: gpu_support.one_wave_step_kernel)"""
+    with one_wave_step_kernel(mode == "one_wave"):
         sim = make_sim(kind, n, flags=FREE, frame_skip=frame_skip, seed=4, max_episode_steps=2, envs_per_workgroup=epw)
-    finally:
-        if mode == "one_wave":
-            if old is None:
-                del os.environ["SO100_MW_MAX_ENVS"]
-            else:
-                os.environ["SO100_MW_MAX_ENVS"] = old
     assert sim.envs_per_workgroup == epw
     sim.set_policy(_policy(sim.obs_dim, sim.device))
     sim.reset()

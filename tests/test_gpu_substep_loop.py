@@ -6,14 +6,12 @@ T = 3 steps.  The persistent rollout is compared row by row with the stepwise po
 step kernel (the same substep loop in another kernel) and through the one-wave so100_step_fused (physics_substeps: a loop of its own),
 selected by the library's dispatch override.  Tolerances: those of test_gpu_parity.py::test_persistent_rollout_equals_stepwise.
 Two identical launches must agree bit for bit."""
-import os
-
 import pytest
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
-from gpu_support import make_sim, policy_tensors          # noqa: E402
+from gpu_support import make_sim, one_wave_step_kernel, policy_tensors   # noqa: E402
 from scenes import ARM, FREE, REFP                        # noqa: E402
 
 T = 3
@@ -29,18 +27,9 @@ def _policy(obs_dim, device):
 
 def _run(flags, n, frame_skip, mode):
     """mode: "persistent" (one so100_rollout launch), "stepwise" (policy_forward + step, 4-wave step kernel), "one_wave" (the same
-    with so100_step_fused: SO100_MW_MAX_ENVS = 0 is read when the handle is created)"""
-    old = os.environ.get("SO100_MW_MAX_ENVS")
-    if mode == "one_wave":
-        os.environ["SO100_MW_MAX_ENVS"] = "0"
-    try:
+    with so100_step_fused: gpu_support.one_wave_step_kernel)"""
+    with one_wave_step_kernel(mode == "one_wave"):
         sim = make_sim(1, n, flags=flags, frame_skip=frame_skip, seed=4, max_episode_steps=2, envs_per_workgroup=32)
-    finally:
-        if mode == "one_wave":
-            if old is None:
-                del os.environ["SO100_MW_MAX_ENVS"]
-            else:
-                os.environ["SO100_MW_MAX_ENVS"] = old
     assert sim.envs_per_workgroup == 32
     sim.set_policy(_policy(sim.obs_dim, sim.device))
     sim.reset()
