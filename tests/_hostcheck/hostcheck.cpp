@@ -151,6 +151,16 @@ void hc_env_qpos(void* ev, double* qpos13, double* qvel12) {
     for (int i = 0; i < 3; i++) qpos13[6+i] = e->cube.pos[i];
     for (int i = 0; i < 4; i++) qpos13[9+i] = e->cube.quat[i];
 }
+// what so100_set_state does to the state rows (q, v, the cube's pose and velocity; the compensation qc is dropped with the old q), and,
+// where given, the commanded angles of the look-at kinds (the cmd0..5 rows of so100_set_field) and the reach kinds' stale cube position (cx_x..z)
+void hc_env_set_state(void* ev, const double* qpos13, const double* qvel12, const double* cmd6, const double* cx3) {
+    EnvState* e = (EnvState*)ev;
+    for (int i = 0; i < 6; i++) { e->q[i] = (float)qpos13[i]; e->v[i] = (float)qvel12[i]; e->cube.vel[i] = (float)qvel12[6+i]; e->qc[i] = 0.0f; }
+    for (int i = 0; i < 3; i++) e->cube.pos[i] = (float)qpos13[6+i];
+    for (int i = 0; i < 4; i++) e->cube.quat[i] = (float)qpos13[9+i];
+    if (cmd6) for (int i = 0; i < 6; i++) e->cmd[i] = (float)cmd6[i];
+    if (cx3) for (int i = 0; i < 3; i++) e->cx[i] = (float)cx3[i];
+}
 }
 
 // ---- the device's random draws on the host: Philox, the env's uniforms (draw8), the policy noise -----------------------------

@@ -34,6 +34,7 @@ HOSTCHECK = {
     "hc_env_step": (None, [_p, _i, _u, _i, _i, _i, _ull, _u] + [_p]*7),
     "hc_env_stats": (None, [_p, _p]),
     "hc_env_qpos": (None, [_p]*3),
+    "hc_env_set_state": (None, [_p]*5),
     "hc_philox4x32": (None, [_p]*3),
     "hc_draw8": (None, [_ull, _u, _u, _i, _p]),
     "hc_policy_noise": (None, [_ull, _u, _u, _p]),

@@ -228,18 +228,29 @@ def test_contact_kernels_agree_with_each_other(flags):
 
 
 @pytest.mark.parametrize("flags", [REFP, C5])
-def test_tail_workgroups_with_pad_contacts(flags):
-    """batch sizes that are not a multiple of the envs-per-workgroup count (16 here): env by env the results must be BIT-IDENTICAL
-    to the same envs inside a 256-env batch -- the contact wave's lane groups that belong to no env must not matter"""
-    for n in (1, 17, 130):
-        big = make_sim(1, 256, flags=flags, seed=5, max_episode_steps=25); small = make_sim(1, n, flags=flags, seed=5, max_episode_steps=25)
+@pytest.mark.parametrize("epw", [16, 32, 64])
+def test_tail_workgroups_with_pad_contacts(epw, flags):
+    """batch sizes that are not a multiple of the envs-per-workgroup count: env by env the results must be BIT-IDENTICAL to the same envs
+    inside a 256-env batch -- the contact wave's lane groups that belong to no env must not matter.  At 16 envs per workgroup (what the
+    library chooses by itself at these sizes: 4 lanes of the contact wave per env), and pinned to 32 and 64 (2 lanes, 1 lane), which it
+    chooses above 4096 and 8192 envs"""
+    if epw == 16:
+        auto = make_sim(1, 256, flags=flags, seed=5, max_episode_steps=25)
+        assert auto.envs_per_workgroup == 16
+        auto.close()
+    for n in (1, epw + 1, 130):
+        big = make_sim(1, 256, flags=flags, seed=5, max_episode_steps=25, envs_per_workgroup=epw)
+        small = make_sim(1, n, flags=flags, seed=5, max_episode_steps=25, envs_per_workgroup=epw)
+        assert big.envs_per_workgroup == epw and small.envs_per_workgroup == epw
         assert torch.equal(big.reset()[:n], small.reset())
         g = torch.Generator(device="cuda"); g.manual_seed(3); touched = 0
         for t in range(40):
             a = torch.rand(256, 6, device="cuda", generator=g)*2 - 1; a[:, 1] = 1.0      # shoulder down: the pads reach the floor within a few steps
             o1, r1, d1, _ = big.step(a); o2, r2, d2, _ = small.step(a[:n].contiguous())
             assert torch.equal(o1[:n], o2) and torch.equal(r1[:n], r2) and torch.equal(d1[:n], d2), (n, t)
-            touched = max(touched, int((small.get_field("contact_stat", dtype=torch.int32) & 255).max()))
+            cs1 = big.get_field("contact_stat", dtype=torch.int32); cs2 = small.get_field("contact_stat", dtype=torch.int32)
+            assert torch.equal(cs1[:n], cs2), (n, t)
+            touched = max(touched, int((cs2 & 255).max()))
         q1, v1 = big.get_state(); q2, v2 = small.get_state()
         assert torch.equal(q1[:, :n], q2) and torch.equal(v1[:, :n], v2) and touched >= 2
         big.close(); small.close()

@@ -147,23 +147,26 @@ def test_contact5_determinism_and_shard_invariance_4096():
     assert torch.isfinite(full).all() and coupled >= 8       # face-face manifolds on both sides of the cube
 
 
-def test_workgroup_balancing_leaves_every_result_bit_identical():
+@pytest.mark.parametrize("epw", [0, 32, 64])
+def test_workgroup_balancing_leaves_every_result_bit_identical(epw):
     """so100_rollout deals the envs that ended the previous chunk in pad contact out over the workgroups (csrc/so100_balance.hpp): which
     lane computes an env must not change a single bit of its results.  Half of the batch starts on the table, half parked in the air, so
-    the map differs from the identity; three chunks, TimeLimit resets inside."""
+    the map differs from the identity; three chunks, TimeLimit resets inside.  epw 0: what the library chooses for 1000 envs, 16 per
+    workgroup; pinned to 32 and 64 the map is dealt over 32 and 16 workgroups, as it is above 4096 and 8192 envs."""
     import os
     from so100_mujoco_rl_amd.vec_env import So100VecEnv
     from so100_mujoco_rl_amd.collector import RolloutCollector
-    n, T = 1000, 6                                           # 63 workgroups of 16 envs, the last one partially filled
+    n, T = 1000, 6                                           # 63 workgroups of 16 envs (32 of 32, 16 of 64), the last one partially filled
     qpos, qvel = _contact_rich_state(n, REFP, 3)
     qpos[::2, :6] = [0.0, -1.9, 1.6, 0.3, 1.5708, 0.1]; qvel[::2] = 0.0      # every other arm folded up 28 cm above the table
     outs = []
     for bal in ("1", "0"):
         os.environ["SO100_BALANCE"] = bal
         try:
-            env = So100VecEnv(1, n, flags=REFP, seed=8, max_episode_steps=11)
+            env = So100VecEnv(1, n, flags=REFP, seed=8, max_episode_steps=11, envs_per_workgroup=epw)
         finally:
             del os.environ["SO100_BALANCE"]
+        assert env.sim.envs_per_workgroup == (epw or 16)
         sd = RolloutCollector.random_policy_state(15, env.device, seed=5); sd["action_net.bias"][1] = 0.4
         col = RolloutCollector(env, sd, T=T, persistent=True, bootstrap_truncated=False)
         _start(env, col, qpos, qvel, 1)
