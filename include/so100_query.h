@@ -1,5 +1,6 @@
 /* so100_query.h -- model queries of libso100sim.so: what MuJoCo's users read from MjData or get from mj_jac, mj_fullM,
- * mj_inverse and mj_forward, for M independent problems at once, one GPU lane per problem (the forward query: four).
+ * mj_inverse and mj_forward, for M independent problems at once, one GPU lane per problem (the forward query: four), and where M states
+ * end up under M open-loop control sequences (the trajectory query).
  *
  * Additive to so100_sim.h (SO100_ABI_VERSION is unchanged) and under its conventions: extern "C"; `*_dev` pointers are DEVICE
  * pointers owned by the caller; 0 on success, a negative SO100_E_* code otherwise with the message in so100_last_error(); all
@@ -147,6 +148,59 @@ typedef struct {
 } so100_forward_io;
 
 int so100_query_forward(so100_sim* sim, const so100_forward_io* io, int32_t M, void* hip_stream);
+
+/* Open-loop trajectories: where M states end up under M control sequences of T control steps, nsub physics substeps each -- the physics of
+ * T calls of the step function without its task layer (no reward, TimeLimit, reset, RNG or curriculum motion of the cube), in one launch, with the state in
+ * registers from the first substep to the last.  The handle's simulation does not move.
+ *
+ * Start.  qpos [13][M] and qvel [12][M] in the state getter's layout; qvel alone NULL: zero.  An explicit state starts cold, as a freshly
+ * reset env: no warm start (friction-loss and limit forces, the cube's and the contact Newton's), no Kahan compensation, no force on the cube.
+ * Both NULL: the handle's state (M must be N) -- the query continues the handle's simulation: it also reads (and never writes) the
+ * warm-start rows, the Kahan rows and the anti-gravity bit of `bits`.  Within a call the warm starts carry from substep to substep and from
+ * step to step; the contact solve's active-set memory restarts at each control step, as it does at each env step.
+ *
+ * Controls.  ctrl [T][6][M].  SO100_TRAJ_TARGETS: the servo targets in radians, one set per control step.  SO100_TRAJ_ACTIONS: actions; the
+ * targets of step t are q(start of step t) + 0.075 a, each operation rounded (the reach envs' law).
+ * flags: SO100_F_*, decided per call (the handle's own flags are not consulted).  T in 1..4096, nsub in 1..1024, T * nsub <= 65 536.
+ *
+ * Outputs.  Row t is the state after control step t.  ee: the reference's end-effector point at that q (the fresh value the kinematics query
+ * gives for it, not the step kernels' stale pose).  ncon / dropped / sig / residual: the contact_stat & 255, contact_stat >> 8, contact_sig
+ * and solver_residual rows a step with these controls would leave: the most records in one substep, the contacts over the budget, the
+ * signature of the last substep's set, the largest solver residual.  bad_step: the first control step whose controls or resulting state
+ * are not finite (a non-finite start: 0), -1 if none; from that step on the problem is not advanced, its float rows (the final ones
+ * included) are NaN and its int rows 0.  The other problems never see it.  Every output is nullable; at least one is required.
+ *
+ * Argument errors, in this order: a null handle or io; M < 1 (or M != N where the handle's state is read); qvel_dev without qpos_dev; a null
+ * ctrl_dev; an unknown mode; T, nsub or T * nsub outside the limits; flag bits outside SO100_F_*; SO100_F_PADS_CUBE or SO100_F_LINKS_CUBE
+ * with SO100_F_CUBE_PINNED; an iteration count outside 1..64; no output. */
+#define SO100_TRAJ_TARGETS      0
+#define SO100_TRAJ_ACTIONS      1
+#define SO100_TRAJ_MAX_T        4096
+#define SO100_TRAJ_MAX_NSUB     1024
+#define SO100_TRAJ_MAX_SUBSTEPS 65536
+typedef struct {
+    const float* qpos_dev;             /* [13][M] or NULL (with qvel_dev NULL: the handle's state)                 */
+    const float* qvel_dev;             /* [12][M] or NULL                                                           */
+    const float* ctrl_dev;             /* [T][6][M] targets (radians) or actions, by mode                           */
+    int32_t      mode;                 /* SO100_TRAJ_TARGETS or SO100_TRAJ_ACTIONS                                  */
+    int32_t      T;                    /* control steps, 1..4096                                                    */
+    int32_t      nsub;                 /* substeps per control step, 1..1024; T * nsub <= 65 536                    */
+    uint32_t     flags;                /* SO100_F_*                                                                 */
+    int32_t      solver_iters;         /* 1..64                                                                     */
+    int32_t      contact_iters;        /* 1..64                                                                     */
+    float*       qpos_traj_dev;        /* [T][13][M]                                                                */
+    float*       qvel_traj_dev;        /* [T][12][M]                                                                */
+    float*       ee_traj_dev;          /* [T][3][M]                                                                 */
+    float*       qpos_final_dev;       /* [13][M] row T - 1 of qpos_traj                                            */
+    float*       qvel_final_dev;       /* [12][M] row T - 1 of qvel_traj                                            */
+    int32_t*     ncon_dev;             /* [T][M]                                                                    */
+    int32_t*     dropped_dev;          /* [T][M]                                                                    */
+    int32_t*     sig_dev;              /* [T][M]                                                                    */
+    float*       residual_dev;         /* [T][M]                                                                    */
+    int32_t*     bad_step_dev;         /* [M]                                                                       */
+} so100_trajectory_io;
+
+int so100_query_trajectory(so100_sim* sim, const so100_trajectory_io* io, int32_t M, void* hip_stream);
 
 #ifdef __cplusplus
 }

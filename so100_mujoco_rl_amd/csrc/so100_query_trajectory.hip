@@ -1,0 +1,143 @@
+// so100_query_trajectory.hip -- the trajectory query (gfx950) and its C ABI (include/so100_query.h: so100_query_trajectory); the arithmetic is
+// in so100_trajectory.hpp.  Like so100_query_forward.hip, not a translation unit of its own: so100_sim.hip includes it behind that file.
+//
+// Shape: so100_step_fused's.  One lane per problem, one wave per workgroup; the problem's physics rows stay in registers for all T x nsub
+// substeps, so HBM sees the start once, one control row per step and the rows the caller asked for.  A lane at or past M returns at once;
+// there is no LDS and no barrier, so no lane waits on another, and every loop has a fixed bound (T, nsub, the iteration counts).
+// Memory.  Every array is [k][M] (ctrl and the trajectories: [T][k][M]): lane i of a wave touches word i of a row, one coalesced segment
+// per wave and row.
+// FL >= 0: the flags are a compile-time constant (so100_step_fused's FL), for the sets without arm contact (8, 11 and F_NOPADS = 7); FL < 0: decided at
+// run time.
+#include "so100_trajectory.hpp"
+
+namespace so100 {
+
+struct TrajectoryArgs {
+    const float *qpos, *qvel; int ld;                        // ld: row length of qpos / qvel (M, or N for the handle's rows)
+    const float* state;                                      // the handle's state matrix where its state is read (warm starts, Kahan rows, bits), else null
+    const float* ctrl;
+    int mode, T, nsub; unsigned flags; int solver_iters, contact_iters;
+    float *qpos_traj, *qvel_traj, *ee_traj, *qpos_final, *qvel_final;
+    int32_t *ncon, *dropped, *sig; float* residual; int32_t* bad_step;
+};
+
+template <int FL>
+__global__ void __launch_bounds__(WG) so100_query_trajectory_k(TrajectoryArgs a, int M) {
+    const size_t i = (size_t)blockIdx.x*WG + threadIdx.x;
+    if (i >= (size_t)M) return;
+    const unsigned flags = FL >= 0 ? (unsigned)FL : a.flags;
+    const size_t m = (size_t)M, ld = (size_t)a.ld;
+    float qpos[13], qvel[12];
+#pragma unroll
+    for (int k = 0; k < 13; k++) qpos[k] = a.qpos[k*ld + i];
+#pragma unroll
+    for (int k = 0; k < 12; k++) qvel[k] = a.qvel ? a.qvel[k*ld + i] : 0.0f;
+    TrajState<float> s;
+    trajectory_cold(qpos, qvel, s);
+    if (a.state) {                                           // the handle's simulation goes on: its warm starts, Kahan rows and anti-gravity bit
+        const float* S = a.state;
+#pragma unroll
+        for (int k = 0; k < 6; k++) {
+            s.ff[k] = S[(SF_ff0 + k)*ld + i]; s.fl[k] = S[(SF_fl0 + k)*ld + i]; s.cube.warm[k] = S[(SF_cw0 + k)*ld + i]; s.qc[k] = S[(SF_qc0 + k)*ld + i];
+            if ((flags & F_ANY_CONTACT) != 0u) s.aw[k] = S[(SF_aw0 + k)*ld + i];
+        }
+        if (__float_as_int(S[SF_bits*ld + i]) & B_ANTIGRAV) s.lift = (float)(so100g::CUBE_MASS*so100g::GRAVITY);
+    }
+    const float nan = __int_as_float(0x7FC00000);
+    const int bad = trajectory_rollout<float>(s, a.T, a.mode, flags, a.solver_iters, a.contact_iters, a.nsub,
+        [&](int t, float c[6]) {
+#pragma unroll
+            for (int k = 0; k < 6; k++) c[k] = a.ctrl[((size_t)t*6 + k)*m + i];
+        },
+        [&](int t, bool ok, const TrajState<float>& st, const TrajStep<float>& o) {
+            const size_t row = (size_t)t;
+            if (a.qpos_traj || a.qvel_traj) {
+                float qp[13], qv[12];
+                trajectory_qpos_qvel(st, qp, qv);
+                if (a.qpos_traj) {
+#pragma unroll
+                    for (int k = 0; k < 13; k++) a.qpos_traj[(row*13 + k)*m + i] = ok ? qp[k] : nan;
+                }
+                if (a.qvel_traj) {
+#pragma unroll
+                    for (int k = 0; k < 12; k++) a.qvel_traj[(row*12 + k)*m + i] = ok ? qv[k] : nan;
+                }
+            }
+            if (a.ee_traj) {
+                float ee[3] = { nan, nan, nan };
+                if (ok) trajectory_ee(st.q, ee);
+#pragma unroll
+                for (int k = 0; k < 3; k++) a.ee_traj[(row*3 + k)*m + i] = ee[k];
+            }
+            if (a.ncon) a.ncon[row*m + i] = ok ? (o.cstat & 255) : 0;
+            if (a.dropped) a.dropped[row*m + i] = ok ? (o.cstat >> 8) : 0;
+            if (a.sig) a.sig[row*m + i] = ok ? o.csig : 0;
+            if (a.residual) a.residual[row*m + i] = ok ? o.res : nan;
+        });
+    if (a.qpos_final || a.qvel_final) {
+        float qp[13], qv[12];
+        trajectory_qpos_qvel(s, qp, qv);
+        if (a.qpos_final) {
+#pragma unroll
+            for (int k = 0; k < 13; k++) a.qpos_final[k*m + i] = bad < 0 ? qp[k] : nan;
+        }
+        if (a.qvel_final) {
+#pragma unroll
+            for (int k = 0; k < 12; k++) a.qvel_final[k*m + i] = bad < 0 ? qv[k] : nan;
+        }
+    }
+    if (a.bad_step) a.bad_step[i] = bad;
+}
+
+}  // namespace so100
+
+static_assert(SO100_TRAJ_TARGETS == so100::TRAJ_TARGETS && SO100_TRAJ_ACTIONS == so100::TRAJ_ACTIONS, "the header names the modes");
+static_assert(SO100_TRAJ_MAX_T == so100::TRAJ_MAX_T && SO100_TRAJ_MAX_NSUB == so100::TRAJ_MAX_NSUB && SO100_TRAJ_MAX_SUBSTEPS == so100::TRAJ_MAX_SUBSTEPS,
+              "the header names the limits");
+static_assert(so100::TRAJ_ACTION_SCALE == so100::JOINT_STEP_SCALE, "actions mode is the reach envs' control law");
+static_assert(SF_ff0 + 5 == SF_ff5 && SF_fl0 + 5 == SF_fl5 && SF_cw0 + 5 == SF_cw5 && SF_qc0 + 5 == SF_qc5 && SF_aw0 + 5 == SF_aw5, "six consecutive rows each");
+
+extern "C" {
+
+int so100_query_trajectory(so100_sim* sim, const so100_trajectory_io* io, int32_t M, void* stream) {
+    using namespace so100;
+    const char* const fn = "so100_query_trajectory";
+    if (!sim || !io) return fail(SO100_E_INVALID, "so100_query_trajectory: null argument");
+    const int n = sim->prm.n;
+    if (M < 1) return fail(SO100_E_INVALID, "%s: M must be >= 1, got %ld", fn, (long)M);
+    if (!io->qpos_dev && !io->qvel_dev && M != n)
+        return fail(SO100_E_INVALID, "%s: M must be the handle's N (%ld) where its state is read, got %ld", fn, (long)n, (long)M);
+    if (!io->qpos_dev && io->qvel_dev) return fail(SO100_E_INVALID, "%s: qvel_dev given without qpos_dev", fn);
+    if (!io->ctrl_dev) return fail(SO100_E_INVALID, "%s: ctrl_dev is required", fn);
+    if (io->mode != SO100_TRAJ_TARGETS && io->mode != SO100_TRAJ_ACTIONS) return fail(SO100_E_INVALID, "%s: unknown mode %ld", fn, (long)io->mode);
+    if (io->T < 1 || io->T > SO100_TRAJ_MAX_T || io->nsub < 1 || io->nsub > SO100_TRAJ_MAX_NSUB || (long)io->T*(long)io->nsub > SO100_TRAJ_MAX_SUBSTEPS)
+        return fail(SO100_E_INVALID, "%s: T must be in 1..%d, nsub in 1..%d and T * nsub <= %d, got T = %ld, nsub = %ld", fn, SO100_TRAJ_MAX_T, SO100_TRAJ_MAX_NSUB,
+                    SO100_TRAJ_MAX_SUBSTEPS, (long)io->T, (long)io->nsub);
+    if (io->flags & ~(SO100_F_FRICTIONLOSS | SO100_F_LIMITS | SO100_F_FLOOR | SO100_F_CUBE_PINNED | SO100_F_PADS_FLOOR | SO100_F_PADS_CUBE | SO100_F_LINKS_FLOOR | SO100_F_LINKS_CUBE))
+        return fail(SO100_E_INVALID, "%s: unknown flag bits", fn);
+    if ((io->flags & (SO100_F_PADS_CUBE | SO100_F_LINKS_CUBE)) && (io->flags & SO100_F_CUBE_PINNED))
+        return fail(SO100_E_INVALID, "%s: SO100_F_PADS_CUBE / SO100_F_LINKS_CUBE need a dynamic cube (not SO100_F_CUBE_PINNED)", fn);
+    if (io->solver_iters < 1 || io->solver_iters > 64) return fail(SO100_E_INVALID, "%s: solver_iters must be in 1..64, got %ld", fn, (long)io->solver_iters);
+    if (io->contact_iters < 1 || io->contact_iters > 64) return fail(SO100_E_INVALID, "%s: contact_iters must be in 1..64, got %ld", fn, (long)io->contact_iters);
+    if (!io->qpos_traj_dev && !io->qvel_traj_dev && !io->ee_traj_dev && !io->qpos_final_dev && !io->qvel_final_dev && !io->ncon_dev && !io->dropped_dev &&
+        !io->sig_dev && !io->residual_dev && !io->bad_step_dev)
+        return fail(SO100_E_INVALID, "%s: no output requested", fn);
+    TrajectoryArgs a{};
+    if (io->qpos_dev) { a.qpos = io->qpos_dev; a.qvel = io->qvel_dev; a.ld = M; a.state = nullptr; }
+    else { a.qpos = sim->state + (size_t)SF_QPOS0*(size_t)n; a.qvel = sim->state + (size_t)SF_QVEL0*(size_t)n; a.ld = n; a.state = sim->state; }
+    a.ctrl = io->ctrl_dev; a.mode = io->mode; a.T = io->T; a.nsub = io->nsub; a.flags = io->flags; a.solver_iters = io->solver_iters; a.contact_iters = io->contact_iters;
+    a.qpos_traj = io->qpos_traj_dev; a.qvel_traj = io->qvel_traj_dev; a.ee_traj = io->ee_traj_dev; a.qpos_final = io->qpos_final_dev; a.qvel_final = io->qvel_final_dev;
+    a.ncon = io->ncon_dev; a.dropped = io->dropped_dev; a.sig = io->sig_dev; a.residual = io->residual_dev; a.bad_step = io->bad_step_dev;
+    SO100_ON_DEVICE(sim->cfg.device, "so100_query_trajectory");
+    const dim3 grid((unsigned)(((size_t)M + WG - 1)/WG)), block(WG);
+    constexpr unsigned FREE = SO100_F_CUBE_PINNED, ROWS = SO100_F_FRICTIONLOSS | SO100_F_LIMITS | SO100_F_CUBE_PINNED,
+                       NOPADS = SO100_F_FRICTIONLOSS | SO100_F_LIMITS | SO100_F_FLOOR;
+    if (io->flags == FREE)        hipLaunchKernelGGL((so100_query_trajectory_k<(int)FREE>), grid, block, 0, (hipStream_t)stream, a, M);
+    else if (io->flags == ROWS)   hipLaunchKernelGGL((so100_query_trajectory_k<(int)ROWS>), grid, block, 0, (hipStream_t)stream, a, M);
+    else if (io->flags == NOPADS) hipLaunchKernelGGL((so100_query_trajectory_k<(int)NOPADS>), grid, block, 0, (hipStream_t)stream, a, M);
+    else                          hipLaunchKernelGGL((so100_query_trajectory_k<-1>), grid, block, 0, (hipStream_t)stream, a, M);
+    HIP_TRY(hipGetLastError(), SO100_E_LAUNCH);
+    return 0;
+}
+
+}  // extern "C"

@@ -303,3 +303,4 @@ int so100_set_field(so100_sim* s, int32_t field, const void* in_dev, void* strea
 // handle defined above, and the list of the product's objects stays what the side-build recipe names
 #include "so100_query.hip"
 #include "so100_query_forward.hip"
+#include "so100_query_trajectory.hip"

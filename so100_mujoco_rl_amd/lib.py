@@ -173,9 +173,19 @@ class ForwardIO(C.Structure):
                                           "con_frame_dev", "con_dist_dev", "con_force_dev", "pad_force_dev", "residual_dev")]
 
 
-QUERY_EXPORTS = ["so100_query_kinematics", "so100_query_jacobian", "so100_query_dynamics", "so100_query_ik", "so100_query_forward"]
+class TrajectoryIO(C.Structure):
+    _fields_ = [("qpos_dev", C.c_void_p), ("qvel_dev", C.c_void_p), ("ctrl_dev", C.c_void_p), ("mode", C.c_int32), ("T", C.c_int32), ("nsub", C.c_int32),
+                ("flags", C.c_uint32), ("solver_iters", C.c_int32), ("contact_iters", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("qpos_traj_dev", "qvel_traj_dev", "ee_traj_dev", "qpos_final_dev", "qvel_final_dev", "ncon_dev", "dropped_dev",
+                                          "sig_dev", "residual_dev", "bad_step_dev")]
+
+
+QUERY_EXPORTS = ["so100_query_kinematics", "so100_query_jacobian", "so100_query_dynamics", "so100_query_ik", "so100_query_forward",
+                 "so100_query_trajectory"]
 QUERY_IO = {"so100_query_kinematics": KinematicsIO, "so100_query_jacobian": JacobianIO, "so100_query_dynamics": DynamicsIO, "so100_query_ik": IkIO,
-            "so100_query_forward": ForwardIO}
+            "so100_query_forward": ForwardIO, "so100_query_trajectory": TrajectoryIO}
+TRAJ_MODES = {"targets": 0, "actions": 1}                      # SO100_TRAJ_TARGETS / SO100_TRAJ_ACTIONS
+TRAJ_MAX_T, TRAJ_MAX_NSUB, TRAJ_MAX_SUBSTEPS = 4096, 1024, 65536    # SO100_TRAJ_MAX_*
 EE_LINK = 4                                                    # SO100_EE_LINK: the reference's end-effector point sits on Fixed_Jaw
 IK_ITERS, IK_DAMPING, IK_TOL, IK_MAX_STEP = 64, 0.02, 1e-4, 0.3     # SO100_IK_*
 FWD_MAXCON, FWD_SOLVER_ITERS, FWD_CONTACT_ITERS = 20, 64, 64        # SO100_FWD_*
@@ -650,6 +660,36 @@ class So100Sim(_Handle):
         return {"qacc": qacc.t(), "qfrc_constraint": qfrc.t(), "ncon": ncon, "dropped": drop, "residual": res, "pad_force": pf.t(),
                 "contacts": {"kind": kind.t(), "feat": feat.t(), "pos": pos.permute(2, 0, 1), "frame": frame.permute(2, 0, 1).unflatten(2, (3, 3)),
                              "dist": dist.t(), "force": force.permute(2, 0, 1)}}
+
+    def trajectory(self, ctrl, qpos=None, qvel=None, mode="targets", nsub=None, flags=None, solver_iters=None, contact_iters=None):
+        """Where M states end up under M open-loop control sequences, in one launch and without moving the simulation: ctrl [T, M, 6] holds, per
+        control step, the servo targets in radians (mode "targets") or actions (mode "actions": targets = q at the start of the step + 0.075 a,
+        the reach envs' law).  qpos [M, 13] and qvel [M, 12] as get_state() lays them out: an explicit state starts cold like a freshly reset env
+        (qvel alone None: zero); both None: the handle's state with its warm starts, M = N -- the prediction of what step() would do next.
+        nsub (substeps per control step), flags and the iteration counts default to the handle's own.  No task layer: no reward, TimeLimit,
+        reset or RNG.  Returns views, row t = the state after control step t: "qpos" [T, M, 13], "qvel" [T, M, 12], "ee" [T, M, 3] (the
+        end-effector point at that q), "ncon", "dropped", "sig" [T, M] int32 and "residual" [T, M] (what the contact_stat, contact_sig and
+        solver_residual rows would hold after such a step) and "bad_step" [M] int32: the first step whose controls or resulting state are not
+        finite (-1: none); from there on that problem's float rows are NaN and its int rows 0."""
+        if mode not in TRAJ_MODES:
+            raise So100Error(f"trajectory: mode must be one of {sorted(TRAJ_MODES)}, got {mode!r}")
+        ctrl = torch.as_tensor(ctrl, dtype=torch.float32, device=self.device)
+        if ctrl.dim() != 3 or ctrl.shape[2] != 6 or ctrl.shape[0] < 1:
+            raise So100Error(f"ctrl: want a [T, M, 6] tensor, got {tuple(ctrl.shape)}")
+        T = ctrl.shape[0]
+        us = ctrl.permute(0, 2, 1).contiguous()
+        qs, vs = self._soa(qpos, 13, "qpos"), self._soa(qvel, 12, "qvel"); M = self._problems(qs, vs, us[0])
+        i32 = dict(dtype=torch.int32)
+        qt, vt, et = self._out(M, T, 13), self._out(M, T, 12), self._out(M, T, 3)
+        ncon, drop, sig, res, bad = self._out(M, T, **i32), self._out(M, T, **i32), self._out(M, T, **i32), self._out(M, T), self._out(M, **i32)
+        c = self.cfg
+        io = TrajectoryIO(qs.data_ptr() if qs is not None else None, vs.data_ptr() if vs is not None else None, us.data_ptr(), TRAJ_MODES[mode], T,
+                          c.frame_skip if nsub is None else nsub, c.flags if flags is None else flags,
+                          c.solver_iters if solver_iters is None else solver_iters, c.contact_iters if contact_iters is None else contact_iters,
+                          qt.data_ptr(), vt.data_ptr(), et.data_ptr(), None, None, ncon.data_ptr(), drop.data_ptr(), sig.data_ptr(), res.data_ptr(), bad.data_ptr())
+        _check(self.L.so100_query_trajectory(self.h, C.byref(io), M, self._stream()), "so100_query_trajectory")
+        return {"qpos": qt.permute(0, 2, 1), "qvel": vt.permute(0, 2, 1), "ee": et.permute(0, 2, 1), "ncon": ncon, "dropped": drop, "sig": sig,
+                "residual": res, "bad_step": bad}
 
 
 def learner_layout(obs_dim):

@@ -3,6 +3,7 @@
 
     python tools/kbench_query.py [--out profiles/query_kbench.json] [--commit LABEL] [--rounds 5]
     python tools/kbench_query.py --forward [--out profiles/forward_kbench.json] [--commit LABEL] [--rounds 5]
+    python tools/kbench_query.py --trajectory [--out profiles/trajectory_kbench.json] [--commit LABEL] [--rounds 5]
 
 Cases, at M = 4096 and M = 1 048 576 problems: kinematics with every output and with the end-effector point alone, the Jacobian (jacp and
 jacr), the dynamics (M, bias and tau) and the IK.  Poses are uniform over the joint ranges; the IK problems are the 400 of the tests' recipe
@@ -17,7 +18,10 @@ pad/floor states of the tests' recipe (tests/forward_support.py: family "floor")
 the same flags and iteration counts, its state set to the same states before every call.  The two are timed alike (timed_pairs: an event pair
 round each single call, the set_state copies outside the span, the calls enqueued without waiting); the forward query's back-to-back time,
 one event pair round all calls of a round, is recorded as well:
-the existing code doing the same solve from the warm-start rows of its state, plus the integration and the task layer."""
+the existing code doing the same solve from the warm-start rows of its state, plus the integration and the task layer.
+
+--trajectory times the trajectory query (so100_query_trajectory) at M = 4096 and M = 262 144, T = 16 control steps of 16 substeps, per flag set
+beside the 16 so100_step calls it predicts (trajectory_main)."""
 import argparse
 import ctypes as C
 import json
@@ -132,15 +136,101 @@ def forward_main(a):
         fh.write("\n")
 
 
+TRAJECTORY_SIZES = [(4096, 20), (262144, 3)]     # (M, timed units per round)
+TRAJECTORY_T, TRAJECTORY_NSUB = 16, 16
+# (name, the handle's flags, the query's flags): the contact-disabled sets with a compile-time form of the kernel, each beside a query that simulates
+# the same thing through the run-time-flags form (SO100_F_FLOOR acts on the cube alone, which SO100_F_CUBE_PINNED holds still; a handle refuses the
+# pair, a query's flags are its own), then the sets with a dynamic cube
+_FREE, _ROWS = lib.F_CUBE_PINNED, lib.F_FRICTIONLOSS | lib.F_LIMITS | lib.F_CUBE_PINNED
+TRAJECTORY_FLAGS = [("free", _FREE, _FREE), ("free_runtime_form", _FREE, _FREE | lib.F_FLOOR),
+                    ("contact_disabled", _ROWS, _ROWS), ("contact_disabled_runtime_form", _ROWS, _ROWS | lib.F_FLOOR),
+                    ("nopads", lib.F_NOPADS, lib.F_NOPADS), ("reference", lib.F_REFERENCE, lib.F_REFERENCE)]
+# (F_NOPADS has a compile-time form too; no other flag set simulates the same thing, so its run-time-form figure is the one measured before the form was added: DESIGN.md 13.4)
+
+
+def trajectory_main(a):
+    """One so100_query_trajectory call (the handle's state, mode = actions, every output) against the T so100_step calls it predicts, on a handle
+    of M Env01 envs after a reset and a few random steps, with the same flags and iteration counts.  Both are timed with forward_main's
+    per-call protocol: the state put back outside the span, an event pair round each single call, enqueued without waiting; a step figure
+    is the sum of its T spans."""
+    T, nsub = TRAJECTORY_T, TRAJECTORY_NSUB
+    doc = {"what": f"HIP-event time of one so100_query_trajectory call (T = {T}, nsub = {nsub}, the handle's state, actions, every output) and of the "
+                   f"{T} so100_step calls (frame_skip = {nsub}) it predicts, the shipped (2, 20) iterations; an event pair round each single call, "
+                   "medians of alternated rounds", "commit": a.commit, "card": torch.cuda.get_device_name(0), "rounds": a.rounds, "cases": []}
+    for M, reps in TRAJECTORY_SIZES:
+        for name, flags, qflags in TRAJECTORY_FLAGS:
+            sim = lib.So100Sim(lib.ENV01, M, device="cuda:0", flags=flags, frame_skip=nsub, max_episode_steps=0, seed=0)
+            dev, L, st = sim.device, sim.L, sim._stream()
+            sim.reset()
+            g = torch.Generator(device=dev).manual_seed(0)
+            for _ in range(3):
+                sim.step(torch.rand(M, 6, generator=g, device=dev)*2 - 1)
+            qs, vs = sim.get_state()
+            act = torch.rand(T, M, 6, generator=g, device=dev)*2 - 1
+            us_ = act.permute(0, 2, 1).contiguous()
+            out = torch.empty(T*(13 + 12 + 3 + 1) + 25, M, dtype=torch.float32, device=dev)
+            ints = torch.empty(3*T + 1, M, dtype=torch.int32, device=dev)
+            p, pi = (lambda r: out[r].data_ptr()), (lambda r: ints[r].data_ptr())
+            io = lib.TrajectoryIO(None, None, us_.data_ptr(), lib.TRAJ_MODES["actions"], T, nsub, qflags, sim.cfg.solver_iters, sim.cfg.contact_iters,
+                                  p(0), p(13*T), p(25*T), p(29*T), p(29*T + 13), pi(0), pi(T), pi(2*T), p(28*T), pi(3*T))
+
+            def pair(call):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(); call(); e1.record()
+                return e0, e1
+
+            def one_query():
+                rc = L.so100_query_trajectory(sim.h, C.byref(io), M, st)
+                assert rc == 0, L.so100_last_error()
+
+            def timed_query(n):
+                pairs = []
+                for _ in range(n):
+                    sim.set_state(qs, vs)
+                    pairs.append(pair(one_query))
+                torch.cuda.synchronize()
+                return sum(e0.elapsed_time(e1) for e0, e1 in pairs)*1e3/n
+
+            def timed_steps(n):
+                pairs = []
+                for _ in range(n):
+                    sim.set_state(qs, vs)
+                    pairs += [pair(lambda t=t: sim.step(act[t])) for t in range(T)]
+                torch.cuda.synchronize()
+                return sum(e0.elapsed_time(e1) for e0, e1 in pairs)*1e3/n
+
+            timed_query(1); timed_steps(1)
+            tq, ts = [], []
+            for _ in range(a.rounds):
+                tq.append(timed_query(reps)); ts.append(timed_steps(reps))
+            sim.set_state(qs, vs); one_query(); torch.cuda.synchronize()
+            ncon = ints[0:T].float()
+            mq, ms = statistics.median(tq), statistics.median(ts)
+            case = {"case": name, "M": M, "flags": int(flags), "query_flags": int(qflags), "T": T, "nsub": nsub, "trajectory_us_per_call": round(mq, 1), "steps_us_per_T_calls": round(ms, 1),
+                    "trajectory_over_steps": round(mq/ms, 3), "trajectory_rounds_us": [round(x, 1) for x in tq], "steps_rounds_us": [round(x, 1) for x in ts],
+                    "units_per_round": reps, "problem_substeps_per_s": round(M*T*nsub/(mq*1e-6), 1),
+                    "share_of_steps_in_contact": round((ncon > 0).float().mean().item(), 4), "bad_problems": int((ints[3*T] >= 0).sum().item())}
+            doc["cases"].append(case)
+            print(json.dumps(case), flush=True)
+            sim.close()
+            del out, ints
+    with open(a.out, "w") as fh:
+        json.dump(doc, fh, indent=1)
+        fh.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None); ap.add_argument("--commit", default="unknown")
     ap.add_argument("--rounds", type=int, default=5); ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--forward", action="store_true", help="time the forward-dynamics query against so100_step (profiles/forward_kbench.json)")
+    ap.add_argument("--trajectory", action="store_true", help="time the trajectory query against the so100_step calls it predicts (profiles/trajectory_kbench.json)")
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "forward_kbench.json" if a.forward else "query_kbench.json")
+        a.out = os.path.join(ROOT, "profiles", "trajectory_kbench.json" if a.trajectory else "forward_kbench.json" if a.forward else "query_kbench.json")
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    if a.trajectory:
+        return trajectory_main(a)
     if a.forward:
         return forward_main(a)
     sim = lib.So100Sim(lib.ENV01, 64, device="cuda:0", flags=lib.F_REFERENCE, seed=0)
