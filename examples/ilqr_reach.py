@@ -1,0 +1,122 @@
+#!/usr/bin/env python3
+"""A gradient-based planner (receding-horizon iLQR) for Env01 built on the derivatives query (needs a GPU): every step each env rolls its
+current plan of `horizon` actions out with So100Sim.trajectory, So100Sim.derivatives linearises all N x horizon (state, action) pairs of
+that rollout in one launch (the arm block of the tangent state: rows and columns 0..5 and 12..17 of A, rows of B), the cost |ee - cube|^2
+summed over the horizon gets its Gauss-Newton terms from So100Sim.jacobian, a batched Riccati pass in torch on the device improves the
+plan, and its first action is executed through step().  Printed next to the zero-action baseline, like examples/mppi_reach.py.
+
+    python examples/ilqr_reach.py [--envs 8] [--horizon 8] [--steps 100] [--iterations 2]
+"""
+import argparse
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from so100_mujoco_rl_amd.lib import ENV01, F_CUBE_PINNED, So100Sim   # noqa: E402
+
+ARM = list(range(0, 6)) + list(range(12, 18))                  # the arm's block of the tangent state: dq 0..5, v 12..17
+
+
+class Ilqr:
+    """policy(sim, obs) -> action [N, 6].  plan [N, horizon, 6] is the current action sequence, shifted by one step after every call;
+    control_cost: the weight of |a|^2 beside |ee - cube|^2 (metres squared); damping: added to Q_uu (Levenberg-Marquardt)."""
+    def __init__(self, horizon=8, iterations=2, control_cost=1e-5, damping=1e-5):
+        self.H, self.iterations, self.control_cost, self.damping = horizon, iterations, control_cost, damping
+        self.plan = None
+
+    def improve(self, sim, q0, v0):
+        N, H, dev = sim.n, self.H, sim.device
+        U = self.plan
+        roll = sim.trajectory(U.permute(1, 0, 2).contiguous(), q0, v0, mode="actions")           # row t: the state after action t
+        Xq = torch.cat([q0[None], roll["qpos"][:-1]]); Xv = torch.cat([v0[None], roll["qvel"][:-1]])   # [H, N, .]: the state action t starts from
+        d = sim.derivatives(U.permute(1, 0, 2).reshape(H*N, 6), Xq.reshape(H*N, 13), Xv.reshape(H*N, 12), mode="actions")
+        if bool(d["bad"].any()) or bool((roll["bad_step"] >= 0).any()):
+            return
+        A = d["A"][:, ARM][:, :, ARM].reshape(H, N, 12, 12)
+        B = d["B"][:, ARM].reshape(H, N, 12, 6).clone()
+        B[..., 5] = 0.0                                              # the jaw does not move the end-effector point
+        # Gauss-Newton terms of |ee(q) - cube|^2 at the states after each action
+        qn = roll["qpos"]
+        J = sim.jacobian(qn[..., :6].reshape(H*N, 6))["jacp"].reshape(H, N, 3, 6)
+        r = roll["ee"] - qn[..., 6:9]
+        lx = torch.zeros(H, N, 12, device=dev); lxx = torch.zeros(H, N, 12, 12, device=dev)
+        lx[..., :6] = 2.0*torch.einsum("hnij,hni->hnj", J, r)
+        lxx[..., :6, :6] = 2.0*torch.einsum("hnij,hnik->hnjk", J, J)
+        eye = torch.eye(6, device=dev)
+        # the backward pass: V is the cost-to-go from the state after action t
+        Vx, Vxx = lx[H - 1], lxx[H - 1]
+        k = torch.zeros(H, N, 6, device=dev); K = torch.zeros(H, N, 6, 12, device=dev)
+        for t in range(H - 1, -1, -1):
+            At, Bt = A[t], B[t]
+            Qx = torch.einsum("nij,ni->nj", At, Vx)
+            Qu = 2.0*self.control_cost*U[:, t] + torch.einsum("nij,ni->nj", Bt, Vx)
+            VA = Vxx @ At
+            Qxx = At.transpose(1, 2) @ VA
+            Qux = Bt.transpose(1, 2) @ VA
+            Quu = Bt.transpose(1, 2) @ Vxx @ Bt + (2.0*self.control_cost + self.damping)*eye
+            k[t] = -torch.linalg.solve(Quu, Qu[..., None])[..., 0]
+            K[t] = -torch.linalg.solve(Quu, Qux)
+            Vx = Qx + torch.einsum("nij,ni->nj", K[t], Qu + torch.einsum("nij,nj->ni", Quu, k[t])) + torch.einsum("nij,ni->nj", Qux, k[t])
+            Vxx = Qxx + K[t].transpose(1, 2) @ Quu @ K[t] + K[t].transpose(1, 2) @ Qux + Qux.transpose(1, 2) @ K[t]
+            Vxx = 0.5*(Vxx + Vxx.transpose(1, 2))
+            if t > 0:
+                Vx = Vx + lx[t - 1]; Vxx = Vxx + lxx[t - 1]
+        # the forward pass on the linearisation, the actions kept in [-1, 1]
+        dx = torch.zeros(N, 12, device=dev)
+        new = U.clone()
+        for t in range(H):
+            new[:, t] = (U[:, t] + k[t] + torch.einsum("nij,nj->ni", K[t], dx)).clamp(-1.0, 1.0)
+            new[:, t, 5] = 0.0
+            dx = torch.einsum("nij,nj->ni", A[t], dx) + torch.einsum("nij,nj->ni", B[t], new[:, t] - U[:, t])
+        self.plan = new
+
+    def __call__(self, sim, obs):
+        if self.plan is None:
+            self.plan = torch.zeros(sim.n, self.H, 6, device=sim.device)
+        qpos, qvel = sim.get_state()                                 # [13, N], [12, N]
+        q0, v0 = qpos.t().contiguous(), qvel.t().contiguous()
+        for _ in range(self.iterations):
+            self.improve(sim, q0, v0)
+        act = self.plan[:, 0].contiguous()
+        self.plan = torch.cat([self.plan[:, 1:], torch.zeros(sim.n, 1, 6, device=sim.device)], dim=1)
+        return act
+
+
+def distance(sim):
+    """mean |cube - ee| from the handle's state: the cube's position (rows 6..8 of qpos) against the end-effector point of the queries"""
+    cube = sim.get_state()[0][6:9].t()
+    return (cube - sim.kinematics()["ee"]).norm(dim=1).mean().item()
+
+
+def run(sim, steps, policy):
+    """(mean |cube - ee| at reset, the same after `steps` steps, mean reward per step) of `policy(sim, obs) -> action`, both distances
+    read from the state"""
+    obs = sim.reset()
+    d0 = distance(sim)
+    total = 0.0
+    for _ in range(steps):
+        obs, rew, _, _ = sim.step(policy(sim, obs))
+        total += rew.mean().item()
+    return d0, distance(sim), total/steps
+
+
+def zero_action(sim, obs):
+    return torch.zeros(sim.n, 6, device=sim.device)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, default=8); ap.add_argument("--horizon", type=int, default=8)
+    ap.add_argument("--steps", type=int, default=100); ap.add_argument("--iterations", type=int, default=2)
+    args = ap.parse_args()
+    for name, policy in (("iLQR", Ilqr(args.horizon, args.iterations)), ("zero action", zero_action)):
+        sim = So100Sim(ENV01, args.envs, flags=F_CUBE_PINNED, max_episode_steps=0, seed=0)
+        d0, d1, r = run(sim, args.steps, policy)
+        print(f"{name:12s} mean |cube - ee|: {d0:.4f} m at reset -> {d1:.4f} m after {args.steps} steps; reward/step {r:+.4f}")
+        sim.close()
+
+
+if __name__ == "__main__":
+    main()

@@ -1,6 +1,7 @@
 /* so100_query.h -- model queries of libso100sim.so: what MuJoCo's users read from MjData or get from mj_jac, mj_fullM,
  * mj_inverse and mj_forward, for M independent problems at once, one GPU lane per problem (the forward query: four), and where M states
- * end up under M open-loop control sequences (the trajectory query).
+ * end up under M open-loop control sequences (the trajectory query), and the finite-difference linearisation of such a control step, one GPU
+ * wave per problem (the derivatives query).
  *
  * Additive to so100_sim.h (SO100_ABI_VERSION is unchanged) and under its conventions: extern "C"; `*_dev` pointers are DEVICE
  * pointers owned by the caller; 0 on success, a negative SO100_E_* code otherwise with the message in so100_last_error(); all
@@ -201,6 +202,53 @@ typedef struct {
 } so100_trajectory_io;
 
 int so100_query_trajectory(so100_sim* sim, const so100_trajectory_io* io, int32_t M, void* hip_stream);
+
+/* Derivatives of one control step: for each of M (state, control) pairs the matrices A = dx'/dx [24][24] and B = dx'/du [24][6] of the
+ * step the trajectory query takes with T = 1 -- MuJoCo's mjd_transitionFD.  The handle's simulation does not move.
+ *
+ * The result is a CENTRED SECANT over +-eps, like mjd_transitionFD with centred differences: column c is (x'(+eps e_c) - x'(-eps e_c))/(2 eps),
+ * from 60 perturbed evaluations of the step and the unperturbed one, all in one wave of the GPU per problem.  With friction loss, joint limits
+ * or contacts the step is not smooth and the result depends on eps: measured on the CPU under SO100_F_FRICTIONLOSS | SO100_F_LIMITS, the
+ * fp64 oracle's own secants at 2^-10 and at 1e-6 differ by up to 0.17 on entries of size 8.  Forward (one-sided) differences are not offered.
+ *
+ * Tangent state.  x = (dq [12], v [12]) in MuJoCo's dof order -- arm 6, cube linear 3 in the world frame, cube angular 3 in the BODY frame --
+ * for the position tangent and for qvel alike; u = the 6 controls.  Columns 0..11 of A perturb the position, 12..23 the velocity.  Every
+ * component is perturbed by one rounded add, x +- eps, except the cube's orientation: quat <- normalize(quat (x) (cos(eps/2), +-sin(eps/2) e_i))
+ * (mj_integratePos).  Rows: (x'+ - x'-)/(2 eps), except the cube's rotation rows 9..11: the rotation vector of (quat'-)^-1 (x) quat'+
+ * (mju_subQuat) over 2 eps.  SO100_TRAJ_ACTIONS: a perturbed arm angle moves that evaluation's targets with it (the reach envs' law,
+ * d ctrl / d q = I included).
+ *
+ * Start, controls, flags and iteration counts: as in so100_trajectory_io with T = 1 (ctrl [6][M]; an explicit state starts cold, the handle's
+ * state continues with its warm-start rows, Kahan rows and anti-gravity bit, the same for all 61 evaluations).
+ *
+ * Layout.  A_dev [M][24][24] and B_dev [M][24][6] are PROBLEM-major, each matrix row-major -- the one exception to this header's SoA rule: a
+ * wave owns a problem.  qpos_next [13][M], qvel_next [12][M] (the unperturbed step: so100_trajectory_io's final rows) and bad [M] are SoA.
+ * bad = 1 where the start or the controls are not finite or any of the 61 evaluations comes out not finite; that problem's float outputs
+ * are then NaN.  The other problems never see it.  Every output is nullable; at least one is required.
+ *
+ * Argument errors, in this order: those of so100_query_trajectory up to the iteration counts (nsub alone outside 1..1024 in place of its
+ * T / nsub check); eps not finite or not positive; no output. */
+#define SO100_DERIV_NX  24
+#define SO100_DERIV_NU  6
+#define SO100_DERIV_EPS 0.015625f      /* 2^-6: the smallest worst error of the fp32 arithmetic against the fp64 derivative */
+typedef struct {
+    const float* qpos_dev;             /* [13][M] or NULL (with qvel_dev NULL: the handle's state)                 */
+    const float* qvel_dev;             /* [12][M] or NULL                                                           */
+    const float* ctrl_dev;             /* [6][M] targets (radians) or actions, by mode                              */
+    int32_t      mode;                 /* SO100_TRAJ_TARGETS or SO100_TRAJ_ACTIONS                                  */
+    int32_t      nsub;                 /* substeps of the control step, 1..1024                                     */
+    uint32_t     flags;                /* SO100_F_*                                                                 */
+    int32_t      solver_iters;         /* 1..64                                                                     */
+    int32_t      contact_iters;        /* 1..64                                                                     */
+    float        eps;                  /* finite and > 0; a power of two makes 1 / (2 eps) exact                    */
+    float*       A_dev;                /* [M][24][24]                                                               */
+    float*       B_dev;                /* [M][24][6]                                                                */
+    float*       qpos_next_dev;        /* [13][M]                                                                   */
+    float*       qvel_next_dev;        /* [12][M]                                                                   */
+    int32_t*     bad_dev;              /* [M]                                                                       */
+} so100_derivatives_io;
+
+int so100_query_derivatives(so100_sim* sim, const so100_derivatives_io* io, int32_t M, void* hip_stream);
 
 #ifdef __cplusplus
 }

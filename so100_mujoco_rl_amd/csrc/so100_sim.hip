@@ -304,3 +304,4 @@ int so100_set_field(so100_sim* s, int32_t field, const void* in_dev, void* strea
 #include "so100_query.hip"
 #include "so100_query_forward.hip"
 #include "so100_query_trajectory.hip"
+#include "so100_query_derivative.hip"

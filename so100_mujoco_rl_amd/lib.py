@@ -180,10 +180,17 @@ class TrajectoryIO(C.Structure):
                                           "sig_dev", "residual_dev", "bad_step_dev")]
 
 
+class DerivativesIO(C.Structure):
+    _fields_ = [("qpos_dev", C.c_void_p), ("qvel_dev", C.c_void_p), ("ctrl_dev", C.c_void_p), ("mode", C.c_int32), ("nsub", C.c_int32),
+                ("flags", C.c_uint32), ("solver_iters", C.c_int32), ("contact_iters", C.c_int32), ("eps", C.c_float)] + \
+               [(n, C.c_void_p) for n in ("A_dev", "B_dev", "qpos_next_dev", "qvel_next_dev", "bad_dev")]
+
+
 QUERY_EXPORTS = ["so100_query_kinematics", "so100_query_jacobian", "so100_query_dynamics", "so100_query_ik", "so100_query_forward",
-                 "so100_query_trajectory"]
+                 "so100_query_trajectory", "so100_query_derivatives"]
 QUERY_IO = {"so100_query_kinematics": KinematicsIO, "so100_query_jacobian": JacobianIO, "so100_query_dynamics": DynamicsIO, "so100_query_ik": IkIO,
-            "so100_query_forward": ForwardIO, "so100_query_trajectory": TrajectoryIO}
+            "so100_query_forward": ForwardIO, "so100_query_trajectory": TrajectoryIO, "so100_query_derivatives": DerivativesIO}
+DERIV_NX, DERIV_NU, DERIV_EPS = 24, 6, 2.0**-6                 # SO100_DERIV_*
 TRAJ_MODES = {"targets": 0, "actions": 1}                      # SO100_TRAJ_TARGETS / SO100_TRAJ_ACTIONS
 TRAJ_MAX_T, TRAJ_MAX_NSUB, TRAJ_MAX_SUBSTEPS = 4096, 1024, 65536    # SO100_TRAJ_MAX_*
 EE_LINK = 4                                                    # SO100_EE_LINK: the reference's end-effector point sits on Fixed_Jaw
@@ -690,6 +697,28 @@ class So100Sim(_Handle):
         _check(self.L.so100_query_trajectory(self.h, C.byref(io), M, self._stream()), "so100_query_trajectory")
         return {"qpos": qt.permute(0, 2, 1), "qvel": vt.permute(0, 2, 1), "ee": et.permute(0, 2, 1), "ncon": ncon, "dropped": drop, "sig": sig,
                 "residual": res, "bad_step": bad}
+
+    def derivatives(self, ctrl, qpos=None, qvel=None, mode="targets", nsub=None, flags=None, eps=None, solver_iters=None, contact_iters=None):
+        """The linearisation of one control step, MuJoCo's mjd_transitionFD, for M (state, control) pairs in one launch and without moving the
+        simulation: the centred secant over +-eps of the step trajectory() takes with T = 1.  ctrl [M, 6], qpos [M, 13], qvel [M, 12], mode, nsub,
+        flags and the iteration counts: as in trajectory() (None: the handle's own values; eps None: SO100_DERIV_EPS = 2^-6).  Tangent state
+        x = (dq, v), 12 + 12 in MuJoCo's dof order: arm 6, cube linear 3 (world frame), cube angular 3 (body frame).  Returns "A" [M, 24, 24] =
+        dx'/dx, "B" [M, 24, 6] = dx'/du, "qpos_next" [M, 13] and "qvel_next" [M, 12] (the unperturbed step) and "bad" [M] int32: 1 where the
+        start, the controls or any of the 61 evaluations is not finite; that problem's float outputs are NaN.  With friction loss, limits or
+        contacts the step is not smooth and the result depends on eps."""
+        if mode not in TRAJ_MODES:
+            raise So100Error(f"derivatives: mode must be one of {sorted(TRAJ_MODES)}, got {mode!r}")
+        us, qs, vs = self._soa(ctrl, 6, "ctrl"), self._soa(qpos, 13, "qpos"), self._soa(qvel, 12, "qvel"); M = self._problems(qs, vs, us)
+        A = torch.empty(M, DERIV_NX, DERIV_NX, dtype=torch.float32, device=self.device)
+        B = torch.empty(M, DERIV_NX, DERIV_NU, dtype=torch.float32, device=self.device)
+        qn, vn, bad = self._out(M, 13), self._out(M, 12), self._out(M, dtype=torch.int32)
+        c = self.cfg
+        io = DerivativesIO(qs.data_ptr() if qs is not None else None, vs.data_ptr() if vs is not None else None, us.data_ptr(), TRAJ_MODES[mode],
+                           c.frame_skip if nsub is None else nsub, c.flags if flags is None else flags,
+                           c.solver_iters if solver_iters is None else solver_iters, c.contact_iters if contact_iters is None else contact_iters,
+                           DERIV_EPS if eps is None else eps, A.data_ptr(), B.data_ptr(), qn.data_ptr(), vn.data_ptr(), bad.data_ptr())
+        _check(self.L.so100_query_derivatives(self.h, C.byref(io), M, self._stream()), "so100_query_derivatives")
+        return {"A": A, "B": B, "qpos_next": qn.t(), "qvel_next": vn.t(), "bad": bad}
 
 
 def learner_layout(obs_dim):

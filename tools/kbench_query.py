@@ -4,6 +4,7 @@
     python tools/kbench_query.py [--out profiles/query_kbench.json] [--commit LABEL] [--rounds 5]
     python tools/kbench_query.py --forward [--out profiles/forward_kbench.json] [--commit LABEL] [--rounds 5]
     python tools/kbench_query.py --trajectory [--out profiles/trajectory_kbench.json] [--commit LABEL] [--rounds 5]
+    python tools/kbench_query.py --derivatives [--out profiles/derivatives_kbench.json] [--commit LABEL] [--rounds 5]
 
 Cases, at M = 4096 and M = 1 048 576 problems: kinematics with every output and with the end-effector point alone, the Jacobian (jacp and
 jacr), the dynamics (M, bias and tau) and the IK.  Poses are uniform over the joint ranges; the IK problems are the 400 of the tests' recipe
@@ -21,7 +22,11 @@ one event pair round all calls of a round, is recorded as well:
 the existing code doing the same solve from the warm-start rows of its state, plus the integration and the task layer.
 
 --trajectory times the trajectory query (so100_query_trajectory) at M = 4096 and M = 262 144, T = 16 control steps of 16 substeps, per flag set
-beside the 16 so100_step calls it predicts (trajectory_main)."""
+beside the 16 so100_step calls it predicts (trajectory_main).
+
+--derivatives times the derivatives query (so100_query_derivatives) at M = 4096 and M = 65 536, nsub = 16, per form of the kernel, beside what a
+user did before it existed: the same 61 M evaluations through so100_query_trajectory (T = 1, the final rows alone) with the perturbed copies
+built and the results differenced in torch (derivatives_main)."""
 import argparse
 import ctypes as C
 import json
@@ -219,16 +224,130 @@ def trajectory_main(a):
         fh.write("\n")
 
 
+DERIVATIVES_SIZES = [(4096, 20), (65536, 4)]     # (M, timed units per round)
+DERIVATIVES_NSUB = 16
+# (name, flags): the three compile-time forms <8>, <11>, <7> and F_REFERENCE through <-1>
+DERIVATIVES_FLAGS = [("free", _FREE), ("contact_disabled", _ROWS), ("nopads", lib.F_NOPADS), ("reference_runtime_form", lib.F_REFERENCE)]
+
+
+def _quat_mul(a, b):
+    return torch.stack([a[0]*b[0] - a[1]*b[1] - a[2]*b[2] - a[3]*b[3], a[0]*b[1] + a[1]*b[0] + a[2]*b[3] - a[3]*b[2],
+                        a[0]*b[2] - a[1]*b[3] + a[2]*b[0] + a[3]*b[1], a[0]*b[3] + a[1]*b[2] - a[2]*b[1] + a[3]*b[0]])
+
+
+def emulated_derivatives(sim, qs, vs, us_, nsub, flags, eps, io_out):
+    """What a user did before the query existed, on SoA arrays [k][M]: 61 copies of every problem (copy r M + i: role r of problem i), 60 of them
+    perturbed, through so100_query_trajectory with T = 1 and the final rows alone, then the tangent difference in torch.  Returns (A [24][24][M]
+    row-major in the leading indices, B [24][6][M])."""
+    M = qs.shape[1]
+    Q, V, U = qs.repeat(1, 61), vs.repeat(1, 61), us_.repeat(1, 61)
+    sn, cs = float(np.sin(0.5*eps)), float(np.cos(0.5*eps))
+    for c in range(30):
+        for s, d in ((0, eps), (1, -eps)):
+            sl = slice((2*c + s)*M, (2*c + s + 1)*M)
+            if c < 9:
+                Q[c, sl] += d
+            elif c < 12:
+                r = torch.zeros(4, 1, device=qs.device); r[0] = cs; r[1 + c - 9] = sn if s == 0 else -sn
+                q = _quat_mul(Q[9:13, sl], r)
+                Q[9:13, sl] = q/q.norm(dim=0, keepdim=True)
+            elif c < 24:
+                V[c - 12, sl] += d
+            else:
+                U[c - 24, sl] += d
+    qf, vf = io_out(61*M)
+    io = lib.TrajectoryIO(Q.data_ptr(), V.data_ptr(), U.data_ptr(), lib.TRAJ_MODES["actions"], 1, nsub, flags, sim.cfg.solver_iters, sim.cfg.contact_iters,
+                          None, None, None, qf.data_ptr(), vf.data_ptr(), None, None, None, None, None)
+    rc = sim.L.so100_query_trajectory(sim.h, C.byref(io), 61*M, sim._stream())
+    assert rc == 0, sim.L.so100_last_error()
+    qp, qm = qf[:, :60*M].reshape(13, 30, 2, M)[:, :, 0], qf[:, :60*M].reshape(13, 30, 2, M)[:, :, 1]
+    vp, vm = vf[:, :60*M].reshape(12, 30, 2, M)[:, :, 0], vf[:, :60*M].reshape(12, 30, 2, M)[:, :, 1]
+    r = 0.5/eps
+    dq = _quat_mul(torch.stack([qm[9], -qm[10], -qm[11], -qm[12]]), qp[9:13])
+    s_ = dq[1:].norm(dim=0)
+    ang = 2.0*torch.atan2(s_, dq[0]); ang = torch.where(ang > np.pi, ang - 2.0*np.pi, ang)
+    rot = dq[1:]*torch.where(s_ < 1e-15, torch.zeros_like(s_), ang/s_)
+    AB = torch.cat([(qp[:9] - qm[:9])*r, rot*r, (vp - vm)*r])          # [24][30][M]
+    return AB[:, :24], AB[:, 24:]
+
+
+def derivatives_main(a):
+    """One so100_query_derivatives call (explicit states, mode = actions, every output, the default eps) against the emulation through
+    so100_query_trajectory, on the states of a handle of M Env01 envs after a reset and a few random steps.  An event pair round each unit,
+    enqueued without waiting; the emulation's trajectory call is timed on its own as well."""
+    nsub, eps = DERIVATIVES_NSUB, lib.DERIV_EPS
+    doc = {"what": f"HIP-event time of one so100_query_derivatives call (nsub = {nsub}, explicit states, actions, every output, eps = {eps}) and of the "
+                   "emulation a user needed before it: 61 M problems built in torch, one so100_query_trajectory call (T = 1, final rows alone), the tangent "
+                   "difference in torch; the shipped (2, 20) iterations; an event pair round each unit, medians of alternated rounds",
+           "commit": a.commit, "card": torch.cuda.get_device_name(0), "rounds": a.rounds, "cases": []}
+    for M, reps in DERIVATIVES_SIZES:
+        for name, flags in DERIVATIVES_FLAGS:
+            sim = lib.So100Sim(lib.ENV01, M, device="cuda:0", flags=flags, frame_skip=nsub, max_episode_steps=0, seed=0)
+            dev, L, st = sim.device, sim.L, sim._stream()
+            sim.reset()
+            g = torch.Generator(device=dev).manual_seed(0)
+            for _ in range(3):
+                sim.step(torch.rand(M, 6, generator=g, device=dev)*2 - 1)
+            qs, vs = (t.contiguous() for t in sim.get_state())
+            us_ = (torch.rand(M, 6, generator=g, device=dev)*2 - 1).t().contiguous()
+            A = torch.empty(M, 24, 24, dtype=torch.float32, device=dev); B = torch.empty(M, 24, 6, dtype=torch.float32, device=dev)
+            nxt = torch.empty(25, M, dtype=torch.float32, device=dev); bad = torch.empty(M, dtype=torch.int32, device=dev)
+            io = lib.DerivativesIO(qs.data_ptr(), vs.data_ptr(), us_.data_ptr(), lib.TRAJ_MODES["actions"], nsub, flags, sim.cfg.solver_iters, sim.cfg.contact_iters,
+                                   eps, A.data_ptr(), B.data_ptr(), nxt[0].data_ptr(), nxt[13].data_ptr(), bad.data_ptr())
+            fin = torch.empty(25, 61*M, dtype=torch.float32, device=dev)
+            io_out = lambda n: (fin[:13], fin[13:])
+            spans = {}
+
+            def pair(call):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(); call(); e1.record()
+                return e0, e1
+
+            def one_query():
+                rc = L.so100_query_derivatives(sim.h, C.byref(io), M, st)
+                assert rc == 0, L.so100_last_error()
+
+            def one_emulation():
+                spans["AB"] = emulated_derivatives(sim, qs, vs, us_, nsub, flags, eps, io_out)
+
+            def timed(call, n):
+                pairs = [pair(call) for _ in range(n)]
+                torch.cuda.synchronize()
+                return sum(e0.elapsed_time(e1) for e0, e1 in pairs)*1e3/n
+
+            timed(one_query, 1); timed(one_emulation, 1)
+            tq, te = [], []
+            for _ in range(a.rounds):
+                tq.append(timed(one_query, reps)); te.append(timed(one_emulation, max(1, reps//4)))
+            Ae, Be = spans["AB"]
+            diff = max((A - Ae.permute(2, 0, 1)).abs().max().item(), (B - Be.permute(2, 0, 1)).abs().max().item())
+            mq, me = statistics.median(tq), statistics.median(te)
+            case = {"case": name, "M": M, "flags": int(flags), "nsub": nsub, "derivatives_us_per_call": round(mq, 1), "emulation_us": round(me, 1),
+                    "derivatives_over_emulation": round(mq/me, 3), "derivatives_rounds_us": [round(x, 1) for x in tq], "emulation_rounds_us": [round(x, 1) for x in te],
+                    "units_per_round": reps, "evaluations_per_s": round(61*M/(mq*1e-6), 1), "problem_substeps_per_s": round(61*M*nsub/(mq*1e-6), 1),
+                    "largest_difference_to_emulation": diff, "bad_problems": int(bad.sum().item())}
+            doc["cases"].append(case)
+            print(json.dumps(case), flush=True)
+            sim.close()
+            del fin, A, B, spans
+    with open(a.out, "w") as fh:
+        json.dump(doc, fh, indent=1)
+        fh.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None); ap.add_argument("--commit", default="unknown")
     ap.add_argument("--rounds", type=int, default=5); ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--forward", action="store_true", help="time the forward-dynamics query against so100_step (profiles/forward_kbench.json)")
     ap.add_argument("--trajectory", action="store_true", help="time the trajectory query against the so100_step calls it predicts (profiles/trajectory_kbench.json)")
+    ap.add_argument("--derivatives", action="store_true", help="time the derivatives query against its emulation through the trajectory query (profiles/derivatives_kbench.json)")
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "trajectory_kbench.json" if a.trajectory else "forward_kbench.json" if a.forward else "query_kbench.json")
+        a.out = os.path.join(ROOT, "profiles", "derivatives_kbench.json" if a.derivatives else "trajectory_kbench.json" if a.trajectory else "forward_kbench.json" if a.forward else "query_kbench.json")
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    if a.derivatives:
+        return derivatives_main(a)
     if a.trajectory:
         return trajectory_main(a)
     if a.forward:
