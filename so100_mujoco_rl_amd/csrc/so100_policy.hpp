@@ -27,7 +27,10 @@ constexpr int policy_odp(int od) { return (od + 3) & ~3; }     // K of layer 1: 
 constexpr int HD_MU_W = 0, HD_V_W = 6*64, HD_MU_B = 7*64, HD_LOG_STD = HD_MU_B + 6, HD_V_B = HD_LOG_STD + 6, HD_WORDS = 7*64 + 16;
 // hm[]: mu_w once more for the matrix-core mean head (so100_rollout.hpp: head_mfma), rows HM_LD floats apart.  One ds_read_b128 of that head
 // touches the four rows (lane & 3) + 4*(lane >> 5) within a 16-lane group: 64 floats apart they share four banks, 68 apart they take sixteen.
-constexpr int HM_LD = 68, HM_WORDS = 6*HM_LD;
+constexpr int HM_LD = 68, HM_STD = 6*HM_LD, HM_WORDS = HM_STD + 8;
+// hm[HM_STD + a] = exp(log_std[a]): the policy does not change inside a launch, so the rollout kernels that keep hm take the exponential once per
+// launch, where hm is filled, with the builtin the sampling used per step (same bits).  It stands here and not in hd: hm exists in those kernels
+// only, so every other kernel keeps the LDS image it had.  (HM_STD is a multiple of four words: the six values are read as b128 + b64.)
 // rollout-buffer row of one env and step: obs[OD] | raw action[6] | reward | done code | value | log-prob (columns past the observation)
 constexpr int ROW_ACT = 0, ROW_REWARD = 6, ROW_DONE = 7, ROW_VALUE = 8, ROW_LOGP = 9, ROW_EXTRA = 10;
 __device__ __forceinline__ float done_code(bool done, bool trunc_only) { return done ? (trunc_only ? 2.0f : 1.0f) : 0.0f; }     // 2 = TimeLimit truncation only

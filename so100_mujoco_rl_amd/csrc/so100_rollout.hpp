@@ -167,7 +167,9 @@ __device__ __forceinline__ void cube_from_lds(float (*xc)[64], int col, Cube<flo
 // Substep 0 is then peeled: ONE barrier, wave 0 solves and integrates, and the loop runs substeps 1 ... as it is.  `after_first_barrier(0)`
 // moves behind the first barrier of substep 1 (behind the peeled barrier when frame_skip = 1).  so100_step_mw gets its action from
 // outside and has nothing to overlap: it compiles the text it had.
-template <bool PADS, bool LINKS, bool PK, bool LOCAL, bool Z, bool PRE, class Hook, class Forget>
+// SERVO (with PRE; the 32-row rollout kernels): inside the loop wave 0 computes the servo force, arm_tau without the bias, in front of the
+// mid-substep barrier instead of behind it.  Every other caller compiles the text it had.
+template <bool PADS, bool LINKS, bool PK, bool LOCAL, bool Z, bool PRE, bool SERVO = false, class Hook, class Forget>
 __device__ __forceinline__ void physics_phase_mw(const SimParams& p, int wave, int lane, EnvState& e, float ctrl[6], float cstale[3],
                                                  Arm<float>& A, const PhaseLds& L, ContactMemo& memo, Prof& prof_, Hook after_first_barrier, Forget forget_caller_state) {
     float (*xq)[64] = L.xq; float (*xc)[64] = L.xc; float (*xb)[64] = L.xb; float (*xa)[64] = L.xa; float (*xk)[64] = L.xk; float (*xm)[64] = L.xm;
@@ -210,6 +212,13 @@ __device__ __forceinline__ void physics_phase_mw(const SimParams& p, int wave, i
     // barrier needs every wave, so the others simply waited for it at the first one: 72 -> 101 us per step.  The cube stays in
     // step with the arm: detection + row set-up in the first half-substep, Newton in the second.)
     static_assert(!PRE || (LOCAL && !PADS), "the pre-computed first half is written for the loop-local factor without pad contacts");
+    static_assert(!SERVO || PRE, "the early servo force is written for the PRE variants");
+    // SERVO: kp*u, rounded once per env step (what the compiler hoists out of the loop's arm_tau: see the peeled substep below)
+    float ku[6] = { 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f };
+    if constexpr (SERVO) {
+#pragma unroll
+        for (int i = 0; i < 6; i++) ku[i] = (float)so100g::ACT_KP*tclamp(ctrl[i], (float)-so100g::ACT_CTRL, (float)so100g::ACT_CTRL);
+    }
     if constexpr (PRE) {
         __syncthreads();                                   // s, c, the bias and the factor of substep 0 are in LDS
         SO100_PROF(15);                                    // substep 0's one barrier wait
@@ -270,9 +279,22 @@ __device__ __forceinline__ void physics_phase_mw(const SimParams& p, int wave, i
         // and no path copies it.  Without LOCAL the kernel keeps the shape it had (the callers say which: section 8f).
         static_assert(!LOCAL || !PADS, "the loop-local factor is written for the variants without pad contacts (nothing publishes M)");
         Arm<float> Fl; Arm<float>& F = LOCAL ? Fl : A;
+        float servo[6];                                    // SERVO: wave 0's alone, defined in front of the barrier and read behind it (no initialiser: one would be six moves on every wave's path)
         if (LOCAL && wave == 0) {
 #pragma unroll
             for (int i = 0; i < 6; i++) { F.s[i] = A.s[i]; F.c[i] = A.c[i]; }
+            if constexpr (SERVO) {
+                // arm_tau's half that does not need the bias (q, v and ctrl only), in front of the barrier; behind it wave 0 subtracts the bias.  The
+                // barrier is where wave 0 waits for wave 1's bias anyway, and these eighteen instructions stood behind it.  Written out in the rounding
+                // the loop's arm_tau compiles to, like the peeled substep above.  (In front of arm_mass: behind arm_factor the register allocation
+                // of the sin/cos update came out with one s_nop more; the scheduler places the instructions inside the block either way.)
+#pragma unroll
+                for (int i = 0; i < 6; i++) {
+                    float f = __builtin_fmaf(-(float)so100g::ACT_KP, e.q[i], ku[i]);
+                    f = __builtin_fmaf(-(float)so100g::ACT_KV[i], e.v[i], f);
+                    servo[i] = tclamp(f, (float)-so100g::ACT_FORCE, (float)so100g::ACT_FORCE);
+                }
+            }
             arm_mass<float, PK, Z>(F);
             arm_factor<float>(p.flags, F);
             SO100_PROF(4);                                 // CRBA + factor (wave 0)
@@ -356,7 +378,10 @@ __device__ __forceinline__ void physics_phase_mw(const SimParams& p, int wave, i
 #pragma unroll
             for (int i = 0; i < 6; i++) F.bias[i] = xb[i][lane];
             float tau[6];
-            arm_tau<float>(e.q, e.v, ctrl, F, tau);
+            if constexpr (SERVO) {
+#pragma unroll
+                for (int i = 0; i < 6; i++) tau[i] = servo[i] - F.bias[i];
+            } else arm_tau<float>(e.q, e.v, ctrl, F, tau);
             if ((p.flags & (F_FRICTIONLOSS | F_LIMITS)) != 0u) {
                 arm_rows<float>(e.q, e.v, tau, e.ff, e.fl, p.flags, F, r0);
                 arm_pgs<float>(e.ff, e.fl, p.solver_iters, F, r0, acc0, pgs_res);
@@ -713,6 +738,8 @@ __global__ void __launch_bounds__(64*NW) so100_rollout_fused(SimParams p, float*
     constexpr bool MH = PRE && HALF;
     __shared__ __attribute__((aligned(16))) float hm[MH ? HM_WORDS : 4];  // mu_w, rows HM_LD apart (written once per launch beside hd)
     __shared__ float xv[MH ? 32 : 1];                             // value of env = index (wave 3's accumulator layout -> its lane = env)
+    // The same kernels take what the step's result does not need on wave 0's chain off it: exp(log_std) once per launch
+    // (hm[HM_STD]) with a straight-line sampling stretch, and the servo force in front of the mid-substep barrier (physics_phase_mw: SERVO = MH).
     ContactMemo memo;                                             // ... and the rest of the contact wave's active-set memory
     if (FL >= 0) p.flags = (unsigned)FL;
     const int lane = threadIdx.x & 63;
@@ -751,6 +778,7 @@ __global__ void __launch_bounds__(64*NW) so100_rollout_fused(SimParams p, float*
         if (lane == 0) hd[HD_V_B] = w.v_b[0];
         if constexpr (MH) {
             for (int i = lane; i < 6*64; i += 64) hm[(i >> 6)*HM_LD + (i & 63)] = w.mu_w[i];
+            if (lane < 6) hm[HM_STD + lane] = __builtin_expf(w.log_std[lane]);
         }
     }
     EnvState e;
@@ -892,6 +920,23 @@ __global__ void __launch_bounds__(64*NW) so100_rollout_fused(SimParams p, float*
 #pragma unroll
             for (int a = 0; a < 6; a++) { mean[a] = xmean[a][lane]; eps[a] = xn[a][lane]; }
             float act[6], lp = 0.0f;
+            if constexpr (MH) {
+                // straight-line: std = exp(log_std) was taken once per launch (hm[HM_STD]), every lane computes, one `live` region stores.  A dead
+                // lane's action moves its parked state (idle_lane_state), which nothing reads.
+                float raw[6];
+#pragma unroll
+                for (int a = 0; a < 6; a++) {
+                    const float ls = hd[HD_LOG_STD + a];
+                    raw[a] = __builtin_fmaf(hm[HM_STD + a], eps[a], mean[a]);
+                    lp += -0.5f*eps[a]*eps[a] - ls - 0.9189385332046727f;
+                    act[a] = tclamp(raw[a], -1.0f, 1.0f);
+                }
+                if (live) {
+#pragma unroll
+                    for (int a = 0; a < 6; a++) row[OD + ROW_ACT + a] = raw[a];
+                    row[OD + ROW_LOGP] = lp;
+                }
+            } else {
 #pragma unroll
             for (int a = 0; a < 6; a++) {
                 const float ls = hd[HD_LOG_STD + a];
@@ -900,7 +945,8 @@ __global__ void __launch_bounds__(64*NW) so100_rollout_fused(SimParams p, float*
                 act[a] = live ? tclamp(raw, -1.0f, 1.0f) : 0.0f;
                 if (live) row[OD + ROW_ACT + a] = raw;
             }
-            if (live) {
+            }
+            if (live && !MH) {
                 if constexpr (!PRE) {
 #pragma unroll
                     for (int k = 0; k < OD; k++) row[k] = oxt[lane][k];
@@ -955,7 +1001,7 @@ __global__ void __launch_bounds__(64*NW) so100_rollout_fused(SimParams p, float*
         {
             Arm<float> A;
             const PhaseLds lds{ xq, xc, xb, pool, xa, xk, PRE ? xf : xm, pbuf, xw };
-            physics_phase_mw<PADS, LINKS, PKF, LOCALF, PKF, PRE>(p, wave, lane, e, ctx.ctrl, cstale, A, lds, memo, prof_, [&](int sub) {
+            physics_phase_mw<PADS, LINKS, PKF, LOCALF, PKF, PRE, MH>(p, wave, lane, e, ctx.ctrl, cstale, A, lds, memo, prof_, [&](int sub) {
                 if (wave == 3 && sub == 0 && t + 1 < ra.T) {       // wave 0 has consumed xn before this barrier
                     float eps[8];
                     policy_noise(p.env_id_offset + (uint32_t)env, ra.step_counter0 + (uint32_t)(t + 1), p.seed_lo, p.seed_hi, eps);
