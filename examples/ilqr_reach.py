@@ -4,8 +4,9 @@ current plan of `horizon` actions out with So100Sim.trajectory, So100Sim.derivat
 that rollout in one launch (the arm block of the tangent state: rows and columns 0..5 and 12..17 of A, rows of B), the cost |ee - cube|^2
 summed over the horizon gets its Gauss-Newton terms from So100Sim.jacobian, a batched Riccati pass in torch on the device improves the
 plan, and its first action is executed through step().  Printed next to the zero-action baseline, like examples/mppi_reach.py.
+--backward query replaces the torch Riccati and forward loops by ONE So100Sim.lqr call (nx = 12: the arm block, read out of the unsliced A, B).
 
-    python examples/ilqr_reach.py [--envs 8] [--horizon 8] [--steps 100] [--iterations 2]
+    python examples/ilqr_reach.py [--envs 8] [--horizon 8] [--steps 100] [--iterations 2] [--backward {torch,query}]
 """
 import argparse
 import os
@@ -21,9 +22,10 @@ ARM = list(range(0, 6)) + list(range(12, 18))                  # the arm's block
 
 class Ilqr:
     """policy(sim, obs) -> action [N, 6].  plan [N, horizon, 6] is the current action sequence, shifted by one step after every call;
-    control_cost: the weight of |a|^2 beside |ee - cube|^2 (metres squared); damping: added to Q_uu (Levenberg-Marquardt)."""
-    def __init__(self, horizon=8, iterations=2, control_cost=1e-5, damping=1e-5):
-        self.H, self.iterations, self.control_cost, self.damping = horizon, iterations, control_cost, damping
+    control_cost: the weight of |a|^2 beside |ee - cube|^2 (metres squared); damping: added to Q_uu (Levenberg-Marquardt); backward: "torch" (the
+    loops below) or "query" (So100Sim.lqr: the same recursion in one launch)."""
+    def __init__(self, horizon=8, iterations=2, control_cost=1e-5, damping=1e-5, backward="torch"):
+        self.H, self.iterations, self.control_cost, self.damping, self.backward = horizon, iterations, control_cost, damping, backward
         self.plan = None
 
     def improve(self, sim, q0, v0):
@@ -34,9 +36,6 @@ class Ilqr:
         d = sim.derivatives(U.permute(1, 0, 2).reshape(H*N, 6), Xq.reshape(H*N, 13), Xv.reshape(H*N, 12), mode="actions")
         if bool(d["bad"].any()) or bool((roll["bad_step"] >= 0).any()):
             return
-        A = d["A"][:, ARM][:, :, ARM].reshape(H, N, 12, 12)
-        B = d["B"][:, ARM].reshape(H, N, 12, 6).clone()
-        B[..., 5] = 0.0                                              # the jaw does not move the end-effector point
         # Gauss-Newton terms of |ee(q) - cube|^2 at the states after each action
         qn = roll["qpos"]
         J = sim.jacobian(qn[..., :6].reshape(H*N, 6))["jacp"].reshape(H, N, 3, 6)
@@ -45,6 +44,23 @@ class Ilqr:
         lx[..., :6] = 2.0*torch.einsum("hnij,hni->hnj", J, r)
         lxx[..., :6, :6] = 2.0*torch.einsum("hnij,hnik->hnjk", J, J)
         eye = torch.eye(6, device=dev)
+        if self.backward == "query":
+            # one launch: A, B as the derivatives query wrote them (row t of the cost is the state BEFORE action t: a zero row in front)
+            Bq = d["B"].reshape(H, N, 24, 6).clone()
+            Bq[..., 5] = 0.0                                         # the jaw does not move the end-effector point
+            Ut = U.permute(1, 0, 2).contiguous()
+            zero = torch.zeros(1, N, 12, device=dev)
+            s = sim.lqr(d["A"].reshape(H, N, 24, 24), Bq, torch.cat([zero, lx]), torch.cat([zero[..., None].expand(1, N, 12, 12), lxx]),
+                        lu=2.0*self.control_cost*Ut, luu=(2.0*self.control_cost*eye).expand(H, N, 6, 6), nx=12, reg=self.damping, u=Ut, u_lo=-1.0, u_hi=1.0)
+            if bool((s["bad"] >= 0).any()):
+                return
+            new = (Ut + s["du"]).permute(1, 0, 2).clone()
+            new[..., 5] = 0.0
+            self.plan = new
+            return
+        A = d["A"][:, ARM][:, :, ARM].reshape(H, N, 12, 12)
+        B = d["B"][:, ARM].reshape(H, N, 12, 6).clone()
+        B[..., 5] = 0.0                                              # the jaw does not move the end-effector point
         # the backward pass: V is the cost-to-go from the state after action t
         Vx, Vxx = lx[H - 1], lxx[H - 1]
         k = torch.zeros(H, N, 6, device=dev); K = torch.zeros(H, N, 6, 12, device=dev)
@@ -110,8 +126,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=8); ap.add_argument("--horizon", type=int, default=8)
     ap.add_argument("--steps", type=int, default=100); ap.add_argument("--iterations", type=int, default=2)
+    ap.add_argument("--backward", choices=("torch", "query"), default="torch")
     args = ap.parse_args()
-    for name, policy in (("iLQR", Ilqr(args.horizon, args.iterations)), ("zero action", zero_action)):
+    for name, policy in (("iLQR", Ilqr(args.horizon, args.iterations, backward=args.backward)), ("zero action", zero_action)):
         sim = So100Sim(ENV01, args.envs, flags=F_CUBE_PINNED, max_episode_steps=0, seed=0)
         d0, d1, r = run(sim, args.steps, policy)
         print(f"{name:12s} mean |cube - ee|: {d0:.4f} m at reset -> {d1:.4f} m after {args.steps} steps; reward/step {r:+.4f}")

@@ -250,6 +250,67 @@ typedef struct {
 
 int so100_query_derivatives(so100_sim* sim, const so100_derivatives_io* io, int32_t M, void* hip_stream);
 
+/* LQR: the time-varying Riccati backward pass, the feedback gains and the linear forward pass of one iLQR / LQR / MPC iteration, for M
+ * independent problems in one launch, one GPU wave per problem -- the step between the linearisation (so100_query_derivatives) and a better
+ * plan.  The handle is taken for the device, the error slot and the conventions: its state is NEVER read or written.
+ *
+ * Per problem: horizon T, state-tangent size n = nx, 6 controls, dx_{t+1} = A_t dx_t + B_t du_t and the quadratic model
+ *     sum_{t<T} [lx_t.dx_t + dx_t' lxx_t dx_t / 2 + lu_t.du_t + du_t' luu_t du_t / 2 + du_t' lux_t dx_t] + lx_T.dx_T + dx_T' lxx_T dx_T / 2.
+ * Backward pass.  Vx = lx_T, Vxx = lxx_T; for t = T-1 .. 0:
+ *     Qx  = lx_t  + A'Vx            Qu  = lu_t  + B'Vx
+ *     Qxx = lxx_t + A'Vxx A         Qux = lux_t + B'Vxx A        Quu = luu_t + B'Vxx B
+ *     Quu_r = Quu + reg I           (6 x 6 Cholesky; a pivot that is <= 0 or not finite FAILS the problem at this t)
+ *     k = -Quu_r^-1 Qu              K = -Quu_r^-1 Qux
+ *     dV1 += k'Qu                   dV2 += k'Quu k / 2           (the unregularised Quu, here and below)
+ *     Vx  = Qx  + K'Quu k + K'Qu  + Qux'k
+ *     Vxx = Qxx + K'Quu K + K'Qux + Qux'K;   Vxx <- (Vxx + Vxx')/2
+ * (Tassa's form, correct under reg > 0).  lxx_t and luu_t are symmetric matrices: lxx_T is symmetrised like every later Vxx, and the lower
+ * triangle of Quu_r is what is factored.
+ * Linear forward pass, run only if du or dx is asked for.  dx_0 = dx0 (NULL: 0);  du_t = alpha k_t + K_t dx_t, or with u (the nominal controls)
+ * du_t = clamp(u_t + alpha k_t + K_t dx_t, u_lo, u_hi) - u_t;  dx_{t+1} = A_t dx_t + B_t du_t.  The bounds are used only with u.
+ *
+ * Forms.  nx = 24: the full tangent state of the derivatives query.  nx = 12: the arm block, tangent indices 0..5 and 12..17 -- what a planner
+ * under SO100_F_CUBE_PINNED uses.  A [T][M][24][24] and B [T][M][24][6] are ALWAYS in the derivatives query's output layout: what
+ * so100_query_derivatives writes for T * M problems ordered t-major; the arm form reads its 12 rows and columns out of them.  Everything else
+ * is in the n of the call and PROBLEM-major (the exception the derivatives query makes: a wave owns a problem).
+ *
+ * bad [M]: -1 where the problem is fine; the t at which the Cholesky failed; T for a non-finite input.  The inputs of step t are tested as the
+ * backward pass reads them, so of a non-finite input at one step and a failing factor at a LATER step the later step is what is reported.
+ * Every float output of a failed problem is NaN; the other problems never see it.  du and dx need k and K (the call has no storage of its
+ * own).  Every output is nullable; at least one is required.
+ *
+ * Argument errors, in this order: a null handle or io; M < 1; nx not 12 or 24; T outside 1..4096; a required pointer (A, B, lx, lxx) that is
+ * NULL; reg negative or not finite, alpha not finite, u_lo > u_hi; du or dx without k and K; no output. */
+#define SO100_LQR_NU    6
+#define SO100_LQR_MAX_T 4096
+typedef struct {
+    int32_t      nx;                   /* 24 or 12                                                                  */
+    int32_t      T;                    /* horizon, 1..4096                                                          */
+    const float* A_dev;                /* [T][M][24][24]                                                            */
+    const float* B_dev;                /* [T][M][24][6]                                                             */
+    const float* lx_dev;               /* [T+1][M][n]                                                               */
+    const float* lxx_dev;              /* [T+1][M][n][n]                                                            */
+    const float* lu_dev;               /* [T][M][6] or NULL: zero                                                   */
+    const float* luu_dev;              /* [T][M][6][6] or NULL: zero                                                */
+    const float* lux_dev;              /* [T][M][6][n] or NULL: zero                                                */
+    const float* u_dev;                /* [T][M][6] nominal controls, or NULL: no clamp                             */
+    const float* dx0_dev;              /* [M][n] or NULL: zero                                                      */
+    float        reg;                  /* finite and >= 0                                                           */
+    float        alpha;                /* finite: the step on k                                                     */
+    float        u_lo;                 /* u_lo <= u_hi; used only with u_dev                                        */
+    float        u_hi;
+    float*       k_dev;                /* [T][M][6]                                                                 */
+    float*       K_dev;                /* [T][M][6][n]                                                              */
+    float*       Vx0_dev;              /* [M][n]                                                                    */
+    float*       Vxx0_dev;             /* [M][n][n]                                                                 */
+    float*       dV_dev;               /* [M][2]: dV1, dV2                                                          */
+    float*       du_dev;               /* [T][M][6]                                                                 */
+    float*       dx_dev;               /* [T+1][M][n]                                                               */
+    int32_t*     bad_dev;              /* [M]                                                                       */
+} so100_lqr_io;
+
+int so100_query_lqr(so100_sim* sim, const so100_lqr_io* io, int32_t M, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -186,11 +186,19 @@ class DerivativesIO(C.Structure):
                [(n, C.c_void_p) for n in ("A_dev", "B_dev", "qpos_next_dev", "qvel_next_dev", "bad_dev")]
 
 
+class LqrIO(C.Structure):
+    _fields_ = [("nx", C.c_int32), ("T", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("A_dev", "B_dev", "lx_dev", "lxx_dev", "lu_dev", "luu_dev", "lux_dev", "u_dev", "dx0_dev")] + \
+               [(n, C.c_float) for n in ("reg", "alpha", "u_lo", "u_hi")] + \
+               [(n, C.c_void_p) for n in ("k_dev", "K_dev", "Vx0_dev", "Vxx0_dev", "dV_dev", "du_dev", "dx_dev", "bad_dev")]
+
+
 QUERY_EXPORTS = ["so100_query_kinematics", "so100_query_jacobian", "so100_query_dynamics", "so100_query_ik", "so100_query_forward",
-                 "so100_query_trajectory", "so100_query_derivatives"]
+                 "so100_query_trajectory", "so100_query_derivatives", "so100_query_lqr"]
 QUERY_IO = {"so100_query_kinematics": KinematicsIO, "so100_query_jacobian": JacobianIO, "so100_query_dynamics": DynamicsIO, "so100_query_ik": IkIO,
-            "so100_query_forward": ForwardIO, "so100_query_trajectory": TrajectoryIO, "so100_query_derivatives": DerivativesIO}
+            "so100_query_forward": ForwardIO, "so100_query_trajectory": TrajectoryIO, "so100_query_derivatives": DerivativesIO, "so100_query_lqr": LqrIO}
 DERIV_NX, DERIV_NU, DERIV_EPS = 24, 6, 2.0**-6                 # SO100_DERIV_*
+LQR_NU, LQR_MAX_T = 6, 4096                                    # SO100_LQR_*
 TRAJ_MODES = {"targets": 0, "actions": 1}                      # SO100_TRAJ_TARGETS / SO100_TRAJ_ACTIONS
 TRAJ_MAX_T, TRAJ_MAX_NSUB, TRAJ_MAX_SUBSTEPS = 4096, 1024, 65536    # SO100_TRAJ_MAX_*
 EE_LINK = 4                                                    # SO100_EE_LINK: the reference's end-effector point sits on Fixed_Jaw
@@ -719,6 +727,44 @@ class So100Sim(_Handle):
                            DERIV_EPS if eps is None else eps, A.data_ptr(), B.data_ptr(), qn.data_ptr(), vn.data_ptr(), bad.data_ptr())
         _check(self.L.so100_query_derivatives(self.h, C.byref(io), M, self._stream()), "so100_query_derivatives")
         return {"A": A, "B": B, "qpos_next": qn.t(), "qvel_next": vn.t(), "bad": bad}
+
+    def lqr(self, A, B, lx, lxx, lu=None, luu=None, lux=None, *, nx=24, reg=0.0, alpha=1.0, u=None, u_lo=-1.0, u_hi=1.0, dx0=None):
+        """The Riccati backward pass and the linear forward pass of one iLQR / LQR iteration for M problems in one launch (the handle's state is
+        not read).  A [T, M, 24, 24] and B [T, M, 24, 6] as derivatives() returns them for T x M problems ordered t-major; nx = 24: the full
+        tangent state, nx = 12: the arm block (tangent indices 0..5 and 12..17, read out of the same A and B).  With n = nx: lx [T + 1, M, n],
+        lxx [T + 1, M, n, n] (row T: the terminal cost), lu [T, M, 6], luu [T, M, 6, 6], lux [T, M, 6, n] (None: zero), u [T, M, 6] nominal controls
+        (None: no clamp; else u + du is kept in [u_lo, u_hi]), dx0 [M, n] (None: zero).  Returns "k" [T, M, 6], "K" [T, M, 6, n], "Vx0" [M, n],
+        "Vxx0" [M, n, n], "dV" [M, 2] (the expected change of the model is alpha dV1 + alpha^2 dV2), "du" [T, M, 6] = alpha k + K dx (clamped with
+        u), "dx" [T + 1, M, n] and "bad" [M] int32: -1, or the step whose Quu + reg I is not positive definite, or T for a non-finite input; a
+        failed problem's float outputs are NaN."""
+        f32 = self._lqr_in
+        A = torch.as_tensor(A, dtype=torch.float32, device=self.device)
+        if A.dim() != 4 or A.shape[0] < 1 or A.shape[1] < 1:
+            raise So100Error(f"A: want a [T, M, 24, 24] tensor, got {tuple(A.shape)}")
+        if nx not in (12, 24):
+            raise So100Error(f"lqr: nx must be 12 or 24, got {nx!r}")
+        T, M, n = A.shape[0], A.shape[1], nx
+        A, B = f32(A, (T, M, 24, 24), "A"), f32(B, (T, M, 24, 6), "B")
+        lx, lxx = f32(lx, (T + 1, M, n), "lx"), f32(lxx, (T + 1, M, n, n), "lxx")
+        lu, luu, lux = f32(lu, (T, M, 6), "lu"), f32(luu, (T, M, 6, 6), "luu"), f32(lux, (T, M, 6, n), "lux")
+        u, dx0 = f32(u, (T, M, 6), "u"), f32(dx0, (M, n), "dx0")
+        new = lambda *shape, **kw: torch.empty(*shape, dtype=kw.get("dtype", torch.float32), device=self.device)
+        out = {"k": new(T, M, 6), "K": new(T, M, 6, n), "Vx0": new(M, n), "Vxx0": new(M, n, n), "dV": new(M, 2), "du": new(T, M, 6),
+               "dx": new(T + 1, M, n), "bad": new(M, dtype=torch.int32)}
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        io = LqrIO(n, T, *[ptr(t) for t in (A, B, lx, lxx, lu, luu, lux, u, dx0)], reg, alpha, u_lo, u_hi,
+                   *[out[name].data_ptr() for name in ("k", "K", "Vx0", "Vxx0", "dV", "du", "dx", "bad")])
+        _check(self.L.so100_query_lqr(self.h, C.byref(io), M, self._stream()), "so100_query_lqr")
+        return out
+
+    def _lqr_in(self, t, shape, name):
+        """a contiguous float32 tensor of exactly `shape` on the handle's device, or None"""
+        if t is None:
+            return None
+        t = torch.as_tensor(t, dtype=torch.float32, device=self.device).contiguous()
+        if tuple(t.shape) != tuple(shape):
+            raise So100Error(f"{name}: want a {list(shape)} tensor, got {tuple(t.shape)}")
+        return t
 
 
 def learner_layout(obs_dim):

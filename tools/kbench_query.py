@@ -5,6 +5,7 @@
     python tools/kbench_query.py --forward [--out profiles/forward_kbench.json] [--commit LABEL] [--rounds 5]
     python tools/kbench_query.py --trajectory [--out profiles/trajectory_kbench.json] [--commit LABEL] [--rounds 5]
     python tools/kbench_query.py --derivatives [--out profiles/derivatives_kbench.json] [--commit LABEL] [--rounds 5]
+    python tools/kbench_query.py --lqr [--form mfma] [--out profiles/lqr_kbench.json] [--commit LABEL] [--rounds 5]
 
 Cases, at M = 4096 and M = 1 048 576 problems: kinematics with every output and with the end-effector point alone, the Jacobian (jacp and
 jacr), the dynamics (M, bias and tau) and the IK.  Poses are uniform over the joint ranges; the IK problems are the 400 of the tests' recipe
@@ -26,7 +27,12 @@ beside the 16 so100_step calls it predicts (trajectory_main).
 
 --derivatives times the derivatives query (so100_query_derivatives) at M = 4096 and M = 65 536, nsub = 16, per form of the kernel, beside what a
 user did before it existed: the same 61 M evaluations through so100_query_trajectory (T = 1, the final rows alone) with the perturbed copies
-built and the results differenced in torch (derivatives_main)."""
+built and the results differenced in torch (derivatives_main).
+
+--lqr times the LQR query (so100_query_lqr, every output, with nominal controls and bounds) at M in {8, 4096}, T in {8, 64}, both nx, beside what
+a user did before it existed: the backward and forward loops of examples/ilqr_reach.py in torch, on identical inputs (lqr_main).  --form labels
+the cases with the form of the kernel the loaded library holds (SO100_LIB=<a side build with -DSO100_LQR_VALU=1> --form valu); the cases of
+other forms already in the output file are kept."""
 import argparse
 import ctypes as C
 import json
@@ -335,6 +341,114 @@ def derivatives_main(a):
         fh.write("\n")
 
 
+LQR_SIZES = [(8, 8, 50, 5), (8, 64, 20, 3), (4096, 8, 20, 3), (4096, 64, 5, 2)]       # (M, T, query calls, torch loops per timed round)
+LQR_ARM = list(range(0, 6)) + list(range(12, 18))
+
+
+def torch_lqr(A, B, lx, lxx, lu, luu, reg, U):
+    """the loops of examples/ilqr_reach.py (backward pass, then the clamped linear forward pass) on A [T, M, n, n], B [T, M, n, 6], lx [T + 1, M, n],
+    lxx [T + 1, M, n, n], lu [T, M, 6], luu [6, 6], the plan U [T, M, 6]: (k, K, du)"""
+    T, M, n = A.shape[0], A.shape[1], A.shape[2]
+    dev = A.device
+    eye = torch.eye(6, device=dev)
+    Vx, Vxx = lx[T], lxx[T]
+    k = torch.zeros(T, M, 6, device=dev); K = torch.zeros(T, M, 6, n, device=dev)
+    for t in range(T - 1, -1, -1):
+        At, Bt = A[t], B[t]
+        Qx = lx[t] + torch.einsum("nij,ni->nj", At, Vx)
+        Qu = lu[t] + torch.einsum("nij,ni->nj", Bt, Vx)
+        VA = Vxx @ At
+        Qxx = lxx[t] + At.transpose(1, 2) @ VA
+        Qux = Bt.transpose(1, 2) @ VA
+        Quu = Bt.transpose(1, 2) @ Vxx @ Bt + luu
+        Quu_r = Quu + reg*eye
+        k[t] = -torch.linalg.solve(Quu_r, Qu[..., None])[..., 0]
+        K[t] = -torch.linalg.solve(Quu_r, Qux)
+        Vx = Qx + torch.einsum("nij,ni->nj", K[t], Qu + torch.einsum("nij,nj->ni", Quu, k[t])) + torch.einsum("nij,ni->nj", Qux, k[t])
+        Vxx = Qxx + K[t].transpose(1, 2) @ Quu @ K[t] + K[t].transpose(1, 2) @ Qux + Qux.transpose(1, 2) @ K[t]
+        Vxx = 0.5*(Vxx + Vxx.transpose(1, 2))
+    dx = torch.zeros(M, n, device=dev)
+    du = torch.zeros(T, M, 6, device=dev)
+    for t in range(T):
+        du[t] = (U[t] + k[t] + torch.einsum("nij,nj->ni", K[t], dx)).clamp(-1.0, 1.0) - U[t]
+        dx = torch.einsum("nij,nj->ni", A[t], dx) + torch.einsum("nij,nj->ni", B[t], du[t])
+    return k, K, du
+
+
+def lqr_main(a):
+    """One so100_query_lqr call (every output, nominal controls with bounds) against torch_lqr on the same inputs: seeded synthetic problems of the
+    tests' family S (A = I + 0.3 N / sqrt(n), B = 0.3 N, lxx = C C' + 0.1 I, lx, lu = N, luu = 0.2 I, no cross term, reg = 1e-5).  An event pair round
+    each unit, enqueued without waiting."""
+    sim = lib.So100Sim(lib.ENV01, 8, device="cuda:0", flags=lib.F_CUBE_PINNED, seed=0)
+    dev, L, st = sim.device, sim.L, sim._stream()
+    doc = {"what": "HIP-event time of one so100_query_lqr call (every output, u with bounds) and of the torch loops of examples/ilqr_reach.py (backward pass "
+                   "and clamped forward pass; the arm block sliced beforehand, outside the span) on identical inputs; an event pair round each unit, medians of "
+                   "alternated rounds; `form`: the kernel's products on the matrix instruction (mfma) or as plain FMA loops (valu, a side build)",
+           "commit": a.commit, "card": torch.cuda.get_device_name(0), "rounds": a.rounds, "cases": []}
+    if os.path.exists(a.out):
+        doc["cases"] = [c for c in json.load(open(a.out)).get("cases", []) if c.get("form") != a.form]
+    reg = 1e-5
+    for nx in (12, 24):
+        for M, T, reps, loops in LQR_SIZES:
+            g = torch.Generator(device=dev).manual_seed(0)
+            rn = lambda *shape: torch.randn(*shape, generator=g, device=dev)
+            A = torch.eye(24, device=dev) + 0.3*rn(T, M, 24, 24)/nx**0.5
+            B = 0.3*rn(T, M, 24, 6)
+            Cm = rn(T + 1, M, nx, nx)/nx**0.5
+            lxx = (Cm @ Cm.transpose(2, 3) + 0.1*torch.eye(nx, device=dev)).contiguous()
+            del Cm
+            lx, lu = rn(T + 1, M, nx), rn(T, M, 6)
+            luu1 = 0.2*torch.eye(6, device=dev)
+            luu = luu1.expand(T, M, 6, 6).contiguous()
+            U = torch.zeros(T, M, 6, device=dev)
+            out = {"k": (T, M, 6), "K": (T, M, 6, nx), "Vx0": (M, nx), "Vxx0": (M, nx, nx), "dV": (M, 2), "du": (T, M, 6), "dx": (T + 1, M, nx)}
+            out = {k: torch.empty(*shape, dtype=torch.float32, device=dev) for k, shape in out.items()}
+            bad = torch.empty(M, dtype=torch.int32, device=dev)
+            io = lib.LqrIO(nx, T, A.data_ptr(), B.data_ptr(), lx.data_ptr(), lxx.data_ptr(), lu.data_ptr(), luu.data_ptr(), None, U.data_ptr(), None, reg, 1.0, -1.0, 1.0,
+                           *[out[k].data_ptr() for k in ("k", "K", "Vx0", "Vxx0", "dV", "du", "dx")], bad.data_ptr())
+            idx = LQR_ARM if nx == 12 else list(range(24))
+            As = A[:, :, idx][:, :, :, idx].contiguous() if nx == 12 else A
+            Bs = B[:, :, idx].contiguous() if nx == 12 else B
+            spans = {}
+
+            def pair(call):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(); call(); e1.record()
+                return e0, e1
+
+            def one_query():
+                rc = L.so100_query_lqr(sim.h, C.byref(io), M, st)
+                assert rc == 0, L.so100_last_error()
+
+            def one_torch():
+                spans["r"] = torch_lqr(As, Bs, lx, lxx, lu, luu1, reg, U)
+
+            def timed(call, n):
+                pairs = [pair(call) for _ in range(n)]
+                torch.cuda.synchronize()
+                return sum(e0.elapsed_time(e1) for e0, e1 in pairs)*1e3/n
+
+            timed(one_query, 2); timed(one_torch, 1)
+            tq, tt = [], []
+            for _ in range(a.rounds):
+                tq.append(timed(one_query, reps)); tt.append(timed(one_torch, loops))
+            kt, Kt, dut = spans["r"]
+            diff = {"k": (out["k"] - kt).abs().max().item(), "K": (out["K"] - Kt).abs().max().item(), "du": (out["du"] - dut).abs().max().item()}
+            mq, mt = statistics.median(tq), statistics.median(tt)
+            words = T*M*(576 + 144 + nx*nx + nx + 6 + 36 + 6) + M*(nx*nx + nx) + T*M*(6 + 6*nx)*2 + T*M*(6 + nx)
+            case = {"form": a.form, "nx": nx, "M": M, "T": T, "lqr_us_per_call": round(mq, 1), "torch_loops_us": round(mt, 1), "lqr_over_torch": round(mq/mt, 4),
+                    "lqr_rounds_us": [round(x, 1) for x in tq], "torch_rounds_us": [round(x, 1) for x in tt], "units_per_round": [reps, loops],
+                    "problem_steps_per_s": round(M*T/(mq*1e-6), 1), "GB_per_s": round(words*4/(mq*1e-6)/1e9, 1),
+                    "largest_difference_to_torch": {k: float(f"{v:.3e}") for k, v in diff.items()}, "bad_problems": int((bad >= 0).sum().item())}
+            doc["cases"].append(case)
+            print(json.dumps(case), flush=True)
+            del A, B, lxx, lx, lu, luu, out, As, Bs, spans
+    sim.close()
+    with open(a.out, "w") as fh:
+        json.dump(doc, fh, indent=1)
+        fh.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None); ap.add_argument("--commit", default="unknown")
@@ -342,10 +456,14 @@ def main():
     ap.add_argument("--forward", action="store_true", help="time the forward-dynamics query against so100_step (profiles/forward_kbench.json)")
     ap.add_argument("--trajectory", action="store_true", help="time the trajectory query against the so100_step calls it predicts (profiles/trajectory_kbench.json)")
     ap.add_argument("--derivatives", action="store_true", help="time the derivatives query against its emulation through the trajectory query (profiles/derivatives_kbench.json)")
+    ap.add_argument("--lqr", action="store_true", help="time the LQR query against the torch loops of examples/ilqr_reach.py (profiles/lqr_kbench.json)")
+    ap.add_argument("--form", default="mfma", help="--lqr: the label of the loaded library's kernel form (mfma, or valu for a -DSO100_LQR_VALU=1 side build)")
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "derivatives_kbench.json" if a.derivatives else "trajectory_kbench.json" if a.trajectory else "forward_kbench.json" if a.forward else "query_kbench.json")
+        a.out = os.path.join(ROOT, "profiles", "lqr_kbench.json" if a.lqr else "derivatives_kbench.json" if a.derivatives else "trajectory_kbench.json" if a.trajectory else "forward_kbench.json" if a.forward else "query_kbench.json")
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    if a.lqr:
+        return lqr_main(a)
     if a.derivatives:
         return derivatives_main(a)
     if a.trajectory:
