@@ -89,16 +89,59 @@ __global__ __launch_bounds__(QUERY_THREADS) void so100_query_ik_k(const float* q
 
 namespace {
 
-// what the four calls check alike and read from the handle: the joint rows (the caller's, or the state matrix's) and their row length
-struct QuerySource { const float* q; int ld; };
-int query_source(const char* fn, const so100_sim* s, const float* q_dev, int32_t M, QuerySource& src) {
+// The checks the entries share (this file's and those of the files so100_sim.hip includes behind it).  Each returns fail()'s code or 0; an entry
+// calls them in the order of its own checks, with what only it checks in between, so the first error of a call is the one its header names.
+
+// the batch size of every query; reads_state: the caller gave no start of its own, so the problems are the handle's N envs
+int query_batch(const char* fn, const so100_sim* s, bool reads_state, int32_t M) {
     const int n = s->prm.n;
     if (M < 1) return fail(SO100_E_INVALID, "%s: M must be >= 1, got %ld", fn, (long)M);
-    if (!q_dev && M != n) return fail(SO100_E_INVALID, "%s: M must be the handle's N (%ld) where its state is read, got %ld", fn, (long)n, (long)M);
-    src.q = q_dev ? q_dev : s->state + (size_t)SF_q0*(size_t)n;
-    src.ld = q_dev ? M : n;
+    if (reads_state && M != n) return fail(SO100_E_INVALID, "%s: M must be the handle's N (%ld) where its state is read, got %ld", fn, (long)n, (long)M);
     return 0;
 }
+// the four original queries start from joint rows (the caller's, or the state matrix's) and their row length
+struct QuerySource { const float* q; int ld; };
+int query_source(const char* fn, const so100_sim* s, const float* q_dev, int32_t M, QuerySource& src) {
+    if (const int rc = query_batch(fn, s, !q_dev, M)) return rc;
+    src.q = q_dev ? q_dev : s->state + (size_t)SF_q0*(size_t)s->prm.n;
+    src.ld = q_dev ? M : s->prm.n;
+    return 0;
+}
+// forward, trajectory and derivatives start from a whole state: the caller's rows (qvel may be null: zero), or the handle's so100_get_state
+// rows, their row length N and the state matrix itself (what a simulation that goes on reads beside qpos and qvel)
+struct QueryStart { const float *qpos, *qvel; int ld; const float* state; };
+int query_start(const char* fn, const so100_sim* s, const float* qpos_dev, const float* qvel_dev, int32_t M, QueryStart& st) {
+    if (const int rc = query_batch(fn, s, !qpos_dev && !qvel_dev, M)) return rc;
+    if (!qpos_dev && qvel_dev) return fail(SO100_E_INVALID, "%s: qvel_dev given without qpos_dev", fn);
+    const size_t n = (size_t)s->prm.n;
+    if (qpos_dev) st = { qpos_dev, qvel_dev, M, nullptr };
+    else st = { s->state + (size_t)SF_QPOS0*n, s->state + (size_t)SF_QVEL0*n, s->prm.n, s->state };
+    return 0;
+}
+int query_control(const char* fn, const float* ctrl_dev, int32_t mode) {
+    if (!ctrl_dev) return fail(SO100_E_INVALID, "%s: ctrl_dev is required", fn);
+    if (mode != SO100_TRAJ_TARGETS && mode != SO100_TRAJ_ACTIONS) return fail(SO100_E_INVALID, "%s: unknown mode %ld", fn, (long)mode);
+    return 0;
+}
+constexpr uint32_t QUERY_FLAGS = SO100_F_FRICTIONLOSS | SO100_F_LIMITS | SO100_F_FLOOR | SO100_F_CUBE_PINNED | SO100_F_PADS_FLOOR | SO100_F_PADS_CUBE |
+                                 SO100_F_LINKS_FLOOR | SO100_F_LINKS_CUBE;
+int query_solver(const char* fn, uint32_t flags, int32_t solver_iters, int32_t contact_iters) {
+    if (flags & ~QUERY_FLAGS) return fail(SO100_E_INVALID, "%s: unknown flag bits", fn);
+    if ((flags & (SO100_F_PADS_CUBE | SO100_F_LINKS_CUBE)) && (flags & SO100_F_CUBE_PINNED))
+        return fail(SO100_E_INVALID, "%s: SO100_F_PADS_CUBE / SO100_F_LINKS_CUBE need a dynamic cube (not SO100_F_CUBE_PINNED)", fn);
+    if (solver_iters < 1 || solver_iters > 64) return fail(SO100_E_INVALID, "%s: solver_iters must be in 1..64, got %ld", fn, (long)solver_iters);
+    if (contact_iters < 1 || contact_iters > 64) return fail(SO100_E_INVALID, "%s: contact_iters must be in 1..64, got %ld", fn, (long)contact_iters);
+    return 0;
+}
+// The flag sets without arm contact that the trajectory and derivatives kernels are also compiled for (their FL): SO100_WITH_QUERY_FLAGS(flags, body)
+// runs `body` with constexpr int FL = that set where `flags` is one of them, else -1 (flags decided at run time), as SO100_WITH_OBS_DIM does with OD.
+constexpr uint32_t QUERY_FL_FREE = SO100_F_CUBE_PINNED, QUERY_FL_ROWS = SO100_F_FRICTIONLOSS | SO100_F_LIMITS | SO100_F_CUBE_PINNED,
+                   QUERY_FL_NOPADS = SO100_F_FRICTIONLOSS | SO100_F_LIMITS | SO100_F_FLOOR;
+#define SO100_WITH_QUERY_FLAGS(flags, ...) do { \
+    if ((flags) == QUERY_FL_FREE) { constexpr int FL = (int)QUERY_FL_FREE; __VA_ARGS__ } \
+    else if ((flags) == QUERY_FL_ROWS) { constexpr int FL = (int)QUERY_FL_ROWS; __VA_ARGS__ } \
+    else if ((flags) == QUERY_FL_NOPADS) { constexpr int FL = (int)QUERY_FL_NOPADS; __VA_ARGS__ } \
+    else { constexpr int FL = -1; __VA_ARGS__ } } while (0)
 int query_point(const char* fn, int32_t link, const float* offset, QueryPoint& pt) {
     if (link < 0 || link > 5) return fail(SO100_E_INVALID, "%s: link must be in 0..5, got %ld", fn, (long)link);
     pt.link = link;

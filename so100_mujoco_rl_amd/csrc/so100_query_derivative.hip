@@ -96,37 +96,22 @@ int so100_query_derivatives(so100_sim* sim, const so100_derivatives_io* io, int3
     using namespace so100;
     const char* const fn = "so100_query_derivatives";
     if (!sim || !io) return fail(SO100_E_INVALID, "so100_query_derivatives: null argument");
-    const int n = sim->prm.n;
-    if (M < 1) return fail(SO100_E_INVALID, "%s: M must be >= 1, got %ld", fn, (long)M);
-    if (!io->qpos_dev && !io->qvel_dev && M != n)
-        return fail(SO100_E_INVALID, "%s: M must be the handle's N (%ld) where its state is read, got %ld", fn, (long)n, (long)M);
-    if (!io->qpos_dev && io->qvel_dev) return fail(SO100_E_INVALID, "%s: qvel_dev given without qpos_dev", fn);
-    if (!io->ctrl_dev) return fail(SO100_E_INVALID, "%s: ctrl_dev is required", fn);
-    if (io->mode != SO100_TRAJ_TARGETS && io->mode != SO100_TRAJ_ACTIONS) return fail(SO100_E_INVALID, "%s: unknown mode %ld", fn, (long)io->mode);
+    QueryStart st;
+    if (const int rc = query_start(fn, sim, io->qpos_dev, io->qvel_dev, M, st)) return rc;
+    if (const int rc = query_control(fn, io->ctrl_dev, io->mode)) return rc;
     if (io->nsub < 1 || io->nsub > SO100_TRAJ_MAX_NSUB)
         return fail(SO100_E_INVALID, "%s: nsub must be in 1..%d, got %ld", fn, SO100_TRAJ_MAX_NSUB, (long)io->nsub);
-    if (io->flags & ~(SO100_F_FRICTIONLOSS | SO100_F_LIMITS | SO100_F_FLOOR | SO100_F_CUBE_PINNED | SO100_F_PADS_FLOOR | SO100_F_PADS_CUBE | SO100_F_LINKS_FLOOR | SO100_F_LINKS_CUBE))
-        return fail(SO100_E_INVALID, "%s: unknown flag bits", fn);
-    if ((io->flags & (SO100_F_PADS_CUBE | SO100_F_LINKS_CUBE)) && (io->flags & SO100_F_CUBE_PINNED))
-        return fail(SO100_E_INVALID, "%s: SO100_F_PADS_CUBE / SO100_F_LINKS_CUBE need a dynamic cube (not SO100_F_CUBE_PINNED)", fn);
-    if (io->solver_iters < 1 || io->solver_iters > 64) return fail(SO100_E_INVALID, "%s: solver_iters must be in 1..64, got %ld", fn, (long)io->solver_iters);
-    if (io->contact_iters < 1 || io->contact_iters > 64) return fail(SO100_E_INVALID, "%s: contact_iters must be in 1..64, got %ld", fn, (long)io->contact_iters);
+    if (const int rc = query_solver(fn, io->flags, io->solver_iters, io->contact_iters)) return rc;
     if (!(io->eps > 0.0f) || !(io->eps*0.0f == 0.0f)) return fail(SO100_E_INVALID, "%s: eps must be finite and > 0, got %g", fn, (double)io->eps);
     if (!io->A_dev && !io->B_dev && !io->qpos_next_dev && !io->qvel_next_dev && !io->bad_dev) return fail(SO100_E_INVALID, "%s: no output requested", fn);
     DerivativeArgs a{};
-    if (io->qpos_dev) { a.qpos = io->qpos_dev; a.qvel = io->qvel_dev; a.ld = M; a.state = nullptr; }
-    else { a.qpos = sim->state + (size_t)SF_QPOS0*(size_t)n; a.qvel = sim->state + (size_t)SF_QVEL0*(size_t)n; a.ld = n; a.state = sim->state; }
+    a.qpos = st.qpos; a.qvel = st.qvel; a.ld = st.ld; a.state = st.state;
     a.ctrl = io->ctrl_dev; a.mode = io->mode; a.nsub = io->nsub; a.flags = io->flags; a.solver_iters = io->solver_iters; a.contact_iters = io->contact_iters;
     a.eps = io->eps; a.r = 0.5f/io->eps;
     a.A = io->A_dev; a.B = io->B_dev; a.qpos_next = io->qpos_next_dev; a.qvel_next = io->qvel_next_dev; a.bad = io->bad_dev;
     SO100_ON_DEVICE(sim->cfg.device, "so100_query_derivatives");
     const dim3 grid((unsigned)M), block(64);                 // one wave per problem
-    constexpr unsigned FREE = SO100_F_CUBE_PINNED, ROWS = SO100_F_FRICTIONLOSS | SO100_F_LIMITS | SO100_F_CUBE_PINNED,
-                       NOPADS = SO100_F_FRICTIONLOSS | SO100_F_LIMITS | SO100_F_FLOOR;
-    if (io->flags == FREE)        hipLaunchKernelGGL((so100_query_derivative_k<(int)FREE>), grid, block, 0, (hipStream_t)stream, a, M);
-    else if (io->flags == ROWS)   hipLaunchKernelGGL((so100_query_derivative_k<(int)ROWS>), grid, block, 0, (hipStream_t)stream, a, M);
-    else if (io->flags == NOPADS) hipLaunchKernelGGL((so100_query_derivative_k<(int)NOPADS>), grid, block, 0, (hipStream_t)stream, a, M);
-    else                          hipLaunchKernelGGL((so100_query_derivative_k<-1>), grid, block, 0, (hipStream_t)stream, a, M);
+    SO100_WITH_QUERY_FLAGS(io->flags, hipLaunchKernelGGL((so100_query_derivative_k<FL>), grid, block, 0, (hipStream_t)stream, a, M););
     HIP_TRY(hipGetLastError(), SO100_E_LAUNCH);
     return 0;
 }

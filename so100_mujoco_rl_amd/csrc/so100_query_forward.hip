@@ -85,23 +85,14 @@ int so100_query_forward(so100_sim* sim, const so100_forward_io* io, int32_t M, v
     using namespace so100;
     const char* const fn = "so100_query_forward";
     if (!sim || !io) return fail(SO100_E_INVALID, "so100_query_forward: null argument");
-    const int n = sim->prm.n;
-    if (M < 1) return fail(SO100_E_INVALID, "%s: M must be >= 1, got %ld", fn, (long)M);
-    if (!io->qpos_dev && !io->qvel_dev && M != n)
-        return fail(SO100_E_INVALID, "%s: M must be the handle's N (%ld) where its state is read, got %ld", fn, (long)n, (long)M);
-    if (!io->qpos_dev && io->qvel_dev) return fail(SO100_E_INVALID, "%s: qvel_dev given without qpos_dev", fn);
-    if (io->flags & ~(SO100_F_FRICTIONLOSS | SO100_F_LIMITS | SO100_F_FLOOR | SO100_F_CUBE_PINNED | SO100_F_PADS_FLOOR | SO100_F_PADS_CUBE | SO100_F_LINKS_FLOOR | SO100_F_LINKS_CUBE))
-        return fail(SO100_E_INVALID, "%s: unknown flag bits", fn);
-    if ((io->flags & (SO100_F_PADS_CUBE | SO100_F_LINKS_CUBE)) && (io->flags & SO100_F_CUBE_PINNED))
-        return fail(SO100_E_INVALID, "%s: SO100_F_PADS_CUBE / SO100_F_LINKS_CUBE need a dynamic cube (not SO100_F_CUBE_PINNED)", fn);
-    if (io->solver_iters < 1 || io->solver_iters > 64) return fail(SO100_E_INVALID, "%s: solver_iters must be in 1..64, got %ld", fn, (long)io->solver_iters);
-    if (io->contact_iters < 1 || io->contact_iters > 64) return fail(SO100_E_INVALID, "%s: contact_iters must be in 1..64, got %ld", fn, (long)io->contact_iters);
+    QueryStart st;
+    if (const int rc = query_start(fn, sim, io->qpos_dev, io->qvel_dev, M, st)) return rc;
+    if (const int rc = query_solver(fn, io->flags, io->solver_iters, io->contact_iters)) return rc;
     if (!io->qacc_dev && !io->qfrc_constraint_dev && !io->ncon_dev && !io->dropped_dev && !io->con_kind_dev && !io->con_feat_dev && !io->con_pos_dev &&
         !io->con_frame_dev && !io->con_dist_dev && !io->con_force_dev && !io->pad_force_dev && !io->residual_dev)
         return fail(SO100_E_INVALID, "%s: no output requested", fn);
     ForwardArgs a{};
-    if (io->qpos_dev) { a.qpos = io->qpos_dev; a.qvel = io->qvel_dev; a.ld = M; }
-    else { a.qpos = sim->state + (size_t)SF_QPOS0*(size_t)n; a.qvel = sim->state + (size_t)SF_QVEL0*(size_t)n; a.ld = n; }
+    a.qpos = st.qpos; a.qvel = st.qvel; a.ld = st.ld;
     a.ctrl = io->ctrl_dev; a.flags = io->flags; a.solver_iters = io->solver_iters; a.contact_iters = io->contact_iters;
     a.qacc = io->qacc_dev; a.qfrc = io->qfrc_constraint_dev; a.ncon = io->ncon_dev; a.dropped = io->dropped_dev; a.kind = io->con_kind_dev; a.feat = io->con_feat_dev;
     a.pos = io->con_pos_dev; a.frame = io->con_frame_dev; a.dist = io->con_dist_dev; a.force = io->con_force_dev; a.pad_force = io->pad_force_dev;

@@ -275,7 +275,7 @@ int so100_query_lqr(so100_sim* sim, const so100_lqr_io* io, int32_t M, void* str
     using namespace so100;
     const char* const fn = "so100_query_lqr";
     if (!sim || !io) return fail(SO100_E_INVALID, "so100_query_lqr: null argument");
-    if (M < 1) return fail(SO100_E_INVALID, "%s: M must be >= 1, got %ld", fn, (long)M);
+    if (const int rc = query_batch(fn, sim, false, M)) return rc;                 // no state is read: any M >= 1
     if (io->nx != 12 && io->nx != 24) return fail(SO100_E_INVALID, "%s: nx must be 12 or 24, got %ld", fn, (long)io->nx);
     if (io->T < 1 || io->T > SO100_LQR_MAX_T) return fail(SO100_E_INVALID, "%s: T must be in 1..%d, got %ld", fn, SO100_LQR_MAX_T, (long)io->T);
     if (!io->A_dev || !io->B_dev || !io->lx_dev || !io->lxx_dev) return fail(SO100_E_INVALID, "%s: A_dev, B_dev, lx_dev and lxx_dev are required", fn);

@@ -103,39 +103,24 @@ int so100_query_trajectory(so100_sim* sim, const so100_trajectory_io* io, int32_
     using namespace so100;
     const char* const fn = "so100_query_trajectory";
     if (!sim || !io) return fail(SO100_E_INVALID, "so100_query_trajectory: null argument");
-    const int n = sim->prm.n;
-    if (M < 1) return fail(SO100_E_INVALID, "%s: M must be >= 1, got %ld", fn, (long)M);
-    if (!io->qpos_dev && !io->qvel_dev && M != n)
-        return fail(SO100_E_INVALID, "%s: M must be the handle's N (%ld) where its state is read, got %ld", fn, (long)n, (long)M);
-    if (!io->qpos_dev && io->qvel_dev) return fail(SO100_E_INVALID, "%s: qvel_dev given without qpos_dev", fn);
-    if (!io->ctrl_dev) return fail(SO100_E_INVALID, "%s: ctrl_dev is required", fn);
-    if (io->mode != SO100_TRAJ_TARGETS && io->mode != SO100_TRAJ_ACTIONS) return fail(SO100_E_INVALID, "%s: unknown mode %ld", fn, (long)io->mode);
+    QueryStart st;
+    if (const int rc = query_start(fn, sim, io->qpos_dev, io->qvel_dev, M, st)) return rc;
+    if (const int rc = query_control(fn, io->ctrl_dev, io->mode)) return rc;
     if (io->T < 1 || io->T > SO100_TRAJ_MAX_T || io->nsub < 1 || io->nsub > SO100_TRAJ_MAX_NSUB || (long)io->T*(long)io->nsub > SO100_TRAJ_MAX_SUBSTEPS)
         return fail(SO100_E_INVALID, "%s: T must be in 1..%d, nsub in 1..%d and T * nsub <= %d, got T = %ld, nsub = %ld", fn, SO100_TRAJ_MAX_T, SO100_TRAJ_MAX_NSUB,
                     SO100_TRAJ_MAX_SUBSTEPS, (long)io->T, (long)io->nsub);
-    if (io->flags & ~(SO100_F_FRICTIONLOSS | SO100_F_LIMITS | SO100_F_FLOOR | SO100_F_CUBE_PINNED | SO100_F_PADS_FLOOR | SO100_F_PADS_CUBE | SO100_F_LINKS_FLOOR | SO100_F_LINKS_CUBE))
-        return fail(SO100_E_INVALID, "%s: unknown flag bits", fn);
-    if ((io->flags & (SO100_F_PADS_CUBE | SO100_F_LINKS_CUBE)) && (io->flags & SO100_F_CUBE_PINNED))
-        return fail(SO100_E_INVALID, "%s: SO100_F_PADS_CUBE / SO100_F_LINKS_CUBE need a dynamic cube (not SO100_F_CUBE_PINNED)", fn);
-    if (io->solver_iters < 1 || io->solver_iters > 64) return fail(SO100_E_INVALID, "%s: solver_iters must be in 1..64, got %ld", fn, (long)io->solver_iters);
-    if (io->contact_iters < 1 || io->contact_iters > 64) return fail(SO100_E_INVALID, "%s: contact_iters must be in 1..64, got %ld", fn, (long)io->contact_iters);
+    if (const int rc = query_solver(fn, io->flags, io->solver_iters, io->contact_iters)) return rc;
     if (!io->qpos_traj_dev && !io->qvel_traj_dev && !io->ee_traj_dev && !io->qpos_final_dev && !io->qvel_final_dev && !io->ncon_dev && !io->dropped_dev &&
         !io->sig_dev && !io->residual_dev && !io->bad_step_dev)
         return fail(SO100_E_INVALID, "%s: no output requested", fn);
     TrajectoryArgs a{};
-    if (io->qpos_dev) { a.qpos = io->qpos_dev; a.qvel = io->qvel_dev; a.ld = M; a.state = nullptr; }
-    else { a.qpos = sim->state + (size_t)SF_QPOS0*(size_t)n; a.qvel = sim->state + (size_t)SF_QVEL0*(size_t)n; a.ld = n; a.state = sim->state; }
+    a.qpos = st.qpos; a.qvel = st.qvel; a.ld = st.ld; a.state = st.state;
     a.ctrl = io->ctrl_dev; a.mode = io->mode; a.T = io->T; a.nsub = io->nsub; a.flags = io->flags; a.solver_iters = io->solver_iters; a.contact_iters = io->contact_iters;
     a.qpos_traj = io->qpos_traj_dev; a.qvel_traj = io->qvel_traj_dev; a.ee_traj = io->ee_traj_dev; a.qpos_final = io->qpos_final_dev; a.qvel_final = io->qvel_final_dev;
     a.ncon = io->ncon_dev; a.dropped = io->dropped_dev; a.sig = io->sig_dev; a.residual = io->residual_dev; a.bad_step = io->bad_step_dev;
     SO100_ON_DEVICE(sim->cfg.device, "so100_query_trajectory");
     const dim3 grid((unsigned)(((size_t)M + WG - 1)/WG)), block(WG);
-    constexpr unsigned FREE = SO100_F_CUBE_PINNED, ROWS = SO100_F_FRICTIONLOSS | SO100_F_LIMITS | SO100_F_CUBE_PINNED,
-                       NOPADS = SO100_F_FRICTIONLOSS | SO100_F_LIMITS | SO100_F_FLOOR;
-    if (io->flags == FREE)        hipLaunchKernelGGL((so100_query_trajectory_k<(int)FREE>), grid, block, 0, (hipStream_t)stream, a, M);
-    else if (io->flags == ROWS)   hipLaunchKernelGGL((so100_query_trajectory_k<(int)ROWS>), grid, block, 0, (hipStream_t)stream, a, M);
-    else if (io->flags == NOPADS) hipLaunchKernelGGL((so100_query_trajectory_k<(int)NOPADS>), grid, block, 0, (hipStream_t)stream, a, M);
-    else                          hipLaunchKernelGGL((so100_query_trajectory_k<-1>), grid, block, 0, (hipStream_t)stream, a, M);
+    SO100_WITH_QUERY_FLAGS(io->flags, hipLaunchKernelGGL((so100_query_trajectory_k<FL>), grid, block, 0, (hipStream_t)stream, a, M););
     HIP_TRY(hipGetLastError(), SO100_E_LAUNCH);
     return 0;
 }

@@ -295,6 +295,11 @@ def _ptr(t, dtype, shape, device):
     return t.data_ptr()
 
 
+def _optr(t):
+    """pointer of a tensor the caller has already laid out, or None (a null pointer: the argument is optional)"""
+    return None if t is None else t.data_ptr()
+
+
 def _resolve_device(device, what, hip_only=False):
     """the torch.device (with its ordinal) a handle lives on: `device`, or torch's current HIP device where it names none"""
     if not torch.cuda.is_available():
@@ -616,7 +621,7 @@ class So100Sim(_Handle):
         end-effector point, "cam_pos" [M, 3] and "cam_mat" [M, 3, 3] of the wrist camera."""
         qs = self._soa(q, 6, "q"); M = self._problems(qs)
         xpos, xmat, ee, cp, cm = self._out(M, 6, 3), self._out(M, 6, 9), self._out(M, 3), self._out(M, 3), self._out(M, 9)
-        io = KinematicsIO(qs.data_ptr() if qs is not None else None, xpos.data_ptr(), xmat.data_ptr(), ee.data_ptr(), cp.data_ptr(), cm.data_ptr())
+        io = KinematicsIO(_optr(qs), xpos.data_ptr(), xmat.data_ptr(), ee.data_ptr(), cp.data_ptr(), cm.data_ptr())
         _check(self.L.so100_query_kinematics(self.h, C.byref(io), M, self._stream()), "so100_query_kinematics")
         return {"xpos": xpos.permute(2, 0, 1), "xmat": xmat.permute(2, 0, 1).unflatten(2, (3, 3)), "ee": ee.t(), "cam_pos": cp.t(),
                 "cam_mat": cm.t().unflatten(1, (3, 3))}
@@ -627,7 +632,7 @@ class So100Sim(_Handle):
         qs = self._soa(q, 6, "q"); M = self._problems(qs)
         jp, jr = self._out(M, 3, 6), self._out(M, 3, 6)
         off = self._offset(offset)
-        io = JacobianIO(qs.data_ptr() if qs is not None else None, link, C.cast(off, C.c_void_p) if off is not None else None, jp.data_ptr(), jr.data_ptr())
+        io = JacobianIO(_optr(qs), link, C.cast(off, C.c_void_p) if off is not None else None, jp.data_ptr(), jr.data_ptr())
         _check(self.L.so100_query_jacobian(self.h, C.byref(io), M, self._stream()), "so100_query_jacobian")
         return {"jacp": jp.permute(2, 0, 1), "jacr": jr.permute(2, 0, 1)}
 
@@ -638,7 +643,7 @@ class So100Sim(_Handle):
         qs, vs, acs = self._soa(q, 6, "q"), self._soa(v, 6, "v"), self._soa(qacc, 6, "qacc"); M = self._problems(qs, vs, acs)
         Mm, bias = self._out(M, 36), self._out(M, 6)
         tau = self._out(M, 6) if acs is not None else None
-        io = DynamicsIO(*[t.data_ptr() if t is not None else None for t in (qs, vs, acs, Mm, bias, tau)])
+        io = DynamicsIO(*[_optr(t) for t in (qs, vs, acs, Mm, bias, tau)])
         _check(self.L.so100_query_dynamics(self.h, C.byref(io), M, self._stream()), "so100_query_dynamics")
         res = {"M": Mm.t().unflatten(1, (6, 6)), "bias": bias.t()}
         if tau is not None:
@@ -652,7 +657,7 @@ class So100Sim(_Handle):
         ts, qs = self._soa(target, 3, "target"), self._soa(q0, 6, "q0"); M = self._problems(ts, qs)
         q, res, its, conv = self._out(M, 6), self._out(M), self._out(M, dtype=torch.int32), self._out(M, dtype=torch.uint8)
         off = self._offset(offset)
-        io = IkIO(ts.data_ptr(), qs.data_ptr() if qs is not None else None, link, C.cast(off, C.c_void_p) if off is not None else None, iters, damping,
+        io = IkIO(ts.data_ptr(), _optr(qs), link, C.cast(off, C.c_void_p) if off is not None else None, iters, damping,
                   tol, max_step, q.data_ptr(), res.data_ptr(), its.data_ptr(), conv.data_ptr())
         _check(self.L.so100_query_ik(self.h, C.byref(io), M, self._stream()), "so100_query_ik")
         return {"q": q.t(), "residual": res, "iterations": its, "converged": conv}
@@ -669,7 +674,7 @@ class So100Sim(_Handle):
         qacc, qfrc, ncon, drop, res, pf = self._out(M, 12), self._out(M, 12), self._out(M, **i32), self._out(M, **i32), self._out(M), self._out(M, 8)
         kind, feat, pos = self._out(M, FWD_MAXCON, **i32), self._out(M, FWD_MAXCON, **i32), self._out(M, FWD_MAXCON, 3)
         frame, dist, force = self._out(M, FWD_MAXCON, 9), self._out(M, FWD_MAXCON), self._out(M, FWD_MAXCON, 3)
-        io = ForwardIO(*[t.data_ptr() if t is not None else None for t in (qs, vs, us)], self.cfg.flags if flags is None else flags, solver_iters,
+        io = ForwardIO(*[_optr(t) for t in (qs, vs, us)], self.cfg.flags if flags is None else flags, solver_iters,
                        contact_iters, *[t.data_ptr() for t in (qacc, qfrc, ncon, drop, kind, feat, pos, frame, dist, force, pf, res)])
         _check(self.L.so100_query_forward(self.h, C.byref(io), M, self._stream()), "so100_query_forward")
         return {"qacc": qacc.t(), "qfrc_constraint": qfrc.t(), "ncon": ncon, "dropped": drop, "residual": res, "pad_force": pf.t(),
@@ -698,7 +703,7 @@ class So100Sim(_Handle):
         qt, vt, et = self._out(M, T, 13), self._out(M, T, 12), self._out(M, T, 3)
         ncon, drop, sig, res, bad = self._out(M, T, **i32), self._out(M, T, **i32), self._out(M, T, **i32), self._out(M, T), self._out(M, **i32)
         c = self.cfg
-        io = TrajectoryIO(qs.data_ptr() if qs is not None else None, vs.data_ptr() if vs is not None else None, us.data_ptr(), TRAJ_MODES[mode], T,
+        io = TrajectoryIO(_optr(qs), _optr(vs), us.data_ptr(), TRAJ_MODES[mode], T,
                           c.frame_skip if nsub is None else nsub, c.flags if flags is None else flags,
                           c.solver_iters if solver_iters is None else solver_iters, c.contact_iters if contact_iters is None else contact_iters,
                           qt.data_ptr(), vt.data_ptr(), et.data_ptr(), None, None, ncon.data_ptr(), drop.data_ptr(), sig.data_ptr(), res.data_ptr(), bad.data_ptr())
@@ -721,7 +726,7 @@ class So100Sim(_Handle):
         B = torch.empty(M, DERIV_NX, DERIV_NU, dtype=torch.float32, device=self.device)
         qn, vn, bad = self._out(M, 13), self._out(M, 12), self._out(M, dtype=torch.int32)
         c = self.cfg
-        io = DerivativesIO(qs.data_ptr() if qs is not None else None, vs.data_ptr() if vs is not None else None, us.data_ptr(), TRAJ_MODES[mode],
+        io = DerivativesIO(_optr(qs), _optr(vs), us.data_ptr(), TRAJ_MODES[mode],
                            c.frame_skip if nsub is None else nsub, c.flags if flags is None else flags,
                            c.solver_iters if solver_iters is None else solver_iters, c.contact_iters if contact_iters is None else contact_iters,
                            DERIV_EPS if eps is None else eps, A.data_ptr(), B.data_ptr(), qn.data_ptr(), vn.data_ptr(), bad.data_ptr())
@@ -751,8 +756,7 @@ class So100Sim(_Handle):
         new = lambda *shape, **kw: torch.empty(*shape, dtype=kw.get("dtype", torch.float32), device=self.device)
         out = {"k": new(T, M, 6), "K": new(T, M, 6, n), "Vx0": new(M, n), "Vxx0": new(M, n, n), "dV": new(M, 2), "du": new(T, M, 6),
                "dx": new(T + 1, M, n), "bad": new(M, dtype=torch.int32)}
-        ptr = lambda t: t.data_ptr() if t is not None else None
-        io = LqrIO(n, T, *[ptr(t) for t in (A, B, lx, lxx, lu, luu, lux, u, dx0)], reg, alpha, u_lo, u_hi,
+        io = LqrIO(n, T, *[_optr(t) for t in (A, B, lx, lxx, lu, luu, lux, u, dx0)], reg, alpha, u_lo, u_hi,
                    *[out[name].data_ptr() for name in ("k", "K", "Vx0", "Vxx0", "dV", "du", "dx", "bad")])
         _check(self.L.so100_query_lqr(self.h, C.byref(io), M, self._stream()), "so100_query_lqr")
         return out

@@ -1,5 +1,5 @@
 // derivcheck.cpp -- the derivatives query of so100_derivative.hpp on the host, in double (held to the fp64 oracle) and in float (the arithmetic
-// the kernel ships, without FMA contraction), behind a C interface for ctypes (built by the Makefile beside it, loaded and called by
+// the kernel ships, without FMA contraction), behind a C interface for ctypes (built by tests/Makefile, loaded by tests/hostlibs.py, called by
 // tests/derivatives_support.py).  The same templates as the kernel, with a loop over the 61 roles where the kernel has lanes.  Arrays are
 // problem-major (qpos [n][13], ctrl [n][6], A [n][24][24], B [n][24][6]); warm: null for a cold start, or [n][31] as in trajcheck.cpp.
 // Test scaffolding only.

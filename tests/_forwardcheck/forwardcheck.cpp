@@ -1,6 +1,6 @@
 // forwardcheck.cpp -- the forward-dynamics query of so100_forward.hpp on the host, in double (held to the fp64 oracle) and in float (the
 // arithmetic the kernel ships, without FMA contraction), with a group of one lane per problem, behind a C interface for ctypes
-// (built by the Makefile beside it, loaded and called by tests/forward_support.py).  Arrays are problem-major here ([n][k]); the SoA layout is the kernel's matter.
+// (built by tests/Makefile, loaded by tests/hostlibs.py, called by tests/forward_support.py).  Arrays are problem-major here ([n][k]); the SoA layout is the kernel's matter.
 // Test scaffolding only.
 #include <stdint.h>
 #include "../../so100_mujoco_rl_amd/csrc/so100_forward.hpp"

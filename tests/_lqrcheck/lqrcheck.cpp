@@ -1,6 +1,6 @@
 // lqrcheck.cpp -- the LQR query's recursion (lqr_problem of so100_lqr.hpp) on the host, in double (held to the numpy fp64 reference) and in
-// float (the arithmetic the kernel ships, without FMA contraction), behind a C interface for ctypes (built by the Makefile beside it, loaded
-// and called by tests/lqr_support.py).  Arrays as in include/so100_query.h: A [T][M][24][24], B [T][M][24][6], the rest problem-major in the
+// float (the arithmetic the kernel ships, without FMA contraction), behind a C interface for ctypes (built by tests/Makefile, loaded by tests/hostlibs.py,
+// called by tests/lqr_support.py).  Arrays as in include/so100_query.h: A [T][M][24][24], B [T][M][24][6], the rest problem-major in the
 // n of the call; nullable where the header says so.  Test scaffolding only.
 #include <stdint.h>
 #include "../../so100_mujoco_rl_amd/csrc/so100_lqr.hpp"

@@ -1,5 +1,5 @@
 // trajcheck.cpp -- the trajectory query of so100_trajectory.hpp on the host, in double (held to the fp64 oracle) and in float (the arithmetic
-// the kernel ships, without FMA contraction), behind a C interface for ctypes (built by the Makefile beside it, loaded and called by
+// the kernel ships, without FMA contraction), behind a C interface for ctypes (built by tests/Makefile, loaded by tests/hostlibs.py, called by
 // tests/trajectory_support.py).  Arrays are problem-major here (qpos [n][13], ctrl [T][n][6], trajectories [T][n][k]); the SoA layout is the
 // kernel's matter.  warm: null for a cold start, or [n][31] = ff 6, fl 6, cube.warm 6, qc 6, aw 6, lift 1 (the rows the kernel reads from a handle).
 // Test scaffolding only.

@@ -8,14 +8,12 @@ product, its rotation rows through mju_subQuat).  Neither the twin nor the kerne
 computed once per process and never modified."""
 import ctypes as C
 import functools
-import os
-import subprocess
 
 import numpy as np
 
 import scenes
 import trajectory_support as TS
-from hostlibs import ptr
+from hostlibs import derivcheck, ptr
 from oracle import so100_oracle as O
 
 L, M = scenes.L, scenes.M
@@ -23,24 +21,6 @@ NX, NU, NCOL = 24, 6, 30
 EPS = 2.0**-6                                              # SO100_DERIV_EPS
 ITERS = (64, 64)                                           # the smooth families: every evaluation starts cold (trajectory_support.PARITY_ITERS)
 NSUB = 16
-
-# ---- the host twin: tests/_derivcheck/libderivcheck.so, built by that directory's own Makefile ---------------------------------------------------
-DERIVCHECK_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_derivcheck")
-_p, _i, _u, _l, _f, _d = C.c_void_p, C.c_int, C.c_uint, C.c_long, C.c_float, C.c_double
-# name: (restype, argtypes) of every exported symbol, as tests/hostlibs.py declares them for the other twins
-DERIVCHECK = {"dc_derivatives_d": (None, [_l] + [_p]*4 + [_i, _i, _u, _i, _i, _d] + [_p]*5),
-              "dc_derivatives_f": (None, [_l] + [_p]*4 + [_i, _i, _u, _i, _i, _f] + [_p]*5)}
-
-
-@functools.lru_cache(maxsize=None)
-def derivcheck():
-    """the twin, made and loaded once per process"""
-    subprocess.check_call(["make", "-C", DERIVCHECK_DIR, "-s", "libderivcheck.so"])
-    lib = C.CDLL(os.path.join(DERIVCHECK_DIR, "libderivcheck.so"))
-    for name, (restype, argtypes) in DERIVCHECK.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = restype, argtypes
-    return lib
 
 
 def twin(ctrl, qpos, qvel=None, mode="targets", nsub=NSUB, flags=scenes.REFP, dtype=np.float32, solver_iters=2, contact_iters=20, eps=EPS, warm=None):

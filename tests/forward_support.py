@@ -7,14 +7,12 @@ substep_harness.knife_edge / knife_edge_records says so under RandomState(1): bo
 classification are computed once per process and never modified."""
 import ctypes as C
 import functools
-import os
-import subprocess
 
 import numpy as np
 
 import scenes
 import substep_harness as H
-from hostlibs import ptr
+from hostlibs import forwardcheck, ptr
 from oracle import so100_oracle as O
 
 L, M = scenes.L, scenes.M
@@ -30,26 +28,6 @@ EVERY = 4
 QUANTITIES = ("con_pos", "con_frame", "con_dist", "con_force", "pad_force", "qacc", "qfrc_constraint")
 FORCE_QUANTITIES = ("con_force", "pad_force")          # a problem's error is divided by 1 N + the sum of its oracle normal forces
 NEWTON_TOL = {np.float64: 1e-10, np.float32: 1e-3}    # a residual is 0 (converged) or the last step's size: below primal_newton's `small` test
-
-
-# ---- the host twin: tests/_forwardcheck/libforwardcheck.so, built by that directory's own Makefile (the recipe of tests/Makefile) ----------------
-FORWARDCHECK_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_forwardcheck")
-_p, _i, _u, _l = C.c_void_p, C.c_int, C.c_uint, C.c_long
-# name: (restype, argtypes) of every exported symbol, as tests/hostlibs.py declares them for the other twins
-FORWARDCHECK = {
-    "fc_forward_d": (None, [_l] + [_p]*3 + [_u, _i, _i] + [_p]*12), "fc_forward_f": (None, [_l] + [_p]*3 + [_u, _i, _i] + [_p]*12),
-}
-
-
-@functools.lru_cache(maxsize=None)
-def forwardcheck():
-    """the twin, made and loaded once per process"""
-    subprocess.check_call(["make", "-C", FORWARDCHECK_DIR, "-s", "libforwardcheck.so"])
-    lib = C.CDLL(os.path.join(FORWARDCHECK_DIR, "libforwardcheck.so"))
-    for name, (restype, argtypes) in FORWARDCHECK.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = restype, argtypes
-    return lib
 
 
 def decode(f):

@@ -1,7 +1,9 @@
 """The one place that builds and loads the host twins of the device code: tests/_hostcheck/libhostcheck.so (physics, contacts, task
 layer, random draws), tests/_rendercheck/librendercheck.so (render), tests/_learncheck/liblearncheck.so (the learner: lc_ its arithmetic,
-rn_ reward normalisation, on_ observation normalisation, sc_ the shuffle; four sources, one library) and tests/_querycheck/libquerycheck.so
-(the model queries).  tests/Makefile is the one recipe for all of them.  Each is made once per process and cached; argtypes and restype are declared here for EVERY exported symbol (tests/test_hostlibs.py holds
+rn_ reward normalisation, on_ observation normalisation, sc_ the shuffle; four sources, one library), tests/_querycheck/libquerycheck.so
+(the four original model queries) and one library each for the later queries: tests/_forwardcheck/libforwardcheck.so (forward dynamics),
+tests/_trajcheck/libtrajcheck.so (trajectory), tests/_derivcheck/libderivcheck.so (derivatives) and tests/_lqrcheck/liblqrcheck.so (LQR).
+tests/Makefile is the one recipe for all of them.  Each is made once per process and cached; argtypes and restype are declared here for EVERY exported symbol (tests/test_hostlibs.py holds
 the tables to the extern "C" definitions), so that no call depends on which test ran first: a `long` result without its restype is
 silently cut to 32 bits, a Python float without argtypes raises."""
 import ctypes as C
@@ -71,6 +73,15 @@ QUERYCHECK = {
     "qc_ik_d": (None, [_l, _p, _p, _i, _p, _i, _d, _d, _d] + [_p]*4), "qc_ik_f": (None, [_l, _p, _p, _i, _p, _i, _f, _f, _f] + [_p]*4),
     "qc_joint_range": (None, [_p]),
 }
+FORWARDCHECK = {
+    "fc_forward_d": (None, [_l] + [_p]*3 + [_u, _i, _i] + [_p]*12), "fc_forward_f": (None, [_l] + [_p]*3 + [_u, _i, _i] + [_p]*12),
+}
+_SIG = (None, [_l] + [_p]*4 + [_i, _i, _i, _u, _i, _i] + [_p]*10)
+TRAJCHECK = {"tc_trajectory_d": _SIG, "tc_trajectory_f": _SIG}
+DERIVCHECK = {"dc_derivatives_d": (None, [_l] + [_p]*4 + [_i, _i, _u, _i, _i, _d] + [_p]*5),
+              "dc_derivatives_f": (None, [_l] + [_p]*4 + [_i, _i, _u, _i, _i, _f] + [_p]*5)}
+LQRCHECK = {"lq_lqr_d": (None, [_l, _i, _i] + [_p]*9 + [_d]*4 + [_p]*8),
+            "lq_lqr_f": (None, [_l, _i, _i] + [_p]*9 + [_f]*4 + [_p]*8)}
 
 _libs = {}
 
@@ -105,6 +116,22 @@ def learncheck():
 
 def querycheck():
     return _load("_querycheck/libquerycheck.so", QUERYCHECK)
+
+
+def forwardcheck():
+    return _load("_forwardcheck/libforwardcheck.so", FORWARDCHECK)
+
+
+def trajcheck():
+    return _load("_trajcheck/libtrajcheck.so", TRAJCHECK)
+
+
+def derivcheck():
+    return _load("_derivcheck/libderivcheck.so", DERIVCHECK)
+
+
+def lqrcheck():
+    return _load("_lqrcheck/liblqrcheck.so", LQRCHECK)
 
 
 def ptr(a):

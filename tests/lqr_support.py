@@ -5,39 +5,18 @@ References.  (1) reference(): the recursion of include/so100_query.h in numpy fp
 device sees them.  (2) dense_minimiser(): independent of any recursion -- dx = S du condensed, the 6T x 6T Hessian and gradient of the
 quadratic model assembled, one np.linalg.solve; with reg = 0, alpha = 1, no bounds and dx0 = 0 the forward pass's du must equal it.
 Neither the twin nor the kernel is ever its own reference.  Inputs and references are computed once per process and never modified."""
-import ctypes as C
 import functools
-import os
-import subprocess
 
 import numpy as np
 
 import trajectory_support as TS
-from hostlibs import ptr
+from hostlibs import lqrcheck, ptr
 
 NU = 6
 ARM = np.r_[0:6, 12:18]                                    # the arm block of the 24 tangent indices: nx = 12
 IDX = {24: np.arange(24), 12: ARM}
 FLOAT_OUT = ("k", "K", "Vx0", "Vxx0", "dV", "du", "dx")
 OUT = FLOAT_OUT + ("bad",)
-
-# ---- the host twin: tests/_lqrcheck/liblqrcheck.so, built by that directory's own Makefile ----------------------------------------------------------
-LQRCHECK_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_lqrcheck")
-_p, _i, _l, _f, _d = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_double
-# name: (restype, argtypes) of every exported symbol, as tests/hostlibs.py declares them for the other twins
-LQRCHECK = {"lq_lqr_d": (None, [_l, _i, _i] + [_p]*9 + [_d]*4 + [_p]*8),
-            "lq_lqr_f": (None, [_l, _i, _i] + [_p]*9 + [_f]*4 + [_p]*8)}
-
-
-@functools.lru_cache(maxsize=None)
-def lqrcheck():
-    """the twin, made and loaded once per process"""
-    subprocess.check_call(["make", "-C", LQRCHECK_DIR, "-s", "liblqrcheck.so"])
-    lib = C.CDLL(os.path.join(LQRCHECK_DIR, "liblqrcheck.so"))
-    for name, (restype, argtypes) in LQRCHECK.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = restype, argtypes
-    return lib
 
 
 def problem(A, B, lx, lxx, lu=None, luu=None, lux=None, nx=24, reg=0.0, alpha=1.0, u=None, u_lo=-1.0, u_hi=1.0, dx0=None):

@@ -73,28 +73,6 @@ def test_null_arguments_are_refused_without_a_device():
     assert L.so100_last_error() == b"so100_query_derivatives: null argument"
 
 
-def test_signature_table_matches_the_source(monkeypatch):
-    """derivatives_support.DERIVCHECK against the extern "C" definitions of derivcheck.cpp, parsed by tests/test_hostlibs.py's parser (told the prefix)"""
-    import test_hostlibs as TH
-    monkeypatch.setattr(TH, "PREFIXES", "dc")
-    want = TH.defined_symbols(os.path.join(S.DERIVCHECK_DIR, "derivcheck.cpp"))
-    assert sorted(want) == sorted(S.DERIVCHECK) and len(want) == 2
-    lib = S.derivcheck()
-    for name, (restype, argtypes) in want.items():
-        fn = getattr(lib, name)
-        assert list(fn.argtypes) == argtypes and fn.restype is restype, name
-
-
-def test_selftest_program_builds_and_passes(tmp_path):
-    """make -C tests/_derivcheck selftest without a sanitizer: the stand-alone program is built into tmp_path, runs, and reports ok (so that it
-    stays buildable for a host sanitizer run outside Python)"""
-    import subprocess
-    run = subprocess.run(["make", "-C", S.DERIVCHECK_DIR, "-s", "selftest", f"BUILD={tmp_path}"], capture_output=True, text=True)
-    assert run.returncode == 0, run.stdout + run.stderr
-    for precision in ("double", "float"):
-        assert re.search(r"derivcheck selftest \(%s\):.*: ok$" % precision, run.stdout, flags=re.M), run.stdout
-
-
 # ---- A: the smooth families against the oracle's secant ---------------------------------------------------------------------------------------------
 def rows_deviation(got, ref, rows):
     d = np.abs(np.concatenate([got["A"], got["B"]], axis=2) - np.concatenate([ref["A"], ref["B"]], axis=2))[:, rows]

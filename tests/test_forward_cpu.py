@@ -53,28 +53,6 @@ def test_null_arguments_are_refused_without_a_device():
     assert L.so100_last_error() == b"so100_query_forward: null argument"
 
 
-def test_signature_table_matches_the_source(monkeypatch):
-    """forward_support.FORWARDCHECK against the extern "C" definitions of forwardcheck.cpp, parsed by tests/test_hostlibs.py's parser (told the prefix)"""
-    import test_hostlibs as TH
-    monkeypatch.setattr(TH, "PREFIXES", "fc")
-    want = TH.defined_symbols(os.path.join(S.FORWARDCHECK_DIR, "forwardcheck.cpp"))
-    assert sorted(want) == sorted(S.FORWARDCHECK) and len(want) == 2
-    lib = S.forwardcheck()
-    for name, (restype, argtypes) in want.items():
-        fn = getattr(lib, name)
-        assert list(fn.argtypes) == argtypes and fn.restype is restype, name
-
-
-def test_selftest_program_builds_and_passes(tmp_path):
-    """make -C tests/_forwardcheck selftest without a sanitizer: the stand-alone program is built into tmp_path, runs, and reports ok (so that
-    it stays buildable for a host sanitizer run outside Python)"""
-    import subprocess
-    run = subprocess.run(["make", "-C", S.FORWARDCHECK_DIR, "-s", "selftest", f"BUILD={tmp_path}"], capture_output=True, text=True)
-    assert run.returncode == 0, run.stdout + run.stderr
-    for precision in ("double", "float"):
-        assert re.search(r"forwardcheck selftest \(%s\):.*: ok$" % precision, run.stdout, flags=re.M), run.stdout
-
-
 # ---- the recipe -------------------------------------------------------------------------------------------------------------------------------------
 def test_recipe_is_what_the_bounds_were_measured_on():
     """a guard on the RECIPE, not on the feature (it asks the oracle and tests/scenes.py alone and would pass without so100_forward.hpp): the

@@ -10,7 +10,6 @@ F  the surface."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -64,27 +63,6 @@ def test_null_arguments_are_refused_without_a_device():
     L = lib.load()
     assert L.so100_query_lqr(None, C.byref(lib.LqrIO()), 1, None) == -1
     assert L.so100_last_error() == b"so100_query_lqr: null argument"
-
-
-def test_signature_table_matches_the_source(monkeypatch):
-    """lqr_support.LQRCHECK against the extern "C" definitions of lqrcheck.cpp, parsed by tests/test_hostlibs.py's parser (told the prefix)"""
-    import test_hostlibs as TH
-    monkeypatch.setattr(TH, "PREFIXES", "lq")
-    want = TH.defined_symbols(os.path.join(S.LQRCHECK_DIR, "lqrcheck.cpp"))
-    assert sorted(want) == sorted(S.LQRCHECK) and len(want) == 2
-    lib = S.lqrcheck()
-    for name, (restype, argtypes) in want.items():
-        fn = getattr(lib, name)
-        assert list(fn.argtypes) == argtypes and fn.restype is restype, name
-
-
-def test_selftest_program_builds_and_passes(tmp_path):
-    """make -C tests/_lqrcheck selftest without a sanitizer: the stand-alone program is built into tmp_path, runs, and reports ok (so that it
-    stays buildable for a host sanitizer run outside Python)"""
-    run = subprocess.run(["make", "-C", S.LQRCHECK_DIR, "-s", "selftest", f"BUILD={tmp_path}"], capture_output=True, text=True)
-    assert run.returncode == 0, run.stdout + run.stderr
-    for precision in ("double", "float"):
-        assert re.search(r"lqrcheck selftest \(%s\):.*: ok$" % precision, run.stdout, flags=re.M), run.stdout
 
 
 # ---- A: the twin against the fp64 recursion -------------------------------------------------------------------------------------------------------------

@@ -61,28 +61,6 @@ def test_null_arguments_are_refused_without_a_device():
     assert L.so100_last_error() == b"so100_query_trajectory: null argument"
 
 
-def test_signature_table_matches_the_source(monkeypatch):
-    """trajectory_support.TRAJCHECK against the extern "C" definitions of trajcheck.cpp, parsed by tests/test_hostlibs.py's parser (told the prefix)"""
-    import test_hostlibs as TH
-    monkeypatch.setattr(TH, "PREFIXES", "tc")
-    want = TH.defined_symbols(os.path.join(S.TRAJCHECK_DIR, "trajcheck.cpp"))
-    assert sorted(want) == sorted(S.TRAJCHECK) and len(want) == 2
-    lib = S.trajcheck()
-    for name, (restype, argtypes) in want.items():
-        fn = getattr(lib, name)
-        assert list(fn.argtypes) == argtypes and fn.restype is restype, name
-
-
-def test_selftest_program_builds_and_passes(tmp_path):
-    """make -C tests/_trajcheck selftest without a sanitizer: the stand-alone program is built into tmp_path, runs, and reports ok (so that it
-    stays buildable for a host sanitizer run outside Python)"""
-    import subprocess
-    run = subprocess.run(["make", "-C", S.TRAJCHECK_DIR, "-s", "selftest", f"BUILD={tmp_path}"], capture_output=True, text=True)
-    assert run.returncode == 0, run.stdout + run.stderr
-    for precision in ("double", "float"):
-        assert re.search(r"trajcheck selftest \(%s\):.*: ok$" % precision, run.stdout, flags=re.M), run.stdout
-
-
 # ---- A: per-substep parity with the oracle, every contact kind ------------------------------------------------------------------------------------------
 def test_pad_floor_per_substep():
     n, nsub = 64, 32

@@ -6,39 +6,19 @@ sees them (float32 actions or targets; in actions mode the target is the oracle'
 Cases, references and masks are computed once per process and never modified."""
 import ctypes as C
 import functools
-import os
-import subprocess
 
 import numpy as np
 
 import query_support as QS
 import scenes
 import substep_harness as H
-from hostlibs import ptr
+from hostlibs import ptr, trajcheck
 from oracle import so100_oracle as O
 
 L, M = scenes.L, scenes.M
 TARGETS, ACTIONS = 0, 1
 MODES = {"targets": TARGETS, "actions": ACTIONS}
 JS64 = float(scenes.JS)                                    # (double)0.075f: what the fp64 twin multiplies an action by
-
-# ---- the host twin: tests/_trajcheck/libtrajcheck.so, built by that directory's own Makefile ----------------------------------------------------
-TRAJCHECK_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_trajcheck")
-_p, _i, _u, _l = C.c_void_p, C.c_int, C.c_uint, C.c_long
-# name: (restype, argtypes) of every exported symbol, as tests/hostlibs.py declares them for the other twins
-_SIG = (None, [_l] + [_p]*4 + [_i, _i, _i, _u, _i, _i] + [_p]*10)
-TRAJCHECK = {"tc_trajectory_d": _SIG, "tc_trajectory_f": _SIG}
-
-
-@functools.lru_cache(maxsize=None)
-def trajcheck():
-    """the twin, made and loaded once per process"""
-    subprocess.check_call(["make", "-C", TRAJCHECK_DIR, "-s", "libtrajcheck.so"])
-    lib = C.CDLL(os.path.join(TRAJCHECK_DIR, "libtrajcheck.so"))
-    for name, (restype, argtypes) in TRAJCHECK.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = restype, argtypes
-    return lib
 
 
 def twin(ctrl, qpos, qvel=None, mode="targets", nsub=16, flags=scenes.REFP, dtype=np.float32, solver_iters=2, contact_iters=20, warm=None):
