@@ -5,8 +5,12 @@ that rollout in one launch (the arm block of the tangent state: rows and columns
 summed over the horizon gets its Gauss-Newton terms from So100Sim.jacobian, a batched Riccati pass in torch on the device improves the
 plan, and its first action is executed through step().  Printed next to the zero-action baseline, like examples/mppi_reach.py.
 --backward query replaces the torch Riccati and forward loops by ONE So100Sim.lqr call (nx = 12: the arm block, read out of the unsliced A, B).
+--forward closed replaces the LINEAR forward pass (the plan is u + du of the linear model, never checked against the physics) by the nonlinear
+one with a line search: So100Sim.lqr gives k and K (whatever --backward says), ONE So100Sim.closed_loop call rolls the feedback law out on the
+real dynamics at eight step sizes alpha = 0, 1, 1/2, .. 1/64, the true cost of every candidate is summed in torch, and each env takes the controls
+of its cheapest candidate as the new plan.  alpha = 0 is the old plan, so the chosen plan's true cost never exceeds the old one's.
 
-    python examples/ilqr_reach.py [--envs 8] [--horizon 8] [--steps 100] [--iterations 2] [--backward {torch,query}]
+    python examples/ilqr_reach.py [--envs 8] [--horizon 8] [--steps 100] [--iterations 2] [--backward {torch,query}] [--forward {linear,closed}]
 """
 import argparse
 import os
@@ -18,15 +22,18 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from so100_mujoco_rl_amd.lib import ENV01, F_CUBE_PINNED, So100Sim   # noqa: E402
 
 ARM = list(range(0, 6)) + list(range(12, 18))                  # the arm's block of the tangent state: dq 0..5, v 12..17
+ALPHAS = (0.0,) + tuple(2.0**-i for i in range(7))             # the line search's candidates: the old plan, then 1, 1/2, .. 1/64
 
 
 class Ilqr:
     """policy(sim, obs) -> action [N, 6].  plan [N, horizon, 6] is the current action sequence, shifted by one step after every call;
     control_cost: the weight of |a|^2 beside |ee - cube|^2 (metres squared); damping: added to Q_uu (Levenberg-Marquardt); backward: "torch" (the
-    loops below) or "query" (So100Sim.lqr: the same recursion in one launch)."""
-    def __init__(self, horizon=8, iterations=2, control_cost=1e-5, damping=1e-5, backward="torch"):
-        self.H, self.iterations, self.control_cost, self.damping, self.backward = horizon, iterations, control_cost, damping, backward
+    loops below) or "query" (So100Sim.lqr: the same recursion in one launch); forward: "linear" (the linear model's u + du) or "closed" (the
+    feedback law on the real dynamics at ALPHAS, the cheapest candidate per env; costs: per improve() the (chosen, alpha = 0) true costs [N])."""
+    def __init__(self, horizon=8, iterations=2, control_cost=1e-5, damping=1e-5, backward="torch", forward="linear"):
+        self.H, self.iterations, self.control_cost, self.damping, self.backward, self.forward = horizon, iterations, control_cost, damping, backward, forward
         self.plan = None
+        self.costs = []
 
     def improve(self, sim, q0, v0):
         N, H, dev = sim.n, self.H, sim.device
@@ -44,6 +51,27 @@ class Ilqr:
         lx[..., :6] = 2.0*torch.einsum("hnij,hni->hnj", J, r)
         lxx[..., :6, :6] = 2.0*torch.einsum("hnij,hnik->hnjk", J, J)
         eye = torch.eye(6, device=dev)
+        if self.forward == "closed":
+            Bq = d["B"].reshape(H, N, 24, 6).clone()
+            Bq[..., 5] = 0.0                                         # the jaw does not move the end-effector point
+            Ut = U.permute(1, 0, 2).contiguous()
+            zero = torch.zeros(1, N, 12, device=dev)
+            s = sim.lqr(d["A"].reshape(H, N, 24, 24), Bq, torch.cat([zero, lx]), torch.cat([zero[..., None].expand(1, N, 12, 12), lxx]),
+                        lu=2.0*self.control_cost*Ut, luu=(2.0*self.control_cost*eye).expand(H, N, 6, 6), nx=12, reg=self.damping)
+            if bool((s["bad"] >= 0).any()):
+                return
+            # the nonlinear forward pass at every step size in one launch; k's and K's jaw rows are zero (B's jaw column is), so the jaw keeps the plan's 0
+            c = sim.closed_loop(Ut, roll["qpos"], roll["qvel"], s["K"], s["k"], alphas=ALPHAS, nx=12, qpos=q0, qvel=v0, mode="actions", clamp=(-1.0, 1.0))
+            cube = q0[:, 6:9]                                        # pinned: where it is at the start
+            cost = ((c["ee"] - cube[None, :, None]).square().sum(-1) + self.control_cost*c["u"].square().sum(-1)).sum(0)      # [N, L]
+            cost = torch.where(c["bad_step"] >= 0, torch.full_like(cost, float("inf")), cost)
+            best = cost.argmin(dim=1)
+            env = torch.arange(N, device=dev)
+            if bool(torch.isinf(cost[env, best]).any()):             # an env without a single candidate that got through: keep the plan
+                return
+            self.costs.append((cost[env, best].cpu(), cost[:, 0].cpu()))
+            self.plan = c["u"][:, env, best].permute(1, 0, 2).contiguous()
+            return
         if self.backward == "query":
             # one launch: A, B as the derivatives query wrote them (row t of the cost is the state BEFORE action t: a zero row in front)
             Bq = d["B"].reshape(H, N, 24, 6).clone()
@@ -127,8 +155,9 @@ def main():
     ap.add_argument("--envs", type=int, default=8); ap.add_argument("--horizon", type=int, default=8)
     ap.add_argument("--steps", type=int, default=100); ap.add_argument("--iterations", type=int, default=2)
     ap.add_argument("--backward", choices=("torch", "query"), default="torch")
+    ap.add_argument("--forward", choices=("linear", "closed"), default="linear")
     args = ap.parse_args()
-    for name, policy in (("iLQR", Ilqr(args.horizon, args.iterations, backward=args.backward)), ("zero action", zero_action)):
+    for name, policy in (("iLQR", Ilqr(args.horizon, args.iterations, backward=args.backward, forward=args.forward)), ("zero action", zero_action)):
         sim = So100Sim(ENV01, args.envs, flags=F_CUBE_PINNED, max_episode_steps=0, seed=0)
         d0, d1, r = run(sim, args.steps, policy)
         print(f"{name:12s} mean |cube - ee|: {d0:.4f} m at reset -> {d1:.4f} m after {args.steps} steps; reward/step {r:+.4f}")

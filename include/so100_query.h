@@ -1,7 +1,8 @@
 /* so100_query.h -- model queries of libso100sim.so: what MuJoCo's users read from MjData or get from mj_jac, mj_fullM,
  * mj_inverse and mj_forward, for M independent problems at once, one GPU lane per problem (the forward query: four), and where M states
  * end up under M open-loop control sequences (the trajectory query), and the finite-difference linearisation of such a control step, one GPU
- * wave per problem (the derivatives query).
+ * wave per problem (the derivatives query), the Riccati pass on such linearisations (the LQR query) and the rollouts under the feedback law it
+ * gives, one GPU lane per rollout (the closed-loop query).
  *
  * Additive to so100_sim.h (SO100_ABI_VERSION is unchanged) and under its conventions: extern "C"; `*_dev` pointers are DEVICE
  * pointers owned by the caller; 0 on success, a negative SO100_E_* code otherwise with the message in so100_last_error(); all
@@ -310,6 +311,76 @@ typedef struct {
 } so100_lqr_io;
 
 int so100_query_lqr(so100_sim* sim, const so100_lqr_io* io, int32_t M, void* hip_stream);
+
+/* Closed-loop trajectories: the trajectory query under a time-varying feedback law around a nominal plan -- the NONLINEAR forward pass of iLQR
+ * at L step sizes at once (the line search's candidates), and LQR tracking of one plan from disturbed starts.  M problems with L candidates each
+ * are M * L rollouts of T control steps, nsub substeps each, one GPU lane per rollout with the state in registers throughout.  The handle's
+ * simulation does not move.
+ *
+ * Start (qpos_dev, qvel_dev; both NULL: the handle's state with its warm-start rows, Kahan rows and anti-gravity bit, M = N; an explicit state
+ * starts cold), mode, T, nsub, flags, solver_iters, contact_iters and their limits: exactly as in so100_trajectory_io.  All L candidates of a
+ * problem start from the same state.
+ *
+ * Nominal plan.  u [T][6][M] (SoA, the trajectory query's ctrl).  qpos_ref [T][13][M] and qvel_ref [T][12][M] hold in row t the nominal state
+ * AFTER step t -- what so100_query_trajectory writes as qpos_traj / qvel_traj, passed straight in; the nominal state at the start of step
+ * t >= 1 is row t - 1, and row T - 1 is never read (T = 1: the references may be NULL).  qpos_ref0 [13][M], qvel_ref0 [12][M]: the nominal
+ * state at the start of step 0; both NULL: the start itself, dx_0 = 0 exactly (the iLQR case).
+ * Gains.  nx = 24 or 12 (the arm block, tangent indices 0..5 and 12..17: the reference's cube rows are then never read).  k [T][M][6] and
+ * K [T][M][6][nx] are PROBLEM-major, bit for bit what so100_query_lqr writes.  k NULL: zero.
+ * Candidates.  L in 1..SO100_CL_MAX_L; alpha: a HOST pointer to L finite floats, copied into the launch.
+ *
+ * Law, per rollout at step t, from the state x_t the step starts from:
+ *     dx  = x_t (-) xref_t       in the derivatives query's tangent: a rounded difference per row, the rotation vector of quat_ref^-1 (x) quat
+ *                                (mju_subQuat) for the cube's rotation rows 9..11
+ *     c_j = u_j + (alpha k_j + sum_i K_ji dx_i)       i ascending, the sum started from alpha k_j
+ *     c_j = clamp(c_j, u_lo, u_hi)                    where clamp != 0
+ * and c is the step's control as in so100_trajectory_io (SO100_TRAJ_ACTIONS: the targets are q(start of step t) + 0.075 c).
+ *
+ * Outputs.  SoA over the M * L rollouts, rollout (m, a) in column m L + a.  u_traj [T][6][ML]: the controls applied -- the chosen candidate's
+ * column is the next plan.  The others: as in so100_trajectory_io; bad_step also fires at step t where a gain, a nominal control or a reference
+ * row read at step t is not finite.  A failed rollout's float rows are NaN from that step on; no other rollout sees it.  Every output is
+ * nullable; at least one is required.
+ *
+ * Argument errors, in this order: those of so100_query_trajectory up to the iteration counts (u_dev in ctrl_dev's place); nx not 12 or 24;
+ * L outside 1..16 or M * L over INT32_MAX; a null alpha, K_dev, or (T > 1) qpos_ref_dev or qvel_ref_dev; exactly one of qpos_ref0_dev and
+ * qvel_ref0_dev; an alpha that is not finite; clamp with u_lo > u_hi or a bound that is not finite; no output. */
+#define SO100_CL_MAX_L 16
+typedef struct {
+    const float* qpos_dev;             /* [13][M] or NULL (with qvel_dev NULL: the handle's state)                 */
+    const float* qvel_dev;             /* [12][M] or NULL                                                           */
+    const float* u_dev;                /* [T][6][M] nominal controls: targets (radians) or actions, by mode         */
+    int32_t      mode;                 /* SO100_TRAJ_TARGETS or SO100_TRAJ_ACTIONS                                  */
+    int32_t      T;                    /* control steps, 1..4096                                                    */
+    int32_t      nsub;                 /* substeps per control step, 1..1024; T * nsub <= 65 536                    */
+    uint32_t     flags;                /* SO100_F_*                                                                 */
+    int32_t      solver_iters;         /* 1..64                                                                     */
+    int32_t      contact_iters;        /* 1..64                                                                     */
+    const float* qpos_ref_dev;         /* [T][13][M] nominal state after step t (T = 1: may be NULL)                */
+    const float* qvel_ref_dev;         /* [T][12][M]                                                                */
+    const float* qpos_ref0_dev;        /* [13][M] nominal state at the start, or NULL: the start itself             */
+    const float* qvel_ref0_dev;        /* [12][M] or NULL, together with qpos_ref0_dev                              */
+    int32_t      nx;                   /* 24 or 12                                                                  */
+    const float* k_dev;                /* [T][M][6] or NULL: zero                                                   */
+    const float* K_dev;                /* [T][M][6][nx]                                                             */
+    int32_t      L;                    /* candidates per problem, 1..16                                             */
+    const float* alpha;                /* HOST pointer to L finite floats                                           */
+    int32_t      clamp;                /* != 0: c is kept in [u_lo, u_hi]                                           */
+    float        u_lo;
+    float        u_hi;
+    float*       u_traj_dev;           /* [T][6][ML] the controls applied                                           */
+    float*       qpos_traj_dev;        /* [T][13][ML]                                                               */
+    float*       qvel_traj_dev;        /* [T][12][ML]                                                               */
+    float*       ee_traj_dev;          /* [T][3][ML]                                                                */
+    float*       qpos_final_dev;       /* [13][ML] row T - 1 of qpos_traj                                           */
+    float*       qvel_final_dev;       /* [12][ML] row T - 1 of qvel_traj                                           */
+    int32_t*     ncon_dev;             /* [T][ML]                                                                   */
+    int32_t*     dropped_dev;          /* [T][ML]                                                                   */
+    int32_t*     sig_dev;              /* [T][ML]                                                                   */
+    float*       residual_dev;         /* [T][ML]                                                                   */
+    int32_t*     bad_step_dev;         /* [ML]                                                                      */
+} so100_closed_loop_io;
+
+int so100_query_closed_loop(so100_sim* sim, const so100_closed_loop_io* io, int32_t M, void* hip_stream);
 
 #ifdef __cplusplus
 }

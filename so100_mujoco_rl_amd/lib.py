@@ -193,12 +193,24 @@ class LqrIO(C.Structure):
                [(n, C.c_void_p) for n in ("k_dev", "K_dev", "Vx0_dev", "Vxx0_dev", "dV_dev", "du_dev", "dx_dev", "bad_dev")]
 
 
+class ClosedLoopIO(C.Structure):
+    _fields_ = [("qpos_dev", C.c_void_p), ("qvel_dev", C.c_void_p), ("u_dev", C.c_void_p), ("mode", C.c_int32), ("T", C.c_int32), ("nsub", C.c_int32),
+                ("flags", C.c_uint32), ("solver_iters", C.c_int32), ("contact_iters", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("qpos_ref_dev", "qvel_ref_dev", "qpos_ref0_dev", "qvel_ref0_dev")] + \
+               [("nx", C.c_int32), ("k_dev", C.c_void_p), ("K_dev", C.c_void_p), ("L", C.c_int32), ("alpha", C.c_void_p), ("clamp", C.c_int32),
+                ("u_lo", C.c_float), ("u_hi", C.c_float)] + \
+               [(n, C.c_void_p) for n in ("u_traj_dev", "qpos_traj_dev", "qvel_traj_dev", "ee_traj_dev", "qpos_final_dev", "qvel_final_dev", "ncon_dev",
+                                          "dropped_dev", "sig_dev", "residual_dev", "bad_step_dev")]
+
+
 QUERY_EXPORTS = ["so100_query_kinematics", "so100_query_jacobian", "so100_query_dynamics", "so100_query_ik", "so100_query_forward",
-                 "so100_query_trajectory", "so100_query_derivatives", "so100_query_lqr"]
+                 "so100_query_trajectory", "so100_query_derivatives", "so100_query_lqr", "so100_query_closed_loop"]
 QUERY_IO = {"so100_query_kinematics": KinematicsIO, "so100_query_jacobian": JacobianIO, "so100_query_dynamics": DynamicsIO, "so100_query_ik": IkIO,
-            "so100_query_forward": ForwardIO, "so100_query_trajectory": TrajectoryIO, "so100_query_derivatives": DerivativesIO, "so100_query_lqr": LqrIO}
+            "so100_query_forward": ForwardIO, "so100_query_trajectory": TrajectoryIO, "so100_query_derivatives": DerivativesIO, "so100_query_lqr": LqrIO,
+            "so100_query_closed_loop": ClosedLoopIO}
 DERIV_NX, DERIV_NU, DERIV_EPS = 24, 6, 2.0**-6                 # SO100_DERIV_*
 LQR_NU, LQR_MAX_T = 6, 4096                                    # SO100_LQR_*
+CL_MAX_L = 16                                                  # SO100_CL_MAX_L
 TRAJ_MODES = {"targets": 0, "actions": 1}                      # SO100_TRAJ_TARGETS / SO100_TRAJ_ACTIONS
 TRAJ_MAX_T, TRAJ_MAX_NSUB, TRAJ_MAX_SUBSTEPS = 4096, 1024, 65536    # SO100_TRAJ_MAX_*
 EE_LINK = 4                                                    # SO100_EE_LINK: the reference's end-effector point sits on Fixed_Jaw
@@ -760,6 +772,60 @@ class So100Sim(_Handle):
                    *[out[name].data_ptr() for name in ("k", "K", "Vx0", "Vxx0", "dV", "du", "dx", "bad")])
         _check(self.L.so100_query_lqr(self.h, C.byref(io), M, self._stream()), "so100_query_lqr")
         return out
+
+    def closed_loop(self, u, qpos_ref, qvel_ref, K, k=None, *, alphas=(1.0,), nx=24, qpos=None, qvel=None, ref0=None, mode="targets", nsub=None, flags=None,
+                    clamp=None, solver_iters=None, contact_iters=None):
+        """Rollouts on the real dynamics under the feedback law c_t = u_t + alpha k_t + K_t (x_t (-) xref_t), for every step size in `alphas` at once:
+        the nonlinear forward pass of iLQR with its line-search candidates, or LQR tracking of one plan from disturbed starts.  One launch, the
+        simulation does not move.  u [T, M, 6] nominal controls and qpos_ref [T, M, 13], qvel_ref [T, M, 12] the nominal rollout, in trajectory()'s
+        shapes (row t: the state AFTER step t -- trajectory()'s "qpos" and "qvel"; None with T = 1); K [T, M, 6, nx] and k [T, M, 6] (None: zero) as
+        lqr() returns them; nx = 24 or 12 (the arm block).  qpos, qvel, mode, nsub, flags and the iteration counts: as in trajectory().  ref0 =
+        (qpos [M, 13], qvel [M, 12]): the nominal state at the start; None: the start itself.  clamp = (lo, hi) keeps the controls applied inside.
+        x (-) xref is the derivatives query's tangent difference.  Returns views with L = len(alphas): "u" [T, M, L, 6] the controls applied (the chosen
+        candidate's is the next plan), "qpos" [T, M, L, 13], "qvel" [T, M, L, 12], "ee" [T, M, L, 3], "ncon", "dropped", "sig" [T, M, L] int32, "residual"
+        [T, M, L] and "bad_step" [M, L] int32: trajectory()'s, firing also where a gain, nominal control or reference value read at that step is not finite."""
+        if mode not in TRAJ_MODES:
+            raise So100Error(f"closed_loop: mode must be one of {sorted(TRAJ_MODES)}, got {mode!r}")
+        if nx not in (12, 24):
+            raise So100Error(f"closed_loop: nx must be 12 or 24, got {nx!r}")
+        u = torch.as_tensor(u, dtype=torch.float32, device=self.device)
+        if u.dim() != 3 or u.shape[2] != 6 or u.shape[0] < 1:
+            raise So100Error(f"u: want a [T, M, 6] tensor, got {tuple(u.shape)}")
+        T = u.shape[0]
+        al = [float(a) for a in alphas]
+        L = len(al)
+        if not 1 <= L <= CL_MAX_L:
+            raise So100Error(f"closed_loop: want 1..{CL_MAX_L} alphas, got {L}")
+        us = u.permute(0, 2, 1).contiguous()
+        qs, vs = self._soa(qpos, 13, "qpos"), self._soa(qvel, 12, "qvel"); M = self._problems(qs, vs, us[0])
+
+        def rows(t, kk, what):
+            if t is None:
+                return None
+            t = torch.as_tensor(t, dtype=torch.float32, device=self.device)
+            if tuple(t.shape) != (T, M, kk):
+                raise So100Error(f"{what}: want a [{T}, {M}, {kk}] tensor, got {tuple(t.shape)}")
+            return t.permute(0, 2, 1).contiguous()
+        rq, rv = rows(qpos_ref, 13, "qpos_ref"), rows(qvel_ref, 12, "qvel_ref")
+        r0q, r0v = (None, None) if ref0 is None else (self._soa(ref0[0], 13, "ref0 qpos"), self._soa(ref0[1], 12, "ref0 qvel"))
+        self._problems(us[0], r0q, r0v)
+        Kt, kt = self._lqr_in(K, (T, M, 6, nx), "K"), self._lqr_in(k, (T, M, 6), "k")
+        i32 = dict(dtype=torch.int32)
+        ML = M*L
+        ut, qt, vt, et = self._out(ML, T, 6), self._out(ML, T, 13), self._out(ML, T, 12), self._out(ML, T, 3)
+        ncon, drop, sig, res, bad = self._out(ML, T, **i32), self._out(ML, T, **i32), self._out(ML, T, **i32), self._out(ML, T), self._out(ML, **i32)
+        alpha = (C.c_float*L)(*al)
+        c = self.cfg
+        lo, hi = (0.0, 0.0) if clamp is None else clamp
+        io = ClosedLoopIO(_optr(qs), _optr(vs), us.data_ptr(), TRAJ_MODES[mode], T, c.frame_skip if nsub is None else nsub, c.flags if flags is None else flags,
+                          c.solver_iters if solver_iters is None else solver_iters, c.contact_iters if contact_iters is None else contact_iters,
+                          _optr(rq), _optr(rv), _optr(r0q), _optr(r0v), nx, _optr(kt), _optr(Kt), L, C.cast(alpha, C.c_void_p), int(clamp is not None), lo, hi,
+                          ut.data_ptr(), qt.data_ptr(), vt.data_ptr(), et.data_ptr(), None, None, ncon.data_ptr(), drop.data_ptr(), sig.data_ptr(), res.data_ptr(),
+                          bad.data_ptr())
+        _check(self.L.so100_query_closed_loop(self.h, C.byref(io), M, self._stream()), "so100_query_closed_loop")
+        cols = lambda t: t.unflatten(-1, (M, L))
+        return {"u": cols(ut).permute(0, 2, 3, 1), "qpos": cols(qt).permute(0, 2, 3, 1), "qvel": cols(vt).permute(0, 2, 3, 1), "ee": cols(et).permute(0, 2, 3, 1),
+                "ncon": cols(ncon), "dropped": cols(drop), "sig": cols(sig), "residual": cols(res), "bad_step": cols(bad)}
 
     def _lqr_in(self, t, shape, name):
         """a contiguous float32 tensor of exactly `shape` on the handle's device, or None"""

@@ -6,6 +6,7 @@
     python tools/kbench_query.py --trajectory [--out profiles/trajectory_kbench.json] [--commit LABEL] [--rounds 5]
     python tools/kbench_query.py --derivatives [--out profiles/derivatives_kbench.json] [--commit LABEL] [--rounds 5]
     python tools/kbench_query.py --lqr [--form mfma] [--out profiles/lqr_kbench.json] [--commit LABEL] [--rounds 5]
+    python tools/kbench_query.py --closed-loop [--form global] [--out profiles/closed_loop_kbench.json] [--commit LABEL] [--rounds 5]
 
 Cases, at M = 4096 and M = 1 048 576 problems: kinematics with every output and with the end-effector point alone, the Jacobian (jacp and
 jacr), the dynamics (M, bias and tau) and the IK.  Poses are uniform over the joint ranges; the IK problems are the 400 of the tests' recipe
@@ -32,7 +33,12 @@ built and the results differenced in torch (derivatives_main).
 --lqr times the LQR query (so100_query_lqr, every output, with nominal controls and bounds) at M in {8, 4096}, T in {8, 64}, both nx, beside what
 a user did before it existed: the backward and forward loops of examples/ilqr_reach.py in torch, on identical inputs (lqr_main).  --form labels
 the cases with the form of the kernel the loaded library holds (SO100_LIB=<a side build with -DSO100_LQR_VALU=1> --form valu); the cases of
-other forms already in the output file are kept."""
+other forms already in the output file are kept.
+
+--closed-loop times the closed-loop trajectory query (so100_query_closed_loop; u, qpos, qvel, ee and bad_step asked for) at (M, L, T) in {(8, 8, 8),
+(4096, 8, 8), (4096, 8, 64), (65536, 1, 16)}, nsub = 16, both nx, beside what a user did before it existed: T calls of so100_query_trajectory (T = 1)
+on M L problems with the feedback law in torch between them (closed_loop_main).  --form labels the cases with how the loaded library's kernel
+reads its gains (global: the product; lds: SO100_LIB=<a side build with -DSO100_CL_LDS=1> --form lds)."""
 import argparse
 import ctypes as C
 import json
@@ -449,6 +455,126 @@ def lqr_main(a):
         fh.write("\n")
 
 
+CLOSED_LOOP_SIZES = [(8, 8, 8, 20, 5), (4096, 8, 8, 5, 2), (4096, 8, 64, 2, 1), (65536, 1, 16, 2, 1)]      # (M, L, T, query calls, baseline runs) per round
+
+
+def torch_tangent_difference(qp, qv, xq, xv):
+    """x (-) xref on SoA rows [k][n]: derivative_column with r = 1, in torch"""
+    d = torch.empty(24, qp.shape[1], device=qp.device)
+    d[:9] = qp[:9] - xq[:9]; d[12:] = qv - xv
+    a0, a1, a2, a3 = xq[9], -xq[10], -xq[11], -xq[12]
+    b0, b1, b2, b3 = qp[9], qp[10], qp[11], qp[12]
+    w = a0*b0 - a1*b1 - a2*b2 - a3*b3
+    vec = torch.stack([a0*b1 + a1*b0 + a2*b3 - a3*b2, a0*b2 - a1*b3 + a2*b0 + a3*b1, a0*b3 + a1*b2 - a2*b1 + a3*b0])
+    sn = vec.norm(dim=0)
+    angle = 2.0*torch.atan2(sn, w)
+    angle = torch.where(angle > torch.pi, angle - 2.0*torch.pi, angle)
+    d[9:12] = vec*torch.where(sn < 1e-15, torch.zeros_like(sn), angle/sn.clamp_min(1e-30))
+    return d
+
+
+def closed_loop_main(a):
+    """One so100_query_closed_loop call against T so100_query_trajectory calls (T = 1, M L problems, final rows and ee) with the law in torch between
+    them, on identical inputs: arms around the idle pose under SO100_F_CUBE_PINNED, a seeded plan of actions with its own rollout as the reference, PD-like
+    gains (-2 / -0.1 on a joint's own position / velocity column, 0.05 N elsewhere, k = 0.2 N), alpha = 0, 1, 1/2, .., clamp to [-1, 1].  The gains
+    repeated per candidate are built outside the baseline's span.  An event pair round each unit, enqueued without waiting."""
+    sim = lib.So100Sim(lib.ENV01, 8, device="cuda:0", flags=lib.F_CUBE_PINNED, seed=0)
+    dev, L_, st = sim.device, sim.L, sim._stream()
+    doc = {"what": "HIP-event time of one so100_query_closed_loop call (u, qpos, qvel, ee, bad_step) and of its emulation: T so100_query_trajectory calls "
+                   "(T = 1) on M L problems with the feedback law in torch between them, on identical inputs, nsub = 16, SO100_F_CUBE_PINNED; an event pair round "
+                   "each unit, medians of alternated rounds; `form`: the kernel reads its gains from global memory per lane (global) or through a cooperative "
+                   "coalesced load into LDS (lds, a side build)",
+           "commit": a.commit, "card": torch.cuda.get_device_name(0), "rounds": a.rounds, "cases": []}
+    if os.path.exists(a.out):
+        doc["cases"] = [c for c in json.load(open(a.out)).get("cases", []) if c.get("form") != a.form]
+    nsub, flags, iters = 16, lib.F_CUBE_PINNED, (2, 20)
+    idle = np.array([0, -1.5, 1.5, 0.5, 0, 0.2, 0.2, -0.2, 0.0099, 1, 0, 0, 0], np.float32)      # tests/scenes.idle_batch: the arm folded above the table
+    for nx in (12, 24):
+        idx = torch.tensor(list(range(6)) + list(range(12, 18)) if nx == 12 else list(range(24)), device=dev)
+        for M, Lc, T, reps, loops in CLOSED_LOOP_SIZES:
+            ML = M*Lc
+            g = torch.Generator(device=dev).manual_seed(0)
+            rn = lambda *shape: torch.randn(*shape, generator=g, device=dev)
+            qpos = torch.from_numpy(idle).to(dev)[:, None].repeat(1, M).contiguous()
+            qpos[:6] += 0.3*(2*torch.rand(6, M, generator=g, device=dev) - 1)
+            qvel = torch.zeros(12, M, device=dev); qvel[:6] = 0.5*(2*torch.rand(6, M, generator=g, device=dev) - 1)
+            U = (torch.rand(T, 6, M, generator=g, device=dev) - 0.5).contiguous()
+            K = 0.05*rn(T, M, 6, nx)
+            for j in range(6):
+                K[..., j, j] = -2.0; K[..., j, nx//2 + j] = -0.1
+            k = 0.2*rn(T, M, 6)
+            alphas = [0.0] + [2.0**-i for i in range(Lc - 1)] if Lc > 1 else [1.0]
+            al = (C.c_float*Lc)(*alphas)
+            rq, rv = torch.empty(T, 13, M, device=dev), torch.empty(T, 12, M, device=dev)
+            tio = lib.TrajectoryIO(qpos_dev=qpos.data_ptr(), qvel_dev=qvel.data_ptr(), ctrl_dev=U.data_ptr(), mode=1, T=T, nsub=nsub, flags=flags, solver_iters=iters[0],
+                                   contact_iters=iters[1], qpos_traj_dev=rq.data_ptr(), qvel_traj_dev=rv.data_ptr())
+            assert L_.so100_query_trajectory(sim.h, C.byref(tio), M, st) == 0, L_.so100_last_error()
+            out = {"u": torch.empty(T, 6, ML, device=dev), "qpos": torch.empty(T, 13, ML, device=dev), "qvel": torch.empty(T, 12, ML, device=dev),
+                   "ee": torch.empty(T, 3, ML, device=dev)}
+            bad = torch.empty(ML, dtype=torch.int32, device=dev)
+            io = lib.ClosedLoopIO(qpos_dev=qpos.data_ptr(), qvel_dev=qvel.data_ptr(), u_dev=U.data_ptr(), mode=1, T=T, nsub=nsub, flags=flags, solver_iters=iters[0],
+                                  contact_iters=iters[1], qpos_ref_dev=rq.data_ptr(), qvel_ref_dev=rv.data_ptr(), nx=nx, k_dev=k.data_ptr(), K_dev=K.data_ptr(), L=Lc,
+                                  alpha=C.cast(al, C.c_void_p), clamp=1, u_lo=-1.0, u_hi=1.0, u_traj_dev=out["u"].data_ptr(), qpos_traj_dev=out["qpos"].data_ptr(),
+                                  qvel_traj_dev=out["qvel"].data_ptr(), ee_traj_dev=out["ee"].data_ptr(), bad_step_dev=bad.data_ptr())
+            # the baseline's buffers: everything per rollout, the gains repeated per candidate outside the span
+            rep = lambda t, dim: t.repeat_interleave(Lc, dim=dim).contiguous()
+            Ur, kr, Kr = rep(U, 2), rep(k, 1).permute(0, 2, 1).contiguous(), rep(K, 1)                # [T, 6, ML], [T, 6, ML], [T, ML, 6, nx]
+            rqr, rvr = rep(rq, 2), rep(rv, 2)
+            alr = torch.tensor(alphas, device=dev).repeat(M)[None]                                      # [1, ML]
+            q0r, v0r = rep(qpos, 1), rep(qvel, 1)
+            base = {"u": torch.empty(T, 6, ML, device=dev), "qpos": torch.empty(T, 13, ML, device=dev), "qvel": torch.empty(T, 12, ML, device=dev),
+                    "ee": torch.empty(T, 3, ML, device=dev)}
+            ios = []
+            for t in range(T):
+                src_q, src_v = (q0r, v0r) if t == 0 else (base["qpos"][t - 1], base["qvel"][t - 1])
+                ios.append(lib.TrajectoryIO(qpos_dev=src_q.data_ptr(), qvel_dev=src_v.data_ptr(), ctrl_dev=base["u"][t].data_ptr(), mode=1, T=1, nsub=nsub, flags=flags,
+                                            solver_iters=iters[0], contact_iters=iters[1], qpos_final_dev=base["qpos"][t].data_ptr(),
+                                            qvel_final_dev=base["qvel"][t].data_ptr(), ee_traj_dev=base["ee"][t].data_ptr()))
+
+            def one_query():
+                rc = L_.so100_query_closed_loop(sim.h, C.byref(io), M, st)
+                assert rc == 0, L_.so100_last_error()
+
+            def one_baseline():
+                for t in range(T):
+                    if t == 0:
+                        c = Ur[0] + alr*kr[0]
+                    else:
+                        dx = torch_tangent_difference(base["qpos"][t - 1], base["qvel"][t - 1], rqr[t - 1], rvr[t - 1])
+                        c = Ur[t] + (alr*kr[t] + torch.einsum("mji,im->jm", Kr[t], dx[idx]))
+                    torch.clamp(c, -1.0, 1.0, out=base["u"][t])
+                    rc = L_.so100_query_trajectory(sim.h, C.byref(ios[t]), ML, st)
+                    assert rc == 0, L_.so100_last_error()
+
+            def pair(call):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(); call(); e1.record()
+                return e0, e1
+
+            def timed(call, n):
+                pairs = [pair(call) for _ in range(n)]
+                torch.cuda.synchronize()
+                return sum(e0.elapsed_time(e1) for e0, e1 in pairs)*1e3/n
+
+            timed(one_query, 2); timed(one_baseline, 1)
+            tq, tb = [], []
+            for _ in range(a.rounds):
+                tq.append(timed(one_query, reps)); tb.append(timed(one_baseline, loops))
+            diff = {name: (out[name] - base[name]).abs().max().item() for name in ("u", "qpos", "qvel", "ee")}
+            mq, mb = statistics.median(tq), statistics.median(tb)
+            case = {"form": a.form, "nx": nx, "M": M, "L": Lc, "T": T, "nsub": nsub, "closed_loop_us_per_call": round(mq, 1), "trajectory_calls_and_torch_us": round(mb, 1),
+                    "closed_loop_over_baseline": round(mq/mb, 4), "baseline_us_per_step": round(mb/T, 1), "closed_loop_rounds_us": [round(x, 1) for x in tq],
+                    "baseline_rounds_us": [round(x, 1) for x in tb], "units_per_round": [reps, loops], "rollout_substeps_per_s": round(ML*T*nsub/(mq*1e-6), 1),
+                    "largest_difference_to_baseline": {name: float(f"{v:.3e}") for name, v in diff.items()}, "bad_rollouts": int((bad >= 0).sum().item())}
+            doc["cases"].append(case)
+            print(json.dumps(case), flush=True)
+            del out, base, Ur, kr, Kr, rqr, rvr, ios, K, k, rq, rv
+    sim.close()
+    with open(a.out, "w") as fh:
+        json.dump(doc, fh, indent=1)
+        fh.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None); ap.add_argument("--commit", default="unknown")
@@ -457,11 +583,17 @@ def main():
     ap.add_argument("--trajectory", action="store_true", help="time the trajectory query against the so100_step calls it predicts (profiles/trajectory_kbench.json)")
     ap.add_argument("--derivatives", action="store_true", help="time the derivatives query against its emulation through the trajectory query (profiles/derivatives_kbench.json)")
     ap.add_argument("--lqr", action="store_true", help="time the LQR query against the torch loops of examples/ilqr_reach.py (profiles/lqr_kbench.json)")
-    ap.add_argument("--form", default="mfma", help="--lqr: the label of the loaded library's kernel form (mfma, or valu for a -DSO100_LQR_VALU=1 side build)")
+    ap.add_argument("--closed-loop", action="store_true", help="time the closed-loop trajectory query against T trajectory calls with the law in torch (profiles/closed_loop_kbench.json)")
+    ap.add_argument("--form", default=None, help="--lqr: the label of the loaded library's kernel form (mfma, or valu for a -DSO100_LQR_VALU=1 side build); "
+                                                 "--closed-loop: global, or lds for a -DSO100_CL_LDS=1 side build")
     a = ap.parse_args()
+    if a.form is None:
+        a.form = "global" if a.closed_loop else "mfma"
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "lqr_kbench.json" if a.lqr else "derivatives_kbench.json" if a.derivatives else "trajectory_kbench.json" if a.trajectory else "forward_kbench.json" if a.forward else "query_kbench.json")
+        a.out = os.path.join(ROOT, "profiles", "closed_loop_kbench.json" if a.closed_loop else "lqr_kbench.json" if a.lqr else "derivatives_kbench.json" if a.derivatives else "trajectory_kbench.json" if a.trajectory else "forward_kbench.json" if a.forward else "query_kbench.json")
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    if a.closed_loop:
+        return closed_loop_main(a)
     if a.lqr:
         return lqr_main(a)
     if a.derivatives:
