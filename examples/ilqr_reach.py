@@ -9,8 +9,13 @@ plan, and its first action is executed through step().  Printed next to the zero
 one with a line search: So100Sim.lqr gives k and K (whatever --backward says), ONE So100Sim.closed_loop call rolls the feedback law out on the
 real dynamics at eight step sizes alpha = 0, 1, 1/2, .. 1/64, the true cost of every candidate is summed in torch, and each env takes the controls
 of its cheapest candidate as the new plan.  alpha = 0 is the old plan, so the chosen plan's true cost never exceeds the old one's.
+--cost query takes the cost's quadratic model (lx, lxx, lu, luu) from ONE So100Sim.cost_terms call in place of the Jacobian query and the torch
+arithmetic behind it (cube target, nx = 12: So100Sim.lqr is then the backward pass, whatever --backward says), and with --forward closed the line
+search's sum, mask, argmin and gather from ONE So100Sim.cost_select call with the old plan as the fallback: an iteration is then six calls on one
+stream with no torch operation between them.
 
     python examples/ilqr_reach.py [--envs 8] [--horizon 8] [--steps 100] [--iterations 2] [--backward {torch,query}] [--forward {linear,closed}]
+                                  [--cost {torch,query}]
 """
 import argparse
 import os
@@ -29,9 +34,11 @@ class Ilqr:
     """policy(sim, obs) -> action [N, 6].  plan [N, horizon, 6] is the current action sequence, shifted by one step after every call;
     control_cost: the weight of |a|^2 beside |ee - cube|^2 (metres squared); damping: added to Q_uu (Levenberg-Marquardt); backward: "torch" (the
     loops below) or "query" (So100Sim.lqr: the same recursion in one launch); forward: "linear" (the linear model's u + du) or "closed" (the
-    feedback law on the real dynamics at ALPHAS, the cheapest candidate per env; costs: per improve() the (chosen, alpha = 0) true costs [N])."""
-    def __init__(self, horizon=8, iterations=2, control_cost=1e-5, damping=1e-5, backward="torch", forward="linear"):
+    feedback law on the real dynamics at ALPHAS, the cheapest candidate per env; costs: per improve() the (chosen, alpha = 0) true costs [N]);
+    cost: "torch" (the arithmetic below) or "query" (So100Sim.cost_terms and, with forward "closed", So100Sim.cost_select)."""
+    def __init__(self, horizon=8, iterations=2, control_cost=1e-5, damping=1e-5, backward="torch", forward="linear", cost="torch"):
         self.H, self.iterations, self.control_cost, self.damping, self.backward, self.forward = horizon, iterations, control_cost, damping, backward, forward
+        self.cost = cost
         self.plan = None
         self.costs = []
 
@@ -42,6 +49,9 @@ class Ilqr:
         Xq = torch.cat([q0[None], roll["qpos"][:-1]]); Xv = torch.cat([v0[None], roll["qvel"][:-1]])   # [H, N, .]: the state action t starts from
         d = sim.derivatives(U.permute(1, 0, 2).reshape(H*N, 6), Xq.reshape(H*N, 13), Xv.reshape(H*N, 12), mode="actions")
         if bool(d["bad"].any()) or bool((roll["bad_step"] >= 0).any()):
+            return
+        if self.cost == "query":
+            self.improve_with_cost_queries(sim, q0, v0, roll, d)
             return
         # Gauss-Newton terms of |ee(q) - cube|^2 at the states after each action
         qn = roll["qpos"]
@@ -116,6 +126,31 @@ class Ilqr:
             dx = torch.einsum("nij,nj->ni", A[t], dx) + torch.einsum("nij,nj->ni", B[t], new[:, t] - U[:, t])
         self.plan = new
 
+    def improve_with_cost_queries(self, sim, q0, v0, roll, d):
+        """improve() from the rollout and its linearisation on, with the cost on the device: cost_terms -> lqr -> (closed_loop -> cost_select)"""
+        N, H = sim.n, self.H
+        Ut = self.plan.permute(1, 0, 2).contiguous()
+        cost = dict(target_mode="cube", w_point=1.0, w_u=self.control_cost)
+        Bq = d["B"].reshape(H, N, 24, 6).clone()
+        Bq[..., 5] = 0.0                                             # the jaw does not move the end-effector point
+        t = sim.cost_terms(roll["qpos"], roll["qvel"], Ut, nx=12, **cost)
+        closed = self.forward == "closed"
+        s = sim.lqr(d["A"].reshape(H, N, 24, 24), Bq, t["lx"], t["lxx"], lu=t["lu"], luu=t["luu"], nx=12, reg=self.damping,
+                    **({} if closed else dict(u=Ut, u_lo=-1.0, u_hi=1.0)))
+        if bool((s["bad"] >= 0).any()):
+            return
+        if not closed:
+            new = (Ut + s["du"]).permute(1, 0, 2).clone()
+            new[..., 5] = 0.0
+            self.plan = new
+            return
+        c = sim.closed_loop(Ut, roll["qpos"], roll["qvel"], s["K"], s["k"], alphas=ALPHAS, nx=12, qpos=q0, qvel=v0, mode="actions", clamp=(-1.0, 1.0))
+        # the pinned cube stays where it was at the start, so the cube target is the torch path's `cube`; an env without a single candidate that got
+        # through keeps its plan (the fallback) with no look at the result on the host
+        pick = sim.cost_select(c["qpos"], c["qvel"], c["u"], bad_step=c["bad_step"], u_fallback=Ut, **cost)
+        self.costs.append((pick["best_cost"].cpu(), pick["cost"][:, 0].cpu()))
+        self.plan = pick["u_best"].permute(1, 0, 2).contiguous()
+
     def __call__(self, sim, obs):
         if self.plan is None:
             self.plan = torch.zeros(sim.n, self.H, 6, device=sim.device)
@@ -156,8 +191,9 @@ def main():
     ap.add_argument("--steps", type=int, default=100); ap.add_argument("--iterations", type=int, default=2)
     ap.add_argument("--backward", choices=("torch", "query"), default="torch")
     ap.add_argument("--forward", choices=("linear", "closed"), default="linear")
+    ap.add_argument("--cost", choices=("torch", "query"), default="torch")
     args = ap.parse_args()
-    for name, policy in (("iLQR", Ilqr(args.horizon, args.iterations, backward=args.backward, forward=args.forward)), ("zero action", zero_action)):
+    for name, policy in (("iLQR", Ilqr(args.horizon, args.iterations, backward=args.backward, forward=args.forward, cost=args.cost)), ("zero action", zero_action)):
         sim = So100Sim(ENV01, args.envs, flags=F_CUBE_PINNED, max_episode_steps=0, seed=0)
         d0, d1, r = run(sim, args.steps, policy)
         print(f"{name:12s} mean |cube - ee|: {d0:.4f} m at reset -> {d1:.4f} m after {args.steps} steps; reward/step {r:+.4f}")

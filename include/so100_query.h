@@ -2,7 +2,8 @@
  * mj_inverse and mj_forward, for M independent problems at once, one GPU lane per problem (the forward query: four), and where M states
  * end up under M open-loop control sequences (the trajectory query), and the finite-difference linearisation of such a control step, one GPU
  * wave per problem (the derivatives query), the Riccati pass on such linearisations (the LQR query) and the rollouts under the feedback law it
- * gives, one GPU lane per rollout (the closed-loop query).
+ * gives, one GPU lane per rollout (the closed-loop query), and the cost of such plans: its quadratic model in the LQR query's input layout (the
+ * cost-terms query) and the line search's choice among the closed-loop query's candidates (the cost-select query).
  *
  * Additive to so100_sim.h (SO100_ABI_VERSION is unchanged) and under its conventions: extern "C"; `*_dev` pointers are DEVICE
  * pointers owned by the caller; 0 on success, a negative SO100_E_* code otherwise with the message in so100_last_error(); all
@@ -381,6 +382,99 @@ typedef struct {
 } so100_closed_loop_io;
 
 int so100_query_closed_loop(so100_sim* sim, const so100_closed_loop_io* io, int32_t M, void* hip_stream);
+
+/* The cost family of the two cost queries below: a tracked point drawn to a target, joint angles drawn to a nominal pose, joint velocities
+ * and controls drawn to zero.  A HOST struct, copied into the launch.  Per state row (q, the arm's v, the target g):
+ *     r = point(q) - g                                        point: link and offset exactly as in so100_jacobian_io
+ *     s = w_point (r0^2 + r1^2 + r2^2) + sum_j w_q[j] (q_j - q_nom_j)^2 + sum_j w_v[j] v_j^2          summed in that order, j ascending
+ * the control cost of step t is c_t = sum_j w_u[j] u_tj^2, and the total of a rollout of T steps
+ *     J = sum_{t<T} (c_t + sigma_t s_t)                       t ascending; sigma_{T-1} = w_terminal, every other sigma_t = 1
+ * with s_t taken at the state AFTER step t (row t of a trajectory): the start is not a decision variable and is not counted.
+ * Target.  SO100_COST_TARGET_FIXED: target_dev [3][M], one point per problem.  SO100_COST_TARGET_TRAJ: target_dev [T][3][M], row t with the
+ * state after step t.  SO100_COST_TARGET_CUBE: the cube's position, rows 6..8 of the same qpos row; target_dev is not read. */
+#define SO100_COST_TARGET_FIXED 0
+#define SO100_COST_TARGET_TRAJ  1
+#define SO100_COST_TARGET_CUBE  2
+typedef struct {
+    int32_t      link;                 /* 0..5                                                                      */
+    const float* offset;               /* HOST pointer to 3 finite floats or NULL (so100_jacobian_io)               */
+    int32_t      target_mode;          /* SO100_COST_TARGET_*                                                       */
+    float        w_point;              /* every weight finite and >= 0                                              */
+    float        w_q[6];
+    float        q_nom[6];             /* finite                                                                    */
+    float        w_v[6];
+    float        w_u[6];
+    float        w_terminal;           /* multiplies the state terms of the LAST state row                          */
+} so100_cost_def;
+
+/* Cost terms: the quadratic model of that cost along M trajectories of T steps, written in the LQR query's input layout -- lx, lxx, lu and luu
+ * are bit for bit what so100_query_lqr takes, with no operation in between.  The handle is taken for the device and the error slot: its state
+ * is NEVER read or written.
+ *
+ * Inputs.  qpos_traj [T][13][M] and qvel_traj [T][12][M]: what the trajectory and closed-loop queries write (qvel_traj NULL: zero).  u [T][6][M]
+ * (SoA, the trajectory query's ctrl).  nx = 24 or 12 (the arm block, tangent indices 0..5 and 12..17).
+ * Outputs, with n = nx, PROBLEM-major like the LQR query's inputs.  Row 0 of lx and lxx is zero.  Row t + 1 is the model of sigma_t s_t at the state
+ * after step t, in the derivatives query's tangent, with J = jacp of the point:
+ *     lx[0..5]   = 2 sigma (w_point J'r + w_q o (q - q_nom))          lxx[0..5][0..5] = 2 sigma (w_point J'J + diag w_q)
+ *     lx[12..17] = 2 sigma w_v o v   (6..11 where n = 12)             lxx diagonal 12..17 = 2 sigma w_v
+ * This is the GAUSS-NEWTON model: the term of the point's second derivative, w_point sum_a r_a d2 p_a / dq2, is dropped.  With the cube target and
+ * n = 24 the cube's world-frame linear tangent 6..8 enters with dr/dx = -I: lx[6..8] = -2 sigma w_point r, lxx[0..5][6..8] = -2 sigma w_point J'
+ * and its transpose, lxx[6..8][6..8] = 2 sigma w_point I; with n = 12 those columns are dropped (the pinned-cube planner's case).  Every other
+ * entry of lxx is zero, and lxx is symmetric to the bit: entry (i, j) is computed from (min, max).  lu_t = 2 w_u o u_t, luu_t = diag(2 w_u).
+ * A value that is not finite among those a state row's cost reads (q, the arm's v, the target) makes that row's lx and lxx NaN -- all of
+ * them -- and a u_t that is not finite makes lu_t and luu_t NaN; so100_query_lqr then reports bad = T for that problem.  No other problem sees it.
+ * Every output is nullable; at least one is required.
+ *
+ * Argument errors, in this order: a null handle or io; M < 1; nx not 12 or 24; T outside 1..SO100_LQR_MAX_T; a null cost; link outside 0..5; an
+ * offset that is not finite; an unknown target_mode; a weight that is negative or not finite or a q_nom that is not finite; a required pointer
+ * (qpos_traj_dev, u_dev; target_dev unless the target is the cube) that is NULL; no output. */
+typedef struct {
+    const so100_cost_def* cost;        /* HOST pointer                                                              */
+    const float* target_dev;           /* [3][M] or [T][3][M] by target_mode; not read with the cube target         */
+    int32_t      nx;                   /* 24 or 12                                                                  */
+    int32_t      T;                    /* horizon, 1..4096                                                          */
+    const float* qpos_traj_dev;        /* [T][13][M] the state after step t                                         */
+    const float* qvel_traj_dev;        /* [T][12][M] or NULL: zero                                                  */
+    const float* u_dev;                /* [T][6][M]                                                                 */
+    float*       lx_dev;               /* [T+1][M][n]                                                               */
+    float*       lxx_dev;              /* [T+1][M][n][n]                                                            */
+    float*       lu_dev;               /* [T][M][6]                                                                 */
+    float*       luu_dev;              /* [T][M][6][6]                                                              */
+} so100_cost_terms_io;
+
+int so100_query_cost_terms(so100_sim* sim, const so100_cost_terms_io* io, int32_t M, void* hip_stream);
+
+/* Cost select: the line search's decision on the closed-loop query's output -- the total cost J of each of M * L rollouts, per problem the
+ * cheapest candidate, and its controls gathered as the next plan.  One GPU lane per rollout.  The handle's state is NEVER read or written.
+ *
+ * Inputs.  Rollout (m, a) is in column m L + a, the closed-loop query's output layout: qpos_traj [T][13][ML], qvel_traj [T][12][ML] (NULL: zero),
+ * u_traj [T][6][ML] the controls applied, bad_step [ML] (NULL: none failed).  Targets are per PROBLEM, [3][M] or [T][3][M]: a problem's candidates
+ * share them.  u_fallback [T][6][M] (nullable): the plan to keep where no candidate can be taken.
+ * Outputs.  cost [ML]: J, or +inf where bad_step >= 0 or J is not finite.  best [M]: the candidate with the smallest cost, ties to the LOWEST
+ * index, -1 if every candidate is +inf.  best_cost [M]: its cost, +inf where best = -1.  u_best [T][6][M]: the winner's column of u_traj; where
+ * best = -1 the column of u_fallback, or NaN without one.  The result is the same bits on every run, whatever M, L and the problem's place.
+ * Every output is nullable; at least one is required.
+ *
+ * Argument errors, in this order: a null handle or io; M < 1; T outside 1..SO100_LQR_MAX_T; L outside 1..SO100_CL_MAX_L or M * L over INT32_MAX;
+ * then those of the cost as in so100_cost_terms_io (from the null cost to q_nom); a required pointer (qpos_traj_dev, u_traj_dev; target_dev unless
+ * the target is the cube) that is NULL; no output. */
+typedef struct {
+    const so100_cost_def* cost;        /* HOST pointer                                                              */
+    const float* target_dev;           /* [3][M] or [T][3][M] by target_mode; not read with the cube target         */
+    int32_t      T;                    /* horizon, 1..4096                                                          */
+    int32_t      L;                    /* candidates per problem, 1..16                                             */
+    const float* qpos_traj_dev;        /* [T][13][ML]                                                               */
+    const float* qvel_traj_dev;        /* [T][12][ML] or NULL: zero                                                 */
+    const float* u_traj_dev;           /* [T][6][ML]                                                                */
+    const int32_t* bad_step_dev;       /* [ML] or NULL                                                              */
+    const float* u_fallback_dev;       /* [T][6][M] or NULL                                                         */
+    float*       cost_dev;             /* [ML]                                                                      */
+    int32_t*     best_dev;             /* [M]                                                                       */
+    float*       best_cost_dev;        /* [M]                                                                       */
+    float*       u_best_dev;           /* [T][6][M]                                                                 */
+} so100_cost_select_io;
+
+int so100_query_cost_select(so100_sim* sim, const so100_cost_select_io* io, int32_t M, void* hip_stream);
 
 #ifdef __cplusplus
 }

@@ -203,11 +203,29 @@ class ClosedLoopIO(C.Structure):
                                           "dropped_dev", "sig_dev", "residual_dev", "bad_step_dev")]
 
 
+class CostDef(C.Structure):
+    _fields_ = [("link", C.c_int32), ("offset", C.c_void_p), ("target_mode", C.c_int32), ("w_point", C.c_float), ("w_q", C.c_float*6), ("q_nom", C.c_float*6),
+                ("w_v", C.c_float*6), ("w_u", C.c_float*6), ("w_terminal", C.c_float)]
+
+
+class CostTermsIO(C.Structure):
+    _fields_ = [("cost", C.POINTER(CostDef)), ("target_dev", C.c_void_p), ("nx", C.c_int32), ("T", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("qpos_traj_dev", "qvel_traj_dev", "u_dev", "lx_dev", "lxx_dev", "lu_dev", "luu_dev")]
+
+
+class CostSelectIO(C.Structure):
+    _fields_ = [("cost", C.POINTER(CostDef)), ("target_dev", C.c_void_p), ("T", C.c_int32), ("L", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("qpos_traj_dev", "qvel_traj_dev", "u_traj_dev", "bad_step_dev", "u_fallback_dev", "cost_dev", "best_dev", "best_cost_dev",
+                                          "u_best_dev")]
+
+
 QUERY_EXPORTS = ["so100_query_kinematics", "so100_query_jacobian", "so100_query_dynamics", "so100_query_ik", "so100_query_forward",
-                 "so100_query_trajectory", "so100_query_derivatives", "so100_query_lqr", "so100_query_closed_loop"]
+                 "so100_query_trajectory", "so100_query_derivatives", "so100_query_lqr", "so100_query_closed_loop", "so100_query_cost_terms",
+                 "so100_query_cost_select"]
 QUERY_IO = {"so100_query_kinematics": KinematicsIO, "so100_query_jacobian": JacobianIO, "so100_query_dynamics": DynamicsIO, "so100_query_ik": IkIO,
             "so100_query_forward": ForwardIO, "so100_query_trajectory": TrajectoryIO, "so100_query_derivatives": DerivativesIO, "so100_query_lqr": LqrIO,
-            "so100_query_closed_loop": ClosedLoopIO}
+            "so100_query_closed_loop": ClosedLoopIO, "so100_query_cost_terms": CostTermsIO, "so100_query_cost_select": CostSelectIO}
+COST_TARGETS = {"fixed": 0, "traj": 1, "cube": 2}               # SO100_COST_TARGET_*
 DERIV_NX, DERIV_NU, DERIV_EPS = 24, 6, 2.0**-6                 # SO100_DERIV_*
 LQR_NU, LQR_MAX_T = 6, 4096                                    # SO100_LQR_*
 CL_MAX_L = 16                                                  # SO100_CL_MAX_L
@@ -827,14 +845,92 @@ class So100Sim(_Handle):
         return {"u": cols(ut).permute(0, 2, 3, 1), "qpos": cols(qt).permute(0, 2, 3, 1), "qvel": cols(vt).permute(0, 2, 3, 1), "ee": cols(et).permute(0, 2, 3, 1),
                 "ncon": cols(ncon), "dropped": cols(drop), "sig": cols(sig), "residual": cols(res), "bad_step": cols(bad)}
 
-    def _lqr_in(self, t, shape, name):
-        """a contiguous float32 tensor of exactly `shape` on the handle's device, or None"""
-        if t is None:
-            return None
-        t = torch.as_tensor(t, dtype=torch.float32, device=self.device).contiguous()
+    def _cost(self, what, T, M, target, target_mode, link, offset, w_point, w_q, q_nom, w_v, w_u, w_terminal):
+        """(so100_cost_def, what it points to, the target in the kernels' layout) of the cost arguments cost_terms() and cost_select() share"""
+        if target_mode is None:
+            target_mode = "cube" if target is None else ("fixed" if torch.as_tensor(target).dim() == 2 else "traj")
+        if target_mode not in COST_TARGETS:
+            raise So100Error(f"{what}: target_mode must be one of {sorted(COST_TARGETS)}, got {target_mode!r}")
+        six = lambda w: (C.c_float*6)(*([float(w)]*6 if isinstance(w, (int, float)) else [float(x) for x in w]))
+        off = self._offset(offset)
+        tg = None
+        if target_mode != "cube":
+            if target is None:
+                raise So100Error(f"{what}: target_mode {target_mode!r} needs a target")
+            tg = torch.as_tensor(target, dtype=torch.float32, device=self.device)
+            want = (M, 3) if target_mode == "fixed" else (T, M, 3)
+            if tuple(tg.shape) != want:
+                raise So100Error(f"target: want a {list(want)} tensor, got {tuple(tg.shape)}")
+            tg = tg.transpose(-1, -2).contiguous()
+        d = CostDef(link, C.cast(off, C.c_void_p) if off is not None else None, COST_TARGETS[target_mode], w_point, six(w_q), six(q_nom), six(w_v), six(w_u),
+                    w_terminal)
+        return d, off, tg
+
+    def cost_terms(self, qpos, qvel, u, *, nx=24, target=None, target_mode=None, link=EE_LINK, offset=None, w_point=1.0, w_q=0.0, q_nom=0.0, w_v=0.0,
+                   w_u=0.0, w_terminal=1.0):
+        """The Gauss-Newton quadratic model of the cost family of include/so100_query.h (so100_cost_def) along M trajectories, in one launch, as lqr()
+        takes it.  qpos [T, M, 13], qvel [T, M, 12] (None: zero) and u [T, M, 6] in trajectory()'s shapes, row t the state AFTER step t.  The cost
+        per state row: w_point |point - target|^2 + sum w_q (q - q_nom)^2 + sum w_v v^2, w_terminal times that at the last row, plus sum w_u u^2 per
+        step; the point is (link, offset) as in jacobian().  target [M, 3] ("fixed"), [T, M, 3] ("traj") or None ("cube": the cube's position in
+        the same row); target_mode None picks by the target's shape.  w_q, q_nom, w_v, w_u: 6 values or one for all.  nx = 24 or 12 (the arm
+        block).  Returns "lx" [T + 1, M, nx], "lxx" [T + 1, M, nx, nx] (row 0 zero), "lu" [T, M, 6], "luu" [T, M, 6, 6]; a state row or control that is
+        not finite gives NaN terms for that (step, problem)."""
+        if nx not in (12, 24):
+            raise So100Error(f"cost_terms: nx must be 12 or 24, got {nx!r}")
+        u = torch.as_tensor(u, dtype=torch.float32, device=self.device)
+        if u.dim() != 3 or u.shape[2] != 6 or u.shape[0] < 1 or u.shape[1] < 1:
+            raise So100Error(f"u: want a [T, M, 6] tensor, got {tuple(u.shape)}")
+        T, M = u.shape[0], u.shape[1]
+        rows = lambda t, k, name: None if t is None else self._shaped(t, (T, M, k), name).permute(0, 2, 1).contiguous()      # trajectory()'s views: no copy
+        qs, vs, us = rows(qpos, 13, "qpos"), rows(qvel, 12, "qvel"), rows(u, 6, "u")
+        if qs is None:
+            raise So100Error("cost_terms: qpos is required")
+        d, keep, tg = self._cost("cost_terms", T, M, target, target_mode, link, offset, w_point, w_q, q_nom, w_v, w_u, w_terminal)
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=self.device)
+        out = {"lx": new(T + 1, M, nx), "lxx": new(T + 1, M, nx, nx), "lu": new(T, M, 6), "luu": new(T, M, 6, 6)}
+        io = CostTermsIO(C.pointer(d), _optr(tg), nx, T, qs.data_ptr(), _optr(vs), us.data_ptr(), *[out[k].data_ptr() for k in ("lx", "lxx", "lu", "luu")])
+        _check(self.L.so100_query_cost_terms(self.h, C.byref(io), M, self._stream()), "so100_query_cost_terms")
+        return out
+
+    def cost_select(self, qpos, qvel, u, *, bad_step=None, u_fallback=None, target=None, target_mode=None, link=EE_LINK, offset=None, w_point=1.0, w_q=0.0,
+                    q_nom=0.0, w_v=0.0, w_u=0.0, w_terminal=1.0):
+        """The line search on closed_loop()'s output in one launch: the total cost of every candidate rollout, the cheapest candidate per problem and
+        its controls as the next plan.  qpos [T, M, L, 13], qvel [T, M, L, 12] (None: zero), u [T, M, L, 6] (closed_loop()'s "qpos", "qvel", "u"),
+        bad_step [M, L] int32 (None: no rollout failed), u_fallback [T, M, 6] (None: NaN): the plan kept where no candidate can be taken.  The cost
+        arguments: as in cost_terms(); targets are per problem ([M, 3] or [T, M, 3]).  Returns "cost" [M, L] (+inf for a failed rollout), "best" [M]
+        int32 (ties: the lowest index; -1: every candidate is +inf), "best_cost" [M] and "u_best" [T, M, 6]."""
+        u = torch.as_tensor(u, dtype=torch.float32, device=self.device)
+        if u.dim() != 4 or u.shape[3] != 6 or u.shape[0] < 1 or u.shape[1] < 1 or not 1 <= u.shape[2] <= CL_MAX_L:
+            raise So100Error(f"u: want a [T, M, L, 6] tensor with L in 1..{CL_MAX_L}, got {tuple(u.shape)}")
+        T, M, L = u.shape[0], u.shape[1], u.shape[2]
+        cols = lambda t, k, name: None if t is None else self._shaped(t, (T, M, L, k), name).permute(0, 3, 1, 2).reshape(T, k, M*L).contiguous()   # closed_loop()'s views: no copy
+        qs, vs, us = cols(qpos, 13, "qpos"), cols(qvel, 12, "qvel"), cols(u, 6, "u")
+        if qs is None:
+            raise So100Error("cost_select: qpos is required")
+        bs = None
+        if bad_step is not None:
+            bs = torch.as_tensor(bad_step, dtype=torch.int32, device=self.device)
+            if tuple(bs.shape) != (M, L):
+                raise So100Error(f"bad_step: want a [{M}, {L}] tensor, got {tuple(bs.shape)}")
+            bs = bs.reshape(M*L).contiguous()
+        fb = None if u_fallback is None else self._shaped(u_fallback, (T, M, 6), "u_fallback").permute(0, 2, 1).contiguous()
+        d, keep, tg = self._cost("cost_select", T, M, target, target_mode, link, offset, w_point, w_q, q_nom, w_v, w_u, w_terminal)
+        cost, best, bc, ub = self._out(M*L), self._out(M, dtype=torch.int32), self._out(M), self._out(M, T, 6)
+        io = CostSelectIO(C.pointer(d), _optr(tg), T, L, qs.data_ptr(), _optr(vs), us.data_ptr(), _optr(bs), _optr(fb), cost.data_ptr(), best.data_ptr(),
+                          bc.data_ptr(), ub.data_ptr())
+        _check(self.L.so100_query_cost_select(self.h, C.byref(io), M, self._stream()), "so100_query_cost_select")
+        return {"cost": cost.unflatten(0, (M, L)), "best": best, "best_cost": bc, "u_best": ub.permute(0, 2, 1)}
+
+    def _shaped(self, t, shape, name):
+        """a float32 tensor of exactly `shape` on the handle's device, in whatever strides it has"""
+        t = torch.as_tensor(t, dtype=torch.float32, device=self.device)
         if tuple(t.shape) != tuple(shape):
             raise So100Error(f"{name}: want a {list(shape)} tensor, got {tuple(t.shape)}")
         return t
+
+    def _lqr_in(self, t, shape, name):
+        """a contiguous float32 tensor of exactly `shape` on the handle's device, or None"""
+        return None if t is None else self._shaped(t, shape, name).contiguous()
 
 
 def learner_layout(obs_dim):

@@ -7,6 +7,7 @@
     python tools/kbench_query.py --derivatives [--out profiles/derivatives_kbench.json] [--commit LABEL] [--rounds 5]
     python tools/kbench_query.py --lqr [--form mfma] [--out profiles/lqr_kbench.json] [--commit LABEL] [--rounds 5]
     python tools/kbench_query.py --closed-loop [--form global] [--out profiles/closed_loop_kbench.json] [--commit LABEL] [--rounds 5]
+    python tools/kbench_query.py --cost [--out profiles/cost_kbench.json] [--commit LABEL] [--rounds 5]
 
 Cases, at M = 4096 and M = 1 048 576 problems: kinematics with every output and with the end-effector point alone, the Jacobian (jacp and
 jacr), the dynamics (M, bias and tau) and the IK.  Poses are uniform over the joint ranges; the IK problems are the 400 of the tests' recipe
@@ -38,7 +39,11 @@ other forms already in the output file are kept.
 --closed-loop times the closed-loop trajectory query (so100_query_closed_loop; u, qpos, qvel, ee and bad_step asked for) at (M, L, T) in {(8, 8, 8),
 (4096, 8, 8), (4096, 8, 64), (65536, 1, 16)}, nsub = 16, both nx, beside what a user did before it existed: T calls of so100_query_trajectory (T = 1)
 on M L problems with the feedback law in torch between them (closed_loop_main).  --form labels the cases with how the loaded library's kernel
-reads its gains (global: the product; lds: SO100_LIB=<a side build with -DSO100_CL_LDS=1> --form lds)."""
+reads its gains (global: the product; lds: SO100_LIB=<a side build with -DSO100_CL_LDS=1> --form lds).
+
+--cost times the two cost queries (so100_query_cost_terms with every output; so100_query_cost_select with every output at L = 8) at (M, T) in {(8, 8),
+(4096, 8), (4096, 64)}, both nx for the terms, beside what examples/ilqr_reach.py did before they existed: So100Sim.jacobian plus the einsums, zero
+fills and cats for the terms; the torch sum, mask, argmin and gather for the selection (cost_main)."""
 import argparse
 import ctypes as C
 import json
@@ -575,6 +580,133 @@ def closed_loop_main(a):
         fh.write("\n")
 
 
+COST_SIZES = [(8, 8, 50, 20), (4096, 8, 20, 10), (4096, 64, 5, 3)]      # (M, T, query calls, baseline runs) per round
+COST_L = 8
+
+
+def cost_main(a):
+    """One so100_query_cost_terms / so100_query_cost_select call against the torch arithmetic of examples/ilqr_reach.py on identical inputs: seeded states
+    (q uniform over the joint ranges, v in +-2, the cube in a +-0.3 m box, u in +-1), the example's cost (cube target, w_point = 1, w_u = 1e-5).  An event
+    pair round each unit, enqueued without waiting; medians of alternated rounds."""
+    sim = lib.So100Sim(lib.ENV01, 8, device="cuda:0", flags=lib.F_CUBE_PINNED, seed=0)
+    dev, L, st = sim.device, sim.L, sim._stream()
+    cc = 1e-5
+    six = lambda w: (C.c_float*6)(*([w]*6))
+    cdef = lib.CostDef(lib.EE_LINK, None, lib.COST_TARGETS["cube"], 1.0, six(0.0), six(0.0), six(0.0), six(cc), 1.0)
+    doc = {"what": "HIP-event time of one so100_query_cost_terms call (lx, lxx, lu, luu) and one so100_query_cost_select call (cost, best, best_cost, u_best; "
+                   "L = 8) and of the torch arithmetic of examples/ilqr_reach.py they replace, on identical inputs: So100Sim.jacobian, two einsums, the zero "
+                   "fills, the two cats and lu / luu for the terms (the ee rows it reads are the trajectory query's, not timed); the sum over ee and u rows, "
+                   "mask, argmin and gather for the selection (the query recomputes the point from qpos).  An event pair round each unit, medians of "
+                   "alternated rounds.  A record, not a gate: nothing comparable existed",
+           "commit": a.commit, "card": torch.cuda.get_device_name(0), "rounds": a.rounds, "cases": []}
+    rng = torch.as_tensor(S.joint_range(), dtype=torch.float32, device=dev)
+
+    def pair(call):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(); call(); e1.record()
+        return e0, e1
+
+    def timed(call, n):
+        pairs = [pair(call) for _ in range(n)]
+        torch.cuda.synchronize()
+        return sum(e0.elapsed_time(e1) for e0, e1 in pairs)*1e3/n
+
+    def states(T, cols):
+        g = torch.Generator(device=dev).manual_seed(0)
+        r = lambda *shape: torch.rand(*shape, generator=g, device=dev)
+        qpos = torch.zeros(T, cols, 13, device=dev)
+        qpos[..., :6] = rng[:, 0] + (rng[:, 1] - rng[:, 0])*r(T, cols, 6)
+        qpos[..., 6:9] = 0.6*r(T, cols, 3) - 0.3
+        qpos[..., 9] = 1.0
+        return qpos, 4.0*r(T, cols, 12) - 2.0, 2.0*r(T, cols, 6) - 1.0
+
+    for M, T, reps, loops in COST_SIZES:
+        qpos, qvel, u = states(T, M)
+        ee = sim.kinematics(qpos[..., :6].reshape(T*M, 6))["ee"].reshape(T, M, 3).contiguous()
+        qs, vs, us = (x.permute(0, 2, 1).contiguous() for x in (qpos, qvel, u))
+        for nx in (12, 24):
+            out = {"lx": torch.empty(T + 1, M, nx, device=dev), "lxx": torch.empty(T + 1, M, nx, nx, device=dev), "lu": torch.empty(T, M, 6, device=dev),
+                   "luu": torch.empty(T, M, 6, 6, device=dev)}
+            io = lib.CostTermsIO(C.pointer(cdef), None, nx, T, qs.data_ptr(), vs.data_ptr(), us.data_ptr(), *[out[k].data_ptr() for k in ("lx", "lxx", "lu", "luu")])
+            keep = {}
+
+            def one_query():
+                rc = L.so100_query_cost_terms(sim.h, C.byref(io), M, st)
+                assert rc == 0, L.so100_last_error()
+
+            def one_torch():
+                J = sim.jacobian(qpos[..., :6].reshape(T*M, 6))["jacp"].reshape(T, M, 3, 6)
+                r = ee - qpos[..., 6:9]
+                lx = torch.zeros(T, M, nx, device=dev); lxx = torch.zeros(T, M, nx, nx, device=dev)
+                lx[..., :6] = 2.0*torch.einsum("hnij,hni->hnj", J, r)
+                lxx[..., :6, :6] = 2.0*torch.einsum("hnij,hnik->hnjk", J, J)
+                if nx == 24:
+                    lx[..., 6:9] = -2.0*r
+                    lxx[..., :6, 6:9] = -2.0*J.transpose(2, 3); lxx[..., 6:9, :6] = -2.0*J
+                    lxx[..., 6:9, 6:9] = 2.0*torch.eye(3, device=dev)
+                zero = torch.zeros(1, M, nx, device=dev)
+                keep["r"] = (torch.cat([zero, lx]), torch.cat([zero[..., None].expand(1, M, nx, nx), lxx]), 2.0*cc*u,
+                             (2.0*cc*torch.eye(6, device=dev)).expand(T, M, 6, 6).contiguous())
+
+            timed(one_query, 2); timed(one_torch, 1)
+            tq, tt = [], []
+            for _ in range(a.rounds):
+                tq.append(timed(one_query, reps)); tt.append(timed(one_torch, loops))
+            diff = {k: (out[k] - ref).abs().max().item() for k, ref in zip(("lx", "lxx", "lu", "luu"), keep["r"])}
+            mq, mt = statistics.median(tq), statistics.median(tt)
+            words = T*M*(13 + 12 + 6) + (T + 1)*M*(nx + nx*nx) + T*M*42
+            case = {"query": "cost_terms", "nx": nx, "M": M, "T": T, "query_us_per_call": round(mq, 1), "torch_us": round(mt, 1), "query_over_torch": round(mq/mt, 4),
+                    "query_rounds_us": [round(x, 1) for x in tq], "torch_rounds_us": [round(x, 1) for x in tt], "units_per_round": [reps, loops],
+                    "GB_per_s": round(words*4/(mq*1e-6)/1e9, 1), "largest_difference_to_torch": {k: float(f"{v:.3e}") for k, v in diff.items()}}
+            doc["cases"].append(case)
+            print(json.dumps(case), flush=True)
+            del out, keep
+        # the selection: M problems x COST_L candidates
+        Lc = COST_L
+        qpos, qvel, u = states(T, M*Lc)
+        ee = sim.kinematics(qpos[..., :6].reshape(T*M*Lc, 6))["ee"].reshape(T, M, Lc, 3).contiguous()
+        qs, vs, us = (x.permute(0, 2, 1).contiguous() for x in (qpos, qvel, u))
+        u4, cube = u.reshape(T, M, Lc, 6), qpos.reshape(T, M, Lc, 13)[0, :, 0, 6:9].contiguous()
+        qs[:, 6:9] = cube.t().repeat_interleave(Lc, dim=1)[None]          # pinned: every row holds the start's cube, so both sides measure the same thing
+        bad = torch.full((M, Lc), -1, dtype=torch.int32, device=dev); bad[::7, 3] = 2
+        fb = torch.zeros(T, 6, M, device=dev)
+        cost, best, bc, ub = torch.empty(M*Lc, device=dev), torch.empty(M, dtype=torch.int32, device=dev), torch.empty(M, device=dev), torch.empty(T, 6, M, device=dev)
+        io = lib.CostSelectIO(C.pointer(cdef), None, T, Lc, qs.data_ptr(), vs.data_ptr(), us.data_ptr(), bad.data_ptr(), fb.data_ptr(), cost.data_ptr(), best.data_ptr(),
+                              bc.data_ptr(), ub.data_ptr())
+        keep = {}
+
+        def one_query():
+            rc = L.so100_query_cost_select(sim.h, C.byref(io), M, st)
+            assert rc == 0, L.so100_last_error()
+
+        def one_torch():
+            c = ((ee - cube[None, :, None]).square().sum(-1) + cc*u4.square().sum(-1)).sum(0)
+            c = torch.where(bad >= 0, torch.full_like(c, float("inf")), c)
+            b = c.argmin(dim=1)
+            env = torch.arange(M, device=dev)
+            keep["r"] = (c, b, c[env, b], u4[:, env, b].permute(1, 0, 2).contiguous())
+
+        timed(one_query, 2); timed(one_torch, 1)
+        tq, tt = [], []
+        for _ in range(a.rounds):
+            tq.append(timed(one_query, reps)); tt.append(timed(one_torch, loops))
+        c, b, _, plan = keep["r"]
+        mq, mt = statistics.median(tq), statistics.median(tt)
+        words = T*M*Lc*(9 + 6 + 6) + M*Lc*2 + M*2 + 2*T*M*6
+        case = {"query": "cost_select", "L": Lc, "M": M, "T": T, "query_us_per_call": round(mq, 1), "torch_us": round(mt, 1), "query_over_torch": round(mq/mt, 4),
+                "query_rounds_us": [round(x, 1) for x in tq], "torch_rounds_us": [round(x, 1) for x in tt], "units_per_round": [reps, loops],
+                "GB_per_s": round(words*4/(mq*1e-6)/1e9, 1),
+                "largest_difference_to_torch": {"cost": float(f"{(cost.reshape(M, Lc) - c).nan_to_num(posinf=0.0).abs().max().item():.3e}")},
+                "same_best_share": round((best == b).float().mean().item(), 4),
+                "same_plan_where_same_best": bool((ub.permute(2, 0, 1)[best == b] == plan[best == b]).all().item())}
+        doc["cases"].append(case)
+        print(json.dumps(case), flush=True)
+    sim.close()
+    with open(a.out, "w") as fh:
+        json.dump(doc, fh, indent=1)
+        fh.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None); ap.add_argument("--commit", default="unknown")
@@ -584,14 +716,17 @@ def main():
     ap.add_argument("--derivatives", action="store_true", help="time the derivatives query against its emulation through the trajectory query (profiles/derivatives_kbench.json)")
     ap.add_argument("--lqr", action="store_true", help="time the LQR query against the torch loops of examples/ilqr_reach.py (profiles/lqr_kbench.json)")
     ap.add_argument("--closed-loop", action="store_true", help="time the closed-loop trajectory query against T trajectory calls with the law in torch (profiles/closed_loop_kbench.json)")
+    ap.add_argument("--cost", action="store_true", help="time the two cost queries against the torch arithmetic of examples/ilqr_reach.py (profiles/cost_kbench.json)")
     ap.add_argument("--form", default=None, help="--lqr: the label of the loaded library's kernel form (mfma, or valu for a -DSO100_LQR_VALU=1 side build); "
                                                  "--closed-loop: global, or lds for a -DSO100_CL_LDS=1 side build")
     a = ap.parse_args()
     if a.form is None:
         a.form = "global" if a.closed_loop else "mfma"
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "closed_loop_kbench.json" if a.closed_loop else "lqr_kbench.json" if a.lqr else "derivatives_kbench.json" if a.derivatives else "trajectory_kbench.json" if a.trajectory else "forward_kbench.json" if a.forward else "query_kbench.json")
+        a.out = os.path.join(ROOT, "profiles", "cost_kbench.json" if a.cost else "closed_loop_kbench.json" if a.closed_loop else "lqr_kbench.json" if a.lqr else "derivatives_kbench.json" if a.derivatives else "trajectory_kbench.json" if a.trajectory else "forward_kbench.json" if a.forward else "query_kbench.json")
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    if a.cost:
+        return cost_main(a)
     if a.closed_loop:
         return closed_loop_main(a)
     if a.lqr:
