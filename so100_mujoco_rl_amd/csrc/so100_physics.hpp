@@ -473,7 +473,8 @@ template <typename T, bool Z> struct CrbP {
         M[K*(K+1)/2 + (J1-1)] = n[so100g::LINK_AXIS[J1-1]];
     }
     // the same step for columns K (.x) and K-1 (.y) together, for frames J1 .. 1
-    template <int K, int J1> SO100_HD static void walk2(const T s[6], const T c[6], V F[3], V N[3], T M[21]) {
+    // PM: the entries M[K][j] | M[K-1][j] stay the pair they are, in Mp[j] (for ldl6_p), instead of going to M
+    template <int K, int J1, bool PM = false> SO100_HD static void walk2(const T s[6], const T c[6], V F[3], V N[3], T M[21], V* Mp = nullptr) {
         if constexpr (J1 > 0) {
             V fp[3], np[3], t[3];
             const V sv = V(s[J1]), cv = V(c[J1]);
@@ -483,13 +484,16 @@ template <typename T, bool Z> struct CrbP {
 #pragma unroll
             for (int i = 0; i < 3; i++) { F[i] = fp[i]; N[i] = zadd<Z>(np[i], t[i]); }
             constexpr int AXJ = so100g::LINK_AXIS[J1-1];
-            M[K*(K+1)/2 + (J1-1)] = N[AXJ].x;
-            M[(K-1)*K/2 + (J1-1)] = N[AXJ].y;
-            walk2<K, J1-1>(s, c, F, N, M);
+            if constexpr (PM) Mp[J1-1] = N[AXJ];
+            else {
+                M[K*(K+1)/2 + (J1-1)] = N[AXJ].x;
+                M[(K-1)*K/2 + (J1-1)] = N[AXJ].y;
+            }
+            walk2<K, J1-1, PM>(s, c, F, N, M, Mp);
         }
     }
     // columns K and K-1 (K odd), and the composites of links K and K-1 added into their parents
-    template <int K> SO100_HD static void columns(const T s[6], const T c[6], Composite<T> cmp[6], T M[21]) {
+    template <int K, bool PM = false> SO100_HD static void columns(const T s[6], const T c[6], Composite<T> cmp[6], T M[21], V* Mp = nullptr) {
         T fa[3], na[3], fb[3], nb[3];
         column<K>(cmp, fa, na, M);
         step<K, K>(s, c, fa, na, M);
@@ -497,7 +501,7 @@ template <typename T, bool Z> struct CrbP {
         column<K-1>(cmp, fb, nb, M);
         V F[3] = { V{ fa[0], fb[0] }, V{ fa[1], fb[1] }, V{ fa[2], fb[2] } };
         V N[3] = { V{ na[0], nb[0] }, V{ na[1], nb[1] }, V{ na[2], nb[2] } };
-        walk2<K, K-1>(s, c, F, N, M);
+        walk2<K, K-1, PM>(s, c, F, N, M, Mp);
         if constexpr (K - 1 > 0) LinkCrb<K-1, T, Z>::accumulate(s, c, cmp);
     }
 };
@@ -534,6 +538,19 @@ template <typename T, bool PK = true> SO100_HD void arm_trig_update(const T q[6]
             const T sn = A.s[k]*cd + A.c[k]*sd, cs = A.c[k]*cd - A.s[k]*sd;
             A.s[k] = sn; A.c[k] = cs;
         }
+    }
+}
+// the PK form for a caller that holds the increment as the pairs arm_integrate_p leaves (fp32 only)
+template <typename T> SO100_HD void arm_trig_update_p(const V2<T> dq[3], Arm<T>& A) {
+    using V = V2<T>;
+    static_assert(sizeof(T) == 4, "the incremental sin/cos update is the fp32 path");
+#pragma unroll
+    for (int k = 0; k < 6; k += 2) {
+        const V d = dq[k/2], d2 = d*d, s0 = V{ A.s[k], A.s[k+1] }, c0 = V{ A.c[k], A.c[k+1] };
+        const V sd = d*(V(1) + d2*(V(-1.0/6.0) + d2*V(1.0/120.0)));
+        const V cd = V(1) + d2*(V(-0.5) + d2*(V(1.0/24.0) + d2*V(-1.0/720.0)));
+        const V sn = s0*cd + c0*sd, cs = c0*cd - s0*sd;
+        A.s[k] = sn.x; A.s[k+1] = sn.y; A.c[k] = cs.x; A.c[k+1] = cs.y;
     }
 }
 // PK = true: the pair form (LinkFwdP / LinkBwdP / CrbP); PK = false: one 3-vector at a time.  Both compute every value by
@@ -599,6 +616,22 @@ template <typename T, bool PK = true, bool Z = PK> SO100_HD void arm_mass(Arm<T>
         LinkCrb<0, T, Z>::run(A.s, A.c, cmp, A.M);
     }
 }
+// arm_mass in pair form with the rows 5 | 4 (columns 0 .. 3) and 3 | 2 (columns 0, 1) of M left as the pairs CrbP walks them in:
+// R5[j] = (M[5][j], M[4][j]), R3[j] = (M[3][j], M[2][j]); A.M holds the diagonal, M[1][0], M[3][2] and M[5][4] (the other entries are not written)
+template <typename T, bool Z = true> SO100_HD void arm_mass_p(Arm<T>& A, V2<T> R5[4], V2<T> R3[2]) {
+    Composite<T> cmp[6];
+#pragma unroll
+    for (int k = 0; k < 6; k++) {
+        cmp[k].m = T(so100g::LINK_MASS[k]);
+#pragma unroll
+        for (int i = 0; i < 3; i++) cmp[k].h[i] = T(so100g::LINK_H[k][i]);
+#pragma unroll
+        for (int i = 0; i < 6; i++) cmp[k].I[i] = T(so100g::LINK_IORG[k][i]);
+    }
+    CrbP<T, Z>::template columns<5, true>(A.s, A.c, cmp, A.M, R5);
+    CrbP<T, Z>::template columns<3, true>(A.s, A.c, cmp, A.M, R3);
+    CrbP<T, Z>::template columns<1>(A.s, A.c, cmp, A.M);
+}
 template <typename T> SO100_HD void arm_dynamics(const T q[6], const T v[6], Arm<T>& A) {
     arm_trig(q, A);
     arm_bias(v, A);
@@ -637,6 +670,79 @@ template <typename T> SO100_HD void ldl6_solve(const T L[21], const T Dinv[6], T
     for (int i = 4; i >= 0; i--)
 #pragma unroll
         for (int k = i + 1; k < 6; k++) x[i] -= L[SO100_TRI(k, i)]*x[k];
+}
+// ldl6 over the row pairs 3 | 2 and 5 | 4, which arm_mass_p leaves as pairs: R3[j] = (M[3][j], M[2][j]) for the columns j = 0, 1 both rows have left
+// of row 2's diagonal, R5[j] = (M[5][j], M[4][j]) for j = 0 .. 3.  Per element it is ldl6's expression, t -= L[i][k]*L[j][k]*D[k] with k ascending,
+// then L[i][j] = t*Dinv[j]; the diagonal, M[1][0], M[3][2] and M[5][4] stay scalar, on the pairs' halves.  On return M holds what ldl6 leaves
+// (the pairs' halves written back: values, not instructions) and R3, R5 the columns of L in the pairs ldl6_forward_p reads.
+template <typename T> SO100_HD void ldl6_p(T M[21], V2<T> R5[4], V2<T> R3[2], T Dinv[6]) {
+    using V = V2<T>;
+    // L[i][k] of any row from where it lives: rows 2 .. 5 left of their pair's diagonal block in the pairs
+    auto at = [&](int i, int k) -> T {
+        if (i >= 4 && k < 4) return i == 5 ? R5[k].x : R5[k].y;
+        if ((i == 2 || i == 3) && k < 2) return i == 3 ? R3[k].x : R3[k].y;
+        return M[SO100_TRI(i, k)];
+    };
+#pragma unroll
+    for (int j = 0; j < 6; j++) {
+        T d = M[SO100_TRI(j, j)];
+#pragma unroll
+        for (int k = 0; k < j; k++) d -= at(j, k)*at(j, k)*M[SO100_TRI(k, k)];
+        M[SO100_TRI(j, j)] = d;
+        Dinv[j] = trcp(d);
+        // the scalar entry below the diagonal of a pair's own block: M[1][0], M[3][2], M[5][4]
+        if (j % 2 == 0) {
+            T t = M[SO100_TRI(j + 1, j)];
+#pragma unroll
+            for (int k = 0; k < j; k++) t -= at(j + 1, k)*at(j, k)*M[SO100_TRI(k, k)];
+            M[SO100_TRI(j + 1, j)] = t*Dinv[j];
+        }
+        if (j < 2) {
+            V t = R3[j];
+#pragma unroll
+            for (int k = 0; k < j; k++) t -= R3[k]*V(at(j, k))*V(M[SO100_TRI(k, k)]);
+            R3[j] = t*V(Dinv[j]);
+        }
+        if (j < 4) {
+            V t = R5[j];
+#pragma unroll
+            for (int k = 0; k < j; k++) t -= R5[k]*V(at(j, k))*V(M[SO100_TRI(k, k)]);
+            R5[j] = t*V(Dinv[j]);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; k++) { M[SO100_TRI(5, k)] = R5[k].x; M[SO100_TRI(4, k)] = R5[k].y; }
+#pragma unroll
+    for (int k = 0; k < 2; k++) { M[SO100_TRI(3, k)] = R3[k].x; M[SO100_TRI(2, k)] = R3[k].y; }
+}
+// ldl6_solve on pairs.  The right-hand side comes in the order the factor's pairs have, x[j] = (x_2j+1, x_2j): the forward substitution takes
+// the rows 3 | 2 and 5 | 4 of L together over the columns both have (k = 0, 1 and k = 0 .. 3); each x_i still accumulates its k in ascending
+// order, by the scalar code's expression, so every half is the value ldl6_solve computes.  x_1's k = 0, x_3's k = 2 and x_5's k = 4 wait for the
+// other half of their own pair and stay scalar.  D^-1 and the back substitution run on the halves: there x_i needs the finished x_i+1 first, a
+// pair (i, i+1) would reorder the sum.  They leave the solution as the joint pairs acc[j] = (x_2j, x_2j+1) that arm_integrate_p takes.
+template <typename T> SO100_HD void ldl6_forward_p(const T L[21], V2<T> x[3]) {
+    using V = V2<T>;
+    x[0].x -= L[SO100_TRI(1, 0)]*x[0].y;
+#pragma unroll
+    for (int j = 1; j < 3; j++) {
+#pragma unroll
+        for (int k = 0; k < 2*j; k++) {
+            const T xk = (k & 1) ? x[k/2].x : x[k/2].y;
+            x[j] -= V{ L[SO100_TRI(2*j + 1, k)], L[SO100_TRI(2*j, k)] }*V(xk);
+        }
+        x[j].x -= L[SO100_TRI(2*j + 1, 2*j)]*x[j].y;
+    }
+}
+template <typename T> SO100_HD void ldl6_back_p(const T L[21], const T Dinv[6], const V2<T> x[3], V2<T> acc[3]) {
+    T y[6] = { x[0].y, x[0].x, x[1].y, x[1].x, x[2].y, x[2].x };
+#pragma unroll
+    for (int i = 0; i < 6; i++) y[i] *= Dinv[i];
+#pragma unroll
+    for (int i = 4; i >= 0; i--)
+#pragma unroll
+        for (int k = i + 1; k < 6; k++) y[i] -= L[SO100_TRI(k, i)]*y[k];
+#pragma unroll
+    for (int j = 0; j < 3; j++) acc[j] = V2<T>{ y[2*j], y[2*j + 1] };
 }
 // Minv (packed lower) = L^-T D^-1 L^-1
 template <typename T> SO100_HD void ldl6_inverse(const T L[21], const T Dinv[6], T Minv[21]) {
@@ -879,6 +985,27 @@ SO100_HD void arm_integrate(T q[6], T v[6], T qc[6], const T acc[6], T dq[6]) {
         qc[i] = (t - q[i]) - y;
         q[i] = t;
         dq[i] = y;                              // the (compensated) increment: what the next substep's trig update rotates by
+    }
+}
+
+// arm_tau's last line (on pairs in any order, the same in all three arguments) and arm_integrate on the joint pairs (0,1), (2,3), (4,5): the same expressions element by element (one product and one
+// addend each, so the contraction is the scalar code's: fma(h, acc, v), fma(h, v, -qc)); nothing crosses from one half of a pair to the other
+template <typename T>
+SO100_HD void arm_tau_p(const V2<T> servo[3], const V2<T> bias[3], V2<T> tau[3]) {
+#pragma unroll
+    for (int j = 0; j < 3; j++) tau[j] = servo[j] - bias[j];
+}
+template <typename T>
+SO100_HD void arm_integrate_p(V2<T> q[3], V2<T> v[3], V2<T> qc[3], const V2<T> acc[3], V2<T> dq[3]) {
+    using V = V2<T>;
+    const V h = V(T(so100g::TIMESTEP));
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+        v[j] += h*acc[j];
+        const V y = h*v[j] - qc[j], t = q[j] + y;
+        qc[j] = (t - q[j]) - y;
+        q[j] = t;
+        dq[j] = y;
     }
 }
 

@@ -169,7 +169,15 @@ __device__ __forceinline__ void cube_from_lds(float (*xc)[64], int col, Cube<flo
 // outside and has nothing to overlap: it compiles the text it had.
 // SERVO (with PRE; the 32-row rollout kernels): inside the loop wave 0 computes the servo force, arm_tau without the bias, in front of the
 // mid-substep barrier instead of behind it.  Every other caller compiles the text it had.
-template <bool PADS, bool LINKS, bool PK, bool LOCAL, bool Z, bool PRE, bool SERVO = false, class Hook, class Forget>
+// PSOLVE (with SERVO; the same kernels, whose compile-time flags simulate no constraint rows): behind the peeled substep wave 0 holds q, v, qc and
+// the integration increment as the joint pairs (0,1), (2,3), (4,5) round the loop, and the servo force across the mid-substep barrier; tau, the
+// forward substitution and the integration run on the pairs (so100_physics.hpp: arm_tau_p, ldl6_forward_p, arm_integrate_p), D^-1 and the back
+// substitution on their halves, and the increment reaches the sin/cos update as the pairs it takes.  Behind the loop the
+// pairs go back into `e`.  The factor works on the rows 5 | 4 and 3 | 2 of M as the pairs CRBA walks them in (arm_mass_p, ldl6_p), and the right-hand
+// side of the solve has their order, (tau_2j+1, tau_2j): the servo force is packed so, and the bias comes so from LDS -- with PSOLVE row i of xb holds
+// the bias of joint i ^ 1, from both of its writers (wave 1 here and the caller's pre-step) to both of its readers (the peeled substep and the loop).
+// Every other caller compiles the text it had.
+template <bool PADS, bool LINKS, bool PK, bool LOCAL, bool Z, bool PRE, bool SERVO = false, bool PSOLVE = false, class Hook, class Forget>
 __device__ __forceinline__ void physics_phase_mw(const SimParams& p, int wave, int lane, EnvState& e, float ctrl[6], float cstale[3],
                                                  Arm<float>& A, const PhaseLds& L, ContactMemo& memo, Prof& prof_, Hook after_first_barrier, Forget forget_caller_state) {
     float (*xq)[64] = L.xq; float (*xc)[64] = L.xc; float (*xb)[64] = L.xb; float (*xa)[64] = L.xa; float (*xk)[64] = L.xk; float (*xm)[64] = L.xm;
@@ -213,6 +221,9 @@ __device__ __forceinline__ void physics_phase_mw(const SimParams& p, int wave, i
     // step with the arm: detection + row set-up in the first half-substep, Newton in the second.)
     static_assert(!PRE || (LOCAL && !PADS), "the pre-computed first half is written for the loop-local factor without pad contacts");
     static_assert(!SERVO || PRE, "the early servo force is written for the PRE variants");
+    static_assert(!PSOLVE || (SERVO && PK), "the pair-form solve reads the early servo force and feeds the pair-form sin/cos update");
+    using V = V2<float>;
+    V qp[3], vp[3], cp[3], dp[3];                          // PSOLVE: wave 0's alone, defined behind the peeled substep (no initialiser: see servo below)
     // SERVO: kp*u, rounded once per env step (what the compiler hoists out of the loop's arm_tau: see the peeled substep below)
     float ku[6] = { 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f };
     if constexpr (SERVO) {
@@ -226,7 +237,7 @@ __device__ __forceinline__ void physics_phase_mw(const SimParams& p, int wave, i
         if (wave == 0) {
             Arm<float> F0; float tau[6], acc0[6];
 #pragma unroll
-            for (int i = 0; i < 6; i++) { A.s[i] = xq[i][lane]; A.c[i] = xq[6 + i][lane]; F0.bias[i] = xb[i][lane]; F0.Dinv[i] = xm[15 + i][lane]; }
+            for (int i = 0; i < 6; i++) { A.s[i] = xq[i][lane]; A.c[i] = xq[6 + i][lane]; F0.bias[i] = xb[PSOLVE ? i ^ 1 : i][lane]; F0.Dinv[i] = xm[15 + i][lane]; }
 #pragma unroll
             for (int i = 1; i < 6; i++)
 #pragma unroll
@@ -247,15 +258,20 @@ __device__ __forceinline__ void physics_phase_mw(const SimParams& p, int wave, i
             SO100_PROF(6);                                 // solve (wave 0)
             arm_integrate<float>(e.q, e.v, e.qc, acc0, dq);
             SO100_PROF(9);                                 // integrate
+            if constexpr (PSOLVE) {
+#pragma unroll
+                for (int j = 0; j < 3; j++) { qp[j] = V{ e.q[2*j], e.q[2*j + 1] }; vp[j] = V{ e.v[2*j], e.v[2*j + 1] }; cp[j] = V{ e.qc[2*j], e.qc[2*j + 1] }; dp[j] = V{ dq[2*j], dq[2*j + 1] }; }
+            }
         }
     }
 #pragma unroll 1
     for (int sub = PRE ? 1 : 0; sub < p.frame_skip; sub++) {
         if (wave == 0) {
             // sin/cos: exact at the first substep, then rotated by the integration increment (arm_substep does the same)
-            if (!PRE && sub == 0) arm_trig<float>(e.q, A); else arm_trig_update<float, PK>(e.q, dq, A);
+            if constexpr (PSOLVE) arm_trig_update_p<float>(dp, A);
+            else if (!PRE && sub == 0) arm_trig<float>(e.q, A); else arm_trig_update<float, PK>(e.q, dq, A);
 #pragma unroll
-            for (int i = 0; i < 6; i++) { xq[i][lane] = A.s[i]; xq[6 + i][lane] = A.c[i]; xq[12 + i][lane] = e.v[i]; }
+            for (int i = 0; i < 6; i++) { xq[i][lane] = A.s[i]; xq[6 + i][lane] = A.c[i]; xq[12 + i][lane] = PSOLVE ? ((i & 1) ? vp[i/2].y : vp[i/2].x) : e.v[i]; }
             if (pads) {
 #pragma unroll
                 for (int i = 0; i < 6; i++) xq[18 + i][lane] = e.q[i];
@@ -280,10 +296,21 @@ __device__ __forceinline__ void physics_phase_mw(const SimParams& p, int wave, i
         static_assert(!LOCAL || !PADS, "the loop-local factor is written for the variants without pad contacts (nothing publishes M)");
         Arm<float> Fl; Arm<float>& F = LOCAL ? Fl : A;
         float servo[6];                                    // SERVO: wave 0's alone, defined in front of the barrier and read behind it (no initialiser: one would be six moves on every wave's path)
+        V servop[3];                                       // PSOLVE: the same as the pairs (1 | 0), (3 | 2), (5 | 4)
         if (LOCAL && wave == 0) {
 #pragma unroll
             for (int i = 0; i < 6; i++) { F.s[i] = A.s[i]; F.c[i] = A.c[i]; }
-            if constexpr (SERVO) {
+            if constexpr (PSOLVE) {
+                // (the block below on the pairs' halves)
+#pragma unroll
+                for (int i = 0; i < 6; i++) {
+                    float f = __builtin_fmaf(-(float)so100g::ACT_KP, (i & 1) ? qp[i/2].y : qp[i/2].x, ku[i]);
+                    f = __builtin_fmaf(-(float)so100g::ACT_KV[i], (i & 1) ? vp[i/2].y : vp[i/2].x, f);
+                    servo[i] = tclamp(f, (float)-so100g::ACT_FORCE, (float)so100g::ACT_FORCE);
+                }
+#pragma unroll
+                for (int j = 0; j < 3; j++) servop[j] = V{ servo[2*j + 1], servo[2*j] };      // in the order of the factor's pairs (ldl6_forward_p)
+            } else if constexpr (SERVO) {
                 // arm_tau's half that does not need the bias (q, v and ctrl only), in front of the barrier; behind it wave 0 subtracts the bias.  The
                 // barrier is where wave 0 waits for wave 1's bias anyway, and these eighteen instructions stood behind it.  Written out in the rounding
                 // the loop's arm_tau compiles to, like the peeled substep above.  (In front of arm_mass: behind arm_factor the register allocation
@@ -295,8 +322,14 @@ __device__ __forceinline__ void physics_phase_mw(const SimParams& p, int wave, i
                     servo[i] = tclamp(f, (float)-so100g::ACT_FORCE, (float)so100g::ACT_FORCE);
                 }
             }
-            arm_mass<float, PK, Z>(F);
-            arm_factor<float>(p.flags, F);
+            if constexpr (PSOLVE) {                        // the rows 5 | 4 and 3 | 2 from CRBA to the factor as the pairs they are walked in
+                V R5[4], R3[2];
+                arm_mass_p<float, Z>(F, R5, R3);
+                ldl6_p<float>(F.M, R5, R3, F.Dinv);
+            } else {
+                arm_mass<float, PK, Z>(F);
+                arm_factor<float>(p.flags, F);
+            }
             SO100_PROF(4);                                 // CRBA + factor (wave 0)
         } else if (LOCAL && wave == 1) {
             Arm<float> R; float v1[6];
@@ -304,7 +337,7 @@ __device__ __forceinline__ void physics_phase_mw(const SimParams& p, int wave, i
             for (int i = 0; i < 6; i++) { R.s[i] = xq[i][lane]; R.c[i] = xq[6 + i][lane]; v1[i] = xq[12 + i][lane]; }
             arm_bias<float, PK, Z>(v1, R);
 #pragma unroll
-            for (int i = 0; i < 6; i++) xb[i][lane] = R.bias[i];
+            for (int i = 0; i < 6; i++) xb[PSOLVE ? i ^ 1 : i][lane] = R.bias[i];
             SO100_PROF(4);                                 // RNEA (wave 1)
         } else if (wave == 1) {
             float v1[6], q1[6] = { 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f }, c1[6] = { 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f };
@@ -374,7 +407,20 @@ __device__ __forceinline__ void physics_phase_mw(const SimParams& p, int wave, i
         // ---- second half: solves
         float cal[3], caa[3], acc0[6]; ArmRows<float> r0; float pgs_res = 0.0f;
         if (wave == 2 && cube_live) { cube_solve<float>(cb, p.flags, p.contact_iters, cprep, cal, caa); SO100_PROF(6); }   // Newton behind the arm's solve
-        if (wave == 0) {
+        if constexpr (PSOLVE) {
+            // solve and integration in one stretch: nothing stands between them without pad contacts (behind it wave 0 adds nothing to slots 8 and 9)
+            if (wave == 0) {
+                V bp[3], xp[3], accp[3];
+#pragma unroll
+                for (int j = 0; j < 3; j++) bp[j] = V{ xb[2*j][lane], xb[2*j + 1][lane] };      // = (bias_2j+1, bias_2j): see above
+                arm_tau_p<float>(servop, bp, xp);
+                ldl6_forward_p<float>(F.M, xp);
+                ldl6_back_p<float>(F.M, F.Dinv, xp, accp);
+                SO100_PROF(6);                             // solve (wave 0)
+                arm_integrate_p<float>(qp, vp, cp, accp, dp);
+                SO100_PROF(9);                             // integrate
+            }
+        } else if (wave == 0) {
 #pragma unroll
             for (int i = 0; i < 6; i++) F.bias[i] = xb[i][lane];
             float tau[6];
@@ -467,7 +513,7 @@ __device__ __forceinline__ void physics_phase_mw(const SimParams& p, int wave, i
                 if (nc > 0 && (unsigned)e.cload < (CLOAD_MAX << 16))       // this launch's contact substeps ride in the upper half until the
                     e.cload = (int)((unsigned)e.cload + (1u << 16));         // launch folds them in; saturated at CLOAD_MAX, below the sign bit
             }
-            arm_integrate<float>(e.q, e.v, e.qc, acc0, dq);
+            if constexpr (!PSOLVE) arm_integrate<float>(e.q, e.v, e.qc, acc0, dq);
         }
         if (wave == 2 && cube_live) {
             if (padcube && (__float_as_int(xa[12][lane]) & 256) != 0) {      // arm and cube were solved together on the contact wave
@@ -477,6 +523,12 @@ __device__ __forceinline__ void physics_phase_mw(const SimParams& p, int wave, i
             cube_integrate<float>(cb, cal, caa);
         }
         SO100_PROF(9);                                     // integrate
+    }
+    if constexpr (PSOLVE) {
+        if (wave == 0) {
+#pragma unroll
+            for (int j = 0; j < 3; j++) { e.q[2*j] = qp[j].x; e.q[2*j + 1] = qp[j].y; e.v[2*j] = vp[j].x; e.v[2*j + 1] = vp[j].y; e.qc[2*j] = cp[j].x; e.qc[2*j + 1] = cp[j].y; }
+        }
     }
     if (cube_live) {
         if (wave == 2) cube_to_lds(xc, lane, cb);
@@ -969,7 +1021,7 @@ __global__ void __launch_bounds__(64*NW) so100_rollout_fused(SimParams p, float*
             SO100_PROF(13);                                        // pre-step sin/cos (waves 1, 2)
             arm_bias<float, PKF, PKF>(v1, R);
 #pragma unroll
-            for (int i = 0; i < 6; i++) xb[i][lane] = R.bias[i];
+            for (int i = 0; i < 6; i++) xb[MH ? i ^ 1 : i][lane] = R.bias[i];      // (physics_phase_mw: PSOLVE = MH reads the pairs swapped)
             SO100_PROF(14);                                        // pre-step RNEA (wave 1) / CRBA + factor (wave 2)
           } else if (wave == 2) {
             // wave 2: sin/cos (its own: no barrier between the two waves), CRBA + factor -> xf
@@ -1001,7 +1053,7 @@ __global__ void __launch_bounds__(64*NW) so100_rollout_fused(SimParams p, float*
         {
             Arm<float> A;
             const PhaseLds lds{ xq, xc, xb, pool, xa, xk, PRE ? xf : xm, pbuf, xw };
-            physics_phase_mw<PADS, LINKS, PKF, LOCALF, PKF, PRE, MH>(p, wave, lane, e, ctx.ctrl, cstale, A, lds, memo, prof_, [&](int sub) {
+            physics_phase_mw<PADS, LINKS, PKF, LOCALF, PKF, PRE, MH, MH>(p, wave, lane, e, ctx.ctrl, cstale, A, lds, memo, prof_, [&](int sub) {
                 if (wave == 3 && sub == 0 && t + 1 < ra.T) {       // wave 0 has consumed xn before this barrier
                     float eps[8];
                     policy_noise(p.env_id_offset + (uint32_t)env, ra.step_counter0 + (uint32_t)(t + 1), p.seed_lo, p.seed_hi, eps);
