@@ -5,7 +5,13 @@ launch, the cost of a sequence is |cube - ee| summed over the horizon (from the 
 the cost-weighted mean is executed through step().  Printed next to the zero-action and the uniformly random baselines, like
 examples/ik_reach.py.
 
-    python examples/mppi_reach.py [--envs 8] [--samples 256] [--horizon 8] [--steps 100] [--contact]
+--plan torch (the default) does everything around the rollout in torch.  --plan query is three calls on one stream with nothing in between:
+So100Sim.plan_sample draws the candidates straight into the trajectory query's layout (Philox noise, reproducible from (seed, draw) in any language),
+trajectory rolls them out, cost_blend sums the cost family of include/so100_query.h (the cube target: |cube - ee|^2 per step), takes the soft-min weights
+and returns the blended plan, already shifted.  That cost is quadratic in the distance where the torch path sums norms, so the two paths have
+temperatures of their own and are not expected to end at the same figure; --plan query prints both paths' lines.
+
+    python examples/mppi_reach.py [--envs 8] [--samples 256] [--horizon 8] [--steps 100] [--contact] [--plan {torch,query}]
 """
 import argparse
 import os
@@ -19,12 +25,34 @@ from so100_mujoco_rl_amd.lib import ENV01, F_CUBE_PINNED, F_REFERENCE, So100Sim 
 
 class Mppi:
     """policy(sim, obs) -> action [N, 6].  plan [N, horizon, 6] is the mean sequence, shifted by one step after every call; sigma: the
-    sampling noise (actions live in [-1, 1]); temperature: the softmax's, in metres summed over the horizon."""
-    def __init__(self, samples=256, horizon=8, sigma=0.5, temperature=0.02, seed=0):
+    sampling noise (actions live in [-1, 1]); temperature: the softmax's, in metres summed over the horizon (plan "torch"; None: 0.02) or in
+    metres squared summed over the horizon (plan "query"; None: QUERY_TEMPERATURE)."""
+    QUERY_TEMPERATURE = 0.01                                         # d(sum |r|^2) = 2 |r| d(sum |r|): the torch path's 0.02 at |r| = 0.25 m
+
+    def __init__(self, samples=256, horizon=8, sigma=0.5, temperature=None, seed=0, plan="torch"):
+        if plan not in ("torch", "query"):
+            raise ValueError(f"plan must be 'torch' or 'query', got {plan!r}")
+        if temperature is None:
+            temperature = 0.02 if plan == "torch" else self.QUERY_TEMPERATURE
         self.K, self.T, self.sigma, self.temperature = samples, horizon, sigma, temperature
-        self.gen, self.seed, self.plan = None, seed, None
+        self.gen, self.seed, self.plan, self.mode, self.draw = None, seed, None, plan, 0
+
+    def query_step(self, sim):
+        """plan_sample -> trajectory -> cost_blend; self.plan is [horizon, N, 6] here, the queries' own layout"""
+        if self.plan is None:
+            self.plan = torch.zeros(self.T, sim.n, 6, device=sim.device)
+        qpos, qvel = sim.get_state()                                 # [13, N], [12, N]
+        cand = sim.plan_sample(self.plan, self.K, (self.sigma,)*5 + (0.0,), seed=self.seed, draw=self.draw, qpos=qpos.t(), qvel=qvel.t())
+        self.draw += 1                                               # the jaw's sigma is 0: it does not move the end-effector point
+        roll = sim.trajectory(cand["ctrl"], cand["qpos"], cand["qvel"], mode="actions")
+        out = sim.cost_blend(roll["qpos"], None, cand["ctrl"], self.K, temperature=self.temperature, bad_step=roll["bad_step"], u_fallback=self.plan,
+                             shift=1, tail="zero", target_mode="cube")
+        self.plan = out["u_plan"]
+        return out["u_first"].contiguous()
 
     def __call__(self, sim, obs):
+        if self.mode == "query":
+            return self.query_step(sim)
         N, K, T = sim.n, self.K, self.T
         if self.plan is None:
             self.plan = torch.zeros(N, T, 6, device=sim.device)
@@ -77,9 +105,16 @@ def main():
     ap.add_argument("--envs", type=int, default=8); ap.add_argument("--samples", type=int, default=256)
     ap.add_argument("--horizon", type=int, default=8); ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--contact", action="store_true", help="the reference scene's contacts (default: contact disabled, cube pinned)")
+    ap.add_argument("--plan", choices=("torch", "query"), default="torch", help="torch: sample and re-weight in torch; query: plan_sample -> trajectory -> cost_blend")
     args = ap.parse_args()
     torch.manual_seed(0)
-    for name, policy in (("MPPI", Mppi(args.samples, args.horizon)), ("zero action", zero_action), ("random", random_action)):
+    # --plan query prints both MPPI lines: the torch path's (the default's, unchanged) and the query path's with its own temperature
+    planners = [("MPPI", Mppi(args.samples, args.horizon))]
+    if args.plan == "query":
+        query = Mppi(args.samples, args.horizon, plan="query")
+        planners.append(("MPPI (query)", query))
+        print(f"temperature: torch path {planners[0][1].temperature} m, query path {query.temperature} m^2, each summed over the horizon")
+    for name, policy in planners + [("zero action", zero_action), ("random", random_action)]:
         sim = So100Sim(ENV01, args.envs, flags=F_REFERENCE if args.contact else F_CUBE_PINNED, max_episode_steps=0, seed=0)
         d0, d1, r = run(sim, args.steps, policy)
         print(f"{name:12s} mean |cube - ee|: {d0:.4f} m at reset -> {d1:.4f} m after {args.steps} steps; reward/step {r:+.4f}")

@@ -3,7 +3,9 @@
  * end up under M open-loop control sequences (the trajectory query), and the finite-difference linearisation of such a control step, one GPU
  * wave per problem (the derivatives query), the Riccati pass on such linearisations (the LQR query) and the rollouts under the feedback law it
  * gives, one GPU lane per rollout (the closed-loop query), and the cost of such plans: its quadratic model in the LQR query's input layout (the
- * cost-terms query) and the line search's choice among the closed-loop query's candidates (the cost-select query).
+ * cost-terms query) and the line search's choice among the closed-loop query's candidates (the cost-select query), and the two ends of a sampling
+ * planner's step round the trajectory query: the candidate plans in its input layout (the plan-sample query) and their cost-weighted blend (the
+ * cost-blend query).
  *
  * Additive to so100_sim.h (SO100_ABI_VERSION is unchanged) and under its conventions: extern "C"; `*_dev` pointers are DEVICE
  * pointers owned by the caller; 0 on success, a negative SO100_E_* code otherwise with the message in so100_last_error(); all
@@ -475,6 +477,93 @@ typedef struct {
 } so100_cost_select_io;
 
 int so100_query_cost_select(so100_sim* sim, const so100_cost_select_io* io, int32_t M, void* hip_stream);
+
+/* Plan sample: the candidates of a sampling planner (MPPI, CEM), K perturbed copies of each of N nominal plans, written in the trajectory
+ * query's INPUT layout -- ctrl, qpos_rep and qvel_rep are bit for bit what so100_query_trajectory takes for M = N K problems, with no operation
+ * in between.  One GPU lane per candidate.  The handle is taken for the device and the error slot: its state is NEVER read or written.
+ *
+ * Candidates.  plan [T][6][N] (SoA); candidate (n, k) is column n K + k of ctrl [T][6][NK]:
+ *     ctrl[t][j][n K + k] = clamp(plan[t][j][n] + sigma[j] eps(n, k, t, j), u_lo, u_hi)       the product and the sum each rounded once
+ * Candidate k = 0 has eps = 0 and a dimension with sigma[j] = 0 is never perturbed: both are clamp(plan) itself.  A plan entry that is not
+ * finite is NaN in all K candidates (the trajectory query then reports bad_step for them).
+ * Noise.  A function of (seed, draw, id_offset + n, k, t, j) alone, so a problem's candidates are the same bits whatever N is and wherever it
+ * stands in the batch: for b in 0, 1 the Philox4x32-10 counter is (id_offset + n, draw, k, 0x4D500000 | t << 1 | b), the key (seed & 0xffffffff,
+ * seed >> 32); words (2i, 2i + 1) of block b give eps[4b + 2i], eps[4b + 2i + 1] by the policy noise's Box-Muller transform (u1 = ((r_even >> 8) + 1) 2^-24,
+ * u2 = (r_odd >> 8) 2^-24, rad = sqrt(-2 ln u1), ang = 2 pi u2 - pi, (rad cos ang, rad sin ang)); the first six of the eight are j = 0..5.
+ * draw: the planner's call counter.  id_offset: the global index of problem 0 (a sharded caller draws what an unsharded one would).
+ * Fan-out.  qpos_rep [13][NK] and qvel_rep [12][NK]: each problem's start copied to its K columns, bit for bit.
+ * Every output is nullable; at least one is required.
+ *
+ * Argument errors, in this order: a null handle or io; N < 1; T outside 1..SO100_TRAJ_MAX_T; K outside 1..SO100_MPPI_MAX_K or N * K over
+ * INT32_MAX; a sigma that is negative or not finite; u_lo or u_hi not finite or u_lo > u_hi; a null plan_dev; qvel_dev without qpos_dev;
+ * qpos_rep_dev without qpos_dev or qvel_rep_dev without qvel_dev; no output. */
+#define SO100_MPPI_MAX_K 4096
+typedef struct {
+    const float* plan_dev;             /* [T][6][N] the nominal controls                                            */
+    float        sigma[6];             /* finite and >= 0; 0: that dimension is never perturbed                     */
+    float        u_lo;                 /* finite, u_lo <= u_hi                                                      */
+    float        u_hi;
+    int32_t      K;                    /* candidates per problem, 1..4096; N * K <= INT32_MAX                       */
+    int32_t      T;                    /* control steps, 1..4096                                                    */
+    uint64_t     seed;
+    uint32_t     draw;                 /* the planner's call counter                                                */
+    uint32_t     id_offset;            /* the global index of problem 0                                             */
+    const float* qpos_dev;             /* [13][N] or NULL                                                           */
+    const float* qvel_dev;             /* [12][N] or NULL                                                           */
+    float*       ctrl_dev;             /* [T][6][NK]                                                                */
+    float*       qpos_rep_dev;         /* [13][NK]                                                                  */
+    float*       qvel_rep_dev;         /* [12][NK]                                                                  */
+} so100_plan_sample_io;
+
+int so100_query_plan_sample(so100_sim* sim, const so100_plan_sample_io* io, int32_t N, void* hip_stream);
+
+/* Cost blend: the sampling planner's decision on the trajectory query's output -- the total cost J of each of N * K rollouts (so100_cost_def,
+ * exactly as so100_query_cost_select computes it), per problem the soft-min weights over its K candidates and the weighted mean of their controls
+ * as the next plan.  One GPU workgroup per problem.  The handle's state is NEVER read or written.
+ *
+ * Inputs.  Those of so100_cost_select_io with K in place of L: rollout (n, k) in column n K + k of qpos_traj [T][13][NK], qvel_traj [T][12][NK]
+ * (NULL: zero), u_traj [T][6][NK] the controls applied (so100_plan_sample_io's ctrl), bad_step [NK] (NULL: none failed); targets per PROBLEM;
+ * u_fallback [T][6][N] (nullable).  temperature: lambda.
+ * Outputs.  cost [NK], best [N], best_cost [N]: as in so100_cost_select_io.
+ *     weight[n K + k] = exp(-(J_k - J_min) / lambda) / sum_k exp(-(J_k - J_min) / lambda)       0 where J_k = +inf; all 0 where best = -1
+ *     ess[n]          = 1 / sum_k w_k^2   the effective sample size; 0 where best = -1
+ *     blend[t][j]     = sum_k w_k u_traj[t][j][n K + k]       (a candidate of weight 0 is not read into it)
+ * u_first [6][N]: row 0 of the blend, the control to execute now.  u_plan [T][6][N]: the blend; with shift = 1 row t holds blended row t + 1 and
+ * row T - 1 is 0 (SO100_BLEND_TAIL_ZERO: the actions mode's "stay") or blended row T - 1 again (SO100_BLEND_TAIL_HOLD: servo targets) -- the
+ * receding-horizon step.  Where best = -1 the blend is the column of u_fallback, or NaN without one, shifted the same way (a ZERO tail row is 0 there too).
+ * J_min is an exact minimum and every sum over k is taken in one fixed order that depends on K alone: a problem's outputs are the same bits on
+ * every run, whatever N is and wherever the problem stands, and each output is the same whether requested alone or with the others.  K = 1
+ * returns w = 1 and its only candidate's controls, bit for bit.  Every output is nullable; at least one is required.
+ *
+ * Argument errors, in this order: a null handle or io; N < 1; T outside 1..SO100_TRAJ_MAX_T; K outside 1..SO100_MPPI_MAX_K or N * K over
+ * INT32_MAX; those of the cost as in so100_cost_terms_io (from the null cost to q_nom); a temperature that is not finite or not positive;
+ * shift not 0 or 1; an unknown tail; a required pointer (qpos_traj_dev, u_traj_dev; target_dev unless the target is the cube) that is NULL;
+ * no output. */
+#define SO100_BLEND_TAIL_ZERO 0
+#define SO100_BLEND_TAIL_HOLD 1
+typedef struct {
+    const so100_cost_def* cost;        /* HOST pointer                                                              */
+    const float* target_dev;           /* [3][N] or [T][3][N] by target_mode; not read with the cube target         */
+    int32_t      T;                    /* horizon, 1..4096                                                          */
+    int32_t      K;                    /* candidates per problem, 1..4096; N * K <= INT32_MAX                       */
+    const float* qpos_traj_dev;        /* [T][13][NK]                                                               */
+    const float* qvel_traj_dev;        /* [T][12][NK] or NULL: zero                                                 */
+    const float* u_traj_dev;           /* [T][6][NK]                                                                */
+    const int32_t* bad_step_dev;       /* [NK] or NULL                                                              */
+    const float* u_fallback_dev;       /* [T][6][N] or NULL                                                         */
+    float        temperature;          /* lambda, finite and > 0                                                    */
+    int32_t      shift;                /* 0, or 1: u_plan is the blend moved up one step                            */
+    int32_t      tail;                 /* SO100_BLEND_TAIL_*: row T - 1 of a shifted u_plan                         */
+    float*       cost_dev;             /* [NK]                                                                      */
+    int32_t*     best_dev;             /* [N]                                                                       */
+    float*       best_cost_dev;        /* [N]                                                                       */
+    float*       weight_dev;           /* [NK]                                                                      */
+    float*       ess_dev;              /* [N]                                                                       */
+    float*       u_plan_dev;           /* [T][6][N]                                                                 */
+    float*       u_first_dev;          /* [6][N]                                                                    */
+} so100_cost_blend_io;
+
+int so100_query_cost_blend(so100_sim* sim, const so100_cost_blend_io* io, int32_t N, void* hip_stream);
 
 #ifdef __cplusplus
 }

@@ -219,12 +219,28 @@ class CostSelectIO(C.Structure):
                                           "u_best_dev")]
 
 
+class PlanSampleIO(C.Structure):
+    _fields_ = [("plan_dev", C.c_void_p), ("sigma", C.c_float*6), ("u_lo", C.c_float), ("u_hi", C.c_float), ("K", C.c_int32), ("T", C.c_int32),
+                ("seed", C.c_uint64), ("draw", C.c_uint32), ("id_offset", C.c_uint32)] + \
+               [(n, C.c_void_p) for n in ("qpos_dev", "qvel_dev", "ctrl_dev", "qpos_rep_dev", "qvel_rep_dev")]
+
+
+class CostBlendIO(C.Structure):
+    _fields_ = [("cost", C.POINTER(CostDef)), ("target_dev", C.c_void_p), ("T", C.c_int32), ("K", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("qpos_traj_dev", "qvel_traj_dev", "u_traj_dev", "bad_step_dev", "u_fallback_dev")] + \
+               [("temperature", C.c_float), ("shift", C.c_int32), ("tail", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("cost_dev", "best_dev", "best_cost_dev", "weight_dev", "ess_dev", "u_plan_dev", "u_first_dev")]
+
+
 QUERY_EXPORTS = ["so100_query_kinematics", "so100_query_jacobian", "so100_query_dynamics", "so100_query_ik", "so100_query_forward",
                  "so100_query_trajectory", "so100_query_derivatives", "so100_query_lqr", "so100_query_closed_loop", "so100_query_cost_terms",
-                 "so100_query_cost_select"]
+                 "so100_query_cost_select", "so100_query_plan_sample", "so100_query_cost_blend"]
 QUERY_IO = {"so100_query_kinematics": KinematicsIO, "so100_query_jacobian": JacobianIO, "so100_query_dynamics": DynamicsIO, "so100_query_ik": IkIO,
             "so100_query_forward": ForwardIO, "so100_query_trajectory": TrajectoryIO, "so100_query_derivatives": DerivativesIO, "so100_query_lqr": LqrIO,
-            "so100_query_closed_loop": ClosedLoopIO, "so100_query_cost_terms": CostTermsIO, "so100_query_cost_select": CostSelectIO}
+            "so100_query_closed_loop": ClosedLoopIO, "so100_query_cost_terms": CostTermsIO, "so100_query_cost_select": CostSelectIO,
+            "so100_query_plan_sample": PlanSampleIO, "so100_query_cost_blend": CostBlendIO}
+MPPI_MAX_K = 4096                                              # SO100_MPPI_MAX_K
+BLEND_TAILS = {"zero": 0, "hold": 1}                           # SO100_BLEND_TAIL_*
 COST_TARGETS = {"fixed": 0, "traj": 1, "cube": 2}               # SO100_COST_TARGET_*
 DERIV_NX, DERIV_NU, DERIV_EPS = 24, 6, 2.0**-6                 # SO100_DERIV_*
 LQR_NU, LQR_MAX_T = 6, 4096                                    # SO100_LQR_*
@@ -920,6 +936,75 @@ class So100Sim(_Handle):
                           bc.data_ptr(), ub.data_ptr())
         _check(self.L.so100_query_cost_select(self.h, C.byref(io), M, self._stream()), "so100_query_cost_select")
         return {"cost": cost.unflatten(0, (M, L)), "best": best, "best_cost": bc, "u_best": ub.permute(0, 2, 1)}
+
+    def plan_sample(self, plan, K, sigma, *, seed=0, draw=0, id_offset=0, u_lo=-1.0, u_hi=1.0, qpos=None, qvel=None):
+        """The candidates of a sampling planner in one launch, laid out as trajectory() reads them: K copies of each of the N plans [T, N, 6],
+        perturbed by sigma (6 values or one for all; 0: never perturbed) times a standard normal and clamped to [u_lo, u_hi]; candidate 0 of every
+        problem is the clamped plan itself.  The noise is a function of (seed, draw, id_offset + n, k, t, j) alone (include/so100_query.h): draw is
+        the planner's call counter, id_offset the global index of problem 0.  qpos [N, 13] and qvel [N, 12] (optional): the start states to fan
+        out.  Returns views of the SoA buffers, candidate (n, k) in row n K + k: "ctrl" [T, N K, 6] and, where given, "qpos" [N K, 13] and "qvel"
+        [N K, 12] -- trajectory(res["ctrl"], res["qpos"], res["qvel"]) copies none of them."""
+        plan = torch.as_tensor(plan, dtype=torch.float32, device=self.device)
+        if plan.dim() != 3 or plan.shape[2] != 6 or plan.shape[0] < 1 or plan.shape[1] < 1:
+            raise So100Error(f"plan: want a [T, N, 6] tensor, got {tuple(plan.shape)}")
+        T, N = plan.shape[0], plan.shape[1]
+        if not 1 <= K <= MPPI_MAX_K:
+            raise So100Error(f"plan_sample: K must be in 1..{MPPI_MAX_K}, got {K!r}")
+        if qvel is not None and qpos is None:
+            raise So100Error("plan_sample: qvel needs qpos")
+        ps = plan.permute(0, 2, 1).contiguous()
+        qs, vs = self._soa(qpos, 13, "qpos"), self._soa(qvel, 12, "qvel")
+        self._problems(ps[0], qs, vs)
+        ctrl = self._out(N*K, T, 6)
+        qr, vr = (None if qs is None else self._out(N*K, 13)), (None if vs is None else self._out(N*K, 12))
+        sg = torch.as_tensor(sigma, dtype=torch.float32).reshape(-1).tolist()      # a number of any kind (one for all), or six
+        if len(sg) not in (1, 6):
+            raise So100Error(f"sigma: want 6 values or one for all, got {len(sg)}")
+        sg = (C.c_float*6)(*(sg*6 if len(sg) == 1 else sg))
+        io = PlanSampleIO(ps.data_ptr(), sg, u_lo, u_hi, K, T, seed, draw, id_offset, _optr(qs), _optr(vs), ctrl.data_ptr(), _optr(qr), _optr(vr))
+        _check(self.L.so100_query_plan_sample(self.h, C.byref(io), N, self._stream()), "so100_query_plan_sample")
+        res = {"ctrl": ctrl.permute(0, 2, 1)}
+        if qr is not None:
+            res["qpos"] = qr.t()
+        if vr is not None:
+            res["qvel"] = vr.t()
+        return res
+
+    def cost_blend(self, qpos, qvel, u, K, *, temperature, bad_step=None, u_fallback=None, shift=0, tail="zero", target=None, target_mode=None, link=EE_LINK,
+                   offset=None, w_point=1.0, w_q=0.0, q_nom=0.0, w_v=0.0, w_u=0.0, w_terminal=1.0):
+        """The sampling planner's decision on trajectory()'s output in one launch: the total cost of each of the N K rollouts, per problem the
+        soft-min weights exp(-(J - J_min) / temperature), normalised, over its K candidates, and the weighted mean of their controls as the next plan.
+        qpos [T, N K, 13], qvel [T, N K, 12] (None: zero) and u [T, N K, 6] (the controls applied: plan_sample()'s "ctrl") in trajectory()'s
+        shapes, candidate (n, k) in row n K + k; bad_step [N K] int32 (None: no rollout failed), u_fallback [T, N, 6] (None: NaN): the plan kept where
+        every candidate failed.  shift = 1 moves the plan up one step, its last row 0 (tail "zero") or the blend's last row again ("hold").  The cost
+        arguments: as in cost_terms(); targets are per problem.  Returns "cost" [N, K] (+inf for a failed rollout), "best" [N] int32 (-1: all failed),
+        "best_cost" [N], "weight" [N, K], "ess" [N] (1 / sum w^2), "u_plan" [T, N, 6] and "u_first" [N, 6] (row 0 of the blend before the shift)."""
+        u = torch.as_tensor(u, dtype=torch.float32, device=self.device)
+        if u.dim() != 3 or u.shape[2] != 6 or u.shape[0] < 1 or not 1 <= K <= MPPI_MAX_K or u.shape[1] < K or u.shape[1] % K:
+            raise So100Error(f"u: want a [T, N K, 6] tensor with K = {K!r} in 1..{MPPI_MAX_K}, got {tuple(u.shape)}")
+        if tail not in BLEND_TAILS:
+            raise So100Error(f"cost_blend: tail must be one of {sorted(BLEND_TAILS)}, got {tail!r}")
+        T, NK = u.shape[0], u.shape[1]
+        N = NK//K
+        rows = lambda t, k, name: None if t is None else self._shaped(t, (T, NK, k), name).permute(0, 2, 1).contiguous()     # trajectory()'s views: no copy
+        qs, vs, us = rows(qpos, 13, "qpos"), rows(qvel, 12, "qvel"), rows(u, 6, "u")
+        if qs is None:
+            raise So100Error("cost_blend: qpos is required")
+        bs = None
+        if bad_step is not None:
+            bs = torch.as_tensor(bad_step, dtype=torch.int32, device=self.device)
+            if bs.numel() != NK:
+                raise So100Error(f"bad_step: want {NK} values, got {tuple(bs.shape)}")
+            bs = bs.reshape(NK).contiguous()
+        fb = None if u_fallback is None else self._shaped(u_fallback, (T, N, 6), "u_fallback").permute(0, 2, 1).contiguous()
+        d, keep, tg = self._cost("cost_blend", T, N, target, target_mode, link, offset, w_point, w_q, q_nom, w_v, w_u, w_terminal)
+        cost, best, bc, wt, ess = self._out(NK), self._out(N, dtype=torch.int32), self._out(N), self._out(NK), self._out(N)
+        up, uf = self._out(N, T, 6), self._out(N, 6)
+        io = CostBlendIO(C.pointer(d), _optr(tg), T, K, qs.data_ptr(), _optr(vs), us.data_ptr(), _optr(bs), _optr(fb), temperature, shift, BLEND_TAILS[tail],
+                         cost.data_ptr(), best.data_ptr(), bc.data_ptr(), wt.data_ptr(), ess.data_ptr(), up.data_ptr(), uf.data_ptr())
+        _check(self.L.so100_query_cost_blend(self.h, C.byref(io), N, self._stream()), "so100_query_cost_blend")
+        return {"cost": cost.unflatten(0, (N, K)), "best": best, "best_cost": bc, "weight": wt.unflatten(0, (N, K)), "ess": ess, "u_plan": up.permute(0, 2, 1),
+                "u_first": uf.t()}
 
     def _shaped(self, t, shape, name):
         """a float32 tensor of exactly `shape` on the handle's device, in whatever strides it has"""

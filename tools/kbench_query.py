@@ -8,6 +8,7 @@
     python tools/kbench_query.py --lqr [--form mfma] [--out profiles/lqr_kbench.json] [--commit LABEL] [--rounds 5]
     python tools/kbench_query.py --closed-loop [--form global] [--out profiles/closed_loop_kbench.json] [--commit LABEL] [--rounds 5]
     python tools/kbench_query.py --cost [--out profiles/cost_kbench.json] [--commit LABEL] [--rounds 5]
+    python tools/kbench_query.py --mppi [--out profiles/mppi_kbench.json] [--commit LABEL] [--rounds 5]
 
 Cases, at M = 4096 and M = 1 048 576 problems: kinematics with every output and with the end-effector point alone, the Jacobian (jacp and
 jacr), the dynamics (M, bias and tau) and the IK.  Poses are uniform over the joint ranges; the IK problems are the 400 of the tests' recipe
@@ -43,7 +44,11 @@ reads its gains (global: the product; lds: SO100_LIB=<a side build with -DSO100_
 
 --cost times the two cost queries (so100_query_cost_terms with every output; so100_query_cost_select with every output at L = 8) at (M, T) in {(8, 8),
 (4096, 8), (4096, 64)}, both nx for the terms, beside what examples/ilqr_reach.py did before they existed: So100Sim.jacobian plus the einsums, zero
-fills and cats for the terms; the torch sum, mask, argmin and gather for the selection (cost_main)."""
+fills and cats for the terms; the torch sum, mask, argmin and gather for the selection (cost_main).
+
+--mppi times the two sampling-planner queries (so100_query_plan_sample and so100_query_cost_blend, every output) at (N, K, T) in {(8, 64, 8), (8, 256, 8),
+(512, 256, 16)} beside the torch arithmetic of examples/mppi_reach.py for the same job, and at the first two sizes the whole planning step: the three
+queries against the example's torch path around the same trajectory call (mppi_main)."""
 import argparse
 import ctypes as C
 import json
@@ -707,6 +712,114 @@ def cost_main(a):
         fh.write("\n")
 
 
+MPPI_SIZES = [(8, 64, 8, 50, 20, True), (8, 256, 8, 50, 20, True), (512, 256, 16, 5, 3, False)]      # (N, K, T, query calls, torch runs per round, time the whole step too)
+MPPI_SIGMA, MPPI_TEMPERATURE = 0.5, 0.01
+
+
+def mppi_main(a):
+    """One so100_query_plan_sample / so100_query_cost_blend call against the torch arithmetic of examples/mppi_reach.py for the same job on identical
+    inputs, and the whole planning step (plan_sample -> trajectory -> cost_blend against the example's torch path around the same trajectory call).  An
+    event pair round each unit, enqueued without waiting; medians of alternated rounds."""
+    doc = {"what": "HIP-event time of one so100_query_plan_sample call (ctrl, qpos_rep, qvel_rep) against randn, the zeroing of candidate 0, add, scale, clamp, "
+                   "the two repeat_interleaves and the permute().contiguous() of examples/mppi_reach.py; of one so100_query_cost_blend call (all seven outputs, "
+                   "shift 1) against the example's cost sum from the trajectory query's ee rows, mask, min, softmax, weighted sum and shift (the query recomputes "
+                   "the point from qpos and its cost is quadratic: the same job, not the same numbers); and of the whole planning step, the three queries against "
+                   "the example's torch path around the same so100_query_trajectory call.  An event pair round each unit, medians of alternated rounds.  A "
+                   "record, not a gate: nothing comparable existed",
+           "commit": a.commit, "card": torch.cuda.get_device_name(0), "rounds": a.rounds, "cases": []}
+
+    def pair(call):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(); call(); e1.record()
+        return e0, e1
+
+    def timed(call, n):
+        pairs = [pair(call) for _ in range(n)]
+        torch.cuda.synchronize()
+        return sum(e0.elapsed_time(e1) for e0, e1 in pairs)*1e3/n
+
+    def rounds(one_query, one_torch, reps, loops):
+        timed(one_query, 2); timed(one_torch, 1)
+        tq, tt = [], []
+        for _ in range(a.rounds):
+            tq.append(timed(one_query, reps)); tt.append(timed(one_torch, loops))
+        mq, mt = statistics.median(tq), statistics.median(tt)
+        return {"query_us_per_call": round(mq, 1), "torch_us": round(mt, 1), "query_over_torch": round(mq/mt, 4), "query_rounds_us": [round(x, 1) for x in tq],
+                "torch_rounds_us": [round(x, 1) for x in tt], "units_per_round": [reps, loops]}, mq
+
+    for N, K, T, reps, loops, whole in MPPI_SIZES:
+        sim = lib.So100Sim(lib.ENV01, N, device="cuda:0", flags=lib.F_CUBE_PINNED, max_episode_steps=0, seed=0)
+        sim.reset()
+        dev, L, st = sim.device, sim.L, sim._stream()
+        NK = N*K
+        plan = (0.4*torch.rand(T, N, 6, device=dev) - 0.2)
+        plan_soa = plan.permute(0, 2, 1).contiguous()
+        qpos, qvel = sim.get_state()                                 # [13, N], [12, N]
+        ctrl, qr, vr = torch.empty(T, 6, NK, device=dev), torch.empty(13, NK, device=dev), torch.empty(12, NK, device=dev)
+        sio = lib.PlanSampleIO(plan_soa.data_ptr(), (C.c_float*6)(*([MPPI_SIGMA]*5 + [0.0])), -1.0, 1.0, K, T, 0, 0, 0, qpos.data_ptr(), qvel.data_ptr(),
+                               ctrl.data_ptr(), qr.data_ptr(), vr.data_ptr())
+        gen = torch.Generator(device=dev).manual_seed(0)
+        plan_nt = plan.permute(1, 0, 2).contiguous()                 # the example's [N, T, 6]
+        keep = {}
+
+        def sample_query():
+            rc = L.so100_query_plan_sample(sim.h, C.byref(sio), N, st)
+            assert rc == 0, L.so100_last_error()
+
+        def sample_torch():
+            eps = torch.randn(N, K, T, 6, device=dev, generator=gen)
+            eps[:, 0] = 0.0
+            cand = (plan_nt[:, None] + MPPI_SIGMA*eps).clamp(-1.0, 1.0)
+            cand[..., 5] = 0.0
+            keep["s"] = (cand, qpos.t().repeat_interleave(K, dim=0), qvel.t().repeat_interleave(K, dim=0), cand.reshape(NK, T, 6).permute(1, 0, 2).contiguous())
+
+        case, mq = rounds(sample_query, sample_torch, reps, loops)
+        case = {"query": "plan_sample", "N": N, "K": K, "T": T, **case, "GB_per_s": round((T*6 + 25)*NK*4/(mq*1e-6)/1e9, 1)}
+        doc["cases"].append(case); print(json.dumps(case), flush=True)
+
+        # the blend: on the rollouts of the sampled candidates
+        cand, sq, sv, cc = keep["s"]
+        roll = sim.trajectory(ctrl.permute(0, 2, 1), qr.t(), vr.t(), mode="actions")
+        qs, us = roll["qpos"].permute(0, 2, 1).contiguous(), ctrl
+        ee, cube, bad = roll["ee"].contiguous(), roll["qpos"][:, :, 6:9].contiguous(), roll["bad_step"]
+        cand_q = ctrl.permute(2, 0, 1).reshape(N, K, T, 6).contiguous()           # the example's cand, holding the query's candidates
+        six = lambda w: (C.c_float*6)(*([w]*6))
+        cdef = lib.CostDef(lib.EE_LINK, None, lib.COST_TARGETS["cube"], 1.0, six(0.0), six(0.0), six(0.0), six(0.0), 1.0)
+        out = [torch.empty(NK, device=dev), torch.empty(N, dtype=torch.int32, device=dev), torch.empty(N, device=dev), torch.empty(NK, device=dev), torch.empty(N, device=dev),
+               torch.empty(T, 6, N, device=dev), torch.empty(6, N, device=dev)]
+        bio = lib.CostBlendIO(C.pointer(cdef), None, T, K, qs.data_ptr(), None, us.data_ptr(), bad.data_ptr(), plan_soa.data_ptr(), MPPI_TEMPERATURE, 1, 0,
+                              *[t.data_ptr() for t in out])
+
+        def blend_query():
+            rc = L.so100_query_cost_blend(sim.h, C.byref(bio), N, st)
+            assert rc == 0, L.so100_last_error()
+
+        def blend_torch():
+            cost = (cube - ee).norm(dim=2).sum(dim=0).reshape(N, K)
+            cost = torch.where(bad.reshape(N, K) >= 0, torch.full_like(cost, float("inf")), cost)
+            w = torch.softmax(-(cost - cost.min(dim=1, keepdim=True).values)/0.02, dim=1)
+            p = (w[:, :, None, None]*cand_q).sum(dim=1)
+            keep["b"] = (p[:, 0].contiguous(), torch.cat([p[:, 1:], torch.zeros(N, 1, 6, device=dev)], dim=1))
+
+        case, mq = rounds(blend_query, blend_torch, reps, loops)
+        case = {"query": "cost_blend", "N": N, "K": K, "T": T, **case, "GB_per_s": round((T*(9 + 6 + 6) + 3)*NK*4/(mq*1e-6)/1e9, 1),
+                "least_ess": round(out[4].min().item(), 2), "form": a.form}
+        doc["cases"].append(case); print(json.dumps(case), flush=True)
+
+        if whole:
+            sys.path.insert(0, os.path.join(ROOT, "examples"))
+            import mppi_reach
+            planners = {m: mppi_reach.Mppi(K, T, plan=m) for m in ("query", "torch")}
+            case, _ = rounds(lambda: planners["query"](sim, None), lambda: planners["torch"](sim, None), loops, loops)
+            roll_us = timed(lambda: sim.trajectory(ctrl.permute(0, 2, 1), qr.t(), vr.t(), mode="actions"), loops)
+            case = {"query": "planning_step", "N": N, "K": K, "T": T, **case, "trajectory_alone_us": round(roll_us, 1)}
+            doc["cases"].append(case); print(json.dumps(case), flush=True)
+        sim.close()
+    with open(a.out, "w") as fh:
+        json.dump(doc, fh, indent=1)
+        fh.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None); ap.add_argument("--commit", default="unknown")
@@ -717,14 +830,17 @@ def main():
     ap.add_argument("--lqr", action="store_true", help="time the LQR query against the torch loops of examples/ilqr_reach.py (profiles/lqr_kbench.json)")
     ap.add_argument("--closed-loop", action="store_true", help="time the closed-loop trajectory query against T trajectory calls with the law in torch (profiles/closed_loop_kbench.json)")
     ap.add_argument("--cost", action="store_true", help="time the two cost queries against the torch arithmetic of examples/ilqr_reach.py (profiles/cost_kbench.json)")
+    ap.add_argument("--mppi", action="store_true", help="time the two sampling-planner queries and the whole planning step against the torch arithmetic of examples/mppi_reach.py (profiles/mppi_kbench.json)")
     ap.add_argument("--form", default=None, help="--lqr: the label of the loaded library's kernel form (mfma, or valu for a -DSO100_LQR_VALU=1 side build); "
-                                                 "--closed-loop: global, or lds for a -DSO100_CL_LDS=1 side build")
+                                                 "--closed-loop: global, or lds for a -DSO100_CL_LDS=1 side build; --mppi: the blend's workgroup form")
     a = ap.parse_args()
     if a.form is None:
-        a.form = "global" if a.closed_loop else "mfma"
+        a.form = "four waves per problem at every K (ships)" if a.mppi else "global" if a.closed_loop else "mfma"
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "cost_kbench.json" if a.cost else "closed_loop_kbench.json" if a.closed_loop else "lqr_kbench.json" if a.lqr else "derivatives_kbench.json" if a.derivatives else "trajectory_kbench.json" if a.trajectory else "forward_kbench.json" if a.forward else "query_kbench.json")
+        a.out = os.path.join(ROOT, "profiles", "mppi_kbench.json" if a.mppi else "cost_kbench.json" if a.cost else "closed_loop_kbench.json" if a.closed_loop else "lqr_kbench.json" if a.lqr else "derivatives_kbench.json" if a.derivatives else "trajectory_kbench.json" if a.trajectory else "forward_kbench.json" if a.forward else "query_kbench.json")
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    if a.mppi:
+        return mppi_main(a)
     if a.cost:
         return cost_main(a)
     if a.closed_loop:
