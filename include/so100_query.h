@@ -565,6 +565,96 @@ typedef struct {
 
 int so100_query_cost_blend(so100_sim* sim, const so100_cost_blend_io* io, int32_t N, void* hip_stream);
 
+/* Plan sample with a sigma per entry: so100_query_plan_sample with the noise scale read from the device, one per (step, joint, problem) -- what a
+ * cross-entropy planner refits after every round (so100_query_cost_refit's sigma_out, passed on as it is).  Layout, noise counter words,
+ * candidate 0, clamp, fan-out rows and the lane map are so100_query_plan_sample's:
+ *     ctrl[t][j][n K + k] = clamp(plan[t][j][n] + sigma[t][j][n] eps(n, k, t, j), u_lo, u_hi)
+ * With sigma[t][j][n] = s[j] the output equals so100_query_plan_sample's under sigma = s bit for bit.  An entry whose sigma is 0 is clamp(plan) in
+ * every candidate.  An entry whose sigma is negative, NaN or infinite cannot be refused on the host: it is NaN in every candidate k >= 1 (the
+ * trajectory query then reports bad_step for them); candidate 0 stays clamp(plan) and no other entry moves.
+ *
+ * Argument errors, in this order: those of so100_query_plan_sample with "a null sigma_dev" where the sigma check stands. */
+typedef struct {
+    const float* plan_dev;             /* [T][6][N] the nominal controls                                            */
+    const float* sigma_dev;            /* [T][6][N] the noise scale per entry; 0: that entry is never perturbed     */
+    float        u_lo;                 /* finite, u_lo <= u_hi                                                      */
+    float        u_hi;
+    int32_t      K;                    /* candidates per problem, 1..4096; N * K <= INT32_MAX                       */
+    int32_t      T;                    /* control steps, 1..4096                                                    */
+    uint64_t     seed;
+    uint32_t     draw;                 /* the planner's call counter                                                */
+    uint32_t     id_offset;            /* the global index of problem 0                                             */
+    const float* qpos_dev;             /* [13][N] or NULL                                                           */
+    const float* qvel_dev;             /* [12][N] or NULL                                                           */
+    float*       ctrl_dev;             /* [T][6][NK]                                                                */
+    float*       qpos_rep_dev;         /* [13][NK]                                                                  */
+    float*       qvel_rep_dev;         /* [12][NK]                                                                  */
+} so100_plan_sample_tv_io;
+
+int so100_query_plan_sample_tv(so100_sim* sim, const so100_plan_sample_tv_io* io, int32_t N, void* hip_stream);
+
+/* Cost refit: the cross-entropy planner's decision on the trajectory query's output -- the total cost J of each of N * K rollouts (exactly as
+ * so100_query_cost_blend computes it), per problem the E cheapest candidates, and the mean and standard deviation of their controls, smoothed
+ * against the old ones, as the next plan and the next sigma.  One GPU workgroup per problem.  The handle's state is NEVER read or written.
+ *
+ * Inputs.  so100_cost_blend_io's rollouts, cost, targets, bad_step and u_fallback, with the same meaning.  E: the number of elites.  alpha: the
+ * smoothing factor; plan [T][6][N] and sigma [T][6][N]: the old mean and sigma (each nullable; both required with alpha > 0, neither read with
+ * alpha = 0).  sigma_min[j] <= sigma_out <= sigma_max[j]; sigma_init[j]: the sigma of a row that has no history.
+ * Outputs.  cost [NK], best [N], best_cost [N]: so100_cost_blend_io's, the same bits.
+ *     order        candidate k stands before k' iff J_k < J_k' or (J_k = J_k' and k < k'); rank(k): the number of candidates before k
+ *     elites       k is an elite iff rank(k) < E and J_k is finite (+inf: a failed or non-finite rollout);  n_elite[n] = min(E, finite costs)
+ *     elite [N][E] the elites in ascending rank, -1 from slot n_elite on;  threshold[n]: the cost of the last elite, +inf where there is none
+ *     per row (t, j), over the elites:   mu = (sum u_k) / n_elite;  var = (sum (u_k - mu)^2) / n_elite;  sd = sqrt(var)
+ *     mean_new  = alpha plan + (1 - alpha) mu
+ *     sigma_new = clamp(alpha sigma + (1 - alpha) sd, sigma_min[j], sigma_max[j])
+ * The order is total, so the elite set is unique: the same on every run, whatever N, the problem's place, the outputs asked for and the way it
+ * is found.  Both sums over the elites are taken in so100_cost_blend_io's one order over k = 0..K-1 with a non-elite's term left out (its
+ * controls are never read into a sum and may be anything): the bits depend on K and the elite set alone.  The variance is the population
+ * variance in two passes; every product is rounded once before it is added, each operation of the smoothing is rounded once, and with alpha = 0
+ * the old value's term is not formed: mean_new is mu and sigma_new is clamp(sd) as they are.  n_elite = 1 gives sd = 0; E = K = 1 gives the
+ * candidate's controls as mean, bit for bit.
+ * u_first [6][N]: row 0 of mean_new before the shift.  mean [T][6][N]: mean_new, with shift = 1 moved up one step with the tail row as in
+ * so100_cost_blend_io's u_plan.  sigma_out [T][6][N]: sigma_new, moved up the same way; its row T - 1 is then sigma_init[j] under either tail.
+ * Where best = -1 (no finite cost): n_elite = 0, the elite slots are -1, threshold = +inf, mean is the column of u_fallback (or NaN without one)
+ * shifted as in the blend, and sigma_out is sigma_init[j] in every row.
+ * Every output is nullable; at least one is required; each is the same bits whether requested alone or with the others.
+ *
+ * Argument errors, in this order: those of so100_cost_blend_io up to and including the cost's; E outside 1..K; an alpha that is not finite or
+ * outside [0, 1); a sigma_min, sigma_max or sigma_init entry that is not finite, negative, or sigma_min > sigma_max; shift not 0 or 1; an unknown
+ * tail; a required pointer (qpos_traj_dev, u_traj_dev; target_dev unless the target is the cube; plan_dev and sigma_dev with alpha > 0) that is
+ * NULL; no output. */
+typedef struct {
+    const so100_cost_def* cost;        /* HOST pointer                                                              */
+    const float* target_dev;           /* [3][N] or [T][3][N] by target_mode; not read with the cube target         */
+    int32_t      T;                    /* horizon, 1..4096                                                          */
+    int32_t      K;                    /* candidates per problem, 1..4096; N * K <= INT32_MAX                       */
+    const float* qpos_traj_dev;        /* [T][13][NK]                                                               */
+    const float* qvel_traj_dev;        /* [T][12][NK] or NULL: zero                                                 */
+    const float* u_traj_dev;           /* [T][6][NK]                                                                */
+    const int32_t* bad_step_dev;       /* [NK] or NULL                                                              */
+    const float* u_fallback_dev;       /* [T][6][N] or NULL                                                         */
+    int32_t      E;                    /* elites per problem, 1..K                                                  */
+    float        alpha;                /* smoothing: the old value's share, finite and in [0, 1)                    */
+    const float* plan_dev;             /* [T][6][N] the old mean; required with alpha > 0                           */
+    const float* sigma_dev;            /* [T][6][N] the old sigma; required with alpha > 0                          */
+    float        sigma_min[6];         /* finite, 0 <= sigma_min <= sigma_max                                       */
+    float        sigma_max[6];
+    float        sigma_init[6];        /* finite and >= 0: row T - 1 of a shifted sigma_out; every row where best = -1 */
+    int32_t      shift;                /* 0, or 1: mean and sigma_out are moved up one step                         */
+    int32_t      tail;                 /* SO100_BLEND_TAIL_*: row T - 1 of a shifted mean                           */
+    float*       cost_dev;             /* [NK]                                                                      */
+    int32_t*     best_dev;             /* [N]                                                                       */
+    float*       best_cost_dev;        /* [N]                                                                       */
+    int32_t*     elite_dev;            /* [N][E]                                                                    */
+    int32_t*     n_elite_dev;          /* [N]                                                                       */
+    float*       threshold_dev;        /* [N]                                                                       */
+    float*       mean_dev;             /* [T][6][N]                                                                 */
+    float*       sigma_out_dev;        /* [T][6][N]                                                                 */
+    float*       u_first_dev;          /* [6][N]                                                                    */
+} so100_cost_refit_io;
+
+int so100_query_cost_refit(so100_sim* sim, const so100_cost_refit_io* io, int32_t N, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

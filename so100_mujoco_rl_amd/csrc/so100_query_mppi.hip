@@ -38,7 +38,9 @@ struct CostBlendArgs {
     float* cost; int32_t* best; float *best_cost, *weight, *ess, *u_plan, *u_first;
 };
 
-__global__ void __launch_bounds__(MPPI_SAMPLE_WG) so100_query_plan_sample_k(PlanSampleArgs a, int N) {
+// one candidate column: its T x 6 entries and its fan-out rows.  A: PlanSampleArgs, or the per-entry-sigma form of so100_query_cem.hip with the same
+// fields; entry(row, j, n, p, eps, perturbed): the candidate's value from the plan entry p
+template <typename A, typename Entry> __device__ __forceinline__ void plan_sample_column(const A& a, int N, Entry&& entry) {
     const size_t Nz = (size_t)N, NK = Nz*(size_t)a.K, col = (size_t)blockIdx.x*MPPI_SAMPLE_WG + threadIdx.x;
     if (col >= NK) return;
     const uint32_t n = (uint32_t)col/(uint32_t)a.K, k = (uint32_t)col - n*(uint32_t)a.K;      // N K <= INT32_MAX
@@ -49,7 +51,7 @@ __global__ void __launch_bounds__(MPPI_SAMPLE_WG) so100_query_plan_sample_k(Plan
 #pragma unroll
             for (int j = 0; j < 6; j++) {
                 const size_t row = (size_t)t*6 + j;
-                a.ctrl[row*NK + col] = mppi_candidate<float>(a.plan[row*Nz + n], a.sigma[j], eps[j], k > 0, a.lo, a.hi);
+                a.ctrl[row*NK + col] = entry(row, j, n, a.plan[row*Nz + n], eps[j], k > 0);
             }
         }
     }
@@ -63,11 +65,39 @@ __global__ void __launch_bounds__(MPPI_SAMPLE_WG) so100_query_plan_sample_k(Plan
     }
 }
 
+__global__ void __launch_bounds__(MPPI_SAMPLE_WG) so100_query_plan_sample_k(PlanSampleArgs a, int N) {
+    plan_sample_column(a, N, [&](size_t, int j, uint32_t, float p, float eps, bool perturbed) { return mppi_candidate<float>(p, a.sigma[j], eps, perturbed, a.lo, a.hi); });
+}
+
 // the exchange tree of so100_mppi.hpp's summation order over the wave's 64 partial sums: every lane takes part and ends with the same bits
 __device__ __forceinline__ float mppi_wave_sum(float x) {
 #pragma unroll
     for (int d = MPPI_WAVE/2; d >= 1; d >>= 1) x += __shfl_xor(x, d);
     return x;
+}
+
+// the summed cost of rollout column `col` of problem n.  A: CostBlendArgs, or so100_query_cem.hip's with the same input fields
+template <typename A> __device__ __forceinline__ float mppi_rollout_total(const A& a, size_t Nz, size_t NK, size_t n, size_t col) {
+    return cost_total<float>(a.c, a.T, [&](int t, float q[6], float v[6], float u[6], float g[3]) {
+        const float* qp = a.qpos + (size_t)t*13*NK;
+#pragma unroll
+        for (int j = 0; j < 6; j++) {
+            q[j] = qp[(size_t)j*NK + col];
+            v[j] = a.qvel ? a.qvel[((size_t)t*12 + j)*NK + col] : 0.0f;
+            u[j] = a.u[((size_t)t*6 + j)*NK + col];
+        }
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+            if (a.c.target_mode == COST_TARGET_CUBE) g[i] = qp[(size_t)(6 + i)*NK + col];
+            else g[i] = a.target[((a.c.target_mode == COST_TARGET_TRAJ ? (size_t)t*3 : (size_t)0) + i)*Nz + n];
+        }
+    });
+}
+// what a rollout costs: +inf where it failed or its sum is not finite
+template <typename A> __device__ __forceinline__ float mppi_rollout_cost(const A& a, size_t Nz, size_t NK, size_t n, size_t col) {
+    const float total = mppi_rollout_total(a, Nz, NK, n, col);
+    const bool failed = a.bad_step && a.bad_step[col] >= 0;
+    return (failed || !cost_finite(total)) ? __int_as_float(0x7F800000) : total;
 }
 
 __global__ void __launch_bounds__(MPPI_BLEND_WG) so100_query_cost_blend_k(CostBlendArgs a, int N) {
@@ -77,20 +107,7 @@ __global__ void __launch_bounds__(MPPI_BLEND_WG) so100_query_cost_blend_k(CostBl
     const float inf = __int_as_float(0x7F800000), nan = __int_as_float(0x7FC00000);
     for (int k = tid; k < K; k += threads) {
         const size_t col = base + (size_t)k;
-        const float total = cost_total<float>(a.c, a.T, [&](int t, float q[6], float v[6], float u[6], float g[3]) {
-            const float* qp = a.qpos + (size_t)t*13*NK;
-#pragma unroll
-            for (int j = 0; j < 6; j++) {
-                q[j] = qp[(size_t)j*NK + col];
-                v[j] = a.qvel ? a.qvel[((size_t)t*12 + j)*NK + col] : 0.0f;
-                u[j] = a.u[((size_t)t*6 + j)*NK + col];
-            }
-#pragma unroll
-            for (int i = 0; i < 3; i++) {
-                if (a.c.target_mode == COST_TARGET_CUBE) g[i] = qp[(size_t)(6 + i)*NK + col];
-                else g[i] = a.target[((a.c.target_mode == COST_TARGET_TRAJ ? (size_t)t*3 : (size_t)0) + i)*Nz + n];
-            }
-        });
+        const float total = mppi_rollout_total(a, Nz, NK, n, col);
         const bool failed = a.bad_step && a.bad_step[col] >= 0;
         const float cost = (failed || !cost_finite(total)) ? inf : total;
         if (a.cost) a.cost[col] = cost;

@@ -309,3 +309,4 @@ int so100_set_field(so100_sim* s, int32_t field, const void* in_dev, void* strea
 #include "so100_query_closed_loop.hip"
 #include "so100_query_cost.hip"
 #include "so100_query_mppi.hip"
+#include "so100_query_cem.hip"

@@ -232,13 +232,29 @@ class CostBlendIO(C.Structure):
                [(n, C.c_void_p) for n in ("cost_dev", "best_dev", "best_cost_dev", "weight_dev", "ess_dev", "u_plan_dev", "u_first_dev")]
 
 
+class PlanSampleTvIO(C.Structure):
+    _fields_ = [("plan_dev", C.c_void_p), ("sigma_dev", C.c_void_p), ("u_lo", C.c_float), ("u_hi", C.c_float), ("K", C.c_int32), ("T", C.c_int32),
+                ("seed", C.c_uint64), ("draw", C.c_uint32), ("id_offset", C.c_uint32)] + \
+               [(n, C.c_void_p) for n in ("qpos_dev", "qvel_dev", "ctrl_dev", "qpos_rep_dev", "qvel_rep_dev")]
+
+
+class CostRefitIO(C.Structure):
+    _fields_ = [("cost", C.POINTER(CostDef)), ("target_dev", C.c_void_p), ("T", C.c_int32), ("K", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("qpos_traj_dev", "qvel_traj_dev", "u_traj_dev", "bad_step_dev", "u_fallback_dev")] + \
+               [("E", C.c_int32), ("alpha", C.c_float), ("plan_dev", C.c_void_p), ("sigma_dev", C.c_void_p), ("sigma_min", C.c_float*6), ("sigma_max", C.c_float*6),
+                ("sigma_init", C.c_float*6), ("shift", C.c_int32), ("tail", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("cost_dev", "best_dev", "best_cost_dev", "elite_dev", "n_elite_dev", "threshold_dev", "mean_dev", "sigma_out_dev",
+                                          "u_first_dev")]
+
+
 QUERY_EXPORTS = ["so100_query_kinematics", "so100_query_jacobian", "so100_query_dynamics", "so100_query_ik", "so100_query_forward",
                  "so100_query_trajectory", "so100_query_derivatives", "so100_query_lqr", "so100_query_closed_loop", "so100_query_cost_terms",
-                 "so100_query_cost_select", "so100_query_plan_sample", "so100_query_cost_blend"]
+                 "so100_query_cost_select", "so100_query_plan_sample", "so100_query_cost_blend", "so100_query_plan_sample_tv", "so100_query_cost_refit"]
 QUERY_IO = {"so100_query_kinematics": KinematicsIO, "so100_query_jacobian": JacobianIO, "so100_query_dynamics": DynamicsIO, "so100_query_ik": IkIO,
             "so100_query_forward": ForwardIO, "so100_query_trajectory": TrajectoryIO, "so100_query_derivatives": DerivativesIO, "so100_query_lqr": LqrIO,
             "so100_query_closed_loop": ClosedLoopIO, "so100_query_cost_terms": CostTermsIO, "so100_query_cost_select": CostSelectIO,
-            "so100_query_plan_sample": PlanSampleIO, "so100_query_cost_blend": CostBlendIO}
+            "so100_query_plan_sample": PlanSampleIO, "so100_query_cost_blend": CostBlendIO, "so100_query_plan_sample_tv": PlanSampleTvIO,
+            "so100_query_cost_refit": CostRefitIO}
 MPPI_MAX_K = 4096                                              # SO100_MPPI_MAX_K
 BLEND_TAILS = {"zero": 0, "hold": 1}                           # SO100_BLEND_TAIL_*
 COST_TARGETS = {"fixed": 0, "traj": 1, "cube": 2}               # SO100_COST_TARGET_*
@@ -1005,6 +1021,82 @@ class So100Sim(_Handle):
         _check(self.L.so100_query_cost_blend(self.h, C.byref(io), N, self._stream()), "so100_query_cost_blend")
         return {"cost": cost.unflatten(0, (N, K)), "best": best, "best_cost": bc, "weight": wt.unflatten(0, (N, K)), "ess": ess, "u_plan": up.permute(0, 2, 1),
                 "u_first": uf.t()}
+
+    def plan_sample_tv(self, plan, K, sigma, *, seed=0, draw=0, id_offset=0, u_lo=-1.0, u_hi=1.0, qpos=None, qvel=None):
+        """plan_sample() with a noise scale per entry, read on the device: sigma [T, N, 6] like plan (cost_refit()'s "sigma_out", passed on without a
+        copy).  An entry with sigma 0 is never perturbed; one whose sigma is negative or not finite is NaN in every candidate but candidate 0.
+        With sigma[t, n, j] = s[j] the result is plan_sample(plan, K, s)'s bit for bit.  Everything else, the returned views included: as in
+        plan_sample()."""
+        plan = torch.as_tensor(plan, dtype=torch.float32, device=self.device)
+        if plan.dim() != 3 or plan.shape[2] != 6 or plan.shape[0] < 1 or plan.shape[1] < 1:
+            raise So100Error(f"plan: want a [T, N, 6] tensor, got {tuple(plan.shape)}")
+        T, N = plan.shape[0], plan.shape[1]
+        if not 1 <= K <= MPPI_MAX_K:
+            raise So100Error(f"plan_sample_tv: K must be in 1..{MPPI_MAX_K}, got {K!r}")
+        if qvel is not None and qpos is None:
+            raise So100Error("plan_sample_tv: qvel needs qpos")
+        ps, sg = plan.permute(0, 2, 1).contiguous(), self._shaped(sigma, (T, N, 6), "sigma").permute(0, 2, 1).contiguous()
+        qs, vs = self._soa(qpos, 13, "qpos"), self._soa(qvel, 12, "qvel")
+        self._problems(ps[0], qs, vs)
+        ctrl = self._out(N*K, T, 6)
+        qr, vr = (None if qs is None else self._out(N*K, 13)), (None if vs is None else self._out(N*K, 12))
+        io = PlanSampleTvIO(ps.data_ptr(), sg.data_ptr(), u_lo, u_hi, K, T, seed, draw, id_offset, _optr(qs), _optr(vs), ctrl.data_ptr(), _optr(qr), _optr(vr))
+        _check(self.L.so100_query_plan_sample_tv(self.h, C.byref(io), N, self._stream()), "so100_query_plan_sample_tv")
+        res = {"ctrl": ctrl.permute(0, 2, 1)}
+        if qr is not None:
+            res["qpos"] = qr.t()
+        if vr is not None:
+            res["qvel"] = vr.t()
+        return res
+
+    def cost_refit(self, qpos, qvel, u, K, E, *, alpha=0.0, plan=None, sigma=None, sigma_min, sigma_max, sigma_init, bad_step=None, u_fallback=None,
+                   shift=0, tail="zero", target=None, target_mode=None, link=EE_LINK, offset=None, w_point=1.0, w_q=0.0, q_nom=0.0, w_v=0.0, w_u=0.0, w_terminal=1.0):
+        """The cross-entropy planner's decision on trajectory()'s output in one launch: the total cost of each of the N K rollouts, per problem the E
+        cheapest candidates (ordered by (cost, index); a failed rollout is never one), and the mean and the population standard deviation of their
+        controls per (step, joint) as the next plan and the next sigma: mean = alpha plan + (1 - alpha) mu, sigma = clamp(alpha sigma + (1 - alpha) sd,
+        sigma_min, sigma_max).  qpos, qvel, u, bad_step, u_fallback, shift, tail and the cost arguments: as in cost_blend().  plan and sigma [T, N, 6]:
+        the old mean and sigma, both needed with alpha > 0.  sigma_min, sigma_max, sigma_init: 6 values or one for all; sigma_init is the last row of a
+        shifted "sigma_out" and every row of a problem whose candidates all failed.  Returns "cost" [N, K], "best" [N] int32, "best_cost" [N] (cost_blend()'s
+        bits), "elite" [N, E] int32 in ascending rank (-1 from slot n_elite on), "n_elite" [N] int32, "threshold" [N] (the last elite's cost), "mean"
+        [T, N, 6], "sigma_out" [T, N, 6] and "u_first" [N, 6] (row 0 of the mean before the shift) -- views of the SoA buffers:
+        plan_sample_tv(res["mean"], K, res["sigma_out"]) copies neither."""
+        u = torch.as_tensor(u, dtype=torch.float32, device=self.device)
+        if u.dim() != 3 or u.shape[2] != 6 or u.shape[0] < 1 or not 1 <= K <= MPPI_MAX_K or u.shape[1] < K or u.shape[1] % K:
+            raise So100Error(f"u: want a [T, N K, 6] tensor with K = {K!r} in 1..{MPPI_MAX_K}, got {tuple(u.shape)}")
+        if not 1 <= E <= K:
+            raise So100Error(f"cost_refit: E must be in 1..K = {K}, got {E!r}")
+        if tail not in BLEND_TAILS:
+            raise So100Error(f"cost_refit: tail must be one of {sorted(BLEND_TAILS)}, got {tail!r}")
+        T, NK = u.shape[0], u.shape[1]
+        N = NK//K
+        rows = lambda t, k, name: None if t is None else self._shaped(t, (T, NK, k), name).permute(0, 2, 1).contiguous()     # trajectory()'s views: no copy
+        qs, vs, us = rows(qpos, 13, "qpos"), rows(qvel, 12, "qvel"), rows(u, 6, "u")
+        if qs is None:
+            raise So100Error("cost_refit: qpos is required")
+        bs = None
+        if bad_step is not None:
+            bs = torch.as_tensor(bad_step, dtype=torch.int32, device=self.device)
+            if bs.numel() != NK:
+                raise So100Error(f"bad_step: want {NK} values, got {tuple(bs.shape)}")
+            bs = bs.reshape(NK).contiguous()
+        per = lambda t, name: None if t is None else self._shaped(t, (T, N, 6), name).permute(0, 2, 1).contiguous()
+        fb, pl, sg = per(u_fallback, "u_fallback"), per(plan, "plan"), per(sigma, "sigma")
+
+        def six(x, name):
+            v = torch.as_tensor(x, dtype=torch.float32).reshape(-1).tolist()
+            if len(v) not in (1, 6):
+                raise So100Error(f"{name}: want 6 values or one for all, got {len(v)}")
+            return (C.c_float*6)(*(v*6 if len(v) == 1 else v))
+        d, keep, tg = self._cost("cost_refit", T, N, target, target_mode, link, offset, w_point, w_q, q_nom, w_v, w_u, w_terminal)
+        cost, best, bc = self._out(NK), self._out(N, dtype=torch.int32), self._out(N)
+        el, ne, th = self._out(N*E, dtype=torch.int32), self._out(N, dtype=torch.int32), self._out(N)
+        mean, so, uf = self._out(N, T, 6), self._out(N, T, 6), self._out(N, 6)
+        io = CostRefitIO(C.pointer(d), _optr(tg), T, K, qs.data_ptr(), _optr(vs), us.data_ptr(), _optr(bs), _optr(fb), E, alpha, _optr(pl), _optr(sg),
+                         six(sigma_min, "sigma_min"), six(sigma_max, "sigma_max"), six(sigma_init, "sigma_init"), shift, BLEND_TAILS[tail],
+                         cost.data_ptr(), best.data_ptr(), bc.data_ptr(), el.data_ptr(), ne.data_ptr(), th.data_ptr(), mean.data_ptr(), so.data_ptr(), uf.data_ptr())
+        _check(self.L.so100_query_cost_refit(self.h, C.byref(io), N, self._stream()), "so100_query_cost_refit")
+        return {"cost": cost.unflatten(0, (N, K)), "best": best, "best_cost": bc, "elite": el.unflatten(0, (N, E)), "n_elite": ne, "threshold": th,
+                "mean": mean.permute(0, 2, 1), "sigma_out": so.permute(0, 2, 1), "u_first": uf.t()}
 
     def _shaped(self, t, shape, name):
         """a float32 tensor of exactly `shape` on the handle's device, in whatever strides it has"""

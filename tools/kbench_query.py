@@ -9,6 +9,7 @@
     python tools/kbench_query.py --closed-loop [--form global] [--out profiles/closed_loop_kbench.json] [--commit LABEL] [--rounds 5]
     python tools/kbench_query.py --cost [--out profiles/cost_kbench.json] [--commit LABEL] [--rounds 5]
     python tools/kbench_query.py --mppi [--out profiles/mppi_kbench.json] [--commit LABEL] [--rounds 5]
+    python tools/kbench_query.py --cem [--out profiles/cem_kbench.json] [--commit LABEL] [--rounds 5]
 
 Cases, at M = 4096 and M = 1 048 576 problems: kinematics with every output and with the end-effector point alone, the Jacobian (jacp and
 jacr), the dynamics (M, bias and tau) and the IK.  Poses are uniform over the joint ranges; the IK problems are the 400 of the tests' recipe
@@ -48,7 +49,11 @@ fills and cats for the terms; the torch sum, mask, argmin and gather for the sel
 
 --mppi times the two sampling-planner queries (so100_query_plan_sample and so100_query_cost_blend, every output) at (N, K, T) in {(8, 64, 8), (8, 256, 8),
 (512, 256, 16)} beside the torch arithmetic of examples/mppi_reach.py for the same job, and at the first two sizes the whole planning step: the three
-queries against the example's torch path around the same trajectory call (mppi_main)."""
+queries against the example's torch path around the same trajectory call (mppi_main).
+
+--cem times so100_query_plan_sample_tv against so100_query_plan_sample on equal inputs and so100_query_cost_refit (every output, E = K / 8) against the torch
+arithmetic for the same job at (N, K, T) in {(8, 64, 8), (8, 256, 8), (512, 256, 16), (1, 4096, 1)}, and at the first two sizes a whole CEM round both ways
+(cem_main)."""
 import argparse
 import ctypes as C
 import json
@@ -820,6 +825,140 @@ def mppi_main(a):
         fh.write("\n")
 
 
+CEM_SIZES = [(8, 64, 8, 50, 20, True), (8, 256, 8, 50, 20, True), (512, 256, 16, 5, 3, False), (1, 4096, 1, 50, 20, False)]      # as MPPI_SIZES; E = K / 8
+CEM_ALPHA, CEM_SIGMA_MIN = 0.1, 0.05
+
+
+def cem_main(a):
+    """One so100_query_plan_sample_tv call against one so100_query_plan_sample call on equal inputs (what reading sigma from memory costs), one
+    so100_query_cost_refit call against the torch arithmetic for the same job, and a whole CEM round both ways around the same trajectory call.  An event
+    pair round each unit, enqueued without waiting; medians of alternated rounds."""
+    doc = {"what": "HIP-event time of one so100_query_plan_sample_tv call (ctrl, qpos_rep, qvel_rep; sigma_dev holding sigma[j] in every entry) against one "
+                   "so100_query_plan_sample call with that sigma[6] on the same plan and states (tv_over_plain); of one so100_query_cost_refit call (all nine "
+                   "outputs, E = K / 8, alpha 0.1, shift 1) against torch for the same job: the cost sum from the trajectory query's ee rows, mask, topk, gather, "
+                   "mean, var, sqrt, smoothing, clamp and shift (the query recomputes the point from qpos and its cost is quadratic: the same job, not the same "
+                   "numbers); and of a whole CEM round, plan_sample_tv -> trajectory -> cost_refit against randn sampling, the same trajectory call and the "
+                   "torch refit.  An event pair round each unit, medians of alternated rounds.  A record, not a gate: nothing comparable existed",
+           "commit": a.commit, "card": torch.cuda.get_device_name(0), "rounds": a.rounds, "cases": []}
+
+    def pair(call):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(); call(); e1.record()
+        return e0, e1
+
+    def timed(call, n):
+        pairs = [pair(call) for _ in range(n)]
+        torch.cuda.synchronize()
+        return sum(e0.elapsed_time(e1) for e0, e1 in pairs)*1e3/n
+
+    def rounds(one_query, one_other, reps, loops, names=("query_us_per_call", "torch_us", "query_over_torch")):
+        timed(one_query, 2); timed(one_other, 1)
+        tq, tt = [], []
+        for _ in range(a.rounds):
+            tq.append(timed(one_query, reps)); tt.append(timed(one_other, loops))
+        mq, mt = statistics.median(tq), statistics.median(tt)
+        return {names[0]: round(mq, 1), names[1]: round(mt, 1), names[2]: round(mq/mt, 4), "first_rounds_us": [round(x, 1) for x in tq],
+                "second_rounds_us": [round(x, 1) for x in tt], "units_per_round": [reps, loops]}, mq
+
+    for N, K, T, reps, loops, whole in CEM_SIZES:
+        sim = lib.So100Sim(lib.ENV01, N, device="cuda:0", flags=lib.F_CUBE_PINNED, max_episode_steps=0, seed=0)
+        sim.reset()
+        dev, L, st = sim.device, sim.L, sim._stream()
+        NK, E = N*K, K//8
+        six = lambda w: (C.c_float*6)(*w)
+        sig6 = [MPPI_SIGMA]*5 + [0.0]
+        plan = (0.4*torch.rand(T, N, 6, device=dev) - 0.2)
+        plan_soa = plan.permute(0, 2, 1).contiguous()
+        sigma = torch.tensor(sig6, device=dev).expand(T, N, 6).contiguous()
+        sigma_soa = sigma.permute(0, 2, 1).contiguous()
+        qpos, qvel = sim.get_state()                                 # [13, N], [12, N]
+        ctrl, qr, vr = torch.empty(T, 6, NK, device=dev), torch.empty(13, NK, device=dev), torch.empty(12, NK, device=dev)
+        sio = lib.PlanSampleIO(plan_soa.data_ptr(), six(sig6), -1.0, 1.0, K, T, 0, 0, 0, qpos.data_ptr(), qvel.data_ptr(), ctrl.data_ptr(), qr.data_ptr(), vr.data_ptr())
+        tio = lib.PlanSampleTvIO(plan_soa.data_ptr(), sigma_soa.data_ptr(), -1.0, 1.0, K, T, 0, 0, 0, qpos.data_ptr(), qvel.data_ptr(), ctrl.data_ptr(), qr.data_ptr(),
+                                 vr.data_ptr())
+
+        def sample_tv():
+            rc = L.so100_query_plan_sample_tv(sim.h, C.byref(tio), N, st)
+            assert rc == 0, L.so100_last_error()
+
+        def sample_plain():
+            rc = L.so100_query_plan_sample(sim.h, C.byref(sio), N, st)
+            assert rc == 0, L.so100_last_error()
+
+        case, mq = rounds(sample_tv, sample_plain, reps, reps, ("tv_us_per_call", "plain_us_per_call", "tv_over_plain"))
+        case = {"query": "plan_sample_tv", "N": N, "K": K, "T": T, **case, "GB_per_s": round((T*6 + 25)*NK*4/(mq*1e-6)/1e9, 1)}
+        doc["cases"].append(case); print(json.dumps(case), flush=True)
+
+        # the refit: on the rollouts of the sampled candidates
+        roll = sim.trajectory(ctrl.permute(0, 2, 1), qr.t(), vr.t(), mode="actions")
+        qs, us = roll["qpos"].permute(0, 2, 1).contiguous(), ctrl
+        ee, cube, bad = roll["ee"].contiguous(), roll["qpos"][:, :, 6:9].contiguous(), roll["bad_step"]
+        cand_q = ctrl.permute(2, 0, 1).reshape(N, K, T, 6).contiguous()           # [N, K, T, 6], holding the query's candidates
+        plan_nt, sigma_nt = plan.permute(1, 0, 2).contiguous(), sigma.permute(1, 0, 2).contiguous()
+        lo_t, hi_t, init_t = (torch.tensor(v, device=dev) for v in ([CEM_SIGMA_MIN]*5 + [0.0], sig6, sig6))
+        cdef = lib.CostDef(lib.EE_LINK, None, lib.COST_TARGETS["cube"], 1.0, six([0.0]*6), six([0.0]*6), six([0.0]*6), six([0.0]*6), 1.0)
+        out = [torch.empty(NK, device=dev), torch.empty(N, dtype=torch.int32, device=dev), torch.empty(N, device=dev), torch.empty(N*E, dtype=torch.int32, device=dev),
+               torch.empty(N, dtype=torch.int32, device=dev), torch.empty(N, device=dev), torch.empty(T, 6, N, device=dev), torch.empty(T, 6, N, device=dev),
+               torch.empty(6, N, device=dev)]
+        rio = lib.CostRefitIO(C.pointer(cdef), None, T, K, qs.data_ptr(), None, us.data_ptr(), bad.data_ptr(), plan_soa.data_ptr(), E, CEM_ALPHA, plan_soa.data_ptr(),
+                              sigma_soa.data_ptr(), six([CEM_SIGMA_MIN]*5 + [0.0]), six(sig6), six(sig6), 1, 0, *[t.data_ptr() for t in out])
+        keep = {}
+
+        def refit_query():
+            rc = L.so100_query_cost_refit(sim.h, C.byref(rio), N, st)
+            assert rc == 0, L.so100_last_error()
+
+        def torch_refit(ee, cube, bad, cand, old_mean, old_sigma):
+            cost = (cube - ee).norm(dim=2).sum(dim=0).reshape(N, K)
+            cost = torch.where(bad.reshape(N, K) >= 0, torch.full_like(cost, float("inf")), cost)
+            top = torch.topk(cost, E, dim=1, largest=False)
+            el = cand.gather(1, top.indices[:, :, None, None].expand(N, E, T, 6))
+            mu, sd = el.mean(dim=1), el.var(dim=1, unbiased=False).sqrt()
+            mean = CEM_ALPHA*old_mean + (1.0 - CEM_ALPHA)*mu
+            sg = torch.minimum(torch.maximum(CEM_ALPHA*old_sigma + (1.0 - CEM_ALPHA)*sd, lo_t), hi_t)
+            return (mean[:, 0].contiguous(), torch.cat([mean[:, 1:], torch.zeros(N, 1, 6, device=dev)], dim=1),
+                    torch.cat([sg[:, 1:], init_t.expand(N, 1, 6)], dim=1), top.values[:, -1])
+
+        def refit_torch():
+            keep["r"] = torch_refit(ee, cube, bad, cand_q, plan_nt, sigma_nt)
+
+        case, mq = rounds(refit_query, refit_torch, reps, loops)
+        case = {"query": "cost_refit", "N": N, "K": K, "E": E, "T": T, **case, "GB_per_s": round((T*(9 + 6 + 2*6*E/K) + 2)*NK*4/(mq*1e-6)/1e9, 1),
+                "least_n_elite": int(out[4].min().item())}
+        doc["cases"].append(case); print(json.dumps(case), flush=True)
+
+        if whole:
+            gen = torch.Generator(device=dev).manual_seed(0)
+            state = {"q": (plan, sigma, 0), "t": (plan_nt, sigma_nt)}
+
+            def round_query():
+                mean, sg, draw = state["q"]
+                cand = sim.plan_sample_tv(mean, K, sg, draw=draw, qpos=qpos.t(), qvel=qvel.t())
+                r = sim.trajectory(cand["ctrl"], cand["qpos"], cand["qvel"], mode="actions")
+                o = sim.cost_refit(r["qpos"], None, cand["ctrl"], K, E, alpha=CEM_ALPHA, plan=mean, sigma=sg, sigma_min=[CEM_SIGMA_MIN]*5 + [0.0], sigma_max=sig6,
+                                   sigma_init=sig6, bad_step=r["bad_step"], u_fallback=mean, shift=1, target_mode="cube")
+                state["q"] = (o["mean"], o["sigma_out"], draw + 1)
+
+            def round_torch():
+                mean, sg = state["t"]
+                eps = torch.randn(N, K, T, 6, device=dev, generator=gen)
+                eps[:, 0] = 0.0
+                cand = (mean[:, None] + sg[:, None]*eps).clamp(-1.0, 1.0)
+                r = sim.trajectory(cand.reshape(NK, T, 6).permute(1, 0, 2).contiguous(), qpos.t().repeat_interleave(K, dim=0), qvel.t().repeat_interleave(K, dim=0),
+                                   mode="actions")
+                _, m2, s2, _ = torch_refit(r["ee"], r["qpos"][:, :, 6:9], r["bad_step"], cand, mean, sg)
+                state["t"] = (m2, s2)
+
+            case, _ = rounds(round_query, round_torch, loops, loops)
+            roll_us = timed(lambda: sim.trajectory(ctrl.permute(0, 2, 1), qr.t(), vr.t(), mode="actions"), loops)
+            case = {"query": "cem_round", "N": N, "K": K, "E": E, "T": T, **case, "trajectory_alone_us": round(roll_us, 1)}
+            doc["cases"].append(case); print(json.dumps(case), flush=True)
+        sim.close()
+    with open(a.out, "w") as fh:
+        json.dump(doc, fh, indent=1)
+        fh.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None); ap.add_argument("--commit", default="unknown")
@@ -831,14 +970,17 @@ def main():
     ap.add_argument("--closed-loop", action="store_true", help="time the closed-loop trajectory query against T trajectory calls with the law in torch (profiles/closed_loop_kbench.json)")
     ap.add_argument("--cost", action="store_true", help="time the two cost queries against the torch arithmetic of examples/ilqr_reach.py (profiles/cost_kbench.json)")
     ap.add_argument("--mppi", action="store_true", help="time the two sampling-planner queries and the whole planning step against the torch arithmetic of examples/mppi_reach.py (profiles/mppi_kbench.json)")
+    ap.add_argument("--cem", action="store_true", help="time the two cross-entropy planner queries and a whole CEM round against so100_query_plan_sample and the torch arithmetic for the same job (profiles/cem_kbench.json)")
     ap.add_argument("--form", default=None, help="--lqr: the label of the loaded library's kernel form (mfma, or valu for a -DSO100_LQR_VALU=1 side build); "
                                                  "--closed-loop: global, or lds for a -DSO100_CL_LDS=1 side build; --mppi: the blend's workgroup form")
     a = ap.parse_args()
     if a.form is None:
         a.form = "four waves per problem at every K (ships)" if a.mppi else "global" if a.closed_loop else "mfma"
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "mppi_kbench.json" if a.mppi else "cost_kbench.json" if a.cost else "closed_loop_kbench.json" if a.closed_loop else "lqr_kbench.json" if a.lqr else "derivatives_kbench.json" if a.derivatives else "trajectory_kbench.json" if a.trajectory else "forward_kbench.json" if a.forward else "query_kbench.json")
+        a.out = os.path.join(ROOT, "profiles", "cem_kbench.json" if a.cem else "mppi_kbench.json" if a.mppi else "cost_kbench.json" if a.cost else "closed_loop_kbench.json" if a.closed_loop else "lqr_kbench.json" if a.lqr else "derivatives_kbench.json" if a.derivatives else "trajectory_kbench.json" if a.trajectory else "forward_kbench.json" if a.forward else "query_kbench.json")
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    if a.cem:
+        return cem_main(a)
     if a.mppi:
         return mppi_main(a)
     if a.cost:
