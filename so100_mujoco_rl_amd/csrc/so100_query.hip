@@ -87,6 +87,18 @@ __global__ __launch_bounds__(QUERY_THREADS) void so100_query_ik_k(const float* q
     if (io.converged) io.converged[i] = R.converged ? 1 : 0;
 }
 
+// forward, trajectory, derivatives and closed loop start from a whole state: the caller's rows (qvel may be null: zero), or the handle's
+// so100_get_state rows, their row length ld = N and the state matrix itself (what a simulation that goes on reads beside qpos and qvel; else null).
+// The rollout kernels' argument structs begin with one (filled by query_start below).
+struct QueryStart { const float *qpos, *qvel; int ld; const float* state; };
+
+// the trajectory-shaped outputs of a rollout kernel, each [T][k][stride] (the finals [k][stride], bad_step [stride]) or null (filled and checked by
+// query_roll_out below); a rollout writes word `col` of every row
+struct QueryRollOut {
+    float *qpos_traj, *qvel_traj, *ee_traj, *qpos_final, *qvel_final;
+    int32_t *ncon, *dropped, *sig; float* residual; int32_t* bad_step;
+};
+
 namespace {
 
 // The checks the entries share (this file's and those of the files so100_sim.hip includes behind it).  Each returns fail()'s code or 0; an entry
@@ -107,15 +119,37 @@ int query_source(const char* fn, const so100_sim* s, const float* q_dev, int32_t
     src.ld = q_dev ? M : s->prm.n;
     return 0;
 }
-// forward, trajectory and derivatives start from a whole state: the caller's rows (qvel may be null: zero), or the handle's so100_get_state
-// rows, their row length N and the state matrix itself (what a simulation that goes on reads beside qpos and qvel)
-struct QueryStart { const float *qpos, *qvel; int ld; const float* state; };
 int query_start(const char* fn, const so100_sim* s, const float* qpos_dev, const float* qvel_dev, int32_t M, QueryStart& st) {
     if (const int rc = query_batch(fn, s, !qpos_dev && !qvel_dev, M)) return rc;
     if (!qpos_dev && qvel_dev) return fail(SO100_E_INVALID, "%s: qvel_dev given without qpos_dev", fn);
     const size_t n = (size_t)s->prm.n;
     if (qpos_dev) st = { qpos_dev, qvel_dev, M, nullptr };
     else st = { s->state + (size_t)SF_QPOS0*n, s->state + (size_t)SF_QVEL0*n, s->prm.n, s->state };
+    return 0;
+}
+// the horizon of the trajectory and closed-loop entries
+int query_horizon(const char* fn, int32_t T, int32_t nsub) {
+    if (T < 1 || T > SO100_TRAJ_MAX_T || nsub < 1 || nsub > SO100_TRAJ_MAX_NSUB || (long)T*(long)nsub > SO100_TRAJ_MAX_SUBSTEPS)
+        return fail(SO100_E_INVALID, "%s: T must be in 1..%d, nsub in 1..%d and T * nsub <= %d, got T = %ld, nsub = %ld", fn, SO100_TRAJ_MAX_T, SO100_TRAJ_MAX_NSUB,
+                    SO100_TRAJ_MAX_SUBSTEPS, (long)T, (long)nsub);
+    return 0;
+}
+// the steps of an entry without substeps of its own (limit: SO100_LQR_MAX_T or SO100_TRAJ_MAX_T)
+int query_steps(const char* fn, int32_t T, int limit) {
+    if (T < 1 || T > limit) return fail(SO100_E_INVALID, "%s: T must be in 1..%d, got %ld", fn, limit, (long)T);
+    return 0;
+}
+// the candidates of each problem: `count` of them (named c: "L" or "K") for each of `batch` problems (named b: "M" or "N"); every rollout has an int32 index
+int query_candidates(const char* fn, const char* c, const char* b, int32_t count, int limit, int32_t batch) {
+    if (count < 1 || count > limit || (long long)batch*(long long)count > (long long)INT32_MAX)
+        return fail(SO100_E_INVALID, "%s: %s must be in 1..%d and %s * %s <= %ld, got %s = %ld, %s = %ld", fn, c, limit, b, c, (long)INT32_MAX, c, (long)count, b, (long)batch);
+    return 0;
+}
+// the trajectory-shaped outputs of an io struct (so100_trajectory_io, so100_closed_loop_io); also: an output the entry has beside them, or null
+template <typename IO> int query_roll_out(const char* fn, const IO& io, const void* also, QueryRollOut& o) {
+    o = { io.qpos_traj_dev, io.qvel_traj_dev, io.ee_traj_dev, io.qpos_final_dev, io.qvel_final_dev, io.ncon_dev, io.dropped_dev, io.sig_dev, io.residual_dev, io.bad_step_dev };
+    if (!also && !o.qpos_traj && !o.qvel_traj && !o.ee_traj && !o.qpos_final && !o.qvel_final && !o.ncon && !o.dropped && !o.sig && !o.residual && !o.bad_step)
+        return fail(SO100_E_INVALID, "%s: no output requested", fn);
     return 0;
 }
 int query_control(const char* fn, const float* ctrl_dev, int32_t mode) {
@@ -155,6 +189,7 @@ unsigned query_grid(int M) { return (unsigned)((M + QUERY_THREADS - 1)/QUERY_THR
 
 static_assert(SF_q5 == SF_q0 + 5 && SF_v5 == SF_v0 + 5, "the arm's qpos / qvel rows are contiguous");
 static_assert(SO100_EE_LINK == EE_LINK, "the header names the same end-effector point");
+static_assert(SF_ff0 + 5 == SF_ff5 && SF_fl0 + 5 == SF_fl5 && SF_cw0 + 5 == SF_cw5 && SF_qc0 + 5 == SF_qc5 && SF_aw0 + 5 == SF_aw5, "six consecutive rows each");
 
 extern "C" {
 

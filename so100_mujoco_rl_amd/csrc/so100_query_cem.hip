@@ -1,14 +1,14 @@
 // so100_query_cem.hip -- the two cross-entropy planner queries (gfx950) and their C ABI (include/so100_query.h: so100_query_plan_sample_tv,
 // so100_query_cost_refit); every number's arithmetic is in so100_cem.hpp.  Like so100_query_mppi.hip, not a translation unit of its own:
-// so100_sim.hip includes it behind that file and it uses its plan_sample_column(), mppi_rollout_cost() and mppi_wave_sum(), and cost_def(),
-// query_batch() and fail() of the files before.
+// so100_sim.hip includes it behind that file and it uses its plan_sample_column(), plan_sample_entry(), plan_placement() and mppi_wave_sum(), and
+// cost_rollout(), cost_def(), cost_rollouts() and the checks of the files before.
 //
 // Sample.  so100_query_mppi.hip's column body with the entry's sigma loaded from sigma[t][j][n]: all lanes of a problem read one address, as they
 // do for the plan.  No LDS.
 //
 // Refit.  One workgroup of four waves per problem.  LDS (dynamic): P 64-bit keys, P = K rounded up to a power of two and at least 64, then K floats
 // -- 48 KB at K = 4096, 768 B at K = 64.
-//   1. thread i sums the cost of rollouts i, i + 256, ... with the blend's code (mppi_rollout_cost) into the K floats; key (J_k, k) into the table,
+//   1. thread i sums the cost of rollouts i, i + 256, ... with the blend's code (cost_rollout) into the K floats; key (J_k, k) into the table,
 //      a padding key above every cost behind them
 //   2. a bitonic sort of the keys, ascending.  The steps at distances 32 .. 1 work on 64 consecutive keys: a wave holds them one per lane and
 //      exchanges them across lanes, no LDS traffic and no barrier between such steps (all 21 steps up to runs of 64; the last six of every
@@ -34,10 +34,8 @@ struct PlanSampleTvArgs {
     float* ctrl; uint32_t *qpos_rep, *qvel_rep;
 };
 struct CostRefitArgs {
-    CostDef<float> c;
-    const float *target, *qpos, *qvel, *u;
-    const int32_t* bad_step; const float* u_fallback;
-    int T, K, E, P;
+    CostRollouts in;
+    int E, P;
     float alpha; const float *plan, *sigma;
     float sigma_min[6], sigma_max[6], sigma_init[6];
     int shift, tail;
@@ -90,12 +88,12 @@ __global__ void __launch_bounds__(CEM_REFIT_WG) so100_query_cost_refit_k(CostRef
     extern __shared__ unsigned long long cem_lds[];              // P keys, then K floats: the costs, then the elite flags
     uint64_t* key = reinterpret_cast<uint64_t*>(cem_lds);
     float* w = reinterpret_cast<float*>(cem_lds + a.P);
-    const int tid = (int)threadIdx.x, threads = (int)blockDim.x, lane = tid & (MPPI_WAVE - 1), wave = tid/MPPI_WAVE, waves = threads/MPPI_WAVE, K = a.K, P = a.P;
+    const int tid = (int)threadIdx.x, threads = (int)blockDim.x, lane = tid & (MPPI_WAVE - 1), wave = tid/MPPI_WAVE, waves = threads/MPPI_WAVE, K = a.in.K, P = a.P;
     const size_t Nz = (size_t)N, NK = Nz*(size_t)K, n = (size_t)blockIdx.x, base = n*(size_t)K;
     const float inf = __int_as_float(0x7F800000), nan = __int_as_float(0x7FC00000);
     for (int k = tid; k < K; k += threads) {
         const size_t col = base + (size_t)k;
-        const float cost = mppi_rollout_cost(a, Nz, NK, n, col);
+        const float cost = cost_rollout(a.in, Nz, NK, n, col);
         if (a.cost) a.cost[col] = cost;
         w[k] = cost;
         key[k] = cem_key(cost, k);
@@ -142,25 +140,25 @@ __global__ void __launch_bounds__(CEM_REFIT_WG) so100_query_cost_refit_k(CostRef
     for (int r = tid; r < K; r += threads) w[cem_key_index(key[r])] = r < n_elite ? 1.0f : 0.0f;
     __syncthreads();
     // ---- the rows ----
-    for (int r = wave; r < a.T*COST_NU; r += waves) {         // row r = (t, j); r and n_elite are the same in every lane of the wave
+    for (int r = wave; r < a.in.T*COST_NU; r += waves) {      // row r = (t, j); r and n_elite are the same in every lane of the wave
         const int t = r/COST_NU, j = r - t*COST_NU;
         float m, s;
         if (n_elite > 0) {
-            const float* u = a.u + (size_t)r*NK + base;
+            const float* u = a.in.u + (size_t)r*NK + base;
             const float mu = cem_mean(mppi_wave_sum(mppi_lane_sum<float>(K, lane, [&](int k) { return cem_sum_term<float>(w[k] != 0.0f, u[k]); })), n_elite);
             const float sd = cem_sd(mppi_wave_sum(mppi_lane_sum<float>(K, lane, [&](int k) { return cem_dev_term<float>(w[k] != 0.0f, u[k], mu); })), n_elite);
             const bool old = a.alpha > 0.0f;
             m = cem_mix<float>(a.alpha, old ? a.plan[(size_t)r*Nz + n] : 0.0f, mu);
             s = cem_sigma<float>(a.alpha, old ? a.sigma[(size_t)r*Nz + n] : 0.0f, sd, a.sigma_min[j], a.sigma_max[j]);
         } else {
-            m = a.u_fallback ? a.u_fallback[(size_t)r*Nz + n] : nan;
+            m = a.in.u_fallback ? a.in.u_fallback[(size_t)r*Nz + n] : nan;
             s = a.sigma_init[j];
         }
         if (lane == 0) {
-            mppi_place<float>(t, a.T, a.shift, a.tail, m,
+            mppi_place<float>(t, a.in.T, a.shift, a.tail, m,
                               [&](int row, float y) { if (a.mean) a.mean[((size_t)row*COST_NU + j)*Nz + n] = y; },
                               [&](float y) { if (a.u_first) a.u_first[(size_t)j*Nz + n] = y; });
-            cem_place_sigma<float>(t, a.T, a.shift, s, a.sigma_init[j], [&](int row, float y) { if (a.sigma_out) a.sigma_out[((size_t)row*COST_NU + j)*Nz + n] = y; });
+            cem_place_sigma<float>(t, a.in.T, a.shift, s, a.sigma_init[j], [&](int row, float y) { if (a.sigma_out) a.sigma_out[((size_t)row*COST_NU + j)*Nz + n] = y; });
         }
     }
 }
@@ -174,30 +172,11 @@ extern "C" {
 int so100_query_plan_sample_tv(so100_sim* sim, const so100_plan_sample_tv_io* io, int32_t N, void* stream) {
     using namespace so100;
     const char* const fn = "so100_query_plan_sample_tv";
-    if (!sim || !io) return fail(SO100_E_INVALID, "so100_query_plan_sample_tv: null argument");
-    if (const int rc = query_batch(fn, sim, false, N)) return rc;                 // no state is read: any N >= 1
-    if (io->T < 1 || io->T > SO100_TRAJ_MAX_T) return fail(SO100_E_INVALID, "%s: T must be in 1..%d, got %ld", fn, SO100_TRAJ_MAX_T, (long)io->T);
-    if (io->K < 1 || io->K > SO100_MPPI_MAX_K || (long long)N*(long long)io->K > (long long)INT32_MAX)
-        return fail(SO100_E_INVALID, "%s: K must be in 1..%d and N * K <= %ld, got K = %ld, N = %ld", fn, SO100_MPPI_MAX_K, (long)INT32_MAX, (long)io->K, (long)N);
-    if (!io->sigma_dev) return fail(SO100_E_INVALID, "%s: sigma_dev is required", fn);
-    const auto finite = [](float x) { return x*0.0f == 0.0f; };
-    if (!finite(io->u_lo) || !finite(io->u_hi) || io->u_lo > io->u_hi) return fail(SO100_E_INVALID, "%s: u_lo and u_hi must be finite and u_lo <= u_hi", fn);
-    if (!io->plan_dev) return fail(SO100_E_INVALID, "%s: plan_dev is required", fn);
-    if (io->qvel_dev && !io->qpos_dev) return fail(SO100_E_INVALID, "%s: qvel_dev needs qpos_dev", fn);
-    if ((io->qpos_rep_dev && !io->qpos_dev) || (io->qvel_rep_dev && !io->qvel_dev))
-        return fail(SO100_E_INVALID, "%s: qpos_rep_dev needs qpos_dev and qvel_rep_dev needs qvel_dev", fn);
-    if (!io->ctrl_dev && !io->qpos_rep_dev && !io->qvel_rep_dev) return fail(SO100_E_INVALID, "%s: no output requested", fn);
-    PlanSampleTvArgs a{};
-    a.plan = io->plan_dev; a.sigma = io->sigma_dev; a.lo = io->u_lo; a.hi = io->u_hi; a.K = io->K; a.T = io->T;
-    a.seed_lo = (uint32_t)(io->seed & 0xffffffffu); a.seed_hi = (uint32_t)(io->seed >> 32); a.draw = io->draw; a.id_offset = io->id_offset;
-    a.qpos = reinterpret_cast<const uint32_t*>(io->qpos_dev); a.qvel = reinterpret_cast<const uint32_t*>(io->qvel_dev);
-    a.ctrl = io->ctrl_dev; a.qpos_rep = reinterpret_cast<uint32_t*>(io->qpos_rep_dev); a.qvel_rep = reinterpret_cast<uint32_t*>(io->qvel_rep_dev);
-    SO100_ON_DEVICE(sim->cfg.device, "so100_query_plan_sample_tv");
-    const size_t cols = (size_t)N*(size_t)io->K;
-    const dim3 grid((unsigned)((cols + MPPI_SAMPLE_WG - 1)/MPPI_SAMPLE_WG)), block(MPPI_SAMPLE_WG);
-    hipLaunchKernelGGL(so100_query_plan_sample_tv_k, grid, block, 0, (hipStream_t)stream, a, N);
-    HIP_TRY(hipGetLastError(), SO100_E_LAUNCH);
-    return 0;
+    return plan_sample_entry(fn, so100_query_plan_sample_tv_k, sim, io, N, stream, [&](PlanSampleTvArgs& a) {
+        if (!io->sigma_dev) return fail(SO100_E_INVALID, "%s: sigma_dev is required", fn);
+        a.sigma = io->sigma_dev;
+        return 0;
+    });
 }
 
 int so100_query_cost_refit(so100_sim* sim, const so100_cost_refit_io* io, int32_t N, void* stream) {
@@ -205,11 +184,10 @@ int so100_query_cost_refit(so100_sim* sim, const so100_cost_refit_io* io, int32_
     const char* const fn = "so100_query_cost_refit";
     if (!sim || !io) return fail(SO100_E_INVALID, "so100_query_cost_refit: null argument");
     if (const int rc = query_batch(fn, sim, false, N)) return rc;
-    if (io->T < 1 || io->T > SO100_TRAJ_MAX_T) return fail(SO100_E_INVALID, "%s: T must be in 1..%d, got %ld", fn, SO100_TRAJ_MAX_T, (long)io->T);
-    if (io->K < 1 || io->K > SO100_MPPI_MAX_K || (long long)N*(long long)io->K > (long long)INT32_MAX)
-        return fail(SO100_E_INVALID, "%s: K must be in 1..%d and N * K <= %ld, got K = %ld, N = %ld", fn, SO100_MPPI_MAX_K, (long)INT32_MAX, (long)io->K, (long)N);
+    if (const int rc = query_steps(fn, io->T, SO100_TRAJ_MAX_T)) return rc;
+    if (const int rc = query_candidates(fn, "K", "N", io->K, SO100_MPPI_MAX_K, N)) return rc;
     CostRefitArgs a{};
-    if (const int rc = cost_def(fn, io->cost, a.c)) return rc;
+    if (const int rc = cost_def(fn, io->cost, a.in.c)) return rc;
     if (io->E < 1 || io->E > io->K) return fail(SO100_E_INVALID, "%s: E must be in 1..K, got E = %ld, K = %ld", fn, (long)io->E, (long)io->K);
     const auto finite = [](float x) { return x*0.0f == 0.0f; };
     if (!finite(io->alpha) || !(io->alpha >= 0.0f && io->alpha < 1.0f)) return fail(SO100_E_INVALID, "%s: alpha must be finite and in [0, 1)", fn);
@@ -217,24 +195,22 @@ int so100_query_cost_refit(so100_sim* sim, const so100_cost_refit_io* io, int32_
         if (!finite(io->sigma_min[j]) || !finite(io->sigma_max[j]) || !finite(io->sigma_init[j]) || io->sigma_min[j] < 0.0f || io->sigma_min[j] > io->sigma_max[j] ||
             io->sigma_init[j] < 0.0f)
             return fail(SO100_E_INVALID, "%s: sigma_min, sigma_max and sigma_init must be finite, 0 <= sigma_min <= sigma_max and sigma_init >= 0", fn);
-    if (io->shift != 0 && io->shift != 1) return fail(SO100_E_INVALID, "%s: shift must be 0 or 1, got %ld", fn, (long)io->shift);
-    if (io->tail != SO100_BLEND_TAIL_ZERO && io->tail != SO100_BLEND_TAIL_HOLD) return fail(SO100_E_INVALID, "%s: unknown tail %ld", fn, (long)io->tail);
-    if (!io->qpos_traj_dev || !io->u_traj_dev || (a.c.target_mode != COST_TARGET_CUBE && !io->target_dev) || (io->alpha > 0.0f && (!io->plan_dev || !io->sigma_dev)))
-        return fail(SO100_E_INVALID, "%s: qpos_traj_dev, u_traj_dev, (unless the target is the cube) target_dev and (with alpha > 0) plan_dev and sigma_dev are required", fn);
+    if (const int rc = plan_placement(fn, io->shift, io->tail)) return rc;
+    if (const int rc = cost_rollouts(fn, *io, io->K, "qpos_traj_dev, u_traj_dev, (unless the target is the cube) target_dev and (with alpha > 0) plan_dev and sigma_dev",
+                                     io->alpha > 0.0f && (!io->plan_dev || !io->sigma_dev), a.in)) return rc;
     if (!io->cost_dev && !io->best_dev && !io->best_cost_dev && !io->elite_dev && !io->n_elite_dev && !io->threshold_dev && !io->mean_dev && !io->sigma_out_dev &&
         !io->u_first_dev)
         return fail(SO100_E_INVALID, "%s: no output requested", fn);
-    a.target = io->target_dev; a.qpos = io->qpos_traj_dev; a.qvel = io->qvel_traj_dev; a.u = io->u_traj_dev; a.bad_step = io->bad_step_dev;
-    a.u_fallback = io->u_fallback_dev; a.T = io->T; a.K = io->K; a.E = io->E; a.alpha = io->alpha; a.plan = io->plan_dev; a.sigma = io->sigma_dev;
+    a.E = io->E; a.alpha = io->alpha; a.plan = io->plan_dev; a.sigma = io->sigma_dev;
     for (int j = 0; j < 6; j++) { a.sigma_min[j] = io->sigma_min[j]; a.sigma_max[j] = io->sigma_max[j]; a.sigma_init[j] = io->sigma_init[j]; }
     a.shift = io->shift; a.tail = io->tail;
     a.P = MPPI_WAVE;
-    while (a.P < a.K) a.P <<= 1;
+    while (a.P < io->K) a.P <<= 1;
     a.cost = io->cost_dev; a.best = io->best_dev; a.best_cost = io->best_cost_dev; a.elite = io->elite_dev; a.n_elite = io->n_elite_dev;
     a.threshold = io->threshold_dev; a.mean = io->mean_dev; a.sigma_out = io->sigma_out_dev; a.u_first = io->u_first_dev;
     SO100_ON_DEVICE(sim->cfg.device, "so100_query_cost_refit");
     const dim3 grid((unsigned)N), block(CEM_REFIT_WG);
-    hipLaunchKernelGGL(so100_query_cost_refit_k, grid, block, (size_t)a.P*sizeof(uint64_t) + (size_t)a.K*sizeof(float), (hipStream_t)stream, a, N);
+    hipLaunchKernelGGL(so100_query_cost_refit_k, grid, block, (size_t)a.P*sizeof(uint64_t) + (size_t)io->K*sizeof(float), (hipStream_t)stream, a, N);
     HIP_TRY(hipGetLastError(), SO100_E_LAUNCH);
     return 0;
 }

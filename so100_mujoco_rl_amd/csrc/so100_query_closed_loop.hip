@@ -25,13 +25,12 @@ constexpr bool CL_LDS = false;
 #endif
 
 struct ClosedLoopArgs {
-    const float *qpos, *qvel; int ld; const float* state;    // as in TrajectoryArgs
+    QueryStart start;
     const float *u, *qpos_ref, *qvel_ref, *qpos_ref0, *qvel_ref0, *k, *K;
     int nx, L; float alpha[CL_MAX_L];
     int clamp; float u_lo, u_hi;
     int mode, T, nsub; unsigned flags; int solver_iters, contact_iters;
-    float *u_traj, *qpos_traj, *qvel_traj, *ee_traj, *qpos_final, *qvel_final;
-    int32_t *ncon, *dropped, *sig; float* residual; int32_t* bad_step;
+    float* u_traj; QueryRollOut out;                         // u_traj [T][6][M L]: the controls the law made, NaN from a failed step on
 };
 
 // the most problems one wave of 64 consecutive rollouts can touch: 64 / L whole groups and, where L does not divide 64, a cut one at each end
@@ -81,16 +80,16 @@ __global__ void __launch_bounds__(WG) so100_query_closed_loop_k(ClosedLoopArgs a
     const size_t L = (size_t)a.L, m = i/L;
     const int cand = (int)(i - m*L);
     const unsigned flags = FL >= 0 ? (unsigned)FL : a.flags;
-    const size_t ml = (size_t)ML, ld = (size_t)a.ld;
+    const size_t ml = (size_t)ML, ld = (size_t)a.start.ld;
     float qpos[13], qvel[12];
 #pragma unroll
-    for (int k = 0; k < 13; k++) qpos[k] = a.qpos[k*ld + m];
+    for (int k = 0; k < 13; k++) qpos[k] = a.start.qpos[k*ld + m];
 #pragma unroll
-    for (int k = 0; k < 12; k++) qvel[k] = a.qvel ? a.qvel[k*ld + m] : 0.0f;
+    for (int k = 0; k < 12; k++) qvel[k] = a.start.qvel ? a.start.qvel[k*ld + m] : 0.0f;
     TrajState<float> s;
     trajectory_cold(qpos, qvel, s);
-    if (a.state) {                                           // the handle's simulation goes on: its warm starts, Kahan rows and anti-gravity bit
-        const float* S = a.state;
+    if (a.start.state) {                                     // the handle's simulation goes on: its warm starts, Kahan rows and anti-gravity bit
+        const float* S = a.start.state;
 #pragma unroll
         for (int k = 0; k < 6; k++) {
             s.ff[k] = S[(SF_ff0 + k)*ld + m]; s.fl[k] = S[(SF_fl0 + k)*ld + m]; s.cube.warm[k] = S[(SF_cw0 + k)*ld + m]; s.qc[k] = S[(SF_qc0 + k)*ld + m];
@@ -114,43 +113,43 @@ __global__ void __launch_bounds__(WG) so100_query_closed_loop_k(ClosedLoopArgs a
 #pragma unroll
                 for (int k = 0; k < 6; k++) a.u_traj[(row*6 + k)*ml + i] = ok ? c[k] : nan;
             }
-            if (a.qpos_traj || a.qvel_traj) {
+            if (a.out.qpos_traj || a.out.qvel_traj) {
                 float qp[13], qv[12];
                 trajectory_qpos_qvel(st, qp, qv);
-                if (a.qpos_traj) {
+                if (a.out.qpos_traj) {
 #pragma unroll
-                    for (int k = 0; k < 13; k++) a.qpos_traj[(row*13 + k)*ml + i] = ok ? qp[k] : nan;
+                    for (int k = 0; k < 13; k++) a.out.qpos_traj[(row*13 + k)*ml + i] = ok ? qp[k] : nan;
                 }
-                if (a.qvel_traj) {
+                if (a.out.qvel_traj) {
 #pragma unroll
-                    for (int k = 0; k < 12; k++) a.qvel_traj[(row*12 + k)*ml + i] = ok ? qv[k] : nan;
+                    for (int k = 0; k < 12; k++) a.out.qvel_traj[(row*12 + k)*ml + i] = ok ? qv[k] : nan;
                 }
             }
-            if (a.ee_traj) {
+            if (a.out.ee_traj) {
                 float ee[3] = { nan, nan, nan };
                 if (ok) trajectory_ee(st.q, ee);
 #pragma unroll
-                for (int k = 0; k < 3; k++) a.ee_traj[(row*3 + k)*ml + i] = ee[k];
+                for (int k = 0; k < 3; k++) a.out.ee_traj[(row*3 + k)*ml + i] = ee[k];
             }
-            if (a.ncon) a.ncon[row*ml + i] = ok ? (o.cstat & 255) : 0;
-            if (a.dropped) a.dropped[row*ml + i] = ok ? (o.cstat >> 8) : 0;
-            if (a.sig) a.sig[row*ml + i] = ok ? o.csig : 0;
-            if (a.residual) a.residual[row*ml + i] = ok ? o.res : nan;
+            if (a.out.ncon) a.out.ncon[row*ml + i] = ok ? (o.cstat & 255) : 0;
+            if (a.out.dropped) a.out.dropped[row*ml + i] = ok ? (o.cstat >> 8) : 0;
+            if (a.out.sig) a.out.sig[row*ml + i] = ok ? o.csig : 0;
+            if (a.out.residual) a.out.residual[row*ml + i] = ok ? o.res : nan;
         });
     if (!live) return;
-    if (a.qpos_final || a.qvel_final) {
+    if (a.out.qpos_final || a.out.qvel_final) {
         float qp[13], qv[12];
         trajectory_qpos_qvel(s, qp, qv);
-        if (a.qpos_final) {
+        if (a.out.qpos_final) {
 #pragma unroll
-            for (int k = 0; k < 13; k++) a.qpos_final[k*ml + i] = bad < 0 ? qp[k] : nan;
+            for (int k = 0; k < 13; k++) a.out.qpos_final[k*ml + i] = bad < 0 ? qp[k] : nan;
         }
-        if (a.qvel_final) {
+        if (a.out.qvel_final) {
 #pragma unroll
-            for (int k = 0; k < 12; k++) a.qvel_final[k*ml + i] = bad < 0 ? qv[k] : nan;
+            for (int k = 0; k < 12; k++) a.out.qvel_final[k*ml + i] = bad < 0 ? qv[k] : nan;
         }
     }
-    if (a.bad_step) a.bad_step[i] = bad;
+    if (a.out.bad_step) a.out.bad_step[i] = bad;
 }
 
 }  // namespace so100
@@ -166,13 +165,10 @@ int so100_query_closed_loop(so100_sim* sim, const so100_closed_loop_io* io, int3
     QueryStart st;
     if (const int rc = query_start(fn, sim, io->qpos_dev, io->qvel_dev, M, st)) return rc;
     if (const int rc = query_control(fn, io->u_dev, io->mode)) return rc;
-    if (io->T < 1 || io->T > SO100_TRAJ_MAX_T || io->nsub < 1 || io->nsub > SO100_TRAJ_MAX_NSUB || (long)io->T*(long)io->nsub > SO100_TRAJ_MAX_SUBSTEPS)
-        return fail(SO100_E_INVALID, "%s: T must be in 1..%d, nsub in 1..%d and T * nsub <= %d, got T = %ld, nsub = %ld", fn, SO100_TRAJ_MAX_T, SO100_TRAJ_MAX_NSUB,
-                    SO100_TRAJ_MAX_SUBSTEPS, (long)io->T, (long)io->nsub);
+    if (const int rc = query_horizon(fn, io->T, io->nsub)) return rc;
     if (const int rc = query_solver(fn, io->flags, io->solver_iters, io->contact_iters)) return rc;
     if (io->nx != 12 && io->nx != 24) return fail(SO100_E_INVALID, "%s: nx must be 12 or 24, got %ld", fn, (long)io->nx);
-    if (io->L < 1 || io->L > SO100_CL_MAX_L || (long long)M*(long long)io->L > (long long)INT32_MAX)
-        return fail(SO100_E_INVALID, "%s: L must be in 1..%d and M * L <= %ld, got L = %ld, M = %ld", fn, SO100_CL_MAX_L, (long)INT32_MAX, (long)io->L, (long)M);
+    if (const int rc = query_candidates(fn, "L", "M", io->L, SO100_CL_MAX_L, M)) return rc;
     if (!io->alpha || !io->K_dev || (io->T > 1 && (!io->qpos_ref_dev || !io->qvel_ref_dev)))
         return fail(SO100_E_INVALID, "%s: alpha, K_dev and (for T > 1) qpos_ref_dev and qvel_ref_dev are required", fn);
     if (!io->qpos_ref0_dev != !io->qvel_ref0_dev) return fail(SO100_E_INVALID, "%s: qpos_ref0_dev and qvel_ref0_dev are given together or not at all", fn);
@@ -180,19 +176,14 @@ int so100_query_closed_loop(so100_sim* sim, const so100_closed_loop_io* io, int3
         if (!(io->alpha[q]*0.0f == 0.0f)) return fail(SO100_E_INVALID, "%s: alpha[%d] must be finite, got %g", fn, q, (double)io->alpha[q]);
     if (io->clamp && (!(io->u_lo <= io->u_hi) || !((io->u_lo + io->u_hi)*0.0f == 0.0f)))
         return fail(SO100_E_INVALID, "%s: u_lo and u_hi must be finite with u_lo <= u_hi, got %g and %g", fn, (double)io->u_lo, (double)io->u_hi);
-    if (!io->u_traj_dev && !io->qpos_traj_dev && !io->qvel_traj_dev && !io->ee_traj_dev && !io->qpos_final_dev && !io->qvel_final_dev && !io->ncon_dev &&
-        !io->dropped_dev && !io->sig_dev && !io->residual_dev && !io->bad_step_dev)
-        return fail(SO100_E_INVALID, "%s: no output requested", fn);
     ClosedLoopArgs a{};
-    a.qpos = st.qpos; a.qvel = st.qvel; a.ld = st.ld; a.state = st.state;
+    if (const int rc = query_roll_out(fn, *io, io->u_traj_dev, a.out)) return rc;
+    a.start = st; a.u_traj = io->u_traj_dev;
     a.u = io->u_dev; a.qpos_ref = io->qpos_ref_dev; a.qvel_ref = io->qvel_ref_dev; a.qpos_ref0 = io->qpos_ref0_dev; a.qvel_ref0 = io->qvel_ref0_dev;
     a.k = io->k_dev; a.K = io->K_dev; a.nx = io->nx; a.L = io->L;
     for (int q = 0; q < CL_MAX_L; q++) a.alpha[q] = q < io->L ? io->alpha[q] : 0.0f;
     a.clamp = io->clamp; a.u_lo = io->u_lo; a.u_hi = io->u_hi;
     a.mode = io->mode; a.T = io->T; a.nsub = io->nsub; a.flags = io->flags; a.solver_iters = io->solver_iters; a.contact_iters = io->contact_iters;
-    a.u_traj = io->u_traj_dev; a.qpos_traj = io->qpos_traj_dev; a.qvel_traj = io->qvel_traj_dev; a.ee_traj = io->ee_traj_dev;
-    a.qpos_final = io->qpos_final_dev; a.qvel_final = io->qvel_final_dev;
-    a.ncon = io->ncon_dev; a.dropped = io->dropped_dev; a.sig = io->sig_dev; a.residual = io->residual_dev; a.bad_step = io->bad_step_dev;
     SO100_ON_DEVICE(sim->cfg.device, "so100_query_closed_loop");
     const int ML = M*io->L;
     const dim3 grid((unsigned)(((size_t)ML + WG - 1)/WG)), block(WG);

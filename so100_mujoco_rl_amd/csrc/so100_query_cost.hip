@@ -31,11 +31,16 @@ struct CostTermsArgs {
     int T;
     float *lx, *lxx, *lu, *luu;
 };
-struct CostSelectArgs {
+// the rollouts a planner query prices (select, and the blend and refit of the files behind this one): [T][k][columns] rows of `columns` rollouts, the
+// candidates of a problem side by side; target and u_fallback are per problem.  qvel, bad_step and u_fallback may be null
+struct CostRollouts {
     CostDef<float> c;
     const float *target, *qpos, *qvel, *u;
     const int32_t* bad_step; const float* u_fallback;
-    int T, L;
+    int T, K;                                                // steps; candidates of a problem (select's L)
+};
+struct CostSelectArgs {
+    CostRollouts in;
     float* cost; int32_t* best; float* best_cost; float* u_best;
 };
 
@@ -130,8 +135,28 @@ __global__ void __launch_bounds__(COST_TERMS_WG) so100_query_cost_terms_k(CostTe
     });
 }
 
+// what rollout `col` of problem n costs: the sum of its T steps and the terminal term, +inf where it failed or the sum is not finite
+__device__ __forceinline__ float cost_rollout(const CostRollouts& a, size_t problems, size_t columns, size_t n, size_t col) {
+    const float total = cost_total<float>(a.c, a.T, [&](int t, float q[6], float v[6], float u[6], float g[3]) {
+        const float* qp = a.qpos + (size_t)t*13*columns;
+#pragma unroll
+        for (int j = 0; j < 6; j++) {
+            q[j] = qp[(size_t)j*columns + col];
+            v[j] = a.qvel ? a.qvel[((size_t)t*12 + j)*columns + col] : 0.0f;
+            u[j] = a.u[((size_t)t*6 + j)*columns + col];
+        }
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+            if (a.c.target_mode == COST_TARGET_CUBE) g[i] = qp[(size_t)(6 + i)*columns + col];
+            else g[i] = a.target[((a.c.target_mode == COST_TARGET_TRAJ ? (size_t)t*3 : (size_t)0) + i)*problems + n];
+        }
+    });
+    const bool failed = a.bad_step && a.bad_step[col] >= 0;
+    return (failed || !cost_finite(total)) ? __int_as_float(0x7F800000) : total;
+}
+
 __global__ void __launch_bounds__(COST_WAVE) so100_query_cost_select_k(CostSelectArgs a, int M) {
-    const int lane = (int)threadIdx.x, L = a.L, G = COST_WAVE/L;
+    const int lane = (int)threadIdx.x, L = a.in.K, G = COST_WAVE/L;
     const int grp = lane/L, cand = lane - grp*L;
     const size_t Mz = (size_t)M, ML = Mz*(size_t)L, m = (size_t)blockIdx.x*(size_t)G + (size_t)grp;
     const bool live = grp < G && m < Mz;
@@ -139,22 +164,7 @@ __global__ void __launch_bounds__(COST_WAVE) so100_query_cost_select_k(CostSelec
     const float inf = __int_as_float(0x7F800000), nan = __int_as_float(0x7FC00000);
     float cost = inf;
     if (live) {
-        const float total = cost_total<float>(a.c, a.T, [&](int t, float q[6], float v[6], float u[6], float g[3]) {
-            const float* qp = a.qpos + (size_t)t*13*ML;
-#pragma unroll
-            for (int j = 0; j < 6; j++) {
-                q[j] = qp[(size_t)j*ML + col];
-                v[j] = a.qvel ? a.qvel[((size_t)t*12 + j)*ML + col] : 0.0f;
-                u[j] = a.u[((size_t)t*6 + j)*ML + col];
-            }
-#pragma unroll
-            for (int i = 0; i < 3; i++) {
-                if (a.c.target_mode == COST_TARGET_CUBE) g[i] = qp[(size_t)(6 + i)*ML + col];
-                else g[i] = a.target[((a.c.target_mode == COST_TARGET_TRAJ ? (size_t)t*3 : (size_t)0) + i)*Mz + m];
-            }
-        });
-        const bool failed = a.bad_step && a.bad_step[col] >= 0;
-        cost = (failed || !cost_finite(total)) ? inf : total;
+        cost = cost_rollout(a.in, Mz, ML, m, col);
         if (a.cost) a.cost[col] = cost;
     }
     if (!a.best && !a.best_cost && !a.u_best) return;        // uniform: the whole wave leaves or stays
@@ -167,11 +177,11 @@ __global__ void __launch_bounds__(COST_WAVE) so100_query_cost_select_k(CostSelec
         if (a.best_cost) a.best_cost[m] = best_cost;
     }
     if (a.u_best) {
-        const int words = a.T*COST_NU;                       // the (t, j) rows of the winner's column, dealt over the group's lanes
+        const int words = a.in.T*COST_NU;                     // the (t, j) rows of the winner's column, dealt over the group's lanes
         for (int w = cand; w < words; w += L) {
             float x = nan;
-            if (best >= 0) x = a.u[(size_t)w*ML + m*(size_t)L + (size_t)best];
-            else if (a.u_fallback) x = a.u_fallback[(size_t)w*Mz + m];
+            if (best >= 0) x = a.in.u[(size_t)w*ML + m*(size_t)L + (size_t)best];
+            else if (a.in.u_fallback) x = a.in.u_fallback[(size_t)w*Mz + m];
             a.u_best[(size_t)w*Mz + m] = x;
         }
     }
@@ -198,6 +208,17 @@ int cost_def(const char* fn, const so100_cost_def* d, CostDef<float>& c) {
     return 0;
 }
 
+// the rollouts of a select, blend or refit io struct (K candidates a problem), behind cost_def(fn, io.cost, in.c): the pointers every one of them needs (`also_missing`: one the
+// entry needs beside them is null; `required`: the message's list of both) and the block's copy for the launch
+template <typename IO> int cost_rollouts(const char* fn, const IO& io, int32_t K, const char* required, bool also_missing, CostRollouts& in) {
+    if (!io.qpos_traj_dev || !io.u_traj_dev || (in.c.target_mode != COST_TARGET_CUBE && !io.target_dev) || also_missing)
+        return fail(SO100_E_INVALID, "%s: %s are required", fn, required);
+    in.target = io.target_dev; in.qpos = io.qpos_traj_dev; in.qvel = io.qvel_traj_dev; in.u = io.u_traj_dev; in.bad_step = io.bad_step_dev;
+    in.u_fallback = io.u_fallback_dev; in.T = io.T; in.K = K;
+    return 0;
+}
+constexpr const char* COST_ROLLOUTS_REQUIRED = "qpos_traj_dev, u_traj_dev and (unless the target is the cube) target_dev";
+
 bool cost_aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
 }  // namespace
@@ -215,7 +236,7 @@ int so100_query_cost_terms(so100_sim* sim, const so100_cost_terms_io* io, int32_
     if (!sim || !io) return fail(SO100_E_INVALID, "so100_query_cost_terms: null argument");
     if (const int rc = query_batch(fn, sim, false, M)) return rc;                 // no state is read: any M >= 1
     if (io->nx != 12 && io->nx != 24) return fail(SO100_E_INVALID, "%s: nx must be 12 or 24, got %ld", fn, (long)io->nx);
-    if (io->T < 1 || io->T > SO100_LQR_MAX_T) return fail(SO100_E_INVALID, "%s: T must be in 1..%d, got %ld", fn, SO100_LQR_MAX_T, (long)io->T);
+    if (const int rc = query_steps(fn, io->T, SO100_LQR_MAX_T)) return rc;
     CostTermsArgs a{};
     if (const int rc = cost_def(fn, io->cost, a.c)) return rc;
     if (!io->qpos_traj_dev || !io->u_dev || (a.c.target_mode != COST_TARGET_CUBE && !io->target_dev))
@@ -242,16 +263,12 @@ int so100_query_cost_select(so100_sim* sim, const so100_cost_select_io* io, int3
     const char* const fn = "so100_query_cost_select";
     if (!sim || !io) return fail(SO100_E_INVALID, "so100_query_cost_select: null argument");
     if (const int rc = query_batch(fn, sim, false, M)) return rc;
-    if (io->T < 1 || io->T > SO100_LQR_MAX_T) return fail(SO100_E_INVALID, "%s: T must be in 1..%d, got %ld", fn, SO100_LQR_MAX_T, (long)io->T);
-    if (io->L < 1 || io->L > SO100_CL_MAX_L || (long long)M*(long long)io->L > (long long)INT32_MAX)
-        return fail(SO100_E_INVALID, "%s: L must be in 1..%d and M * L <= %ld, got L = %ld, M = %ld", fn, SO100_CL_MAX_L, (long)INT32_MAX, (long)io->L, (long)M);
+    if (const int rc = query_steps(fn, io->T, SO100_LQR_MAX_T)) return rc;
+    if (const int rc = query_candidates(fn, "L", "M", io->L, SO100_CL_MAX_L, M)) return rc;
     CostSelectArgs a{};
-    if (const int rc = cost_def(fn, io->cost, a.c)) return rc;
-    if (!io->qpos_traj_dev || !io->u_traj_dev || (a.c.target_mode != COST_TARGET_CUBE && !io->target_dev))
-        return fail(SO100_E_INVALID, "%s: qpos_traj_dev, u_traj_dev and (unless the target is the cube) target_dev are required", fn);
+    if (const int rc = cost_def(fn, io->cost, a.in.c)) return rc;
+    if (const int rc = cost_rollouts(fn, *io, io->L, COST_ROLLOUTS_REQUIRED, false, a.in)) return rc;
     if (!io->cost_dev && !io->best_dev && !io->best_cost_dev && !io->u_best_dev) return fail(SO100_E_INVALID, "%s: no output requested", fn);
-    a.target = io->target_dev; a.qpos = io->qpos_traj_dev; a.qvel = io->qvel_traj_dev; a.u = io->u_traj_dev; a.bad_step = io->bad_step_dev;
-    a.u_fallback = io->u_fallback_dev; a.T = io->T; a.L = io->L;
     a.cost = io->cost_dev; a.best = io->best_dev; a.best_cost = io->best_cost_dev; a.u_best = io->u_best_dev;
     SO100_ON_DEVICE(sim->cfg.device, "so100_query_cost_select");
     const size_t per_wave = (size_t)(COST_WAVE/io->L);

@@ -15,8 +15,7 @@
 namespace so100 {
 
 struct DerivativeArgs {
-    const float *qpos, *qvel; int ld;                        // ld: row length of qpos / qvel (M, or N for the handle's rows)
-    const float* state;                                      // the handle's state matrix where its state is read, else null
+    QueryStart start;
     const float* ctrl;
     int mode, nsub; unsigned flags; int solver_iters, contact_iters;
     float eps, r;                                            // r = 1/(2 eps), formed once on the host
@@ -28,18 +27,18 @@ __global__ void __launch_bounds__(64) so100_query_derivative_k(DerivativeArgs a,
     const size_t i = blockIdx.x;                             // the problem: wave-uniform
     const int lane = (int)threadIdx.x;                       // the role
     const unsigned flags = FL >= 0 ? (unsigned)FL : a.flags;
-    const size_t m = (size_t)M, ld = (size_t)a.ld;
+    const size_t m = (size_t)M, ld = (size_t)a.start.ld;
     float qpos[13], qvel[12], c[6];
 #pragma unroll
-    for (int k = 0; k < 13; k++) qpos[k] = a.qpos[k*ld + i];
+    for (int k = 0; k < 13; k++) qpos[k] = a.start.qpos[k*ld + i];
 #pragma unroll
-    for (int k = 0; k < 12; k++) qvel[k] = a.qvel ? a.qvel[k*ld + i] : 0.0f;
+    for (int k = 0; k < 12; k++) qvel[k] = a.start.qvel ? a.start.qvel[k*ld + i] : 0.0f;
 #pragma unroll
     for (int k = 0; k < 6; k++) c[k] = a.ctrl[k*m + i];
     TrajState<float> s;
     trajectory_cold(qpos, qvel, s);
-    if (a.state) {                                           // every lane reads the same warm starts, Kahan rows and anti-gravity bit
-        const float* S = a.state;
+    if (a.start.state) {                                     // every lane reads the same warm starts, Kahan rows and anti-gravity bit
+        const float* S = a.start.state;
 #pragma unroll
         for (int k = 0; k < 6; k++) {
             s.ff[k] = S[(SF_ff0 + k)*ld + i]; s.fl[k] = S[(SF_fl0 + k)*ld + i]; s.cube.warm[k] = S[(SF_cw0 + k)*ld + i]; s.qc[k] = S[(SF_qc0 + k)*ld + i];
@@ -105,7 +104,7 @@ int so100_query_derivatives(so100_sim* sim, const so100_derivatives_io* io, int3
     if (!(io->eps > 0.0f) || !(io->eps*0.0f == 0.0f)) return fail(SO100_E_INVALID, "%s: eps must be finite and > 0, got %g", fn, (double)io->eps);
     if (!io->A_dev && !io->B_dev && !io->qpos_next_dev && !io->qvel_next_dev && !io->bad_dev) return fail(SO100_E_INVALID, "%s: no output requested", fn);
     DerivativeArgs a{};
-    a.qpos = st.qpos; a.qvel = st.qvel; a.ld = st.ld; a.state = st.state;
+    a.start = st;
     a.ctrl = io->ctrl_dev; a.mode = io->mode; a.nsub = io->nsub; a.flags = io->flags; a.solver_iters = io->solver_iters; a.contact_iters = io->contact_iters;
     a.eps = io->eps; a.r = 0.5f/io->eps;
     a.A = io->A_dev; a.B = io->B_dev; a.qpos_next = io->qpos_next_dev; a.qvel_next = io->qvel_next_dev; a.bad = io->bad_dev;

@@ -1,6 +1,6 @@
 // so100_query_mppi.hip -- the two sampling-planner queries (gfx950) and their C ABI (include/so100_query.h: so100_query_plan_sample,
 // so100_query_cost_blend); every number's arithmetic is in so100_mppi.hpp.  Like so100_query_cost.hip, not a translation unit of its own:
-// so100_sim.hip includes it behind that file and it uses its cost_def(), and query_batch() and fail() of the files before.
+// so100_sim.hip includes it behind that file and it uses its cost_def(), cost_rollouts() and cost_rollout(), and the checks of the files before.
 //
 // Sample.  One lane per candidate column c = n K + k, walking t: two Philox blocks and four Box-Muller pairs per (column, step), six stores.  The
 // lanes of a wave are consecutive k of a problem (or of two, at a problem's end), so each store of a wave is one contiguous segment of an SoA row
@@ -30,10 +30,7 @@ struct PlanSampleArgs {
     float* ctrl; uint32_t *qpos_rep, *qvel_rep;
 };
 struct CostBlendArgs {
-    CostDef<float> c;
-    const float *target, *qpos, *qvel, *u;
-    const int32_t* bad_step; const float* u_fallback;
-    int T, K;
+    CostRollouts in;
     float lambda; int shift, tail;
     float* cost; int32_t* best; float *best_cost, *weight, *ess, *u_plan, *u_first;
 };
@@ -76,40 +73,14 @@ __device__ __forceinline__ float mppi_wave_sum(float x) {
     return x;
 }
 
-// the summed cost of rollout column `col` of problem n.  A: CostBlendArgs, or so100_query_cem.hip's with the same input fields
-template <typename A> __device__ __forceinline__ float mppi_rollout_total(const A& a, size_t Nz, size_t NK, size_t n, size_t col) {
-    return cost_total<float>(a.c, a.T, [&](int t, float q[6], float v[6], float u[6], float g[3]) {
-        const float* qp = a.qpos + (size_t)t*13*NK;
-#pragma unroll
-        for (int j = 0; j < 6; j++) {
-            q[j] = qp[(size_t)j*NK + col];
-            v[j] = a.qvel ? a.qvel[((size_t)t*12 + j)*NK + col] : 0.0f;
-            u[j] = a.u[((size_t)t*6 + j)*NK + col];
-        }
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-            if (a.c.target_mode == COST_TARGET_CUBE) g[i] = qp[(size_t)(6 + i)*NK + col];
-            else g[i] = a.target[((a.c.target_mode == COST_TARGET_TRAJ ? (size_t)t*3 : (size_t)0) + i)*Nz + n];
-        }
-    });
-}
-// what a rollout costs: +inf where it failed or its sum is not finite
-template <typename A> __device__ __forceinline__ float mppi_rollout_cost(const A& a, size_t Nz, size_t NK, size_t n, size_t col) {
-    const float total = mppi_rollout_total(a, Nz, NK, n, col);
-    const bool failed = a.bad_step && a.bad_step[col] >= 0;
-    return (failed || !cost_finite(total)) ? __int_as_float(0x7F800000) : total;
-}
-
 __global__ void __launch_bounds__(MPPI_BLEND_WG) so100_query_cost_blend_k(CostBlendArgs a, int N) {
     extern __shared__ float w[];                             // K floats: the costs, then e, then the weights
-    const int tid = (int)threadIdx.x, threads = (int)blockDim.x, lane = tid & (MPPI_WAVE - 1), wave = tid/MPPI_WAVE, waves = threads/MPPI_WAVE, K = a.K;
+    const int tid = (int)threadIdx.x, threads = (int)blockDim.x, lane = tid & (MPPI_WAVE - 1), wave = tid/MPPI_WAVE, waves = threads/MPPI_WAVE, K = a.in.K;
     const size_t Nz = (size_t)N, NK = Nz*(size_t)K, n = (size_t)blockIdx.x, base = n*(size_t)K;
     const float inf = __int_as_float(0x7F800000), nan = __int_as_float(0x7FC00000);
     for (int k = tid; k < K; k += threads) {
         const size_t col = base + (size_t)k;
-        const float total = mppi_rollout_total(a, Nz, NK, n, col);
-        const bool failed = a.bad_step && a.bad_step[col] >= 0;
-        const float cost = (failed || !cost_finite(total)) ? inf : total;
+        const float cost = cost_rollout(a.in, Nz, NK, n, col);
         if (a.cost) a.cost[col] = cost;
         w[k] = cost;
     }
@@ -145,22 +116,63 @@ __global__ void __launch_bounds__(MPPI_BLEND_WG) so100_query_cost_blend_k(CostBl
         if (lane == 0) a.ess[n] = best >= 0 ? 1.0f/s2 : 0.0f;
     }
     if (!a.u_plan && !a.u_first) return;
-    for (int r = wave; r < a.T*COST_NU; r += waves) {         // row r = (t, j); r and best are the same in every lane of the wave
+    for (int r = wave; r < a.in.T*COST_NU; r += waves) {      // row r = (t, j); r and best are the same in every lane of the wave
         const int t = r/COST_NU, j = r - t*COST_NU;
         float x;
         if (best >= 0) {
-            const float* u = a.u + (size_t)r*NK + base;
+            const float* u = a.in.u + (size_t)r*NK + base;
             x = mppi_wave_sum(mppi_lane_sum<float>(K, lane, [&](int k) { return mppi_term<float>(w[k], u[k]); }));
         } else {
-            x = a.u_fallback ? a.u_fallback[(size_t)r*Nz + n] : nan;
+            x = a.in.u_fallback ? a.in.u_fallback[(size_t)r*Nz + n] : nan;
         }
         if (lane == 0)
-            mppi_place<float>(t, a.T, a.shift, a.tail, x,
+            mppi_place<float>(t, a.in.T, a.shift, a.tail, x,
                               [&](int row, float y) { if (a.u_plan) a.u_plan[((size_t)row*COST_NU + j)*Nz + n] = y; },
                               [&](float y) { if (a.u_first) a.u_first[(size_t)j*Nz + n] = y; });
     }
 }
 
+}  // namespace so100
+
+namespace so100 {
+namespace {
+
+// where a refreshed plan goes: the blend's and the refit's
+int plan_placement(const char* fn, int32_t shift, int32_t tail) {
+    if (shift != 0 && shift != 1) return fail(SO100_E_INVALID, "%s: shift must be 0 or 1, got %ld", fn, (long)shift);
+    if (tail != SO100_BLEND_TAIL_ZERO && tail != SO100_BLEND_TAIL_HOLD) return fail(SO100_E_INVALID, "%s: unknown tail %ld", fn, (long)tail);
+    return 0;
+}
+
+// a sampler's entry: Args is its kernel's argument struct; sigma(a) checks the io struct's sigma and puts it into a, where the two samplers differ
+template <typename Args, typename IO, typename Sigma>
+int plan_sample_entry(const char* fn, void (*kernel)(Args, int), so100_sim* sim, const IO* io, int32_t N, void* stream, Sigma&& sigma) {
+    if (!sim || !io) return fail(SO100_E_INVALID, "%s: null argument", fn);
+    if (const int rc = query_batch(fn, sim, false, N)) return rc;                 // no state is read: any N >= 1
+    if (const int rc = query_steps(fn, io->T, SO100_TRAJ_MAX_T)) return rc;
+    if (const int rc = query_candidates(fn, "K", "N", io->K, SO100_MPPI_MAX_K, N)) return rc;
+    Args a{};
+    if (const int rc = sigma(a)) return rc;
+    const auto finite = [](float x) { return x*0.0f == 0.0f; };
+    if (!finite(io->u_lo) || !finite(io->u_hi) || io->u_lo > io->u_hi) return fail(SO100_E_INVALID, "%s: u_lo and u_hi must be finite and u_lo <= u_hi", fn);
+    if (!io->plan_dev) return fail(SO100_E_INVALID, "%s: plan_dev is required", fn);
+    if (io->qvel_dev && !io->qpos_dev) return fail(SO100_E_INVALID, "%s: qvel_dev needs qpos_dev", fn);
+    if ((io->qpos_rep_dev && !io->qpos_dev) || (io->qvel_rep_dev && !io->qvel_dev))
+        return fail(SO100_E_INVALID, "%s: qpos_rep_dev needs qpos_dev and qvel_rep_dev needs qvel_dev", fn);
+    if (!io->ctrl_dev && !io->qpos_rep_dev && !io->qvel_rep_dev) return fail(SO100_E_INVALID, "%s: no output requested", fn);
+    a.plan = io->plan_dev; a.lo = io->u_lo; a.hi = io->u_hi; a.K = io->K; a.T = io->T;
+    a.seed_lo = (uint32_t)(io->seed & 0xffffffffu); a.seed_hi = (uint32_t)(io->seed >> 32); a.draw = io->draw; a.id_offset = io->id_offset;
+    a.qpos = reinterpret_cast<const uint32_t*>(io->qpos_dev); a.qvel = reinterpret_cast<const uint32_t*>(io->qvel_dev);
+    a.ctrl = io->ctrl_dev; a.qpos_rep = reinterpret_cast<uint32_t*>(io->qpos_rep_dev); a.qvel_rep = reinterpret_cast<uint32_t*>(io->qvel_rep_dev);
+    SO100_ON_DEVICE(sim->cfg.device, fn);
+    const size_t cols = (size_t)N*(size_t)io->K;
+    const dim3 grid((unsigned)((cols + MPPI_SAMPLE_WG - 1)/MPPI_SAMPLE_WG)), block(MPPI_SAMPLE_WG);
+    hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)stream, a, N);
+    HIP_TRY(hipGetLastError(), SO100_E_LAUNCH);
+    return 0;
+}
+
+}  // namespace
 }  // namespace so100
 
 static_assert(SO100_MPPI_MAX_K == so100::MPPI_MAX_K && SO100_BLEND_TAIL_ZERO == so100::BLEND_TAIL_ZERO && SO100_BLEND_TAIL_HOLD == so100::BLEND_TAIL_HOLD &&
@@ -172,32 +184,13 @@ extern "C" {
 int so100_query_plan_sample(so100_sim* sim, const so100_plan_sample_io* io, int32_t N, void* stream) {
     using namespace so100;
     const char* const fn = "so100_query_plan_sample";
-    if (!sim || !io) return fail(SO100_E_INVALID, "so100_query_plan_sample: null argument");
-    if (const int rc = query_batch(fn, sim, false, N)) return rc;                 // no state is read: any N >= 1
-    if (io->T < 1 || io->T > SO100_TRAJ_MAX_T) return fail(SO100_E_INVALID, "%s: T must be in 1..%d, got %ld", fn, SO100_TRAJ_MAX_T, (long)io->T);
-    if (io->K < 1 || io->K > SO100_MPPI_MAX_K || (long long)N*(long long)io->K > (long long)INT32_MAX)
-        return fail(SO100_E_INVALID, "%s: K must be in 1..%d and N * K <= %ld, got K = %ld, N = %ld", fn, SO100_MPPI_MAX_K, (long)INT32_MAX, (long)io->K, (long)N);
-    const auto finite = [](float x) { return x*0.0f == 0.0f; };
-    for (int j = 0; j < 6; j++)
-        if (!finite(io->sigma[j]) || io->sigma[j] < 0.0f) return fail(SO100_E_INVALID, "%s: sigma must be finite and >= 0", fn);
-    if (!finite(io->u_lo) || !finite(io->u_hi) || io->u_lo > io->u_hi) return fail(SO100_E_INVALID, "%s: u_lo and u_hi must be finite and u_lo <= u_hi", fn);
-    if (!io->plan_dev) return fail(SO100_E_INVALID, "%s: plan_dev is required", fn);
-    if (io->qvel_dev && !io->qpos_dev) return fail(SO100_E_INVALID, "%s: qvel_dev needs qpos_dev", fn);
-    if ((io->qpos_rep_dev && !io->qpos_dev) || (io->qvel_rep_dev && !io->qvel_dev))
-        return fail(SO100_E_INVALID, "%s: qpos_rep_dev needs qpos_dev and qvel_rep_dev needs qvel_dev", fn);
-    if (!io->ctrl_dev && !io->qpos_rep_dev && !io->qvel_rep_dev) return fail(SO100_E_INVALID, "%s: no output requested", fn);
-    PlanSampleArgs a{};
-    a.plan = io->plan_dev; a.lo = io->u_lo; a.hi = io->u_hi; a.K = io->K; a.T = io->T;
-    for (int j = 0; j < 6; j++) a.sigma[j] = io->sigma[j];
-    a.seed_lo = (uint32_t)(io->seed & 0xffffffffu); a.seed_hi = (uint32_t)(io->seed >> 32); a.draw = io->draw; a.id_offset = io->id_offset;
-    a.qpos = reinterpret_cast<const uint32_t*>(io->qpos_dev); a.qvel = reinterpret_cast<const uint32_t*>(io->qvel_dev);
-    a.ctrl = io->ctrl_dev; a.qpos_rep = reinterpret_cast<uint32_t*>(io->qpos_rep_dev); a.qvel_rep = reinterpret_cast<uint32_t*>(io->qvel_rep_dev);
-    SO100_ON_DEVICE(sim->cfg.device, "so100_query_plan_sample");
-    const size_t cols = (size_t)N*(size_t)io->K;
-    const dim3 grid((unsigned)((cols + MPPI_SAMPLE_WG - 1)/MPPI_SAMPLE_WG)), block(MPPI_SAMPLE_WG);
-    hipLaunchKernelGGL(so100_query_plan_sample_k, grid, block, 0, (hipStream_t)stream, a, N);
-    HIP_TRY(hipGetLastError(), SO100_E_LAUNCH);
-    return 0;
+    return plan_sample_entry(fn, so100_query_plan_sample_k, sim, io, N, stream, [&](PlanSampleArgs& a) {
+        for (int j = 0; j < 6; j++) {
+            if (!(io->sigma[j]*0.0f == 0.0f) || io->sigma[j] < 0.0f) return fail(SO100_E_INVALID, "%s: sigma must be finite and >= 0", fn);
+            a.sigma[j] = io->sigma[j];
+        }
+        return 0;
+    });
 }
 
 int so100_query_cost_blend(so100_sim* sim, const so100_cost_blend_io* io, int32_t N, void* stream) {
@@ -205,20 +198,16 @@ int so100_query_cost_blend(so100_sim* sim, const so100_cost_blend_io* io, int32_
     const char* const fn = "so100_query_cost_blend";
     if (!sim || !io) return fail(SO100_E_INVALID, "so100_query_cost_blend: null argument");
     if (const int rc = query_batch(fn, sim, false, N)) return rc;
-    if (io->T < 1 || io->T > SO100_TRAJ_MAX_T) return fail(SO100_E_INVALID, "%s: T must be in 1..%d, got %ld", fn, SO100_TRAJ_MAX_T, (long)io->T);
-    if (io->K < 1 || io->K > SO100_MPPI_MAX_K || (long long)N*(long long)io->K > (long long)INT32_MAX)
-        return fail(SO100_E_INVALID, "%s: K must be in 1..%d and N * K <= %ld, got K = %ld, N = %ld", fn, SO100_MPPI_MAX_K, (long)INT32_MAX, (long)io->K, (long)N);
+    if (const int rc = query_steps(fn, io->T, SO100_TRAJ_MAX_T)) return rc;
+    if (const int rc = query_candidates(fn, "K", "N", io->K, SO100_MPPI_MAX_K, N)) return rc;
     CostBlendArgs a{};
-    if (const int rc = cost_def(fn, io->cost, a.c)) return rc;
+    if (const int rc = cost_def(fn, io->cost, a.in.c)) return rc;
     if (!(io->temperature*0.0f == 0.0f) || !(io->temperature > 0.0f)) return fail(SO100_E_INVALID, "%s: temperature must be finite and > 0", fn);
-    if (io->shift != 0 && io->shift != 1) return fail(SO100_E_INVALID, "%s: shift must be 0 or 1, got %ld", fn, (long)io->shift);
-    if (io->tail != SO100_BLEND_TAIL_ZERO && io->tail != SO100_BLEND_TAIL_HOLD) return fail(SO100_E_INVALID, "%s: unknown tail %ld", fn, (long)io->tail);
-    if (!io->qpos_traj_dev || !io->u_traj_dev || (a.c.target_mode != COST_TARGET_CUBE && !io->target_dev))
-        return fail(SO100_E_INVALID, "%s: qpos_traj_dev, u_traj_dev and (unless the target is the cube) target_dev are required", fn);
+    if (const int rc = plan_placement(fn, io->shift, io->tail)) return rc;
+    if (const int rc = cost_rollouts(fn, *io, io->K, COST_ROLLOUTS_REQUIRED, false, a.in)) return rc;
     if (!io->cost_dev && !io->best_dev && !io->best_cost_dev && !io->weight_dev && !io->ess_dev && !io->u_plan_dev && !io->u_first_dev)
         return fail(SO100_E_INVALID, "%s: no output requested", fn);
-    a.target = io->target_dev; a.qpos = io->qpos_traj_dev; a.qvel = io->qvel_traj_dev; a.u = io->u_traj_dev; a.bad_step = io->bad_step_dev;
-    a.u_fallback = io->u_fallback_dev; a.T = io->T; a.K = io->K; a.lambda = io->temperature; a.shift = io->shift; a.tail = io->tail;
+    a.lambda = io->temperature; a.shift = io->shift; a.tail = io->tail;
     a.cost = io->cost_dev; a.best = io->best_dev; a.best_cost = io->best_cost_dev; a.weight = io->weight_dev; a.ess = io->ess_dev;
     a.u_plan = io->u_plan_dev; a.u_first = io->u_first_dev;
     SO100_ON_DEVICE(sim->cfg.device, "so100_query_cost_blend");

@@ -13,12 +13,10 @@
 namespace so100 {
 
 struct TrajectoryArgs {
-    const float *qpos, *qvel; int ld;                        // ld: row length of qpos / qvel (M, or N for the handle's rows)
-    const float* state;                                      // the handle's state matrix where its state is read (warm starts, Kahan rows, bits), else null
+    QueryStart start;
     const float* ctrl;
     int mode, T, nsub; unsigned flags; int solver_iters, contact_iters;
-    float *qpos_traj, *qvel_traj, *ee_traj, *qpos_final, *qvel_final;
-    int32_t *ncon, *dropped, *sig; float* residual; int32_t* bad_step;
+    QueryRollOut out;
 };
 
 template <int FL>
@@ -26,16 +24,16 @@ __global__ void __launch_bounds__(WG) so100_query_trajectory_k(TrajectoryArgs a,
     const size_t i = (size_t)blockIdx.x*WG + threadIdx.x;
     if (i >= (size_t)M) return;
     const unsigned flags = FL >= 0 ? (unsigned)FL : a.flags;
-    const size_t m = (size_t)M, ld = (size_t)a.ld;
+    const size_t m = (size_t)M, ld = (size_t)a.start.ld;
     float qpos[13], qvel[12];
 #pragma unroll
-    for (int k = 0; k < 13; k++) qpos[k] = a.qpos[k*ld + i];
+    for (int k = 0; k < 13; k++) qpos[k] = a.start.qpos[k*ld + i];
 #pragma unroll
-    for (int k = 0; k < 12; k++) qvel[k] = a.qvel ? a.qvel[k*ld + i] : 0.0f;
+    for (int k = 0; k < 12; k++) qvel[k] = a.start.qvel ? a.start.qvel[k*ld + i] : 0.0f;
     TrajState<float> s;
     trajectory_cold(qpos, qvel, s);
-    if (a.state) {                                           // the handle's simulation goes on: its warm starts, Kahan rows and anti-gravity bit
-        const float* S = a.state;
+    if (a.start.state) {
+        const float* S = a.start.state;
 #pragma unroll
         for (int k = 0; k < 6; k++) {
             s.ff[k] = S[(SF_ff0 + k)*ld + i]; s.fl[k] = S[(SF_fl0 + k)*ld + i]; s.cube.warm[k] = S[(SF_cw0 + k)*ld + i]; s.qc[k] = S[(SF_qc0 + k)*ld + i];
@@ -51,42 +49,42 @@ __global__ void __launch_bounds__(WG) so100_query_trajectory_k(TrajectoryArgs a,
         },
         [&](int t, bool ok, const TrajState<float>& st, const TrajStep<float>& o) {
             const size_t row = (size_t)t;
-            if (a.qpos_traj || a.qvel_traj) {
+            if (a.out.qpos_traj || a.out.qvel_traj) {
                 float qp[13], qv[12];
                 trajectory_qpos_qvel(st, qp, qv);
-                if (a.qpos_traj) {
+                if (a.out.qpos_traj) {
 #pragma unroll
-                    for (int k = 0; k < 13; k++) a.qpos_traj[(row*13 + k)*m + i] = ok ? qp[k] : nan;
+                    for (int k = 0; k < 13; k++) a.out.qpos_traj[(row*13 + k)*m + i] = ok ? qp[k] : nan;
                 }
-                if (a.qvel_traj) {
+                if (a.out.qvel_traj) {
 #pragma unroll
-                    for (int k = 0; k < 12; k++) a.qvel_traj[(row*12 + k)*m + i] = ok ? qv[k] : nan;
+                    for (int k = 0; k < 12; k++) a.out.qvel_traj[(row*12 + k)*m + i] = ok ? qv[k] : nan;
                 }
             }
-            if (a.ee_traj) {
+            if (a.out.ee_traj) {
                 float ee[3] = { nan, nan, nan };
                 if (ok) trajectory_ee(st.q, ee);
 #pragma unroll
-                for (int k = 0; k < 3; k++) a.ee_traj[(row*3 + k)*m + i] = ee[k];
+                for (int k = 0; k < 3; k++) a.out.ee_traj[(row*3 + k)*m + i] = ee[k];
             }
-            if (a.ncon) a.ncon[row*m + i] = ok ? (o.cstat & 255) : 0;
-            if (a.dropped) a.dropped[row*m + i] = ok ? (o.cstat >> 8) : 0;
-            if (a.sig) a.sig[row*m + i] = ok ? o.csig : 0;
-            if (a.residual) a.residual[row*m + i] = ok ? o.res : nan;
+            if (a.out.ncon) a.out.ncon[row*m + i] = ok ? (o.cstat & 255) : 0;
+            if (a.out.dropped) a.out.dropped[row*m + i] = ok ? (o.cstat >> 8) : 0;
+            if (a.out.sig) a.out.sig[row*m + i] = ok ? o.csig : 0;
+            if (a.out.residual) a.out.residual[row*m + i] = ok ? o.res : nan;
         });
-    if (a.qpos_final || a.qvel_final) {
+    if (a.out.qpos_final || a.out.qvel_final) {
         float qp[13], qv[12];
         trajectory_qpos_qvel(s, qp, qv);
-        if (a.qpos_final) {
+        if (a.out.qpos_final) {
 #pragma unroll
-            for (int k = 0; k < 13; k++) a.qpos_final[k*m + i] = bad < 0 ? qp[k] : nan;
+            for (int k = 0; k < 13; k++) a.out.qpos_final[k*m + i] = bad < 0 ? qp[k] : nan;
         }
-        if (a.qvel_final) {
+        if (a.out.qvel_final) {
 #pragma unroll
-            for (int k = 0; k < 12; k++) a.qvel_final[k*m + i] = bad < 0 ? qv[k] : nan;
+            for (int k = 0; k < 12; k++) a.out.qvel_final[k*m + i] = bad < 0 ? qv[k] : nan;
         }
     }
-    if (a.bad_step) a.bad_step[i] = bad;
+    if (a.out.bad_step) a.out.bad_step[i] = bad;
 }
 
 }  // namespace so100
@@ -95,7 +93,6 @@ static_assert(SO100_TRAJ_TARGETS == so100::TRAJ_TARGETS && SO100_TRAJ_ACTIONS ==
 static_assert(SO100_TRAJ_MAX_T == so100::TRAJ_MAX_T && SO100_TRAJ_MAX_NSUB == so100::TRAJ_MAX_NSUB && SO100_TRAJ_MAX_SUBSTEPS == so100::TRAJ_MAX_SUBSTEPS,
               "the header names the limits");
 static_assert(so100::TRAJ_ACTION_SCALE == so100::JOINT_STEP_SCALE, "actions mode is the reach envs' control law");
-static_assert(SF_ff0 + 5 == SF_ff5 && SF_fl0 + 5 == SF_fl5 && SF_cw0 + 5 == SF_cw5 && SF_qc0 + 5 == SF_qc5 && SF_aw0 + 5 == SF_aw5, "six consecutive rows each");
 
 extern "C" {
 
@@ -106,18 +103,12 @@ int so100_query_trajectory(so100_sim* sim, const so100_trajectory_io* io, int32_
     QueryStart st;
     if (const int rc = query_start(fn, sim, io->qpos_dev, io->qvel_dev, M, st)) return rc;
     if (const int rc = query_control(fn, io->ctrl_dev, io->mode)) return rc;
-    if (io->T < 1 || io->T > SO100_TRAJ_MAX_T || io->nsub < 1 || io->nsub > SO100_TRAJ_MAX_NSUB || (long)io->T*(long)io->nsub > SO100_TRAJ_MAX_SUBSTEPS)
-        return fail(SO100_E_INVALID, "%s: T must be in 1..%d, nsub in 1..%d and T * nsub <= %d, got T = %ld, nsub = %ld", fn, SO100_TRAJ_MAX_T, SO100_TRAJ_MAX_NSUB,
-                    SO100_TRAJ_MAX_SUBSTEPS, (long)io->T, (long)io->nsub);
+    if (const int rc = query_horizon(fn, io->T, io->nsub)) return rc;
     if (const int rc = query_solver(fn, io->flags, io->solver_iters, io->contact_iters)) return rc;
-    if (!io->qpos_traj_dev && !io->qvel_traj_dev && !io->ee_traj_dev && !io->qpos_final_dev && !io->qvel_final_dev && !io->ncon_dev && !io->dropped_dev &&
-        !io->sig_dev && !io->residual_dev && !io->bad_step_dev)
-        return fail(SO100_E_INVALID, "%s: no output requested", fn);
     TrajectoryArgs a{};
-    a.qpos = st.qpos; a.qvel = st.qvel; a.ld = st.ld; a.state = st.state;
+    if (const int rc = query_roll_out(fn, *io, nullptr, a.out)) return rc;
+    a.start = st;
     a.ctrl = io->ctrl_dev; a.mode = io->mode; a.T = io->T; a.nsub = io->nsub; a.flags = io->flags; a.solver_iters = io->solver_iters; a.contact_iters = io->contact_iters;
-    a.qpos_traj = io->qpos_traj_dev; a.qvel_traj = io->qvel_traj_dev; a.ee_traj = io->ee_traj_dev; a.qpos_final = io->qpos_final_dev; a.qvel_final = io->qvel_final_dev;
-    a.ncon = io->ncon_dev; a.dropped = io->dropped_dev; a.sig = io->sig_dev; a.residual = io->residual_dev; a.bad_step = io->bad_step_dev;
     SO100_ON_DEVICE(sim->cfg.device, "so100_query_trajectory");
     const dim3 grid((unsigned)(((size_t)M + WG - 1)/WG)), block(WG);
     SO100_WITH_QUERY_FLAGS(io->flags, hipLaunchKernelGGL((so100_query_trajectory_k<FL>), grid, block, 0, (hipStream_t)stream, a, M););

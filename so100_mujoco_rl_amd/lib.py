@@ -5,6 +5,7 @@ device pointer (`tensor.data_ptr()`) plus the current HIP stream handle.  There 
 shared object is missing or no HIP device is usable, loading / `So100Sim()` raises.
 """
 import ctypes as C
+import math
 import os
 import subprocess
 
@@ -677,6 +678,23 @@ class So100Sim(_Handle):
     def _offset(offset):
         return None if offset is None else (C.c_float * 3)(*[float(v) for v in offset])
 
+    @staticmethod
+    def _six(x, name):
+        """float[6] of six values or of one for all (a number of any kind, a sequence or a tensor)"""
+        v = torch.as_tensor(x, dtype=torch.float32).reshape(-1).tolist()
+        if len(v) not in (1, 6):
+            raise So100Error(f"{name}: want 6 values or one for all, got {len(v)}")
+        return (C.c_float*6)(*(v*6 if len(v) == 1 else v))
+
+    def _stepping(self, what, mode, nsub, flags, solver_iters, contact_iters):
+        """(mode, nsub, flags, solver_iters, contact_iters) as the io structs of trajectory(), derivatives() and closed_loop() hold them: the
+        mode's number, and the handle's own value for each None"""
+        if mode not in TRAJ_MODES:
+            raise So100Error(f"{what}: mode must be one of {sorted(TRAJ_MODES)}, got {mode!r}")
+        c = self.cfg
+        return (TRAJ_MODES[mode], c.frame_skip if nsub is None else nsub, c.flags if flags is None else flags,
+                c.solver_iters if solver_iters is None else solver_iters, c.contact_iters if contact_iters is None else contact_iters)
+
     def kinematics(self, q=None):
         """World poses from joint angles q [M, 6] (None: the handle's current joints, M = N).  Returns a dict of views, one row per problem:
         "xpos" [M, 6, 3] and "xmat" [M, 6, 3, 3] of the six link frames (link k = MuJoCo body k + 2), "ee" [M, 3] the reference's
@@ -753,8 +771,7 @@ class So100Sim(_Handle):
         end-effector point at that q), "ncon", "dropped", "sig" [T, M] int32 and "residual" [T, M] (what the contact_stat, contact_sig and
         solver_residual rows would hold after such a step) and "bad_step" [M] int32: the first step whose controls or resulting state are not
         finite (-1: none); from there on that problem's float rows are NaN and its int rows 0."""
-        if mode not in TRAJ_MODES:
-            raise So100Error(f"trajectory: mode must be one of {sorted(TRAJ_MODES)}, got {mode!r}")
+        md, *knobs = self._stepping("trajectory", mode, nsub, flags, solver_iters, contact_iters)
         ctrl = torch.as_tensor(ctrl, dtype=torch.float32, device=self.device)
         if ctrl.dim() != 3 or ctrl.shape[2] != 6 or ctrl.shape[0] < 1:
             raise So100Error(f"ctrl: want a [T, M, 6] tensor, got {tuple(ctrl.shape)}")
@@ -764,11 +781,7 @@ class So100Sim(_Handle):
         i32 = dict(dtype=torch.int32)
         qt, vt, et = self._out(M, T, 13), self._out(M, T, 12), self._out(M, T, 3)
         ncon, drop, sig, res, bad = self._out(M, T, **i32), self._out(M, T, **i32), self._out(M, T, **i32), self._out(M, T), self._out(M, **i32)
-        c = self.cfg
-        io = TrajectoryIO(_optr(qs), _optr(vs), us.data_ptr(), TRAJ_MODES[mode], T,
-                          c.frame_skip if nsub is None else nsub, c.flags if flags is None else flags,
-                          c.solver_iters if solver_iters is None else solver_iters, c.contact_iters if contact_iters is None else contact_iters,
-                          qt.data_ptr(), vt.data_ptr(), et.data_ptr(), None, None, ncon.data_ptr(), drop.data_ptr(), sig.data_ptr(), res.data_ptr(), bad.data_ptr())
+        io = TrajectoryIO(_optr(qs), _optr(vs), us.data_ptr(), md, T, *knobs, qt.data_ptr(), vt.data_ptr(), et.data_ptr(), None, None, ncon.data_ptr(), drop.data_ptr(), sig.data_ptr(), res.data_ptr(), bad.data_ptr())
         _check(self.L.so100_query_trajectory(self.h, C.byref(io), M, self._stream()), "so100_query_trajectory")
         return {"qpos": qt.permute(0, 2, 1), "qvel": vt.permute(0, 2, 1), "ee": et.permute(0, 2, 1), "ncon": ncon, "dropped": drop, "sig": sig,
                 "residual": res, "bad_step": bad}
@@ -781,17 +794,12 @@ class So100Sim(_Handle):
         dx'/dx, "B" [M, 24, 6] = dx'/du, "qpos_next" [M, 13] and "qvel_next" [M, 12] (the unperturbed step) and "bad" [M] int32: 1 where the
         start, the controls or any of the 61 evaluations is not finite; that problem's float outputs are NaN.  With friction loss, limits or
         contacts the step is not smooth and the result depends on eps."""
-        if mode not in TRAJ_MODES:
-            raise So100Error(f"derivatives: mode must be one of {sorted(TRAJ_MODES)}, got {mode!r}")
+        md, *knobs = self._stepping("derivatives", mode, nsub, flags, solver_iters, contact_iters)
         us, qs, vs = self._soa(ctrl, 6, "ctrl"), self._soa(qpos, 13, "qpos"), self._soa(qvel, 12, "qvel"); M = self._problems(qs, vs, us)
         A = torch.empty(M, DERIV_NX, DERIV_NX, dtype=torch.float32, device=self.device)
         B = torch.empty(M, DERIV_NX, DERIV_NU, dtype=torch.float32, device=self.device)
         qn, vn, bad = self._out(M, 13), self._out(M, 12), self._out(M, dtype=torch.int32)
-        c = self.cfg
-        io = DerivativesIO(_optr(qs), _optr(vs), us.data_ptr(), TRAJ_MODES[mode],
-                           c.frame_skip if nsub is None else nsub, c.flags if flags is None else flags,
-                           c.solver_iters if solver_iters is None else solver_iters, c.contact_iters if contact_iters is None else contact_iters,
-                           DERIV_EPS if eps is None else eps, A.data_ptr(), B.data_ptr(), qn.data_ptr(), vn.data_ptr(), bad.data_ptr())
+        io = DerivativesIO(_optr(qs), _optr(vs), us.data_ptr(), md, *knobs, DERIV_EPS if eps is None else eps, A.data_ptr(), B.data_ptr(), qn.data_ptr(), vn.data_ptr(), bad.data_ptr())
         _check(self.L.so100_query_derivatives(self.h, C.byref(io), M, self._stream()), "so100_query_derivatives")
         return {"A": A, "B": B, "qpos_next": qn.t(), "qvel_next": vn.t(), "bad": bad}
 
@@ -834,8 +842,7 @@ class So100Sim(_Handle):
         x (-) xref is the derivatives query's tangent difference.  Returns views with L = len(alphas): "u" [T, M, L, 6] the controls applied (the chosen
         candidate's is the next plan), "qpos" [T, M, L, 13], "qvel" [T, M, L, 12], "ee" [T, M, L, 3], "ncon", "dropped", "sig" [T, M, L] int32, "residual"
         [T, M, L] and "bad_step" [M, L] int32: trajectory()'s, firing also where a gain, nominal control or reference value read at that step is not finite."""
-        if mode not in TRAJ_MODES:
-            raise So100Error(f"closed_loop: mode must be one of {sorted(TRAJ_MODES)}, got {mode!r}")
+        md, *knobs = self._stepping("closed_loop", mode, nsub, flags, solver_iters, contact_iters)
         if nx not in (12, 24):
             raise So100Error(f"closed_loop: nx must be 12 or 24, got {nx!r}")
         u = torch.as_tensor(u, dtype=torch.float32, device=self.device)
@@ -865,11 +872,8 @@ class So100Sim(_Handle):
         ut, qt, vt, et = self._out(ML, T, 6), self._out(ML, T, 13), self._out(ML, T, 12), self._out(ML, T, 3)
         ncon, drop, sig, res, bad = self._out(ML, T, **i32), self._out(ML, T, **i32), self._out(ML, T, **i32), self._out(ML, T), self._out(ML, **i32)
         alpha = (C.c_float*L)(*al)
-        c = self.cfg
         lo, hi = (0.0, 0.0) if clamp is None else clamp
-        io = ClosedLoopIO(_optr(qs), _optr(vs), us.data_ptr(), TRAJ_MODES[mode], T, c.frame_skip if nsub is None else nsub, c.flags if flags is None else flags,
-                          c.solver_iters if solver_iters is None else solver_iters, c.contact_iters if contact_iters is None else contact_iters,
-                          _optr(rq), _optr(rv), _optr(r0q), _optr(r0v), nx, _optr(kt), _optr(Kt), L, C.cast(alpha, C.c_void_p), int(clamp is not None), lo, hi,
+        io = ClosedLoopIO(_optr(qs), _optr(vs), us.data_ptr(), md, T, *knobs, _optr(rq), _optr(rv), _optr(r0q), _optr(r0v), nx, _optr(kt), _optr(Kt), L, C.cast(alpha, C.c_void_p), int(clamp is not None), lo, hi,
                           ut.data_ptr(), qt.data_ptr(), vt.data_ptr(), et.data_ptr(), None, None, ncon.data_ptr(), drop.data_ptr(), sig.data_ptr(), res.data_ptr(),
                           bad.data_ptr())
         _check(self.L.so100_query_closed_loop(self.h, C.byref(io), M, self._stream()), "so100_query_closed_loop")
@@ -883,7 +887,6 @@ class So100Sim(_Handle):
             target_mode = "cube" if target is None else ("fixed" if torch.as_tensor(target).dim() == 2 else "traj")
         if target_mode not in COST_TARGETS:
             raise So100Error(f"{what}: target_mode must be one of {sorted(COST_TARGETS)}, got {target_mode!r}")
-        six = lambda w: (C.c_float*6)(*([float(w)]*6 if isinstance(w, (int, float)) else [float(x) for x in w]))
         off = self._offset(offset)
         tg = None
         if target_mode != "cube":
@@ -894,9 +897,29 @@ class So100Sim(_Handle):
             if tuple(tg.shape) != want:
                 raise So100Error(f"target: want a {list(want)} tensor, got {tuple(tg.shape)}")
             tg = tg.transpose(-1, -2).contiguous()
-        d = CostDef(link, C.cast(off, C.c_void_p) if off is not None else None, COST_TARGETS[target_mode], w_point, six(w_q), six(q_nom), six(w_v), six(w_u),
-                    w_terminal)
+        d = CostDef(link, C.cast(off, C.c_void_p) if off is not None else None, COST_TARGETS[target_mode], w_point, self._six(w_q, "w_q"), self._six(q_nom, "q_nom"),
+                    self._six(w_v, "w_v"), self._six(w_u, "w_u"), w_terminal)
         return d, off, tg
+
+    def _rollouts(self, what, qpos, qvel, u, lead, bad_step, u_fallback, N):
+        """The rollout arrays of cost_select(), cost_blend() and cost_refit() in the kernels' layout.  lead = (T, M, L) or (T, N K): qpos, qvel (None
+        stays None) and u of shape lead + (k,) become [T][k][columns] -- closed_loop()'s and trajectory()'s views: no copy --, bad_step ([M, L], or
+        N K values) [columns] int32 and u_fallback [T, N, 6] becomes [T][6][N]"""
+        T, columns = lead[0], math.prod(lead[1:])
+        soa = lambda t, k, name: None if t is None else self._shaped(t, (*lead, k), name).movedim(-1, 1).reshape(T, k, columns).contiguous()
+        qs, vs, us = soa(qpos, 13, "qpos"), soa(qvel, 12, "qvel"), soa(u, 6, "u")
+        if qs is None:
+            raise So100Error(f"{what}: qpos is required")
+        bs = None
+        if bad_step is not None:
+            bs = torch.as_tensor(bad_step, dtype=torch.int32, device=self.device)
+            if len(lead) == 3 and tuple(bs.shape) != tuple(lead[1:]):
+                raise So100Error(f"bad_step: want a [{lead[1]}, {lead[2]}] tensor, got {tuple(bs.shape)}")
+            if bs.numel() != columns:
+                raise So100Error(f"bad_step: want {columns} values, got {tuple(bs.shape)}")
+            bs = bs.reshape(columns).contiguous()
+        fb = None if u_fallback is None else self._shaped(u_fallback, (T, N, 6), "u_fallback").permute(0, 2, 1).contiguous()
+        return qs, vs, us, bs, fb
 
     def cost_terms(self, qpos, qvel, u, *, nx=24, target=None, target_mode=None, link=EE_LINK, offset=None, w_point=1.0, w_q=0.0, q_nom=0.0, w_v=0.0,
                    w_u=0.0, w_terminal=1.0):
@@ -935,17 +958,7 @@ class So100Sim(_Handle):
         if u.dim() != 4 or u.shape[3] != 6 or u.shape[0] < 1 or u.shape[1] < 1 or not 1 <= u.shape[2] <= CL_MAX_L:
             raise So100Error(f"u: want a [T, M, L, 6] tensor with L in 1..{CL_MAX_L}, got {tuple(u.shape)}")
         T, M, L = u.shape[0], u.shape[1], u.shape[2]
-        cols = lambda t, k, name: None if t is None else self._shaped(t, (T, M, L, k), name).permute(0, 3, 1, 2).reshape(T, k, M*L).contiguous()   # closed_loop()'s views: no copy
-        qs, vs, us = cols(qpos, 13, "qpos"), cols(qvel, 12, "qvel"), cols(u, 6, "u")
-        if qs is None:
-            raise So100Error("cost_select: qpos is required")
-        bs = None
-        if bad_step is not None:
-            bs = torch.as_tensor(bad_step, dtype=torch.int32, device=self.device)
-            if tuple(bs.shape) != (M, L):
-                raise So100Error(f"bad_step: want a [{M}, {L}] tensor, got {tuple(bs.shape)}")
-            bs = bs.reshape(M*L).contiguous()
-        fb = None if u_fallback is None else self._shaped(u_fallback, (T, M, 6), "u_fallback").permute(0, 2, 1).contiguous()
+        qs, vs, us, bs, fb = self._rollouts("cost_select", qpos, qvel, u, (T, M, L), bad_step, u_fallback, M)
         d, keep, tg = self._cost("cost_select", T, M, target, target_mode, link, offset, w_point, w_q, q_nom, w_v, w_u, w_terminal)
         cost, best, bc, ub = self._out(M*L), self._out(M, dtype=torch.int32), self._out(M), self._out(M, T, 6)
         io = CostSelectIO(C.pointer(d), _optr(tg), T, L, qs.data_ptr(), _optr(vs), us.data_ptr(), _optr(bs), _optr(fb), cost.data_ptr(), best.data_ptr(),
@@ -960,25 +973,29 @@ class So100Sim(_Handle):
         the planner's call counter, id_offset the global index of problem 0.  qpos [N, 13] and qvel [N, 12] (optional): the start states to fan
         out.  Returns views of the SoA buffers, candidate (n, k) in row n K + k: "ctrl" [T, N K, 6] and, where given, "qpos" [N K, 13] and "qvel"
         [N K, 12] -- trajectory(res["ctrl"], res["qpos"], res["qvel"]) copies none of them."""
+        return self._plan_sample("plan_sample", plan, K, sigma, False, seed, draw, id_offset, u_lo, u_hi, qpos, qvel)
+
+    def _plan_sample(self, what, plan, K, sigma, per_entry, seed, draw, id_offset, u_lo, u_hi, qpos, qvel):
+        """plan_sample() and plan_sample_tv() (per_entry: sigma is a [T, N, 6] tensor read on the device)"""
         plan = torch.as_tensor(plan, dtype=torch.float32, device=self.device)
         if plan.dim() != 3 or plan.shape[2] != 6 or plan.shape[0] < 1 or plan.shape[1] < 1:
             raise So100Error(f"plan: want a [T, N, 6] tensor, got {tuple(plan.shape)}")
         T, N = plan.shape[0], plan.shape[1]
         if not 1 <= K <= MPPI_MAX_K:
-            raise So100Error(f"plan_sample: K must be in 1..{MPPI_MAX_K}, got {K!r}")
+            raise So100Error(f"{what}: K must be in 1..{MPPI_MAX_K}, got {K!r}")
         if qvel is not None and qpos is None:
-            raise So100Error("plan_sample: qvel needs qpos")
+            raise So100Error(f"{what}: qvel needs qpos")
         ps = plan.permute(0, 2, 1).contiguous()
+        if per_entry:
+            sg = self._shaped(sigma, (T, N, 6), "sigma").permute(0, 2, 1).contiguous()
         qs, vs = self._soa(qpos, 13, "qpos"), self._soa(qvel, 12, "qvel")
         self._problems(ps[0], qs, vs)
         ctrl = self._out(N*K, T, 6)
         qr, vr = (None if qs is None else self._out(N*K, 13)), (None if vs is None else self._out(N*K, 12))
-        sg = torch.as_tensor(sigma, dtype=torch.float32).reshape(-1).tolist()      # a number of any kind (one for all), or six
-        if len(sg) not in (1, 6):
-            raise So100Error(f"sigma: want 6 values or one for all, got {len(sg)}")
-        sg = (C.c_float*6)(*(sg*6 if len(sg) == 1 else sg))
-        io = PlanSampleIO(ps.data_ptr(), sg, u_lo, u_hi, K, T, seed, draw, id_offset, _optr(qs), _optr(vs), ctrl.data_ptr(), _optr(qr), _optr(vr))
-        _check(self.L.so100_query_plan_sample(self.h, C.byref(io), N, self._stream()), "so100_query_plan_sample")
+        IO = PlanSampleTvIO if per_entry else PlanSampleIO
+        io = IO(ps.data_ptr(), sg.data_ptr() if per_entry else self._six(sigma, "sigma"), u_lo, u_hi, K, T, seed, draw, id_offset, _optr(qs), _optr(vs),
+                ctrl.data_ptr(), _optr(qr), _optr(vr))
+        _check(getattr(self.L, "so100_query_" + what)(self.h, C.byref(io), N, self._stream()), "so100_query_" + what)
         res = {"ctrl": ctrl.permute(0, 2, 1)}
         if qr is not None:
             res["qpos"] = qr.t()
@@ -1002,17 +1019,7 @@ class So100Sim(_Handle):
             raise So100Error(f"cost_blend: tail must be one of {sorted(BLEND_TAILS)}, got {tail!r}")
         T, NK = u.shape[0], u.shape[1]
         N = NK//K
-        rows = lambda t, k, name: None if t is None else self._shaped(t, (T, NK, k), name).permute(0, 2, 1).contiguous()     # trajectory()'s views: no copy
-        qs, vs, us = rows(qpos, 13, "qpos"), rows(qvel, 12, "qvel"), rows(u, 6, "u")
-        if qs is None:
-            raise So100Error("cost_blend: qpos is required")
-        bs = None
-        if bad_step is not None:
-            bs = torch.as_tensor(bad_step, dtype=torch.int32, device=self.device)
-            if bs.numel() != NK:
-                raise So100Error(f"bad_step: want {NK} values, got {tuple(bs.shape)}")
-            bs = bs.reshape(NK).contiguous()
-        fb = None if u_fallback is None else self._shaped(u_fallback, (T, N, 6), "u_fallback").permute(0, 2, 1).contiguous()
+        qs, vs, us, bs, fb = self._rollouts("cost_blend", qpos, qvel, u, (T, NK), bad_step, u_fallback, N)
         d, keep, tg = self._cost("cost_blend", T, N, target, target_mode, link, offset, w_point, w_q, q_nom, w_v, w_u, w_terminal)
         cost, best, bc, wt, ess = self._out(NK), self._out(N, dtype=torch.int32), self._out(N), self._out(NK), self._out(N)
         up, uf = self._out(N, T, 6), self._out(N, 6)
@@ -1027,27 +1034,7 @@ class So100Sim(_Handle):
         copy).  An entry with sigma 0 is never perturbed; one whose sigma is negative or not finite is NaN in every candidate but candidate 0.
         With sigma[t, n, j] = s[j] the result is plan_sample(plan, K, s)'s bit for bit.  Everything else, the returned views included: as in
         plan_sample()."""
-        plan = torch.as_tensor(plan, dtype=torch.float32, device=self.device)
-        if plan.dim() != 3 or plan.shape[2] != 6 or plan.shape[0] < 1 or plan.shape[1] < 1:
-            raise So100Error(f"plan: want a [T, N, 6] tensor, got {tuple(plan.shape)}")
-        T, N = plan.shape[0], plan.shape[1]
-        if not 1 <= K <= MPPI_MAX_K:
-            raise So100Error(f"plan_sample_tv: K must be in 1..{MPPI_MAX_K}, got {K!r}")
-        if qvel is not None and qpos is None:
-            raise So100Error("plan_sample_tv: qvel needs qpos")
-        ps, sg = plan.permute(0, 2, 1).contiguous(), self._shaped(sigma, (T, N, 6), "sigma").permute(0, 2, 1).contiguous()
-        qs, vs = self._soa(qpos, 13, "qpos"), self._soa(qvel, 12, "qvel")
-        self._problems(ps[0], qs, vs)
-        ctrl = self._out(N*K, T, 6)
-        qr, vr = (None if qs is None else self._out(N*K, 13)), (None if vs is None else self._out(N*K, 12))
-        io = PlanSampleTvIO(ps.data_ptr(), sg.data_ptr(), u_lo, u_hi, K, T, seed, draw, id_offset, _optr(qs), _optr(vs), ctrl.data_ptr(), _optr(qr), _optr(vr))
-        _check(self.L.so100_query_plan_sample_tv(self.h, C.byref(io), N, self._stream()), "so100_query_plan_sample_tv")
-        res = {"ctrl": ctrl.permute(0, 2, 1)}
-        if qr is not None:
-            res["qpos"] = qr.t()
-        if vr is not None:
-            res["qvel"] = vr.t()
-        return res
+        return self._plan_sample("plan_sample_tv", plan, K, sigma, True, seed, draw, id_offset, u_lo, u_hi, qpos, qvel)
 
     def cost_refit(self, qpos, qvel, u, K, E, *, alpha=0.0, plan=None, sigma=None, sigma_min, sigma_max, sigma_init, bad_step=None, u_fallback=None,
                    shift=0, tail="zero", target=None, target_mode=None, link=EE_LINK, offset=None, w_point=1.0, w_q=0.0, q_nom=0.0, w_v=0.0, w_u=0.0, w_terminal=1.0):
@@ -1069,30 +1056,15 @@ class So100Sim(_Handle):
             raise So100Error(f"cost_refit: tail must be one of {sorted(BLEND_TAILS)}, got {tail!r}")
         T, NK = u.shape[0], u.shape[1]
         N = NK//K
-        rows = lambda t, k, name: None if t is None else self._shaped(t, (T, NK, k), name).permute(0, 2, 1).contiguous()     # trajectory()'s views: no copy
-        qs, vs, us = rows(qpos, 13, "qpos"), rows(qvel, 12, "qvel"), rows(u, 6, "u")
-        if qs is None:
-            raise So100Error("cost_refit: qpos is required")
-        bs = None
-        if bad_step is not None:
-            bs = torch.as_tensor(bad_step, dtype=torch.int32, device=self.device)
-            if bs.numel() != NK:
-                raise So100Error(f"bad_step: want {NK} values, got {tuple(bs.shape)}")
-            bs = bs.reshape(NK).contiguous()
+        qs, vs, us, bs, fb = self._rollouts("cost_refit", qpos, qvel, u, (T, NK), bad_step, u_fallback, N)
         per = lambda t, name: None if t is None else self._shaped(t, (T, N, 6), name).permute(0, 2, 1).contiguous()
-        fb, pl, sg = per(u_fallback, "u_fallback"), per(plan, "plan"), per(sigma, "sigma")
-
-        def six(x, name):
-            v = torch.as_tensor(x, dtype=torch.float32).reshape(-1).tolist()
-            if len(v) not in (1, 6):
-                raise So100Error(f"{name}: want 6 values or one for all, got {len(v)}")
-            return (C.c_float*6)(*(v*6 if len(v) == 1 else v))
+        pl, sg = per(plan, "plan"), per(sigma, "sigma")
         d, keep, tg = self._cost("cost_refit", T, N, target, target_mode, link, offset, w_point, w_q, q_nom, w_v, w_u, w_terminal)
         cost, best, bc = self._out(NK), self._out(N, dtype=torch.int32), self._out(N)
         el, ne, th = self._out(N*E, dtype=torch.int32), self._out(N, dtype=torch.int32), self._out(N)
         mean, so, uf = self._out(N, T, 6), self._out(N, T, 6), self._out(N, 6)
         io = CostRefitIO(C.pointer(d), _optr(tg), T, K, qs.data_ptr(), _optr(vs), us.data_ptr(), _optr(bs), _optr(fb), E, alpha, _optr(pl), _optr(sg),
-                         six(sigma_min, "sigma_min"), six(sigma_max, "sigma_max"), six(sigma_init, "sigma_init"), shift, BLEND_TAILS[tail],
+                         self._six(sigma_min, "sigma_min"), self._six(sigma_max, "sigma_max"), self._six(sigma_init, "sigma_init"), shift, BLEND_TAILS[tail],
                          cost.data_ptr(), best.data_ptr(), bc.data_ptr(), el.data_ptr(), ne.data_ptr(), th.data_ptr(), mean.data_ptr(), so.data_ptr(), uf.data_ptr())
         _check(self.L.so100_query_cost_refit(self.h, C.byref(io), N, self._stream()), "so100_query_cost_refit")
         return {"cost": cost.unflatten(0, (N, K)), "best": best, "best_cost": bc, "elite": el.unflatten(0, (N, E)), "n_elite": ne, "threshold": th,

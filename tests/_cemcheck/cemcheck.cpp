@@ -1,49 +1,25 @@
 // cemcheck.cpp -- the two cross-entropy planner queries of so100_cem.hpp on the host, in double (held to the numpy reference) and in float (the
-// arithmetic the kernels ship, without FMA contraction), behind a C interface for ctypes (built by the Makefile beside it, loaded and called by
+// arithmetic the kernels ship, without FMA contraction), behind a C interface for ctypes (built by tests/Makefile, loaded by tests/hostlibs.py and called by
 // tests/cem_support.py).  Arrays are problem-major as in mppicheck.cpp: plan and sigma [T][n][6], qpos [n][13], qvel [n][12] -> ctrl [T][n K][6],
 // qpos_rep [n K][13], qvel_rep [n K][12]; the refit's rollouts [T][n K][.], rollout (m, k) at m K + k, targets, fallback, plan and sigma per problem ->
 // cost [n K], best [n], best_cost [n], elite [n][E], n_elite [n], threshold [n], mean [T][n][6], sigma_out [T][n][6], u_first [n][6].  def and w:
 // costcheck.cpp's.  The elites are found by std::sort under cem_before -- not the kernel's sort of cem_key: cm_key_disagreements holds the two orders
 // to each other.  Test scaffolding only.
-#include <stdint.h>
-#include <string.h>
 #include <algorithm>
-#include <limits>
 #include <vector>
+#include "../planner_twin.hpp"
 #include "../../so100_mujoco_rl_amd/csrc/so100_cem.hpp"
 
 using namespace so100;
+using planner_twin::make_def; using planner_twin::rollout_cost;
 
 namespace {
-
-template <typename T> CostDef<T> make_def(int link, int target_mode, const T* w) {
-    CostDef<T> c;
-    c.link = link; c.target_mode = target_mode;
-    for (int i = 0; i < 3; i++) c.o[i] = w[i];
-    c.w_point = w[3];
-    for (int j = 0; j < 6; j++) { c.w_q[j] = w[4 + j]; c.q_nom[j] = w[10 + j]; c.w_v[j] = w[16 + j]; c.w_u[j] = w[22 + j]; }
-    c.w_terminal = w[28];
-    return c;
-}
 
 // ctrl, qpos_rep and qvel_rep may each be null; qpos_rep needs qpos, qvel_rep needs qvel
 template <typename T> void sample(long n, int K, int steps, const T* plan, const T* sigma, T lo, T hi, unsigned long long seed, unsigned draw, unsigned id_offset,
                                   const T* qpos, const T* qvel, T* ctrl, T* qpos_rep, T* qvel_rep) {
-    const long nk = n*K;
-    for (long m = 0; m < n; m++)
-        for (int k = 0; k < K; k++) {
-            const long col = m*K + k;
-            for (int t = 0; t < steps && ctrl; t++) {
-                T eps[8];
-                mppi_noise<T>((uint32_t)(id_offset + (uint32_t)m), draw, (uint32_t)k, t, (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), eps);
-                for (int j = 0; j < 6; j++) {
-                    const long e = ((long)t*n + m)*6 + j;
-                    ctrl[((long)t*nk + col)*6 + j] = cem_candidate<T>(plan[e], sigma[e], eps[j], k > 0, lo, hi);
-                }
-            }
-            if (qpos_rep) memcpy(qpos_rep + 13*col, qpos + 13*m, 13*sizeof(T));
-            if (qvel_rep) memcpy(qvel_rep + 12*col, qvel + 12*m, 12*sizeof(T));
-        }
+    planner_twin::sample<T>(n, K, steps, seed, draw, id_offset, qpos, qvel, ctrl, qpos_rep, qvel_rep,
+                            [&](long e, int, T eps, bool perturbed) { return cem_candidate<T>(plan[e], sigma[e], eps, perturbed, lo, hi); });
 }
 
 // bad_step, u_fallback, plan and sigma may be null (the last two only with alpha = 0)
@@ -58,14 +34,7 @@ template <typename T> void refit(long n, int steps, int K, int link, int target_
     for (long m = 0; m < n; m++) {
         T* J = cost + m*K;
         for (int k = 0; k < K; k++) {
-            const long col = m*K + k;
-            const T total = cost_total<T>(c, steps, [&](int t, T q[6], T v[6], T uu[6], T g[3]) {
-                const long p = (long)t*nk + col;
-                for (int j = 0; j < 6; j++) { q[j] = qpos[13*p + j]; v[j] = qvel ? qvel[12*p + j] : T(0); uu[j] = u[6*p + j]; }
-                for (int i = 0; i < 3; i++)
-                    g[i] = c.target_mode == COST_TARGET_CUBE ? qpos[13*p + 6 + i] : target[((c.target_mode == COST_TARGET_TRAJ ? (long)t*n : 0) + m)*3 + i];
-            });
-            J[k] = ((bad_step && bad_step[col] >= 0) || !cost_finite(total)) ? inf : total;
+            J[k] = rollout_cost<T>(c, steps, n, nk, m, m*K + k, target, qpos, qvel, u, bad_step);
             order[k] = k;
         }
         std::sort(order.begin(), order.end(), [&](int a, int b) { return cem_before<T>(J[a], a, J[b], b); });

@@ -1,5 +1,5 @@
 // closedcheck.cpp -- the closed-loop trajectory query of so100_closed_loop.hpp on the host, in double (held to the fp64 oracle) and in float (the
-// arithmetic the kernel ships, without FMA contraction), behind a C interface for ctypes (built by the Makefile beside it, loaded and
+// arithmetic the kernel ships, without FMA contraction), behind a C interface for ctypes (built by tests/Makefile, loaded by tests/hostlibs.py and
 // called by tests/closed_loop_support.py).  Arrays are problem-major here (qpos [n][13], u [T][n][6], references [T][n][k], k [T][n][6],
 // K [T][n][6][nx]); outputs are rollout-major ([T][n L][k], rollout (m, a) at m L + a); the SoA layout is the kernel's matter.  warm: null for a
 // cold start, or [n][31] as in trajcheck.cpp.  Test scaffolding only.

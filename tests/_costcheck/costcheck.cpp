@@ -1,31 +1,15 @@
 // costcheck.cpp -- the two cost queries of so100_cost.hpp on the host, in double (held to the numpy reference) and in float (the arithmetic the
-// kernels ship, without FMA contraction), behind a C interface for ctypes (built by the Makefile beside it, loaded and called by
+// kernels ship, without FMA contraction), behind a C interface for ctypes (built by tests/Makefile, loaded by tests/hostlibs.py and called by
 // tests/cost_support.py).  Arrays are problem-major here: qpos [T][n][13], qvel [T][n][12] (null: zero), u [T][n][6], target [n][3] or [T][n][3];
 // the select call's rollouts are [T][n L][.], rollout (m, a) at m L + a, its targets and fallback per problem.  The outputs are in the queries' own
 // layouts (lx [T+1][n][nx], lxx [T+1][n][nx][nx], lu [T][n][6], luu [T][n][6][6]; cost [n L], best [n], best_cost [n], u_best [T][n][6]).  def: link,
 // target_mode; w: offset 3, w_point, w_q 6, q_nom 6, w_v 6, w_u 6, w_terminal (29 numbers).  Test scaffolding only.
-#include <stdint.h>
-#include <limits>
-#include "../../so100_mujoco_rl_amd/csrc/so100_cost.hpp"
+#include "../planner_twin.hpp"
 
 using namespace so100;
+using planner_twin::make_def; using planner_twin::target_of; using planner_twin::rollout_cost;
 
 namespace {
-
-template <typename T> CostDef<T> make_def(int link, int target_mode, const T* w) {
-    CostDef<T> c;
-    c.link = link; c.target_mode = target_mode;
-    for (int i = 0; i < 3; i++) c.o[i] = w[i];
-    c.w_point = w[3];
-    for (int j = 0; j < 6; j++) { c.w_q[j] = w[4 + j]; c.q_nom[j] = w[10 + j]; c.w_v[j] = w[16 + j]; c.w_u[j] = w[22 + j]; }
-    c.w_terminal = w[28];
-    return c;
-}
-
-template <typename T> void target_of(const CostDef<T>& c, const T* target, const T* qpos_row, long n, long m, int t, T g[3]) {
-    for (int i = 0; i < 3; i++)
-        g[i] = c.target_mode == COST_TARGET_CUBE ? qpos_row[6 + i] : target[((c.target_mode == COST_TARGET_TRAJ ? (long)t*n : 0) + m)*3 + i];
-}
 
 template <typename T> void terms(long n, int steps, int nx, int link, int target_mode, const T* w, const T* target, const T* qpos, const T* qvel, const T* u,
                                  T* lx, T* lxx, T* lu, T* luu) {
@@ -68,12 +52,7 @@ template <typename T> void select(long n, int steps, int L, int link, int target
     for (long m = 0; m < n; m++) {
         for (int a = 0; a < L; a++) {
             const long col = m*L + a;
-            const T total = cost_total<T>(c, steps, [&](int t, T q[6], T v[6], T uu[6], T g[3]) {
-                const long p = (long)t*nl + col;
-                for (int j = 0; j < 6; j++) { q[j] = qpos[13*p + j]; v[j] = qvel ? qvel[12*p + j] : T(0); uu[j] = u[6*p + j]; }
-                target_of(c, target, qpos + 13*p, n, m, t, g);
-            });
-            cost[col] = ((bad_step && bad_step[col] >= 0) || !cost_finite(total)) ? inf : total;
+            cost[col] = rollout_cost<T>(c, steps, n, nl, m, col, target, qpos, qvel, u, bad_step);
         }
         T bc;
         const int b = cost_argmin<T>(L, inf, [&](int a) { return cost[m*L + a]; }, bc);

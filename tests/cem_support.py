@@ -1,5 +1,5 @@
-"""Shared by tests/test_cem_cpu.py and tests/test_gpu_cem.py: the host twin of the two cross-entropy planner queries (tests/_cemcheck: its Makefile, its
-signature table and its loader are here and there), the cases, the numpy reference, the bounds and the exact properties both the twin and the kernels
+"""Shared by tests/test_cem_cpu.py and tests/test_gpu_cem.py: the host twin of the two cross-entropy planner queries (tests/_cemcheck, built and
+loaded by tests/hostlibs.py), the cases, the numpy reference, the bounds and the exact properties both the twin and the kernels
 are held to.
 
 Cases need no physics: the rollouts are mppi_support.blend_case's seeded states and controls, the old plans mppi_support.sample_case's, the old sigmas
@@ -13,39 +13,17 @@ the reference's costs within twice the cost bound (check_elites): a near-tie at 
 A `sample` callable is mppi_support's with sigma [T, N, 6]; a `refit` callable is f(cost, qpos [T, N, K, 13], qvel, u [T, N, K, 6], target, E, alpha=0.0,
 plan=None, sigma=None [T, N, 6], sigma_min=, sigma_max=, sigma_init= [6], bad_step=None [N, K], u_fallback=None [T, N, 6], shift=0, tail="zero") ->
 {"cost" [N, K], "best", "best_cost" [N], "elite" [N, E], "n_elite", "threshold" [N], "mean", "sigma_out" [T, N, 6], "u_first" [N, 6]}; numpy in and out."""
-import ctypes as C
 import functools
-import os
-import subprocess
 
 import numpy as np
 
 import cost_support as CS
 import mppi_support as MS
-from hostlibs import ptr
+from hostlibs import cemcheck, ptr
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-_p, _i, _l, _u, _ull, _f, _d = C.c_void_p, C.c_int, C.c_long, C.c_uint, C.c_ulonglong, C.c_float, C.c_double
-# name: (restype, argtypes) of every symbol tests/_cemcheck/cemcheck.cpp exports (tests/test_cem_cpu.py holds the table to the extern "C" definitions)
-CEMCHECK = {"cm_sample_d": (None, [_l, _i, _i, _p, _p, _d, _d, _ull, _u, _u] + [_p]*5), "cm_sample_f": (None, [_l, _i, _i, _p, _p, _f, _f, _ull, _u, _u] + [_p]*5),
-            "cm_refit_d": (None, [_l, _i, _i, _i, _i] + [_p]*7 + [_i, _d] + [_p]*5 + [_i, _i] + [_p]*9),
-            "cm_refit_f": (None, [_l, _i, _i, _i, _i] + [_p]*7 + [_i, _f] + [_p]*5 + [_i, _i] + [_p]*9),
-            "cm_key_disagreements": (_l, [_l, _p])}
 OUTPUTS = ("cost", "best", "best_cost", "elite", "n_elite", "threshold", "mean", "sigma_out", "u_first")
 PER_PROBLEM = ("cost", "best", "best_cost", "elite", "n_elite", "threshold", "u_first")        # outputs with the problem in axis 0; mean and sigma_out: axis 1
 bits = CS.bits
-
-
-@functools.lru_cache(maxsize=None)
-def cemcheck():
-    """tests/_cemcheck/libcemcheck.so, made by its own Makefile and loaded once, every symbol with its argtypes and restype"""
-    here = os.path.join(HERE, "_cemcheck")
-    subprocess.check_call(["make", "-C", here, "-s", "libcemcheck.so"])
-    lib = C.CDLL(os.path.join(here, "libcemcheck.so"))
-    for name, (restype, argtypes) in CEMCHECK.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = restype, argtypes
-    return lib
 
 
 # ---- the twin --------------------------------------------------------------------------------------------------------------------------------------------

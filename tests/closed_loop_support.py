@@ -1,5 +1,5 @@
 """Shared by tests/test_closed_loop_cpu.py and tests/test_gpu_closed_loop.py: the host twin of the closed-loop trajectory query
-(tests/_closedcheck: its Makefile, its signature table and its loader are here and there), the input families, the references and the bounds.
+(tests/_closedcheck, built and loaded by tests/hostlibs.py), the input families, the references and the bounds.
 
 Reference.  The fp64 ORACLE chained as trajectory_support chains it (so100o_step from the fp32-rounded start), with the feedback law of
 include/so100_query.h written in numpy fp64 from its formula, on the float32 inputs as the device sees them (gains, nominal controls,
@@ -7,8 +7,6 @@ references, alpha).  It is not a second instantiation of so100_closed_loop.hpp. 
 never modified."""
 import ctypes as C
 import functools
-import os
-import subprocess
 
 import numpy as np
 
@@ -16,26 +14,7 @@ import derivatives_support as DS
 import lqr_support as LS
 import scenes
 import trajectory_support as TS
-from hostlibs import ptr
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-_p, _i, _u, _l, _f, _d = C.c_void_p, C.c_int, C.c_uint, C.c_long, C.c_float, C.c_double
-# name: (restype, argtypes) of every symbol tests/_closedcheck/closedcheck.cpp exports, as tests/hostlibs.py declares the other twins'
-# (tests/test_closed_loop_cpu.py holds the table to the extern "C" definitions)
-CLOSEDCHECK = {"cc_closed_loop_d": (None, [_l] + [_p]*4 + [_i, _i, _i, _u, _i, _i] + [_p]*4 + [_i, _p, _p, _i, _p, _i, _d, _d] + [_p]*11),
-               "cc_closed_loop_f": (None, [_l] + [_p]*4 + [_i, _i, _i, _u, _i, _i] + [_p]*4 + [_i, _p, _p, _i, _p, _i, _f, _f] + [_p]*11)}
-
-
-@functools.lru_cache(maxsize=None)
-def closedcheck():
-    """tests/_closedcheck/libclosedcheck.so, made by its own Makefile and loaded once, every symbol with its argtypes and restype"""
-    here = os.path.join(HERE, "_closedcheck")
-    subprocess.check_call(["make", "-C", here, "-s", "libclosedcheck.so"])
-    lib = C.CDLL(os.path.join(here, "libclosedcheck.so"))
-    for name, (restype, argtypes) in CLOSEDCHECK.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = restype, argtypes
-    return lib
+from hostlibs import closedcheck, ptr
 
 
 NU = 6

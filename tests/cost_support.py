@@ -1,5 +1,5 @@
-"""Shared by tests/test_cost_cpu.py and tests/test_gpu_cost.py: the host twin of the two cost queries (tests/_costcheck: its Makefile, its signature
-table and its loader are here and there), the seeded cases, the numpy reference, the bounds and the exact properties both the twin and the kernels
+"""Shared by tests/test_cost_cpu.py and tests/test_gpu_cost.py: the host twin of the two cost queries (tests/_costcheck, built and loaded by
+tests/hostlibs.py), the seeded cases, the numpy reference, the bounds and the exact properties both the twin and the kernels
 are held to.
 
 Cases need no physics: states are seeded arrays -- q uniform over the joint ranges, v in +-2 rad/s, the cube in a +-0.3 m box, u in +-1, targets in
@@ -11,36 +11,16 @@ mj_jac's formula); it is not a second instantiation of so100_cost.hpp.  Computed
 A `terms` callable is f(cost, qpos [T, M, 13], qvel [T, M, 12] or None, u [T, M, 6], target, nx) -> {"lx", "lxx", "lu", "luu"}; a `select` callable is
 f(cost, qpos [T, M, L, 13], qvel, u [T, M, L, 6], target, bad_step=None, u_fallback=None) -> {"cost", "best", "best_cost", "u_best"}; numpy in and out.
 `cost` is a dict of So100Sim.cost_terms' cost arguments (cost_def())."""
-import ctypes as C
 import functools
-import os
-import subprocess
 
 import numpy as np
 
 import query_support as QS
-from hostlibs import ptr
+from hostlibs import costcheck, ptr
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-_p, _i, _l = C.c_void_p, C.c_int, C.c_long
-# name: (restype, argtypes) of every symbol tests/_costcheck/costcheck.cpp exports (tests/test_cost_cpu.py holds the table to the extern "C" definitions)
-COSTCHECK = {"ck_terms_d": (None, [_l, _i, _i, _i, _i] + [_p]*9), "ck_terms_f": (None, [_l, _i, _i, _i, _i] + [_p]*9),
-             "ck_select_d": (None, [_l, _i, _i, _i, _i] + [_p]*11), "ck_select_f": (None, [_l, _i, _i, _i, _i] + [_p]*11)}
 TARGETS = {"fixed": 0, "traj": 1, "cube": 2}
 IDX = {24: np.arange(24), 12: np.r_[0:6, 12:18]}           # nx -> the tangent indices of the form
 MAX_L = 16
-
-
-@functools.lru_cache(maxsize=None)
-def costcheck():
-    """tests/_costcheck/libcostcheck.so, made by its own Makefile and loaded once, every symbol with its argtypes and restype"""
-    here = os.path.join(HERE, "_costcheck")
-    subprocess.check_call(["make", "-C", here, "-s", "libcostcheck.so"])
-    lib = C.CDLL(os.path.join(here, "libcostcheck.so"))
-    for name, (restype, argtypes) in COSTCHECK.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = restype, argtypes
-    return lib
 
 
 # ---- the cost definition -----------------------------------------------------------------------------------------------------------------------------

@@ -2,7 +2,9 @@
 layer, random draws), tests/_rendercheck/librendercheck.so (render), tests/_learncheck/liblearncheck.so (the learner: lc_ its arithmetic,
 rn_ reward normalisation, on_ observation normalisation, sc_ the shuffle; four sources, one library), tests/_querycheck/libquerycheck.so
 (the four original model queries) and one library each for the later queries: tests/_forwardcheck/libforwardcheck.so (forward dynamics),
-tests/_trajcheck/libtrajcheck.so (trajectory), tests/_derivcheck/libderivcheck.so (derivatives) and tests/_lqrcheck/liblqrcheck.so (LQR).
+tests/_trajcheck/libtrajcheck.so (trajectory), tests/_derivcheck/libderivcheck.so (derivatives), tests/_lqrcheck/liblqrcheck.so (LQR),
+tests/_closedcheck/libclosedcheck.so (closed loop), tests/_costcheck/libcostcheck.so (cost terms and selection), tests/_mppicheck/libmppicheck.so
+(sampling planner) and tests/_cemcheck/libcemcheck.so (cross-entropy planner; the last three share tests/planner_twin.hpp).
 tests/Makefile is the one recipe for all of them.  Each is made once per process and cached; argtypes and restype are declared here for EVERY exported symbol (tests/test_hostlibs.py holds
 the tables to the extern "C" definitions), so that no call depends on which test ran first: a `long` result without its restype is
 silently cut to 32 bits, a Python float without argtypes raises."""
@@ -82,6 +84,16 @@ DERIVCHECK = {"dc_derivatives_d": (None, [_l] + [_p]*4 + [_i, _i, _u, _i, _i, _d
               "dc_derivatives_f": (None, [_l] + [_p]*4 + [_i, _i, _u, _i, _i, _f] + [_p]*5)}
 LQRCHECK = {"lq_lqr_d": (None, [_l, _i, _i] + [_p]*9 + [_d]*4 + [_p]*8),
             "lq_lqr_f": (None, [_l, _i, _i] + [_p]*9 + [_f]*4 + [_p]*8)}
+CLOSEDCHECK = {"cc_closed_loop_d": (None, [_l] + [_p]*4 + [_i, _i, _i, _u, _i, _i] + [_p]*4 + [_i, _p, _p, _i, _p, _i, _d, _d] + [_p]*11),
+               "cc_closed_loop_f": (None, [_l] + [_p]*4 + [_i, _i, _i, _u, _i, _i] + [_p]*4 + [_i, _p, _p, _i, _p, _i, _f, _f] + [_p]*11)}
+COSTCHECK = {"ck_terms_d": (None, [_l, _i, _i, _i, _i] + [_p]*9), "ck_terms_f": (None, [_l, _i, _i, _i, _i] + [_p]*9),
+             "ck_select_d": (None, [_l, _i, _i, _i, _i] + [_p]*11), "ck_select_f": (None, [_l, _i, _i, _i, _i] + [_p]*11)}
+MPPICHECK = {"mp_sample_d": (None, [_l, _i, _i, _p, _p, _d, _d, _ull, _u, _u] + [_p]*5), "mp_sample_f": (None, [_l, _i, _i, _p, _p, _f, _f, _ull, _u, _u] + [_p]*5),
+             "mp_blend_d": (None, [_l, _i, _i, _i, _i] + [_p]*7 + [_d, _i, _i] + [_p]*7), "mp_blend_f": (None, [_l, _i, _i, _i, _i] + [_p]*7 + [_f, _i, _i] + [_p]*7)}
+CEMCHECK = {"cm_sample_d": (None, [_l, _i, _i, _p, _p, _d, _d, _ull, _u, _u] + [_p]*5), "cm_sample_f": (None, [_l, _i, _i, _p, _p, _f, _f, _ull, _u, _u] + [_p]*5),
+            "cm_refit_d": (None, [_l, _i, _i, _i, _i] + [_p]*7 + [_i, _d] + [_p]*5 + [_i, _i] + [_p]*9),
+            "cm_refit_f": (None, [_l, _i, _i, _i, _i] + [_p]*7 + [_i, _f] + [_p]*5 + [_i, _i] + [_p]*9),
+            "cm_key_disagreements": (_l, [_l, _p])}
 
 _libs = {}
 
@@ -132,6 +144,22 @@ def derivcheck():
 
 def lqrcheck():
     return _load("_lqrcheck/liblqrcheck.so", LQRCHECK)
+
+
+def closedcheck():
+    return _load("_closedcheck/libclosedcheck.so", CLOSEDCHECK)
+
+
+def costcheck():
+    return _load("_costcheck/libcostcheck.so", COSTCHECK)
+
+
+def mppicheck():
+    return _load("_mppicheck/libmppicheck.so", MPPICHECK)
+
+
+def cemcheck():
+    return _load("_cemcheck/libcemcheck.so", CEMCHECK)
 
 
 def ptr(a):

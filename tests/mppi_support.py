@@ -1,5 +1,5 @@
-"""Shared by tests/test_mppi_cpu.py and tests/test_gpu_mppi.py: the host twin of the two sampling-planner queries (tests/_mppicheck: its Makefile, its
-signature table and its loader are here and there), the seeded cases, the numpy reference, the bounds and the exact properties both the twin and
+"""Shared by tests/test_mppi_cpu.py and tests/test_gpu_mppi.py: the host twin of the two sampling-planner queries (tests/_mppicheck, built and
+loaded by tests/hostlibs.py), the seeded cases, the numpy reference, the bounds and the exact properties both the twin and
 the kernels are held to.
 
 Cases need no physics: states and controls are cost_support.seeded_states' arrays, plans uniform in +-1.2 (so that some entries clamp), rounded to
@@ -13,38 +13,18 @@ A `sample` callable is f(plan [T, N, 6], K, sigma [6], seed=, draw=, id_offset=,
 {"ctrl" [T, N, K, 6], "qpos" [N, K, 13], "qvel" [N, K, 12]}; a `blend` callable is f(cost, qpos [T, N, K, 13], qvel, u [T, N, K, 6], target, temperature,
 bad_step=None [N, K], u_fallback=None [T, N, 6], shift=0, tail="zero") -> {"cost", "weight" [N, K], "best", "best_cost", "ess" [N], "u_plan" [T, N, 6],
 "u_first" [N, 6]}; numpy in and out."""
-import ctypes as C
 import functools
-import os
-import subprocess
 
 import numpy as np
 
 import cost_support as CS
-from hostlibs import ptr
+from hostlibs import mppicheck, ptr
 from oracle import so100_oracle as O
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-_p, _i, _l, _u, _ull, _f, _d = C.c_void_p, C.c_int, C.c_long, C.c_uint, C.c_ulonglong, C.c_float, C.c_double
-# name: (restype, argtypes) of every symbol tests/_mppicheck/mppicheck.cpp exports (tests/test_mppi_cpu.py holds the table to the extern "C" definitions)
-MPPICHECK = {"mp_sample_d": (None, [_l, _i, _i, _p, _p, _d, _d, _ull, _u, _u] + [_p]*5), "mp_sample_f": (None, [_l, _i, _i, _p, _p, _f, _f, _ull, _u, _u] + [_p]*5),
-             "mp_blend_d": (None, [_l, _i, _i, _i, _i] + [_p]*7 + [_d, _i, _i] + [_p]*7), "mp_blend_f": (None, [_l, _i, _i, _i, _i] + [_p]*7 + [_f, _i, _i] + [_p]*7)}
 TAILS = {"zero": 0, "hold": 1}
 MAX_K = 4096
 STREAM_C3 = 0x4D500000
 bits = CS.bits
-
-
-@functools.lru_cache(maxsize=None)
-def mppicheck():
-    """tests/_mppicheck/libmppicheck.so, made by its own Makefile and loaded once, every symbol with its argtypes and restype"""
-    here = os.path.join(HERE, "_mppicheck")
-    subprocess.check_call(["make", "-C", here, "-s", "libmppicheck.so"])
-    lib = C.CDLL(os.path.join(here, "libmppicheck.so"))
-    for name, (restype, argtypes) in MPPICHECK.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = restype, argtypes
-    return lib
 
 
 # ---- the twin --------------------------------------------------------------------------------------------------------------------------------------------

@@ -1,17 +1,15 @@
 """The two cross-entropy planner queries on the CPU: the surface of include/so100_query.h (so100_query_plan_sample_tv, so100_query_cost_refit), the host twin
-of so100_cem.hpp (tests/_cemcheck) against the numpy reference of tests/cem_support.py, the exact properties in both precisions, the integer keys' order, and
-the twin's table against its source.  The same cases run on the kernels in tests/test_gpu_cem.py."""
+of so100_cem.hpp (tests/_cemcheck) against the numpy reference of tests/cem_support.py, the exact properties in both precisions, and the integer keys' order.
+The twin's table and its stand-alone program are held in tests/test_hostlibs.py.  The same cases run on the kernels in tests/test_gpu_cem.py."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import cem_support as S
 import mppi_support as MS
-import test_hostlibs as TH
 import test_mppi_cpu as TM
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -49,28 +47,7 @@ def test_null_arguments_are_refused_without_a_device():
         assert L.so100_last_error() == (fn + ": null argument").encode()
 
 
-# ---- the twin's table, its stand-alone program, the keys ---------------------------------------------------------------------------------------------------
-def test_the_twins_table_matches_its_source():
-    src = TH.expand_macros(re.sub(r"//[^\n]*", "", open(os.path.join(HERE, "_cemcheck", "cemcheck.cpp")).read()))
-    found = {}
-    for ret, name, params in re.findall(r'^\s*(?:extern "C" )?(void\*?|int|long)\s+(cm_\w+)\s*\(([^)]*)\)\s*\{', src, flags=re.M):
-        args = [C.c_void_p if "*" in p else TH.SCALARS[" ".join(p.split()[:-1])] for p in (x.strip() for x in params.split(",")) if p not in ("", "void")]
-        found[name] = (TH.RETURNS[ret], args)
-    assert found == S.CEMCHECK and sorted(found) == ["cm_key_disagreements", "cm_refit_d", "cm_refit_f", "cm_sample_d", "cm_sample_f"]
-    lib = S.cemcheck()
-    for name, (restype, argtypes) in found.items():
-        fn = getattr(lib, name)
-        assert fn.restype == restype and list(fn.argtypes) == argtypes, name
-
-
-def test_the_stand_alone_program_builds_and_passes(tmp_path):
-    """the program a host sanitizer run uses (make -C tests/_cemcheck selftest SAN=...), here without a sanitizer"""
-    out = subprocess.run(["make", "-C", os.path.join(HERE, "_cemcheck"), "-s", "selftest", f"BUILD={tmp_path}"], capture_output=True, text=True)
-    assert out.returncode == 0, out.stdout + out.stderr
-    lines = [l for l in out.stdout.splitlines() if l.startswith("cemcheck selftest")]
-    assert len(lines) == 3 and all(l.endswith(": ok") for l in lines) and "(double)" in lines[0] and "(float)" in lines[1] and "(keys)" in lines[2]
-
-
+# ---- the keys -------------------------------------------------------------------------------------------------------------------------------------------
 def test_the_integer_keys_order_is_the_definitions():
     """the kernel sorts cem_key(J, k); over all pairs of 600 costs -- zeros of both signs, denormals, infinities, repeats, negative values -- that order is
     cem_before's, every key lies below the padding and returns its index"""

@@ -1,17 +1,15 @@
 """The closed-loop trajectory query on the CPU: the host twin of so100_closed_loop.hpp (tests/_closedcheck) against the fp64 oracle under the
-feedback law in numpy (tests/closed_loop_support.py), the exact properties of the law and the rollout, the failure cases, and the twin's table in
-tests/closed_loop_support.py against the source's extern "C" definitions.  The same cases run on the kernel in tests/test_gpu_closed_loop.py."""
+feedback law in numpy (tests/closed_loop_support.py), the exact properties of the law and the rollout, and the failure cases.  The twin's table and its
+stand-alone program are held in tests/test_hostlibs.py.  The same cases run on the kernel in tests/test_gpu_closed_loop.py."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import closed_loop_support as S
 import scenes
-import test_hostlibs as TH
 import trajectory_support as TS
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -55,29 +53,6 @@ def test_null_arguments_are_refused_without_a_device():
     L = lib.load()
     assert L.so100_query_closed_loop(None, C.byref(lib.ClosedLoopIO()), 1, None) == -1
     assert L.so100_last_error() == b"so100_query_closed_loop: null argument"
-
-
-# ---- the twin's table and its stand-alone program ----------------------------------------------------------------------------------------------------------------------
-def test_the_twins_table_matches_its_source():
-    """test_hostlibs.defined_symbols reads a fixed list of prefixes; cc_ is not among them, so its pattern is applied here to the expanded source"""
-    src = TH.expand_macros(re.sub(r"//[^\n]*", "", open(os.path.join(HERE, "_closedcheck", "closedcheck.cpp")).read()))
-    found = {}
-    for ret, name, params in re.findall(r'^\s*(?:extern "C" )?(void\*?|int|long)\s+(cc_\w+)\s*\(([^)]*)\)\s*\{', src, flags=re.M):
-        args = [C.c_void_p if "*" in p else TH.SCALARS[" ".join(p.split()[:-1])] for p in (x.strip() for x in params.split(",")) if p not in ("", "void")]
-        found[name] = (TH.RETURNS[ret], args)
-    assert found == S.CLOSEDCHECK and sorted(found) == ["cc_closed_loop_d", "cc_closed_loop_f"]
-    lib = S.closedcheck()
-    for name, (restype, argtypes) in found.items():
-        fn = getattr(lib, name)
-        assert fn.restype == restype and list(fn.argtypes) == argtypes, name
-
-
-def test_the_stand_alone_program_builds_and_passes(tmp_path):
-    """the program a host sanitizer run uses (make -C tests/_closedcheck selftest SAN=...), here without a sanitizer"""
-    out = subprocess.run(["make", "-C", os.path.join(HERE, "_closedcheck"), "-s", "selftest", f"BUILD={tmp_path}"], capture_output=True, text=True)
-    assert out.returncode == 0, out.stdout + out.stderr
-    lines = [l for l in out.stdout.splitlines() if l.startswith("closedcheck selftest")]
-    assert len(lines) == 2 and all(l.endswith(": ok") for l in lines) and "(double)" in lines[0] and "(float)" in lines[1]
 
 
 # ---- deviation bounds ------------------------------------------------------------------------------------------------------------------------------------

@@ -1,16 +1,14 @@
 """The two cost queries on the CPU: the surface of include/so100_query.h (so100_cost_def, so100_query_cost_terms, so100_query_cost_select), the host twin
 of so100_cost.hpp (tests/_costcheck) against the numpy reference of tests/cost_support.py, the reference's own lx against central differences, the
-exact properties, and the twin's table against its source.  The same cases run on the kernels in tests/test_gpu_cost.py."""
+exact properties.  The twin's table and its stand-alone program are held in tests/test_hostlibs.py.  The same cases run on the kernels in tests/test_gpu_cost.py."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import cost_support as S
-import test_hostlibs as TH
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -64,28 +62,6 @@ def test_null_arguments_are_refused_without_a_device():
     for fn, io in (("so100_query_cost_terms", lib.CostTermsIO), ("so100_query_cost_select", lib.CostSelectIO)):
         assert getattr(L, fn)(None, C.byref(io()), 1, None) == -1
         assert L.so100_last_error() == (fn + ": null argument").encode()
-
-
-# ---- the twin's table and its stand-alone program --------------------------------------------------------------------------------------------------------
-def test_the_twins_table_matches_its_source():
-    src = TH.expand_macros(re.sub(r"//[^\n]*", "", open(os.path.join(HERE, "_costcheck", "costcheck.cpp")).read()))
-    found = {}
-    for ret, name, params in re.findall(r'^\s*(?:extern "C" )?(void\*?|int|long)\s+(ck_\w+)\s*\(([^)]*)\)\s*\{', src, flags=re.M):
-        args = [C.c_void_p if "*" in p else TH.SCALARS[" ".join(p.split()[:-1])] for p in (x.strip() for x in params.split(",")) if p not in ("", "void")]
-        found[name] = (TH.RETURNS[ret], args)
-    assert found == S.COSTCHECK and sorted(found) == ["ck_select_d", "ck_select_f", "ck_terms_d", "ck_terms_f"]
-    lib = S.costcheck()
-    for name, (restype, argtypes) in found.items():
-        fn = getattr(lib, name)
-        assert fn.restype == restype and list(fn.argtypes) == argtypes, name
-
-
-def test_the_stand_alone_program_builds_and_passes(tmp_path):
-    """the program a host sanitizer run uses (make -C tests/_costcheck selftest SAN=...), here without a sanitizer"""
-    out = subprocess.run(["make", "-C", os.path.join(HERE, "_costcheck"), "-s", "selftest", f"BUILD={tmp_path}"], capture_output=True, text=True)
-    assert out.returncode == 0, out.stdout + out.stderr
-    lines = [l for l in out.stdout.splitlines() if l.startswith("costcheck selftest")]
-    assert len(lines) == 2 and all(l.endswith(": ok") for l in lines) and "(double)" in lines[0] and "(float)" in lines[1]
 
 
 # ---- the reference against itself -------------------------------------------------------------------------------------------------------------------------
