@@ -13,9 +13,16 @@ of its cheapest candidate as the new plan.  alpha = 0 is the old plan, so the ch
 arithmetic behind it (cube target, nx = 12: So100Sim.lqr is then the backward pass, whatever --backward says), and with --forward closed the line
 search's sum, mask, argmin and gather from ONE So100Sim.cost_select call with the old plan as the fallback: an iteration is then six calls on one
 stream with no torch operation between them.
+--reg adaptive (implies --forward closed --cost query) gives every env a regulariser of its own, a [N] tensor that lives across improvements and
+control steps: So100Sim.lqr_reg starts each env's backward pass from it and, where the factor of Quu + reg I fails, runs that env's pass again
+under a raised one inside the launch; after the line search ONE So100Sim.reg_schedule call lowers the reg of the envs whose plan improved and
+raises the others'.  No result is looked at on the host in between: a bad linearisation or rollout becomes NaN gains, then a failed candidate,
+then the old plan (the fallback) and a raised reg.  --control-cost and --damping set the weight of |a|^2 and the fixed reg (the adaptive one's
+start); with both 0 the jaw's zero column of B gives Quu an exactly zero pivot, the fixed reg fails every env at the last step and the plan never
+moves, and the adaptive one lifts itself to its floor.
 
     python examples/ilqr_reach.py [--envs 8] [--horizon 8] [--steps 100] [--iterations 2] [--backward {torch,query}] [--forward {linear,closed}]
-                                  [--cost {torch,query}]
+                                  [--cost {torch,query}] [--reg {fixed,adaptive}] [--control-cost 1e-5] [--damping 1e-5]
 """
 import argparse
 import os
@@ -28,6 +35,8 @@ from so100_mujoco_rl_amd.lib import ENV01, F_CUBE_PINNED, So100Sim   # noqa: E40
 
 ARM = list(range(0, 6)) + list(range(12, 18))                  # the arm's block of the tangent state: dq 0..5, v 12..17
 ALPHAS = (0.0,) + tuple(2.0**-i for i in range(7))             # the line search's candidates: the old plan, then 1, 1/2, .. 1/64
+REG = dict(reg_min=1e-6, reg_max=1e4, reg_up=10.0)             # --reg adaptive: the floor, the ceiling and the factor up
+REG_DOWN, REG_TRIES = 0.1, 8                                   # the factor down after an improvement; backward passes per env and improvement
 
 
 class Ilqr:
@@ -35,10 +44,16 @@ class Ilqr:
     control_cost: the weight of |a|^2 beside |ee - cube|^2 (metres squared); damping: added to Q_uu (Levenberg-Marquardt); backward: "torch" (the
     loops below) or "query" (So100Sim.lqr: the same recursion in one launch); forward: "linear" (the linear model's u + du) or "closed" (the
     feedback law on the real dynamics at ALPHAS, the cheapest candidate per env; costs: per improve() the (chosen, alpha = 0) true costs [N]);
-    cost: "torch" (the arithmetic below) or "query" (So100Sim.cost_terms and, with forward "closed", So100Sim.cost_select)."""
-    def __init__(self, horizon=8, iterations=2, control_cost=1e-5, damping=1e-5, backward="torch", forward="linear", cost="torch"):
+    cost: "torch" (the arithmetic below) or "query" (So100Sim.cost_terms and, with forward "closed", So100Sim.cost_select); reg: "fixed" (damping
+    for every env) or "adaptive" (regs [N], one per env, starting from damping: So100Sim.lqr_reg and So100Sim.reg_schedule; forward and cost are then
+    "closed" and "query")."""
+    def __init__(self, horizon=8, iterations=2, control_cost=1e-5, damping=1e-5, backward="torch", forward="linear", cost="torch", reg="fixed"):
         self.H, self.iterations, self.control_cost, self.damping, self.backward, self.forward = horizon, iterations, control_cost, damping, backward, forward
         self.cost = cost
+        self.adaptive = reg == "adaptive"
+        if self.adaptive:
+            self.forward, self.cost = "closed", "query"
+        self.regs = None
         self.plan = None
         self.costs = []
 
@@ -48,6 +63,9 @@ class Ilqr:
         roll = sim.trajectory(U.permute(1, 0, 2).contiguous(), q0, v0, mode="actions")           # row t: the state after action t
         Xq = torch.cat([q0[None], roll["qpos"][:-1]]); Xv = torch.cat([v0[None], roll["qvel"][:-1]])   # [H, N, .]: the state action t starts from
         d = sim.derivatives(U.permute(1, 0, 2).reshape(H*N, 6), Xq.reshape(H*N, 13), Xv.reshape(H*N, 12), mode="actions")
+        if self.adaptive:
+            self.improve_with_a_reg_per_env(sim, q0, v0, roll, d)
+            return
         if bool(d["bad"].any()) or bool((roll["bad_step"] >= 0).any()):
             return
         if self.cost == "query":
@@ -151,9 +169,28 @@ class Ilqr:
         self.costs.append((pick["best_cost"].cpu(), pick["cost"][:, 0].cpu()))
         self.plan = pick["u_best"].permute(1, 0, 2).contiguous()
 
+    def improve_with_a_reg_per_env(self, sim, q0, v0, roll, d):
+        """improve() from the rollout and its linearisation on, with no look at a result on the host: cost_terms -> lqr_reg -> closed_loop ->
+        cost_select -> reg_schedule (with the two calls before them, seven on one stream).  A linearisation or rollout that is not finite gives NaN gains (bad = T), those a failed
+        candidate at every step size, cost_select then keeps the old plan (best = -1), and reg_schedule raises that env's reg."""
+        N, H = sim.n, self.H
+        Ut = self.plan.permute(1, 0, 2).contiguous()
+        cost = dict(target_mode="cube", w_point=1.0, w_u=self.control_cost)
+        Bq = d["B"].reshape(H, N, 24, 6).clone()
+        Bq[..., 5] = 0.0                                             # the jaw does not move the end-effector point
+        t = sim.cost_terms(roll["qpos"], roll["qvel"], Ut, nx=12, **cost)
+        s = sim.lqr_reg(d["A"].reshape(H, N, 24, 24), Bq, t["lx"], t["lxx"], lu=t["lu"], luu=t["luu"], nx=12, reg=self.regs, tries=REG_TRIES, **REG)
+        c = sim.closed_loop(Ut, roll["qpos"], roll["qvel"], s["K"], s["k"], alphas=ALPHAS, nx=12, qpos=q0, qvel=v0, mode="actions", clamp=(-1.0, 1.0))
+        pick = sim.cost_select(c["qpos"], c["qvel"], c["u"], bad_step=c["bad_step"], u_fallback=Ut, **cost)
+        sim.reg_schedule(s["reg_used"], pick["best"], keep=0, reg_down=REG_DOWN, out=self.regs, **REG)      # ALPHAS[0] = 0: candidate 0 is the old plan
+        self.costs.append((pick["best_cost"].cpu(), pick["cost"][:, 0].cpu()))
+        self.plan = pick["u_best"].permute(1, 0, 2).contiguous()
+
     def __call__(self, sim, obs):
         if self.plan is None:
             self.plan = torch.zeros(sim.n, self.H, 6, device=sim.device)
+        if self.adaptive and self.regs is None:
+            self.regs = torch.full((sim.n,), float(self.damping), device=sim.device)
         qpos, qvel = sim.get_state()                                 # [13, N], [12, N]
         q0, v0 = qpos.t().contiguous(), qvel.t().contiguous()
         for _ in range(self.iterations):
@@ -192,8 +229,11 @@ def main():
     ap.add_argument("--backward", choices=("torch", "query"), default="torch")
     ap.add_argument("--forward", choices=("linear", "closed"), default="linear")
     ap.add_argument("--cost", choices=("torch", "query"), default="torch")
+    ap.add_argument("--reg", choices=("fixed", "adaptive"), default="fixed")
+    ap.add_argument("--control-cost", type=float, default=1e-5); ap.add_argument("--damping", type=float, default=1e-5)
     args = ap.parse_args()
-    for name, policy in (("iLQR", Ilqr(args.horizon, args.iterations, backward=args.backward, forward=args.forward, cost=args.cost)), ("zero action", zero_action)):
+    ilqr = Ilqr(args.horizon, args.iterations, args.control_cost, args.damping, backward=args.backward, forward=args.forward, cost=args.cost, reg=args.reg)
+    for name, policy in (("iLQR", ilqr), ("zero action", zero_action)):
         sim = So100Sim(ENV01, args.envs, flags=F_CUBE_PINNED, max_episode_steps=0, seed=0)
         d0, d1, r = run(sim, args.steps, policy)
         print(f"{name:12s} mean |cube - ee|: {d0:.4f} m at reset -> {d1:.4f} m after {args.steps} steps; reward/step {r:+.4f}")

@@ -315,6 +315,70 @@ typedef struct {
 
 int so100_query_lqr(so100_sim* sim, const so100_lqr_io* io, int32_t M, void* hip_stream);
 
+/* LQR with a regulariser PER PROBLEM and a retry inside the launch: so100_query_lqr whose reg is the problem's own and whose backward pass, where
+ * the Cholesky of Quu + reg I fails, is run again under a raised reg without a look from the host -- what an iLQR does between a failed factor
+ * and the next try (Tassa's iLQG, MJPC).  One wave per problem as before; a problem that retries costs only itself.
+ *
+ * Per problem m:
+ *   Start.  r = reg_dev ? reg_dev[m] : base.reg.  An r that is not finite or is negative is a non-finite input: bad = T, tries = 0,
+ *           reg_used = NaN, and no pass runs.
+ *   Raise.  raise(r) = min(reg_max, max(reg_min, r * reg_up)), the product rounded once in fp32; raise(0) = reg_min.
+ *   Pass a = 1, 2, ...: the backward pass of so100_query_lqr with reg = r, from the terminal cost, dV1 and dV2 restarted.
+ *           It goes through: the problem is done, bad = -1, reg_used = r, tries = a.
+ *           The Cholesky fails at step t, a < tries and r < reg_max: r = raise(r), the next pass.
+ *           Otherwise the problem fails: bad = the t of this last pass, reg_used = r, tries = a, every float output NaN as in so100_query_lqr.
+ *           A non-finite input (bad = T) is found by the first pass and never retried: tries = 1, reg_used = r.
+ *   The linear forward pass runs after the pass that went through, the NaN fill after a final failure, both unchanged.  No row of k or K that
+ *   a failed pass wrote survives: each is written again or NaN.
+ * Identities, bit for bit.  reg_dev = NULL and tries = 1: every output is so100_query_lqr's.  A problem that succeeds: every float output is what
+ * so100_query_lqr gives for that problem alone with reg = reg_used[m].
+ *
+ * reg_used [M]: the reg of the LAST pass run.  tries [M]: the backward passes run, 1..tries; 0 for a start that is no reg.  Both nullable; they
+ * count as outputs.  so100_query_reg_schedule (below) turns reg_used and the line search's verdict into the next call's reg_dev.
+ *
+ * Argument errors, in this order: a null handle or io; those of so100_query_lqr on base, from M < 1 to du or dx without k and K (base.reg is
+ * checked even where reg_dev is given); reg_min not finite or <= 0; reg_max not finite or < reg_min; reg_up not finite or <= 1; tries outside
+ * 1..SO100_LQR_REG_MAX_TRIES; no output. */
+#define SO100_LQR_REG_MAX_TRIES 16
+typedef struct {
+    so100_lqr_io base;                 /* everything of so100_query_lqr; base.reg is used where reg_dev is NULL      */
+    const float* reg_dev;              /* [M] starting reg per problem, or NULL: base.reg for all                   */
+    float        reg_min;              /* finite, > 0                                                               */
+    float        reg_max;              /* finite, >= reg_min                                                        */
+    float        reg_up;               /* finite, > 1                                                               */
+    int32_t      tries;                /* 1..16: backward passes allowed per problem                                */
+    float*       reg_used_dev;         /* [M] the reg of the LAST pass run, or NULL                                 */
+    int32_t*     tries_dev;            /* [M] backward passes run (1..tries; 0 for a start that is no reg), or NULL */
+} so100_lqr_reg_io;
+
+int so100_query_lqr_reg(so100_sim* sim, const so100_lqr_reg_io* io, int32_t M, void* hip_stream);
+
+/* The regulariser's schedule: the line search's verdict on each problem becomes its next reg, on the device, one GPU lane per problem (the
+ * handle's state is never read or written).  Per problem m:
+ *     r = reg_used[m]; a value that is not finite or is negative counts as 0
+ *     improved = best[m] >= 0 && best[m] != keep       (so100_query_cost_select's best: -1 where no candidate got through; keep: the index of the
+ *                                                       candidate that IS the old plan, alpha = 0, or -1 where there is none)
+ *     improved:      r' = r * reg_down, and r' = 0 where r' < reg_min            (Tassa's rule: a reg under reg_min is 0)
+ *     not improved:  r' = raise(r) of so100_query_lqr_reg
+ *     reg[m] = r';  improved[m] = 1 or 0
+ * reg_dev may be reg_used_dev.
+ *
+ * Argument errors, in this order: a null handle or io; M < 1; reg_used_dev, best_dev or reg_dev NULL; keep < -1; reg_min, reg_max, reg_up as in
+ * so100_query_lqr_reg; reg_down not in (0, 1]. */
+typedef struct {
+    const float*   reg_used_dev;       /* [M] so100_query_lqr_reg's                                                 */
+    const int32_t* best_dev;           /* [M] so100_query_cost_select's best                                        */
+    int32_t        keep;               /* the candidate index that IS the old plan (alpha = 0), or -1: none         */
+    float          reg_min;            /* as in so100_lqr_reg_io                                                    */
+    float          reg_max;
+    float          reg_up;
+    float          reg_down;           /* finite, in (0, 1]                                                         */
+    float*         reg_dev;            /* [M] the next reg; may alias reg_used_dev                                  */
+    uint8_t*       improved_dev;       /* [M] or NULL                                                               */
+} so100_reg_schedule_io;
+
+int so100_query_reg_schedule(so100_sim* sim, const so100_reg_schedule_io* io, int32_t M, void* hip_stream);
+
 /* Closed-loop trajectories: the trajectory query under a time-varying feedback law around a nominal plan -- the NONLINEAR forward pass of iLQR
  * at L step sizes at once (the line search's candidates), and LQR tracking of one plan from disturbed starts.  M problems with L candidates each
  * are M * L rollouts of T control steps, nsub substeps each, one GPU lane per rollout with the state in registers throughout.  The handle's

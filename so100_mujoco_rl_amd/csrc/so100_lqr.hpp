@@ -17,6 +17,8 @@
 // and, if asked for, dx_0 = dx0, du_t = alpha k_t + K_t dx_t (with u: clamp(u_t + that, u_lo, u_hi) - u_t), dx_{t+1} = A_t dx_t + B_t du_t.
 // lxx_T is symmetrised like every later Vxx.  A and B are always in the derivatives query's layout ([T][M][24][24], [T][M][24][6]); every
 // other array is in the n of the call, problem-major.
+// With a regulariser per problem (so100_query_lqr_reg, so100_query_reg_schedule): lqr_reg_raise, lqr_reg_again and lqr_reg_next
+// are what the kernels, the twin (tests/_lqrregcheck) and the schedule share; lqr_reg_problem is the twin's retry loop round lqr_problem.
 #pragma once
 #include <math.h>
 #include <stddef.h>
@@ -95,12 +97,31 @@ template <typename T> SO100_HD void lqr_solve6(const T L[6][6], const T inv[6], 
     for (int i = 0; i < 6; i++) x[i] = -x[i];
 }
 
-// The whole query for problem m of M, element by element: the twin's form (the kernel deals the same arithmetic over a wave).  The inputs of
-// step t are tested for finiteness as they are read: bad = T at the first step (from the end) that has one, bad = t where the factor fails.
-template <typename T, int N> inline void lqr_problem(const LqrArgs<T>& a, size_t M, size_t m) {
-    constexpr int NU = LQR_NU, NP = N + NU;
+// A failed problem m of M: bad is written and every float output is NaN.
+template <typename T, int N> inline void lqr_failed(const LqrArgs<T>& a, size_t M, size_t m, int bad) {
+    constexpr int NU = LQR_NU;
     const int TT = a.horizon;
     const T nan = lqr_nan<T>();
+    if (a.bad) a.bad[m] = bad;
+    for (int t = 0; t <= TT; t++) {
+        const size_t p = (size_t)t*M + m;
+        if (a.dx) for (int i = 0; i < N; i++) a.dx[p*N + i] = nan;
+        if (t == TT) break;
+        if (a.k) for (int i = 0; i < NU; i++) a.k[p*NU + i] = nan;
+        if (a.K) for (int i = 0; i < NU*N; i++) a.K[p*NU*N + i] = nan;
+        if (a.du) for (int i = 0; i < NU; i++) a.du[p*NU + i] = nan;
+    }
+    if (a.Vx0) for (int i = 0; i < N; i++) a.Vx0[m*N + i] = nan;
+    if (a.Vxx0) for (int i = 0; i < N*N; i++) a.Vxx0[m*(N*N) + i] = nan;
+    if (a.dV) a.dV[2*m] = a.dV[2*m + 1] = nan;
+}
+
+// The whole query for problem m of M, element by element: the twin's form (the kernel deals the same arithmetic over a wave).  The inputs of
+// step t are tested for finiteness as they are read: bad = T at the first step (from the end) that has one, bad = t where the factor fails.
+// Returns bad.
+template <typename T, int N> inline int lqr_problem(const LqrArgs<T>& a, size_t M, size_t m) {
+    constexpr int NU = LQR_NU, NP = N + NU;
+    const int TT = a.horizon;
     T Vx[N], Vxx[N][N], dV1 = T(0), dV2 = T(0);
     int bad = -1;
     bool fin = true;
@@ -168,25 +189,12 @@ template <typename T, int N> inline void lqr_problem(const LqrArgs<T>& a, size_t
         if (a.k) for (int i = 0; i < NU; i++) a.k[p*NU + i] = kk[i];
         if (a.K) for (int i = 0; i < NU; i++) for (int j = 0; j < N; j++) a.K[(p*NU + i)*N + j] = K[i][j];
     }
+    if (bad >= 0) { lqr_failed<T, N>(a, M, m, bad); return bad; }
     if (a.bad) a.bad[m] = bad;
-    if (bad >= 0) {                                          // every float output of a failed problem is NaN
-        for (int t = 0; t <= TT; t++) {
-            const size_t p = (size_t)t*M + m;
-            if (a.dx) for (int i = 0; i < N; i++) a.dx[p*N + i] = nan;
-            if (t == TT) break;
-            if (a.k) for (int i = 0; i < NU; i++) a.k[p*NU + i] = nan;
-            if (a.K) for (int i = 0; i < NU*N; i++) a.K[p*NU*N + i] = nan;
-            if (a.du) for (int i = 0; i < NU; i++) a.du[p*NU + i] = nan;
-        }
-        if (a.Vx0) for (int i = 0; i < N; i++) a.Vx0[m*N + i] = nan;
-        if (a.Vxx0) for (int i = 0; i < N*N; i++) a.Vxx0[m*(N*N) + i] = nan;
-        if (a.dV) a.dV[2*m] = a.dV[2*m + 1] = nan;
-        return;
-    }
     if (a.Vx0) for (int i = 0; i < N; i++) a.Vx0[m*N + i] = Vx[i];
     if (a.Vxx0) for (int i = 0; i < N; i++) for (int j = 0; j < N; j++) a.Vxx0[m*(N*N) + i*N + j] = Vxx[i][j];
     if (a.dV) { a.dV[2*m] = dV1; a.dV[2*m + 1] = dV2; }
-    if (!a.du && !a.dx) return;
+    if (!a.du && !a.dx) return bad;
     T dx[N];
     for (int i = 0; i < N; i++) dx[i] = a.dx0 ? a.dx0[m*N + i] : T(0);
     for (int t = 0; t < TT; t++) {
@@ -210,6 +218,57 @@ template <typename T, int N> inline void lqr_problem(const LqrArgs<T>& a, size_t
         for (int i = 0; i < N; i++) dx[i] = nx[i];
     }
     if (a.dx) for (int i = 0; i < N; i++) a.dx[((size_t)TT*M + m)*N + i] = dx[i];
+    return bad;
+}
+
+// ---- the regulariser per problem (so100_query_lqr_reg, so100_query_reg_schedule) ------------------------------------------------
+constexpr int LQR_REG_MAX_TRIES = 16;                        // SO100_LQR_REG_MAX_TRIES
+
+template <typename T> struct LqrRegArgs {
+    const T* reg;                                            // [M] or null: LqrArgs::reg for every problem
+    T reg_min, reg_max, reg_up;
+    int tries;
+    T* reg_used;                                             // [M] or null
+    int32_t* tries_out;                                      // [M] or null
+};
+
+// the reg a failed pass goes on with: min(reg_max, max(reg_min, r reg_up)), the product rounded once; raise(0) = reg_min
+template <typename T> SO100_HD T lqr_reg_raise(T r, T reg_min, T reg_max, T reg_up) {
+    T v = r*reg_up;
+    v = v > reg_min ? v : reg_min;
+    return v < reg_max ? v : reg_max;
+}
+// a reg to start from: finite and >= 0
+template <typename T> SO100_HD bool lqr_reg_valid(T r) { return r >= T(0) && lqr_finite(r); }
+// whether a pass that ended with `bad` under r, the `pass`-th of `tries`, is followed by another: the factor failed (not an input) and there is room
+template <typename T> SO100_HD bool lqr_reg_again(int bad, int horizon, int pass, int tries, T r, T reg_max) {
+    return bad >= 0 && bad < horizon && pass < tries && r < reg_max;
+}
+// the line search's verdict on the reg a plan was made with (Tassa's schedule: a reg under reg_min becomes 0); r not finite or negative counts as 0
+template <typename T> SO100_HD T lqr_reg_next(T r, bool improved, T reg_min, T reg_max, T reg_up, T reg_down) {
+    if (!lqr_reg_valid(r)) r = T(0);
+    if (!improved) return lqr_reg_raise(r, reg_min, reg_max, reg_up);
+    const T v = r*reg_down;
+    return v < reg_min ? T(0) : v;
+}
+
+// so100_query_lqr_reg for problem m of M, the twin's form: lqr_problem under r, again under raise(r) while the factor fails and there is room.
+// A pass that fails leaves NaN behind it, the next one writes every row again, so what stands in the end is the last pass's.
+template <typename T, int N> inline void lqr_reg_problem(const LqrArgs<T>& a, const LqrRegArgs<T>& g, size_t M, size_t m) {
+    LqrArgs<T> b = a;
+    T r = g.reg ? g.reg[m] : a.reg;
+    int pass = 0;
+    if (!lqr_reg_valid(r)) { lqr_failed<T, N>(a, M, m, a.horizon); r = lqr_nan<T>(); }
+    else
+        for (;;) {
+            b.reg = r;
+            const int bad = lqr_problem<T, N>(b, M, m);
+            pass++;
+            if (!lqr_reg_again(bad, a.horizon, pass, g.tries, r, g.reg_max)) break;
+            r = lqr_reg_raise(r, g.reg_min, g.reg_max, g.reg_up);
+        }
+    if (g.reg_used) g.reg_used[m] = r;
+    if (g.tries_out) g.tries_out[m] = pass;
 }
 
 }  // namespace so100

@@ -139,6 +139,13 @@ int query_steps(const char* fn, int32_t T, int limit) {
     if (T < 1 || T > limit) return fail(SO100_E_INVALID, "%s: T must be in 1..%d, got %ld", fn, limit, (long)T);
     return 0;
 }
+// the regulariser's range and its factor up (so100_query_lqr_reg, so100_query_reg_schedule)
+int query_reg_range(const char* fn, float reg_min, float reg_max, float reg_up) {
+    if (!(reg_min > 0.0f) || !std::isfinite(reg_min)) return fail(SO100_E_INVALID, "%s: reg_min must be finite and > 0, got %g", fn, (double)reg_min);
+    if (!(reg_max >= reg_min) || !std::isfinite(reg_max)) return fail(SO100_E_INVALID, "%s: reg_max must be finite and >= reg_min, got %g", fn, (double)reg_max);
+    if (!(reg_up > 1.0f) || !std::isfinite(reg_up)) return fail(SO100_E_INVALID, "%s: reg_up must be finite and > 1, got %g", fn, (double)reg_up);
+    return 0;
+}
 // the candidates of each problem: `count` of them (named c: "L" or "K") for each of `batch` problems (named b: "M" or "N"); every rollout has an int32 index
 int query_candidates(const char* fn, const char* c, const char* b, int32_t count, int limit, int32_t batch) {
     if (count < 1 || count > limit || (long long)batch*(long long)count > (long long)INT32_MAX)

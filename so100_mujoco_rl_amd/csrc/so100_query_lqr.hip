@@ -1,4 +1,5 @@
-// so100_query_lqr.hip -- the LQR query (gfx950) and its C ABI (include/so100_query.h: so100_query_lqr); the recursion and the pieces shared with
+// so100_query_lqr.hip -- the LQR query (gfx950) and its C ABI (include/so100_query.h: so100_query_lqr, and with a regulariser per problem
+// so100_query_lqr_reg and so100_query_reg_schedule); the recursion and the pieces shared with
 // the host twin are in so100_lqr.hpp.  Like so100_query_derivative.hip, not a translation unit of its own: so100_sim.hip includes it.
 //
 // Shape: one workgroup is one wave is one problem (blockIdx.x).  Lane l = (c, h): c = l & 31 is a COLUMN of a 32 x 32 tile, h = l >> 5 picks
@@ -31,8 +32,16 @@ constexpr bool LQR_MFMA = false;                             // a side build (to
 constexpr bool LQR_MFMA = true;
 #endif
 
-template <int N, bool MFMA>
-__global__ void __launch_bounds__(64) so100_query_lqr_k(LqrArgs<float> a, int M) {
+// REG (so100_query_lqr_reg): the regulariser is the problem's own, and a pass whose factor fails is run again from the terminal cost
+// under a raised one.  reg, the pass count and the decision are the same in every lane (the factor's failure goes through a ballot), so the wave
+// never diverges on it.  Beside the plain form's accesses: one read of reg[m] and lane 0's stores to reg_used[m] and tries_out[m] of LqrRegArgs; no LDS.
+// Beyond three locals (reg, which the factor reads, pass and valid) every statement of it is behind if constexpr (REG): the plain instantiations
+// take no second struct and compile to the instructions they had.
+__device__ __forceinline__ const LqrRegArgs<float>& lqr_reg_args(const LqrRegArgs<float>& g) { return g; }
+
+template <int N, bool MFMA, bool REG, typename... G>
+__global__ void __launch_bounds__(64) so100_query_lqr_k(LqrArgs<float> a, int M, G... extra) {
+    static_assert(sizeof...(G) == (REG ? 1 : 0), "the REG forms alone take the second argument struct");
     constexpr int NU = LQR_NU, NP = N + NU, NR = N == 24 ? 12 : 8, QCOL = 30;
     static_assert(NP <= QCOL && 2*NR >= N, "the tile holds G, and column 30 is free");
     __shared__ float S[32][36], Gs[32][32], Qs[6][32], Ks[6][32], vx[32], qx[32], dxs[32], dus[8];
@@ -56,6 +65,15 @@ __global__ void __launch_bounds__(64) so100_query_lqr_k(LqrArgs<float> a, int M)
             for (int r = 0; r < NR; r++) S[LQR_ROW(r)][c] = V[r];
         }
     };
+    float reg = a.reg;
+    int pass = 0;
+    bool valid = true;
+    if constexpr (REG) {
+        const LqrRegArgs<float>& rg = lqr_reg_args(extra...);
+        if (rg.reg) reg = rg.reg[m];                         // the same word in every lane
+        valid = lqr_reg_valid(reg);
+    }
+again:                                                       // REG: a backward pass starts here, from the terminal cost; else reached once
     bool fin = true;
     {
         const float* lxx = a.lxx + ((size_t)TT*Mz + m)*(size_t)(N*N);
@@ -70,6 +88,7 @@ __global__ void __launch_bounds__(64) so100_query_lqr_k(LqrArgs<float> a, int M)
         symmetrise();
     }
     int bad = __builtin_amdgcn_ballot_w64(!fin) != 0ull ? TT : -1;
+    if constexpr (REG) { if (valid) pass++; else bad = TT; } // a start that is no reg is a non-finite input, and no pass runs
     float dV1 = 0.0f, dV2 = 0.0f;
     for (int t = TT - 1; t >= 0 && bad < 0; t--) {
         const size_t p = (size_t)t*Mz + m;
@@ -171,7 +190,7 @@ __global__ void __launch_bounds__(64) so100_query_lqr_k(LqrArgs<float> a, int M)
 #pragma unroll
             for (int j = 0; j < NU; j++) Quu[i][j] = Qs[i][N + j];
         }
-        const bool ok = lqr_chol6(Quu, a.reg, L, inv);
+        const bool ok = lqr_chol6(Quu, reg, L, inv);
         if (__builtin_amdgcn_ballot_w64(!ok) != 0ull) { bad = t; break; }
         lqr_solve6(L, inv, Qu, kk);
         lqr_solve6(L, inv, Qc, Kc);
@@ -208,6 +227,13 @@ __global__ void __launch_bounds__(64) so100_query_lqr_k(LqrArgs<float> a, int M)
         __syncthreads();                                     // every read of vx, qx, Qs and Ks of this step is done
         if (lane < N) vx[lane] = vnew;
         symmetrise();
+    }
+    if constexpr (REG) {
+        const LqrRegArgs<float>& rg = lqr_reg_args(extra...);
+        // the failed step's reads of vx, S and Gs lie before its barrier, and the next pass writes Qs, qx and Ks behind symmetrise's: no barrier here
+        if (lqr_reg_again(bad, TT, pass, rg.tries, reg, rg.reg_max)) { reg = lqr_reg_raise(reg, rg.reg_min, rg.reg_max, rg.reg_up); goto again; }
+        if (lane == 0 && rg.reg_used) rg.reg_used[m] = valid ? reg : nan;
+        if (lane == 0 && rg.tries_out) rg.tries_out[m] = pass;
     }
     if (lane == 0 && a.bad) a.bad[m] = bad;
     if (bad >= 0) {                                          // every float output of a failed problem is NaN
@@ -264,17 +290,22 @@ __global__ void __launch_bounds__(64) so100_query_lqr_k(LqrArgs<float> a, int M)
 #undef LQR_ROW
 }
 
-}  // namespace so100
+// so100_query_reg_schedule: one lane per problem.  reg and reg_used may be the same array: a lane reads its word before it writes it.
+struct RegScheduleArgs { const float* reg_used; const int32_t* best; int keep; float reg_min, reg_max, reg_up, reg_down; float* reg; uint8_t* improved; };
 
-static_assert(SO100_LQR_NU == so100::LQR_NU && SO100_LQR_MAX_T == so100::LQR_MAX_T && SO100_DERIV_NX == 24 && SO100_DERIV_NU == 6,
-              "the header names the sizes; A and B are in the derivatives query's layout");
+__global__ void __launch_bounds__(QUERY_THREADS) so100_query_reg_schedule_k(RegScheduleArgs s, int M) {
+    const size_t i = (size_t)blockIdx.x*QUERY_THREADS + threadIdx.x;
+    if (i >= (size_t)M) return;
+    const int best = s.best[i];
+    const bool improved = best >= 0 && best != s.keep;
+    s.reg[i] = lqr_reg_next(s.reg_used[i], improved, s.reg_min, s.reg_max, s.reg_up, s.reg_down);
+    if (s.improved) s.improved[i] = improved ? 1 : 0;
+}
 
-extern "C" {
+namespace {
 
-int so100_query_lqr(so100_sim* sim, const so100_lqr_io* io, int32_t M, void* stream) {
-    using namespace so100;
-    const char* const fn = "so100_query_lqr";
-    if (!sim || !io) return fail(SO100_E_INVALID, "so100_query_lqr: null argument");
+// the checks so100_query_lqr and so100_query_lqr_reg share, up to the one on the outputs (each entry counts its own)
+int lqr_check(const char* fn, const so100_sim* sim, const so100_lqr_io* io, int32_t M) {
     if (const int rc = query_batch(fn, sim, false, M)) return rc;                 // no state is read: any M >= 1
     if (io->nx != 12 && io->nx != 24) return fail(SO100_E_INVALID, "%s: nx must be 12 or 24, got %ld", fn, (long)io->nx);
     if (io->T < 1 || io->T > SO100_LQR_MAX_T) return fail(SO100_E_INVALID, "%s: T must be in 1..%d, got %ld", fn, SO100_LQR_MAX_T, (long)io->T);
@@ -283,16 +314,73 @@ int so100_query_lqr(so100_sim* sim, const so100_lqr_io* io, int32_t M, void* str
     if (!(io->alpha*0.0f == 0.0f)) return fail(SO100_E_INVALID, "%s: alpha must be finite, got %g", fn, (double)io->alpha);
     if (!(io->u_lo <= io->u_hi)) return fail(SO100_E_INVALID, "%s: u_lo must be <= u_hi, got %g and %g", fn, (double)io->u_lo, (double)io->u_hi);
     if ((io->du_dev || io->dx_dev) && (!io->k_dev || !io->K_dev)) return fail(SO100_E_INVALID, "%s: du_dev and dx_dev need k_dev and K_dev", fn);
-    if (!io->k_dev && !io->K_dev && !io->Vx0_dev && !io->Vxx0_dev && !io->dV_dev && !io->du_dev && !io->dx_dev && !io->bad_dev)
-        return fail(SO100_E_INVALID, "%s: no output requested", fn);
+    return 0;
+}
+bool lqr_any_output(const so100_lqr_io* io) {
+    return io->k_dev || io->K_dev || io->Vx0_dev || io->Vxx0_dev || io->dV_dev || io->du_dev || io->dx_dev || io->bad_dev;
+}
+LqrArgs<float> lqr_args(const so100_lqr_io* io) {
     LqrArgs<float> a{};
     a.A = io->A_dev; a.B = io->B_dev; a.lx = io->lx_dev; a.lxx = io->lxx_dev; a.lu = io->lu_dev; a.luu = io->luu_dev; a.lux = io->lux_dev;
     a.u = io->u_dev; a.dx0 = io->dx0_dev; a.horizon = io->T; a.reg = io->reg; a.alpha = io->alpha; a.u_lo = io->u_lo; a.u_hi = io->u_hi;
     a.k = io->k_dev; a.K = io->K_dev; a.Vx0 = io->Vx0_dev; a.Vxx0 = io->Vxx0_dev; a.dV = io->dV_dev; a.du = io->du_dev; a.dx = io->dx_dev; a.bad = io->bad_dev;
+    return a;
+}
+
+}  // namespace
+}  // namespace so100
+
+static_assert(SO100_LQR_NU == so100::LQR_NU && SO100_LQR_MAX_T == so100::LQR_MAX_T && SO100_DERIV_NX == 24 && SO100_DERIV_NU == 6,
+              "the header names the sizes; A and B are in the derivatives query's layout");
+static_assert(SO100_LQR_REG_MAX_TRIES == so100::LQR_REG_MAX_TRIES, "the header names the limit");
+
+extern "C" {
+
+int so100_query_lqr(so100_sim* sim, const so100_lqr_io* io, int32_t M, void* stream) {
+    using namespace so100;
+    const char* const fn = "so100_query_lqr";
+    if (!sim || !io) return fail(SO100_E_INVALID, "so100_query_lqr: null argument");
+    if (const int rc = lqr_check(fn, sim, io, M)) return rc;
+    if (!lqr_any_output(io)) return fail(SO100_E_INVALID, "%s: no output requested", fn);
+    const LqrArgs<float> a = lqr_args(io);
     SO100_ON_DEVICE(sim->cfg.device, "so100_query_lqr");
     const dim3 grid((unsigned)M), block(64);                 // one wave per problem
-    if (io->nx == 24) hipLaunchKernelGGL((so100_query_lqr_k<24, LQR_MFMA>), grid, block, 0, (hipStream_t)stream, a, M);
-    else              hipLaunchKernelGGL((so100_query_lqr_k<12, LQR_MFMA>), grid, block, 0, (hipStream_t)stream, a, M);
+    if (io->nx == 24) hipLaunchKernelGGL((so100_query_lqr_k<24, LQR_MFMA, false>), grid, block, 0, (hipStream_t)stream, a, M);
+    else              hipLaunchKernelGGL((so100_query_lqr_k<12, LQR_MFMA, false>), grid, block, 0, (hipStream_t)stream, a, M);
+    HIP_TRY(hipGetLastError(), SO100_E_LAUNCH);
+    return 0;
+}
+
+int so100_query_lqr_reg(so100_sim* sim, const so100_lqr_reg_io* io, int32_t M, void* stream) {
+    using namespace so100;
+    const char* const fn = "so100_query_lqr_reg";
+    if (!sim || !io) return fail(SO100_E_INVALID, "so100_query_lqr_reg: null argument");
+    if (const int rc = lqr_check(fn, sim, &io->base, M)) return rc;
+    if (const int rc = query_reg_range(fn, io->reg_min, io->reg_max, io->reg_up)) return rc;
+    if (io->tries < 1 || io->tries > SO100_LQR_REG_MAX_TRIES) return fail(SO100_E_INVALID, "%s: tries must be in 1..%d, got %ld", fn, SO100_LQR_REG_MAX_TRIES, (long)io->tries);
+    if (!lqr_any_output(&io->base) && !io->reg_used_dev && !io->tries_dev) return fail(SO100_E_INVALID, "%s: no output requested", fn);
+    const LqrArgs<float> a = lqr_args(&io->base);
+    const LqrRegArgs<float> rg{ io->reg_dev, io->reg_min, io->reg_max, io->reg_up, io->tries, io->reg_used_dev, io->tries_dev };
+    SO100_ON_DEVICE(sim->cfg.device, "so100_query_lqr_reg");
+    const dim3 grid((unsigned)M), block(64);                 // one wave per problem
+    if (io->base.nx == 24) hipLaunchKernelGGL((so100_query_lqr_k<24, LQR_MFMA, true, LqrRegArgs<float>>), grid, block, 0, (hipStream_t)stream, a, M, rg);
+    else                   hipLaunchKernelGGL((so100_query_lqr_k<12, LQR_MFMA, true, LqrRegArgs<float>>), grid, block, 0, (hipStream_t)stream, a, M, rg);
+    HIP_TRY(hipGetLastError(), SO100_E_LAUNCH);
+    return 0;
+}
+
+int so100_query_reg_schedule(so100_sim* sim, const so100_reg_schedule_io* io, int32_t M, void* stream) {
+    using namespace so100;
+    const char* const fn = "so100_query_reg_schedule";
+    if (!sim || !io) return fail(SO100_E_INVALID, "so100_query_reg_schedule: null argument");
+    if (const int rc = query_batch(fn, sim, false, M)) return rc;                 // no state is read: any M >= 1
+    if (!io->reg_used_dev || !io->best_dev || !io->reg_dev) return fail(SO100_E_INVALID, "%s: reg_used_dev, best_dev and reg_dev are required", fn);
+    if (io->keep < -1) return fail(SO100_E_INVALID, "%s: keep must be a candidate index or -1, got %ld", fn, (long)io->keep);
+    if (const int rc = query_reg_range(fn, io->reg_min, io->reg_max, io->reg_up)) return rc;
+    if (!(io->reg_down > 0.0f) || !(io->reg_down <= 1.0f)) return fail(SO100_E_INVALID, "%s: reg_down must be in (0, 1], got %g", fn, (double)io->reg_down);
+    const RegScheduleArgs s{ io->reg_used_dev, io->best_dev, io->keep, io->reg_min, io->reg_max, io->reg_up, io->reg_down, io->reg_dev, io->improved_dev };
+    SO100_ON_DEVICE(sim->cfg.device, "so100_query_reg_schedule");
+    hipLaunchKernelGGL(so100_query_reg_schedule_k, dim3(query_grid(M)), dim3(QUERY_THREADS), 0, (hipStream_t)stream, s, M);
     HIP_TRY(hipGetLastError(), SO100_E_LAUNCH);
     return 0;
 }

@@ -194,6 +194,16 @@ class LqrIO(C.Structure):
                [(n, C.c_void_p) for n in ("k_dev", "K_dev", "Vx0_dev", "Vxx0_dev", "dV_dev", "du_dev", "dx_dev", "bad_dev")]
 
 
+class LqrRegIO(C.Structure):
+    _fields_ = [("base", LqrIO), ("reg_dev", C.c_void_p), ("reg_min", C.c_float), ("reg_max", C.c_float), ("reg_up", C.c_float), ("tries", C.c_int32),
+                ("reg_used_dev", C.c_void_p), ("tries_dev", C.c_void_p)]
+
+
+class RegScheduleIO(C.Structure):
+    _fields_ = [("reg_used_dev", C.c_void_p), ("best_dev", C.c_void_p), ("keep", C.c_int32), ("reg_min", C.c_float), ("reg_max", C.c_float),
+                ("reg_up", C.c_float), ("reg_down", C.c_float), ("reg_dev", C.c_void_p), ("improved_dev", C.c_void_p)]
+
+
 class ClosedLoopIO(C.Structure):
     _fields_ = [("qpos_dev", C.c_void_p), ("qvel_dev", C.c_void_p), ("u_dev", C.c_void_p), ("mode", C.c_int32), ("T", C.c_int32), ("nsub", C.c_int32),
                 ("flags", C.c_uint32), ("solver_iters", C.c_int32), ("contact_iters", C.c_int32)] + \
@@ -250,17 +260,18 @@ class CostRefitIO(C.Structure):
 
 QUERY_EXPORTS = ["so100_query_kinematics", "so100_query_jacobian", "so100_query_dynamics", "so100_query_ik", "so100_query_forward",
                  "so100_query_trajectory", "so100_query_derivatives", "so100_query_lqr", "so100_query_closed_loop", "so100_query_cost_terms",
-                 "so100_query_cost_select", "so100_query_plan_sample", "so100_query_cost_blend", "so100_query_plan_sample_tv", "so100_query_cost_refit"]
+                 "so100_query_cost_select", "so100_query_plan_sample", "so100_query_cost_blend", "so100_query_plan_sample_tv", "so100_query_cost_refit",
+                 "so100_query_lqr_reg", "so100_query_reg_schedule"]
 QUERY_IO = {"so100_query_kinematics": KinematicsIO, "so100_query_jacobian": JacobianIO, "so100_query_dynamics": DynamicsIO, "so100_query_ik": IkIO,
             "so100_query_forward": ForwardIO, "so100_query_trajectory": TrajectoryIO, "so100_query_derivatives": DerivativesIO, "so100_query_lqr": LqrIO,
             "so100_query_closed_loop": ClosedLoopIO, "so100_query_cost_terms": CostTermsIO, "so100_query_cost_select": CostSelectIO,
             "so100_query_plan_sample": PlanSampleIO, "so100_query_cost_blend": CostBlendIO, "so100_query_plan_sample_tv": PlanSampleTvIO,
-            "so100_query_cost_refit": CostRefitIO}
+            "so100_query_cost_refit": CostRefitIO, "so100_query_lqr_reg": LqrRegIO, "so100_query_reg_schedule": RegScheduleIO}
 MPPI_MAX_K = 4096                                              # SO100_MPPI_MAX_K
 BLEND_TAILS = {"zero": 0, "hold": 1}                           # SO100_BLEND_TAIL_*
 COST_TARGETS = {"fixed": 0, "traj": 1, "cube": 2}               # SO100_COST_TARGET_*
 DERIV_NX, DERIV_NU, DERIV_EPS = 24, 6, 2.0**-6                 # SO100_DERIV_*
-LQR_NU, LQR_MAX_T = 6, 4096                                    # SO100_LQR_*
+LQR_NU, LQR_MAX_T, LQR_REG_MAX_TRIES = 6, 4096, 16             # SO100_LQR_*
 CL_MAX_L = 16                                                  # SO100_CL_MAX_L
 TRAJ_MODES = {"targets": 0, "actions": 1}                      # SO100_TRAJ_TARGETS / SO100_TRAJ_ACTIONS
 TRAJ_MAX_T, TRAJ_MAX_NSUB, TRAJ_MAX_SUBSTEPS = 4096, 1024, 65536    # SO100_TRAJ_MAX_*
@@ -812,6 +823,55 @@ class So100Sim(_Handle):
         "Vxx0" [M, n, n], "dV" [M, 2] (the expected change of the model is alpha dV1 + alpha^2 dV2), "du" [T, M, 6] = alpha k + K dx (clamped with
         u), "dx" [T + 1, M, n] and "bad" [M] int32: -1, or the step whose Quu + reg I is not positive definite, or T for a non-finite input; a
         failed problem's float outputs are NaN."""
+        io, M, out = self._lqr_io(A, B, lx, lxx, lu, luu, lux, nx, reg, alpha, u, u_lo, u_hi, dx0)
+        _check(self.L.so100_query_lqr(self.h, C.byref(io), M, self._stream()), "so100_query_lqr")
+        return out
+
+    def lqr_reg(self, A, B, lx, lxx, lu=None, luu=None, lux=None, *, nx=24, reg=0.0, reg_min=1e-6, reg_max=1e10, reg_up=10.0, tries=8, alpha=1.0, u=None,
+                u_lo=-1.0, u_hi=1.0, dx0=None):
+        """lqr() with a regulariser per problem and the retry of a failed factor inside the launch.  reg: a float (every problem starts from it) or an
+        [M] tensor (float32 on the device: read in place).  A problem whose Quu + reg I is not positive definite at some step runs its backward pass
+        again under reg <- min(reg_max, max(reg_min, reg * reg_up)), up to `tries` passes and while reg < reg_max; the others are not held up by it
+        and keep the reg they came with.  Returns lqr()'s dict -- for a problem that got through, bit for bit lqr()'s outputs under reg =
+        reg_used -- plus "reg_used" [M] (the reg of the last pass run; NaN for a start that is negative or not finite) and "tries" [M] int32 (passes
+        run: 0 for such a start).  "bad" is the last pass's."""
+        start = None
+        if isinstance(reg, torch.Tensor):
+            if reg.dim() != 1:
+                raise So100Error(f"reg: want a float or an [M] tensor, got {tuple(reg.shape)}")
+            start = self._lqr_in(reg, (reg.shape[0],), "reg")
+        base, M, out = self._lqr_io(A, B, lx, lxx, lu, luu, lux, nx, 0.0 if start is not None else reg, alpha, u, u_lo, u_hi, dx0)
+        if start is not None and start.shape[0] != M:
+            raise So100Error(f"reg: want a float or a [{M}] tensor, got {tuple(start.shape)}")
+        out["reg_used"], out["tries"] = self._out(M), self._out(M, dtype=torch.int32)
+        io = LqrRegIO(base, _optr(start), reg_min, reg_max, reg_up, tries, out["reg_used"].data_ptr(), out["tries"].data_ptr())
+        _check(self.L.so100_query_lqr_reg(self.h, C.byref(io), M, self._stream()), "so100_query_lqr_reg")
+        return out
+
+    def reg_schedule(self, reg_used, best, *, keep=0, reg_min=1e-6, reg_max=1e10, reg_up=10.0, reg_down=0.1, out=None):
+        """The next regulariser of each problem from the one its plan was made with (lqr_reg()'s "reg_used" [M]) and the line search's verdict
+        (cost_select()'s "best" [M] int32), in one launch.  A problem improved where best is a candidate other than `keep` -- the index of the
+        candidate that is the old plan (alpha = 0), -1 if there is none.  Improved: reg * reg_down, and 0 where that is under reg_min; not improved:
+        min(reg_max, max(reg_min, reg * reg_up)).  out: the [M] tensor to write (reg_used itself is allowed), None: a new one.  Returns "reg" [M]
+        and "improved" [M] uint8."""
+        ru = torch.as_tensor(reg_used, dtype=torch.float32, device=self.device)
+        if ru.dim() != 1 or ru.shape[0] < 1 or not ru.is_contiguous():
+            raise So100Error(f"reg_used: want a contiguous [M] tensor, got {tuple(ru.shape)}")
+        M = ru.shape[0]
+        bs = torch.as_tensor(best, dtype=torch.int32, device=self.device).contiguous()
+        if tuple(bs.shape) != (M,):
+            raise So100Error(f"best: want a [{M}] tensor, got {tuple(bs.shape)}")
+        if out is None:
+            out = self._out(M)
+        elif out.dtype != torch.float32 or tuple(out.shape) != (M,) or not out.is_contiguous() or out.device != ru.device:
+            raise So100Error(f"out: want a contiguous float32 [{M}] tensor on {ru.device}")
+        imp = self._out(M, dtype=torch.uint8)
+        io = RegScheduleIO(ru.data_ptr(), bs.data_ptr(), keep, reg_min, reg_max, reg_up, reg_down, out.data_ptr(), imp.data_ptr())
+        _check(self.L.so100_query_reg_schedule(self.h, C.byref(io), M, self._stream()), "so100_query_reg_schedule")
+        return {"reg": out, "improved": imp}
+
+    def _lqr_io(self, A, B, lx, lxx, lu, luu, lux, nx, reg, alpha, u, u_lo, u_hi, dx0):
+        """lqr()'s arguments checked and packed: (the LqrIO, M, the outputs it points to)"""
         f32 = self._lqr_in
         A = torch.as_tensor(A, dtype=torch.float32, device=self.device)
         if A.dim() != 4 or A.shape[0] < 1 or A.shape[1] < 1:
@@ -828,8 +888,8 @@ class So100Sim(_Handle):
                "dx": new(T + 1, M, n), "bad": new(M, dtype=torch.int32)}
         io = LqrIO(n, T, *[_optr(t) for t in (A, B, lx, lxx, lu, luu, lux, u, dx0)], reg, alpha, u_lo, u_hi,
                    *[out[name].data_ptr() for name in ("k", "K", "Vx0", "Vxx0", "dV", "du", "dx", "bad")])
-        _check(self.L.so100_query_lqr(self.h, C.byref(io), M, self._stream()), "so100_query_lqr")
-        return out
+        io._inputs = (A, B, lx, lxx, lu, luu, lux, u, dx0)           # converted copies live as long as the io
+        return io, M, out
 
     def closed_loop(self, u, qpos_ref, qvel_ref, K, k=None, *, alphas=(1.0,), nx=24, qpos=None, qvel=None, ref0=None, mode="targets", nsub=None, flags=None,
                     clamp=None, solver_iters=None, contact_iters=None):

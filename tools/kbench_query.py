@@ -6,6 +6,7 @@
     python tools/kbench_query.py --trajectory [--out profiles/trajectory_kbench.json] [--commit LABEL] [--rounds 5]
     python tools/kbench_query.py --derivatives [--out profiles/derivatives_kbench.json] [--commit LABEL] [--rounds 5]
     python tools/kbench_query.py --lqr [--form mfma] [--out profiles/lqr_kbench.json] [--commit LABEL] [--rounds 5]
+    python tools/kbench_query.py --lqr-reg [--out profiles/lqr_reg_kbench.json] [--commit LABEL] [--rounds 5]
     python tools/kbench_query.py --closed-loop [--form global] [--out profiles/closed_loop_kbench.json] [--commit LABEL] [--rounds 5]
     python tools/kbench_query.py --cost [--out profiles/cost_kbench.json] [--commit LABEL] [--rounds 5]
     python tools/kbench_query.py --mppi [--out profiles/mppi_kbench.json] [--commit LABEL] [--rounds 5]
@@ -464,6 +465,135 @@ def lqr_main(a):
             doc["cases"].append(case)
             print(json.dumps(case), flush=True)
             del A, B, lxx, lx, lu, luu, out, As, Bs, spans
+    sim.close()
+    with open(a.out, "w") as fh:
+        json.dump(doc, fh, indent=1)
+        fh.write("\n")
+
+
+def lqr_reg_main(a):
+    """so100_query_lqr_reg and so100_query_reg_schedule at lqr_main's shapes and inputs, in three parts.  (a) lqr_reg with tries = 1 and no reg_dev
+    against lqr: the same work through the REG kernel.  (b) every fourth problem made to need four passes (lqr_support's indefinite case: luu = -I,
+    B a tenth at the middle step; reg 0 -> 0.125 -> 0.5 -> 2), one lqr_reg call with tries = 4 against what a caller does today: a call, a readback of
+    bad on the host, and three more whole-batch calls under the raised regs.  (c) reg_schedule against the same arithmetic in torch.  An event pair
+    round each unit; (b)'s baseline has a host synchronisation inside its span, which is part of what it costs."""
+    sim = lib.So100Sim(lib.ENV01, 8, device="cuda:0", flags=lib.F_CUBE_PINNED, seed=0)
+    dev, L, st = sim.device, sim.L, sim._stream()
+    knobs = dict(reg_min=0.125, reg_max=32.0, reg_up=4.0)
+    doc = {"what": "HIP-event times of so100_query_lqr_reg and so100_query_reg_schedule; an event pair round each unit, medians of alternated rounds.  "
+                   "(a) lqr_reg with tries = 1 against lqr on identical inputs; (b) a quarter of the problems needing four passes: one lqr_reg call against "
+                   "a lqr call, a readback of bad and three more whole-batch lqr calls; (c) reg_schedule against the same arithmetic in torch",
+           "commit": a.commit, "card": torch.cuda.get_device_name(0), "rounds": a.rounds, "knobs": dict(knobs, tries=4), "same_work": [], "retry": [], "schedule": []}
+
+    def pair(call):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(); call(); e1.record()
+        return e0, e1
+
+    def timed(call, n):
+        pairs = [pair(call) for _ in range(n)]
+        torch.cuda.synchronize()
+        return sum(e0.elapsed_time(e1) for e0, e1 in pairs)*1e3/n
+
+    def rounds(one, other, reps):
+        timed(one, 2); timed(other, 2)
+        t1, t2 = [], []
+        for _ in range(a.rounds):
+            t1.append(timed(one, reps)); t2.append(timed(other, reps))
+        return t1, t2
+
+    us = lambda xs: [round(x, 1) for x in xs]
+    for nx in (12, 24):
+        for M, T, reps, _ in LQR_SIZES:
+            g = torch.Generator(device=dev).manual_seed(0)
+            rn = lambda *shape: torch.randn(*shape, generator=g, device=dev)
+            A = torch.eye(24, device=dev) + 0.3*rn(T, M, 24, 24)/nx**0.5
+            B = 0.3*rn(T, M, 24, 6)
+            Cm = rn(T + 1, M, nx, nx)/nx**0.5
+            lxx = (Cm @ Cm.transpose(2, 3) + 0.1*torch.eye(nx, device=dev)).contiguous()
+            del Cm
+            lx, lu = rn(T + 1, M, nx), rn(T, M, 6)
+            luu = (0.2*torch.eye(6, device=dev)).expand(T, M, 6, 6).contiguous()
+            U = torch.zeros(T, M, 6, device=dev)
+            shapes = {"k": (T, M, 6), "K": (T, M, 6, nx), "Vx0": (M, nx), "Vxx0": (M, nx, nx), "dV": (M, 2), "du": (T, M, 6), "dx": (T + 1, M, nx)}
+            new = lambda: {k: torch.empty(*shape, dtype=torch.float32, device=dev) for k, shape in shapes.items()}
+            o1, o2 = new(), new()
+            bad1, bad2 = torch.empty(M, dtype=torch.int32, device=dev), torch.empty(M, dtype=torch.int32, device=dev)
+            used, ran = torch.empty(M, device=dev), torch.empty(M, dtype=torch.int32, device=dev)
+            base = lambda o, bad, reg: lib.LqrIO(nx, T, A.data_ptr(), B.data_ptr(), lx.data_ptr(), lxx.data_ptr(), lu.data_ptr(), luu.data_ptr(), None, U.data_ptr(), None,
+                                                 reg, 1.0, -1.0, 1.0, *[o[k].data_ptr() for k in ("k", "K", "Vx0", "Vxx0", "dV", "du", "dx")], bad.data_ptr())
+            state = {"tries": 1, "reg": 1e-5}
+
+            def one_reg():
+                io = lib.LqrRegIO(base(o1, bad1, state["reg"]), None, knobs["reg_min"], knobs["reg_max"], knobs["reg_up"], state["tries"], used.data_ptr(), ran.data_ptr())
+                rc = L.so100_query_lqr_reg(sim.h, C.byref(io), M, st)
+                assert rc == 0, L.so100_last_error()
+
+            def one_plain(reg=1e-5):
+                io = base(o2, bad2, reg)
+                rc = L.so100_query_lqr(sim.h, C.byref(io), M, st)
+                assert rc == 0, L.so100_last_error()
+
+            # (a) the same work
+            tr, tp = rounds(one_reg, one_plain, reps)
+            torch.cuda.synchronize()
+            equal = all(torch.equal(o1[k], o2[k]) for k in o1) and torch.equal(bad1, bad2)
+            mr, mp = statistics.median(tr), statistics.median(tp)
+            case = {"nx": nx, "M": M, "T": T, "lqr_reg_us_per_call": round(mr, 1), "lqr_us_per_call": round(mp, 1), "lqr_reg_over_lqr": round(mr/mp, 4),
+                    "lqr_reg_rounds_us": us(tr), "lqr_rounds_us": us(tp), "calls_per_round": reps, "outputs_bit_equal": bool(equal)}
+            doc["same_work"].append(case)
+            print(json.dumps(dict(case, part="a")), flush=True)
+
+            # (b) every fourth problem needs four passes
+            at = T//2
+            hard = torch.arange(1, M, 4, device=dev)
+            luu[at, hard] = -torch.eye(6, device=dev)
+            B[at, hard] *= 0.1
+            state.update(tries=4, reg=0.0)
+
+            def today():
+                one_plain(0.0)
+                if bool((bad2 >= 0).any()):                      # the look at the result every caller has to take
+                    for reg in (0.125, 0.5, 2.0):
+                        one_plain(reg)
+
+            tr, tp = rounds(one_reg, today, reps)
+            torch.cuda.synchronize()
+            hist = torch.bincount(ran, minlength=5).tolist()
+            mr, mp = statistics.median(tr), statistics.median(tp)
+            case = {"nx": nx, "M": M, "T": T, "lqr_reg_us_per_call": round(mr, 1), "four_calls_and_a_readback_us": round(mp, 1), "lqr_reg_over_today": round(mr/mp, 4),
+                    "lqr_reg_rounds_us": us(tr), "today_rounds_us": us(tp), "units_per_round": reps, "problems_by_passes_run": hist,
+                    "bad_problems": [int((bad1 >= 0).sum().item()), int((bad2 >= 0).sum().item())]}
+            doc["retry"].append(case)
+            print(json.dumps(dict(case, part="b")), flush=True)
+            del A, B, lxx, lx, lu, luu, o1, o2
+    # (c) the schedule
+    for M in sorted({m for m, _, _, _ in LQR_SIZES}):
+        g = torch.Generator(device=dev).manual_seed(1)
+        reg_used = torch.rand(M, generator=g, device=dev)*40.0 - 4.0
+        best = torch.randint(-1, 8, (M,), generator=g, device=dev, dtype=torch.int32)
+        reg, imp = torch.empty(M, device=dev), torch.empty(M, dtype=torch.uint8, device=dev)
+        io = lib.RegScheduleIO(reg_used.data_ptr(), best.data_ptr(), 0, knobs["reg_min"], knobs["reg_max"], knobs["reg_up"], 0.25, reg.data_ptr(), imp.data_ptr())
+        spans = {}
+
+        def one_query():
+            rc = L.so100_query_reg_schedule(sim.h, C.byref(io), M, st)
+            assert rc == 0, L.so100_last_error()
+
+        def one_torch():
+            r = torch.where(torch.isfinite(reg_used) & (reg_used >= 0), reg_used, torch.zeros_like(reg_used))
+            improved = (best >= 0) & (best != 0)
+            down = r*0.25
+            down = torch.where(down < knobs["reg_min"], torch.zeros_like(down), down)
+            spans["r"] = torch.where(improved, down, (r*knobs["reg_up"]).clamp(knobs["reg_min"], knobs["reg_max"])), improved
+
+        tq, tt = rounds(one_query, one_torch, 50)
+        torch.cuda.synchronize()
+        mq, mt = statistics.median(tq), statistics.median(tt)
+        case = {"M": M, "reg_schedule_us_per_call": round(mq, 1), "torch_us": round(mt, 1), "reg_schedule_over_torch": round(mq/mt, 4), "reg_schedule_rounds_us": us(tq),
+                "torch_rounds_us": us(tt), "units_per_round": 50, "equal_to_torch": bool(torch.equal(reg, spans["r"][0]) and torch.equal(imp.bool(), spans["r"][1]))}
+        doc["schedule"].append(case)
+        print(json.dumps(dict(case, part="c")), flush=True)
     sim.close()
     with open(a.out, "w") as fh:
         json.dump(doc, fh, indent=1)
@@ -967,6 +1097,7 @@ def main():
     ap.add_argument("--trajectory", action="store_true", help="time the trajectory query against the so100_step calls it predicts (profiles/trajectory_kbench.json)")
     ap.add_argument("--derivatives", action="store_true", help="time the derivatives query against its emulation through the trajectory query (profiles/derivatives_kbench.json)")
     ap.add_argument("--lqr", action="store_true", help="time the LQR query against the torch loops of examples/ilqr_reach.py (profiles/lqr_kbench.json)")
+    ap.add_argument("--lqr-reg", action="store_true", help="time so100_query_lqr_reg against so100_query_lqr, alone and with the caller's retry round it, and so100_query_reg_schedule against torch (profiles/lqr_reg_kbench.json)")
     ap.add_argument("--closed-loop", action="store_true", help="time the closed-loop trajectory query against T trajectory calls with the law in torch (profiles/closed_loop_kbench.json)")
     ap.add_argument("--cost", action="store_true", help="time the two cost queries against the torch arithmetic of examples/ilqr_reach.py (profiles/cost_kbench.json)")
     ap.add_argument("--mppi", action="store_true", help="time the two sampling-planner queries and the whole planning step against the torch arithmetic of examples/mppi_reach.py (profiles/mppi_kbench.json)")
@@ -977,8 +1108,10 @@ def main():
     if a.form is None:
         a.form = "four waves per problem at every K (ships)" if a.mppi else "global" if a.closed_loop else "mfma"
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "cem_kbench.json" if a.cem else "mppi_kbench.json" if a.mppi else "cost_kbench.json" if a.cost else "closed_loop_kbench.json" if a.closed_loop else "lqr_kbench.json" if a.lqr else "derivatives_kbench.json" if a.derivatives else "trajectory_kbench.json" if a.trajectory else "forward_kbench.json" if a.forward else "query_kbench.json")
+        a.out = os.path.join(ROOT, "profiles", "lqr_reg_kbench.json" if a.lqr_reg else "cem_kbench.json" if a.cem else "mppi_kbench.json" if a.mppi else "cost_kbench.json" if a.cost else "closed_loop_kbench.json" if a.closed_loop else "lqr_kbench.json" if a.lqr else "derivatives_kbench.json" if a.derivatives else "trajectory_kbench.json" if a.trajectory else "forward_kbench.json" if a.forward else "query_kbench.json")
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    if a.lqr_reg:
+        return lqr_reg_main(a)
     if a.cem:
         return cem_main(a)
     if a.mppi:
